@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — Msplats/s + frames/s of the tile-raster hot path on synthetic random-Gaussian scenes.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -29,6 +29,25 @@ import splat_renderer_amd as sr  # noqa: E402
 from splat_renderer_amd import _lib, dist  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (spec); ~6.3 TB/s achievable
+
+
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+
+
+def dump_image(out_dir, image):
+    """--dump-outputs: the RGBA8 image the timed frames returned, as float32 (the exact byte values 0..255) in
+    out_dir/image.npy.  An image larger than the budget is replaced by a fixed sample of its pixels (seed 0, the
+    same pixels for the same size): image_sample.npy (k, 4) and their flat indices y * width + x, image_sample_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    px = np.ascontiguousarray(image).reshape(-1, 4).astype(np.float32)
+    if px.nbytes + 4096 <= DUMP_BUDGET_BYTES:  # (4096: room for the .npy headers)
+        np.save(os.path.join(out_dir, "image.npy"), px.reshape(image.shape))
+        return ["image.npy"]
+    k = (DUMP_BUDGET_BYTES - 4096) // (4 * 4 + 8)
+    idx = np.sort(np.random.default_rng(0).choice(px.shape[0], size=k, replace=False))
+    np.save(os.path.join(out_dir, "image_sample.npy"), px[idx])
+    np.save(os.path.join(out_dir, "image_sample_index.npy"), idx.astype(np.float64))
+    return ["image_sample.npy", "image_sample_index.npy"]
 
 
 def composite_alg_bytes(p_used, width, height):
@@ -318,7 +337,12 @@ def main():
                     help="run the N > 1 code path (slice projection, the all-gather through the communicator, band frame, the exchange's "
                          "self-checks) whatever WORLD_SIZE is: with one rank the band is the whole screen and the all-gather a one-rank "
                          "collective.  A rehearsal of run_multi on one GPU (VERDICT r4 item 1), not the N = 1 headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write the image of the last timed frame to DIR/image.npy (float32 RGBA byte "
+                         "values; a seeded pixel sample for images over 64 MB): two builds can then be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -408,6 +432,7 @@ def run_single(args, name, n, width, height, tile, ntx, nty, props, normals, u, 
     launches_timed = int(cnt_.value)
     _lib.check(lib.splat_set_timing_sampling(ctx, 1), ctx)
     r.finish()  # settles the last timed frame's report: a failed order check in ANY timed frame has been counted by now
+    dumped = dump_image(args.dump_outputs, r.readPixels()) if args.dump_outputs else None  # (the last timed frame's image)
     ranking = dict(dev.rankStatus(), framesMisranked=r.framesMisranked, framesOverflowed=int(r.previousFrameOverflowed))
     # per-stage breakdown from a separate short loop with every stage's events on (not part of `value`), and the entries
     # the composite staged / consumed per frame: a property of the input, counted here so that the timed region runs the
@@ -486,6 +511,8 @@ def run_single(args, name, n, width, height, tile, ntx, nty, props, normals, u, 
                            "frac": frame_bytes / (dt / args.steps) / 1e9 / HBM_PEAK_GBS,
                            "frac_of_measured_copy": frame_bytes / (dt / args.steps) / 1e9 / copy_gbs},
     }
+    if dumped:
+        result["dumped_outputs"] = dumped
     assert ranking["orderFaults"] == 0 and ranking["framesMisranked"] == 0, f"a timed frame failed the tile-list order check and was rendered again: {ranking}"
     if not disc and not args.no_extras:
         # SURVEY 8d's composite-only figure: early-out OFF, every entry of every list consumed (68 P + 4WH), the same
@@ -729,6 +756,15 @@ def _run_multi(args, name, n, width, height, tile, ntx, nty, props, normals, u, 
     tmax = torch.tensor([dt], dtype=torch.float64, device="cuda")
     td.all_reduce(tmax, op=td.ReduceOp.MAX)
     dt = float(tmax.item())
+    dumped = None
+    if args.dump_outputs:  # the last timed frame's image: every rank's band, summed into one image on rank 0 (bands are disjoint)
+        timed_r = local if local is not None else br
+        b0, b1 = timed_r.pixel_rows()
+        whole = torch.zeros((height, width, 4), dtype=torch.int32, device="cuda")
+        whole[b0:b1] = timed_r.image[b0:b1].to(torch.int32)
+        td.all_reduce(whole, op=td.ReduceOp.SUM)
+        if rank == 0:
+            dumped = dump_image(args.dump_outputs, whole.to(torch.uint8).cpu().numpy())
     comp_ms = tstages.stage_avg_ms(_lib.STAGE_COMPOSITE)
     # (before the settling frame below adds its own entries)
     p_used = (tstages.timing_consumed()[1] if local is not None else int(stages.consumed[:, 1].sum().item())) / args.steps
@@ -794,6 +830,8 @@ def _run_multi(args, name, n, width, height, tile, ntx, nty, props, normals, u, 
                      "avg_launch_ms": infos[slow][4] / 1e6, "rank": slow},
         "cpu_baseline": None,  # reported at N=1 only
     }
+    if dumped:
+        result["dumped_outputs"] = dumped
     if args.band_path:
         result["config"]["band_path"] = ("--band-path: run_multi's code path (slice projection, all-gather through the communicator, band "
                                          "frame, self-checks) with WORLD_SIZE " + str(world) + "; not the N = 1 headline (run_single)")
