@@ -298,7 +298,7 @@ int splat_validate_tile_order(splat_ctx *ctx, const void *projected, const void 
 typedef struct splat_composite_cfg {
     uint32_t mode;       /* SPLAT_COMPOSITE_* */
     uint32_t early_out;  /* 1 = stop a pixel at alpha >= 0.99 (reference :187-190) */
-    uint32_t tile_size;  /* must equal the binner's; only 16 is implemented */
+    uint32_t tile_size;  /* must equal the binner's: 1 ... 4096 (16: k_composite_px / k_composite; any other: k_composite_tile) */
     uint32_t tile_row0;  /* render tile rows [tile_row0, tile_row1) (multi-GPU band) */
     uint32_t tile_row1;  /* UINT32_MAX = to the last row */
     uint32_t record_format; /* what `projected` / `records` point at: SPLAT_RECORDS_PROJECTED (32-byte

@@ -63,6 +63,10 @@ struct splat_ctx {
     size_t scan_ws_bytes = 0;
     unsigned long long *d_consumed = nullptr; // per tile: list entries staged by the composite while timing is on
     uint32_t consumed_tiles = 0;              // entries allocated in d_consumed
+    // k_composite_tile (tiles of more than one 16x16 window) with counters: per window {entries staged, entries consumed},
+    // reduced per tile into the counters by k_window_counts after the launch
+    uint2 *d_window_counts = nullptr;
+    uint32_t window_counts_cap = 0; // windows allocated
     // pinned host staging for uploads / tiny readbacks
     void *pinned = nullptr;
     size_t pinned_bytes = 0;

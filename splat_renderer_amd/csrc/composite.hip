@@ -22,83 +22,11 @@
 // achieved fraction is reported honestly against that model.
 //
 // Compiled with -ffp-contract=fast; compared with the oracle within a stated tolerance.
-#include "common.h"
-#include "disc.h"
-#include "shade.h"
+#include "composite.h"
 
 #include <hip/hip_ext.h>
 
 #include <cstdlib>
-
-typedef float v2f __attribute__((ext_vector_type(2))); // maps onto the packed FP32 instructions (v_pk_*_f32)
-
-constexpr int CT = 16;        // tile edge (pixels)
-constexpr int CBATCH = 256;   // list entries staged per round
-
-struct CompositeParams {
-    const float4 *color;  uint32_t color_stride;   // vec4(rgb, opacity)
-    const float4 *normals; uint32_t normal_stride; // vec4(normal, scaleFactor)
-    const float4 *projected;                       // 2 x float4 per splat (ProjectedSplat), or 1 x float4 (compact exchange record)
-    uint32_t compact;
-    uint32_t lit32;                                // projected holds lit composite records (shade.h): colour and normals are not read
-    uint32_t disc;                                 // projected holds disc records (disc.h): the oriented-disc footprint
-    uint32_t disc_stride;                          // float4s between disc records: 2 (projector's) or 3 (48-byte exchange records, lit disc records)
-    uint32_t disc_lit;                             // the third float4 of a disc record is the splat's lit colour: colour and normals are not read
-    uint32_t prelit;                               // color holds lit colours (k_lit_colors): normals are not read
-    const uint32_t *indices, *counts, *offsets;
-    uint32_t width, height, ntx, tile_row0;
-    uint32_t *out_rgba8;
-    float4 *out_rgba32f;
-    unsigned long long *consumed; // per tile {entries staged, entries consumed}, accumulated (or NULL)
-    // the frame's report (tile-first frames; NULL otherwise): this launch is the frame's last kernel, so its first
-    // workgroup tells the host {pair total, flags incl. the per-tile sort's order check, sequence number}
-    const uint32_t *frame_total;
-    uint32_t *report;
-    uint32_t report_seq;
-    const uint32_t *tile_order; // k_composite_px: workgroup b works on tile tile_order[b] of the band (NULL: b)
-    uint32_t *tile_cost;        // k_composite_px: chunks each tile's consumer walked (NULL: not kept)
-    const uint32_t *order_src;  // k_composite_px, workgroup 0: the costs the PREVIOUS launch over this band left (NULL: none) ...
-    uint32_t *order_dst;        // ... sorted into the order the NEXT launch takes its tiles in
-    const uint32_t *cost_prev;  // k_composite_px: the same costs, read by every tile: how many chunks to build and gather ahead of need (NULL: all)
-#ifdef PX_PROFILE
-    uint32_t debug_cap;         // (measuring build only, SPLAT_PX_CAP: every list cut after this many entries — a WRONG image: what do the long tiles cost?)
-#endif
-};
-
-__device__ __forceinline__ uint32_t unorm8(float v) {
-    v = fminf(fmaxf(v, 0.0f), 1.0f); // fmaxf(NaN,0) = 0
-    return (uint32_t)(v * 255.0f + 0.5f);
-}
-
-// 64-bit lane mask of one 8x8 quadrant from its 8-bit column mask xb and row mask yb: lane
-// ly*8+lx is set iff bit lx of xb and bit ly of yb are.  (y & 15) * 0x00204081 drops bit i of y at
-// bit 8i (the four shifted copies do not overlap), & 0x01010101 keeps those, * xb copies xb into
-// every selected byte.
-__device__ __forceinline__ uint2 quadrant_mask(uint32_t xb, uint32_t yb) {
-    const uint32_t lo = (((yb & 15u) * 0x00204081u) & 0x01010101u) * xb;
-    const uint32_t hi = (((yb >> 4) * 0x00204081u) & 0x01010101u) * xb;
-    return make_uint2(lo, hi);
-}
-
-// Pixel columns j in [0,16) of a tile whose centres c0 + j lie inside [lo, hi]
-// (ComputeShaderRenderer.ts:118-121 keeps a pixel iff !(p < min || p > max)).  c0 = tile origin +
-// 0.5 >= 0.5.  For a result in [0,16) the subtraction is exact (lo >= c0 > 0 and the difference is a
-// multiple of ulp(lo) no larger than lo), outside that range only its sign / being >= 16 matters
-// and rounding is monotone (x - y == 0 only when x == y), so the mask is exactly the set the
-// reference's comparisons select.
-__device__ __forceinline__ uint32_t span_mask16(float lo, float hi, float c0) {
-    const float a = fmaxf(ceilf(lo - c0), 0.0f), b = fminf(floorf(hi - c0), 15.0f);
-    if (!(a <= b)) return 0u; // also NaN
-    const uint32_t ia = (uint32_t)a, ib = (uint32_t)b;
-    return ((2u << ib) - 1u) & ~((1u << ia) - 1u);
-}
-
-// Pins a wave-uniform 64-bit value into scalar registers (the compiler's divergence analysis gives
-// up on loop-carried masks and would otherwise keep them, and every test on them, in VGPRs).
-__device__ __forceinline__ unsigned long long uniform64(unsigned long long v) {
-    return ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) |
-           (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-}
 
 // The lit colours of all splats as a plane: when the composite is given this plane (cfg->prelit) it
 // gathers two lines per staged entry (record, lit colour) instead of three (record, colour, normal) —
@@ -108,58 +36,6 @@ __global__ __launch_bounds__(256) void k_lit_colors(const float4 *__restrict__ c
                                                     float4 *__restrict__ lit) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i < n) lit[i] = lit_color(color[(size_t)i * color_stride], normals[(size_t)i * normal_stride]);
-}
-
-// bounds and screen radius of splat idx.  Compact exchange records (multi-GPU frame) carry {centre x,
-// y, radius, depth}: the bounds are rebuilt exactly as the projector forms them (SplatProjector.ts:
-// 119-121) — with contraction switched off for this function (the file is compiled with it on).
-__device__ __forceinline__ void fetch_record(const CompositeParams &p, uint32_t idx, float4 &bounds, float &radius) {
-    if (p.compact) {
-        const float4 c = p.projected[idx];
-        bounds = lit_bounds(c); // the bounds must be the projector's: one rounding per operation
-        radius = c.z;
-    } else {
-        bounds = p.projected[(size_t)idx * 2];
-        radius = reinterpret_cast<const float *>(p.projected)[(size_t)idx * 8 + 5];
-    }
-}
-
-// The stop test of the nearest-first loop is (1 - T) >= 0.99 on the transmittance T (the reference's alpha >= 0.99,
-// ComputeShaderRenderer.ts:187-190).  A correctly rounded 1 - T is monotone in T, so the test is EXACTLY T <= the
-// largest binary32 T that passes it — 0x1.47ae4p-7 (found by stepping ulps; NaN fails both forms) — and the
-// subtraction leaves the per-pixel loop.
-constexpr float T_STOP = 0x1.47ae4p-7f;
-static_assert((1.0f - T_STOP) >= 0.99f && !((1.0f - 0x1.47ae42p-7f) >= 0.99f), "T_STOP is the last transmittance that stops a pixel");
-
-// exp(-0.5 * d2 / (0.4 * 0.4)) = exp2(d2 * this)   (SequentialRenderer.ts:132-133)
-constexpr float DISC_EXP2_SCALE = -4.508422002777011f;
-
-// DISC: the footprint is SequentialRenderer's oriented disc (disc.h) — per entry the 32-byte disc record and
-// the lit colour are staged, a pixel is inside when u^2 + v^2 <= 1 with (u,v) = B*d / (1 - q.d); the
-// coverage masks come from the disc's exact bounds, as the binner's tile ranges do.
-// LIT32: `projected` holds the frame's lit composite records (shade.h) — ONE 32-byte gather per staged entry gives
-// centre, radius and lit colour; colour and normal arrays are not touched.
-template <int MODE, bool EARLY_OUT, bool DISC, bool LIT32>
-__device__ __forceinline__ void fetch_entry(const CompositeParams &p, uint32_t idx, float4 &f_b, float4 &f_b2, float4 &f_c, float4 &f_n,
-                                            float &f_r) {
-    if constexpr (DISC) {
-        f_b = p.projected[(size_t)idx * p.disc_stride];
-        f_b2 = p.projected[(size_t)idx * p.disc_stride + 1];
-        if (p.disc_lit) {
-            f_c = p.projected[(size_t)idx * p.disc_stride + 2];
-            return;
-        }
-    } else if constexpr (LIT32) {
-        const float4 c = p.projected[(size_t)idx * 2];
-        f_c = p.projected[(size_t)idx * 2 + 1];
-        f_b = lit_bounds(c);
-        f_r = c.z;
-        return;
-    } else {
-        fetch_record(p, idx, f_b, f_r);
-    }
-    f_c = p.color[(size_t)idx * p.color_stride];
-    if (!p.prelit) f_n = p.normals[(size_t)idx * p.normal_stride];
 }
 
 template <int MODE, bool EARLY_OUT, bool DISC, bool LIT32>
@@ -1234,10 +1110,16 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
                                     uint32_t report_seq, bool *launched) {
     if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
     ARG_CHECK(ctx, cfg != nullptr);
-    ARG_CHECK(ctx, cfg->tile_size == CT); // the kernel's quadrant mapping is built for 16x16 tiles
+    // 16x16 tiles: k_composite_px / k_composite, whose quadrant mapping is built for them; any other size the binner
+    // accepts: k_composite_tile (composite_tile.hip)
+    const uint32_t T = cfg->tile_size;
+    ARG_CHECK(ctx, T >= 1 && T <= 4096);
     ARG_CHECK(ctx, cfg->mode == SPLAT_COMPOSITE_FRONT_TO_BACK || cfg->mode == SPLAT_COMPOSITE_REFERENCE_LITERAL);
     ARG_CHECK(ctx, cfg->record_format <= SPLAT_RECORDS_LIT32);
-    ARG_CHECK(ctx, width >= 1 && height >= 1 && width <= 65535u * CT && height <= 65535u * CT);
+    ARG_CHECK(ctx, width >= 1 && height >= 1);
+    // (k_composite_tile's grid: ceil(T / 16)^2 windows of 16x16 pixels per tile, up to 65535 in x and in y)
+    ARG_CHECK(ctx, T == CT ? (width <= 65535u * CT && height <= 65535u * CT)
+                           : (div_up64(width, T) * div_up(T, CT) <= 65535u && div_up64(height, T) * div_up(T, CT) <= 65535u));
     // the records carry the lit colour (isotropic: 32-byte lit composite records; disc: the colour behind each disc record): no colour / normal arrays
     const bool lit32 = cfg->record_format == SPLAT_RECORDS_LIT32;
     ARG_CHECK(ctx, lit32 || (color_opacity && (normals || cfg->prelit)));
@@ -1251,7 +1133,7 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
     ARG_CHECK(ctx, cfg->footprint != SPLAT_FOOTPRINT_DISC ||
                        (cfg->mode == SPLAT_COMPOSITE_FRONT_TO_BACK && cfg->record_format != SPLAT_RECORDS_COMPACT));
     ARG_CHECK(ctx, cfg->record_format != SPLAT_RECORDS_DISC48 || cfg->footprint == SPLAT_FOOTPRINT_DISC);
-    const uint32_t ntx = div_up(width, CT), nty = div_up(height, CT);
+    const uint32_t ntx = div_up(width, T), nty = div_up(height, T);
     uint32_t r0 = cfg->tile_row0, r1 = cfg->tile_row1 > nty ? nty : cfg->tile_row1;
     if (r0 >= r1) return SPLAT_OK;
     CompositeParams p;
@@ -1287,6 +1169,7 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
 #ifdef PX_PROFILE
     p.debug_cap = getenv("SPLAT_PX_CAP") ? (uint32_t)strtoul(getenv("SPLAT_PX_CAP"), nullptr, 10) : 0xffffffffu;
 #endif
+    if (T != CT) return composite_tile_launch(ctx, cfg, p, nty, r0, r1, launched);
     dim3 grid(ntx, r1 - r0), block(256);
     const bool eo = cfg->early_out != 0;
     // timed runs attach the event pair to the launch itself (no marker packets around the kernel).  The pair is taken right

@@ -140,6 +140,7 @@ void splat_ctx_destroy(splat_ctx *ctx) {
         for (auto e : t.end) (void)hipEventDestroy(e);
     }
     if (ctx->d_consumed) (void)hipFree(ctx->d_consumed);
+    if (ctx->d_window_counts) (void)hipFree(ctx->d_window_counts);
     for (auto &h : ctx->px_hist)
         if (h.mem) (void)hipFree(h.mem);
     if (ctx->scan_ws) (void)hipFree(ctx->scan_ws);
