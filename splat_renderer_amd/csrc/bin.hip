@@ -449,13 +449,13 @@ int binner_run(splat_binner *b, const void *projected, uint32_t n_splats, const 
         hipLaunchKernelGGL(k_bin_expand, dim3(blocks), dim3(BIN_THREADS), 0, ctx->stream, (const uint32_t *)sorted, n_sorted,
                            b->ranges, b->blocksums, ntx, b->pair_limit, b->d_total + 1, b->pairs.keys, b->pairs.payload);
         LAUNCH_CHECK(ctx, "k_bin_expand");
-        uint32_t bits = 1;
-        while ((1u << bits) < tiles) ++bits;
+        const uint32_t bits = tile_id_bits(tiles);
         const uint32_t *p_dev = async ? b->d_total : nullptr;
         // tile ids up to 16 bits: two passes with the bits split evenly (13 bits -> 6 + 7) rather than
         // 8 + 5: a pass scatters in digit runs, and 64 + 128 bins give longer runs than 256 + 32
         // measured at C2 (13 bits): 5+8 0.627, 6+7 0.619, 7+6 0.629, 8+5 0.649 ms/frame
-        const uint32_t lo_bits = bits <= 8 ? bits : bits / 2;
+        // (wider ids: a first digit of 8 bits, then 8-bit passes: tile_id_low_bits)
+        const uint32_t lo_bits = tile_id_low_bits(tiles);
         rc = radix_sort_pairs(ctx, b->pairs.keys, b->pairs.payload, b->pairs.keys_b, b->pairs.payload_b, b->pairs.hist, total32, 0,
                               bits, &b->pairs.result_in_primary, 0, p_dev, false, lo_bits);
         if (rc != SPLAT_OK) return rc;

@@ -251,7 +251,9 @@ struct TfHistOut {
 __device__ __forceinline__ uint32_t xcd_block_of(uint32_t i, uint32_t xcd_per) {
     return xcd_per ? (i & 7u) * xcd_per + (i >> 3) : i;
 }
-// tile-id bits and their split over the two sort passes (13 bits -> 6 + 7: longer digit runs than 8 + 5)
+// tile-id bits and their split over the two sort passes (13 bits -> 6 + 7: longer digit runs than 8 + 5).  The first digit
+// is at most 8 bits wide, the widest radix_sort_pairs takes: ids of 18 to 24 bits (sort-first screens of more than 2^17
+// tiles) get 8 + 8 and then further 8-bit passes.  Up to 17 bits, and so on every tile-first screen, this is bits / 2.
 static inline uint32_t tile_id_bits(uint32_t tiles) {
     uint32_t bits = 1;
     while ((1u << bits) < tiles) ++bits;
@@ -259,7 +261,7 @@ static inline uint32_t tile_id_bits(uint32_t tiles) {
 }
 static inline uint32_t tile_id_low_bits(uint32_t tiles) {
     const uint32_t bits = tile_id_bits(tiles);
-    return bits <= 8 ? bits : bits / 2;
+    return bits <= 8 ? bits : bits / 2 < 8 ? bits / 2 : 8;
 }
 
 // report: host-mapped pinned words that receive {pair total, overflow flag, frame sequence number} —

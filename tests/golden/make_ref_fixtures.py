@@ -8,7 +8,9 @@ build container (the reference is not present anywhere else), reads those statem
 /root/reference as text, strips TypeScript-only syntax IN MEMORY (there is none in these ranges beyond
 non-null assertions, but the stripper is applied anyway), and executes them under the container's
 Node 12 — the program goes to `node -` on stdin, nothing of it is written to disk — on the inputs of
-the committed fixtures plus an edge-case set (off-screen, straddling, NaN, padding indices).  Only the
+the committed fixtures plus an edge-case set (off-screen, straddling, NaN, padding indices), all at tile size 16,
+and cases at other tile sizes: bounds on and one f32 ulp either side of tile edges at T = 1, 10, 24 and 4096, and
+records-only scenes of more than 2^17 and 2^18 tiles (tile ids wider than 17 bits).  Only the
 resulting arrays are stored.  tests/ then hold BOTH the oracle and the HIP path to these arrays, so the
 integer half of the parity contract (tile counts, offsets, lists; the scan) is pinned to an execution
 of the reference itself.  Still unpinned: every float stage (projector, composite) and gl-matrix.
@@ -26,7 +28,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 REF = "/root/reference/src"
-TILE = 16
+TILE = 16  # the scene fixtures' and `edges`' tile size
 
 
 def strip_types(js):
@@ -96,6 +98,51 @@ def edge_case():
     return rec, order, w, h
 
 
+def tile_edge_case(tile, w, h, n=240, seed=5):
+    """Bounds on multiples of `tile` and one f32 ulp either side of them (and of the screen's width and height), in
+    every coordinate, so that floor(x / tile) lands on both sides of every tile edge.  A non-power-of-two tile takes
+    the f64 branch of the binner's tile range, a power of two the f32 one: both must equal the JS-number division."""
+    rng = np.random.default_rng(seed)
+
+    def edge_values(limit):
+        v = np.arange(0, limit + tile, tile, dtype=np.float32)
+        v = np.concatenate([v, np.float32([limit, -1.0, limit + 1.0])])
+        return np.concatenate([np.nextafter(v, np.float32(-np.inf)), v, np.nextafter(v, np.float32(np.inf))]).astype(np.float32)
+
+    xs, ys = edge_values(w), edge_values(h)
+    rec = np.zeros((n, 8), np.float32)
+    a, b = rng.choice(xs, (2, n)), rng.choice(ys, (2, n))
+    rec[:, 0], rec[:, 2] = np.minimum(a[0], a[1]), np.maximum(a[0], a[1])
+    rec[:, 1], rec[:, 3] = np.minimum(b[0], b[1]), np.maximum(b[0], b[1])
+    rec[::17, 2] = rec[::17, 0]  # some empty in x, some reversed in y
+    rec[5::19, 1], rec[5::19, 3] = rec[5::19, 3], rec[5::19, 1]
+    rec[:, 4:] = rng.random((n, 4), np.float32)
+    order = rng.permutation(n).astype(np.uint32)
+    order = np.insert(order, [3, n // 2], 0xFFFFFFFF)
+    return rec, order
+
+
+def records_only_case(n, w, h, size, seed):
+    """A records-only scene: n random boxes of up to `size` pixels a side over a w x h screen (some hanging off it) in a
+    random sorted order."""
+    rng = np.random.default_rng(seed)
+    rec = np.zeros((n, 8), np.float32)
+    x0 = rng.uniform(-size, w, n).astype(np.float32)
+    y0 = rng.uniform(-size, h, n).astype(np.float32)
+    rec[:, 0], rec[:, 1] = x0, y0
+    rec[:, 2] = x0 + rng.uniform(0, size, n).astype(np.float32)
+    rec[:, 3] = y0 + rng.uniform(0, size, n).astype(np.float32)
+    rec[:, 4:] = rng.random((n, 4), np.float32)
+    return rec, rng.permutation(n).astype(np.uint32)
+
+
+# (name, tile, width, height) of the edge cases at other tile sizes; the screens are not multiples of the tile, and at 4096
+# the one tile is larger than the screen
+TILE_EDGE_CASES = [("edges_t1", 1, 13, 9), ("edges_t10", 10, 73, 47), ("edges_t24", 24, 101, 77), ("edges_t4096", 4096, 70, 52)]
+# (name, tile, width, height, boxes, box size, seed): 140 000 tiles (18-bit ids) and 265 200 tiles (19-bit ids)
+RECORDS_ONLY_CASES = [("boxes_t2_800x700", 2, 800, 700, 3000, 24.0, 7), ("boxes_t1_520x510", 1, 520, 510, 400, 12.0, 8)]
+
+
 def main():
     loops, scan = reference_statements()
     program = PROGRAM % {"LOOPS": loops, "SCAN": scan}
@@ -103,11 +150,15 @@ def main():
     for name in ("tiny7", "small300", "ragged1000"):
         g = np.load(os.path.join(HERE, name + ".npz"))
         n, w, h, _ = (int(x) for x in g["dims"])
-        inputs[name] = (g["projected"], g["order"][:n].copy(), w, h)
+        inputs[name] = (g["projected"], g["order"][:n].copy(), w, h, TILE)
     rec, order, w, h = edge_case()
-    inputs["edges"] = (rec, order, w, h)
-    for name, (proj, order, w, h) in inputs.items():
-        bins[name] = {"width": w, "height": h, "tile": TILE, "sorted": [int(x) for x in order],
+    inputs["edges"] = (rec, order, w, h, TILE)
+    for name, tile, w, h in TILE_EDGE_CASES:
+        inputs[name] = tile_edge_case(tile, w, h) + (w, h, tile)
+    for name, tile, w, h, n, size, seed in RECORDS_ONLY_CASES:
+        inputs[name] = records_only_case(n, w, h, size, seed) + (w, h, tile)
+    for name, (proj, order, w, h, tile) in inputs.items():
+        bins[name] = {"width": w, "height": h, "tile": tile, "sorted": [int(x) for x in order],
                       "projected_bits": [int(x) for x in np.ascontiguousarray(proj, np.float32).view(np.uint32).reshape(-1)]}
     rng = np.random.default_rng(11)
     scans = [[1, 2, 3, 4, 5], [0] * 9, [7], [int(x) for x in rng.integers(0, 5000, 8160)], [int(x) for x in rng.integers(0, 3, 1024)]]
@@ -116,11 +167,11 @@ def main():
     if r.returncode != 0:
         sys.exit("node failed:\n" + r.stderr)
     out = json.loads(r.stdout)
-    for name, (proj, order, w, h) in inputs.items():
+    for name, (proj, order, w, h, tile) in inputs.items():
         o = out[name]
         assert o["total"] == len(o["indices"])
         np.savez_compressed(os.path.join(HERE, f"ref_binsorted_{name}.npz"), projected=np.ascontiguousarray(proj, np.float32),
-                            sorted=order, dims=np.array([w, h, TILE], np.int64), counts=np.array(o["counts"], np.uint32),
+                            sorted=order, dims=np.array([w, h, tile], np.int64), counts=np.array(o["counts"], np.uint32),
                             offsets=np.array(o["offsets"], np.uint32), indices=np.array(o["indices"], np.uint32))
         print(f"ref_binsorted_{name}.npz: {len(o['counts'])} tiles, {o['total']} pairs")
     np.savez_compressed(os.path.join(HERE, "ref_scan.npz"), **{f"in{i}": np.array(a, np.uint32) for i, a in enumerate(scans)},

@@ -174,21 +174,24 @@ def test_update_props_matches_twin():
     assert np.array_equal(bits(O.update_props(pos, cur)), bits(NP.update_props(pos, cur)))
 
 
-REF_BINS = ("tiny7", "small300", "ragged1000", "edges")
+REF_SCENE_BINS = ("tiny7", "small300", "ragged1000")  # the reference's lists of the scene fixtures of those names
+# edges at T = 16, edges at T = 1, 10, 24 and 4096, and records-only screens of 140 000 tiles at T = 2 and 265 200 at T = 1
+REF_BINS = REF_SCENE_BINS + ("edges", "edges_t1", "edges_t10", "edges_t24", "edges_t4096", "boxes_t2_800x700", "boxes_t1_520x510")
 
 
 @pytest.mark.parametrize("name", REF_BINS)
 def test_oracle_tile_lists_equal_the_reference_own_code(name):
     """ref_binsorted_*.npz hold what the REFERENCE's binSorted loops (src/TileBinner.ts:426-495, executed under Node
     by tests/golden/make_ref_fixtures.py) produce for these records and sorted orders — including off-screen,
-    straddling, degenerate, NaN and infinite bounds and padding indices: both restatements must give exactly that."""
+    straddling, degenerate, NaN and infinite bounds and padding indices, bounds one ulp either side of tile edges at
+    tile sizes other than 16, and screens of more than 2^17 tiles: both restatements must give exactly that."""
     g = np.load(os.path.join(GOLDEN, f"ref_binsorted_{name}.npz"))
     w, h, tile = (int(x) for x in g["dims"])
     for impl in (O, NP):
         counts, offsets, idx = impl.bin_sorted(g["projected"], g["sorted"], w, h, tile)
         assert np.array_equal(counts, g["counts"]) and np.array_equal(offsets, g["offsets"]), impl.__name__
         assert np.array_equal(idx, g["indices"]), impl.__name__
-    if name != "edges":  # the same inputs as the oracle-made fixture of that name: one more link between the two sets
+    if name in REF_SCENE_BINS:  # the same inputs as the oracle-made fixture of that name: one more link between the two sets
         f = np.load(os.path.join(GOLDEN, name + ".npz"))
         assert np.array_equal(f["indices"], g["indices"]) and np.array_equal(bits(f["projected"]), bits(g["projected"]))
 
