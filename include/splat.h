@@ -262,7 +262,8 @@ int splat_bin_total(splat_binner *b, uint64_t *total_pairs); /* sum of counts of
 /* Order of work inside splat_render_frame (results are identical, tests hold both to the same lists):
  *   SPLAT_FRAME_SORT_FIRST  global depth sort of the splats, then bin in sorted order (the staged API's order);
  *   SPLAT_FRAME_TILE_FIRST  bin in index order, then depth-sort every tile's list (PerTileSorter,
- *                           src/PerTileSorter.ts:66-122) — needs tile coordinates that fit 8 bits;
+ *                           src/PerTileSorter.ts:66-122) — needs tile coordinates that fit 8 bits (screens of at
+ *                           most 256 x 256 tiles; beyond them every frame bins sort-first);
  *   SPLAT_FRAME_ORDER_DEFAULT  the library's choice (environment SPLAT_FRAME_ORDER=sortfirst|tilefirst overrides). */
 #define SPLAT_FRAME_ORDER_DEFAULT (-1)
 #define SPLAT_FRAME_SORT_FIRST 0
@@ -292,7 +293,8 @@ int splat_validate_tile_order(splat_ctx *ctx, const void *projected, const void 
                                 * 32-byte line: the ProjectedSplat's bounds are centre -/+ radius * 1.5 in the projector's operation
                                 * order (src/SplatProjector.ts:119-121), the colour already carries the shading of :143-145.
                                 * splat_render_frame* writes them in place of the ProjectedSplat records when asked to (isotropic
-                                * footprint); the composite then gathers one line per staged list entry instead of three. */
+                                * footprint), on every screen the binner takes; the composite then gathers one line per
+                                * staged list entry instead of three. */
 #define SPLAT_FOOTPRINT_ISOTROPIC 0
 #define SPLAT_FOOTPRINT_DISC 1
 typedef struct splat_composite_cfg {
@@ -335,7 +337,11 @@ int splat_composite(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *
 /* ---- whole frame: project -> keys -> sort -> bin -> composite ----------------
  * With cfg->tile_row0/1 set to a strict band of tile rows (multi-GPU, no exchange: every rank renders its band from
  * its own copy of the splats) only that band's pixels, lists and counts are produced, and `projected` holds records
- * only for splats that may reach the band (the projector skips the others after a conservative test). */
+ * only for splats that may reach the band (the projector skips the others after a conservative test).
+ * Every screen the binner takes (at most 65535 tiles a side, 2^24 in all) accepts every record format and, for disc
+ * frames, projected == NULL: the projector leaves each splat's clamped tile range per index — 4 bytes with 8-bit
+ * coordinates up to 256 x 256 tiles, 8 bytes with 16-bit coordinates beyond (sort-first order there) — and the
+ * binner bins from that range, never from the records. */
 int splat_render_frame(splat_ctx *ctx, splat_sorter *sorter, splat_binner *binner,
                        const splat_composite_cfg *cfg, const float *uniforms, const void *props,
                        const void *normals, uint32_t n, uint32_t width, uint32_t height,
@@ -381,7 +387,9 @@ int splat_project_slice_compact(splat_ctx *ctx, const float *uniforms, const voi
 /* The oriented-disc footprint's exchange records: 48 bytes per splat, 3 x float4 {disc record (8 floats, see
  * splat_project_disc), depth, 0, 0, 0}.  The disc's bounds are a pure function of the record and the index is the
  * position in the gathered array, so splat_band_frame (cfg->footprint = SPLAT_FOOTPRINT_DISC, cfg->record_format =
- * SPLAT_RECORDS_DISC48; tile-first order, screens up to 256 x 256 tiles) needs nothing else. */
+ * SPLAT_RECORDS_DISC48) needs nothing else.  DISC48 band frames take the tile-first order wherever it exists (screens of
+ * at most 256 x 256 tiles: with the sort-first order set there they return SPLAT_ERR_INVALID) and bin sort-first only
+ * beyond 256 x 256 tiles, where no tile-first order exists. */
 int splat_project_slice_disc(splat_ctx *ctx, const float *uniforms, const void *pos_radius, uint32_t pr_stride_vec4,
                              const void *normals, uint32_t normal_stride_vec4, uint32_t first, uint32_t count,
                              void *records48_slice);
@@ -398,7 +406,8 @@ int splat_band_keys(splat_ctx *ctx, splat_sorter *sorter, const void *projected,
  * cfg->tile_row1) binned, depth-sorted and composited from the gathered records.  Tile-first order
  * (default): one pass over the records gives depth keys and tile ranges clamped to the band — a splat
  * outside it has an empty range — then the frame's binner and per-tile sort; sort-first order: band
- * filter (kept count on the device) -> depth sort -> bin.  records: n_records records in
+ * filter (kept count on the device) -> depth sort -> bin, the only order beyond 256 x 256 tiles (there the
+ * filter leaves each kept splat's 8-byte tile range for the binner).  records: n_records records in
  * cfg->record_format whose position is the global splat index (the all-gathered shards);
  * props/normals: the full scene in the reference's layouts (props = interleaved records); with
  * cfg->prelit, props is the plane of lit colours (splat_lit_colors) and normals may be NULL.

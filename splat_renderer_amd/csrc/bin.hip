@@ -87,6 +87,33 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin_count(const float4 *__restr
     if (threadIdx.x == 0) blocksums[blockIdx.x] = total;
 }
 
+// The same count from the 8-byte range the frame's projector (or a band's prepare pass) wrote per splat index on a screen
+// beyond 256 x 256 tiles: it already is the per-position layout, so the gather is one 8-byte load.
+__global__ __launch_bounds__(BIN_THREADS) void k_bin_count_wide(const uint2 *__restrict__ range_wide, uint32_t n_splats,
+                                                                const uint32_t *__restrict__ sorted, uint32_t n_sorted_host,
+                                                                const uint32_t *__restrict__ n_sorted_dev, uint2 *__restrict__ ranges,
+                                                                uint32_t *__restrict__ blocksums, uint32_t *__restrict__ overflow_flag) {
+    __shared__ uint32_t wsum[4];
+    uint32_t local = 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *overflow_flag = 0;
+    uint32_t n_sorted = n_sorted_host;
+    if (n_sorted_dev) n_sorted = min(*n_sorted_dev, n_sorted_host);
+#pragma unroll
+    for (uint32_t k = 0; k < BIN_PER_THREAD; ++k) {
+        const uint32_t i = blockIdx.x * BIN_BLOCK + k * BIN_THREADS + threadIdx.x;
+        if (i < n_sorted) {
+            const uint32_t s = sorted[i];
+            const uint2 r = s < n_splats ? range_wide[s] : make_uint2(1u, 1u); // (0xFFFFFFFF padding bins nowhere)
+            ranges[i] = r;
+            local += range_hits(r);
+        } else if (i < n_sorted_host) {
+            ranges[i] = make_uint2(1u, 1u);
+        }
+    }
+    const uint32_t total = block_sum(local, wsum);
+    if (threadIdx.x == 0) blocksums[blockIdx.x] = total;
+}
+
 // expand: the (tile id, splat idx) pairs of a block land in [block_base, block_base + block_total) in
 // sorted order: position-major (k * 256 + thread), then row-major over the splat's tile rectangle.
 // Small blocks are staged in LDS so that the global stores are contiguous runs.
@@ -259,6 +286,12 @@ int binner_reserve_range32(splat_binner *b, uint32_t n_splats) {
     return SPLAT_OK;
 }
 
+// (one buffer for both: a binner renders one screen at a time)
+int binner_reserve_range_wide(splat_binner *b, uint32_t n_splats) {
+    if (n_splats > 0x7ffffff0u) return ctx_fail(b->ctx, SPLAT_ERR_CAPACITY, "binner: too many splats for the wide tile range");
+    return binner_reserve_range32(b, 2u * n_splats);
+}
+
 static void binner_free_wide(splat_binner *b) {
     if (b->wide_a) (void)hipFree(b->wide_a);
     if (b->wide_b) (void)hipFree(b->wide_b);
@@ -320,7 +353,7 @@ int binner_reserve(splat_binner *b, uint32_t tiles, uint32_t n_sorted) {
 // order of work (tile_first.hip): `sorted` is then unused, the lists are depth-sorted per tile.
 int binner_run(splat_binner *b, const void *projected, uint32_t n_splats, const void *sorted, uint32_t n_sorted, uint32_t width,
                uint32_t height, uint32_t tile_row0, uint32_t tile_row1, const uint32_t *range32, const uint32_t *n_sorted_dev,
-               const uint32_t *depth_keys) {
+               const uint32_t *depth_keys, const uint2 *range_wide) {
     splat_ctx *ctx = b->ctx;
     const bool tile_first = depth_keys != nullptr;
     // what the caller prepared for THIS run (its projector's histogram; a band's compacted splats) is taken and cleared before
@@ -333,6 +366,7 @@ int binner_run(splat_binner *b, const void *projected, uint32_t n_splats, const 
     ARG_CHECK(ctx, width >= 1 && height >= 1);
     ARG_CHECK(ctx, n_sorted == 0 || (projected && (sorted || tile_first)));
     ARG_CHECK(ctx, !tile_first || (range32 && n_sorted == n_splats && !n_sorted_dev));
+    ARG_CHECK(ctx, !range_wide || (!range32 && !tile_first));
     const uint32_t ntx = div_up(width, b->tile), nty = div_up(height, b->tile); // GPUTileBinner.ts:198-200
     ARG_CHECK(ctx, ntx <= 65535 && nty <= 65535 && (uint64_t)ntx * nty <= (1u << 24));
     const uint32_t tiles = ntx * nty;
@@ -364,7 +398,10 @@ int binner_run(splat_binner *b, const void *projected, uint32_t n_splats, const 
             // (tf_hist: per 1024-splat block its pairs per low tile-id digit, the first sort pass's histogram)
             rc = radix_rowscan_launch(ctx, b->tf_hist, div_up(n_splats, b->tf_block), 1u << tf_lo_bits);
             if (rc != SPLAT_OK) return rc;
-        } else if (range32)
+        } else if (range_wide)
+            hipLaunchKernelGGL(k_bin_count_wide, dim3(blocks), dim3(BIN_THREADS), 0, ctx->stream, range_wide, n_splats,
+                               (const uint32_t *)sorted, n_sorted, n_sorted_dev, b->ranges, b->blocksums, b->d_total + 1);
+        else if (range32)
             hipLaunchKernelGGL(k_bin_count<true>, dim3(blocks), dim3(BIN_THREADS), 0, ctx->stream, (const float4 *)projected, range32,
                                n_splats, (const uint32_t *)sorted, n_sorted, n_sorted_dev, bp, b->ranges, b->blocksums, b->d_total + 1);
         else

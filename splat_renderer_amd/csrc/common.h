@@ -279,7 +279,8 @@ __device__ __forceinline__ void tile_report(const uint32_t *d_total, uint32_t *r
 int binner_reserve_range32(splat_binner *b, uint32_t n_splats);
 int binner_run(splat_binner *b, const void *projected, uint32_t n_splats, const void *sorted, uint32_t n_sorted, uint32_t width,
                uint32_t height, uint32_t tile_row0, uint32_t tile_row1, const uint32_t *range32,
-               const uint32_t *n_sorted_dev = nullptr, const uint32_t *depth_keys = nullptr);
+               const uint32_t *n_sorted_dev = nullptr, const uint32_t *depth_keys = nullptr,
+               const uint2 *range_wide = nullptr); // per splat index, the 8-byte range (screens beyond 256 x 256 tiles, sort-first)
 int binner_reserve(splat_binner *b, uint32_t tiles, uint32_t n_sorted); // per-tile and per-position buffers
 // tile_first.hip (the frame path's bin-then-sort-per-tile kernels) and the wide-payload radix sort
 int tf_scatter_launch(splat_ctx *ctx, const uint32_t *range32, const uint32_t *depth_keys, uint32_t n, uint32_t ntx, uint32_t mask,
@@ -305,4 +306,6 @@ int project_launch(splat_ctx *ctx, const float *uniforms, const void *pos_radius
                    uint32_t index_base, void *projected, void *keys, void *payload, uint32_t n_padded, uint32_t *range32,
                    const BinParams *bp, const TfHistOut *hist_out = nullptr, const void *normals = nullptr,
                    uint32_t normal_stride_vec4 = 1, void *discs = nullptr, // discs != NULL: the oriented-disc footprint (disc.h)
-                   const struct LitIO *lit = nullptr);                     // lit->records != NULL: also write lit composite records (shade.h)
+                   const struct LitIO *lit = nullptr,                      // lit->records != NULL: also write lit composite records (shade.h)
+                   uint2 *range_wide = nullptr); // instead of range32 (screens beyond 256 x 256 tiles): the 8-byte range, sort-first
+int binner_reserve_range_wide(splat_binner *b, uint32_t n_splats); // the range32 buffer, grown to 8 bytes per splat; its uint2s

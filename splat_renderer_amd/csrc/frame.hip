@@ -69,6 +69,43 @@ __global__ __launch_bounds__(BAND_THREADS) void k_band_prepare(const float4 *__r
     if (threadIdx.x == 0) blocksums[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
 }
 
+// The same pass on a screen beyond 256 x 256 tiles (sort-first, the only order there): the 8-byte wide range per record.
+// FORMAT: PROJECTED, or DISC48, whose bounds are the disc's (disc_bounds, as k_band_prepare_tf).  (COMPACT records reach the
+// sort-first path rebuilt as ProjectedSplat.)
+template <int FORMAT>
+__global__ __launch_bounds__(BAND_THREADS) void k_band_prepare_wide(const float4 *__restrict__ records, uint32_t n, BinParams bp,
+                                                                    uint32_t *__restrict__ keys_by_idx, uint2 *__restrict__ range_wide,
+                                                                    uint32_t *__restrict__ blocksums) {
+    __shared__ uint32_t wsum[4];
+    uint32_t kept = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < BAND_PER_THREAD; ++k) {
+        const uint32_t i = blockIdx.x * BAND_BLOCK + k * BAND_THREADS + threadIdx.x;
+        if (i < n) {
+            float4 a;
+            float depth;
+            if (FORMAT == SPLAT_RECORDS_DISC48) {
+                const DiscRecord d = {records[(size_t)i * 3], records[(size_t)i * 3 + 1]};
+                disc_bounds(d, a); // (NaN padding records: not finite -> all zero -> bins nowhere)
+                depth = records[(size_t)i * 3 + 2].x;
+            } else {
+                a = records[(size_t)i * 2];
+                depth = records[(size_t)i * 2 + 1].x;
+            }
+            uint32_t tx0, tx1, ty0, ty1;
+            const bool ok = tile_range(a, bp.width, bp.height, bp.tile, bp.ntx, bp.nty, bp.row0, bp.row1, tx0, tx1, ty0, ty1);
+            range_wide[i] = pack_range_wide(ok, tx0, tx1, ty0, ty1);
+            keys_by_idx[i] = depth_key_of(depth);
+            kept += ok ? 1u : 0u;
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) kept += __shfl_xor(kept, d);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = kept;
+    __syncthreads();
+    if (threadIdx.x == 0) blocksums[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
 // Tile-first band frame: the same pass, 1024 records per block (the binner's block), which also counts
 // the block's pairs per low tile-id digit like k_project_hist; a splat outside the band simply has an
 // empty range (no compaction, no sort of the kept splats).
@@ -298,6 +335,34 @@ __global__ __launch_bounds__(BAND_THREADS) void k_band_compact(const uint32_t *_
     }
 }
 
+// the same compaction from the 8-byte wide ranges (k_band_prepare_wide).  (A copy, not a shared body: k_band_compact built
+// from a shared template compiles to different code, and the <= 256 x 256 path stays as it was.)
+__global__ __launch_bounds__(BAND_THREADS) void k_band_compact_wide(const uint32_t *__restrict__ keys_by_idx,
+                                                                    const uint2 *__restrict__ range_wide, uint32_t n,
+                                                                    const uint32_t *__restrict__ block_base,
+                                                                    uint32_t *__restrict__ keys, uint32_t *__restrict__ payload) {
+    __shared__ uint32_t wsum[4];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    uint32_t carry = block_base[blockIdx.x];
+#pragma unroll
+    for (uint32_t k = 0; k < BAND_PER_THREAD; ++k) {
+        const uint32_t i = blockIdx.x * BAND_BLOCK + k * BAND_THREADS + tid;
+        const bool keep = (i < n) && ((range_wide[i].x & 0xffffu) <= (range_wide[i].x >> 16)); // tx0 <= tx1: not the empty code
+        const unsigned long long m = __ballot(keep);
+        const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+        if (lane == 0) wsum[w] = (uint32_t)__popcll(m);
+        __syncthreads();
+        const uint32_t s0 = wsum[0], s1 = wsum[1], s2 = wsum[2], s3 = wsum[3];
+        __syncthreads();
+        if (keep) {
+            const uint32_t o = carry + (w > 0 ? s0 : 0u) + (w > 1 ? s1 : 0u) + (w > 2 ? s2 : 0u) + below;
+            keys[o] = keys_by_idx[i];
+            payload[o] = i;
+        }
+        carry += s0 + s1 + s2 + s3;
+    }
+}
+
 // Resolves the previous splat_band_frame's kept-count readback.  If that frame kept more splats than
 // the bound its grids were sized for, it was rendered from a truncated set: say so (once).
 static int band_settle_count(splat_ctx *ctx, splat_sorter *sorter) {
@@ -338,6 +403,12 @@ static int band_keys_device(splat_ctx *ctx, splat_sorter *sorter, const void *pr
     stage_end(ctx, SPLAT_STAGE_PROJECT);
     return SPLAT_OK;
 }
+
+// Which packed tile range a frame carries per splat index.  A frame "has a packed range" on every screen the binner takes
+// (binner_run: at most 65535 tiles a side, 2^24 in all): range32 on screens of at most 256 x 256 tiles (the only screens that
+// may bin tile-first), the 8-byte wide range beyond them (sort-first).  Screens the binner refuses carry none.
+static bool range_fits_8_bits(uint32_t ntx, uint32_t nty) { return ntx <= 256 && nty <= 256; }
+static bool bin_accepts(uint32_t ntx, uint32_t nty) { return ntx <= 65535 && nty <= 65535 && (uint64_t)ntx * nty <= (1u << 24); }
 
 // which order of work splat_render_frame uses for this binner (see splat_bin_set_frame_order)
 static int g_frame_order = -2;
@@ -413,12 +484,17 @@ int splat_band_frame(splat_ctx *ctx, splat_sorter *sorter, splat_binner *binner,
     uint32_t row0 = cfg->tile_row0, row1 = cfg->tile_row1 > nty ? nty : cfg->tile_row1;
     if (row0 > row1) row0 = row1;
     const uint32_t ntx = div_up(width, tile);
-    const bool fast = ntx <= 256 && nty <= 256 && n_records > 0;
+    // fast: range32, and the tile-first order may run; wide: beyond 256 x 256 tiles, the 8-byte range (sort-first)
+    const bool fast = range_fits_8_bits(ntx, nty) && n_records > 0;
+    const bool wide = !fast && n_records > 0 && bin_accepts(ntx, nty);
     const bool compact = cfg->record_format == SPLAT_RECORDS_COMPACT;
     const bool disc = cfg->record_format == SPLAT_RECORDS_DISC48;
-    if (disc && n_records > 0 && !(fast && frame_order(binner) == SPLAT_FRAME_TILE_FIRST))
+    // oriented-disc records bin tile-first wherever that order exists (at most 256 x 256 tiles), sort-first from the wide range
+    // beyond, where it does not
+    if (disc && n_records > 0 && !(fast ? frame_order(binner) == SPLAT_FRAME_TILE_FIRST : wide))
         return ctx_fail(ctx, SPLAT_ERR_INVALID,
-                        "splat_band_frame: oriented-disc records need the tile-first frame order and a screen of at most 256 x 256 tiles");
+                        "splat_band_frame: oriented-disc records need the tile-first frame order on a screen of at most 256 x 256 tiles, "
+                        "and a screen the binner takes beyond that");
     ARG_CHECK(ctx, ((uintptr_t)records & 15) == 0);
     if (compact && n_records > 0 && !(fast && frame_order(binner) == SPLAT_FRAME_TILE_FIRST)) {
         // the other orders of work read ProjectedSplat records: rebuild them once (bit-exact) and go on
@@ -500,6 +576,7 @@ int splat_band_frame(splat_ctx *ctx, splat_sorter *sorter, splat_binner *binner,
         return rc;
     }
     uint32_t *range32 = nullptr;
+    uint2 *range_wide = nullptr;
     // grids of the sort and of the binner's count/expand are sized for `bound` kept splats: all
     // records on a first frame, 1.125x the previous frame's kept count afterwards
     uint32_t bound = n_records;
@@ -526,6 +603,28 @@ int splat_band_frame(splat_ctx *ctx, splat_sorter *sorter, splat_binner *binner,
                                blocksums, sorter->keys, sorter->payload);
             LAUNCH_CHECK(ctx, "k_band_compact");
             stage_end(ctx, SPLAT_STAGE_PROJECT);
+        } else if (wide) {
+            // the same keep-and-compact with 16-bit tile coordinates (COMPACT records arrive here rebuilt as ProjectedSplat)
+            rc = binner_reserve_range_wide(binner, n_records);
+            if (rc != SPLAT_OK) return rc;
+            range_wide = reinterpret_cast<uint2 *>(binner->range32);
+            const BinParams bp = {width, height, tile, ntx, nty, row0, row1};
+            const uint32_t blocks = div_up(n_records, BAND_BLOCK);
+            uint32_t *keys_by_idx = sorter->keys_b, *blocksums = sorter->hist; // both free until the sort starts
+            stage_begin(ctx, SPLAT_STAGE_PROJECT);
+            if (disc)
+                hipLaunchKernelGGL(k_band_prepare_wide<SPLAT_RECORDS_DISC48>, dim3(blocks), dim3(BAND_THREADS), 0, ctx->stream,
+                                   (const float4 *)records, n_records, bp, keys_by_idx, range_wide, blocksums);
+            else
+                hipLaunchKernelGGL(k_band_prepare_wide<SPLAT_RECORDS_PROJECTED>, dim3(blocks), dim3(BAND_THREADS), 0, ctx->stream,
+                                   (const float4 *)records, n_records, bp, keys_by_idx, range_wide, blocksums);
+            LAUNCH_CHECK(ctx, "k_band_prepare_wide");
+            rc = scan_exclusive_u32(ctx, blocksums, blocksums, blocks, sorter->d_count);
+            if (rc != SPLAT_OK) return rc;
+            hipLaunchKernelGGL(k_band_compact_wide, dim3(blocks), dim3(BAND_THREADS), 0, ctx->stream, keys_by_idx, range_wide, n_records,
+                               blocksums, sorter->keys, sorter->payload);
+            LAUNCH_CHECK(ctx, "k_band_compact_wide");
+            stage_end(ctx, SPLAT_STAGE_PROJECT);
         } else {
             rc = band_keys_device(ctx, sorter, records, n_records, width, height, tile, row0, row1);
             if (rc != SPLAT_OK) return rc;
@@ -548,7 +647,7 @@ int splat_band_frame(splat_ctx *ctx, splat_sorter *sorter, splat_binner *binner,
         sorter->ran = true;
     }
     rc = binner_run(binner, records, n_records, splat_sort_sorted_payload(sorter), bound, width, height, row0, row1, range32,
-                    n_records ? sorter->d_count : nullptr);
+                    n_records ? sorter->d_count : nullptr, nullptr, range_wide);
     if (rc != SPLAT_OK) return rc;
     void *indices = binner->pairs.result_in_primary ? binner->pairs.payload : binner->pairs.payload_b;
     splat_composite_cfg c2 = *cfg;
@@ -621,24 +720,32 @@ static int render_frame_impl(splat_ctx *ctx, splat_sorter *sorter, splat_binner 
     if (n > splat_sort_capacity(sorter)) return ctx_fail(ctx, SPLAT_ERR_CAPACITY, "splat_render_frame: n exceeds the sorter's capacity");
     ARG_CHECK(ctx, width >= 1 && height >= 1);
     // SplatProjector.project + DepthKeyExtractor.extract fused; props is the interleaved buffer.
-    // When tile coordinates fit 8 bits the projector also emits each splat's clamped tile range,
-    // which turns the binner's 16-byte bounds gather (in sorted order) into a 4-byte one.
+    // The projector also emits each splat's clamped tile range, which turns the binner's 16-byte bounds gather (in sorted
+    // order) into a 4-byte one (tile coordinates of 8 bits) or an 8-byte one (16 bits).
     const uint32_t tile = splat_bin_tile_size(binner);
     const uint32_t ntx = div_up(width, tile), nty = div_up(height, tile);
     uint32_t row0 = cfg->tile_row0, row1 = cfg->tile_row1 > nty ? nty : cfg->tile_row1;
     if (row0 > row1) row0 = row1;
-    const bool fast = ntx <= 256 && nty <= 256 && n > 0;
-    if ((!projected || lit || disc_lit) && n > 0 && !fast)
-        return ctx_fail(ctx, SPLAT_ERR_INVALID, "splat_render_frame: screens beyond 256 x 256 tiles bin from ProjectedSplat records: pass a "
-                                                "buffer and cfg->record_format = SPLAT_RECORDS_PROJECTED");
+    // fast: range32, and the tile-first order may run; wide: beyond 256 x 256 tiles, the 8-byte range (sort-first).  Either way
+    // the binner never reads the records, so lit records and a disc frame without ProjectedSplat records work on every screen.
+    const bool fast = range_fits_8_bits(ntx, nty) && n > 0;
+    const bool wide = !fast && n > 0 && bin_accepts(ntx, nty);
+    if ((!projected || lit || disc_lit) && n > 0 && !fast && !wide)
+        return ctx_fail(ctx, SPLAT_ERR_INVALID, "splat_render_frame: the screen has more tiles than the binner takes (65535 a side, 2^24 "
+                                                "in all)");
     int rc = SPLAT_OK;
     uint32_t *range32 = nullptr;
+    uint2 *range_wide = nullptr;
     // (a strict band: the projector skips what provably cannot reach it; those splats' records are then not written)
     const BinParams bp = {width, height, tile, ntx, nty, row0, row1, (row0 > 0 || row1 < nty) ? 1u : 0u};
     if (fast) {
         rc = binner_reserve_range32(binner, n);
         if (rc != SPLAT_OK) return rc;
         range32 = binner->range32;
+    } else if (wide) {
+        rc = binner_reserve_range_wide(binner, n);
+        if (rc != SPLAT_OK) return rc;
+        range_wide = reinterpret_cast<uint2 *>(binner->range32);
     }
     ARG_CHECK(ctx, (((uintptr_t)props | (uintptr_t)projected) & 15) == 0);
     const bool tile_first = fast && frame_order(binner) == SPLAT_FRAME_TILE_FIRST;
@@ -676,7 +783,7 @@ static int render_frame_impl(splat_ctx *ctx, splat_sorter *sorter, splat_binner 
     const LitIO lio = {(const float4 *)color, (const float4 *)normals, color_stride, 1u, cfg->prelit,
                        lit ? (float4 *)projected : disc_lit ? (float4 *)binner->discs : nullptr};
     rc = project_launch(ctx, uniforms, props, pos_stride, n, 0, lit ? nullptr : projected, splat_sort_keys(sorter), nullptr, n, range32, &bp,
-                        tile_first ? &ho : nullptr, normals, 1, disc ? binner->discs : nullptr, &lio);
+                        tile_first ? &ho : nullptr, normals, 1, disc ? binner->discs : nullptr, &lio, range_wide);
     if (rc != SPLAT_OK) return rc;
     binner->tf_hist_ready = tile_first;
     binner->tf_cidx = band_compact ? binner->band_idx : nullptr;
@@ -695,7 +802,8 @@ static int render_frame_impl(splat_ctx *ctx, splat_sorter *sorter, splat_binner 
         stage_end(ctx, SPLAT_STAGE_SORT);
         if (rc != SPLAT_OK) return rc;
         sorter->ran = true;
-        rc = binner_run(binner, bin_records, n, splat_sort_sorted_payload(sorter), n, width, height, row0, row1, range32);
+        rc = binner_run(binner, bin_records, n, splat_sort_sorted_payload(sorter), n, width, height, row0, row1, range32, nullptr, nullptr,
+                        range_wide);
         if (rc != SPLAT_OK) return rc;
     }
     // (fields, not the public getters: those wait for a sync-free frame's pair total to come back)

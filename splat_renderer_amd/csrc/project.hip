@@ -135,7 +135,9 @@ __device__ __forceinline__ SplatIn load_splat(const float4 *__restrict__ pos_rad
     return s;
 }
 
-template <bool WITH_KEYS, bool WITH_RANGE, bool DISC, bool LIT = false>
+// WIDE (screens beyond 256 x 256 tiles): the range goes to range32 as an 8-byte pack_range_wide (range32 then points at
+// uint2s); the return value is then not a range.
+template <bool WITH_KEYS, bool WITH_RANGE, bool DISC, bool LIT = false, bool WIDE = false>
 __device__ __forceinline__ uint32_t project_one(const FrameUniforms &u, const SplatIn &in, uint32_t i, uint32_t index_base,
                                                 float4 *__restrict__ projected, uint32_t *__restrict__ keys,
                                                 uint32_t *__restrict__ payload, uint32_t *__restrict__ range32, const BinParams &bp,
@@ -180,8 +182,12 @@ __device__ __forceinline__ uint32_t project_one(const FrameUniforms &u, const Sp
     if (WITH_RANGE) { // the binner's clamped tile range while the bounds are still in registers
         uint32_t tx0, tx1, ty0, ty1;
         const bool ok = tile_range(a, bp.width, bp.height, bp.tile, bp.ntx, bp.nty, bp.row0, bp.row1, tx0, tx1, ty0, ty1);
-        packed = pack_range32(ok, tx0, tx1, ty0, ty1);
-        range32[ks] = packed;
+        if (WIDE) {
+            reinterpret_cast<uint2 *>(range32)[ks] = pack_range_wide(ok, tx0, tx1, ty0, ty1);
+        } else {
+            packed = pack_range32(ok, tx0, tx1, ty0, ty1);
+            range32[ks] = packed;
+        }
     }
     return packed;
 }
@@ -237,6 +243,23 @@ __global__ __launch_bounds__(256) void k_project(FrameUniforms u, const float4 *
     }
     const SplatIn in = load_splat<DISC, LIT>(pos_radius, stride_vec4, i, dio, lio);
     project_one<WITH_KEYS, WITH_RANGE, DISC, LIT>(u, in, i, index_base, projected, keys, payload, range32, bp, dio, lio);
+}
+
+// The frame's projector on screens beyond 256 x 256 tiles (sort-first only): k_project<true, true, DISC, LIT> with the
+// 8-byte wide range per splat index instead of range32 (no payload: the sort's first pass synthesises it).
+template <bool DISC, bool LIT>
+__global__ __launch_bounds__(256) void k_project_wide(FrameUniforms u, const float4 *__restrict__ pos_radius, uint32_t stride_vec4,
+                                                      uint32_t n, uint32_t n_padded, float4 *__restrict__ projected,
+                                                      uint32_t *__restrict__ keys, uint2 *__restrict__ range_wide, BinParams bp,
+                                                      DiscIO dio, LitIO lio) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) {
+        if (i < n_padded) keys[i] = 0xffffffffu;
+        return;
+    }
+    const SplatIn in = load_splat<DISC, LIT>(pos_radius, stride_vec4, i, dio, lio);
+    project_one<true, true, DISC, LIT, true>(u, in, i, 0, projected, keys, nullptr, reinterpret_cast<uint32_t *>(range_wide), bp, dio,
+                                             lio);
 }
 
 // Tile-first frame path: 1024 splats per workgroup (the binner's block), and while each splat's tile
@@ -512,7 +535,7 @@ static void load_uniforms(FrameUniforms &u, const float *uniforms) {
 int project_launch(splat_ctx *ctx, const float *uniforms, const void *pos_radius, uint32_t pr_stride_vec4, uint32_t n,
                    uint32_t index_base, void *projected, void *keys, void *payload, uint32_t n_padded, uint32_t *range32,
                    const BinParams *bp, const TfHistOut *hist_out, const void *normals, uint32_t normal_stride_vec4, void *discs,
-                   const LitIO *lit) {
+                   const LitIO *lit, uint2 *range_wide) {
     FrameUniforms u;
     load_uniforms(u, uniforms);
     const uint32_t work = keys ? n_padded : n;
@@ -523,7 +546,7 @@ int project_launch(splat_ctx *ctx, const float *uniforms, const void *pos_radius
     // lit composite records (shade.h) of an isotropic frame, written next to the keys and tile ranges; a disc frame's lit
     // colours go behind its disc records (lit->records = discs there: 48-byte records)
     const bool with_lit = lit && lit->records && !disc, disc_lit = lit && lit->records && disc;
-    if ((with_lit || disc_lit) && !(keys && range32 && !payload && index_base == 0))
+    if ((with_lit || disc_lit) && !(keys && (range32 || range_wide) && !payload && index_base == 0))
         return ctx_fail(ctx, SPLAT_ERR_INVALID, "project_launch: lit records are written by the frame's projector only");
     const DiscIO dio = {disc ? (const float4 *)normals + (size_t)index_base * normal_stride_vec4 : nullptr, normal_stride_vec4,
                         (float4 *)discs, disc_lit ? 3u : 2u};
@@ -572,6 +595,15 @@ int project_launch(splat_ctx *ctx, const float *uniforms, const void *pos_radius
         else if (bp->skip_outside) SPLAT_PROJECT_HIST_LAUNCH(k_project_hist_band, false, false);
         else if (with_lit) SPLAT_PROJECT_HIST_LAUNCH_PER(false, true);
         else SPLAT_PROJECT_HIST_LAUNCH_PER(false, false);
+    } else if (keys && range_wide && !payload && index_base == 0) {
+#define SPLAT_PROJECT_WIDE(D, L)                                                                                                   \
+    hipLaunchKernelGGL((k_project_wide<D, L>), grid, block, 0, ctx->stream, u, src, pr_stride_vec4, n, n_padded, (float4 *)projected, \
+                       (uint32_t *)keys, range_wide, *bp, dio, lio)
+        if (disc_lit) SPLAT_PROJECT_WIDE(true, true);
+        else if (disc) SPLAT_PROJECT_WIDE(true, false);
+        else if (with_lit) SPLAT_PROJECT_WIDE(false, true);
+        else SPLAT_PROJECT_WIDE(false, false);
+#undef SPLAT_PROJECT_WIDE
     } else if (keys && range32) {
         if (disc_lit) SPLAT_PROJECT_LAUNCH(true, true, true, true, range32, *bp);
         else if (disc) SPLAT_PROJECT_LAUNCH(true, true, true, false, range32, *bp);

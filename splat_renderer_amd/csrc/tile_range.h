@@ -43,6 +43,13 @@ __device__ __forceinline__ uint32_t pack_range32(bool ok, uint32_t tx0, uint32_t
     return ok ? (tx0 | (tx1 << 8) | (ty0 << 16) | (ty1 << 24)) : 1u;
 }
 
+// 16-bit packed tile range (frame path, a side beyond 256 tiles; the binner takes at most 65535 a side):
+// {tx0 | tx1<<16, ty0 | ty1<<16}, the layout of the binner's own per-position ranges (bin.hip: k_bin_count).
+// An empty range is (1, 1): tx0 = 1 > tx1 = 0.
+__device__ __forceinline__ uint2 pack_range_wide(bool ok, uint32_t tx0, uint32_t tx1, uint32_t ty0, uint32_t ty1) {
+    return ok ? make_uint2(tx0 | (tx1 << 16), ty0 | (ty1 << 16)) : make_uint2(1u, 1u);
+}
+
 // First sort pass's histogram (tile_first.hip): one count per tile of the rectangle, keyed by the low
 // tile-id digit, into a wave-private 256-counter LDS histogram.  Returns the number of tiles.
 __device__ __forceinline__ uint32_t hist_add_rect(uint32_t *wave_hist, uint32_t tx0, uint32_t tx1, uint32_t ty0, uint32_t ty1,

@@ -762,12 +762,13 @@ class Renderer:
         # composite gathers per staged list entry — "lit" (default): the 32-byte lit composite records (centre,
         # radius, depth | lit colour; SPLAT_RECORDS_LIT32), ONE line per entry; "projected": the reference's
         # ProjectedSplat records, with colour (and normal) gathered from the property buffers as the reference does.
-        # Same image bit for bit.  Screens beyond 256 x 256 tiles always use "projected".
+        # Same image bit for bit.  "lit" falls back to "projected" on screens beyond 256 x 256 tiles; "lit-always" is "lit" on
+        # every screen the binner takes.
         self.footprint = _footprint(footprint)
         if not writeProjected and self.footprint != _lib.FOOTPRINT_DISC:
             raise SplatError(-1, "writeProjected=False: the isotropic composite reads the records the projector writes")
-        if records not in ("lit", "projected"):
-            raise SplatError(-1, f"records must be 'lit' or 'projected', not {records!r}")
+        if records not in ("lit", "lit-always", "projected"):
+            raise SplatError(-1, f"records must be 'lit', 'lit-always' or 'projected', not {records!r}")
         # (disc frames, "lit": the lit colour rides behind each disc record — 48-byte records inside the binner, one gathered
         # record per staged entry instead of disc record + colour + normal; the ProjectedSplat buffer is what it always was)
         self.records = records
@@ -813,7 +814,7 @@ class Renderer:
             self.outputFloat = d.createBuffer(width * height * 16)
         prelit = isinstance(propertyBuffer, PropertyPlanes) and propertyBuffer.prelit
         ts = self.tileSize
-        lit = self.records == "lit" and -(-width // ts) <= 256 and -(-height // ts) <= 256
+        lit = self.records == "lit-always" or (self.records == "lit" and -(-width // ts) <= 256 and -(-height // ts) <= 256)
         # what the FRAME composites from (a disc frame with "lit": 48-byte lit disc records inside the binner) ...
         frame_format = self.frameRecordFormat = _lib.RECORDS_LIT32 if lit else _lib.RECORDS_PROJECTED
         # ... and what projector.getRecordsBuffer() holds after this frame — what a caller passes, with this format, to the staged

@@ -65,7 +65,7 @@ export class OrbitCameraController {
 /** the render loop of src/main.ts:110-193 for the tile-raster path, headless */
 export class FrameLoop {
   constructor(device: Device, numPoints: number, width: number, height: number, tileSize?: number, camera?: Camera | null,
-              rendererOptions?: { footprint?: Footprint; records?: "lit" | "projected" });
+              rendererOptions?: { footprint?: Footprint; records?: "lit" | "lit-always" | "projected" });
   readonly camera: Camera;
   readonly renderer: Renderer;
   frame: number;
@@ -248,7 +248,7 @@ export class TileRenderer extends ComputeShaderRenderer {
   render(uniformData: Float32Array, splatPropertyBuffer: Buffer, splatIndicesBuffer: Buffer, curvatureBuffer: Buffer, tileCountsData: Uint32Array | Buffer, numTilesX: number, numTilesY: number, tileSize: number, maxSplatsPerTile: number, width: number, height: number): Promise<void>;
 }
 export class Renderer {
-  constructor(device: Device, context?: unknown, presentationFormat?: string, numPoints?: number, tileSize?: number, options?: { footprint?: Footprint; records?: "lit" | "projected" });
+  constructor(device: Device, context?: unknown, presentationFormat?: string, numPoints?: number, tileSize?: number, options?: { footprint?: Footprint; records?: "lit" | "lit-always" | "projected" });
   recordFormat: number;
   render(uniformData: Float32Array | Buffer, propertyBuffer: Buffer | PropertyPlanes, normalsBuffer: Buffer, scaleFactorsBuffer: Buffer | null, width: number, height: number): Buffer;
   finish(): number;

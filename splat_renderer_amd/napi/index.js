@@ -460,9 +460,10 @@ class Renderer {
     // 'disc': SequentialRenderer's oriented discs (normalsBuffer then always required)
     // records 'lit' (default, isotropic frames): the projector leaves 32-byte lit composite records (centre, radius, depth |
     // lit colour) in projector.getProjectedBuffer() and the composite gathers ONE line per staged list entry;
-    // 'projected': the reference's ProjectedSplat records, colour and normal gathered per entry.  Same image.
+    // 'projected': the reference's ProjectedSplat records, colour and normal gathered per entry.  Same image.  'lit' falls back
+    // to 'projected' on screens beyond 256 x 256 tiles; 'lit-always' is 'lit' on every screen the binner takes.
     // (disc frames, 'lit': the lit colour rides behind each disc record inside the binner — one gathered record per staged entry)
-    this.records = options.records === 'projected' ? 'projected' : 'lit';
+    this.records = options.records === 'projected' || options.records === 'lit-always' ? options.records : 'lit';
     this.projector = new SplatProjector(device, numPoints);
     this.sorter = new RadixSorter(device, numPoints);
     this.binner = new GPUTileBinner(device, tileSize);
@@ -488,7 +489,7 @@ class Renderer {
     }
     const small = Math.ceil(width / this.tileSize) <= 256 && Math.ceil(height / this.tileSize) <= 256;
     // what the FRAME composites from (a disc frame with 'lit': 48-byte lit disc records inside the binner) ...
-    const frameFormat = this.records === 'lit' && small ? RECORDS_LIT32 : RECORDS_PROJECTED;
+    const frameFormat = this.records === 'lit-always' || (this.records === 'lit' && small) ? RECORDS_LIT32 : RECORDS_PROJECTED;
     // ... and what projector.getRecordsBuffer() holds after this frame — what a caller passes, with this format, to the staged
     // composite: lit composite records for an isotropic 'lit' frame, ProjectedSplat records otherwise (a disc frame's too)
     const isoLit = frameFormat === RECORDS_LIT32 && this.footprint !== FOOTPRINT_DISC;
