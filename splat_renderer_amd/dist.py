@@ -212,9 +212,10 @@ class HipStages:
             check(rc, self.ctx)
             self.pairs = int(t.value)
 
-    def local_frame(self, uniforms, props_ptr, normals_ptr, n, row0, row1, out_image, settle=False):
+    def local_frame(self, uniforms, props_ptr, normals_ptr, n, row0, row1, out_image, settle=False, out_float=None):
         """Tile rows [row0, row1) of the frame from THIS rank's copy of the splats (splat_render_frame with a band): no
-        exchange; every rank projects all n splats itself.  Same sync-free rules as band_frame."""
+        exchange; every rank projects all n splats itself.  Same sync-free rules as band_frame.  out_float: an optional
+        float32 [height, width, 4] image the frame also writes."""
         prelit = self.lit is not None
         # (isotropic: the projector leaves lit composite records, one gathered line per staged entry)
         small = -(-self.width // self.tile) <= 256 and -(-self.height // self.tile) <= 256
@@ -226,7 +227,7 @@ class HipStages:
         u = np.ascontiguousarray(uniforms, np.float32)
         head = (self.ctx, self.sorter, self.binner, C.byref(cfg), u.ctypes.data_as(C.POINTER(C.c_float)))
         tail = (normals_ptr if (self.disc or not prelit) else None, n, self.width, self.height, self.local_projected.data_ptr(),
-                out_image.data_ptr(), None)
+                out_image.data_ptr(), out_float.data_ptr() if out_float is not None else None)
         if prelit:
             fn, args = self.lib.splat_render_frame_planes, head + (self.pos_plane.data_ptr(), self.lit.data_ptr()) + tail
         else:
@@ -380,8 +381,10 @@ class LocalBandRenderer:
         self.row0, self.row1 = band_rows(self.nty, rank, world)
         self.image = stages.new_image()
 
-    def render(self, uniforms, props_ptr, normals_ptr, settle=False):
-        self.stages.local_frame(uniforms, props_ptr, normals_ptr, self.n, self.row0, self.row1, self.image, settle)
+    def render(self, uniforms, props_ptr, normals_ptr, settle=False, image_float=None):
+        # (image_float: HipStages only — a float32 [height, width, 4] image the frame also writes)
+        extra = {} if image_float is None else {"out_float": image_float}
+        self.stages.local_frame(uniforms, props_ptr, normals_ptr, self.n, self.row0, self.row1, self.image, settle, **extra)
         return self.image
 
     def pixel_rows(self):

@@ -439,31 +439,35 @@ def test_disc_full_size_C2_properties(device):
 @pytest.mark.parametrize("prelit", [False, True])
 def test_exchange_free_bands_stitch_to_the_single_gpu_frame(device, footprint, prelit):
     """dist.LocalBandRenderer: every (virtual) rank projects all splats from its own copy and renders its band — no
-    exchange.  The stitched rgba8 image must be bit-identical to the single-GPU frame, for both footprints."""
+    exchange.  The stitched rgba8 and float images must be bit-identical to the single-GPU frame's, for both footprints."""
     import torch
     from splat_renderer_amd import dist
     world, n, w, h = 3, 30001, 400, 232
     props, normals, u = make_case(n, w, h, 41, 1.5)
     pbuf, nbuf = device.createBufferFrom(props), device.createBufferFrom(normals)
     full = sr.Renderer(device, None, "rgba8unorm", n, footprint=footprint)
-    full.render(u, pbuf, nbuf, None, w, h)
+    full.render(u, pbuf, nbuf, None, w, h, wantFloat=True)
     want = full.readPixels().copy()
+    want_f = full.readPixelsFloat().view(np.uint32).copy()
     device.sync()
     pt, nt = torch.from_numpy(props).cuda(), torch.from_numpy(normals).cuda()
     stages = dist.HipStages(torch, 0, n, w, h, footprint=footprint)
     if prelit:
         stages.set_lit(pt.data_ptr(), nt.data_ptr(), n)
         assert_same(stages.pos_plane.cpu().numpy(), props[:, :4], "disc L421")
-    got = np.zeros_like(want)
+    got, got_f = np.zeros_like(want), np.zeros_like(want_f)
     for rank in range(world):
         lr = dist.LocalBandRenderer(stages, n, w, h, rank, world)
+        imf = torch.zeros((h, w, 4), dtype=torch.float32, device="cuda:0")
         for _ in range(2):  # the second one is a sync-free frame
-            lr.render(u, pt.data_ptr(), nt.data_ptr())
-        lr.render(u, pt.data_ptr(), nt.data_ptr(), settle=True)
+            lr.render(u, pt.data_ptr(), nt.data_ptr(), image_float=imf)
+        lr.render(u, pt.data_ptr(), nt.data_ptr(), settle=True, image_float=imf)
         torch.cuda.synchronize()
         r0, r1 = lr.pixel_rows()
         got[r0:r1] = lr.image.cpu().numpy()[r0:r1]
+        got_f[r0:r1] = imf.cpu().numpy().view(np.uint32)[r0:r1]
     assert_same(got, want, "disc L431")
+    assert_same(got_f, want_f, ("exchange-free bands, float image", footprint, prelit))
     stages.destroy()
     for o in (full, pbuf, nbuf):
         o.destroy()
@@ -478,22 +482,32 @@ def test_full_size_C2_eight_exchange_free_bands_stitch_bit_identically(device, f
     props, normals, u = make_case(n, w, h)
     pbuf, nbuf = device.createBufferFrom(props), device.createBufferFrom(normals)
     r = sr.Renderer(device, None, "rgba8unorm", n, footprint=footprint)
-    r.render(u, pbuf, nbuf, None, w, h)
+    r.render(u, pbuf, nbuf, None, w, h, wantFloat=True)
     want = r.readPixels().copy()
+    want_f = r.readPixelsFloat().view(np.uint32).copy()
     total = r.finish()
     counts_full = r.binner.getTileCountsBuffer().read(np.uint32).copy()
+    offsets_full = r.binner.getTileOffsetsBuffer().read(np.uint32).copy()
+    lists_full = r.binner.getTileIndicesBuffer().read(np.uint32, total).copy()
     nty = -(-h // 16)
+    ntx = counts_full.shape[0] // nty
     bands = dist.balanced_rows(counts_full.reshape(nty, -1).sum(axis=1), 8)
-    got = np.zeros_like(want)
+    got, got_f = np.zeros_like(want), np.zeros_like(want_f)
     pairs = 0
     for (r0, r1) in bands:
-        r.render(u, pbuf, nbuf, None, w, h, tileRows=(r0, r1))
+        r.render(u, pbuf, nbuf, None, w, h, tileRows=(r0, r1), wantFloat=True)
         got[r0 * 16:min(r1 * 16, h)] = r.readPixels()[r0 * 16:min(r1 * 16, h)]
+        got_f[r0 * 16:min(r1 * 16, h)] = r.readPixelsFloat().view(np.uint32)[r0 * 16:min(r1 * 16, h)]
         c = r.binner.getTileCountsBuffer().read(np.uint32).reshape(nty, -1)
         assert np.array_equal(c[r0:r1], counts_full.reshape(nty, -1)[r0:r1])  # the band's lists are the full frame's
-        pairs += int(c[r0:r1].sum(dtype=np.uint64))
+        band_pairs = int(c[r0:r1].sum(dtype=np.uint64))
+        lo = int(offsets_full[r0 * ntx])
+        assert_same(r.binner.getTileIndicesBuffer().read(np.uint32, band_pairs), lists_full[lo:lo + band_pairs],
+                    ("C2 band lists", footprint, r0, r1))
+        pairs += band_pairs
     assert pairs == total
     assert_same(got, want, "disc L461")
+    assert_same(got_f, want_f, ("C2 bands, float image", footprint))
     for o in (r, pbuf, nbuf):
         o.destroy()
 

@@ -516,10 +516,11 @@ def test_lit_composite_records_give_the_same_frame_bit_for_bit(device, order):
         a.destroy()
     # a band of tile rows (the exchange-free multi-GPU cut): records of splats that can reach the band, same pixels
     full = sr.Renderer(device, None, "rgba8unorm", n, frameOrder=order)
-    full.render(u, pm.getPropertyBuffer(), nbuf, None, w, h)
+    full.render(u, pm.getPropertyBuffer(), nbuf, None, w, h, wantFloat=True)
     band = sr.Renderer(device, None, "rgba8unorm", n, frameOrder=order)
-    band.render(u, pm.getPropertyBuffer(), nbuf, None, w, h, tileRows=(5, 11))
+    band.render(u, pm.getPropertyBuffer(), nbuf, None, w, h, tileRows=(5, 11), wantFloat=True)
     assert_same(band.readPixels()[80:176], full.readPixels()[80:176], "L435")
+    assert_same(band.readPixelsFloat().view(np.uint32)[80:176], full.readPixelsFloat().view(np.uint32)[80:176], ("L435 float", order))
     for o in (full, band, pm, nbuf):
         o.destroy()
 
