@@ -171,7 +171,9 @@ def composite(mode, early_out, color_opacity, normals, projected, indices, count
                 g = np.where(inside, np.exp(((F(-0.5) * nd) * nd) / (F(0.5) * F(0.5))), F(0.0)).astype(np.float32)
                 nrm = normals[s]
                 ndl = (nrm[0] * inv3 + nrm[1] * inv3) + nrm[2] * inv3
-                k = F(0.85) + F(0.15) * max(ndl, F(0.0))
+                # :144 max(dot(normal, lightDir), 0.0): a NaN dot (NaN normal) is dropped, as oracle.c's fmaxf and the
+                # kernels' lit_color drop it (Python's max(NaN, 0) would keep the NaN)
+                k = F(0.85) + F(0.15) * np.fmax(ndl, F(0.0))
                 lit = (color_opacity[s, :3] * k).astype(np.float32)
             g = np.where(live, g, F(0.0)).astype(np.float32)
             if mode == 1:

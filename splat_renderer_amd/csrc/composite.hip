@@ -515,6 +515,14 @@ __device__ __forceinline__ v2f fma_clamp01(v2f a, v2f b, v2f c) {
     return r;
 }
 
+// Whether any of a lane's four pixels still accumulates: T > T_STOP compared as bit patterns — for T >= 0 the same as the float
+// comparison, and a pixel whose T went negative or NaN (it took a NaN Gaussian: see the builder) still counts, as a NaN alpha
+// never reaches the reference's 0.99 (:187-190) and that pixel walks the whole list.  (As many instructions as the float form.)
+__device__ __forceinline__ bool px_any_live(const v2f *T) {
+    const uint32_t m = max(max(__float_as_uint(T[0].x), __float_as_uint(T[0].y)), max(__float_as_uint(T[1].x), __float_as_uint(T[1].y)));
+    return m > __float_as_uint(T_STOP);
+}
+
 template <bool EARLY_OUT, bool LIT32, bool COUNT, int AH, bool DISC>
 __global__ __launch_bounds__(128, PX_WAVES) void k_composite_px(CompositeParams p, uint32_t band_tiles) {
     constexpr uint32_t NB = AH + 1;
@@ -605,7 +613,18 @@ __global__ __launch_bounds__(128, PX_WAVES) void k_composite_px(CompositeParams 
                 // comes from the partner lane (e, 1 - h) — v_permlane32_swap, one instruction — because an entry that misses
                 // the tile on EITHER axis draws nothing in it (ComputeShaderRenderer.ts:118-121)
                 const float lo = h ? b.y : b.x, hi = h ? b.w : b.z;
-                const float fa = fmaxf(ceilf(lo - tile_c), 0.0f), fb = fminf(floorf(hi - tile_c), 15.0f);
+                // The tables below are a recurrence seeded at the first covered pair, which holds only while the seed
+                // exp2(-u0^2) is a normal float and R = exp2(-4k(u + k)) stays finite.  A projector record (box c +- 1.5 r)
+                // starts at |u0| <= 6; a free box from the staged API may start far further out (c - 100 r: G underflows to
+                // 0, R overflows, and the table holds 0 * inf = NaN, or zeros where the Gaussian is 1).  So the span starts
+                // no further than 3.25 r left of the centre: pixels beyond have a per-axis factor < 2^-30, so 1 - g is 1 in
+                // binary32 and their contribution is below 2^-30 of a colour — the same to the last bit for T, and far
+                // inside the tolerance for colour.  For projector records this bound never bites (1.75 r >= 0.875 px of
+                // margin), so their images are unchanged.  (fmaxf drops a NaN centre or radius: the span stays as it was.
+                // DISC: rad is a flag there, and the disc's tables are not a recurrence.)
+                const float reach = DISC ? -INFINITY : ceilf((lo + hi) * 0.5f - 3.25f * rad - tile_c);
+                const float fa = fmaxf(fmaxf(ceilf(lo - tile_c), reach), 0.0f);
+                const float fb = fminf(floorf(hi - tile_c), 15.0f);
                 const uint32_t ia = (uint32_t)fminf(fa, 15.0f), ib = (uint32_t)fmaxf(fb, 0.0f); // (in range whatever the bounds: an empty span is rejected below)
                 uint32_t own = ((2u << ib) - 1u) & ~((1u << ia) - 1u);
                 if (!(fa <= fb) || !(cb0 + e < count) || rad < 0.5f) own = 0; // (NaN bounds;) past the list's end; :127-129 "too small"
@@ -624,10 +643,24 @@ __global__ __launch_bounds__(128, PX_WAVES) void k_composite_px(CompositeParams 
                 // gaussian = exp(-0.5 (dist / r)^2 / 0.25) = exp2(-((dx k)^2 + (dy k)^2)), k = sqrt(2 log2 e) / r (:133-140), one
                 // axis per lane, in tile-local coordinates.  u = (pixel centre - splat centre) k at the first covered pair's two
                 // pixels; v_rcp_f32, 1 ulp: the correctly rounded quotient costs ten instructions on this wave's path.
-                const float k1 = 1.6986436005760381f * __builtin_amdgcn_rcpf(rad);
+                float k1 = 1.6986436005760381f * __builtin_amdgcn_rcpf(rad);
                 const float cl = (lo + hi) * 0.5f - tile_0; // :124, then exact
-                const float u0 = ((float)(2u * p0) + 0.5f - cl) * k1, u1 = u0 + k1, u2 = u1 + k1, k4 = 4.0f * k1;
-                v2f G = {__builtin_amdgcn_exp2f(-(u0 * u0)), __builtin_amdgcn_exp2f(-(u1 * u1))};
+                float u0 = ((float)(2u * p0) + 0.5f - cl) * k1, bias = 0.0f;
+                if constexpr (EARLY_OUT) {
+                    // A NaN Gaussian (NaN radius or centre on either axis, or an infinite centre with r = inf: NaN in the sum of
+                    // the four bounds times k — the same for both lanes of the entry) must reach only the pixels still
+                    // accumulating.  The consumer stops a pixel by a factor (w = T g m, m = 0 once T <= T_STOP), and NaN * 0 is
+                    // NaN: a pixel that had stopped would turn NaN where the reference has left its loop (:187-190).  So such an
+                    // entry's table is 2^60 on both axes (u = k = 0, bias 60: g = 2^120, finite): a stopped pixel takes
+                    // T g 0 = 0, a live one w = T g >= T_STOP 2^120, which drives its T below zero — it then takes nothing
+                    // more, and is written as NaN, what the reference's NaN gives (px_any_live keeps it walking the list).
+                    const bool nan_g = __builtin_isnan(((b.x + b.z) + (b.y + b.w)) * k1);
+                    u0 = nan_g ? 0.0f : u0;
+                    k1 = nan_g ? 0.0f : k1;
+                    bias = nan_g ? 60.0f : 0.0f;
+                }
+                const float u1 = u0 + k1, u2 = u1 + k1, k4 = 4.0f * k1;
+                v2f G = {__builtin_amdgcn_exp2f(__builtin_fmaf(-u0, u0, bias)), __builtin_amdgcn_exp2f(__builtin_fmaf(-u1, u1, bias))};
                 v2f R = {__builtin_amdgcn_exp2f(-(k4 * u1)), __builtin_amdgcn_exp2f(-(k4 * u2))}; // G(u + 2k) / G(u)
                 const float Dd = __builtin_amdgcn_exp2f(-2.0f * (k4 * k1));                        // R(u + 2k) / R(u)
                 const v2f D = {Dd, Dd};
@@ -753,7 +786,7 @@ __global__ __launch_bounds__(128, PX_WAVES) void k_composite_px(CompositeParams 
             PX_PRIORITY(k);
             const bool ahead = AH >= 2 && k + 1u < lim; // chunk k + 1 is built: lanes may run ahead into it
             // a lane whose four pixels have all stopped takes no more entries
-            const bool lane_live = !EARLY_OUT || fmaxf(fmaxf(T[0].x, T[0].y), fmaxf(T[1].x, T[1].y)) > T_STOP;
+            const bool lane_live = !EARLY_OUT || px_any_live(T);
             uint32_t mine, nxt = 0;
             {
                 const uint2 *q0 = reinterpret_cast<const uint2 *>(lds + o0 + offsetof(Buf, q4));
@@ -931,7 +964,7 @@ __global__ __launch_bounds__(128, PX_WAVES) void k_composite_px(CompositeParams 
             if (COUNT && EARLY_OUT && jlast != NONE) stop_pos = cb0 + jlast + 1; // (a lane's entries come in list order: later ones overwrite)
             if (EARLY_OUT) {
                 // the tile is finished when every pixel has stopped: both waves leave after the next barrier
-                const bool live = fmaxf(fmaxf(T[0].x, T[0].y), fmaxf(T[1].x, T[1].y)) > T_STOP;
+                const bool live = px_any_live(T);
                 finished = __ballot(live) == 0;
                 if (finished && lane == 0) s_done[(k + 1u) & 1u] = 1;
             }
@@ -948,7 +981,7 @@ __global__ __launch_bounds__(128, PX_WAVES) void k_composite_px(CompositeParams 
         uint32_t used = stop_pos;
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) used = max(used, (uint32_t)__shfl_xor((int)used, d));
-        const bool px_live = fmaxf(fmaxf(T[0].x, T[0].y), fmaxf(T[1].x, T[1].y)) > T_STOP;
+        const bool px_live = px_any_live(T);
         if (!EARLY_OUT || __ballot(px_live) != 0) used = count;
         if (lane == 0) p.consumed[(size_t)tile_idx * 2 + 1] += (unsigned long long)used;
     }
@@ -959,6 +992,10 @@ __global__ __launch_bounds__(128, PX_WAVES) void k_composite_px(CompositeParams 
     for (int r = 0; r < 2; ++r) {
         const uint32_t py = py0 + r;
         if (py >= p.height || !okx0) continue;
+        if (EARLY_OUT && !DISC) { // T < 0: the pixel took a NaN Gaussian while it accumulated (the builder's 2^60 tables)
+            T[r].x = (T[r].x >= 0.0f) ? T[r].x : __builtin_nanf("");
+            T[r].y = (T[r].y >= 0.0f) ? T[r].y : __builtin_nanf("");
+        }
         const float r0 = cr[r].x + 0.05f * T[r].x, g0 = cg[r].x + 0.05f * T[r].x, b0 = cb[r].x + 0.1f * T[r].x;
         const float r1 = cr[r].y + 0.05f * T[r].y, g1 = cg[r].y + 0.05f * T[r].y, b1 = cb[r].y + 0.1f * T[r].y;
         const size_t o = (size_t)py * p.width + px0;
