@@ -477,6 +477,26 @@ int splat_sdf_generate(splat_ctx *ctx, const splat_sdf_instr *program, uint32_t 
                        uint64_t seed, const void *positions_in, uint32_t n, uint32_t steps, void *positions_out, void *gradients_out,
                        void *curvature_out, void *props_out);
 
+/* ---- Renderer.render: the image the reference app draws  (src/Renderer.ts:68-143,196-201,250-311; src/main.ts:183-190) ---
+ * One opaque quad per point in the tangent plane of its SDF gradient (normal = normalize(gradient.yzw), the tangent frame
+ * of computeTangent, half-side 0.025 * scale), two triangles, drawn in index order through a depth test ("less" against a
+ * depth buffer cleared to 1), shaded from the normal, on the clear colour (0.05, 0.05, 0.1, 1).  Conventions:
+ * pixel centres at +0.5, top-left fill rule, stored depth z/w (a fragment passes when 0 <= z/w < the stored value; on
+ * equal depth the lower index wins), no clipper: a quad with a corner at w <= 0 is dropped, and a point whose normal,
+ * scale or corners are not finite covers nothing.
+ *   uniforms: the 22-float block of splat_project (VP = floats 0-15 are read);
+ *   positions: vec4 (xyz used), pos_stride_vec4 float4s apart; gradients: vec4(distance, gradient), grad_stride_vec4
+ *   apart; scales: the first point's f32 scale, the next scale_stride_f32 floats on (1: CurvatureSampler's scale-factor
+ *   buffer; 4 with scales = curvature + 3 floats: the .w of the vec4(normal, scale) buffer splat_sdf_generate writes);
+ *   outputs, each W*H and each optional (NULL = not written): out_rgba8 (rgba8unorm), out_rgba32f (vec4 f32), out_depth_f32
+ *   (z/w of the visible fragment, 1.0 where none), out_ids (u32 index of the visible point, 0xFFFFFFFF where none).
+ * The binner must have tile size 16 and serve this frame only: it bins every frame in index order, and the per-point
+ * records the frame builds live in it.  Everything runs on the ctx stream; one host round trip per frame (the binner's
+ * pair total is read back: no frame ever needs to be rendered again). */
+int splat_point_frame(splat_ctx *ctx, splat_binner *binner, const float *uniforms, const void *positions, uint32_t pos_stride_vec4,
+                      const void *gradients, uint32_t grad_stride_vec4, const void *scales, uint32_t scale_stride_f32, uint32_t n,
+                      uint32_t width, uint32_t height, void *out_rgba8, void *out_rgba32f, void *out_depth_f32, void *out_ids);
+
 /* ---- the multi-GPU frame's one exchange (no reference equivalent): RCCL over xGMI ------------------
  * One process per GPU.  Rank 0 makes a unique id (splat_comm_unique_id) and hands its SPLAT_COMM_ID_BYTES to the
  * other ranks by any channel the host has (a file, a socket, MPI, torch.distributed.broadcast); every rank then

@@ -630,6 +630,7 @@ void splat_bin_destroy(splat_binner *b) {
     binner_free_wide(b);
     if (b->expanded) (void)hipFree(b->expanded);
     if (b->discs) (void)hipFree(b->discs);
+    if (b->points) (void)hipFree(b->points);
     if (b->band_idx) (void)hipFree(b->band_idx);
     if (b->pinned) (void)hipHostFree(b->pinned);
     if (b->readback_done) (void)hipEventDestroy(b->readback_done);

@@ -180,6 +180,8 @@ struct splat_binner {
     uint32_t expanded_cap = 0;
     void *discs = nullptr;                          // frame path, oriented-disc footprint: the projector's 32-byte disc records
     uint32_t discs_cap = 0;
+    void *points = nullptr;                         // splat_point_frame: per point its ProjectedSplat, raster record, colour, index
+    uint32_t points_cap = 0;
     bool tf_hist_ready = false;                     // the projector already filled tf_hist / blocksums for the next tile-first run
     uint32_t tf_block = 1024;                       // splats per block of that histogram (TF_BLOCK_SMALL for small frames)
     // a multi-GPU band frame whose prepare pass compacted the kept splats per group of 4096 records (k_band_prepare_tfc): their

@@ -17,7 +17,7 @@ import zlib
 import numpy as np
 
 from .camera import Camera
-from .host import Renderer
+from .host import PointRenderer, Renderer
 
 
 class MouseEvent:
@@ -152,6 +152,7 @@ class SdfSplatSource:
         self.curvatureSampler = CurvatureSampler(device, scene, n)
         self.positionUpdater = PositionUpdater(device, None, n)
         self.properties = SplatPropertyManager(device, n)
+        self._fused = None  # the producer mode of the last step()
 
     def step(self, reinitialize=True, fused=True):
         """One frame's splats.  fused=True (default): splat_sdf_generate, the whole producer in one launch; False: the
@@ -159,6 +160,7 @@ class SdfSplatSource:
         pm, gs, cs = self.pointManager, self.gradientSampler, self.curvatureSampler
         gs.updateSceneParameters()  # :119-120 (the caller may have animated the primitives)
         cs.updateSceneParameters()
+        self._fused = fused
         if fused:
             return self._step_fused(reinitialize)
         if reinitialize:
@@ -196,6 +198,18 @@ class SdfSplatSource:
         pm.swap()  # (five swaps in the staged form: the same buffer ends up current)
         return self.properties.getPropertyBuffer(), cs.curvatureBuffer
 
+    def getPointBuffers(self):
+        """What main.ts:183-190 hands to its Renderer after step(): (positionBuffer, gradientBuffer, scaleFactorsBuffer,
+        scaleStride) for PointRenderer.render / FrameLoop.renderPoints.  The gradients are those of the last evaluation;
+        the scales are CurvatureSampler's buffer after a staged step (stride 1), the .w of the vec4(normal, scale) buffer
+        after a fused one (stride 4): the same values either way."""
+        if self._fused is None:
+            raise RuntimeError("step() has not run")
+        pos, grad = self.pointManager.getCurrentPositionBuffer(), self.gradientSampler.getGradientBuffer()
+        if self._fused:
+            return pos, grad, self.curvatureSampler.curvatureBuffer, 4
+        return pos, grad, self.curvatureSampler.getScaleFactorsBuffer(), 1
+
     def destroy(self):
         for o in (self.pointManager, self.gradientSampler, self.curvatureSampler, self.properties):
             o.destroy()
@@ -210,6 +224,9 @@ class FrameLoop:
         self.camera = camera if camera is not None else Camera()
         self.camera.setAspect(width / height)  # resizeCanvas, main.ts:97-101
         self.renderer = Renderer(device, None, "rgba8unorm", numPoints, tileSize, **renderer_options)
+        self.pointRenderer = None  # made by the first renderPoints()
+        self.numPoints = numPoints
+        self._drawn = self.renderer  # what readPixels reads: the renderer of the last frame
         self.frame = 0
 
     def render(self, propertyBuffer, normalsBuffer, time=None):
@@ -218,10 +235,23 @@ class FrameLoop:
         out = self.renderer.render(self.camera.uniforms(self.width, self.height, time=t), propertyBuffer, normalsBuffer, None,
                                    self.width, self.height)
         self.frame += 1
+        self._drawn = self.renderer
+        return out
+
+    def renderPoints(self, positionBuffer, gradientBuffer, scaleFactorsBuffer, scaleStride=1, time=None):
+        """One frame of what main.ts:183-190 draws — its Renderer's opaque depth-tested quads (PointRenderer) — with the
+        camera as it stands; returns the output buffer.  SdfSplatSource.getPointBuffers() gives the four arguments."""
+        if self.pointRenderer is None:
+            self.pointRenderer = PointRenderer(self.device, None, "rgba8unorm", self.numPoints)
+        t = self.frame / 60.0 if time is None else time
+        out = self.pointRenderer.render(self.camera.uniforms(self.width, self.height, time=t), positionBuffer, gradientBuffer,
+                                        scaleFactorsBuffer, self.width, self.height, scaleStride=scaleStride)
+        self.frame += 1
+        self._drawn = self.pointRenderer
         return out
 
     def readPixels(self):
-        return self.renderer.readPixels()
+        return self._drawn.readPixels()
 
     def turntable(self, propertyBuffer, normalsBuffer, frames, on_frame=None):
         """`frames` frames of a full orbit (Camera.rotate by 2 pi / frames after each); on_frame(k, rgba8) gets every
@@ -234,3 +264,5 @@ class FrameLoop:
 
     def destroy(self):
         self.renderer.destroy()
+        if self.pointRenderer is not None:
+            self.pointRenderer.destroy()

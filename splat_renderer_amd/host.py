@@ -876,6 +876,81 @@ class Renderer:
             self.outputFloat.destroy()
 
 
+class PointRenderer:
+    """src/Renderer.ts — what the reference app draws (src/main.ts:183-190): one opaque quad per point in the tangent plane
+    of its SDF gradient, 0.025 * scale a half-side, through a depth test, shaded from the normal, on (0.05, 0.05, 0.1).
+    render() takes the reference's arguments; with scaleStride=k point i's scale is the last of the k floats of record i
+    (k=4: the .w of the vec4(normal, scale) buffer splat_sdf_generate writes).  The frame is splat_point_frame (include/splat.h): quad setup, a binner of this
+    renderer's own in index order, and a per-pixel nearest-fragment resolve.  Besides the image it leaves a depth buffer
+    (z/w, 1.0 where empty) and a point-id buffer (0xFFFFFFFF where empty) for picking and compositing.  It never touches
+    Device.lastProjector / lastBinner: no TileRenderer can pair with its lists."""
+
+    EMPTY = U32_MAX
+
+    def __init__(self, device, context=None, presentationFormat="rgba8unorm", numPoints=0):
+        self.device, self.numPoints = device, numPoints
+        p = C.c_void_p()
+        check(device.lib.splat_bin_create(device.ctx, 16, C.byref(p)), device.ctx)
+        self._b = p.value
+        self.output = self.outputFloat = self.depthBuffer = self.idBuffer = None
+        self._wh = (0, 0)
+
+    def _ensureOutputs(self, width, height, wantFloat):  # as Renderer.ts:ensureDepthTexture
+        d = self.device
+        if self._wh != (width, height):
+            for b in (self.output, self.outputFloat, self.depthBuffer, self.idBuffer):
+                if b:
+                    b.destroy()
+            self.outputFloat = None
+            self.output = d.createBuffer(width * height * 4)
+            self.depthBuffer = d.createBuffer(width * height * 4)
+            self.idBuffer = d.createBuffer(width * height * 4)
+            self._wh = (width, height)
+        if wantFloat and self.outputFloat is None:
+            self.outputFloat = d.createBuffer(width * height * 16)
+
+    def render(self, uniformBuffer, positionBuffer, gradientBuffer, scaleFactorsBuffer, width, height, wantFloat=False,
+               scaleStride=1):  # Renderer.ts:250-311
+        d = self.device
+        u = _uniform_floats(uniformBuffer)
+        if u.shape[0] < 16:
+            raise SplatError(-1, "the uniform block needs the 16 floats of the view-projection matrix")
+        if scaleStride < 1:
+            raise SplatError(-1, "scaleStride must be at least 1")
+        self._ensureOutputs(width, height, wantFloat)
+        check(d.lib.splat_point_frame(d.ctx, self._b, u.ctypes.data_as(C.POINTER(C.c_float)), positionBuffer.ptr, 1,
+                                      gradientBuffer.ptr, 1, scaleFactorsBuffer.ptr + 4 * (int(scaleStride) - 1), int(scaleStride),
+                                      self.numPoints, width, height,
+                                      self.output.ptr, self.outputFloat.ptr if wantFloat else None, self.depthBuffer.ptr,
+                                      self.idBuffer.ptr), d.ctx)
+        return self.output
+
+    def readPixels(self):
+        w, h = self._wh
+        return self.output.read(np.uint8).reshape(h, w, 4)
+
+    def readPixelsFloat(self):
+        w, h = self._wh
+        return self.outputFloat.read(np.float32).reshape(h, w, 4)
+
+    def readDepth(self):
+        w, h = self._wh
+        return self.depthBuffer.read(np.float32).reshape(h, w)
+
+    def readIds(self):
+        w, h = self._wh
+        return self.idBuffer.read(np.uint32).reshape(h, w)
+
+    def destroy(self):
+        for b in (self.output, self.outputFloat, self.depthBuffer, self.idBuffer):
+            if b:
+                b.destroy()
+        self.output = self.outputFloat = self.depthBuffer = self.idBuffer = None
+        if self._b:
+            self.device.lib.splat_bin_destroy(self._b)
+            self._b = None
+
+
 class PipelinedRenderer:
     """`depth` frames in flight: frame k is enqueued on stream k % depth (one splat ctx, sorter, binner and record
     buffer per stream), so the device overlaps one frame's latency-bound kernels (per-tile sort, composite prologues)

@@ -68,8 +68,12 @@ export class FrameLoop {
               rendererOptions?: { footprint?: Footprint; records?: "lit" | "lit-always" | "projected" });
   readonly camera: Camera;
   readonly renderer: Renderer;
+  readonly pointRenderer: PointRenderer | null;
   frame: number;
   render(propertyBuffer: Buffer | PropertyPlanes, normalsBuffer: Buffer, time?: number): Buffer;
+  /** One frame of src/main.ts:183-190's own renderer (PointRenderer) with the camera as it stands. */
+  renderPoints(positionBuffer: Buffer, gradientBuffer: Buffer, scaleFactorsBuffer: Buffer, scaleStride?: number, time?: number): Buffer;
+  /** The pixels of the last frame, whichever renderer drew it. */
   readPixels(): Uint8Array;
   turntable(propertyBuffer: Buffer | PropertyPlanes, normalsBuffer: Buffer, frames: number, onFrame?: (k: number, rgba8: Uint8Array) => void): void;
   destroy(): void;
@@ -253,6 +257,20 @@ export class Renderer {
   render(uniformData: Float32Array | Buffer, propertyBuffer: Buffer | PropertyPlanes, normalsBuffer: Buffer, scaleFactorsBuffer: Buffer | null, width: number, height: number): Buffer;
   finish(): number;
   readPixels(): Uint8Array;
+  destroy(): void;
+}
+/** src/Renderer.ts as the reference app draws it: opaque depth-tested quads in the tangent plane of each point's SDF gradient.
+ *  scaleStride k: point i's scale is the last of the k floats of record i (4: the .w of a vec4(normal, scale) buffer). */
+export class PointRenderer {
+  constructor(device: Device, context?: unknown, presentationFormat?: string, numPoints?: number);
+  render(uniformBuffer: Float32Array | Buffer, positionBuffer: Buffer, gradientBuffer: Buffer, scaleFactorsBuffer: Buffer, width: number, height: number,
+         wantFloat?: boolean, scaleStride?: number): Buffer;
+  readPixels(): Uint8Array;
+  readPixelsFloat(): Float32Array;
+  /** z/w of the visible fragment, 1.0 where none */
+  readDepth(): Float32Array;
+  /** index of the visible point, 0xFFFFFFFF where none */
+  readIds(): Uint32Array;
   destroy(): void;
 }
 export const MODE_FRONT_TO_BACK: 0; export const MODE_REFERENCE_LITERAL: 1;

@@ -615,6 +615,65 @@ class Renderer {
   }
 }
 
+/** src/Renderer.ts — what the reference app draws (src/main.ts:183-190): one opaque quad per point in the tangent plane of its
+ * SDF gradient, 0.025 * scale a half-side, through a depth test, shaded from the normal, on (0.05, 0.05, 0.1).  render() takes
+ * the reference's arguments; with scaleStride k point i's scale is the last of the k floats of record i (4: the .w of the
+ * vec4(normal, scale) buffer splat_sdf_generate writes).  One splat_point_frame call per frame, with a binner of this
+ * renderer's own; besides the image it leaves a depth buffer (z/w, 1.0 where empty) and a point-id buffer (0xFFFFFFFF where
+ * empty).  It never touches Device.lastProjector / lastBinner.  host.py PointRenderer. */
+class PointRenderer {
+  declare device: Device;
+  declare numPoints: number;
+  declare handle: unknown;
+  declare output: Buffer_ | null;
+  declare outputFloat: Buffer_ | null;
+  declare depthBuffer: Buffer_ | null;
+  declare idBuffer: Buffer_ | null;
+  declare width: number;
+  declare height: number;
+  constructor(device: Device, context: unknown = null, presentationFormat: string = 'rgba8unorm', numPoints: number = 0) {
+    this.device = device;
+    this.numPoints = numPoints;
+    this.handle = native.bin_create(device.ctx, 16);
+    this.output = null;
+    this.outputFloat = null;
+    this.depthBuffer = null;
+    this.idBuffer = null;
+    this.width = 0;
+    this.height = 0;
+  }
+  render(uniformBuffer: Float32Array | Buffer_, positionBuffer: Buffer_, gradientBuffer: Buffer_, scaleFactorsBuffer: Buffer_, width: number, height: number, wantFloat: boolean = false, scaleStride: number = 1): Buffer_ { // :250-311
+    const u = uniformFloats(uniformBuffer);
+    if (!(scaleStride >= 1)) throw new Error('scaleStride must be at least 1');
+    if (this.width !== width || this.height !== height) { // as ensureDepthTexture
+      for (const b of [this.output, this.outputFloat, this.depthBuffer, this.idBuffer]) if (b) b.destroy();
+      this.outputFloat = null;
+      this.output = this.device.createBuffer(width * height * 4);
+      this.depthBuffer = this.device.createBuffer(width * height * 4);
+      this.idBuffer = this.device.createBuffer(width * height * 4);
+      this.width = width;
+      this.height = height;
+    }
+    if (wantFloat && !this.outputFloat) this.outputFloat = this.device.createBuffer(width * height * 16);
+    native.point_frame(this.device.ctx, this.handle, u, positionBuffer.ptr, 1, gradientBuffer.ptr, 1, scaleFactorsBuffer.ptr + 4 * (scaleStride - 1),
+      scaleStride, this.numPoints, width, height, this.output.ptr, wantFloat ? this.outputFloat.ptr : null, this.depthBuffer.ptr, this.idBuffer.ptr);
+    return this.output;
+  }
+  readPixels(): Uint8Array { return this.output.read(new Uint8Array(this.width * this.height * 4)); }
+  readPixelsFloat(): Float32Array { return this.outputFloat.read(new Float32Array(this.width * this.height * 4)); }
+  readDepth(): Float32Array { return this.depthBuffer.read(new Float32Array(this.width * this.height)); }
+  readIds(): Uint32Array { return this.idBuffer.read(new Uint32Array(this.width * this.height)); }
+  destroy(): void {
+    for (const b of [this.output, this.outputFloat, this.depthBuffer, this.idBuffer]) if (b) b.destroy();
+    this.output = null;
+    this.outputFloat = null;
+    this.depthBuffer = null;
+    this.idBuffer = null;
+    if (this.handle) native.bin_destroy(this.handle);
+    this.handle = null;
+  }
+}
+
 /** src/Camera.ts:3-139 with gl-matrix 3.4.4 semantics (Float32Array stores, f64 arithmetic) */
 class Camera {
   declare target: Float32Array;
@@ -1119,6 +1178,9 @@ class FrameLoop {
   declare height: number;
   declare camera: Camera;
   declare renderer: Renderer;
+  declare pointRenderer: PointRenderer | null;
+  declare numPoints: number;
+  declare drawn: Renderer | PointRenderer;
   declare frame: number;
   constructor(device: Device, numPoints: number, width: number, height: number, tileSize: number = 16, camera: Camera | null = null, rendererOptions: { footprint?: Footprint; records?: "lit" | "lit-always" | "projected" } = {}) {
     this.device = device;
@@ -1127,6 +1189,9 @@ class FrameLoop {
     this.camera = camera || new Camera();
     this.camera.setAspect(width / height); // resizeCanvas, main.ts:97-101
     this.renderer = new Renderer(device, null, 'rgba8unorm', numPoints, tileSize, rendererOptions);
+    this.pointRenderer = null; // made by the first renderPoints()
+    this.numPoints = numPoints;
+    this.drawn = this.renderer; // what readPixels reads: the renderer of the last frame
     this.frame = 0;
   }
   // one frame with the camera as it stands; returns the output buffer (pixels stay on the device)
@@ -1134,9 +1199,20 @@ class FrameLoop {
     const t = time === undefined ? this.frame / 60.0 : time;
     const out = this.renderer.render(this.camera.uniforms(this.width, this.height, t), propertyBuffer, normalsBuffer, null, this.width, this.height);
     this.frame += 1;
+    this.drawn = this.renderer;
     return out;
   }
-  readPixels(): Uint8Array { return this.renderer.readPixels(); }
+  // one frame of what main.ts:183-190 draws — its Renderer's opaque depth-tested quads (PointRenderer) — with the camera as it stands
+  renderPoints(positionBuffer: Buffer_, gradientBuffer: Buffer_, scaleFactorsBuffer: Buffer_, scaleStride: number = 1, time?: number): Buffer_ {
+    if (!this.pointRenderer) this.pointRenderer = new PointRenderer(this.device, null, 'rgba8unorm', this.numPoints);
+    const t = time === undefined ? this.frame / 60.0 : time;
+    const out = this.pointRenderer.render(this.camera.uniforms(this.width, this.height, t), positionBuffer, gradientBuffer, scaleFactorsBuffer,
+      this.width, this.height, false, scaleStride);
+    this.frame += 1;
+    this.drawn = this.pointRenderer;
+    return out;
+  }
+  readPixels(): Uint8Array { return this.drawn.readPixels(); }
   // `frames` frames of a full orbit (Camera.rotate by 2 pi / frames after each); onFrame(k, rgba8) gets every frame's pixels
   turntable(propertyBuffer: Buffer_ | PropertyPlanes, normalsBuffer: Buffer_, frames: number, onFrame?: (k: number, rgba8: Uint8Array) => void): void {
     for (let k = 0; k < frames; k++) {
@@ -1145,7 +1221,10 @@ class FrameLoop {
       this.camera.rotate((2.0 * Math.PI) / frames, 0.0);
     }
   }
-  destroy(): void { this.renderer.destroy(); }
+  destroy(): void {
+    this.renderer.destroy();
+    if (this.pointRenderer) this.pointRenderer.destroy();
+  }
 }
 
 /** The multi-GPU frame's exchange (no reference counterpart: the reference is single-device): one process per GPU, an
@@ -1240,5 +1319,5 @@ class BandRenderer {
 
 module.exports = { native, Device, Buffer: Buffer_, Camera, OrbitCameraController, FrameLoop, PointManager, scaleAABB, Comm, BandRenderer, SDFScene, Sphere, Box, Torus, Capsule, SmoothUnion,
   union, intersection, subtraction, smoothUnion, GradientSampler, PositionUpdater, CurvatureSampler, SplatPropertyManager, SplatProjector, DepthKeyExtractor, RadixSorter, PrefixSumScanner,
-  GPUTileBinner, PerTileSorter, ComputeShaderRenderer, TileRenderer, SequentialRenderer, Renderer, MODE_FRONT_TO_BACK, MODE_REFERENCE_LITERAL,
+  GPUTileBinner, PerTileSorter, ComputeShaderRenderer, TileRenderer, SequentialRenderer, Renderer, PointRenderer, MODE_FRONT_TO_BACK, MODE_REFERENCE_LITERAL,
   FOOTPRINT_ISOTROPIC, FOOTPRINT_DISC, RECORDS_PROJECTED, RECORDS_COMPACT, RECORDS_LIT32 };

@@ -368,6 +368,16 @@ FN(sdf_generate) { /* (ctx, program, boxMin | null, boxMax | null, seed, positio
     return check(env, x, splat_sdf_generate(x, prog, cnt, mn, mx, (uint64_t)seed, pin, n, steps, pout, gout, cout, props), mk_undefined(env));
 }
 
+FN(point_frame) { /* (ctx, binner, Float32Array(22), positions, posStride, gradients, gradStride, scales, scaleStride, n, W, H, out8|null, outF|null, depth|null, ids|null) */
+    ARGS(16); splat_ctx *x = arg_external(&c, 0); splat_binner *b = arg_external(&c, 1); size_t ub = 0; float *u = arg_hostbuf(&c, 2, &ub);
+    void *pos = arg_dptr(&c, 3); uint32_t ps = (uint32_t)arg_number(&c, 4); void *g = arg_dptr(&c, 5); uint32_t gs = (uint32_t)arg_number(&c, 6);
+    void *sc = arg_dptr(&c, 7); uint32_t ss = (uint32_t)arg_number(&c, 8), n = (uint32_t)arg_number(&c, 9);
+    uint32_t w = (uint32_t)arg_number(&c, 10), h = (uint32_t)arg_number(&c, 11);
+    void *o8 = arg_dptr(&c, 12), *of = arg_dptr(&c, 13), *od = arg_dptr(&c, 14), *oi = arg_dptr(&c, 15); BAIL;
+    if (ub < 16 * sizeof(float)) { napi_throw_range_error(env, NULL, "uniform block needs the 16 floats of the view-projection matrix"); return NULL; }
+    return check(env, x, splat_point_frame(x, b, u, pos, ps, g, gs, sc, ss, n, w, h, o8, of, od, oi), mk_undefined(env));
+}
+
 /* ---- multi-GPU band path (include/splat.h: "multi-GPU band path", "the multi-GPU frame's one exchange") ---- */
 FN(project_slice_compact) { /* (ctx, Float32Array(22), posRadius, strideVec4, first, count, records16) */
     ARGS(7); splat_ctx *x = arg_external(&c, 0); size_t ub = 0; float *u = arg_hostbuf(&c, 1, &ub);
@@ -533,6 +543,7 @@ static napi_value init(napi_env env, napi_value exports) {
         EXPORT(composite_forget_history), EXPORT(composite_options), EXPORT(bin_dims), EXPORT(bin_tile_size), EXPORT(project_slice),
         EXPORT(project_slice_disc), EXPORT(expand_compact), EXPORT(band_keys), EXPORT(band_kept), EXPORT(comm_rank), EXPORT(comm_count),
         EXPORT(allgather_records), EXPORT(sdf_gradients), EXPORT(sdf_update_positions), EXPORT(sdf_scale_factors), EXPORT(sdf_curvature), EXPORT(sdf_seed_positions), EXPORT(sdf_generate),
+        EXPORT(point_frame),
     };
     napi_define_properties(env, exports, sizeof d / sizeof d[0], d);
     return exports;
