@@ -334,6 +334,39 @@ int splat_composite(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *
                     const void *tile_offsets, uint32_t width, uint32_t height, void *out_rgba8,
                     void *out_rgba32f, void *consumed_dptr);
 
+/* ---- auxiliary outputs of a Gaussian frame: alpha, depth and splat id beside the image ----------------------------
+ * Nearest-on-top frames only (SPLAT_COMPOSITE_FRONT_TO_BACK).  Per pixel, over the list entries the pixel consumes (those
+ * after its early-out stop contribute nothing): T_i = the transmittance before entry i, g_i = its footprint value (the
+ * isotropic Gaussian or the oriented disc's), w_i = T_i g_i — the product the colour uses.  Each buffer is W*H elements,
+ * full frame, 16-byte aligned, and may be NULL (not written); at least one must be non-NULL.  Only pixels of the rendered
+ * tile rows are written, as for the image.
+ *   alpha_f32  1 - T_end, T_end the transmittance the background term is multiplied by: rgb = C + bg (1 - alpha).  0 where
+ *              nothing contributed.
+ *   depth_f32  sum w_i z_i / sum w_i, z_i the splat's ProjectedSplat depth (distance from the camera to its centre,
+ *              src/SplatProjector.ts:77; the depth the sort orders by), for both footprints.  +inf where sum w_i = 0.
+ *   id_u32     the splat index (the list entry's value) of the entry with the largest w_i; on equal w the earlier entry, the
+ *              nearer one, wins.  0xFFFFFFFF where nothing contributed.
+ * The image of a call with buffers is bit for bit the image of the same call without them (same kernel, same schedule), and
+ * rgba32f's alpha channel stays 1.0.  SPLAT_ERR_INVALID: all three NULL, a misaligned buffer, SPLAT_COMPOSITE_REFERENCE_LITERAL
+ * (an entry's final weight there is not known until its list ends), or depth asked of records that do not carry it:
+ *   - splat_composite_aov with SPLAT_FOOTPRINT_DISC and SPLAT_RECORDS_PROJECTED (the projector's 32-byte disc records; the
+ *     48-byte SPLAT_RECORDS_DISC48 exchange records carry the depth);
+ *   - a disc frame (splat_render_frame*_aov, SPLAT_FOOTPRINT_DISC) with SPLAT_RECORDS_PROJECTED and projected == NULL (with
+ *     `projected` the frame writes ProjectedSplat records and the depth is read there; with SPLAT_RECORDS_LIT32 the frame's
+ *     lit disc records carry it).
+ * Every other record format (PROJECTED, COMPACT, LIT32 isotropic; DISC48 and lit disc records) carries the depth. */
+typedef struct splat_aov {
+    void *depth_f32;
+    void *alpha_f32;
+    void *id_u32;
+} splat_aov;
+/* splat_composite plus the auxiliary outputs (aov == NULL: splat_composite itself) */
+int splat_composite_aov(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity,
+                        uint32_t color_stride_vec4, const void *normals, uint32_t normal_stride_vec4,
+                        const void *projected, const void *tile_indices, const void *tile_counts,
+                        const void *tile_offsets, uint32_t width, uint32_t height, void *out_rgba8,
+                        void *out_rgba32f, void *consumed_dptr, const splat_aov *aov);
+
 /* ---- whole frame: project -> keys -> sort -> bin -> composite ----------------
  * With cfg->tile_row0/1 set to a strict band of tile rows (multi-GPU, no exchange: every rank renders its band from
  * its own copy of the splats) only that band's pixels, lists and counts are produced, and `projected` holds records
@@ -354,6 +387,18 @@ int splat_render_frame_planes(splat_ctx *ctx, splat_sorter *sorter, splat_binner
                               const void *pos_radius, const void *color_opacity, const void *normals,
                               uint32_t n, uint32_t width, uint32_t height, void *projected,
                               void *out_rgba8, void *out_rgba32f);
+/* The two frames plus the auxiliary outputs (splat_aov above; aov == NULL: the frame itself).  Every route a frame takes
+ * writes them: either frame order, screens beyond 256 x 256 tiles, strict bands; a frame rendered again after
+ * SPLAT_ERR_CAPACITY / SPLAT_ERR_RETRY rewrites them with its image. */
+int splat_render_frame_aov(splat_ctx *ctx, splat_sorter *sorter, splat_binner *binner,
+                           const splat_composite_cfg *cfg, const float *uniforms, const void *props,
+                           const void *normals, uint32_t n, uint32_t width, uint32_t height,
+                           void *projected, void *out_rgba8, void *out_rgba32f, const splat_aov *aov);
+int splat_render_frame_planes_aov(splat_ctx *ctx, splat_sorter *sorter, splat_binner *binner,
+                                  const splat_composite_cfg *cfg, const float *uniforms,
+                                  const void *pos_radius, const void *color_opacity, const void *normals,
+                                  uint32_t n, uint32_t width, uint32_t height, void *projected,
+                                  void *out_rgba8, void *out_rgba32f, const splat_aov *aov);
 
 /* ---- multi-GPU band path (no reference equivalent — the reference is single-device) */
 /* The oriented-disc projector (src/SequentialRenderer.ts:68-71,91-112): the splat is the disc

@@ -39,6 +39,11 @@ class SdfInstr(C.Structure):
     _fields_ = [("op", C.c_uint32), ("a", C.c_float * 7)]
 
 
+class Aov(C.Structure):
+    """splat_aov: the auxiliary outputs of a Gaussian frame (device pointers; 0 = not written)."""
+    _fields_ = [("depth_f32", C.c_void_p), ("alpha_f32", C.c_void_p), ("id_u32", C.c_void_p)]
+
+
 class CompositeCfg(C.Structure):
     _fields_ = [("mode", C.c_uint32), ("early_out", C.c_uint32), ("tile_size", C.c_uint32),
                 ("tile_row0", C.c_uint32), ("tile_row1", C.c_uint32), ("record_format", C.c_uint32),
@@ -106,6 +111,12 @@ SIGNATURES = {
                                 _u32, _vp, _vp, _vp]),
     "splat_render_frame_planes": (_i, [_vp, _vp, _vp, C.POINTER(CompositeCfg), C.POINTER(C.c_float), _vp, _vp, _vp, _u32,
                                        _u32, _u32, _vp, _vp, _vp]),
+    "splat_composite_aov": (_i, [_vp, C.POINTER(CompositeCfg), _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32,
+                                 _vp, _vp, _vp, C.POINTER(Aov)]),
+    "splat_render_frame_aov": (_i, [_vp, _vp, _vp, C.POINTER(CompositeCfg), C.POINTER(C.c_float), _vp, _vp, _u32, _u32,
+                                    _u32, _vp, _vp, _vp, C.POINTER(Aov)]),
+    "splat_render_frame_planes_aov": (_i, [_vp, _vp, _vp, C.POINTER(CompositeCfg), C.POINTER(C.c_float), _vp, _vp, _vp,
+                                           _u32, _u32, _u32, _vp, _vp, _vp, C.POINTER(Aov)]),
     "splat_project_slice": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _u32, _u32, _vp]),
     "splat_project_slice_compact": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _u32, _u32, _vp]),
     "splat_project_slice_disc": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _vp, _u32, _u32, _u32, _vp]),

@@ -302,7 +302,11 @@ int binner_settle(splat_binner *b); // resolves a pending report; SPLAT_ERR_CAPA
 int composite_launch(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4, const void *normals,
                      uint32_t normal_stride_vec4, const void *projected, const void *tile_indices, const void *tile_counts,
                      const void *tile_offsets, uint32_t width, uint32_t height, void *out_rgba8, void *out_rgba32f, void *consumed_dptr,
-                     const uint32_t *frame_total, uint32_t *report, uint32_t report_seq);
+                     const uint32_t *frame_total, uint32_t *report, uint32_t report_seq, const splat_aov *aov = nullptr,
+                     const void *disc_depth = nullptr);
+// The checks of a splat_aov request (aov == NULL: none) a frame makes before its first launch and the composite again:
+// a non-NULL buffer, 16-byte alignment, nearest on top, and for depth, records that carry it (has_depth).
+int aov_check(splat_ctx *ctx, const splat_composite_cfg *cfg, const splat_aov *aov, bool has_depth);
 // project.hip internal: the projector with the optional per-index tile range output
 int project_launch(splat_ctx *ctx, const float *uniforms, const void *pos_radius, uint32_t pr_stride_vec4, uint32_t n,
                    uint32_t index_base, void *projected, void *keys, void *payload, uint32_t n_padded, uint32_t *range32,

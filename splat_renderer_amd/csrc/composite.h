@@ -39,7 +39,41 @@ struct CompositeParams {
 #ifdef PX_PROFILE
     uint32_t debug_cap;         // (measuring build only, SPLAT_PX_CAP: every list cut after this many entries — a WRONG image: what do the long tiles cost?)
 #endif
+    // auxiliary outputs (splat_aov; read only by the AOV instantiations, which write each non-NULL one per rendered pixel)
+    float *aov_depth;
+    float *aov_alpha;
+    uint32_t *aov_id;
+    const float *aov_z;         // the depth of splat i is aov_z[i * aov_zstride] (NULL: the records carry none; depth not asked for)
+    uint32_t aov_zstride;
 };
+
+// Per pixel of a one-pixel-per-lane composite (k_composite, k_composite_tile): what the auxiliary outputs need beside the
+// colour — sum w z, sum w, and the largest w with its splat index (strictly larger: on equal weights the earlier, nearer
+// entry keeps the pixel).  w is the colour's own T g, after the coverage / stop masking.
+struct AovPixel {
+    float zw = 0.0f, ws = 0.0f, wmax = 0.0f;
+    uint32_t id = 0xffffffffu;
+    __device__ __forceinline__ void add(float w, float2 zi) {
+        zw += zi.x * w;
+        ws += w;
+        const bool top = w > wmax;
+        wmax = top ? w : wmax;
+        id = top ? __float_as_uint(zi.y) : id;
+    }
+    // alpha = 1 - T_end; depth = sum w z / sum w (+inf where nothing contributed); id 0xffffffff where nothing did
+    __device__ __forceinline__ void store(const CompositeParams &p, size_t o, float T_end) const {
+        if (p.aov_alpha) p.aov_alpha[o] = 1.0f - T_end;
+        if (p.aov_depth) p.aov_depth[o] = ws > 0.0f ? zw / ws : __builtin_inff();
+        if (p.aov_id) p.aov_id[o] = id;
+    }
+};
+
+// {depth, splat index (as bits)} of a staged entry for the AOV instantiations (idx = 0xffffffff: no entry)
+__device__ __forceinline__ float2 aov_entry(const CompositeParams &p, uint32_t idx) {
+    if (idx == 0xffffffffu) return make_float2(0.0f, __uint_as_float(0xffffffffu));
+    const float z = p.aov_z ? p.aov_z[(size_t)idx * p.aov_zstride] : 0.0f;
+    return make_float2(z, __uint_as_float(idx));
+}
 
 __device__ __forceinline__ uint32_t unorm8(float v) {
     v = fminf(fmaxf(v, 0.0f), 1.0f); // fmaxf(NaN,0) = 0

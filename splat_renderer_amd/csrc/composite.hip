@@ -38,7 +38,9 @@ __global__ __launch_bounds__(256) void k_lit_colors(const float4 *__restrict__ c
     if (i < n) lit[i] = lit_color(color[(size_t)i * color_stride], normals[(size_t)i * normal_stride]);
 }
 
-template <int MODE, bool EARLY_OUT, bool DISC, bool LIT32>
+// AOV: also the auxiliary outputs (splat_aov; nearest-on-top only): per staged entry {depth, splat index} beside its
+// parameters, per pixel an AovPixel fed with the colour's own weight
+template <int MODE, bool EARLY_OUT, bool DISC, bool LIT32, bool AOV = false>
 __global__ __launch_bounds__(256) void k_composite(CompositeParams p) {
     // per entry one 32-byte record {centre.x, centre.y, exp2 scale, lit blue | lit red, lit green, -, -}: both
     // halves are read off ONE address register (ds_read_b128 + ds_read_b64 offset:16), and forming an LDS
@@ -50,6 +52,9 @@ __global__ __launch_bounds__(256) void k_composite(CompositeParams p) {
     __shared__ uint2 s_mask[4][CBATCH];  // per quadrant: which of its 64 pixels the entry's box covers
     __shared__ uint32_t s_wave_done[4];
     __shared__ uint32_t s_wave_consumed[4];
+    __shared__ float2 s_aov[AOV ? CBATCH : 1]; // AOV: {depth, splat index} per staged entry
+    static_assert(!AOV || MODE == SPLAT_COMPOSITE_FRONT_TO_BACK, "the auxiliary outputs are nearest-on-top only");
+    AovPixel aov;
 
     const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     if (p.report && blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) tile_report(p.frame_total, p.report, p.report_seq);
@@ -84,6 +89,7 @@ __global__ __launch_bounds__(256) void k_composite(CompositeParams p) {
     uint32_t f_idx = 0xffffffffu;              // splat index of the entry this thread stages
     float4 f_b = make_float4(0, 0, 0, 0), f_c = f_b, f_n = f_b, f_b2 = f_b;
     float f_r = 0.0f;
+    float2 f_zi = make_float2(0.0f, 0.0f);     // AOV: {depth, index} of that entry, fetched with it
     bool f_ready = false;                      // f_* already hold this thread's entry of the batch about to be staged
     uint32_t n_idx = 0xffffffffu;              // index of this thread's entry one batch further on (the gathers depend on it)
     bool n_idx_valid = false;
@@ -105,6 +111,7 @@ __global__ __launch_bounds__(256) void k_composite(CompositeParams p) {
             if (!f_ready) { // the first three batches of a tile: fetch now
                 f_idx = (tid < CBATCH && e < count) ? p.indices[off + e] : 0xffffffffu;
                 if (f_idx != 0xffffffffu) fetch_entry<MODE, EARLY_OUT, DISC, LIT32>(p, f_idx, f_b, f_b2, f_c, f_n, f_r);
+                if constexpr (AOV) f_zi = aov_entry(p, f_idx);
             }
             if (DISC && f_idx != 0xffffffffu) {
                 const DiscRecord rec = {f_b, f_b2};
@@ -149,6 +156,7 @@ __global__ __launch_bounds__(256) void k_composite(CompositeParams p) {
                 s_mask[1][tid] = quadrant_mask(xm >> 8, ym & 0xffu);
                 s_mask[2][tid] = quadrant_mask(xm & 0xffu, ym >> 8);
                 s_mask[3][tid] = quadrant_mask(xm >> 8, ym >> 8);
+                if constexpr (AOV) s_aov[tid] = f_zi;
             }
             // issue the fetches for later batches; nothing below waits for them until the next stage
             f_ready = false;
@@ -156,6 +164,7 @@ __global__ __launch_bounds__(256) void k_composite(CompositeParams p) {
                 if (n_idx_valid) { // index of batch k+1 arrived a batch ago: its gathers go out now
                     f_idx = n_idx;
                     if (f_idx != 0xffffffffu) fetch_entry<MODE, EARLY_OUT, DISC, LIT32>(p, f_idx, f_b, f_b2, f_c, f_n, f_r);
+                    if constexpr (AOV) f_zi = aov_entry(p, f_idx);
                     f_ready = true;
                 }
                 const uint32_t e2 = e + 2 * CBATCH; // batch k+2
@@ -236,6 +245,7 @@ __global__ __launch_bounds__(256) void k_composite(CompositeParams p) {
                     cg += C0.y * wgt;
                     cb += B0 * wgt;
                     acc -= wgt; // T * (1 - g), with the product already in hand
+                    if constexpr (AOV) aov.add(wgt, s_aov[c0 + j0]);
                     if (EARLY_OUT) lv &= ~__ballot(acc <= T_STOP);
                 }
                 lv = uniform64(lv);
@@ -254,6 +264,7 @@ __global__ __launch_bounds__(256) void k_composite(CompositeParams p) {
                     cg += C1.y * wgt;
                     cb += B1 * wgt;
                     acc -= wgt;
+                    if constexpr (AOV) aov.add(wgt, s_aov[c0 + j1]);
                     if (EARLY_OUT) lv &= ~__ballot(acc <= T_STOP);
                 }
                 live = lv;
@@ -284,6 +295,7 @@ __global__ __launch_bounds__(256) void k_composite(CompositeParams p) {
         const size_t o = (size_t)py * p.width + px;
         if (p.out_rgba8) p.out_rgba8[o] = unorm8(fr) | (unorm8(fg) << 8) | (unorm8(fb) << 16) | (255u << 24);
         if (p.out_rgba32f) p.out_rgba32f[o] = make_float4(fr, fg, fb, 1.0f);
+        if constexpr (AOV) aov.store(p, o, acc);
     }
 }
 
@@ -317,6 +329,7 @@ struct PxRaw {
     float4 a, c, n;
     float r;
     float4 a2; // DISC: the disc record's second half
+    float2 zi; // AOV: {depth, splat index (as bits)}
 };
 // DISC (the oriented-disc footprint): a, a2 = the 32-byte disc record (disc.h), c = colour, n = normal
 __device__ __forceinline__ void px_fetch_disc(const CompositeParams &p, uint32_t idx, PxRaw &o) {
@@ -523,14 +536,32 @@ __device__ __forceinline__ bool px_any_live(const v2f *T) {
     return m > __float_as_uint(T_STOP);
 }
 
-template <bool EARLY_OUT, bool LIT32, bool COUNT, int AH, bool DISC>
-__global__ __launch_bounds__(128, PX_WAVES) void k_composite_px(CompositeParams p, uint32_t band_tiles) {
+// AOV: also the auxiliary outputs (splat_aov).  The builder leaves {depth, splat index} of each entry of a chunk in s_aov
+// (slot 0: the idle entry), the consumer reads it beside the entry's tables and keeps, per pixel, sum w z, sum w and the
+// largest w with its index — w being the colour's own T g m.
+// AOV, per pixel: the entry with the largest weight so far (strictly larger: on a tie the earlier one stays)
+__device__ __forceinline__ void px_top(v2f w, uint32_t id, v2f &wmax, v2u &idmax) {
+    const bool t0 = w.x > wmax.x, t1 = w.y > wmax.y;
+    wmax = (v2f){t0 ? w.x : wmax.x, t1 ? w.y : wmax.y};
+    idmax = (v2u){t0 ? id : idmax.x, t1 ? id : idmax.y};
+}
+__device__ __forceinline__ void px_aov_store(const CompositeParams &p, size_t o, float T_end, float zw, float ws, uint32_t id) {
+    if (p.aov_alpha) p.aov_alpha[o] = 1.0f - T_end;
+    if (p.aov_depth) p.aov_depth[o] = ws > 0.0f ? zw / ws : __builtin_inff();
+    if (p.aov_id) p.aov_id[o] = id;
+}
+
+template <bool EARLY_OUT, bool LIT32, bool COUNT, int AH, bool DISC, bool AOV = false>
+// (the AOV instantiations' sixteen more accumulators per lane do not fit the register budget of PX_WAVES waves per SIMD
+// without spilling: they are allowed the budget of four)
+__global__ __launch_bounds__(128, AOV ? 4 : PX_WAVES) void k_composite_px(CompositeParams p, uint32_t band_tiles) {
     constexpr uint32_t NB = AH + 1;
     typedef typename PxBufOf<DISC>::type Buf;
     constexpr uint32_t BUF_BYTES = NB * sizeof(Buf) > PX_ORDER_SCRATCH ? NB * sizeof(Buf) : PX_ORDER_SCRATCH;
     __shared__ __attribute__((aligned(16))) char s_raw[BUF_BYTES];
     Buf *const s_buf = reinterpret_cast<Buf *>(s_raw);
     __shared__ uint32_t s_done[2];
+    __shared__ float2 s_aov[AOV ? NB : 1][PXC + 1];
     const uint32_t tid = threadIdx.x, lane = tid & 63;
     const uint32_t role = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6)); // 0 = consumer, 1 = builder (wave-uniform)
     if (blockIdx.x == 0) { // not a tile: the frame's report, and the next launch's tile order
@@ -571,6 +602,9 @@ __global__ __launch_bounds__(128, PX_WAVES) void k_composite_px(CompositeParams 
                 else s_buf[b].col[0] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             }
         }
+        if constexpr (AOV) {
+            if (lane < NB) s_aov[lane][0] = make_float2(0.0f, __uint_as_float(0xffffffffu)); // the idle entry
+        }
         // Entries are fetched two chunks ahead of their build and their indices three (the gather depends on the index).
         // Every load of this pipeline is UNCONDITIONAL — positions past the last one wanted re-read that one (one line for
         // the whole wave) and are ignored — and nothing is computed from a loaded value before its chunk comes up: a load
@@ -582,7 +616,13 @@ __global__ __launch_bounds__(128, PX_WAVES) void k_composite_px(CompositeParams 
         // already and pays a build, not a gather
         uint32_t fetch_lim = min(count, (lim + 1u) * PXC) - 1u;
         uint32_t idx_c = p.indices[off + min(2 * PXC + e, fetch_lim)];
-#define PX_FETCH(IDX, DST) do { if constexpr (DISC) px_fetch_disc(p, IDX, DST); else px_fetch<LIT32>(p, IDX, DST); } while (0)
+// (AOV: the depth as unconditionally as the records — the host points aov_z at a valid word with stride 0 when it is not wanted)
+#define PX_FETCH(IDX, DST)                                                                                 \
+    do {                                                                                                   \
+        const uint32_t i_ = (IDX);                                                                         \
+        if constexpr (DISC) px_fetch_disc(p, i_, DST); else px_fetch<LIT32>(p, i_, DST);                   \
+        if constexpr (AOV) DST.zi = make_float2(p.aov_z[(size_t)i_ * p.aov_zstride], __uint_as_float(i_)); \
+    } while (0)
         PX_FETCH(p.indices[off + min(e, fetch_lim)], ra);
         PX_FETCH(p.indices[off + min(PXC + e, fetch_lim)], rb);
         uint32_t staged = min(2u * PXC, fetch_lim + 1u);
@@ -683,6 +723,9 @@ __global__ __launch_bounds__(128, PX_WAVES) void k_composite_px(CompositeParams 
                 // the lit colour beside the tables ({r, g | b, 1}: the 1 is the factor of T's update, PX_BLEND), a half per lane
                 reinterpret_cast<float2 *>(&B.col[1 + e])[h] = h ? make_float2(colr.z, 1.0f) : make_float2(colr.x, colr.y);
                 }
+                if constexpr (AOV) {
+                    if (h == 0) s_aov[m % NB][1 + e] = ra.zi;
+                }
                 // queue words: one ballot gives X[c] (lanes 0..31 test the x mask) and Y[c] (lanes 32..63 the y mask)
                 const uint32_t mm = m16 | (m16 >> 1);
                 unsigned long long bal[8];
@@ -741,6 +784,8 @@ __global__ __launch_bounds__(128, PX_WAVES) void k_composite_px(CompositeParams 
     // T > T_STOP (:187-190, see T_STOP); pixels outside the image start at 0 and never do
     v2f cr[2] = {{0.0f, 0.0f}, {0.0f, 0.0f}}, cg[2] = {{0.0f, 0.0f}, {0.0f, 0.0f}}, cb[2] = {{0.0f, 0.0f}, {0.0f, 0.0f}};
     v2f T[2] = {{(okx0 && oky0) ? 1.0f : 0.0f, (okx1 && oky0) ? 1.0f : 0.0f}, {(okx0 && oky1) ? 1.0f : 0.0f, (okx1 && oky1) ? 1.0f : 0.0f}};
+    v2f zw[2] = {{0.0f, 0.0f}, {0.0f, 0.0f}}, ws[2] = {{0.0f, 0.0f}, {0.0f, 0.0f}}, wm[2] = {{0.0f, 0.0f}, {0.0f, 0.0f}}; // AOV
+    v2u idm[2] = {{0xffffffffu, 0xffffffffu}, {0xffffffffu, 0xffffffffu}};
     uint32_t stop_pos = 0; // COUNT: list position after the last entry this lane took while one of its pixels still accumulated
     uint32_t walked = 0;   // chunks this tile needed
     constexpr uint32_t NONE = 0xffffffffu;
@@ -800,6 +845,8 @@ __global__ __launch_bounds__(128, PX_WAVES) void k_composite_px(CompositeParams 
             }
             const uint32_t nxt0 = nxt;
             const uint32_t ax0 = o0 + lane_x, ax1 = o1 + lane_x;
+            // AOV: byte offsets of slot 1 of chunk k's and chunk k + 1's {depth, index} rows
+            const uint32_t zi0 = ((k % NB) * (PXC + 1u) + 1u) * 8u, zi1 = (((k + 1u) % NB) * (PXC + 1u) + 1u) * 8u;
             // ---- trips.  Every lane takes its next entry — of chunk k while it has one, then of chunk k + 1, the idle one when
             // both queues are empty: no divergence, an idle lane adds exact zeros; the NEXT entry's table and colour reads are
             // issued before the current one is blended, so a trip costs its arithmetic, not an LDS round trip.
@@ -819,10 +866,12 @@ __global__ __launch_bounds__(128, PX_WAVES) void k_composite_px(CompositeParams 
                the mask is scalar work */                                                        \
             nxt = __builtin_amdgcn_inverse_ballot_w64((R ? R : ~0ull) | ~alive_m) ? nxt : q2_;   \
             A = sel_ ? ax0 : ax1;                                                                \
+            if (AOV) A##_aov = sel_ ? zi0 : zi1;                                                 \
             if (COUNT) S = sel_ ? 0u : (uint32_t)PXC;                                            \
         } else {                                                                                 \
             mine = q2_;                                                                          \
             A = ax0;                                                                             \
+            if (AOV) A##_aov = zi0;                                                              \
         }                                                                                        \
     } while (0)
 #define PX_LOAD(J, A, E)                                                               \
@@ -840,6 +889,7 @@ __global__ __launch_bounds__(128, PX_WAVES) void k_composite_px(CompositeParams 
             E.c0 = make_float2(c_.x, c_.y);                                            \
             E.c1 = make_float2(c_.z, c_.w);                                            \
         }                                                                              \
+        if constexpr (AOV) E.zi = *reinterpret_cast<const float2 *>(reinterpret_cast<const char *>(s_aov) + (A##_aov + (uint32_t)((int)J * 8))); \
     } while (0)
 // The per-pixel stop (:187-190: a pixel that has reached alpha >= 0.99, i.e. T <= T_STOP, takes nothing more) as a FACTOR:
 // m = clamp((T - T_STOP) 2^40, 0, 1) is exactly 1 while T > T_STOP (the smallest positive difference of two binary32 numbers
@@ -907,6 +957,16 @@ __global__ __launch_bounds__(128, PX_WAVES) void k_composite_px(CompositeParams 
             w0 *= m0;                                                                                                         \
             w1 *= m1;                                                                                                         \
         }                                                                                                                     \
+        if constexpr (AOV) { /* sum w z, sum w, the largest w and its index (strictly larger: the earlier entry keeps a tie) */ \
+            /* (C1.y: 1 for an entry, 0 for the idle one — whose disc footprint is 1 at every pixel: w is the colour's weight \
+               only once multiplied by it, exactly) */                                                                        \
+            const v2f e_ = {C1.y, C1.y}, wa0 = w0 * e_, wa1 = w1 * e_;                                                        \
+            const v2f z_ = {E_.zi.x, E_.zi.x};                                                                                \
+            const uint32_t id_ = __float_as_uint(E_.zi.y);                                                                    \
+            zw[0] = __builtin_elementwise_fma(z_, wa0, zw[0]); zw[1] = __builtin_elementwise_fma(z_, wa1, zw[1]);             \
+            ws[0] += wa0; ws[1] += wa1;                                                                                       \
+            px_top(wa0, id_, wm[0], idm[0]); px_top(wa1, id_, wm[1], idm[1]);                                                 \
+        }                                                                                                                     \
         /* SURVEY §8a contract 3: nearest on top.  C += c w in ONE rounding (v_pk_fma_f32; composite.hip is the one file built     \
            with contraction on: the sum is within the composite's stated tolerance either way) */                             \
         cr[0] = __builtin_elementwise_fma((v2f){C0.x, C0.x}, w0, cr[0]); cr[1] = __builtin_elementwise_fma((v2f){C0.x, C0.x}, w1, cr[1]); \
@@ -919,13 +979,14 @@ __global__ __launch_bounds__(128, PX_WAVES) void k_composite_px(CompositeParams 
 #ifdef PX_PROFILE
             const unsigned long long pt0 = __builtin_amdgcn_s_memtime();
 #endif
-            uint32_t ja, jb, jlast = NONE, aa = 0, ab = 0, sa = 0, sb = 0;
+            uint32_t ja, jb, jlast = NONE, aa = 0, ab = 0, sa = 0, sb = 0, aa_aov = 0, ab_aov = 0;
             unsigned long long alive_m = __ballot(lane_live); // lanes with a pixel still accumulating (as of the last blend)
             bool all_stopped = false; // every pixel of the tile had stopped before the entry just blended: the rest of the chunk is zeros
             unsigned long long ra_, rb_;
             struct PxEnt { // what a trip reads of its entry: table values and colour, or (DISC) the three parameter vectors
                 float2 gx, gy, c0, c1;
                 float4 p0, p1, p2;
+                float2 zi; // AOV
             } ea, eb;
             PX_POP(ja, ra_, aa, sa);
             PX_LOAD(ja, aa, ea);
@@ -1012,6 +1073,10 @@ __global__ __launch_bounds__(128, PX_WAVES) void k_composite_px(CompositeParams 
             p.out_rgba32f[o] = make_float4(r0, g0, b0, 1.0f);
             if (okx1) p.out_rgba32f[o + 1] = make_float4(r1, g1, b1, 1.0f);
         }
+        if constexpr (AOV) {
+            px_aov_store(p, o, T[r].x, zw[r].x, ws[r].x, idm[r].x);
+            if (okx1) px_aov_store(p, o + 1, T[r].y, zw[r].y, ws[r].y, idm[r].y);
+        }
     }
 }
 
@@ -1087,6 +1152,19 @@ static int px_order_prepare(splat_ctx *ctx, uint32_t band_tiles, uint64_t key, C
     return SPLAT_OK;
 }
 
+int aov_check(splat_ctx *ctx, const splat_composite_cfg *cfg, const splat_aov *aov, bool has_depth) {
+    if (!aov) return SPLAT_OK;
+    ARG_CHECK(ctx, aov->depth_f32 || aov->alpha_f32 || aov->id_u32);
+    ARG_CHECK(ctx, (((uintptr_t)aov->depth_f32 | (uintptr_t)aov->alpha_f32 | (uintptr_t)aov->id_u32) & 15) == 0);
+    if (cfg->mode != SPLAT_COMPOSITE_FRONT_TO_BACK)
+        return ctx_fail(ctx, SPLAT_ERR_INVALID, "splat_aov: the reference-literal blend has no auxiliary outputs (an entry's final weight is "
+                                                "not known until its list ends)");
+    if (aov->depth_f32 && !has_depth)
+        return ctx_fail(ctx, SPLAT_ERR_INVALID, "splat_aov: depth asked for, but the records composited carry no splat depth (32-byte disc "
+                                                "records: composite from SPLAT_RECORDS_DISC48, or render the frame with `projected` or lit records)");
+    return SPLAT_OK;
+}
+
 extern "C" int splat_lit_colors(splat_ctx *ctx, const void *color_opacity, uint32_t color_stride_vec4, const void *normals,
                                 uint32_t normal_stride_vec4, uint32_t n, void *lit) {
     if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
@@ -1107,6 +1185,15 @@ extern "C" int splat_composite(splat_ctx *ctx, const splat_composite_cfg *cfg, c
                                const void *projected, const void *tile_indices, const void *tile_counts,
                                const void *tile_offsets, uint32_t width, uint32_t height, void *out_rgba8, void *out_rgba32f,
                                void *consumed_dptr) {
+    return splat_composite_aov(ctx, cfg, color_opacity, color_stride_vec4, normals, normal_stride_vec4, projected, tile_indices, tile_counts,
+                               tile_offsets, width, height, out_rgba8, out_rgba32f, consumed_dptr, nullptr);
+}
+
+extern "C" int splat_composite_aov(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity,
+                                   uint32_t color_stride_vec4, const void *normals, uint32_t normal_stride_vec4,
+                                   const void *projected, const void *tile_indices, const void *tile_counts,
+                                   const void *tile_offsets, uint32_t width, uint32_t height, void *out_rgba8, void *out_rgba32f,
+                                   void *consumed_dptr, const splat_aov *aov) {
     // lit DISC records (48 bytes: the lit colour behind each disc record) exist only inside a frame's binner; a public caller's
     // disc records are the projector's 32-byte ones (splat_project_disc) or 48-byte exchange records (taken at its
     // word this pair would read idx * 48 out of an n * 32 allocation)
@@ -1114,25 +1201,25 @@ extern "C" int splat_composite(splat_ctx *ctx, const splat_composite_cfg *cfg, c
         return ctx_fail(ctx, SPLAT_ERR_INVALID, "splat_composite: the oriented-disc footprint composites from SPLAT_RECORDS_PROJECTED (32-byte disc "
                                                 "records) or SPLAT_RECORDS_DISC48; lit disc records are internal to splat_render_frame");
     return composite_launch(ctx, cfg, color_opacity, color_stride_vec4, normals, normal_stride_vec4, projected, tile_indices, tile_counts,
-                            tile_offsets, width, height, out_rgba8, out_rgba32f, consumed_dptr, nullptr, nullptr, 0u);
+                            tile_offsets, width, height, out_rgba8, out_rgba32f, consumed_dptr, nullptr, nullptr, 0u, aov);
 }
 
 static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4,
                                     const void *normals, uint32_t normal_stride_vec4, const void *projected, const void *tile_indices,
                                     const void *tile_counts, const void *tile_offsets, uint32_t width, uint32_t height, void *out_rgba8,
                                     void *out_rgba32f, void *consumed_dptr, const uint32_t *frame_total, uint32_t *report,
-                                    uint32_t report_seq, bool *launched);
+                                    uint32_t report_seq, const splat_aov *aov, const void *disc_depth, bool *launched);
 
 // The composite with the frame's report attached.  Whatever happens to the launch, a report that was promised is sent
 // (the host waits for it at its next call).
 int composite_launch(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4, const void *normals,
                      uint32_t normal_stride_vec4, const void *projected, const void *tile_indices, const void *tile_counts,
                      const void *tile_offsets, uint32_t width, uint32_t height, void *out_rgba8, void *out_rgba32f, void *consumed_dptr,
-                     const uint32_t *frame_total, uint32_t *report, uint32_t report_seq) {
+                     const uint32_t *frame_total, uint32_t *report, uint32_t report_seq, const splat_aov *aov, const void *disc_depth) {
     bool launched = false;
     const int rc = composite_launch_checked(ctx, cfg, color_opacity, color_stride_vec4, normals, normal_stride_vec4, projected, tile_indices,
                                             tile_counts, tile_offsets, width, height, out_rgba8, out_rgba32f, consumed_dptr, frame_total, report,
-                                            report_seq, &launched);
+                                            report_seq, aov, disc_depth, &launched);
     if (ctx && report && !launched) { // an empty band of tile rows, or a rejected argument: the report goes out on its own
         hipLaunchKernelGGL(k_frame_report, dim3(1), dim3(1), 0, ctx->stream, frame_total, report, report_seq);
         (void)hipGetLastError();
@@ -1144,7 +1231,7 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
                                     const void *normals, uint32_t normal_stride_vec4, const void *projected, const void *tile_indices,
                                     const void *tile_counts, const void *tile_offsets, uint32_t width, uint32_t height, void *out_rgba8,
                                     void *out_rgba32f, void *consumed_dptr, const uint32_t *frame_total, uint32_t *report,
-                                    uint32_t report_seq, bool *launched) {
+                                    uint32_t report_seq, const splat_aov *aov, const void *disc_depth, bool *launched) {
     if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
     ARG_CHECK(ctx, cfg != nullptr);
     // 16x16 tiles: k_composite_px / k_composite, whose quadrant mapping is built for them; any other size the binner
@@ -1170,6 +1257,30 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
     ARG_CHECK(ctx, cfg->footprint != SPLAT_FOOTPRINT_DISC ||
                        (cfg->mode == SPLAT_COMPOSITE_FRONT_TO_BACK && cfg->record_format != SPLAT_RECORDS_COMPACT));
     ARG_CHECK(ctx, cfg->record_format != SPLAT_RECORDS_DISC48 || cfg->footprint == SPLAT_FOOTPRINT_DISC);
+    ARG_CHECK(ctx, (((uintptr_t)disc_depth) & 15) == 0);
+    // where the auxiliary outputs' depth comes from: float `off` of every record, `stride` floats apart — the ProjectedSplat's
+    // depth (SplatProjector.ts:77), which the compact, lit and 48-byte disc records carry as well; the projector's 32-byte
+    // disc records carry none (a frame hands its ProjectedSplat records in as disc_depth when it writes them)
+    const bool is_disc = cfg->footprint == SPLAT_FOOTPRINT_DISC;
+    const float *zsrc = nullptr;
+    uint32_t zoff = 0, zstride = 0;
+    if (!is_disc) {
+        zsrc = (const float *)projected;
+        zoff = cfg->record_format == SPLAT_RECORDS_PROJECTED ? 4u : 3u;
+        zstride = cfg->record_format == SPLAT_RECORDS_COMPACT ? 4u : 8u;
+    } else if (cfg->record_format == SPLAT_RECORDS_DISC48 || lit32) {
+        zsrc = (const float *)projected; // {disc record, depth, -, -, -} / {disc record, lit r, g, b, depth}
+        zoff = cfg->record_format == SPLAT_RECORDS_DISC48 ? 8u : 11u;
+        zstride = 12u;
+    } else if (disc_depth) {
+        zsrc = (const float *)disc_depth;
+        zoff = 4u;
+        zstride = 8u;
+    }
+    if (aov) {
+        const int arc = aov_check(ctx, cfg, aov, zsrc != nullptr);
+        if (arc != SPLAT_OK) return arc;
+    }
     const uint32_t ntx = div_up(width, T), nty = div_up(height, T);
     uint32_t r0 = cfg->tile_row0, r1 = cfg->tile_row1 > nty ? nty : cfg->tile_row1;
     if (r0 >= r1) return SPLAT_OK;
@@ -1206,6 +1317,13 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
 #ifdef PX_PROFILE
     p.debug_cap = getenv("SPLAT_PX_CAP") ? (uint32_t)strtoul(getenv("SPLAT_PX_CAP"), nullptr, 10) : 0xffffffffu;
 #endif
+    p.aov_depth = aov ? (float *)aov->depth_f32 : nullptr;
+    p.aov_alpha = aov ? (float *)aov->alpha_f32 : nullptr;
+    p.aov_id = aov ? (uint32_t *)aov->id_u32 : nullptr;
+    // (without a depth to gather the kernels still read one word per entry: stride 0 keeps it on a valid one)
+    p.aov_z = (aov && aov->depth_f32) ? zsrc + zoff : (const float *)tile_counts;
+    p.aov_zstride = (aov && aov->depth_f32) ? zstride : 0u;
+    const bool want_aov = aov != nullptr;
     if (T != CT) return composite_tile_launch(ctx, cfg, p, nty, r0, r1, launched);
     dim3 grid(ntx, r1 - r0), block(256);
     const bool eo = cfg->early_out != 0;
@@ -1214,10 +1332,16 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
     // splat_stage_time_stats
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
-#define SPLAT_COMPOSITE_LAUNCH(MODE, EO, DISC, LIT)                                                                       \
-    do {                                                                                                                  \
-        if (timed) hipExtLaunchKernelGGL((k_composite<MODE, EO, DISC, LIT>), grid, block, 0, ctx->stream, ev0, ev1, 0, p); \
-        else hipLaunchKernelGGL((k_composite<MODE, EO, DISC, LIT>), grid, block, 0, ctx->stream, p);                     \
+#define SPLAT_COMPOSITE_LAUNCH1(MODE, EO, DISC, LIT, AOV)                                                                      \
+    do {                                                                                                                        \
+        if (timed) hipExtLaunchKernelGGL((k_composite<MODE, EO, DISC, LIT, AOV>), grid, block, 0, ctx->stream, ev0, ev1, 0, p); \
+        else hipLaunchKernelGGL((k_composite<MODE, EO, DISC, LIT, AOV>), grid, block, 0, ctx->stream, p);                     \
+    } while (0)
+    // (the reference-literal blend has no auxiliary outputs: aov_check refused them)
+#define SPLAT_COMPOSITE_LAUNCH(MODE, EO, DISC, LIT)                                                         \
+    do {                                                                                                    \
+        if (MODE == SPLAT_COMPOSITE_FRONT_TO_BACK && want_aov) SPLAT_COMPOSITE_LAUNCH1(SPLAT_COMPOSITE_FRONT_TO_BACK, EO, DISC, LIT, true); \
+        else SPLAT_COMPOSITE_LAUNCH1(MODE, EO, DISC, LIT, false);                                            \
     } while (0)
     // Which kernel composites the isotropic footprint nearest-on-top (the frame's default): k_composite_px — one wave per
     // tile, every lane walking its own entries — unless SPLAT_COMPOSITE=quadrant asks for round 2's k_composite (one
@@ -1263,10 +1387,15 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
         timed = stage_event_pair(ctx, SPLAT_STAGE_COMPOSITE, &ev0, &ev1);
         // one workgroup of two waves (consumer, builder) per tile, behind workgroup 0 (report, next launch's tile order)
         const dim3 pgrid(band_tiles + 1u), pblock(128);
-#define SPLAT_COMPOSITE_PX_LAUNCH2(EO, LIT, CNT, AH, DISC)                                                                       \
+#define SPLAT_COMPOSITE_PX_LAUNCH3(EO, LIT, CNT, AH, DISC, AOV)                                                                  \
     do {                                                                                                                        \
-        if (timed) hipExtLaunchKernelGGL((k_composite_px<EO, LIT, CNT, AH, DISC>), pgrid, pblock, 0, ctx->stream, ev0, ev1, 0, p, band_tiles); \
-        else hipLaunchKernelGGL((k_composite_px<EO, LIT, CNT, AH, DISC>), pgrid, pblock, 0, ctx->stream, p, band_tiles);                       \
+        if (timed) hipExtLaunchKernelGGL((k_composite_px<EO, LIT, CNT, AH, DISC, AOV>), pgrid, pblock, 0, ctx->stream, ev0, ev1, 0, p, band_tiles); \
+        else hipLaunchKernelGGL((k_composite_px<EO, LIT, CNT, AH, DISC, AOV>), pgrid, pblock, 0, ctx->stream, p, band_tiles);                       \
+    } while (0)
+#define SPLAT_COMPOSITE_PX_LAUNCH2(EO, LIT, CNT, AH, DISC)                          \
+    do {                                                                           \
+        if (want_aov) SPLAT_COMPOSITE_PX_LAUNCH3(EO, LIT, CNT, AH, DISC, true);    \
+        else          SPLAT_COMPOSITE_PX_LAUNCH3(EO, LIT, CNT, AH, DISC, false);   \
     } while (0)
 #define SPLAT_COMPOSITE_PX_LAUNCH(EO, LIT, DISC)                                       \
     do {                                                                               \
@@ -1288,6 +1417,7 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
             if (eo) SPLAT_COMPOSITE_PX_LAUNCH(true, false, false);
             else    SPLAT_COMPOSITE_PX_LAUNCH(false, false, false);
         }
+#undef SPLAT_COMPOSITE_PX_LAUNCH3
 #undef SPLAT_COMPOSITE_PX_LAUNCH2
 #undef SPLAT_COMPOSITE_PX_LAUNCH
         *launched = hipPeekAtLastError() == hipSuccess; // (only a launch that went out carries the frame's report: composite_launch sends it otherwise)
@@ -1315,6 +1445,7 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
             else    SPLAT_COMPOSITE_LAUNCH(SPLAT_COMPOSITE_REFERENCE_LITERAL, false, false, false);
         }
     }
+#undef SPLAT_COMPOSITE_LAUNCH1
 #undef SPLAT_COMPOSITE_LAUNCH
     *launched = hipPeekAtLastError() == hipSuccess;
     LAUNCH_CHECK(ctx, "k_composite");

@@ -18,7 +18,9 @@
 
 #include <hip/hip_ext.h>
 
-template <int MODE, bool EARLY_OUT, bool DISC, bool LIT32>
+// AOV: also the auxiliary outputs (splat_aov; nearest-on-top only): per staged entry {depth, splat index} beside its
+// parameters, per pixel an AovPixel fed with the colour's own weight
+template <int MODE, bool EARLY_OUT, bool DISC, bool LIT32, bool AOV = false>
 __global__ __launch_bounds__(256) void k_composite_tile(CompositeParams p, uint32_t T, uint32_t wpt, uint2 *win_counts) {
     // per entry one 32-byte record {centre.x, centre.y, exp2 scale, lit blue | lit red, lit green, -, -}: both
     // halves are read off ONE address register (ds_read_b128 + ds_read_b64 offset:16), and forming an LDS
@@ -30,6 +32,9 @@ __global__ __launch_bounds__(256) void k_composite_tile(CompositeParams p, uint3
     __shared__ uint2 s_mask[4][CBATCH];  // per quadrant: which of its 64 pixels the entry's box covers
     __shared__ uint32_t s_wave_done[4];
     __shared__ uint32_t s_wave_consumed[4];
+    __shared__ float2 s_aov[AOV ? CBATCH : 1]; // AOV: {depth, splat index} per staged entry
+    static_assert(!AOV || MODE == SPLAT_COMPOSITE_FRONT_TO_BACK, "the auxiliary outputs are nearest-on-top only");
+    AovPixel aov;
 
     const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     if (p.report && blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) tile_report(p.frame_total, p.report, p.report_seq);
@@ -71,6 +76,7 @@ __global__ __launch_bounds__(256) void k_composite_tile(CompositeParams p, uint3
     uint32_t f_idx = 0xffffffffu;              // splat index of the entry this thread stages
     float4 f_b = make_float4(0, 0, 0, 0), f_c = f_b, f_n = f_b, f_b2 = f_b;
     float f_r = 0.0f;
+    float2 f_zi = make_float2(0.0f, 0.0f);     // AOV: {depth, index} of that entry, fetched with it
     bool f_ready = false;                      // f_* already hold this thread's entry of the batch about to be staged
     uint32_t n_idx = 0xffffffffu;              // index of this thread's entry one batch further on (the gathers depend on it)
     bool n_idx_valid = false;
@@ -92,6 +98,7 @@ __global__ __launch_bounds__(256) void k_composite_tile(CompositeParams p, uint3
             if (!f_ready) { // the first three batches of a tile: fetch now
                 f_idx = (tid < CBATCH && e < count) ? p.indices[off + e] : 0xffffffffu;
                 if (f_idx != 0xffffffffu) fetch_entry<MODE, EARLY_OUT, DISC, LIT32>(p, f_idx, f_b, f_b2, f_c, f_n, f_r);
+                if constexpr (AOV) f_zi = aov_entry(p, f_idx);
             }
             if (DISC && f_idx != 0xffffffffu) {
                 const DiscRecord rec = {f_b, f_b2};
@@ -136,6 +143,7 @@ __global__ __launch_bounds__(256) void k_composite_tile(CompositeParams p, uint3
                 s_mask[1][tid] = quadrant_mask(xm >> 8, ym & 0xffu);
                 s_mask[2][tid] = quadrant_mask(xm & 0xffu, ym >> 8);
                 s_mask[3][tid] = quadrant_mask(xm >> 8, ym >> 8);
+                if constexpr (AOV) s_aov[tid] = f_zi;
             }
             // issue the fetches for later batches; nothing below waits for them until the next stage
             f_ready = false;
@@ -143,6 +151,7 @@ __global__ __launch_bounds__(256) void k_composite_tile(CompositeParams p, uint3
                 if (n_idx_valid) { // index of batch k+1 arrived a batch ago: its gathers go out now
                     f_idx = n_idx;
                     if (f_idx != 0xffffffffu) fetch_entry<MODE, EARLY_OUT, DISC, LIT32>(p, f_idx, f_b, f_b2, f_c, f_n, f_r);
+                    if constexpr (AOV) f_zi = aov_entry(p, f_idx);
                     f_ready = true;
                 }
                 const uint32_t e2 = e + 2 * CBATCH; // batch k+2
@@ -223,6 +232,7 @@ __global__ __launch_bounds__(256) void k_composite_tile(CompositeParams p, uint3
                     cg += C0.y * wgt;
                     cb += B0 * wgt;
                     acc -= wgt; // T * (1 - g), with the product already in hand
+                    if constexpr (AOV) aov.add(wgt, s_aov[c0 + j0]);
                     if (EARLY_OUT) lv &= ~__ballot(acc <= T_STOP);
                 }
                 lv = uniform64(lv);
@@ -241,6 +251,7 @@ __global__ __launch_bounds__(256) void k_composite_tile(CompositeParams p, uint3
                     cg += C1.y * wgt;
                     cb += B1 * wgt;
                     acc -= wgt;
+                    if constexpr (AOV) aov.add(wgt, s_aov[c0 + j1]);
                     if (EARLY_OUT) lv &= ~__ballot(acc <= T_STOP);
                 }
                 live = lv;
@@ -279,6 +290,7 @@ __global__ __launch_bounds__(256) void k_composite_tile(CompositeParams p, uint3
         const size_t o = (size_t)py * p.width + px;
         if (p.out_rgba8) p.out_rgba8[o] = unorm8(fr) | (unorm8(fg) << 8) | (unorm8(fb) << 16) | (255u << 24);
         if (p.out_rgba32f) p.out_rgba32f[o] = make_float4(fr, fg, fb, 1.0f);
+        if constexpr (AOV) aov.store(p, o, acc);
     }
 }
 
@@ -326,10 +338,17 @@ int composite_tile_launch(splat_ctx *ctx, const splat_composite_cfg *cfg, const 
     const bool eo = cfg->early_out != 0, lit32 = cfg->record_format == SPLAT_RECORDS_LIT32;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     const bool timed = stage_event_pair(ctx, SPLAT_STAGE_COMPOSITE, &ev0, &ev1); // (after everything that can fail: composite.hip)
-#define SPLAT_COMPOSITE_TILE_LAUNCH(MODE, EO, DISC, LIT)                                                                              \
+#define SPLAT_COMPOSITE_TILE_LAUNCH1(MODE, EO, DISC, LIT, AOV)                                                                         \
     do {                                                                                                                              \
-        if (timed) hipExtLaunchKernelGGL((k_composite_tile<MODE, EO, DISC, LIT>), grid, block, 0, ctx->stream, ev0, ev1, 0, p, T, wpt, win_counts); \
-        else hipLaunchKernelGGL((k_composite_tile<MODE, EO, DISC, LIT>), grid, block, 0, ctx->stream, p, T, wpt, win_counts);                       \
+        if (timed) hipExtLaunchKernelGGL((k_composite_tile<MODE, EO, DISC, LIT, AOV>), grid, block, 0, ctx->stream, ev0, ev1, 0, p, T, wpt, win_counts); \
+        else hipLaunchKernelGGL((k_composite_tile<MODE, EO, DISC, LIT, AOV>), grid, block, 0, ctx->stream, p, T, wpt, win_counts);                       \
+    } while (0)
+    // (the auxiliary outputs are nearest-on-top only: composite.hip's aov_check refused them for the reference-literal blend)
+    const bool want_aov = p.aov_depth || p.aov_alpha || p.aov_id;
+#define SPLAT_COMPOSITE_TILE_LAUNCH(MODE, EO, DISC, LIT)                                                                  \
+    do {                                                                                                                  \
+        if (MODE == SPLAT_COMPOSITE_FRONT_TO_BACK && want_aov) SPLAT_COMPOSITE_TILE_LAUNCH1(SPLAT_COMPOSITE_FRONT_TO_BACK, EO, DISC, LIT, true); \
+        else SPLAT_COMPOSITE_TILE_LAUNCH1(MODE, EO, DISC, LIT, false);                                                     \
     } while (0)
     if (p.disc) {
         if (eo) SPLAT_COMPOSITE_TILE_LAUNCH(SPLAT_COMPOSITE_FRONT_TO_BACK, true, true, false);
@@ -351,6 +370,7 @@ int composite_tile_launch(splat_ctx *ctx, const splat_composite_cfg *cfg, const 
             else    SPLAT_COMPOSITE_TILE_LAUNCH(SPLAT_COMPOSITE_REFERENCE_LITERAL, false, false, false);
         }
     }
+#undef SPLAT_COMPOSITE_TILE_LAUNCH1
 #undef SPLAT_COMPOSITE_TILE_LAUNCH
     *launched = hipPeekAtLastError() == hipSuccess;
     LAUNCH_CHECK(ctx, "k_composite_tile");

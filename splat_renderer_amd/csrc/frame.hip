@@ -700,7 +700,7 @@ int splat_band_kept(splat_ctx *ctx, splat_sorter *sorter, uint32_t *n_kept_host)
 static int render_frame_impl(splat_ctx *ctx, splat_sorter *sorter, splat_binner *binner, const splat_composite_cfg *cfg,
                              const float *uniforms, const void *props, uint32_t pos_stride, const void *color,
                              uint32_t color_stride, const void *normals, uint32_t n, uint32_t width, uint32_t height,
-                             void *projected, void *out_rgba8, void *out_rgba32f) {
+                             void *projected, void *out_rgba8, void *out_rgba32f, const splat_aov *aov) {
     if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
     ARG_CHECK(ctx, sorter && binner && cfg && uniforms && props && color && (normals || cfg->prelit));
     ARG_CHECK(ctx, cfg->tile_size == splat_bin_tile_size(binner));
@@ -717,6 +717,12 @@ static int render_frame_impl(splat_ctx *ctx, splat_sorter *sorter, splat_binner 
     ARG_CHECK(ctx, cfg->record_format == SPLAT_RECORDS_PROJECTED || cfg->record_format == SPLAT_RECORDS_LIT32);
     const bool lit = cfg->record_format == SPLAT_RECORDS_LIT32 && !disc, disc_lit = cfg->record_format == SPLAT_RECORDS_LIT32 && disc;
     ARG_CHECK(ctx, !disc || (normals && (((uintptr_t)normals) & 15) == 0));
+    // the auxiliary outputs, checked before anything runs: a disc frame's depth comes from its lit disc records (their fourth
+    // colour word carries it) or its ProjectedSplat records; the plain disc records have none
+    {
+        const int arc = aov_check(ctx, cfg, aov, !disc || disc_lit || projected);
+        if (arc != SPLAT_OK) return arc;
+    }
     if (n > splat_sort_capacity(sorter)) return ctx_fail(ctx, SPLAT_ERR_CAPACITY, "splat_render_frame: n exceeds the sorter's capacity");
     ARG_CHECK(ctx, width >= 1 && height >= 1);
     // SplatProjector.project + DepthKeyExtractor.extract fused; props is the interleaved buffer.
@@ -815,7 +821,7 @@ static int render_frame_impl(splat_ctx *ctx, splat_sorter *sorter, splat_binner 
     binner->report_for_composite = nullptr;
     return composite_launch(ctx, cfg, color, color_stride, normals, 1, records, indices, counts, offsets, width, height, out_rgba8,
                             out_rgba32f, (ctx->timing && (ctx->timing_mask & SPLAT_TIMING_COUNT_ENTRIES)) ? (void *)ctx->d_consumed : nullptr, binner->d_total,
-                            report, binner->report_seq);
+                            report, binner->report_seq, aov, (disc && !disc_lit) ? projected : nullptr);
 }
 
 extern "C" {
@@ -824,15 +830,31 @@ int splat_render_frame(splat_ctx *ctx, splat_sorter *sorter, splat_binner *binne
                        const float *uniforms, const void *props, const void *normals, uint32_t n, uint32_t width,
                        uint32_t height, void *projected, void *out_rgba8, void *out_rgba32f) {
     // the reference's interleaved records: colour is the second vec4 of each
+    return splat_render_frame_aov(ctx, sorter, binner, cfg, uniforms, props, normals, n, width, height, projected, out_rgba8, out_rgba32f,
+                                  nullptr);
+}
+
+int splat_render_frame_aov(splat_ctx *ctx, splat_sorter *sorter, splat_binner *binner, const splat_composite_cfg *cfg,
+                           const float *uniforms, const void *props, const void *normals, uint32_t n, uint32_t width,
+                           uint32_t height, void *projected, void *out_rgba8, void *out_rgba32f, const splat_aov *aov) {
+    // the reference's interleaved records: colour is the second vec4 of each
     return render_frame_impl(ctx, sorter, binner, cfg, uniforms, props, 2, props ? (const char *)props + 16 : nullptr, 2, normals, n,
-                             width, height, projected, out_rgba8, out_rgba32f);
+                             width, height, projected, out_rgba8, out_rgba32f, aov);
 }
 
 int splat_render_frame_planes(splat_ctx *ctx, splat_sorter *sorter, splat_binner *binner, const splat_composite_cfg *cfg,
                               const float *uniforms, const void *pos_radius, const void *color_opacity, const void *normals,
                               uint32_t n, uint32_t width, uint32_t height, void *projected, void *out_rgba8, void *out_rgba32f) {
+    return splat_render_frame_planes_aov(ctx, sorter, binner, cfg, uniforms, pos_radius, color_opacity, normals, n, width, height, projected,
+                                         out_rgba8, out_rgba32f, nullptr);
+}
+
+int splat_render_frame_planes_aov(splat_ctx *ctx, splat_sorter *sorter, splat_binner *binner, const splat_composite_cfg *cfg,
+                                  const float *uniforms, const void *pos_radius, const void *color_opacity, const void *normals,
+                                  uint32_t n, uint32_t width, uint32_t height, void *projected, void *out_rgba8, void *out_rgba32f,
+                                  const splat_aov *aov) {
     return render_frame_impl(ctx, sorter, binner, cfg, uniforms, pos_radius, 1, color_opacity, 1, normals, n, width, height, projected,
-                             out_rgba8, out_rgba32f);
+                             out_rgba8, out_rgba32f, aov);
 }
 
 } // extern "C"

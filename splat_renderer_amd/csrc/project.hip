@@ -153,10 +153,14 @@ __device__ __forceinline__ uint32_t project_one(const FrameUniforms &u, const Sp
         // LIT: the lit colour rides behind the record (48 bytes per splat): the disc frame's composite then gathers this one
         // record per staged list entry instead of record + colour + normal — the gathers are what a staged entry costs
         // (C2: 168 -> 124 us for one line less, profiles/r04_d_disc_composite_C2.txt)
-        if (LIT) dio.discs[(size_t)i * dio.disc_stride + 2] = lio.prelit ? in.col : lit_color(in.col, in.nrm);
-        disc_bounds(d, a);
         const float dx = pr.x - u.eye[0], dy = pr.y - u.eye[1], dz = pr.z - u.eye[2];
         depth = sqrtf((dx * dx + dy * dy) + dz * dz); // SplatProjector.ts:77: the sort key does not depend on the footprint
+        // (the fourth word, the opacity the composite never reads, carries the depth instead: the auxiliary outputs' splat_aov)
+        if (LIT) {
+            const float4 lc = lio.prelit ? in.col : lit_color(in.col, in.nrm);
+            dio.discs[(size_t)i * dio.disc_stride + 2] = make_float4(lc.x, lc.y, lc.z, depth);
+        }
+        disc_bounds(d, a);
         b = make_float4(depth, 0.5f * fmaxf(a.z - a.x, a.w - a.y), __uint_as_float(index_base + i), 0.0f);
     } else {
         const float4 c = project_centre(u, in.pr);

@@ -591,6 +591,49 @@ class PerTileSorter:
         pass
 
 
+class _AovBuffers:
+    """The auxiliary outputs of a Gaussian frame (splat_aov): depth (f32), alpha (f32) and splat id (u32) per pixel, sized
+    with the image and reallocated when it is resized.  `written`: the latest frame wrote them — the readers refuse otherwise
+    (what a frame rendered without wantAov leaves in them is an older frame's)."""
+
+    def __init__(self, device):
+        self.device = device
+        self.depth = self.alpha = self.ids = None
+        self._wh = (0, 0)
+        self.written = False
+
+    def ensure(self, width, height):
+        if self._wh != (width, height):
+            self.destroy()
+            n = width * height * 4
+            self.depth, self.alpha, self.ids = (self.device.createBuffer(n) for _ in range(3))
+            self._wh = (width, height)
+        return _lib.Aov(self.depth.ptr, self.alpha.ptr, self.ids.ptr)
+
+    def _read(self, buf, dtype):
+        if buf is None or not self.written:
+            raise SplatError(-5, "the latest frame was not rendered with wantAov=True: no depth, alpha or id buffers to read")
+        w, h = self._wh
+        return buf.read(dtype).reshape(h, w)
+
+    def readDepth(self):
+        return self._read(self.depth, np.float32)
+
+    def readAlpha(self):
+        return self._read(self.alpha, np.float32)
+
+    def readIds(self):
+        return self._read(self.ids, np.uint32)
+
+    def destroy(self):
+        for b in (self.depth, self.alpha, self.ids):
+            if b:
+                b.destroy()
+        self.depth = self.alpha = self.ids = None
+        self._wh = (0, 0)
+        self.written = False
+
+
 class ComputeShaderRenderer:
     """src/ComputeShaderRenderer.ts:5-469 — the per-pixel composite.  The canvas blit (:268-338,
     :425-456) is out of scope (no canvas); the rgba8unorm output texture is exposed instead."""
@@ -609,6 +652,7 @@ class ComputeShaderRenderer:
         self._wh = (0, 0)
         self.tileRows = (0, U32_MAX)
         self.consumedBuffer = None
+        self.aov = _AovBuffers(device)
 
     def ensureOutputTexture(self, width, height, wantFloat=False):  # :340-360
         if self._wh != (width, height):
@@ -623,18 +667,23 @@ class ComputeShaderRenderer:
             self.outputFloat = self.device.createBuffer(width * height * 16)
 
     def render(self, uniformData, splatPropertyBuffer, splatIndicesBuffer, curvatureBuffer, projectedBuffer,
-               tileListsBuffer, tileOffsetsBuffer, tileSize, numTilesX, width, height, wantFloat=False):  # :362-462
+               tileListsBuffer, tileOffsetsBuffer, tileSize, numTilesX, width, height, wantFloat=False,
+               wantAov=False):  # :362-462
+        """wantAov: also write the depth, alpha and splat-id buffers (splat_aov; readDepth / readAlpha / readIds)."""
         d = self.device
         if numTilesX != -(-width // tileSize):
             raise SplatError(-1, "numTilesX does not match ceil(width / tileSize)")
         self.ensureOutputTexture(width, height, wantFloat)
         cfg = CompositeCfg(self.mode, int(self.earlyOut), tileSize, self.tileRows[0], self.tileRows[1], self.recordFormat, 0,
                            self.footprint)
-        check(d.lib.splat_composite(d.ctx, C.byref(cfg), splatPropertyBuffer.ptr + 16, 2, curvatureBuffer.ptr, 1,
-                                    projectedBuffer.ptr, splatIndicesBuffer.ptr, tileListsBuffer.ptr, tileOffsetsBuffer.ptr,
-                                    width, height, self.outputTexture.ptr,
-                                    self.outputFloat.ptr if (wantFloat and self.outputFloat) else None,
-                                    self.consumedBuffer.ptr if self.consumedBuffer else None), d.ctx)
+        aov = C.byref(self.aov.ensure(width, height)) if wantAov else None
+        self.aov.written = False
+        check(d.lib.splat_composite_aov(d.ctx, C.byref(cfg), splatPropertyBuffer.ptr + 16, 2, curvatureBuffer.ptr, 1,
+                                        projectedBuffer.ptr, splatIndicesBuffer.ptr, tileListsBuffer.ptr, tileOffsetsBuffer.ptr,
+                                        width, height, self.outputTexture.ptr,
+                                        self.outputFloat.ptr if (wantFloat and self.outputFloat) else None,
+                                        self.consumedBuffer.ptr if self.consumedBuffer else None, aov), d.ctx)
+        self.aov.written = wantAov
 
     def readPixels(self):
         w, h = self._wh
@@ -644,7 +693,17 @@ class ComputeShaderRenderer:
         w, h = self._wh
         return self.outputFloat.read(np.float32).reshape(h, w, 4)
 
+    def readDepth(self):
+        return self.aov.readDepth()
+
+    def readAlpha(self):
+        return self.aov.readAlpha()
+
+    def readIds(self):
+        return self.aov.readIds()
+
     def destroy(self):  # :464-468
+        self.aov.destroy()
         if self.outputTexture:
             self.outputTexture.destroy()
         if self.outputFloat:
@@ -788,6 +847,7 @@ class Renderer:
         # frames whose tile lists failed the per-tile sort's order check (SPLAT_ERR_RETRY) and were rendered again with
         # ballots: NOT a capacity event — the context has changed its ranking for good (Device.rankStatus())
         self.framesMisranked = 0
+        self.aov = _AovBuffers(device)
 
     def _again(self, rc):
         """Books a SPLAT_ERR_CAPACITY / SPLAT_ERR_RETRY report about the previous sync-free frame."""
@@ -797,7 +857,10 @@ class Renderer:
             self.previousFrameOverflowed = True
 
     def render(self, uniformData, propertyBuffer, normalsBuffer, scaleFactorsBuffer, width, height, tileRows=(0, U32_MAX),
-               wantFloat=False):
+               wantFloat=False, wantAov=False):
+        """wantAov: also write the depth, alpha and splat-id buffers (splat_aov; readDepth / readAlpha / readIds).  A disc
+        frame's depth comes from its lit records or its ProjectedSplat records: with records="projected" and
+        writeProjected=False it has none (SplatError)."""
         d = self.device
         u = _uniform_floats(uniformData).copy()
         if u.shape[0] < 22:
@@ -828,16 +891,20 @@ class Renderer:
                 self.projector.projectedBuffer.ptr if self.writeProjected else None, self.output.ptr,
                 self.outputFloat.ptr if wantFloat else None)
         head = (d.ctx, self.sorter._s, self.binner._b, C.byref(cfg), u.ctypes.data_as(C.POINTER(C.c_float)))
+        aov = self.aov.ensure(width, height) if wantAov else None
+        tail = tail + ((C.byref(aov) if aov is not None else None),)
         if isinstance(propertyBuffer, PropertyPlanes):  # the native layout: SplatPropertyManager.getPropertyPlanes()
-            fn, args = d.lib.splat_render_frame_planes, head + (propertyBuffer.posRadius.ptr, propertyBuffer.colorOpacity.ptr) + tail
+            fn, args = d.lib.splat_render_frame_planes_aov, head + (propertyBuffer.posRadius.ptr, propertyBuffer.colorOpacity.ptr) + tail
         else:  # the reference's interleaved records
-            fn, args = d.lib.splat_render_frame, head + (propertyBuffer.ptr,) + tail
-        self._last = (fn, args, u, cfg)  # keeps u/cfg alive; finish() may have to render this frame again
+            fn, args = d.lib.splat_render_frame_aov, head + (propertyBuffer.ptr,) + tail
+        self._last = (fn, args, u, cfg, aov)  # keeps u/cfg/aov alive; finish() may have to render this frame again (buffers too)
+        self.aov.written = False
         rc = fn(*args)
         if rc in _lib.RENDER_AGAIN:  # about the PREVIOUS (sync-free) frame: it outgrew its pair limit (room was made) or misranked
             self._again(rc)
             rc = fn(*args)
         check(rc, d.ctx)
+        self.aov.written = wantAov
         self.binner._tiles = -(-width // self.tileSize) * -(-height // self.tileSize)
         d.lastProjector, d.lastBinner = self.projector, self.binner
         return self.output
@@ -866,7 +933,20 @@ class Renderer:
         w, h = self._wh
         return self.outputFloat.read(np.float32).reshape(h, w, 4)
 
+    def readDepth(self):
+        self.finish()
+        return self.aov.readDepth()
+
+    def readAlpha(self):
+        self.finish()
+        return self.aov.readAlpha()
+
+    def readIds(self):
+        self.finish()
+        return self.aov.readIds()
+
     def destroy(self):
+        self.aov.destroy()
         self.projector.destroy()
         self.sorter.destroy()
         self.binner.destroy()

@@ -239,8 +239,15 @@ export class ComputeShaderRenderer {
   constructor(device: Device, context?: unknown, presentationFormat?: string, options?: { mode?: number; earlyOut?: boolean; footprint?: Footprint; recordFormat?: number });
   recordFormat: number;
   ensureOutputTexture(width: number, height: number): void;
-  render(uniformData: Float32Array, splatPropertyBuffer: Buffer, splatIndicesBuffer: Buffer, curvatureBuffer: Buffer, projectedBuffer: Buffer, tileListsBuffer: Buffer, tileOffsetsBuffer: Buffer, tileSize: number, numTilesX: number, width: number, height: number): void;
+  /** wantAov: also the depth, alpha and splat-id buffers (include/splat.h splat_aov) */
+  render(uniformData: Float32Array, splatPropertyBuffer: Buffer, splatIndicesBuffer: Buffer, curvatureBuffer: Buffer, projectedBuffer: Buffer, tileListsBuffer: Buffer, tileOffsetsBuffer: Buffer, tileSize: number, numTilesX: number, width: number, height: number, wantAov?: boolean): void;
   readPixels(): Uint8Array;
+  /** sum w z / sum w per pixel (+Infinity where nothing contributed); throws unless the latest render() had wantAov */
+  readDepth(): Float32Array;
+  /** 1 - T_end per pixel (0 where nothing contributed) */
+  readAlpha(): Float32Array;
+  /** index of the splat with the largest weight, 0xFFFFFFFF where none */
+  readIds(): Uint32Array;
   destroy(): void;
 }
 /** render() has the reference's eleven arguments (src/TileRenderer.ts:234-246) and needs nothing else: the projected records and
@@ -254,9 +261,16 @@ export class TileRenderer extends ComputeShaderRenderer {
 export class Renderer {
   constructor(device: Device, context?: unknown, presentationFormat?: string, numPoints?: number, tileSize?: number, options?: { footprint?: Footprint; records?: "lit" | "lit-always" | "projected" });
   recordFormat: number;
-  render(uniformData: Float32Array | Buffer, propertyBuffer: Buffer | PropertyPlanes, normalsBuffer: Buffer, scaleFactorsBuffer: Buffer | null, width: number, height: number): Buffer;
+  /** wantAov: also the depth, alpha and splat-id buffers (include/splat.h splat_aov) */
+  render(uniformData: Float32Array | Buffer, propertyBuffer: Buffer | PropertyPlanes, normalsBuffer: Buffer, scaleFactorsBuffer: Buffer | null, width: number, height: number, wantAov?: boolean): Buffer;
   finish(): number;
   readPixels(): Uint8Array;
+  /** sum w z / sum w per pixel (+Infinity where nothing contributed); throws unless the latest render() had wantAov */
+  readDepth(): Float32Array;
+  /** 1 - T_end per pixel (0 where nothing contributed) */
+  readAlpha(): Float32Array;
+  /** index of the splat with the largest weight, 0xFFFFFFFF where none */
+  readIds(): Uint32Array;
   destroy(): void;
 }
 /** src/Renderer.ts as the reference app draws it: opaque depth-tested quads in the tangent plane of each point's SDF gradient.

@@ -343,6 +343,47 @@ class PerTileSorter {
 }
 
 /** src/ComputeShaderRenderer.ts:5-469 (the canvas blit :268-338 is out of scope) */
+/** The auxiliary outputs of a Gaussian frame (include/splat.h splat_aov): depth (f32), alpha (f32) and splat id (u32) per pixel,
+ * sized with the image and reallocated when it is resized.  `written`: the latest frame wrote them — the readers refuse
+ * otherwise (what a frame without wantAov leaves is an older frame's).  host.py _AovBuffers. */
+class AovBuffers {
+  constructor(device) {
+    this.device = device;
+    this.depth = null;
+    this.alpha = null;
+    this.ids = null;
+    this.width = 0;
+    this.height = 0;
+    this.written = false;
+  }
+  ensure(width, height) { // the [depth, alpha, ids] device pointers the native *_aov methods take
+    if (this.width !== width || this.height !== height) {
+      this.destroy();
+      this.depth = this.device.createBuffer(width * height * 4);
+      this.alpha = this.device.createBuffer(width * height * 4);
+      this.ids = this.device.createBuffer(width * height * 4);
+      this.width = width;
+      this.height = height;
+    }
+    return [this.depth.ptr, this.alpha.ptr, this.ids.ptr];
+  }
+  check() {
+    if (!this.written) throw new Error('the latest frame was not rendered with wantAov: no depth, alpha or id buffers to read');
+  }
+  readDepth() { this.check(); return this.depth.read(new Float32Array(this.width * this.height)); }
+  readAlpha() { this.check(); return this.alpha.read(new Float32Array(this.width * this.height)); }
+  readIds() { this.check(); return this.ids.read(new Uint32Array(this.width * this.height)); }
+  destroy() {
+    for (const b of [this.depth, this.alpha, this.ids]) if (b) b.destroy();
+    this.depth = null;
+    this.alpha = null;
+    this.ids = null;
+    this.width = 0;
+    this.height = 0;
+    this.written = false;
+  }
+}
+
 class ComputeShaderRenderer {
   constructor(device, context = null, presentationFormat = 'rgba8unorm', options = {}) {
     this.device = device;
@@ -356,6 +397,7 @@ class ComputeShaderRenderer {
     this.outputTexture = null;
     this.width = 0;
     this.height = 0;
+    this.aov = new AovBuffers(device);
   }
   ensureOutputTexture(width, height) { // :340-360
     if (this.width !== width || this.height !== height) {
@@ -365,14 +407,22 @@ class ComputeShaderRenderer {
       this.height = height;
     }
   }
-  render(uniformData, splatPropertyBuffer, splatIndicesBuffer, curvatureBuffer, projectedBuffer, tileListsBuffer, tileOffsetsBuffer, tileSize, numTilesX, width, height) { // :362-462
+  render(uniformData, splatPropertyBuffer, splatIndicesBuffer, curvatureBuffer, projectedBuffer, tileListsBuffer, tileOffsetsBuffer, tileSize, numTilesX, width, height, wantAov = false) { // :362-462
     if (numTilesX !== Math.ceil(width / tileSize)) throw new Error('numTilesX does not match ceil(width / tileSize)');
     this.ensureOutputTexture(width, height);
-    native.composite(this.device.ctx, [this.mode, this.earlyOut ? 1 : 0, tileSize, 0, U32_MAX, this.recordFormat, 0, this.footprint], splatPropertyBuffer.ptr + 16, 2, curvatureBuffer.ptr, 1,
-      projectedBuffer.ptr, splatIndicesBuffer.ptr, tileListsBuffer.ptr, tileOffsetsBuffer.ptr, width, height, this.outputTexture.ptr, null);
+    // wantAov: also the depth, alpha and splat-id buffers (readDepth / readAlpha / readIds)
+    const aov = wantAov ? this.aov.ensure(width, height) : null;
+    this.aov.written = false;
+    native.composite_aov(this.device.ctx, [this.mode, this.earlyOut ? 1 : 0, tileSize, 0, U32_MAX, this.recordFormat, 0, this.footprint], splatPropertyBuffer.ptr + 16, 2, curvatureBuffer.ptr, 1,
+      projectedBuffer.ptr, splatIndicesBuffer.ptr, tileListsBuffer.ptr, tileOffsetsBuffer.ptr, width, height, this.outputTexture.ptr, null, aov);
+    this.aov.written = wantAov;
   }
   readPixels() { return this.outputTexture.read(new Uint8Array(this.width * this.height * 4)); }
+  readDepth() { return this.aov.readDepth(); }
+  readAlpha() { return this.aov.readAlpha(); }
+  readIds() { return this.aov.readIds(); }
   destroy() {
+    this.aov.destroy();
     if (this.outputTexture) this.outputTexture.destroy();
     this.outputTexture = null;
   } // :464-468
@@ -470,9 +520,12 @@ class Renderer {
     this.output = null;
     this.width = 0;
     this.height = 0;
+    this.aov = new AovBuffers(device);
   }
-  render(uniformData, propertyBuffer, normalsBuffer, scaleFactorsBuffer, width, height) {
-    this.last = [uniformData, propertyBuffer, normalsBuffer, scaleFactorsBuffer, width, height]; // (finish() may render it again)
+  // wantAov: also the depth, alpha and splat-id buffers (readDepth / readAlpha / readIds; a frame rendered again by finish()
+  // rewrites them with its image)
+  render(uniformData, propertyBuffer, normalsBuffer, scaleFactorsBuffer, width, height, wantAov = false) {
+    this.last = [uniformData, propertyBuffer, normalsBuffer, scaleFactorsBuffer, width, height, wantAov]; // (finish() may render it again)
     let u = uniformFloats(uniformData);
     if (u.length < 22) {
       const v = new Float32Array(22);
@@ -496,13 +549,16 @@ class Renderer {
     this.recordFormat = isoLit ? RECORDS_LIT32 : RECORDS_PROJECTED;
     this.projector.contents = isoLit ? 'lit' : 'projected';
     const cfg = [MODE_FRONT_TO_BACK, 1, this.tileSize, 0, U32_MAX, frameFormat, propertyBuffer.prelit ? 1 : 0, this.footprint];
+    const aov = wantAov ? this.aov.ensure(width, height) : null;
+    this.aov.written = false;
     if (propertyBuffer.isPlanes) { // SplatPropertyManager.getPropertyPlanes()
-      native.render_frame_planes(this.device.ctx, this.sorter.handle, this.binner.handle, cfg, u, propertyBuffer.posRadius.ptr, propertyBuffer.colorOpacity.ptr,
-        normalsBuffer.ptr, this.numPoints, width, height, this.projector.projectedBuffer.ptr, this.output.ptr, null);
+      native.render_frame_planes_aov(this.device.ctx, this.sorter.handle, this.binner.handle, cfg, u, propertyBuffer.posRadius.ptr, propertyBuffer.colorOpacity.ptr,
+        normalsBuffer.ptr, this.numPoints, width, height, this.projector.projectedBuffer.ptr, this.output.ptr, null, aov);
     } else {
-      native.render_frame(this.device.ctx, this.sorter.handle, this.binner.handle, cfg, u,
-        propertyBuffer.ptr, normalsBuffer.ptr, this.numPoints, width, height, this.projector.projectedBuffer.ptr, this.output.ptr, null);
+      native.render_frame_aov(this.device.ctx, this.sorter.handle, this.binner.handle, cfg, u,
+        propertyBuffer.ptr, normalsBuffer.ptr, this.numPoints, width, height, this.projector.projectedBuffer.ptr, this.output.ptr, null, aov);
     }
+    this.aov.written = wantAov;
     this.binner.numTiles = Math.ceil(width / this.tileSize) * Math.ceil(height / this.tileSize);
     this.device.lastProjector = this.projector;
     this.device.lastBinner = this.binner;
@@ -524,7 +580,20 @@ class Renderer {
     this.finish();
     return this.output.read(new Uint8Array(this.width * this.height * 4));
   }
+  readDepth() {
+    this.finish();
+    return this.aov.readDepth();
+  }
+  readAlpha() {
+    this.finish();
+    return this.aov.readAlpha();
+  }
+  readIds() {
+    this.finish();
+    return this.aov.readIds();
+  }
   destroy() {
+    this.aov.destroy();
     this.projector.destroy();
     this.sorter.destroy();
     this.binner.destroy();

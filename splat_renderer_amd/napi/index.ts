@@ -397,6 +397,54 @@ class PerTileSorter {
 }
 
 /** src/ComputeShaderRenderer.ts:5-469 (the canvas blit :268-338 is out of scope) */
+/** The auxiliary outputs of a Gaussian frame (include/splat.h splat_aov): depth (f32), alpha (f32) and splat id (u32) per pixel,
+ * sized with the image and reallocated when it is resized.  `written`: the latest frame wrote them — the readers refuse
+ * otherwise (what a frame without wantAov leaves is an older frame's).  host.py _AovBuffers. */
+class AovBuffers {
+  declare device: Device;
+  declare depth: Buffer_ | null;
+  declare alpha: Buffer_ | null;
+  declare ids: Buffer_ | null;
+  declare width: number;
+  declare height: number;
+  declare written: boolean;
+  constructor(device: Device) {
+    this.device = device;
+    this.depth = null;
+    this.alpha = null;
+    this.ids = null;
+    this.width = 0;
+    this.height = 0;
+    this.written = false;
+  }
+  ensure(width: number, height: number): number[] { // the [depth, alpha, ids] device pointers the native *_aov methods take
+    if (this.width !== width || this.height !== height) {
+      this.destroy();
+      this.depth = this.device.createBuffer(width * height * 4);
+      this.alpha = this.device.createBuffer(width * height * 4);
+      this.ids = this.device.createBuffer(width * height * 4);
+      this.width = width;
+      this.height = height;
+    }
+    return [this.depth.ptr, this.alpha.ptr, this.ids.ptr];
+  }
+  check(): void {
+    if (!this.written) throw new Error('the latest frame was not rendered with wantAov: no depth, alpha or id buffers to read');
+  }
+  readDepth(): Float32Array { this.check(); return this.depth.read(new Float32Array(this.width * this.height)); }
+  readAlpha(): Float32Array { this.check(); return this.alpha.read(new Float32Array(this.width * this.height)); }
+  readIds(): Uint32Array { this.check(); return this.ids.read(new Uint32Array(this.width * this.height)); }
+  destroy(): void {
+    for (const b of [this.depth, this.alpha, this.ids]) if (b) b.destroy();
+    this.depth = null;
+    this.alpha = null;
+    this.ids = null;
+    this.width = 0;
+    this.height = 0;
+    this.written = false;
+  }
+}
+
 class ComputeShaderRenderer {
   declare device: Device;
   declare mode: number;
@@ -406,6 +454,7 @@ class ComputeShaderRenderer {
   declare outputTexture: Buffer_ | null;
   declare width: number;
   declare height: number;
+  declare aov: AovBuffers;
   constructor(device: Device, context: unknown = null, presentationFormat: string = 'rgba8unorm', options: { mode?: number; earlyOut?: boolean; footprint?: Footprint; recordFormat?: number } = {}) {
     this.device = device;
     this.mode = options.mode || MODE_FRONT_TO_BACK;
@@ -418,6 +467,7 @@ class ComputeShaderRenderer {
     this.outputTexture = null;
     this.width = 0;
     this.height = 0;
+    this.aov = new AovBuffers(device);
   }
   ensureOutputTexture(width: number, height: number): void { // :340-360
     if (this.width !== width || this.height !== height) {
@@ -427,14 +477,22 @@ class ComputeShaderRenderer {
       this.height = height;
     }
   }
-  render(uniformData: Float32Array, splatPropertyBuffer: Buffer_, splatIndicesBuffer: Buffer_, curvatureBuffer: Buffer_, projectedBuffer: Buffer_, tileListsBuffer: Buffer_, tileOffsetsBuffer: Buffer_, tileSize: number, numTilesX: number, width: number, height: number): void { // :362-462
+  render(uniformData: Float32Array, splatPropertyBuffer: Buffer_, splatIndicesBuffer: Buffer_, curvatureBuffer: Buffer_, projectedBuffer: Buffer_, tileListsBuffer: Buffer_, tileOffsetsBuffer: Buffer_, tileSize: number, numTilesX: number, width: number, height: number, wantAov: boolean = false): void { // :362-462
     if (numTilesX !== Math.ceil(width / tileSize)) throw new Error('numTilesX does not match ceil(width / tileSize)');
     this.ensureOutputTexture(width, height);
-    native.composite(this.device.ctx, [this.mode, this.earlyOut ? 1 : 0, tileSize, 0, U32_MAX, this.recordFormat, 0, this.footprint], splatPropertyBuffer.ptr + 16, 2, curvatureBuffer.ptr, 1,
-      projectedBuffer.ptr, splatIndicesBuffer.ptr, tileListsBuffer.ptr, tileOffsetsBuffer.ptr, width, height, this.outputTexture.ptr, null);
+    // wantAov: also the depth, alpha and splat-id buffers (readDepth / readAlpha / readIds)
+    const aov = wantAov ? this.aov.ensure(width, height) : null;
+    this.aov.written = false;
+    native.composite_aov(this.device.ctx, [this.mode, this.earlyOut ? 1 : 0, tileSize, 0, U32_MAX, this.recordFormat, 0, this.footprint], splatPropertyBuffer.ptr + 16, 2, curvatureBuffer.ptr, 1,
+      projectedBuffer.ptr, splatIndicesBuffer.ptr, tileListsBuffer.ptr, tileOffsetsBuffer.ptr, width, height, this.outputTexture.ptr, null, aov);
+    this.aov.written = wantAov;
   }
   readPixels(): Uint8Array { return this.outputTexture.read(new Uint8Array(this.width * this.height * 4)); }
+  readDepth(): Float32Array { return this.aov.readDepth(); }
+  readAlpha(): Float32Array { return this.aov.readAlpha(); }
+  readIds(): Uint32Array { return this.aov.readIds(); }
   destroy(): void {
+    this.aov.destroy();
     if (this.outputTexture) this.outputTexture.destroy();
     this.outputTexture = null;
   } // :464-468
@@ -533,8 +591,9 @@ class Renderer {
   declare output: Buffer_ | null;
   declare width: number;
   declare height: number;
-  declare last: [Float32Array | Buffer_, Buffer_ | PropertyPlanes, Buffer_, Buffer_ | null, number, number] | null;
+  declare last: [Float32Array | Buffer_, Buffer_ | PropertyPlanes, Buffer_, Buffer_ | null, number, number, boolean] | null;
   declare recordFormat: number;
+  declare aov: AovBuffers;
   constructor(device: Device, context: unknown = null, presentationFormat: string = 'rgba8unorm', numPoints: number = 0, tileSize: number = 16, options: { footprint?: Footprint; records?: "lit" | "lit-always" | "projected" } = {}) {
     this.device = device;
     this.numPoints = numPoints;
@@ -553,9 +612,12 @@ class Renderer {
     this.output = null;
     this.width = 0;
     this.height = 0;
+    this.aov = new AovBuffers(device);
   }
-  render(uniformData: Float32Array | Buffer_, propertyBuffer: Buffer_ | PropertyPlanes, normalsBuffer: Buffer_, scaleFactorsBuffer: Buffer_ | null, width: number, height: number): Buffer_ {
-    this.last = [uniformData, propertyBuffer, normalsBuffer, scaleFactorsBuffer, width, height]; // (finish() may render it again)
+  // wantAov: also the depth, alpha and splat-id buffers (readDepth / readAlpha / readIds; a frame rendered again by finish()
+  // rewrites them with its image)
+  render(uniformData: Float32Array | Buffer_, propertyBuffer: Buffer_ | PropertyPlanes, normalsBuffer: Buffer_, scaleFactorsBuffer: Buffer_ | null, width: number, height: number, wantAov: boolean = false): Buffer_ {
+    this.last = [uniformData, propertyBuffer, normalsBuffer, scaleFactorsBuffer, width, height, wantAov]; // (finish() may render it again)
     let u = uniformFloats(uniformData);
     if (u.length < 22) {
       const v = new Float32Array(22);
@@ -579,13 +641,16 @@ class Renderer {
     this.recordFormat = isoLit ? RECORDS_LIT32 : RECORDS_PROJECTED;
     this.projector.contents = isoLit ? 'lit' : 'projected';
     const cfg = [MODE_FRONT_TO_BACK, 1, this.tileSize, 0, U32_MAX, frameFormat, propertyBuffer.prelit ? 1 : 0, this.footprint];
+    const aov = wantAov ? this.aov.ensure(width, height) : null;
+    this.aov.written = false;
     if (propertyBuffer.isPlanes) { // SplatPropertyManager.getPropertyPlanes()
-      native.render_frame_planes(this.device.ctx, this.sorter.handle, this.binner.handle, cfg, u, propertyBuffer.posRadius.ptr, propertyBuffer.colorOpacity.ptr,
-        normalsBuffer.ptr, this.numPoints, width, height, this.projector.projectedBuffer.ptr, this.output.ptr, null);
+      native.render_frame_planes_aov(this.device.ctx, this.sorter.handle, this.binner.handle, cfg, u, propertyBuffer.posRadius.ptr, propertyBuffer.colorOpacity.ptr,
+        normalsBuffer.ptr, this.numPoints, width, height, this.projector.projectedBuffer.ptr, this.output.ptr, null, aov);
     } else {
-      native.render_frame(this.device.ctx, this.sorter.handle, this.binner.handle, cfg, u,
-        propertyBuffer.ptr, normalsBuffer.ptr, this.numPoints, width, height, this.projector.projectedBuffer.ptr, this.output.ptr, null);
+      native.render_frame_aov(this.device.ctx, this.sorter.handle, this.binner.handle, cfg, u,
+        propertyBuffer.ptr, normalsBuffer.ptr, this.numPoints, width, height, this.projector.projectedBuffer.ptr, this.output.ptr, null, aov);
     }
+    this.aov.written = wantAov;
     this.binner.numTiles = Math.ceil(width / this.tileSize) * Math.ceil(height / this.tileSize);
     this.device.lastProjector = this.projector;
     this.device.lastBinner = this.binner;
@@ -607,7 +672,20 @@ class Renderer {
     this.finish();
     return this.output.read(new Uint8Array(this.width * this.height * 4));
   }
+  readDepth(): Float32Array {
+    this.finish();
+    return this.aov.readDepth();
+  }
+  readAlpha(): Float32Array {
+    this.finish();
+    return this.aov.readAlpha();
+  }
+  readIds(): Uint32Array {
+    this.finish();
+    return this.aov.readIds();
+  }
   destroy(): void {
+    this.aov.destroy();
     this.projector.destroy();
     this.sorter.destroy();
     this.binner.destroy();

@@ -295,6 +295,54 @@ FN(composite) { /* (ctx, cfg[5], color, cStride, normals, nStride, projected, in
     uint32_t w = (uint32_t)arg_number(&c, 10), h = (uint32_t)arg_number(&c, 11); void *o8 = arg_dptr(&c, 12), *of = arg_dptr(&c, 13); BAIL;
     return check(env, x, splat_composite(x, &cfg, col, cs, nrm, ns, proj, idx, cnt, off, w, h, o8, of, NULL), mk_undefined(env));
 }
+/* splat_aov from [depth|null, alpha|null, ids|null] (device pointers); undefined / null: no auxiliary outputs */
+static splat_aov *fill_aov(call_t *c, size_t i, splat_aov *aov) {
+    memset(aov, 0, sizeof *aov);
+    bool is = false;
+    napi_is_array(c->env, c->argv[i], &is);
+    if (!is) return NULL;
+    void **slot[3] = {&aov->depth_f32, &aov->alpha_f32, &aov->id_u32};
+    for (uint32_t k = 0; k < 3; ++k) {
+        napi_value e;
+        napi_valuetype t = napi_undefined;
+        if (napi_get_element(c->env, c->argv[i], k, &e) != napi_ok) continue;
+        napi_typeof(c->env, e, &t);
+        double d = 0; /* a device pointer as a number, as arg_dptr takes it */
+        if (t == napi_number && napi_get_value_double(c->env, e, &d) == napi_ok) *slot[k] = (void *)(uintptr_t)d;
+    }
+    return aov;
+}
+FN(composite_aov) { /* (ctx, cfg[5], color, cStride, normals, nStride, projected, indices, counts, offsets, W, H, out8|null, outF|null, [depth, alpha, ids]) */
+    ARGS(15); splat_ctx *x = arg_external(&c, 0); splat_composite_cfg cfg; fill_cfg(&c, 1, &cfg);
+    void *col = arg_dptr(&c, 2); uint32_t cs = (uint32_t)arg_number(&c, 3); void *nrm = arg_dptr(&c, 4); uint32_t ns = (uint32_t)arg_number(&c, 5);
+    void *proj = arg_dptr(&c, 6), *idx = arg_dptr(&c, 7), *cnt = arg_dptr(&c, 8), *off = arg_dptr(&c, 9);
+    uint32_t w = (uint32_t)arg_number(&c, 10), h = (uint32_t)arg_number(&c, 11); void *o8 = arg_dptr(&c, 12), *of = arg_dptr(&c, 13); BAIL;
+    splat_aov a; const splat_aov *ap = fill_aov(&c, 14, &a);
+    return check(env, x, splat_composite_aov(x, &cfg, col, cs, nrm, ns, proj, idx, cnt, off, w, h, o8, of, NULL, ap), mk_undefined(env));
+}
+FN(render_frame_aov) { /* render_frame's arguments, then [depth, alpha, ids] */
+    ARGS(14); splat_ctx *x = arg_external(&c, 0); splat_sorter *s = arg_external(&c, 1); splat_binner *b = arg_external(&c, 2);
+    splat_composite_cfg cfg; fill_cfg(&c, 3, &cfg); size_t ub = 0; float *u = arg_hostbuf(&c, 4, &ub);
+    void *props = arg_dptr(&c, 5), *nrm = arg_dptr(&c, 6); uint32_t n = (uint32_t)arg_number(&c, 7), w = (uint32_t)arg_number(&c, 8), h = (uint32_t)arg_number(&c, 9);
+    void *proj = arg_dptr(&c, 10), *o8 = arg_dptr(&c, 11), *of = arg_dptr(&c, 12); BAIL;
+    splat_aov a; const splat_aov *ap = fill_aov(&c, 13, &a);
+    if (ub < 22 * sizeof(float)) { napi_throw_range_error(env, NULL, "uniform block needs 22 floats"); return NULL; }
+    int rc = splat_render_frame_aov(x, s, b, &cfg, u, props, nrm, n, w, h, proj, o8, of, ap);
+    if (AGAIN(rc)) rc = splat_render_frame_aov(x, s, b, &cfg, u, props, nrm, n, w, h, proj, o8, of, ap);
+    return check(env, x, rc, mk_undefined(env));
+}
+FN(render_frame_planes_aov) { /* render_frame_planes' arguments, then [depth, alpha, ids] */
+    ARGS(15); splat_ctx *x = arg_external(&c, 0); splat_sorter *s = arg_external(&c, 1); splat_binner *b = arg_external(&c, 2);
+    splat_composite_cfg cfg; fill_cfg(&c, 3, &cfg); size_t ub = 0; float *u = arg_hostbuf(&c, 4, &ub);
+    void *pr = arg_dptr(&c, 5), *co = arg_dptr(&c, 6), *nrm = arg_dptr(&c, 7);
+    uint32_t n = (uint32_t)arg_number(&c, 8), w = (uint32_t)arg_number(&c, 9), h = (uint32_t)arg_number(&c, 10);
+    void *proj = arg_dptr(&c, 11), *o8 = arg_dptr(&c, 12), *of = arg_dptr(&c, 13); BAIL;
+    splat_aov a; const splat_aov *ap = fill_aov(&c, 14, &a);
+    if (ub < 22 * sizeof(float)) { napi_throw_range_error(env, NULL, "uniform block needs 22 floats"); return NULL; }
+    int rc = splat_render_frame_planes_aov(x, s, b, &cfg, u, pr, co, nrm, n, w, h, proj, o8, of, ap);
+    if (AGAIN(rc)) rc = splat_render_frame_planes_aov(x, s, b, &cfg, u, pr, co, nrm, n, w, h, proj, o8, of, ap);
+    return check(env, x, rc, mk_undefined(env));
+}
 FN(render_frame) { /* (ctx, sorter, binner, cfg[5], Float32Array(22), props, normals, n, W, H, projected, out8|null, outF|null) */
     ARGS(13); splat_ctx *x = arg_external(&c, 0); splat_sorter *s = arg_external(&c, 1); splat_binner *b = arg_external(&c, 2);
     splat_composite_cfg cfg; fill_cfg(&c, 3, &cfg); size_t ub = 0; float *u = arg_hostbuf(&c, 4, &ub);
@@ -537,6 +585,7 @@ static napi_value init(napi_env env, napi_value exports) {
         EXPORT(sort_payload), EXPORT(sort_sorted_payload), EXPORT(sort_sorted_keys), EXPORT(sort_run), EXPORT(sort_set_mode),
         EXPORT(scan_u32), EXPORT(bin_create), EXPORT(bin_destroy), EXPORT(bin_run), EXPORT(bin_counts), EXPORT(bin_offsets),
         EXPORT(bin_indices), EXPORT(bin_total), EXPORT(bin_set_frame_order), EXPORT(validate_tile_order), EXPORT(composite), EXPORT(render_frame), EXPORT(render_frame_planes),
+        EXPORT(composite_aov), EXPORT(render_frame_aov), EXPORT(render_frame_planes_aov),
         EXPORT(project_slice_compact), EXPORT(band_frame), EXPORT(band_settle), EXPORT(comm_unique_id), EXPORT(comm_init), EXPORT(comm_destroy),
         EXPORT(ctx_create_on_stream), EXPORT(last_error), EXPORT(set_timing_stages), EXPORT(set_timing_sampling), EXPORT(stage_time_stats), EXPORT(timing_consumed),
         EXPORT(buf_copy), EXPORT(probe_lds_atomic_order),
