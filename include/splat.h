@@ -297,6 +297,7 @@ int splat_validate_tile_order(splat_ctx *ctx, const void *projected, const void 
                                 * staged list entry instead of three. */
 #define SPLAT_FOOTPRINT_ISOTROPIC 0
 #define SPLAT_FOOTPRINT_DISC 1
+#define SPLAT_FOOTPRINT_ELLIPSOID 2 /* an anisotropic 3D Gaussian (extension, no reference counterpart): splat_project_ellipsoid */
 typedef struct splat_composite_cfg {
     uint32_t mode;       /* SPLAT_COMPOSITE_* */
     uint32_t early_out;  /* 1 = stop a pixel at alpha >= 0.99 (reference :187-190) */
@@ -316,7 +317,11 @@ typedef struct splat_composite_cfg {
                              * be FRONT_TO_BACK and record_format PROJECTED; in splat_render_frame* the projector
                              * used is splat_project_disc (normals are required even when prelit) and `projected`
                              * may be NULL (the ProjectedSplat records are then not written: a disc frame's composite
-                             * reads the disc records) */
+                             * reads the disc records)
+                             * SPLAT_FOOTPRINT_ELLIPSOID: the anisotropic 3D Gaussian of splat_project_ellipsoid — its records
+                             * are disc records and every disc rule above holds (nearest on top, PROJECTED records to
+                             * splat_composite*, projected may be NULL in its frame); exp(-0.5 d^T Sigma2^-1 d) inside 3 sigma.
+                             * Its frame is splat_render_frame_ellipsoids; splat_band_frame refuses it */
 } splat_composite_cfg;
 /* color_opacity / normals: vec4 per splat, *_stride_vec4 float4s apart.  out_rgba8 (W*H*4 bytes,
  * rgba8unorm, may be NULL) and out_rgba32f (W*H*16 bytes, may be NULL) are full-frame images;
@@ -399,6 +404,42 @@ int splat_render_frame_planes_aov(splat_ctx *ctx, splat_sorter *sorter, splat_bi
                                   const void *pos_radius, const void *color_opacity, const void *normals,
                                   uint32_t n, uint32_t width, uint32_t height, void *projected,
                                   void *out_rgba8, void *out_rgba32f, const splat_aov *aov);
+
+/* ---- anisotropic 3D Gaussians (SPLAT_FOOTPRINT_ELLIPSOID; an extension, no reference counterpart) ----------------------
+ * One splat = four planes of one vec4 each, *_stride_vec4 float4s apart: position xyz (w ignored), scale sigma x, y, z in world
+ * units (w ignored), rotation quaternion (w, x, y, z) of any non-zero length (q and -q give the same record), and the final
+ * colour and opacity (rgb, opacity: not shaded — an ellipsoid has no normal; see splat_sh_colors).
+ * Per splat: Sigma3 = R S S^T R^T; J the exact derivative at the centre of the projector's screen map ((W/2)(1 + c.x/c.w),
+ * (H/2)(1 - c.y/c.w)), c = VP [p; 1] (= 3DGS's J W for a perspective VP); Sigma2 = J Sigma3 J^T + 0.3 I (px^2, the 3DGS
+ * low-pass dilation).  The footprint is g(d) = exp(-0.5 d^T Sigma2^-1 d) where d^T Sigma2^-1 d <= 9, 0 elsewhere (d = pixel
+ * centre - screen centre); the blend is the other footprints' (nearest on top, alpha = opacity g, the early-out), with no
+ * 0.99 clamp of alpha and no 1/255 skip as in the 3DGS CUDA rasteriser.
+ * splat_project_ellipsoid writes
+ *   records[i]   = the 32-byte disc record {c.x, c.y, B00, B01, 0, B11, 0, 0}, B = U / 3, U upper-triangular with U^T U =
+ *                  Sigma2^-1 (so (u, v) = B d is inside the disc record's unit circle exactly at 3 sigma); all zeros when the
+ *                  centre's clip w is not > 0, the 3-sigma ellipsoid reaches w = 0 (c.w - 3 sqrt(m3 Sigma3 m3^T) <= 0, m3 the w
+ *                  row of VP), det Sigma2 <= 0 or anything is not finite;
+ *   projected[i] = a ProjectedSplat: bounds of the record as for discs (the exact 3-sigma box), depth as splat_project,
+ *                  screenRadius = half the larger extent;
+ * and keys / payload exactly as splat_project.  Sort and bin with `projected`; composite with cfg.footprint =
+ * SPLAT_FOOTPRINT_ELLIPSOID and `records`.  The operation order is stated in csrc/ellipsoid.h. */
+int splat_project_ellipsoid(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4,
+                            const void *scales, uint32_t scale_stride_vec4, const void *rotations, uint32_t rot_stride_vec4,
+                            uint32_t n, void *projected, void *records, void *keys, void *payload, uint32_t n_padded);
+/* View-dependent colour from spherical harmonics of degree 0-3 (the real basis and constants of 3D Gaussian splatting):
+ * color_opacity_out[i] = vec4(max(0.5 + sum_k Y_k(dir) sh_k, 0), opacity_f32[i]), dir = normalize(p_i - eye), with the
+ * coefficient of basis k < (degree + 1)^2 and channel c at sh[i * sh_stride_floats + 3 k + c].  eye3 is a host pointer. */
+int splat_sh_colors(splat_ctx *ctx, const float *eye3, const void *positions, uint32_t pos_stride_vec4, const void *sh,
+                    uint32_t sh_stride_floats, uint32_t degree, const void *opacity_f32, uint32_t n, void *color_opacity_out);
+/* The whole frame of anisotropic Gaussians: splat_render_frame_planes_aov with cfg->footprint = SPLAT_FOOTPRINT_ELLIPSOID,
+ * cfg->prelit = 1 (color_opacity is used as is), planes of stride 1 and the ellipsoid projector.  Both frame orders, record
+ * formats PROJECTED and LIT32, projected == NULL and every screen the binner takes work as for a disc frame; AOV depth follows
+ * the disc rules above (not with PROJECTED records and projected == NULL).  A strict band of tile rows is refused. */
+int splat_render_frame_ellipsoids(splat_ctx *ctx, splat_sorter *sorter, splat_binner *binner,
+                                  const splat_composite_cfg *cfg, const float *uniforms, const void *positions,
+                                  const void *scales, const void *rotations, const void *color_opacity, uint32_t n,
+                                  uint32_t width, uint32_t height, void *projected, void *out_rgba8, void *out_rgba32f,
+                                  const splat_aov *aov);
 
 /* ---- multi-GPU band path (no reference equivalent — the reference is single-device) */
 /* The oriented-disc projector (src/SequentialRenderer.ts:68-71,91-112): the splat is the disc

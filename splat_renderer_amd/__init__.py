@@ -8,9 +8,10 @@ from . import scene  # noqa: F401
 from ._lib import (MODE_FRONT_TO_BACK, MODE_REFERENCE_LITERAL, STAGE_BIN, STAGE_COMPOSITE, STAGE_NAMES,  # noqa: F401
                    STAGE_PROJECT, STAGE_SORT, CompositeCfg, SplatError)
 from .camera import Camera  # noqa: F401
-from .host import (Buffer, CommandEncoder, ComputeShaderRenderer, DepthKeyExtractor, Device, GPUTileBinner,  # noqa: F401
+from .host import (Buffer, CommandEncoder, ComputeShaderRenderer, DepthKeyExtractor, Device, GaussianCloud, GPUTileBinner,  # noqa: F401
                    PerTileSorter, PipelinedRenderer, PointManager, PointRenderer, PrefixSumScanner, PropertyPlanes, RadixSorter, Renderer, SequentialRenderer,
                    SplatProjector, SplatPropertyManager, TileRenderer)
 from .frameloop import FrameLoop, MouseEvent, OrbitCameraController, SdfSplatSource, read_png, write_png  # noqa: F401
 from . import sdf  # noqa: F401
+from .ply import load_gaussian_ply  # noqa: F401
 from .sdf import CurvatureSampler, GradientSampler, PositionUpdater, SDFScene  # noqa: F401

@@ -21,7 +21,7 @@ STAGE_NAMES = ("project", "sort", "bin", "composite", "exchange", "bin_scatter",
 TIMING_COUNT_ENTRIES = 0x80000000  # splat_set_timing_stages: also count the entries a timed frame's composite staged / consumed
 MODE_FRONT_TO_BACK, MODE_REFERENCE_LITERAL = 0, 1
 RECORDS_PROJECTED, RECORDS_COMPACT, RECORDS_DISC48, RECORDS_LIT32 = 0, 1, 2, 3
-FOOTPRINT_ISOTROPIC, FOOTPRINT_DISC = 0, 1
+FOOTPRINT_ISOTROPIC, FOOTPRINT_DISC, FOOTPRINT_ELLIPSOID = 0, 1, 2
 U32_MAX = 0xFFFFFFFF
 
 
@@ -78,6 +78,10 @@ SIGNATURES = {
     "splat_props_to_planes": (_i, [_vp, _vp, _u32, _vp, _vp]),
     "splat_project": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _u32, _vp, _vp, _vp, _u32]),
     "splat_project_disc": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u32]),
+    "splat_project_ellipsoid": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u32]),
+    "splat_sh_colors": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _vp, _u32, _u32, _vp, _u32, _vp]),
+    "splat_render_frame_ellipsoids": (_i, [_vp, _vp, _vp, C.POINTER(CompositeCfg), C.POINTER(C.c_float), _vp, _vp, _vp, _vp, _u32,
+                                           _u32, _u32, _vp, _vp, _vp, C.POINTER(Aov)]),
     "splat_extract_keys": (_i, [_vp, _vp, _u32, _u32, _vp, _vp]),
     "splat_sort_create": (_i, [_vp, _u32, _pvp]),
     "splat_sort_destroy": (None, [_vp]),

@@ -313,5 +313,6 @@ int project_launch(splat_ctx *ctx, const float *uniforms, const void *pos_radius
                    const BinParams *bp, const TfHistOut *hist_out = nullptr, const void *normals = nullptr,
                    uint32_t normal_stride_vec4 = 1, void *discs = nullptr, // discs != NULL: the oriented-disc footprint (disc.h)
                    const struct LitIO *lit = nullptr,                      // lit->records != NULL: also write lit composite records (shade.h)
-                   uint2 *range_wide = nullptr); // instead of range32 (screens beyond 256 x 256 tiles): the 8-byte range, sort-first
+                   uint2 *range_wide = nullptr, // instead of range32 (screens beyond 256 x 256 tiles): the 8-byte range, sort-first
+                   const struct EllIO *ell = nullptr); // with discs: the anisotropic Gaussian (ellipsoid.h) instead of the disc
 int binner_reserve_range_wide(splat_binner *b, uint32_t n_splats); // the range32 buffer, grown to 8 bytes per splat; its uint2s

@@ -133,13 +133,19 @@ static_assert((1.0f - T_STOP) >= 0.99f && !((1.0f - 0x1.47ae42p-7f) >= 0.99f), "
 
 // exp(-0.5 * d2 / (0.4 * 0.4)) = exp2(d2 * this)   (SequentialRenderer.ts:132-133)
 constexpr float DISC_EXP2_SCALE = -4.508422002777011f;
+// exp(-4.5 d2) = exp2(d2 * this), d2 = u^2 + v^2 = d^T Sigma2^-1 d / 9 of an ellipsoid record (ellipsoid.h): exp(-0.5 d^T Sigma2^-1 d)
+constexpr float ELLIPSOID_EXP2_SCALE = -6.492127684000335f;
+// The exponent scale is a property of the footprint; the disc-record kernels take it at compile time (ELL: the ellipsoid's)
+template <bool ELL> struct FootprintExp2 { static constexpr float scale = ELL ? ELLIPSOID_EXP2_SCALE : DISC_EXP2_SCALE; };
 
 // DISC: the footprint is SequentialRenderer's oriented disc (disc.h) — per entry the 32-byte disc record and
 // the lit colour are staged, a pixel is inside when u^2 + v^2 <= 1 with (u,v) = B*d / (1 - q.d); the
 // coverage masks come from the disc's exact bounds, as the binner's tile ranges do.
 // LIT32: `projected` holds the frame's lit composite records (shade.h) — ONE 32-byte gather per staged entry gives
 // centre, radius and lit colour; colour and normal arrays are not touched.
-template <int MODE, bool EARLY_OUT, bool DISC, bool LIT32>
+// ELL: the ellipsoid's records — the colour's fourth word must be its opacity (lit records carry the depth there: it is read
+// from the colour plane)
+template <int MODE, bool EARLY_OUT, bool DISC, bool LIT32, bool ELL = false>
 __device__ __forceinline__ void fetch_entry(const CompositeParams &p, uint32_t idx, float4 &f_b, float4 &f_b2, float4 &f_c, float4 &f_n,
                                             float &f_r) {
     if constexpr (DISC) {
@@ -147,6 +153,7 @@ __device__ __forceinline__ void fetch_entry(const CompositeParams &p, uint32_t i
         f_b2 = p.projected[(size_t)idx * p.disc_stride + 1];
         if (p.disc_lit) {
             f_c = p.projected[(size_t)idx * p.disc_stride + 2];
+            if (ELL) f_c.w = p.color[(size_t)idx * p.color_stride].w;
             return;
         }
     } else if constexpr (LIT32) {

@@ -40,7 +40,8 @@ __global__ __launch_bounds__(256) void k_lit_colors(const float4 *__restrict__ c
 
 // AOV: also the auxiliary outputs (splat_aov; nearest-on-top only): per staged entry {depth, splat index} beside its
 // parameters, per pixel an AovPixel fed with the colour's own weight
-template <int MODE, bool EARLY_OUT, bool DISC, bool LIT32, bool AOV = false>
+// ELL (with DISC): the records are the anisotropic Gaussian's (ellipsoid.h) — the disc footprint with its own exponent scale
+template <int MODE, bool EARLY_OUT, bool DISC, bool LIT32, bool AOV = false, bool ELL = false>
 __global__ __launch_bounds__(256) void k_composite(CompositeParams p) {
     // per entry one 32-byte record {centre.x, centre.y, exp2 scale, lit blue | lit red, lit green, -, -}: both
     // halves are read off ONE address register (ds_read_b128 + ds_read_b64 offset:16), and forming an LDS
@@ -106,11 +107,11 @@ __global__ __launch_bounds__(256) void k_composite(CompositeParams p) {
             const uint32_t e = base + tid;
             float4 geo = make_float4(0.0f, 0.0f, 0.0f, 0.0f), geo2 = geo;
             float2 col = make_float2(0.0f, 0.0f);
-            float col_b = 0.0f;
+            float col_b = 0.0f, col_o = 0.0f;
             uint32_t xm = 0, ym = 0;
             if (!f_ready) { // the first three batches of a tile: fetch now
                 f_idx = (tid < CBATCH && e < count) ? p.indices[off + e] : 0xffffffffu;
-                if (f_idx != 0xffffffffu) fetch_entry<MODE, EARLY_OUT, DISC, LIT32>(p, f_idx, f_b, f_b2, f_c, f_n, f_r);
+                if (f_idx != 0xffffffffu) fetch_entry<MODE, EARLY_OUT, DISC, LIT32, ELL>(p, f_idx, f_b, f_b2, f_c, f_n, f_r);
                 if constexpr (AOV) f_zi = aov_entry(p, f_idx);
             }
             if (DISC && f_idx != 0xffffffffu) {
@@ -120,6 +121,7 @@ __global__ __launch_bounds__(256) void k_composite(CompositeParams p) {
                     const float4 c = (p.prelit || p.disc_lit) ? f_c : lit_color(f_c, f_n);
                     col = make_float2(c.x, c.y);
                     col_b = c.z;
+                    col_o = c.w;
                     geo = make_float4(f_b.x, f_b.y, -f_b2.z, -f_b2.w);
                     geo2 = make_float4(f_b.z, f_b2.x, f_b.w, f_b2.y);
                     xm = span_mask16(bnd.x, bnd.z, tile_cx);
@@ -148,7 +150,7 @@ __global__ __launch_bounds__(256) void k_composite(CompositeParams p) {
                 s_par[tid][0] = geo;
                 if constexpr (DISC) {
                     s_par[tid][1] = geo2;
-                    s_par[tid][2] = make_float4(col.x, col.y, col_b, 0.0f);
+                    s_par[tid][2] = make_float4(col.x, col.y, col_b, ELL ? col_o : 0.0f);
                 } else {
                     s_par[tid][1] = make_float4(col.x, col.y, 0.0f, 0.0f);
                 }
@@ -163,7 +165,7 @@ __global__ __launch_bounds__(256) void k_composite(CompositeParams p) {
             if (base >= CBATCH) { // a tile that needed a second batch usually needs more
                 if (n_idx_valid) { // index of batch k+1 arrived a batch ago: its gathers go out now
                     f_idx = n_idx;
-                    if (f_idx != 0xffffffffu) fetch_entry<MODE, EARLY_OUT, DISC, LIT32>(p, f_idx, f_b, f_b2, f_c, f_n, f_r);
+                    if (f_idx != 0xffffffffu) fetch_entry<MODE, EARLY_OUT, DISC, LIT32, ELL>(p, f_idx, f_b, f_b2, f_c, f_n, f_r);
                     if constexpr (AOV) f_zi = aov_entry(p, f_idx);
                     f_ready = true;
                 }
@@ -218,8 +220,12 @@ __global__ __launch_bounds__(256) void k_composite(CompositeParams p) {
                     const v2f uv0 = ((v2f){M0.x, M0.y} * e0.x + (v2f){M0.z, M0.w} * e0.y) * rd0; // B*d / (1 - q.d)
                     const v2f uv1 = ((v2f){M1.x, M1.y} * e1.x + (v2f){M1.z, M1.w} * e1.y) * rd1;
                     const float d0 = uv0.x * uv0.x + uv0.y * uv0.y, d1 = uv1.x * uv1.x + uv1.y * uv1.y; // :126
-                    g0 = (d0 <= 1.0f) ? __builtin_amdgcn_exp2f(d0 * DISC_EXP2_SCALE) : 0.0f; // :128-133 (NaN: outside)
-                    g1 = (d1 <= 1.0f) ? __builtin_amdgcn_exp2f(d1 * DISC_EXP2_SCALE) : 0.0f;
+                    g0 = (d0 <= 1.0f) ? __builtin_amdgcn_exp2f(d0 * FootprintExp2<ELL>::scale) : 0.0f; // :128-133 (NaN: outside)
+                    g1 = (d1 <= 1.0f) ? __builtin_amdgcn_exp2f(d1 * FootprintExp2<ELL>::scale) : 0.0f;
+                    if constexpr (ELL) { // alpha = opacity g (the ellipsoid's opacity rides in the colour's fourth word)
+                        g0 *= L0.w;
+                        g1 *= L1.w;
+                    }
                 } else {
                     C0 = *reinterpret_cast<const float2 *>(&s_par[c0 + j0][1]);
                     C1 = *reinterpret_cast<const float2 *>(&s_par[c0 + j1][1]);
@@ -332,11 +338,14 @@ struct PxRaw {
     float2 zi; // AOV: {depth, splat index (as bits)}
 };
 // DISC (the oriented-disc footprint): a, a2 = the 32-byte disc record (disc.h), c = colour, n = normal
+// ELL: the ellipsoid's opacity in c.w (its lit records carry the depth there: the opacity comes from the colour plane)
+template <bool ELL = false>
 __device__ __forceinline__ void px_fetch_disc(const CompositeParams &p, uint32_t idx, PxRaw &o) {
     o.a = p.projected[(size_t)idx * p.disc_stride];
     o.a2 = p.projected[(size_t)idx * p.disc_stride + 1];
     if (p.disc_lit) { // (lit disc records: one 48-byte gather is all)
         o.c = p.projected[(size_t)idx * p.disc_stride + 2];
+        if (ELL) o.c.w = p.color[(size_t)idx * p.color_stride].w;
         return;
     }
     o.c = p.color[(size_t)idx * p.color_stride];
@@ -551,7 +560,7 @@ __device__ __forceinline__ void px_aov_store(const CompositeParams &p, size_t o,
     if (p.aov_id) p.aov_id[o] = id;
 }
 
-template <bool EARLY_OUT, bool LIT32, bool COUNT, int AH, bool DISC, bool AOV = false>
+template <bool EARLY_OUT, bool LIT32, bool COUNT, int AH, bool DISC, bool AOV = false, bool ELL = false>
 // (the AOV instantiations' sixteen more accumulators per lane do not fit the register budget of PX_WAVES waves per SIMD
 // without spilling: they are allowed the budget of four)
 __global__ __launch_bounds__(128, AOV ? 4 : PX_WAVES) void k_composite_px(CompositeParams p, uint32_t band_tiles) {
@@ -620,7 +629,7 @@ __global__ __launch_bounds__(128, AOV ? 4 : PX_WAVES) void k_composite_px(Compos
 #define PX_FETCH(IDX, DST)                                                                                 \
     do {                                                                                                   \
         const uint32_t i_ = (IDX);                                                                         \
-        if constexpr (DISC) px_fetch_disc(p, i_, DST); else px_fetch<LIT32>(p, i_, DST);                   \
+        if constexpr (DISC) px_fetch_disc<ELL>(p, i_, DST); else px_fetch<LIT32>(p, i_, DST);                   \
         if constexpr (AOV) DST.zi = make_float2(p.aov_z[(size_t)i_ * p.aov_zstride], __uint_as_float(i_)); \
     } while (0)
         PX_FETCH(p.indices[off + min(e, fetch_lim)], ra);
@@ -676,7 +685,10 @@ __global__ __launch_bounds__(128, AOV ? 4 : PX_WAVES) void k_composite_px(Compos
                         B.par[1 + e][0] = make_float4(ra.a.x, ra.a.y, -ra.a2.z, -ra.a2.w);
                         B.par[1 + e][1] = make_float4(ra.a.z, ra.a2.x, ra.a.w, ra.a2.y); // B by columns
                     } else {
-                        B.par[1 + e][2] = make_float4(colr.x, colr.y, colr.z, 1.0f);
+                        // (ELL: alpha = opacity g — the colour premultiplied by the opacity, and the opacity where the disc's
+                        // 1 stands: T loses o T g, C gains c o T g)
+                        if (ELL) B.par[1 + e][2] = make_float4(colr.x * colr.w, colr.y * colr.w, colr.z * colr.w, colr.w);
+                        else B.par[1 + e][2] = make_float4(colr.x, colr.y, colr.z, 1.0f);
                     }
                 } else {
                 const uint32_t p0 = ia >> 1, npairs = m16 ? (ib >> 1) - p0 + 1u : 0u;
@@ -912,7 +924,7 @@ __global__ __launch_bounds__(128, AOV ? 4 : PX_WAVES) void k_composite_px(Compos
         /* :126 u^2 + v^2 = |B d|^2 / (1 - q.d)^2 — in this form no 0 * inf can arise (|B d| = 0 only at the centre, where    \
            1 - q.d = 1): a pixel on the disc plane's horizon line gets inf (outside), never NaN */                            \
         const v2f d2_ = (nu_ * nu_ + nv_ * nv_) * (rd_ * rd_);                                                                \
-        const v2f ar_ = d2_ * (v2f){DISC_EXP2_SCALE, DISC_EXP2_SCALE};                                                        \
+        const v2f ar_ = d2_ * (v2f){FootprintExp2<ELL>::scale, FootprintExp2<ELL>::scale};                                    \
         /* :128-133 discard outside the unit circle, as a factor: clamp((1 - d2) 2^23 + 1, 0, 1) is exactly 1 for d2 <= 1 and  \
            exactly 0 from the next binary32 number above 1 on (and for NaN): one packed multiply-add for two compares + selects */ \
         v2f in_;                                                                                                              \
@@ -1197,7 +1209,8 @@ extern "C" int splat_composite_aov(splat_ctx *ctx, const splat_composite_cfg *cf
     // lit DISC records (48 bytes: the lit colour behind each disc record) exist only inside a frame's binner; a public caller's
     // disc records are the projector's 32-byte ones (splat_project_disc) or 48-byte exchange records (taken at its
     // word this pair would read idx * 48 out of an n * 32 allocation)
-    if (ctx && cfg && cfg->footprint == SPLAT_FOOTPRINT_DISC && cfg->record_format == SPLAT_RECORDS_LIT32)
+    if (ctx && cfg && (cfg->footprint == SPLAT_FOOTPRINT_DISC || cfg->footprint == SPLAT_FOOTPRINT_ELLIPSOID) &&
+        cfg->record_format == SPLAT_RECORDS_LIT32)
         return ctx_fail(ctx, SPLAT_ERR_INVALID, "splat_composite: the oriented-disc footprint composites from SPLAT_RECORDS_PROJECTED (32-byte disc "
                                                 "records) or SPLAT_RECORDS_DISC48; lit disc records are internal to splat_render_frame");
     return composite_launch(ctx, cfg, color_opacity, color_stride_vec4, normals, normal_stride_vec4, projected, tile_indices, tile_counts,
@@ -1251,17 +1264,18 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
     ARG_CHECK(ctx, color_stride_vec4 >= 1 && normal_stride_vec4 >= 1);
     ARG_CHECK(ctx, out_rgba8 || out_rgba32f);
     ARG_CHECK(ctx, (((uintptr_t)color_opacity | (uintptr_t)normals | (uintptr_t)projected | (uintptr_t)out_rgba32f) & 15) == 0);
-    ARG_CHECK(ctx, cfg->prelit <= 1 && cfg->footprint <= SPLAT_FOOTPRINT_DISC);
+    ARG_CHECK(ctx, cfg->prelit <= 1 && cfg->footprint <= SPLAT_FOOTPRINT_ELLIPSOID);
     // the oriented disc is SequentialRenderer's footprint: nearest-on-top "over" is its only blend, and its
-    // records are the projector's 32-byte disc records
-    ARG_CHECK(ctx, cfg->footprint != SPLAT_FOOTPRINT_DISC ||
+    // records are the projector's 32-byte disc records.  The ellipsoid's records are disc records (ellipsoid.h) under the
+    // same rules, and have no 48-byte exchange form: no band frame exists for them
+    ARG_CHECK(ctx, cfg->footprint == SPLAT_FOOTPRINT_ISOTROPIC ||
                        (cfg->mode == SPLAT_COMPOSITE_FRONT_TO_BACK && cfg->record_format != SPLAT_RECORDS_COMPACT));
     ARG_CHECK(ctx, cfg->record_format != SPLAT_RECORDS_DISC48 || cfg->footprint == SPLAT_FOOTPRINT_DISC);
     ARG_CHECK(ctx, (((uintptr_t)disc_depth) & 15) == 0);
     // where the auxiliary outputs' depth comes from: float `off` of every record, `stride` floats apart — the ProjectedSplat's
     // depth (SplatProjector.ts:77), which the compact, lit and 48-byte disc records carry as well; the projector's 32-byte
     // disc records carry none (a frame hands its ProjectedSplat records in as disc_depth when it writes them)
-    const bool is_disc = cfg->footprint == SPLAT_FOOTPRINT_DISC;
+    const bool is_disc = cfg->footprint != SPLAT_FOOTPRINT_ISOTROPIC;
     const float *zsrc = nullptr;
     uint32_t zoff = 0, zstride = 0;
     if (!is_disc) {
@@ -1293,7 +1307,7 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
     p.compact = cfg->record_format == SPLAT_RECORDS_COMPACT;
     p.lit32 = cfg->record_format == SPLAT_RECORDS_LIT32;
     p.prelit = cfg->prelit != 0;
-    p.disc = cfg->footprint == SPLAT_FOOTPRINT_DISC;
+    p.disc = cfg->footprint != SPLAT_FOOTPRINT_ISOTROPIC;
     p.disc_stride = (cfg->record_format == SPLAT_RECORDS_DISC48 || (p.disc && lit32)) ? 3u : 2u;
     p.disc_lit = p.disc && lit32;
     p.indices = (const uint32_t *)tile_indices;
@@ -1324,6 +1338,7 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
     p.aov_z = (aov && aov->depth_f32) ? zsrc + zoff : (const float *)tile_counts;
     p.aov_zstride = (aov && aov->depth_f32) ? zstride : 0u;
     const bool want_aov = aov != nullptr;
+    const bool ell = cfg->footprint == SPLAT_FOOTPRINT_ELLIPSOID;
     if (T != CT) return composite_tile_launch(ctx, cfg, p, nty, r0, r1, launched);
     dim3 grid(ntx, r1 - r0), block(256);
     const bool eo = cfg->early_out != 0;
@@ -1332,10 +1347,11 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
     // splat_stage_time_stats
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
-#define SPLAT_COMPOSITE_LAUNCH1(MODE, EO, DISC, LIT, AOV)                                                                      \
+#define SPLAT_COMPOSITE_LAUNCH1(MODE, EO, DISC, LIT, AOV) SPLAT_COMPOSITE_LAUNCH1_E(MODE, EO, DISC, LIT, AOV, false)
+#define SPLAT_COMPOSITE_LAUNCH1_E(MODE, EO, DISC, LIT, AOV, ELL)                                                                      \
     do {                                                                                                                        \
-        if (timed) hipExtLaunchKernelGGL((k_composite<MODE, EO, DISC, LIT, AOV>), grid, block, 0, ctx->stream, ev0, ev1, 0, p); \
-        else hipLaunchKernelGGL((k_composite<MODE, EO, DISC, LIT, AOV>), grid, block, 0, ctx->stream, p);                     \
+        if (timed) hipExtLaunchKernelGGL((k_composite<MODE, EO, DISC, LIT, AOV, ELL>), grid, block, 0, ctx->stream, ev0, ev1, 0, p); \
+        else hipLaunchKernelGGL((k_composite<MODE, EO, DISC, LIT, AOV, ELL>), grid, block, 0, ctx->stream, p);                     \
     } while (0)
     // (the reference-literal blend has no auxiliary outputs: aov_check refused them)
 #define SPLAT_COMPOSITE_LAUNCH(MODE, EO, DISC, LIT)                                                         \
@@ -1389,7 +1405,10 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
         const dim3 pgrid(band_tiles + 1u), pblock(128);
 #define SPLAT_COMPOSITE_PX_LAUNCH3(EO, LIT, CNT, AH, DISC, AOV)                                                                  \
     do {                                                                                                                        \
-        if (timed) hipExtLaunchKernelGGL((k_composite_px<EO, LIT, CNT, AH, DISC, AOV>), pgrid, pblock, 0, ctx->stream, ev0, ev1, 0, p, band_tiles); \
+        if (ell) {                                                                                                              \
+            if (timed) hipExtLaunchKernelGGL((k_composite_px<EO, LIT, CNT, AH, DISC, AOV, true>), pgrid, pblock, 0, ctx->stream, ev0, ev1, 0, p, band_tiles); \
+            else hipLaunchKernelGGL((k_composite_px<EO, LIT, CNT, AH, DISC, AOV, true>), pgrid, pblock, 0, ctx->stream, p, band_tiles);                       \
+        } else if (timed) hipExtLaunchKernelGGL((k_composite_px<EO, LIT, CNT, AH, DISC, AOV>), pgrid, pblock, 0, ctx->stream, ev0, ev1, 0, p, band_tiles); \
         else hipLaunchKernelGGL((k_composite_px<EO, LIT, CNT, AH, DISC, AOV>), pgrid, pblock, 0, ctx->stream, p, band_tiles);                       \
     } while (0)
 #define SPLAT_COMPOSITE_PX_LAUNCH2(EO, LIT, CNT, AH, DISC)                          \
@@ -1407,7 +1426,7 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
             else            SPLAT_COMPOSITE_PX_LAUNCH2(EO, LIT, false, 1, DISC);       \
         }                                                                              \
     } while (0)
-        if (p.disc) { // the oriented disc: per-lane queues as well, the footprint evaluated per queued pixel
+        if (p.disc) { // the oriented disc (and the ellipsoid): per-lane queues as well, the footprint evaluated per queued pixel
             if (eo) SPLAT_COMPOSITE_PX_LAUNCH(true, false, true);
             else    SPLAT_COMPOSITE_PX_LAUNCH(false, false, true);
         } else if (lit32) {
@@ -1425,7 +1444,13 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
         return SPLAT_OK;
     }
     timed = stage_event_pair(ctx, SPLAT_STAGE_COMPOSITE, &ev0, &ev1);
-    if (p.disc) {
+    if (ell) {
+        constexpr int F2B = SPLAT_COMPOSITE_FRONT_TO_BACK;
+        if (eo && want_aov) SPLAT_COMPOSITE_LAUNCH1_E(F2B, true, true, false, true, true);
+        else if (eo)        SPLAT_COMPOSITE_LAUNCH1_E(F2B, true, true, false, false, true);
+        else if (want_aov)  SPLAT_COMPOSITE_LAUNCH1_E(F2B, false, true, false, true, true);
+        else                SPLAT_COMPOSITE_LAUNCH1_E(F2B, false, true, false, false, true);
+    } else if (p.disc) {
         if (eo) SPLAT_COMPOSITE_LAUNCH(SPLAT_COMPOSITE_FRONT_TO_BACK, true, true, false);
         else    SPLAT_COMPOSITE_LAUNCH(SPLAT_COMPOSITE_FRONT_TO_BACK, false, true, false);
     } else if (cfg->mode == SPLAT_COMPOSITE_FRONT_TO_BACK) {
@@ -1446,6 +1471,7 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
         }
     }
 #undef SPLAT_COMPOSITE_LAUNCH1
+#undef SPLAT_COMPOSITE_LAUNCH1_E
 #undef SPLAT_COMPOSITE_LAUNCH
     *launched = hipPeekAtLastError() == hipSuccess;
     LAUNCH_CHECK(ctx, "k_composite");

@@ -20,7 +20,8 @@
 
 // AOV: also the auxiliary outputs (splat_aov; nearest-on-top only): per staged entry {depth, splat index} beside its
 // parameters, per pixel an AovPixel fed with the colour's own weight
-template <int MODE, bool EARLY_OUT, bool DISC, bool LIT32, bool AOV = false>
+// ELL (with DISC): the anisotropic Gaussian's records (ellipsoid.h): the disc footprint with its own exponent scale
+template <int MODE, bool EARLY_OUT, bool DISC, bool LIT32, bool AOV = false, bool ELL = false>
 __global__ __launch_bounds__(256) void k_composite_tile(CompositeParams p, uint32_t T, uint32_t wpt, uint2 *win_counts) {
     // per entry one 32-byte record {centre.x, centre.y, exp2 scale, lit blue | lit red, lit green, -, -}: both
     // halves are read off ONE address register (ds_read_b128 + ds_read_b64 offset:16), and forming an LDS
@@ -93,11 +94,11 @@ __global__ __launch_bounds__(256) void k_composite_tile(CompositeParams p, uint3
             const uint32_t e = base + tid;
             float4 geo = make_float4(0.0f, 0.0f, 0.0f, 0.0f), geo2 = geo;
             float2 col = make_float2(0.0f, 0.0f);
-            float col_b = 0.0f;
+            float col_b = 0.0f, col_o = 0.0f;
             uint32_t xm = 0, ym = 0;
             if (!f_ready) { // the first three batches of a tile: fetch now
                 f_idx = (tid < CBATCH && e < count) ? p.indices[off + e] : 0xffffffffu;
-                if (f_idx != 0xffffffffu) fetch_entry<MODE, EARLY_OUT, DISC, LIT32>(p, f_idx, f_b, f_b2, f_c, f_n, f_r);
+                if (f_idx != 0xffffffffu) fetch_entry<MODE, EARLY_OUT, DISC, LIT32, ELL>(p, f_idx, f_b, f_b2, f_c, f_n, f_r);
                 if constexpr (AOV) f_zi = aov_entry(p, f_idx);
             }
             if (DISC && f_idx != 0xffffffffu) {
@@ -107,6 +108,7 @@ __global__ __launch_bounds__(256) void k_composite_tile(CompositeParams p, uint3
                     const float4 c = (p.prelit || p.disc_lit) ? f_c : lit_color(f_c, f_n);
                     col = make_float2(c.x, c.y);
                     col_b = c.z;
+                    col_o = c.w;
                     geo = make_float4(f_b.x, f_b.y, -f_b2.z, -f_b2.w);
                     geo2 = make_float4(f_b.z, f_b2.x, f_b.w, f_b2.y);
                     xm = span_mask16(bnd.x, bnd.z, win_cx);
@@ -135,7 +137,7 @@ __global__ __launch_bounds__(256) void k_composite_tile(CompositeParams p, uint3
                 s_par[tid][0] = geo;
                 if constexpr (DISC) {
                     s_par[tid][1] = geo2;
-                    s_par[tid][2] = make_float4(col.x, col.y, col_b, 0.0f);
+                    s_par[tid][2] = make_float4(col.x, col.y, col_b, ELL ? col_o : 0.0f);
                 } else {
                     s_par[tid][1] = make_float4(col.x, col.y, 0.0f, 0.0f);
                 }
@@ -150,7 +152,7 @@ __global__ __launch_bounds__(256) void k_composite_tile(CompositeParams p, uint3
             if (base >= CBATCH) { // a tile that needed a second batch usually needs more
                 if (n_idx_valid) { // index of batch k+1 arrived a batch ago: its gathers go out now
                     f_idx = n_idx;
-                    if (f_idx != 0xffffffffu) fetch_entry<MODE, EARLY_OUT, DISC, LIT32>(p, f_idx, f_b, f_b2, f_c, f_n, f_r);
+                    if (f_idx != 0xffffffffu) fetch_entry<MODE, EARLY_OUT, DISC, LIT32, ELL>(p, f_idx, f_b, f_b2, f_c, f_n, f_r);
                     if constexpr (AOV) f_zi = aov_entry(p, f_idx);
                     f_ready = true;
                 }
@@ -205,8 +207,12 @@ __global__ __launch_bounds__(256) void k_composite_tile(CompositeParams p, uint3
                     const v2f uv0 = ((v2f){M0.x, M0.y} * e0.x + (v2f){M0.z, M0.w} * e0.y) * rd0; // B*d / (1 - q.d)
                     const v2f uv1 = ((v2f){M1.x, M1.y} * e1.x + (v2f){M1.z, M1.w} * e1.y) * rd1;
                     const float d0 = uv0.x * uv0.x + uv0.y * uv0.y, d1 = uv1.x * uv1.x + uv1.y * uv1.y; // :126
-                    g0 = (d0 <= 1.0f) ? __builtin_amdgcn_exp2f(d0 * DISC_EXP2_SCALE) : 0.0f; // :128-133 (NaN: outside)
-                    g1 = (d1 <= 1.0f) ? __builtin_amdgcn_exp2f(d1 * DISC_EXP2_SCALE) : 0.0f;
+                    g0 = (d0 <= 1.0f) ? __builtin_amdgcn_exp2f(d0 * FootprintExp2<ELL>::scale) : 0.0f; // :128-133 (NaN: outside)
+                    g1 = (d1 <= 1.0f) ? __builtin_amdgcn_exp2f(d1 * FootprintExp2<ELL>::scale) : 0.0f;
+                    if constexpr (ELL) { // alpha = opacity g (the ellipsoid's opacity rides in the colour's fourth word)
+                        g0 *= L0.w;
+                        g1 *= L1.w;
+                    }
                 } else {
                     C0 = *reinterpret_cast<const float2 *>(&s_par[c0 + j0][1]);
                     C1 = *reinterpret_cast<const float2 *>(&s_par[c0 + j1][1]);
@@ -350,7 +356,19 @@ int composite_tile_launch(splat_ctx *ctx, const splat_composite_cfg *cfg, const 
         if (MODE == SPLAT_COMPOSITE_FRONT_TO_BACK && want_aov) SPLAT_COMPOSITE_TILE_LAUNCH1(SPLAT_COMPOSITE_FRONT_TO_BACK, EO, DISC, LIT, true); \
         else SPLAT_COMPOSITE_TILE_LAUNCH1(MODE, EO, DISC, LIT, false);                                                     \
     } while (0)
-    if (p.disc) {
+    if (cfg->footprint == SPLAT_FOOTPRINT_ELLIPSOID) {
+        constexpr int F2B = SPLAT_COMPOSITE_FRONT_TO_BACK;
+#define SPLAT_COMPOSITE_TILE_LAUNCH_ELL(EO, AOV)                                                                                                       \
+    do {                                                                                                                                               \
+        if (timed) hipExtLaunchKernelGGL((k_composite_tile<F2B, EO, true, false, AOV, true>), grid, block, 0, ctx->stream, ev0, ev1, 0, p, T, wpt, win_counts); \
+        else hipLaunchKernelGGL((k_composite_tile<F2B, EO, true, false, AOV, true>), grid, block, 0, ctx->stream, p, T, wpt, win_counts);                       \
+    } while (0)
+        if (eo && want_aov) SPLAT_COMPOSITE_TILE_LAUNCH_ELL(true, true);
+        else if (eo)        SPLAT_COMPOSITE_TILE_LAUNCH_ELL(true, false);
+        else if (want_aov)  SPLAT_COMPOSITE_TILE_LAUNCH_ELL(false, true);
+        else                SPLAT_COMPOSITE_TILE_LAUNCH_ELL(false, false);
+#undef SPLAT_COMPOSITE_TILE_LAUNCH_ELL
+    } else if (p.disc) {
         if (eo) SPLAT_COMPOSITE_TILE_LAUNCH(SPLAT_COMPOSITE_FRONT_TO_BACK, true, true, false);
         else    SPLAT_COMPOSITE_TILE_LAUNCH(SPLAT_COMPOSITE_FRONT_TO_BACK, false, true, false);
     } else if (cfg->mode == SPLAT_COMPOSITE_FRONT_TO_BACK) {

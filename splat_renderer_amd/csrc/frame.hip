@@ -8,6 +8,7 @@
 #include "common.h"
 #include "tile_range.h"
 #include "disc.h"
+#include "ellipsoid.h"
 #include "shade.h"
 
 #include <cstdlib>
@@ -700,23 +701,26 @@ int splat_band_kept(splat_ctx *ctx, splat_sorter *sorter, uint32_t *n_kept_host)
 static int render_frame_impl(splat_ctx *ctx, splat_sorter *sorter, splat_binner *binner, const splat_composite_cfg *cfg,
                              const float *uniforms, const void *props, uint32_t pos_stride, const void *color,
                              uint32_t color_stride, const void *normals, uint32_t n, uint32_t width, uint32_t height,
-                             void *projected, void *out_rgba8, void *out_rgba32f, const splat_aov *aov) {
+                             void *projected, void *out_rgba8, void *out_rgba32f, const splat_aov *aov, const EllIO *ell = nullptr) {
     if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
     ARG_CHECK(ctx, sorter && binner && cfg && uniforms && props && color && (normals || cfg->prelit));
     ARG_CHECK(ctx, cfg->tile_size == splat_bin_tile_size(binner));
-    ARG_CHECK(ctx, cfg->footprint <= SPLAT_FOOTPRINT_DISC);
+    // the anisotropic Gaussian (ellipsoid.h) comes with its planes, through splat_render_frame_ellipsoids only
+    ARG_CHECK(ctx, cfg->footprint <= SPLAT_FOOTPRINT_ELLIPSOID && (cfg->footprint == SPLAT_FOOTPRINT_ELLIPSOID) == (ell != nullptr));
     // the ProjectedSplat records are the isotropic composite's input; a disc frame reads its disc records instead and
     // may leave them out (160 MB of stores per 5M splats that nothing reads)
-    ARG_CHECK(ctx, projected || cfg->footprint == SPLAT_FOOTPRINT_DISC);
-    // the oriented disc (SequentialRenderer's footprint): its projector needs the normals, its records live with the binner
-    const bool disc = cfg->footprint == SPLAT_FOOTPRINT_DISC;
+    ARG_CHECK(ctx, projected || cfg->footprint != SPLAT_FOOTPRINT_ISOTROPIC);
+    // the oriented disc (SequentialRenderer's footprint): its projector needs the normals, its records live with the binner.
+    // An ellipsoid frame is a disc frame whose records come from the ellipsoid projector: final colours, no normals.
+    const bool disc = cfg->footprint != SPLAT_FOOTPRINT_ISOTROPIC;
+    ARG_CHECK(ctx, !ell || (cfg->prelit == 1 && normals == nullptr));
     // cfg->record_format says what the frame leaves in `projected` and composites from: the reference's ProjectedSplat
     // records, or the lit composite records (shade.h) — one gathered line per staged list entry instead of three
     // (a disc frame with SPLAT_RECORDS_LIT32: the lit colour rides behind each 32-byte disc record — 48-byte records, owned by the
     // binner like the plain disc records — and the composite gathers that one record per staged entry)
     ARG_CHECK(ctx, cfg->record_format == SPLAT_RECORDS_PROJECTED || cfg->record_format == SPLAT_RECORDS_LIT32);
     const bool lit = cfg->record_format == SPLAT_RECORDS_LIT32 && !disc, disc_lit = cfg->record_format == SPLAT_RECORDS_LIT32 && disc;
-    ARG_CHECK(ctx, !disc || (normals && (((uintptr_t)normals) & 15) == 0));
+    ARG_CHECK(ctx, !disc || ell || (normals && (((uintptr_t)normals) & 15) == 0));
     // the auxiliary outputs, checked before anything runs: a disc frame's depth comes from its lit disc records (their fourth
     // colour word carries it) or its ProjectedSplat records; the plain disc records have none
     {
@@ -744,6 +748,8 @@ static int render_frame_impl(splat_ctx *ctx, splat_sorter *sorter, splat_binner 
     uint2 *range_wide = nullptr;
     // (a strict band: the projector skips what provably cannot reach it; those splats' records are then not written)
     const BinParams bp = {width, height, tile, ntx, nty, row0, row1, (row0 > 0 || row1 < nty) ? 1u : 0u};
+    if (ell && bp.skip_outside)
+        return ctx_fail(ctx, SPLAT_ERR_INVALID, "splat_render_frame_ellipsoids: the ellipsoid footprint has no band frame (render every tile row)");
     if (fast) {
         rc = binner_reserve_range32(binner, n);
         if (rc != SPLAT_OK) return rc;
@@ -789,7 +795,7 @@ static int render_frame_impl(splat_ctx *ctx, splat_sorter *sorter, splat_binner 
     const LitIO lio = {(const float4 *)color, (const float4 *)normals, color_stride, 1u, cfg->prelit,
                        lit ? (float4 *)projected : disc_lit ? (float4 *)binner->discs : nullptr};
     rc = project_launch(ctx, uniforms, props, pos_stride, n, 0, lit ? nullptr : projected, splat_sort_keys(sorter), nullptr, n, range32, &bp,
-                        tile_first ? &ho : nullptr, normals, 1, disc ? binner->discs : nullptr, &lio, range_wide);
+                        tile_first ? &ho : nullptr, normals, 1, disc ? binner->discs : nullptr, &lio, range_wide, ell);
     if (rc != SPLAT_OK) return rc;
     binner->tf_hist_ready = tile_first;
     binner->tf_cidx = band_compact ? binner->band_idx : nullptr;
@@ -855,6 +861,19 @@ int splat_render_frame_planes_aov(splat_ctx *ctx, splat_sorter *sorter, splat_bi
                                   const splat_aov *aov) {
     return render_frame_impl(ctx, sorter, binner, cfg, uniforms, pos_radius, 1, color_opacity, 1, normals, n, width, height, projected,
                              out_rgba8, out_rgba32f, aov);
+}
+
+int splat_render_frame_ellipsoids(splat_ctx *ctx, splat_sorter *sorter, splat_binner *binner, const splat_composite_cfg *cfg,
+                                  const float *uniforms, const void *positions, const void *scales, const void *rotations,
+                                  const void *color_opacity, uint32_t n, uint32_t width, uint32_t height, void *projected, void *out_rgba8,
+                                  void *out_rgba32f, const splat_aov *aov) {
+    if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
+    ARG_CHECK(ctx, cfg && cfg->footprint == SPLAT_FOOTPRINT_ELLIPSOID);
+    ARG_CHECK(ctx, n == 0 || (scales && rotations));
+    ARG_CHECK(ctx, (((uintptr_t)scales | (uintptr_t)rotations | (uintptr_t)color_opacity) & 15) == 0);
+    const EllIO ell = {(const float4 *)scales, 1u, (const float4 *)rotations, 1u};
+    return render_frame_impl(ctx, sorter, binner, cfg, uniforms, positions, 1, color_opacity, 1, nullptr, n, width, height, projected,
+                             out_rgba8, out_rgba32f, aov, &ell);
 }
 
 } // extern "C"

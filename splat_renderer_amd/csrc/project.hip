@@ -12,6 +12,7 @@
 #include "common.h"
 #include "tile_range.h"
 #include "disc.h"
+#include "ellipsoid.h"
 #include "shade.h"
 
 struct FrameUniforms {
@@ -67,6 +68,7 @@ struct DiscIO {
     uint32_t normal_stride;
     float4 *discs;
     uint32_t disc_stride; // float4s per record: 2, or 3 when the frame asks for LIT disc records (the splat's lit colour behind the record)
+    EllIO ell;            // ELL (the anisotropic Gaussian, ellipsoid.h): its planes instead of the normals
 };
 
 // Band frames without an exchange (every rank projects all splats): most splats cannot reach the rank's
@@ -119,15 +121,19 @@ __device__ __forceinline__ bool cannot_reach_band(const FrameUniforms &u, float4
 // compiler the loads stay behind the previous splat's stores — the output pointers may alias the inputs for all it
 // knows — and every wave sits out two memory round trips per splat.
 struct SplatIn {
-    float4 pr, col, nrm;
+    float4 pr, col, nrm, scl, rot;
 };
-template <bool DISC, bool LIT>
+// ELL (with DISC): the anisotropic Gaussian (ellipsoid.h) — scale and rotation instead of the normal, written as a disc record
+template <bool DISC, bool LIT, bool ELL = false>
 __device__ __forceinline__ SplatIn load_splat(const float4 *__restrict__ pos_radius, uint32_t stride_vec4, uint32_t i, const DiscIO &dio,
                                               const LitIO &lio) {
     SplatIn s;
     s.pr = pos_radius[(size_t)i * stride_vec4];
-    s.col = s.nrm = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (DISC) s.nrm = dio.normals[(size_t)i * dio.normal_stride];
+    s.col = s.nrm = s.scl = s.rot = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (ELL) {
+        s.scl = dio.ell.scales[(size_t)i * dio.ell.scale_stride];
+        s.rot = dio.ell.rotations[(size_t)i * dio.ell.rot_stride];
+    } else if (DISC) s.nrm = dio.normals[(size_t)i * dio.normal_stride];
     if (LIT) {
         s.col = lio.color[(size_t)i * lio.color_stride];
         if (!lio.prelit) s.nrm = lio.normals[(size_t)i * lio.normal_stride];
@@ -137,7 +143,7 @@ __device__ __forceinline__ SplatIn load_splat(const float4 *__restrict__ pos_rad
 
 // WIDE (screens beyond 256 x 256 tiles): the range goes to range32 as an 8-byte pack_range_wide (range32 then points at
 // uint2s); the return value is then not a range.
-template <bool WITH_KEYS, bool WITH_RANGE, bool DISC, bool LIT = false, bool WIDE = false>
+template <bool WITH_KEYS, bool WITH_RANGE, bool DISC, bool LIT = false, bool WIDE = false, bool ELL = false>
 __device__ __forceinline__ uint32_t project_one(const FrameUniforms &u, const SplatIn &in, uint32_t i, uint32_t index_base,
                                                 float4 *__restrict__ projected, uint32_t *__restrict__ keys,
                                                 uint32_t *__restrict__ payload, uint32_t *__restrict__ range32, const BinParams &bp,
@@ -147,7 +153,7 @@ __device__ __forceinline__ uint32_t project_one(const FrameUniforms &u, const Sp
     float depth;
     if (DISC) {
         const float4 pr = in.pr;
-        const DiscRecord d = disc_record(u.m, u.w, u.h, pr, in.nrm);
+        const DiscRecord d = ELL ? ellipsoid_record(u.m, u.w, u.h, pr, in.scl, in.rot) : disc_record(u.m, u.w, u.h, pr, in.nrm);
         dio.discs[(size_t)i * dio.disc_stride] = d.a;
         dio.discs[(size_t)i * dio.disc_stride + 1] = d.b;
         // LIT: the lit colour rides behind the record (48 bytes per splat): the disc frame's composite then gathers this one
@@ -157,7 +163,7 @@ __device__ __forceinline__ uint32_t project_one(const FrameUniforms &u, const Sp
         depth = sqrtf((dx * dx + dy * dy) + dz * dz); // SplatProjector.ts:77: the sort key does not depend on the footprint
         // (the fourth word, the opacity the composite never reads, carries the depth instead: the auxiliary outputs' splat_aov)
         if (LIT) {
-            const float4 lc = lio.prelit ? in.col : lit_color(in.col, in.nrm);
+            const float4 lc = (ELL || lio.prelit) ? in.col : lit_color(in.col, in.nrm); // (an ellipsoid's colour is final: prelit)
             dio.discs[(size_t)i * dio.disc_stride + 2] = make_float4(lc.x, lc.y, lc.z, depth);
         }
         disc_bounds(d, a);
@@ -231,7 +237,7 @@ __global__ __launch_bounds__(256) void k_expand_compact(const float4 *__restrict
     projected[(size_t)i * 2 + 1] = make_float4(c.w, c.z, __uint_as_float(index_base + i), 0.0f);
 }
 
-template <bool WITH_KEYS, bool WITH_RANGE, bool DISC, bool LIT = false>
+template <bool WITH_KEYS, bool WITH_RANGE, bool DISC, bool LIT = false, bool ELL = false>
 __global__ __launch_bounds__(256) void k_project(FrameUniforms u, const float4 *__restrict__ pos_radius,
                                                  uint32_t stride_vec4, uint32_t n, uint32_t n_padded, uint32_t index_base,
                                                  float4 *__restrict__ projected, uint32_t *__restrict__ keys,
@@ -245,13 +251,13 @@ __global__ __launch_bounds__(256) void k_project(FrameUniforms u, const float4 *
         }
         return;
     }
-    const SplatIn in = load_splat<DISC, LIT>(pos_radius, stride_vec4, i, dio, lio);
-    project_one<WITH_KEYS, WITH_RANGE, DISC, LIT>(u, in, i, index_base, projected, keys, payload, range32, bp, dio, lio);
+    const SplatIn in = load_splat<DISC, LIT, ELL>(pos_radius, stride_vec4, i, dio, lio);
+    project_one<WITH_KEYS, WITH_RANGE, DISC, LIT, false, ELL>(u, in, i, index_base, projected, keys, payload, range32, bp, dio, lio);
 }
 
 // The frame's projector on screens beyond 256 x 256 tiles (sort-first only): k_project<true, true, DISC, LIT> with the
 // 8-byte wide range per splat index instead of range32 (no payload: the sort's first pass synthesises it).
-template <bool DISC, bool LIT>
+template <bool DISC, bool LIT, bool ELL = false>
 __global__ __launch_bounds__(256) void k_project_wide(FrameUniforms u, const float4 *__restrict__ pos_radius, uint32_t stride_vec4,
                                                       uint32_t n, uint32_t n_padded, float4 *__restrict__ projected,
                                                       uint32_t *__restrict__ keys, uint2 *__restrict__ range_wide, BinParams bp,
@@ -261,16 +267,16 @@ __global__ __launch_bounds__(256) void k_project_wide(FrameUniforms u, const flo
         if (i < n_padded) keys[i] = 0xffffffffu;
         return;
     }
-    const SplatIn in = load_splat<DISC, LIT>(pos_radius, stride_vec4, i, dio, lio);
-    project_one<true, true, DISC, LIT, true>(u, in, i, 0, projected, keys, nullptr, reinterpret_cast<uint32_t *>(range_wide), bp, dio,
-                                             lio);
+    const SplatIn in = load_splat<DISC, LIT, ELL>(pos_radius, stride_vec4, i, dio, lio);
+    project_one<true, true, DISC, LIT, true, ELL>(u, in, i, 0, projected, keys, nullptr, reinterpret_cast<uint32_t *>(range_wide), bp, dio,
+                                                  lio);
 }
 
 // Tile-first frame path: 1024 splats per workgroup (the binner's block), and while each splat's tile
 // rectangle is in registers the block's pairs are counted per low tile-id digit — the histogram the
 // first pass of the tile-id sort needs (tile_first.hip; k_band_prepare_tf in frame.hip does the same for
 // the gathered records of a multi-GPU band).  The kernel is HBM-bound; the LDS counting hides under the stores.
-template <bool DISC, bool LIT, uint32_t PER, uint32_t AHEAD = 1>
+template <bool DISC, bool LIT, uint32_t PER, uint32_t AHEAD = 1, bool ELL = false>
 __global__ __launch_bounds__(256) void k_project_hist(FrameUniforms u, const float4 *__restrict__ pos_radius, uint32_t stride_vec4,
                                                       uint32_t n, uint32_t n_padded, float4 *__restrict__ projected,
                                                       uint32_t *__restrict__ keys, uint32_t *__restrict__ range32, BinParams bp,
@@ -284,7 +290,7 @@ __global__ __launch_bounds__(256) void k_project_hist(FrameUniforms u, const flo
 #pragma unroll
     for (uint32_t k = 0; k < AHEAD; ++k) { // AHEAD splats' loads in flight before the first dependent instruction
         const uint32_t i = blk * (PER * 256u) + k * 256u + tid;
-        if (i < n) in[k] = load_splat<DISC, LIT>(pos_radius, stride_vec4, i, dio, lio);
+        if (i < n) in[k] = load_splat<DISC, LIT, ELL>(pos_radius, stride_vec4, i, dio, lio);
     }
     if (blk == 0 && tid == 0) *ho.overflow_flag = 0;
     for (uint32_t j = tid; j < 4 * 256; j += 256) (&lh[0][0])[j] = 0;
@@ -294,14 +300,14 @@ __global__ __launch_bounds__(256) void k_project_hist(FrameUniforms u, const flo
     for (uint32_t k = 0; k < PER; ++k) { // (PER * 256 splats per workgroup: the binner's block)
         if (k + AHEAD < PER) { // ... and AHEAD of them in flight from then on
             const uint32_t i = blk * (PER * 256u) + (k + AHEAD) * 256u + tid;
-            if (i < n) in[k + AHEAD] = load_splat<DISC, LIT>(pos_radius, stride_vec4, i, dio, lio);
+            if (i < n) in[k + AHEAD] = load_splat<DISC, LIT, ELL>(pos_radius, stride_vec4, i, dio, lio);
         }
         const uint32_t i = blk * (PER * 256u) + k * 256u + tid;
         if (i >= n) {
             if (i < n_padded) keys[i] = 0xffffffffu;
             continue;
         }
-        const uint32_t r = project_one<true, true, DISC, LIT>(u, in[k], i, 0, projected, keys, nullptr, range32, bp, dio, lio);
+        const uint32_t r = project_one<true, true, DISC, LIT, false, ELL>(u, in[k], i, 0, projected, keys, nullptr, range32, bp, dio, lio);
         const uint32_t tx0 = r & 0xffu, tx1 = (r >> 8) & 0xffu, ty0 = (r >> 16) & 0xffu, ty1 = r >> 24;
         if (tx0 > tx1 || ty0 > ty1) continue;
         local += hist_add_rect(lh[w], tx0, tx1, ty0, ty1, bp.ntx, ho.mask);
@@ -539,7 +545,7 @@ static void load_uniforms(FrameUniforms &u, const float *uniforms) {
 int project_launch(splat_ctx *ctx, const float *uniforms, const void *pos_radius, uint32_t pr_stride_vec4, uint32_t n,
                    uint32_t index_base, void *projected, void *keys, void *payload, uint32_t n_padded, uint32_t *range32,
                    const BinParams *bp, const TfHistOut *hist_out, const void *normals, uint32_t normal_stride_vec4, void *discs,
-                   const LitIO *lit, uint2 *range_wide) {
+                   const LitIO *lit, uint2 *range_wide, const EllIO *ell) {
     FrameUniforms u;
     load_uniforms(u, uniforms);
     const uint32_t work = keys ? n_padded : n;
@@ -547,33 +553,44 @@ int project_launch(splat_ctx *ctx, const float *uniforms, const void *pos_radius
     BinParams none = {0, 0, 1, 0, 0, 0, 0};
     const float4 *src = (const float4 *)pos_radius + (size_t)index_base * pr_stride_vec4;
     const bool disc = discs != nullptr; // the oriented-disc footprint (disc.h): normals in, disc records out
+    // ... or the anisotropic Gaussian's (ellipsoid.h): scales and rotations in, disc records out (not on the band paths)
+    const bool el = disc && ell != nullptr;
+    if (el && hist_out && bp && bp->skip_outside)
+        return ctx_fail(ctx, SPLAT_ERR_INVALID, "project_launch: the ellipsoid footprint has no band projector");
     // lit composite records (shade.h) of an isotropic frame, written next to the keys and tile ranges; a disc frame's lit
     // colours go behind its disc records (lit->records = discs there: 48-byte records)
     const bool with_lit = lit && lit->records && !disc, disc_lit = lit && lit->records && disc;
     if ((with_lit || disc_lit) && !(keys && (range32 || range_wide) && !payload && index_base == 0))
         return ctx_fail(ctx, SPLAT_ERR_INVALID, "project_launch: lit records are written by the frame's projector only");
-    const DiscIO dio = {disc ? (const float4 *)normals + (size_t)index_base * normal_stride_vec4 : nullptr, normal_stride_vec4,
-                        (float4 *)discs, disc_lit ? 3u : 2u};
+    DiscIO dio = {(disc && !el) ? (const float4 *)normals + (size_t)index_base * normal_stride_vec4 : nullptr, normal_stride_vec4,
+                  (float4 *)discs, disc_lit ? 3u : 2u, EllIO{}};
+    if (el) {
+        dio.ell = *ell;
+        dio.ell.scales += (size_t)index_base * ell->scale_stride;
+        dio.ell.rotations += (size_t)index_base * ell->rot_stride;
+    }
     const LitIO lio = (with_lit || disc_lit) ? *lit : LitIO{};
     stage_begin(ctx, SPLAT_STAGE_PROJECT);
     dim3 grid(div_up(work, 256)), block(256);
-#define SPLAT_PROJECT_LAUNCH(K, R, D, L, RANGE, BP)                                                                                \
-    hipLaunchKernelGGL((k_project<K, R, D, L>), grid, block, 0, ctx->stream, u, src, pr_stride_vec4, n, keys ? n_padded : n, index_base, \
+#define SPLAT_PROJECT_LAUNCH_E(K, R, D, L, E, RANGE, BP)                                                                                \
+    hipLaunchKernelGGL((k_project<K, R, D, L, E>), grid, block, 0, ctx->stream, u, src, pr_stride_vec4, n, keys ? n_padded : n, index_base, \
                        (float4 *)projected, (uint32_t *)keys, (uint32_t *)payload, RANGE, BP, dio, lio)
+#define SPLAT_PROJECT_LAUNCH(K, R, D, L, RANGE, BP) SPLAT_PROJECT_LAUNCH_E(K, R, D, L, false, RANGE, BP)
 #define SPLAT_PROJECT_HIST_LAUNCH(KERNEL, D, L)                                                                               \
     hipLaunchKernelGGL((KERNEL<D, L>), dim3(div_up(work, 1024)), block, 0, ctx->stream, u, src, pr_stride_vec4, n, n_padded, \
                        (float4 *)projected, (uint32_t *)keys, range32, *bp, *hist_out, dio, lio)
-#define SPLAT_PROJECT_HIST_LAUNCH_PER(D, L)                                                                                                \
+#define SPLAT_PROJECT_HIST_LAUNCH_PER(D, L) SPLAT_PROJECT_HIST_LAUNCH_PER_E(D, L, false)
+#define SPLAT_PROJECT_HIST_LAUNCH_PER_E(D, L, E)                                                                                           \
     do {                                                                                                                                   \
         TfHistOut ho_ = *hist_out;                                                                                                         \
         const uint32_t blocks_ = div_up(work, hist_out->block == TF_BLOCK_SMALL ? 256u : 1024u);                                           \
         ho_.xcd_per = blocks_ >= 64u ? div_up(blocks_, 8u) : 0u; /* the blocks dealt as k_tf_scatter's are (common.h: xcd_block_of) */      \
         const dim3 grid_(ho_.xcd_per ? 8u * ho_.xcd_per : blocks_);                                                                        \
         if (hist_out->block == TF_BLOCK_SMALL)                                                                                             \
-            hipLaunchKernelGGL((k_project_hist<D, L, 1>), grid_, block, 0, ctx->stream, u, src, pr_stride_vec4, n, n_padded,               \
+            hipLaunchKernelGGL((k_project_hist<D, L, 1, 1, E>), grid_, block, 0, ctx->stream, u, src, pr_stride_vec4, n, n_padded,               \
                                (float4 *)projected, (uint32_t *)keys, range32, *bp, ho_, dio, lio);                                        \
         else                                                                                                                               \
-            hipLaunchKernelGGL((k_project_hist<D, L, 4>), grid_, block, 0, ctx->stream, u, src, pr_stride_vec4, n, n_padded,               \
+            hipLaunchKernelGGL((k_project_hist<D, L, 4, 1, E>), grid_, block, 0, ctx->stream, u, src, pr_stride_vec4, n, n_padded,               \
                                (float4 *)projected, (uint32_t *)keys, range32, *bp, ho_, dio, lio);                                        \
     } while (0)
     if (hist_out && hist_out->cidx && bp->skip_outside && keys && range32 && !payload && index_base == 0) {
@@ -591,7 +608,9 @@ int project_launch(splat_ctx *ctx, const float *uniforms, const void *pos_radius
 #undef SPLAT_PROJECT_BANDC
     } else if (hist_out && keys && range32 && !payload && index_base == 0) {
         // (a strict band's kernel works in 1024-splat blocks only: the caller keeps hist_out->block at TF_BLOCK_LARGE for it)
-        if (disc_lit && bp->skip_outside) SPLAT_PROJECT_HIST_LAUNCH(k_project_hist_band, true, true);
+        if (el && disc_lit) SPLAT_PROJECT_HIST_LAUNCH_PER_E(true, true, true);
+        else if (el) SPLAT_PROJECT_HIST_LAUNCH_PER_E(true, false, true);
+        else if (disc_lit && bp->skip_outside) SPLAT_PROJECT_HIST_LAUNCH(k_project_hist_band, true, true);
         else if (disc_lit) SPLAT_PROJECT_HIST_LAUNCH_PER(true, true);
         else if (disc && bp->skip_outside) SPLAT_PROJECT_HIST_LAUNCH(k_project_hist_band, true, false);
         else if (disc) SPLAT_PROJECT_HIST_LAUNCH_PER(true, false);
@@ -600,29 +619,39 @@ int project_launch(splat_ctx *ctx, const float *uniforms, const void *pos_radius
         else if (with_lit) SPLAT_PROJECT_HIST_LAUNCH_PER(false, true);
         else SPLAT_PROJECT_HIST_LAUNCH_PER(false, false);
     } else if (keys && range_wide && !payload && index_base == 0) {
-#define SPLAT_PROJECT_WIDE(D, L)                                                                                                   \
-    hipLaunchKernelGGL((k_project_wide<D, L>), grid, block, 0, ctx->stream, u, src, pr_stride_vec4, n, n_padded, (float4 *)projected, \
+#define SPLAT_PROJECT_WIDE(D, L) SPLAT_PROJECT_WIDE_E(D, L, false)
+#define SPLAT_PROJECT_WIDE_E(D, L, E)                                                                                              \
+    hipLaunchKernelGGL((k_project_wide<D, L, E>), grid, block, 0, ctx->stream, u, src, pr_stride_vec4, n, n_padded, (float4 *)projected, \
                        (uint32_t *)keys, range_wide, *bp, dio, lio)
-        if (disc_lit) SPLAT_PROJECT_WIDE(true, true);
+        if (el && disc_lit) SPLAT_PROJECT_WIDE_E(true, true, true);
+        else if (el) SPLAT_PROJECT_WIDE_E(true, false, true);
+        else if (disc_lit) SPLAT_PROJECT_WIDE(true, true);
         else if (disc) SPLAT_PROJECT_WIDE(true, false);
         else if (with_lit) SPLAT_PROJECT_WIDE(false, true);
         else SPLAT_PROJECT_WIDE(false, false);
 #undef SPLAT_PROJECT_WIDE
+#undef SPLAT_PROJECT_WIDE_E
     } else if (keys && range32) {
-        if (disc_lit) SPLAT_PROJECT_LAUNCH(true, true, true, true, range32, *bp);
+        if (el && disc_lit) SPLAT_PROJECT_LAUNCH_E(true, true, true, true, true, range32, *bp);
+        else if (el) SPLAT_PROJECT_LAUNCH_E(true, true, true, false, true, range32, *bp);
+        else if (disc_lit) SPLAT_PROJECT_LAUNCH(true, true, true, true, range32, *bp);
         else if (disc) SPLAT_PROJECT_LAUNCH(true, true, true, false, range32, *bp);
         else if (with_lit) SPLAT_PROJECT_LAUNCH(true, true, false, true, range32, *bp);
         else SPLAT_PROJECT_LAUNCH(true, true, false, false, range32, *bp);
     } else if (keys) {
-        if (disc) SPLAT_PROJECT_LAUNCH(true, false, true, false, nullptr, none);
+        if (el) SPLAT_PROJECT_LAUNCH_E(true, false, true, false, true, nullptr, none);
+        else if (disc) SPLAT_PROJECT_LAUNCH(true, false, true, false, nullptr, none);
         else SPLAT_PROJECT_LAUNCH(true, false, false, false, nullptr, none);
     } else {
-        if (disc) SPLAT_PROJECT_LAUNCH(false, false, true, false, nullptr, none);
+        if (el) SPLAT_PROJECT_LAUNCH_E(false, false, true, false, true, nullptr, none);
+        else if (disc) SPLAT_PROJECT_LAUNCH(false, false, true, false, nullptr, none);
         else SPLAT_PROJECT_LAUNCH(false, false, false, false, nullptr, none);
     }
 #undef SPLAT_PROJECT_LAUNCH
+#undef SPLAT_PROJECT_LAUNCH_E
 #undef SPLAT_PROJECT_HIST_LAUNCH
 #undef SPLAT_PROJECT_HIST_LAUNCH_PER
+#undef SPLAT_PROJECT_HIST_LAUNCH_PER_E
     LAUNCH_CHECK(ctx, "k_project");
     stage_end(ctx, SPLAT_STAGE_PROJECT);
     return SPLAT_OK;
@@ -653,6 +682,20 @@ int splat_project_disc(splat_ctx *ctx, const float *uniforms, const void *pos_ra
     // (n == 0 with keys only pads them, which either footprint's kernel does)
     return project_launch(ctx, uniforms, pos_radius, pr_stride_vec4, n, 0, projected, keys, payload, n_padded, nullptr, nullptr, nullptr,
                           normals, normal_stride_vec4, n ? discs : nullptr);
+}
+
+int splat_project_ellipsoid(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4, const void *scales,
+                            uint32_t scale_stride_vec4, const void *rotations, uint32_t rot_stride_vec4, uint32_t n, void *projected,
+                            void *records, void *keys, void *payload, uint32_t n_padded) {
+    if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
+    ARG_CHECK(ctx, uniforms && (n == 0 || (positions && scales && rotations && projected && records)));
+    ARG_CHECK(ctx, pos_stride_vec4 >= 1 && scale_stride_vec4 >= 1 && rot_stride_vec4 >= 1);
+    ARG_CHECK(ctx, (keys == nullptr) == (payload == nullptr));
+    ARG_CHECK(ctx, keys == nullptr || n_padded >= n);
+    ARG_CHECK(ctx, (((uintptr_t)positions | (uintptr_t)scales | (uintptr_t)rotations | (uintptr_t)projected | (uintptr_t)records) & 15) == 0);
+    const EllIO ell = {(const float4 *)scales, scale_stride_vec4, (const float4 *)rotations, rot_stride_vec4};
+    return project_launch(ctx, uniforms, positions, pos_stride_vec4, n, 0, projected, keys, payload, n_padded, nullptr, nullptr, nullptr,
+                          nullptr, 1, n ? records : nullptr, nullptr, nullptr, &ell);
 }
 
 int splat_project_slice(splat_ctx *ctx, const float *uniforms, const void *pos_radius, uint32_t pr_stride_vec4, uint32_t first,

@@ -358,7 +358,86 @@ def _footprint(value):
         return _lib.FOOTPRINT_ISOTROPIC
     if value in ("disc", _lib.FOOTPRINT_DISC):
         return _lib.FOOTPRINT_DISC
-    raise SplatError(-1, f"footprint must be 'isotropic' or 'disc', not {value!r}")
+    if value in ("ellipsoid", _lib.FOOTPRINT_ELLIPSOID):
+        return _lib.FOOTPRINT_ELLIPSOID
+    raise SplatError(-1, f"footprint must be 'isotropic', 'disc' or 'ellipsoid', not {value!r}")
+
+
+def _vec4_rows(a, n, name, fill=0.0):
+    """(n, 3) or (n, 4) float array -> contiguous (n, 4) float32 (w = fill when only three columns are given)."""
+    a = np.asarray(a, dtype=np.float32)
+    if a.ndim != 2 or a.shape[0] != n or a.shape[1] not in (3, 4):
+        raise SplatError(-1, f"{name} must have shape ({n}, 3) or ({n}, 4), not {a.shape}")
+    if a.shape[1] == 3:
+        a = np.concatenate([a, np.full((n, 1), fill, np.float32)], axis=1)
+    return np.ascontiguousarray(a)
+
+
+class GaussianCloud:
+    """Anisotropic 3D Gaussians (footprint="ellipsoid"; an extension, no reference counterpart) as device planes of one vec4
+    per splat: positions (xyz), scales (sigma x, y, z, world units), rotations (quaternion w, x, y, z; any non-zero
+    length) and colorOpacity (final rgb, opacity).  Optionally spherical-harmonic colour: `sh` holds (degree + 1)^2 rgb
+    coefficients per splat (float32, basis-major: sh[i, k, c]) and `opacity` one float per splat; updateColors(eye) then
+    writes colorOpacity from them (splat_sh_colors), and Renderer(footprint="ellipsoid") does so before every frame."""
+
+    def __init__(self, device, n, positions, scales, rotations, colorOpacity, sh=None, shDegree=0, opacity=None):
+        self.device, self.n = device, n
+        self.positions, self.scales, self.rotations, self.colorOpacity = positions, scales, rotations, colorOpacity
+        self.sh, self.shDegree, self.opacity = sh, shDegree, opacity
+
+    @classmethod
+    def fromArrays(cls, device, positions, scales, rotations, colors=None, opacity=None, sh=None, shDegree=None):
+        """positions, scales: (n, 3|4); rotations: (n, 4) as (w, x, y, z).  Colour either as `colors` (n, 3) rgb with
+        `opacity` (n,), or (n, 4) rgb + opacity; or as `sh` ((n, K, 3) or (n, 3K), K = (degree + 1)^2) with `opacity`."""
+        n = int(np.asarray(positions).shape[0])
+        pos = _vec4_rows(positions, n, "positions", 1.0)
+        scl = _vec4_rows(scales, n, "scales")
+        rot = np.ascontiguousarray(np.asarray(rotations, dtype=np.float32))
+        if rot.shape != (n, 4):
+            raise SplatError(-1, f"rotations must have shape ({n}, 4) (w, x, y, z), not {rot.shape}")
+        op = None if opacity is None else np.ascontiguousarray(np.asarray(opacity, dtype=np.float32).reshape(-1))
+        if op is not None and op.shape[0] != n:
+            raise SplatError(-1, f"opacity must hold {n} values, not {op.shape[0]}")
+        shb, deg = None, 0
+        if sh is not None:
+            coeffs = np.ascontiguousarray(np.asarray(sh, dtype=np.float32).reshape(n, -1))
+            k = coeffs.shape[1] // 3
+            deg = {1: 0, 4: 1, 9: 2, 16: 3}.get(k) if coeffs.shape[1] % 3 == 0 else None
+            if deg is None or (shDegree is not None and shDegree != deg):
+                raise SplatError(-1, f"sh must hold 3 (degree + 1)^2 floats per splat for a degree of 0-3, not {coeffs.shape[1]}")
+            if op is None:
+                raise SplatError(-1, "spherical-harmonic colour needs the opacity")
+            shb = device.createBufferFrom(coeffs)
+            col = np.zeros((n, 4), np.float32)
+        elif colors is not None:
+            c = np.asarray(colors, dtype=np.float32)
+            if c.ndim == 2 and c.shape == (n, 3):
+                if op is None:
+                    raise SplatError(-1, "rgb colours need the opacity")
+                c = np.concatenate([c, op[:, None]], axis=1)
+            if c.shape != (n, 4):
+                raise SplatError(-1, f"colors must have shape ({n}, 3) with opacity or ({n}, 4), not {c.shape}")
+            col = np.ascontiguousarray(c)
+        else:
+            raise SplatError(-1, "a GaussianCloud needs colors or sh")
+        opb = device.createBufferFrom(op) if (op is not None and shb is not None) else None
+        return cls(device, n, device.createBufferFrom(pos), device.createBufferFrom(scl), device.createBufferFrom(rot),
+                   device.createBufferFrom(col), shb, deg, opb)
+
+    def updateColors(self, eye):
+        """colorOpacity = the SH colour seen from `eye` (3 floats) with the cloud's opacity; nothing when it has no SH."""
+        if self.sh is None:
+            return
+        d = self.device
+        e = np.ascontiguousarray(np.asarray(eye, dtype=np.float32).reshape(-1)[:3])
+        check(d.lib.splat_sh_colors(d.ctx, e.ctypes.data_as(C.POINTER(C.c_float)), self.positions.ptr, 1, self.sh.ptr,
+                                    3 * (self.shDegree + 1) ** 2, self.shDegree, self.opacity.ptr, self.n, self.colorOpacity.ptr), d.ctx)
+
+    def destroy(self):
+        for b in (self.positions, self.scales, self.rotations, self.colorOpacity, self.sh, self.opacity):
+            if b is not None:
+                b.destroy()
+        self.positions = self.scales = self.rotations = self.colorOpacity = self.sh = self.opacity = None
 
 
 class SplatProjector:
@@ -366,18 +445,21 @@ class SplatProjector:
 
     footprint="disc" (extension): project SequentialRenderer's oriented disc instead of the
     isotropic screen-space Gaussian — project() then needs the normals, the ProjectedSplat bounds are the disc's
-    exact screen extent and getDiscBuffer() holds the 32-byte disc records the composite evaluates."""
+    exact screen extent and getDiscBuffer() holds the 32-byte disc records the composite evaluates.
+    footprint="ellipsoid" (extension): project anisotropic 3D Gaussians — project(..., cloud=GaussianCloud) writes their
+    ProjectedSplat records (the exact 3-sigma box) and, in getDiscBuffer(), their 32-byte records (splat_project_ellipsoid)."""
 
     def __init__(self, device, numSplats, footprint="isotropic"):
         self.device, self.numSplats = device, numSplats
         self.footprint = _footprint(footprint)
         self.projectedBuffer = device.createBuffer(numSplats * 32)  # :19-23
         self.contents = "projected"  # what projectedBuffer holds: ProjectedSplat records, or a frame's lit composite records
-        self.discBuffer = device.createBuffer(numSplats * 32) if self.footprint == _lib.FOOTPRINT_DISC else None
+        self.discBuffer = device.createBuffer(numSplats * 32) if self.footprint != _lib.FOOTPRINT_ISOTROPIC else None
 
     def project(self, commandEncoder, uniformBuffer, splatPropertyBuffer, keysBuffer=None, payloadBuffer=None,
-                paddedSize=0, normalsBuffer=None):  # :174-194
-        """keysBuffer/payloadBuffer (extension): fuse DepthKeyExtractor.extract into the same kernel."""
+                paddedSize=0, normalsBuffer=None, cloud=None):  # :174-194
+        """keysBuffer/payloadBuffer (extension): fuse DepthKeyExtractor.extract into the same kernel.  footprint="ellipsoid":
+        the splats are `cloud` (a GaussianCloud) and splatPropertyBuffer is not read."""
         d = self.device
         u = _uniform_floats(uniformBuffer)
         if u.shape[0] < 22:
@@ -386,6 +468,14 @@ class SplatProjector:
         keys, payload = keysBuffer.ptr if keysBuffer else None, payloadBuffer.ptr if payloadBuffer else None
         d.lastProjector = self
         self.contents = "projected"
+        if self.footprint == _lib.FOOTPRINT_ELLIPSOID:
+            if cloud is None:
+                raise SplatError(-1, "SplatProjector(footprint='ellipsoid').project needs cloud (a GaussianCloud)")
+            if cloud.n > self.numSplats:
+                raise SplatError(-1, "the cloud holds more splats than this projector was created for")
+            check(d.lib.splat_project_ellipsoid(d.ctx, uptr, cloud.positions.ptr, 1, cloud.scales.ptr, 1, cloud.rotations.ptr, 1, cloud.n,
+                                                self.projectedBuffer.ptr, self.discBuffer.ptr, keys, payload, paddedSize), d.ctx)
+            return
         if self.footprint == _lib.FOOTPRINT_DISC:
             if normalsBuffer is None:
                 raise SplatError(-1, "SplatProjector(footprint='disc').project needs normalsBuffer")
@@ -412,7 +502,7 @@ class SplatProjector:
 
     def getDiscBuffer(self):
         if self.discBuffer is None:
-            raise SplatError(-5, "getDiscBuffer: this projector was not created with footprint='disc'")
+            raise SplatError(-5, "getDiscBuffer: this projector was not created with footprint='disc' or 'ellipsoid'")
         return self.discBuffer
 
     def destroy(self):  # :200-202
@@ -646,6 +736,8 @@ class ComputeShaderRenderer:
         # records="lit" leaves in its projector's buffer); colours and normals are then not read
         self.recordFormat = recordFormat
         # footprint="disc": projectedBuffer in render() is SplatProjector(footprint="disc").getDiscBuffer()
+        # footprint="ellipsoid": projectedBuffer is SplatProjector(footprint="ellipsoid").getDiscBuffer() and splatPropertyBuffer
+        # the GaussianCloud (its colorOpacity plane is composited as is; curvatureBuffer is not read)
         self.footprint = _footprint(footprint)
         self.outputTexture = None
         self.outputFloat = None
@@ -674,11 +766,16 @@ class ComputeShaderRenderer:
         if numTilesX != -(-width // tileSize):
             raise SplatError(-1, "numTilesX does not match ceil(width / tileSize)")
         self.ensureOutputTexture(width, height, wantFloat)
-        cfg = CompositeCfg(self.mode, int(self.earlyOut), tileSize, self.tileRows[0], self.tileRows[1], self.recordFormat, 0,
+        ell = self.footprint == _lib.FOOTPRINT_ELLIPSOID
+        if ell and not isinstance(splatPropertyBuffer, GaussianCloud):
+            raise SplatError(-1, "ComputeShaderRenderer(footprint='ellipsoid').render takes a GaussianCloud as splatPropertyBuffer")
+        cfg = CompositeCfg(self.mode, int(self.earlyOut), tileSize, self.tileRows[0], self.tileRows[1], self.recordFormat, int(ell),
                            self.footprint)
         aov = C.byref(self.aov.ensure(width, height)) if wantAov else None
         self.aov.written = False
-        check(d.lib.splat_composite_aov(d.ctx, C.byref(cfg), splatPropertyBuffer.ptr + 16, 2, curvatureBuffer.ptr, 1,
+        colors, cstride = (splatPropertyBuffer.colorOpacity.ptr, 1) if ell else (splatPropertyBuffer.ptr + 16, 2)
+        normals = None if ell else curvatureBuffer.ptr
+        check(d.lib.splat_composite_aov(d.ctx, C.byref(cfg), colors, cstride, normals, 1,
                                         projectedBuffer.ptr, splatIndicesBuffer.ptr, tileListsBuffer.ptr, tileOffsetsBuffer.ptr,
                                         width, height, self.outputTexture.ptr,
                                         self.outputFloat.ptr if (wantFloat and self.outputFloat) else None,
@@ -777,6 +874,8 @@ class SequentialRenderer:
     def __init__(self, device, context=None, presentationFormat="rgba8unorm", numSplats=0, tileSize=16, footprint="disc",
                  earlyOut=True):
         self.device, self.numSplats, self.tileSize = device, numSplats, tileSize
+        if _footprint(footprint) == _lib.FOOTPRINT_ELLIPSOID:
+            raise SplatError(-1, "SequentialRenderer draws discs or isotropic splats; anisotropic Gaussians: Renderer(footprint='ellipsoid')")
         self.projector = SplatProjector(device, numSplats, footprint)
         self.binner = GPUTileBinner(device, tileSize)
         self.compositor = ComputeShaderRenderer(device, context, presentationFormat, earlyOut=earlyOut, footprint=footprint)
@@ -823,8 +922,10 @@ class Renderer:
         # ProjectedSplat records, with colour (and normal) gathered from the property buffers as the reference does.
         # Same image bit for bit.  "lit" falls back to "projected" on screens beyond 256 x 256 tiles; "lit-always" is "lit" on
         # every screen the binner takes.
+        # footprint="ellipsoid": anisotropic 3D Gaussians — render(u, cloud, None, None, w, h) with a GaussianCloud, whose SH colour
+        # (when it has one) is evaluated towards the camera first; the frame is a disc frame in every other respect
         self.footprint = _footprint(footprint)
-        if not writeProjected and self.footprint != _lib.FOOTPRINT_DISC:
+        if not writeProjected and self.footprint == _lib.FOOTPRINT_ISOTROPIC:
             raise SplatError(-1, "writeProjected=False: the isotropic composite reads the records the projector writes")
         if records not in ("lit", "lit-always", "projected"):
             raise SplatError(-1, f"records must be 'lit', 'lit-always' or 'projected', not {records!r}")
@@ -875,7 +976,12 @@ class Renderer:
             self._wh = (width, height)
         if wantFloat and self.outputFloat is None:
             self.outputFloat = d.createBuffer(width * height * 16)
-        prelit = isinstance(propertyBuffer, PropertyPlanes) and propertyBuffer.prelit
+        ell = self.footprint == _lib.FOOTPRINT_ELLIPSOID
+        if ell != isinstance(propertyBuffer, GaussianCloud):
+            raise SplatError(-1, "Renderer(footprint='ellipsoid') renders a GaussianCloud, and only it renders one")
+        if ell and (normalsBuffer is not None or propertyBuffer.n > self.numPoints):
+            raise SplatError(-1, "an ellipsoid frame takes no normals, and at most numPoints splats")
+        prelit = ell or (isinstance(propertyBuffer, PropertyPlanes) and propertyBuffer.prelit)
         ts = self.tileSize
         lit = self.records == "lit-always" or (self.records == "lit" and -(-width // ts) <= 256 and -(-height // ts) <= 256)
         # what the FRAME composites from (a disc frame with "lit": 48-byte lit disc records inside the binner) ...
@@ -893,7 +999,12 @@ class Renderer:
         head = (d.ctx, self.sorter._s, self.binner._b, C.byref(cfg), u.ctypes.data_as(C.POINTER(C.c_float)))
         aov = self.aov.ensure(width, height) if wantAov else None
         tail = tail + ((C.byref(aov) if aov is not None else None),)
-        if isinstance(propertyBuffer, PropertyPlanes):  # the native layout: SplatPropertyManager.getPropertyPlanes()
+        if ell:
+            propertyBuffer.updateColors(u[16:19])
+            tail = (propertyBuffer.n,) + tail[2:]
+            fn, args = d.lib.splat_render_frame_ellipsoids, head + (propertyBuffer.positions.ptr, propertyBuffer.scales.ptr,
+                                                                    propertyBuffer.rotations.ptr, propertyBuffer.colorOpacity.ptr) + tail
+        elif isinstance(propertyBuffer, PropertyPlanes):  # the native layout: SplatPropertyManager.getPropertyPlanes()
             fn, args = d.lib.splat_render_frame_planes_aov, head + (propertyBuffer.posRadius.ptr, propertyBuffer.colorOpacity.ptr) + tail
         else:  # the reference's interleaved records
             fn, args = d.lib.splat_render_frame_aov, head + (propertyBuffer.ptr,) + tail

@@ -180,7 +180,7 @@ export class SplatPropertyManager {
   getLitPlanes(normalsBuffer: Buffer): PropertyPlanes;
   destroy(): void;
 }
-export type Footprint = "isotropic" | "disc" | 0 | 1;
+export type Footprint = "isotropic" | "disc" | "ellipsoid" | 0 | 1 | 2;
 export class SplatProjector {
   constructor(device: Device, numSplats: number, footprint?: Footprint);
   project(enc: CommandEncoder | null, uniformBuffer: Buffer | Float32Array, splatPropertyBuffer: Buffer, keysBuffer?: Buffer | null, payloadBuffer?: Buffer | null, paddedSize?: number, normalsBuffer?: Buffer | null): void;
@@ -258,11 +258,23 @@ export class TileRenderer extends ComputeShaderRenderer {
   // @ts-ignore (the reference's TileRenderer.render: another argument list than ComputeShaderRenderer.render, and async)
   render(uniformData: Float32Array, splatPropertyBuffer: Buffer, splatIndicesBuffer: Buffer, curvatureBuffer: Buffer, tileCountsData: Uint32Array | Buffer, numTilesX: number, numTilesY: number, tileSize: number, maxSplatsPerTile: number, width: number, height: number): Promise<void>;
 }
+/** Anisotropic 3D Gaussians (footprint 'ellipsoid'): vec4 planes per splat, colour or SH (updateColors) */
+export class GaussianCloud {
+  static fromArrays(device: Device, a: { positions: Float32Array; scales: Float32Array; rotations: Float32Array; colors?: Float32Array; sh?: Float32Array; opacity?: Float32Array }): GaussianCloud;
+  readonly n: number;
+  readonly positions: Buffer;
+  readonly scales: Buffer;
+  readonly rotations: Buffer;
+  readonly colorOpacity: Buffer;
+  readonly shDegree: number;
+  updateColors(eye: Float32Array): void;
+  destroy(): void;
+}
 export class Renderer {
   constructor(device: Device, context?: unknown, presentationFormat?: string, numPoints?: number, tileSize?: number, options?: { footprint?: Footprint; records?: "lit" | "lit-always" | "projected" });
   recordFormat: number;
-  /** wantAov: also the depth, alpha and splat-id buffers (include/splat.h splat_aov) */
-  render(uniformData: Float32Array | Buffer, propertyBuffer: Buffer | PropertyPlanes, normalsBuffer: Buffer, scaleFactorsBuffer: Buffer | null, width: number, height: number, wantAov?: boolean): Buffer;
+  /** wantAov: also the depth, alpha and splat-id buffers (include/splat.h splat_aov).  footprint 'ellipsoid': a GaussianCloud, normalsBuffer null */
+  render(uniformData: Float32Array | Buffer, propertyBuffer: Buffer | PropertyPlanes | GaussianCloud, normalsBuffer: Buffer | null, scaleFactorsBuffer: Buffer | null, width: number, height: number, wantAov?: boolean): Buffer;
   finish(): number;
   readPixels(): Uint8Array;
   /** sum w z / sum w per pixel (+Infinity where nothing contributed); throws unless the latest render() had wantAov */
@@ -288,5 +300,5 @@ export class PointRenderer {
   destroy(): void;
 }
 export const MODE_FRONT_TO_BACK: 0; export const MODE_REFERENCE_LITERAL: 1;
-export const FOOTPRINT_ISOTROPIC: 0; export const FOOTPRINT_DISC: 1;
+export const FOOTPRINT_ISOTROPIC: 0; export const FOOTPRINT_DISC: 1; export const FOOTPRINT_ELLIPSOID: 2;
 export const RECORDS_PROJECTED: 0; export const RECORDS_COMPACT: 1; export const RECORDS_LIT32: 3;

@@ -32,12 +32,12 @@ interface PointerLikeEvent {
 }
 interface SceneNode { type: "primitive" | "operation"; }
 interface PropertyPlanes { posRadius: Buffer_; colorOpacity: Buffer_; isPlanes: true; prelit?: boolean; }
-type Footprint = "isotropic" | "disc" | 0 | 1;
+type Footprint = "isotropic" | "disc" | "ellipsoid" | 0 | 1 | 2;
 const native = require('./splat_napi.node');
 
 const U32_MAX = 0xffffffff;
 const MODE_FRONT_TO_BACK = 0;
-const FOOTPRINT_ISOTROPIC = 0, FOOTPRINT_DISC = 1;
+const FOOTPRINT_ISOTROPIC = 0, FOOTPRINT_DISC = 1, FOOTPRINT_ELLIPSOID = 2;
 const MODE_REFERENCE_LITERAL = 1;
 const RECORDS_PROJECTED = 0, RECORDS_COMPACT = 1, RECORDS_LIT32 = 3;
 
@@ -235,7 +235,14 @@ class SplatPropertyManager {
 function footprintCode(f: Footprint | undefined): number {
   if (f === undefined || f === null || f === 'isotropic' || f === FOOTPRINT_ISOTROPIC) return FOOTPRINT_ISOTROPIC;
   if (f === 'disc' || f === FOOTPRINT_DISC) return FOOTPRINT_DISC;
-  throw new Error(`footprint must be 'isotropic' or 'disc', not ${f}`);
+  if (f === 'ellipsoid' || f === FOOTPRINT_ELLIPSOID) return FOOTPRINT_ELLIPSOID;
+  throw new Error(`footprint must be 'isotropic', 'disc' or 'ellipsoid', not ${f}`);
+}
+// the stage classes draw discs and isotropic splats; anisotropic Gaussians go through Renderer (whole frames) here
+function stageFootprint(f: Footprint | undefined): number {
+  const code = footprintCode(f);
+  if (code === FOOTPRINT_ELLIPSOID) throw new Error("footprint 'ellipsoid': use Renderer with a GaussianCloud in the JS host");
+  return code;
 }
 /** footprint 'disc' (extension): SequentialRenderer's oriented disc — project() then needs normalsBuffer, the bounds are
  * the disc's exact screen extent and getDiscBuffer() holds the 32-byte records the composite evaluates. */
@@ -249,7 +256,7 @@ class SplatProjector {
   constructor(device: Device, numSplats: number, footprint: Footprint = 'isotropic') {
     this.device = device;
     this.numSplats = numSplats;
-    this.footprint = footprintCode(footprint);
+    this.footprint = stageFootprint(footprint);
     this.projectedBuffer = device.createBuffer(numSplats * 32);
     this.contents = 'projected';
     this.discBuffer = this.footprint === FOOTPRINT_DISC ? device.createBuffer(numSplats * 32) : null;
@@ -459,7 +466,7 @@ class ComputeShaderRenderer {
     this.device = device;
     this.mode = options.mode || MODE_FRONT_TO_BACK;
     this.earlyOut = options.earlyOut !== false;
-    this.footprint = footprintCode(options.footprint);
+    this.footprint = stageFootprint(options.footprint);
     // RECORDS_LIT32: projectedBuffer in render() holds lit composite records (what a Renderer with records 'lit' leaves in its
     // projector's buffer); colours and normals are then not read
     this.recordFormat = options.recordFormat || RECORDS_PROJECTED;
@@ -578,6 +585,56 @@ class SequentialRenderer {
   } // :316-320
 }
 
+/** Anisotropic 3D Gaussians (footprint 'ellipsoid'; an extension, no reference counterpart): device planes of one vec4 per
+ * splat — positions, scales (sigma x, y, z), rotations (quaternion w, x, y, z), colorOpacity (final rgb, opacity) — and
+ * optionally SH coefficients ((degree + 1)^2 rgb triples per splat, basis-major) with one opacity per splat, from which
+ * updateColors(eye) writes colorOpacity (native.sh_colors); Renderer does that before every frame. */
+class GaussianCloud {
+  declare device: Device;
+  declare n: number;
+  declare positions: Buffer_;
+  declare scales: Buffer_;
+  declare rotations: Buffer_;
+  declare colorOpacity: Buffer_;
+  declare sh: Buffer_ | null;
+  declare shDegree: number;
+  declare opacity: Buffer_ | null;
+  // positions, scales, rotations: 4 floats per splat; colors: 4 per splat (rgb, opacity), or sh (3 (degree + 1)^2 per splat) with opacity (1 per splat)
+  static fromArrays(device: Device, a: { positions: Float32Array; scales: Float32Array; rotations: Float32Array; colors?: Float32Array; sh?: Float32Array; opacity?: Float32Array }): GaussianCloud {
+    const n = a.positions.length / 4;
+    if (!Number.isInteger(n) || a.scales.length !== 4 * n || a.rotations.length !== 4 * n) throw new Error('positions, scales and rotations need 4 floats per splat');
+    const c = new GaussianCloud();
+    c.device = device;
+    c.n = n;
+    c.positions = device.createBufferFrom(a.positions);
+    c.scales = device.createBufferFrom(a.scales);
+    c.rotations = device.createBufferFrom(a.rotations);
+    c.sh = null;
+    c.opacity = null;
+    c.shDegree = 0;
+    if (a.sh) {
+      const k = a.sh.length / (3 * n), deg = [1, 4, 9, 16].indexOf(k);
+      if (deg < 0 || !a.opacity || a.opacity.length !== n) throw new Error('sh needs 3 (degree + 1)^2 floats per splat (degree 0-3) and one opacity per splat');
+      c.sh = device.createBufferFrom(a.sh);
+      c.opacity = device.createBufferFrom(a.opacity);
+      c.shDegree = deg;
+      c.colorOpacity = device.createBuffer(n * 16);
+    } else {
+      if (!a.colors || a.colors.length !== 4 * n) throw new Error('colors need 4 floats per splat (rgb, opacity)');
+      c.colorOpacity = device.createBufferFrom(a.colors);
+    }
+    return c;
+  }
+  updateColors(eye: Float32Array): void {
+    if (!this.sh) return;
+    native.sh_colors(this.device.ctx, eye, this.positions.ptr, 1, this.sh.ptr, 3 * (this.shDegree + 1) * (this.shDegree + 1), this.shDegree,
+      this.opacity.ptr, this.n, this.colorOpacity.ptr);
+  }
+  destroy(): void {
+    for (const b of [this.positions, this.scales, this.rotations, this.colorOpacity, this.sh, this.opacity]) if (b) b.destroy();
+  }
+}
+
 /** src/Renderer.ts:13,250,311 — name kept as the whole-frame facade (project -> keys -> sort -> bin -> composite) */
 class Renderer {
   declare device: Device;
@@ -616,7 +673,9 @@ class Renderer {
   }
   // wantAov: also the depth, alpha and splat-id buffers (readDepth / readAlpha / readIds; a frame rendered again by finish()
   // rewrites them with its image)
-  render(uniformData: Float32Array | Buffer_, propertyBuffer: Buffer_ | PropertyPlanes, normalsBuffer: Buffer_, scaleFactorsBuffer: Buffer_ | null, width: number, height: number, wantAov: boolean = false): Buffer_ {
+  // footprint 'ellipsoid': propertyBuffer is a GaussianCloud (its SH colour, if any, evaluated towards the camera first) and
+  // normalsBuffer is null
+  render(uniformData: Float32Array | Buffer_, propertyBuffer: Buffer_ | PropertyPlanes | GaussianCloud, normalsBuffer: Buffer_ | null, scaleFactorsBuffer: Buffer_ | null, width: number, height: number, wantAov: boolean = false): Buffer_ {
     this.last = [uniformData, propertyBuffer, normalsBuffer, scaleFactorsBuffer, width, height, wantAov]; // (finish() may render it again)
     let u = uniformFloats(uniformData);
     if (u.length < 22) {
@@ -637,13 +696,19 @@ class Renderer {
     const frameFormat = this.records === 'lit-always' || (this.records === 'lit' && small) ? RECORDS_LIT32 : RECORDS_PROJECTED;
     // ... and what projector.getRecordsBuffer() holds after this frame — what a caller passes, with this format, to the staged
     // composite: lit composite records for an isotropic 'lit' frame, ProjectedSplat records otherwise (a disc frame's too)
-    const isoLit = frameFormat === RECORDS_LIT32 && this.footprint !== FOOTPRINT_DISC;
+    const isoLit = frameFormat === RECORDS_LIT32 && this.footprint === FOOTPRINT_ISOTROPIC;
+    const cloud = propertyBuffer instanceof GaussianCloud;
+    if (cloud !== (this.footprint === FOOTPRINT_ELLIPSOID)) throw new Error("Renderer footprint 'ellipsoid' renders a GaussianCloud, and only it renders one");
     this.recordFormat = isoLit ? RECORDS_LIT32 : RECORDS_PROJECTED;
     this.projector.contents = isoLit ? 'lit' : 'projected';
-    const cfg = [MODE_FRONT_TO_BACK, 1, this.tileSize, 0, U32_MAX, frameFormat, propertyBuffer.prelit ? 1 : 0, this.footprint];
+    const cfg = [MODE_FRONT_TO_BACK, 1, this.tileSize, 0, U32_MAX, frameFormat, (cloud || propertyBuffer.prelit) ? 1 : 0, this.footprint];
     const aov = wantAov ? this.aov.ensure(width, height) : null;
     this.aov.written = false;
-    if (propertyBuffer.isPlanes) { // SplatPropertyManager.getPropertyPlanes()
+    if (propertyBuffer instanceof GaussianCloud) {
+      propertyBuffer.updateColors(u.subarray(16, 19));
+      native.render_frame_ellipsoids(this.device.ctx, this.sorter.handle, this.binner.handle, cfg, u, propertyBuffer.positions.ptr, propertyBuffer.scales.ptr,
+        propertyBuffer.rotations.ptr, propertyBuffer.colorOpacity.ptr, propertyBuffer.n, width, height, this.projector.projectedBuffer.ptr, this.output.ptr, null, aov);
+    } else if (propertyBuffer.isPlanes) { // SplatPropertyManager.getPropertyPlanes()
       native.render_frame_planes_aov(this.device.ctx, this.sorter.handle, this.binner.handle, cfg, u, propertyBuffer.posRadius.ptr, propertyBuffer.colorOpacity.ptr,
         normalsBuffer.ptr, this.numPoints, width, height, this.projector.projectedBuffer.ptr, this.output.ptr, null, aov);
     } else {
@@ -1397,5 +1462,5 @@ class BandRenderer {
 
 module.exports = { native, Device, Buffer: Buffer_, Camera, OrbitCameraController, FrameLoop, PointManager, scaleAABB, Comm, BandRenderer, SDFScene, Sphere, Box, Torus, Capsule, SmoothUnion,
   union, intersection, subtraction, smoothUnion, GradientSampler, PositionUpdater, CurvatureSampler, SplatPropertyManager, SplatProjector, DepthKeyExtractor, RadixSorter, PrefixSumScanner,
-  GPUTileBinner, PerTileSorter, ComputeShaderRenderer, TileRenderer, SequentialRenderer, Renderer, PointRenderer, MODE_FRONT_TO_BACK, MODE_REFERENCE_LITERAL,
-  FOOTPRINT_ISOTROPIC, FOOTPRINT_DISC, RECORDS_PROJECTED, RECORDS_COMPACT, RECORDS_LIT32 };
+  GPUTileBinner, PerTileSorter, ComputeShaderRenderer, TileRenderer, SequentialRenderer, Renderer, PointRenderer, GaussianCloud, MODE_FRONT_TO_BACK, MODE_REFERENCE_LITERAL,
+  FOOTPRINT_ISOTROPIC, FOOTPRINT_DISC, FOOTPRINT_ELLIPSOID, RECORDS_PROJECTED, RECORDS_COMPACT, RECORDS_LIT32 };

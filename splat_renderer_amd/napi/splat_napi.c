@@ -343,6 +343,34 @@ FN(render_frame_planes_aov) { /* render_frame_planes' arguments, then [depth, al
     if (AGAIN(rc)) rc = splat_render_frame_planes_aov(x, s, b, &cfg, u, pr, co, nrm, n, w, h, proj, o8, of, ap);
     return check(env, x, rc, mk_undefined(env));
 }
+FN(project_ellipsoid) { /* (ctx, Float32Array(22), positions, posStride, scales, scaleStride, rotations, rotStride, n, projected, records, keys|null, payload|null, nPadded) */
+    ARGS(14); splat_ctx *x = arg_external(&c, 0); size_t ub = 0; float *u = arg_hostbuf(&c, 1, &ub);
+    void *pos = arg_dptr(&c, 2); uint32_t ps = (uint32_t)arg_number(&c, 3); void *scl = arg_dptr(&c, 4); uint32_t ss = (uint32_t)arg_number(&c, 5);
+    void *rot = arg_dptr(&c, 6); uint32_t rs = (uint32_t)arg_number(&c, 7), n = (uint32_t)arg_number(&c, 8);
+    void *proj = arg_dptr(&c, 9), *rec = arg_dptr(&c, 10), *keys = arg_dptr(&c, 11), *pay = arg_dptr(&c, 12); uint32_t np = (uint32_t)arg_number(&c, 13); BAIL;
+    if (ub < 22 * sizeof(float)) { napi_throw_range_error(env, NULL, "uniform block needs 22 floats"); return NULL; }
+    return check(env, x, splat_project_ellipsoid(x, u, pos, ps, scl, ss, rot, rs, n, proj, rec, keys, pay, np), mk_undefined(env));
+}
+FN(sh_colors) { /* (ctx, Float32Array(3) eye, positions, posStride, sh, shStrideFloats, degree, opacity, n, colorOpacityOut) */
+    ARGS(10); splat_ctx *x = arg_external(&c, 0); size_t eb = 0; float *eye = arg_hostbuf(&c, 1, &eb);
+    void *pos = arg_dptr(&c, 2); uint32_t ps = (uint32_t)arg_number(&c, 3); void *sh = arg_dptr(&c, 4);
+    uint32_t shs = (uint32_t)arg_number(&c, 5), deg = (uint32_t)arg_number(&c, 6); void *op = arg_dptr(&c, 7);
+    uint32_t n = (uint32_t)arg_number(&c, 8); void *out = arg_dptr(&c, 9); BAIL;
+    if (eb < 3 * sizeof(float)) { napi_throw_range_error(env, NULL, "eye needs 3 floats"); return NULL; }
+    return check(env, x, splat_sh_colors(x, eye, pos, ps, sh, shs, deg, op, n, out), mk_undefined(env));
+}
+FN(render_frame_ellipsoids) { /* (ctx, sorter, binner, cfg[8], Float32Array(22), positions, scales, rotations, colorOpacity, n, W, H, projected|null, out8|null, outF|null, [depth, alpha, ids]|null) */
+    ARGS(16); splat_ctx *x = arg_external(&c, 0); splat_sorter *s = arg_external(&c, 1); splat_binner *b = arg_external(&c, 2);
+    splat_composite_cfg cfg; fill_cfg(&c, 3, &cfg); size_t ub = 0; float *u = arg_hostbuf(&c, 4, &ub);
+    void *pos = arg_dptr(&c, 5), *scl = arg_dptr(&c, 6), *rot = arg_dptr(&c, 7), *co = arg_dptr(&c, 8);
+    uint32_t n = (uint32_t)arg_number(&c, 9), w = (uint32_t)arg_number(&c, 10), h = (uint32_t)arg_number(&c, 11);
+    void *proj = arg_dptr(&c, 12), *o8 = arg_dptr(&c, 13), *of = arg_dptr(&c, 14); BAIL;
+    splat_aov a; const splat_aov *ap = fill_aov(&c, 15, &a);
+    if (ub < 22 * sizeof(float)) { napi_throw_range_error(env, NULL, "uniform block needs 22 floats"); return NULL; }
+    int rc = splat_render_frame_ellipsoids(x, s, b, &cfg, u, pos, scl, rot, co, n, w, h, proj, o8, of, ap);
+    if (AGAIN(rc)) rc = splat_render_frame_ellipsoids(x, s, b, &cfg, u, pos, scl, rot, co, n, w, h, proj, o8, of, ap);
+    return check(env, x, rc, mk_undefined(env));
+}
 FN(render_frame) { /* (ctx, sorter, binner, cfg[5], Float32Array(22), props, normals, n, W, H, projected, out8|null, outF|null) */
     ARGS(13); splat_ctx *x = arg_external(&c, 0); splat_sorter *s = arg_external(&c, 1); splat_binner *b = arg_external(&c, 2);
     splat_composite_cfg cfg; fill_cfg(&c, 3, &cfg); size_t ub = 0; float *u = arg_hostbuf(&c, 4, &ub);
@@ -592,7 +620,7 @@ static napi_value init(napi_env env, napi_value exports) {
         EXPORT(composite_forget_history), EXPORT(composite_options), EXPORT(bin_dims), EXPORT(bin_tile_size), EXPORT(project_slice),
         EXPORT(project_slice_disc), EXPORT(expand_compact), EXPORT(band_keys), EXPORT(band_kept), EXPORT(comm_rank), EXPORT(comm_count),
         EXPORT(allgather_records), EXPORT(sdf_gradients), EXPORT(sdf_update_positions), EXPORT(sdf_scale_factors), EXPORT(sdf_curvature), EXPORT(sdf_seed_positions), EXPORT(sdf_generate),
-        EXPORT(point_frame),
+        EXPORT(point_frame), EXPORT(project_ellipsoid), EXPORT(sh_colors), EXPORT(render_frame_ellipsoids),
     };
     napi_define_properties(env, exports, sizeof d / sizeof d[0], d);
     return exports;

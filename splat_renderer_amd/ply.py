@@ -1,0 +1,98 @@
+"""Trained 3D Gaussian splatting scenes from PLY files (footprint="ellipsoid"; an extension, no reference counterpart).
+
+load_gaussian_ply reads the binary_little_endian vertex layout that 3D Gaussian splatting writes — x y z, f_dc_0..2,
+f_rest_0..N, opacity, scale_0..2, rot_0..3 (other float properties such as nx ny nz are skipped) — with NumPy alone, and
+applies the activations the renderer expects: scale = exp(scale_k), opacity = sigmoid(opacity), the quaternion as
+(w, x, y, z) = (rot_0, rot_1, rot_2, rot_3).  The file stores the higher SH coefficients channel-major (all of red, then
+green, then blue); they are returned basis-major, sh[i, k, c], with the DC term as k = 0.  The degree follows from the
+number of f_rest properties: 0, 9, 24 or 45 for degrees 0-3.
+"""
+import numpy as np
+
+from ._lib import SplatError
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
+              "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
+              "double": "f8", "float64": "f8"}
+_REST_TO_DEGREE = {0: 0, 9: 1, 24: 2, 45: 3}
+
+
+def _bad(path, why):
+    return SplatError(-1, f"{path}: not a 3D Gaussian splatting PLY file: {why}")
+
+
+def load_gaussian_ply(path):
+    """Returns a dict of float32 arrays: positions (n, 3), scales (n, 3), rotations (n, 4) as (w, x, y, z), opacity (n,),
+    sh (n, (degree + 1)^2, 3), and the int degree.  Pass them to GaussianCloud.fromArrays(device, positions, scales,
+    rotations, opacity=opacity, sh=sh)."""
+    with open(path, "rb") as f:
+        if f.readline().rstrip(b"\r\n") != b"ply":
+            raise _bad(path, "no 'ply' magic line")
+        fmt, n, props, in_vertex, other = None, None, [], False, False
+        while True:
+            line = f.readline()
+            if not line:
+                raise _bad(path, "the header has no end_header line")
+            words = line.decode("ascii", "replace").split()
+            if not words or words[0] in ("comment", "obj_info"):
+                continue
+            if words[0] == "end_header":
+                break
+            if words[0] == "format":
+                fmt = words[1] if len(words) > 1 else None
+            elif words[0] == "element":
+                if len(words) != 3:
+                    raise _bad(path, f"malformed element line {line!r}")
+                in_vertex = words[1] == "vertex"
+                if in_vertex:
+                    if n is not None or other:
+                        raise _bad(path, "the vertex element must be the first and only element with data")
+                    n = int(words[2])
+                elif int(words[2]) > 0:
+                    other = True
+            elif words[0] == "property":
+                if len(words) != 3 or words[1] == "list":
+                    raise _bad(path, f"unsupported property {line!r} (list properties are not Gaussian attributes)")
+                if words[1] not in _PLY_TYPES:
+                    raise _bad(path, f"unknown property type {words[1]!r}")
+                if in_vertex:
+                    props.append((words[2], "<" + _PLY_TYPES[words[1]]))
+        if fmt != "binary_little_endian":
+            raise _bad(path, f"format {fmt!r}; only binary_little_endian is read")
+        if n is None:
+            raise _bad(path, "no vertex element")
+        names = [p[0] for p in props]
+        if len(set(names)) != len(names):
+            raise _bad(path, "a property name repeats")
+        need = ["x", "y", "z", "f_dc_0", "f_dc_1", "f_dc_2", "opacity", "scale_0", "scale_1", "scale_2",
+                "rot_0", "rot_1", "rot_2", "rot_3"]
+        missing = [k for k in need if k not in names]
+        if missing:
+            raise _bad(path, f"missing properties {missing}")
+        rest = sorted((k for k in names if k.startswith("f_rest_")), key=lambda k: int(k[len("f_rest_"):]))
+        if len(rest) not in _REST_TO_DEGREE or rest != [f"f_rest_{j}" for j in range(len(rest))]:
+            raise _bad(path, f"{len(rest)} f_rest properties; 0, 9, 24 or 45 (f_rest_0 ... in order) are expected")
+        dtype = np.dtype(props)
+        raw = f.read(n * dtype.itemsize)
+        if len(raw) != n * dtype.itemsize:
+            raise _bad(path, f"the file ends after {len(raw) // dtype.itemsize} of {n} vertices")
+    v = np.frombuffer(raw, dtype=dtype, count=n)
+
+    def cols(keys):
+        return np.stack([v[k].astype(np.float32) for k in keys], axis=1) if keys else np.zeros((n, 0), np.float32)
+
+    degree = _REST_TO_DEGREE[len(rest)]
+    nb = (degree + 1) ** 2
+    dc = cols(["f_dc_0", "f_dc_1", "f_dc_2"])
+    # channel-major f_rest: f_rest_{c * (nb - 1) + (k - 1)} is channel c of basis k
+    hi = cols(rest).reshape(n, 3, nb - 1).transpose(0, 2, 1)
+    sh = np.ascontiguousarray(np.concatenate([dc[:, None, :], hi], axis=1), dtype=np.float32)
+    op = cols(["opacity"])[:, 0]
+    return {
+        "positions": cols(["x", "y", "z"]),
+        "scales": np.exp(cols(["scale_0", "scale_1", "scale_2"])).astype(np.float32),
+        "rotations": cols(["rot_0", "rot_1", "rot_2", "rot_3"]),
+        "opacity": (1.0 / (1.0 + np.exp(-op.astype(np.float64)))).astype(np.float32),
+        "sh": sh,
+        "degree": degree,
+    }
