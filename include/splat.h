@@ -441,6 +441,43 @@ int splat_render_frame_ellipsoids(splat_ctx *ctx, splat_sorter *sorter, splat_bi
                                   uint32_t width, uint32_t height, void *projected, void *out_rgba8, void *out_rgba32f,
                                   const splat_aov *aov);
 
+/* ---- gradients of a frame of anisotropic 3D Gaussians (SPLAT_FOOTPRINT_ELLIPSOID; an extension) ------------------------
+ * The backward of the staged ellipsoid frame: splat_project_ellipsoid -> sort -> splat_bin_run -> splat_composite_aov.  L is
+ * the loss, G = (dL/drgb, dL/dalpha) per pixel.  Per pixel the forward takes its list in order with T_0 = 1, T_{i+1} =
+ * T_i (1 - alpha_i), alpha_i = opacity_i exp(-4.5 d2) inside the record's cut (d2 = |B d|^2 <= 1) and 0 elsewhere, and stops
+ * after the first entry with 1 - T_{i+1} >= 0.99; L_px entries are consumed.  rgb = sum T_i alpha_i c_i + T_L bg (bg =
+ * (0.05, 0.05, 0.1)), alpha = 1 - T_L.  Gradients are those of this function with the cut and the stop held fixed (zero
+ * outside the cut and for entries a pixel did not consume, as 3DGS treats its cut).  No 0.99 clamp of alpha is needed: every
+ * consumed entry but a pixel's last has 1 - alpha > 0.01 (T_{i+1} > 0.01 and T_{i+1} <= 1 - alpha_i), and the last one's
+ * T_{L-1} is recomputed front to back, never divided for.
+ * The per-splat sums are float atomic adds whose order of arrival varies: gradients are reproducible to rounding, not bit for
+ * bit, from run to run.
+ *
+ * splat_composite_backward: the lists (tile_indices / counts / offsets) must be the ones the forward composited, for the same
+ * records (splat_project_ellipsoid's 32-byte records), color_opacity and screen.  grad_rgba32f: W*H float4, dL/drgb in xyz and
+ * dL/dalpha in w.  ADDS into grad_records (n x 8 f32 per splat: c.x, c.y, B00, B01, -, B11, -, -; the unused columns are not
+ * touched) and grad_color_opacity (n x 4 f32: r, g, b, opacity).  cfg must say footprint ELLIPSOID, FRONT_TO_BACK, early_out =
+ * 1, tile_size = 16, record_format PROJECTED and the whole screen (tile_row0 = 0, tile_row1 >= the tile rows); anything else,
+ * or a buffer not 16-byte aligned, is SPLAT_ERR_INVALID.  Every screen the binner takes works. */
+int splat_composite_backward(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4,
+                             const void *records, const void *tile_indices, const void *tile_counts, const void *tile_offsets,
+                             uint32_t width, uint32_t height, const void *grad_rgba32f, uint32_t n, void *grad_records,
+                             void *grad_color_opacity);
+/* splat_project_ellipsoid's backward: dL/drecords (n x 8, splat_composite_backward's layout) -> dL/dposition (xyz, w = 0),
+ * dL/dscale (xyz, w = 0) and dL/drotation (w, x, y, z of the quaternion as given, through its normalisation), all n x 4 f32,
+ * OVERWRITTEN.  The centre and J move with the position.  The cull decisions are the forward's (csrc/ellipsoid.h); a culled
+ * splat gets exact zeros.  Computed in float64 per splat. */
+int splat_project_ellipsoid_backward(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4,
+                                     const void *scales, uint32_t scale_stride_vec4, const void *rotations, uint32_t rot_stride_vec4,
+                                     uint32_t n, const void *grad_records, void *grad_positions, void *grad_scales, void *grad_rotations);
+/* splat_sh_colors' backward: dL/dcolor_opacity (n x 4) -> dL/dsh (same layout and stride as sh; the floats past
+ * 3 (degree + 1)^2 in a row are not written), dL/dposition (n x 4, through dir = normalize(p - eye); w = 0) and dL/dopacity
+ * (n floats: the fourth column passed through), OVERWRITTEN.  Zero colour gradient where the forward's max(., 0) clamped.
+ * opacity_f32 is the forward's (not read; may be NULL). */
+int splat_sh_colors_backward(splat_ctx *ctx, const float *eye3, const void *positions, uint32_t pos_stride_vec4, const void *sh,
+                             uint32_t sh_stride_floats, uint32_t degree, const void *opacity_f32, const void *grad_color_opacity,
+                             uint32_t n, void *grad_sh, void *grad_positions, void *grad_opacity);
+
 /* ---- multi-GPU band path (no reference equivalent — the reference is single-device) */
 /* The oriented-disc projector (src/SequentialRenderer.ts:68-71,91-112): the splat is the disc
  * p + r*(t*u + b*v), u^2+v^2 <= 1, in the tangent plane of its normal (t = normalize(cross(up, n)), b =

@@ -1,0 +1,347 @@
+"""torch autograd for frames of anisotropic 3D Gaussians (footprint="ellipsoid"; an extension, no reference counterpart).
+
+    rec, aux   = project_ellipsoids(uniforms, means, scales, rotations)  # rec (n, 8) differentiable; aux: ProjectedSplats, keys
+    col        = sh_colors(eye, means, sh, degree, opacities)             # (n, 4) differentiable (or the caller's own (rgb, opacity))
+    rgb, alpha = rasterize(rec, col, aux, width, height)                  # (H, W, 3), (H, W)
+    rgb, alpha = render_gaussians(camera_or_uniforms, means, scales, rotations, opacities, colors=None, sh=None, width=..., height=...)
+
+Every kernel runs on torch's current stream (a Device created on it, cached per device and stream).  Tensors must be CUDA
+float32; there is no CPU path (SplatError).  The forward is the staged frame of include/splat.h (splat_project_ellipsoid ->
+sort -> splat_bin_run -> splat_composite_aov), so rasterize's image is Renderer(footprint="ellipsoid")'s bit for bit; the
+backward is splat_composite_backward, splat_project_ellipsoid_backward and splat_sh_colors_backward, whose contract (the cut
+and the early-out stop held fixed; float atomic sums, reproducible to rounding) is stated in include/splat.h.
+
+`rec` is a real intermediate: rec.retain_grad() gives the screen-space gradient rec.grad[:, :2] that 3DGS densification reads.
+
+The background is the composite's fixed bg = (0.05, 0.05, 0.1).  A caller that wants background b uses
+rgb + (b - bg) * (1 - alpha)[..., None], which is exact and differentiable.
+
+torch is imported when a function here is first called, so `import splat_renderer_amd` does not need it.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import CompositeCfg, SplatError, check
+
+BG = (0.05, 0.05, 0.1)
+TILE = 16
+
+_torch = None
+_devices = {}
+
+
+def _t():
+    global _torch
+    if _torch is None:
+        import torch
+        _torch = torch
+    return _torch
+
+
+class _Ctx:
+    """The splat context on one device and stream, with the sorter and binner the staged frames share.  Each binSplats
+    bumps `generation`: a backward whose forward's lists have since been replaced rebuilds them."""
+
+    def __init__(self, index, stream):
+        from .host import Device
+        self.device = Device(index, stream=stream)
+        self.lib = self.device.lib
+        self.sorter = None
+        self.capacity = 0
+        self.padded = 0
+        b = C.c_void_p()
+        check(self.lib.splat_bin_create(self.device.ctx, TILE, C.byref(b)), self.device.ctx)
+        self.binner = b
+        self.generation = 0
+
+    @property
+    def ctx(self):
+        return self.device.ctx
+
+    def ensure_sorter(self, n):
+        if self.sorter is None or n > self.capacity:
+            if self.sorter is not None:
+                self.lib.splat_sort_destroy(self.sorter)
+                self.sorter = None
+            s = C.c_void_p()
+            cap = max(n, 1)
+            check(self.lib.splat_sort_create(self.ctx, cap, C.byref(s)), self.ctx)
+            self.sorter, self.capacity = s, cap
+            self.padded = int(self.lib.splat_sort_capacity(s))
+        return self.padded
+
+    def bin(self, aux, width, height):
+        """sort aux's keys, bin with its ProjectedSplats: the lists of one frame; returns this binning's generation."""
+        lib, ctx, n = self.lib, self.ctx, aux.n
+        self.ensure_sorter(n)
+        if aux.keys.numel() > self.padded:
+            raise SplatError(-1, "rasterize: the projection's keys outgrew the sorter")
+        kb = aux.keys.numel() * 4
+        check(lib.splat_buf_copy(ctx, lib.splat_sort_keys(self.sorter), aux.keys.data_ptr(), kb), ctx)
+        check(lib.splat_buf_copy(ctx, lib.splat_sort_payload(self.sorter), aux.payload.data_ptr(), kb), ctx)
+        check(lib.splat_sort_run(self.sorter, n, 0, 32), ctx)
+        args = (self.binner, aux.projected.data_ptr(), n, lib.splat_sort_sorted_payload(self.sorter), n, width, height, 0, _lib.U32_MAX)
+        check(lib.splat_bin_run(*args), ctx)
+        # the binner is sync-free: lists that outgrew the pair limit it sized from the frame before are reported here (the
+        # limit has been raised then), and binned again
+        total = C.c_uint64()
+        rc = lib.splat_bin_total(self.binner, C.byref(total))
+        if rc in _lib.RENDER_AGAIN:
+            check(lib.splat_bin_run(*args), ctx)
+            rc = lib.splat_bin_total(self.binner, C.byref(total))
+        check(rc, ctx)
+        self.generation += 1
+        return self.generation
+
+    def lists(self):
+        out = []
+        for fn in (self.lib.splat_bin_indices, self.lib.splat_bin_counts, self.lib.splat_bin_offsets):
+            p = C.c_void_p()
+            check(fn(self.binner, C.byref(p)), self.ctx)
+            out.append(p.value)
+        return out
+
+
+def _context(tensor):
+    torch = _t()
+    index = tensor.device.index if tensor.device.index is not None else torch.cuda.current_device()
+    stream = torch.cuda.current_stream(index).cuda_stream
+    key = (index, stream)
+    c = _devices.get(key)
+    if c is None:
+        c = _devices[key] = _Ctx(index, stream)
+    return c
+
+
+def _cuda_f32(t, name, cols=None):
+    """A contiguous 16-byte-aligned CUDA float32 tensor, or SplatError."""
+    torch = _t()
+    if not isinstance(t, torch.Tensor):
+        raise SplatError(-1, f"{name} must be a torch tensor")
+    if not t.is_cuda:
+        raise SplatError(-1, f"{name} is on {t.device}: splat_renderer_amd has no CPU path")
+    if t.dtype != torch.float32:
+        raise SplatError(-1, f"{name} must be float32, not {t.dtype}")
+    if cols is not None and (t.dim() != 2 or t.shape[1] != cols):
+        raise SplatError(-1, f"{name} must have shape (n, {cols}), not {tuple(t.shape)}")
+    t = t.contiguous()
+    if t.data_ptr() % 16:
+        t = t.clone()
+    if t.data_ptr() % 16:
+        raise SplatError(-1, f"{name} is not 16-byte aligned")
+    return t
+
+
+def _vec4(t, name, fill=0.0):
+    """(n, 3) -> (n, 4) with torch ops (outside the Functions, so autograd handles the slice)."""
+    _cuda_f32(t, name)
+    if t.dim() != 2 or t.shape[1] not in (3, 4):
+        raise SplatError(-1, f"{name} must have shape (n, 3) or (n, 4), not {tuple(t.shape)}")
+    if t.shape[1] == 3:
+        t = _t().cat([t, t.new_full((t.shape[0], 1), fill)], dim=1)
+    return t
+
+
+def _uniforms(camera_or_uniforms, width, height):
+    if hasattr(camera_or_uniforms, "uniforms"):
+        u = camera_or_uniforms.uniforms(width, height)
+    else:
+        u = camera_or_uniforms
+        if hasattr(u, "detach"):
+            u = u.detach().cpu().numpy()
+        u = np.asarray(u, np.float32).reshape(-1)
+        if u.shape[0] < 20:
+            raise SplatError(-1, "uniform block needs 22 floats (VP, eye, time, screenW, screenH)")
+        u = u.copy() if u.shape[0] >= 22 else np.concatenate([u[:20], np.zeros(2, np.float32)])
+        if width is not None:
+            u[20], u[21] = width, height
+    return np.ascontiguousarray(u, np.float32)
+
+
+def _fptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+class ProjectedSplats:
+    """What rasterize needs of a projection beside its records: ProjectedSplat records (n, 8), depth keys and payload (padded
+    to the sorter's capacity), the uniforms and the inputs (for the projector's backward).  No gradient flows through it."""
+
+    def __init__(self, ctx, u, n, projected, keys, payload):
+        self.ctx, self.u, self.n = ctx, u, n
+        self.projected, self.keys, self.payload = projected, keys, payload
+        self.width, self.height = int(u[20]), int(u[21])
+
+
+def _functions():
+    """The three autograd Functions, built on first use (torch imported then)."""
+    torch = _t()
+    if "_fns" in globals():
+        return globals()["_fns"]
+
+    class Project(torch.autograd.Function):
+        @staticmethod
+        def forward(fctx, u, means4, scales4, rots):
+            cx = _context(means4)
+            n = means4.shape[0]
+            padded = cx.ensure_sorter(n)
+            rec = torch.empty((n, 8), device=means4.device, dtype=torch.float32)
+            proj = torch.empty((n, 8), device=means4.device, dtype=torch.float32)
+            keys = torch.empty(padded, device=means4.device, dtype=torch.int32)
+            pay = torch.empty(padded, device=means4.device, dtype=torch.int32)
+            if n:
+                check(cx.lib.splat_project_ellipsoid(cx.ctx, _fptr(u), means4.data_ptr(), 1, scales4.data_ptr(), 1, rots.data_ptr(), 1, n,
+                                                     proj.data_ptr(), rec.data_ptr(), keys.data_ptr(), pay.data_ptr(), padded), cx.ctx)
+            fctx.save_for_backward(means4, scales4, rots)
+            fctx.u = u
+            aux = ProjectedSplats(cx, u, n, proj, keys, pay)
+            return rec, aux
+
+        @staticmethod
+        def backward(fctx, grad_rec, _grad_aux=None):
+            means4, scales4, rots = fctx.saved_tensors
+            n = means4.shape[0]
+            cx = _context(means4)
+            g = _cuda_f32(grad_rec, "grad_records", 8)
+            gp, gs, gr = (torch.empty((n, 4), device=means4.device, dtype=torch.float32) for _ in range(3))
+            if n:
+                check(cx.lib.splat_project_ellipsoid_backward(cx.ctx, _fptr(fctx.u), means4.data_ptr(), 1, scales4.data_ptr(), 1, rots.data_ptr(), 1,
+                                                              n, g.data_ptr(), gp.data_ptr(), gs.data_ptr(), gr.data_ptr()), cx.ctx)
+            return None, gp, gs, gr
+
+    class ShColors(torch.autograd.Function):
+        @staticmethod
+        def forward(fctx, eye, means4, sh, degree, opacities):
+            cx = _context(means4)
+            n = means4.shape[0]
+            out = torch.empty((n, 4), device=means4.device, dtype=torch.float32)
+            if n:
+                check(cx.lib.splat_sh_colors(cx.ctx, _fptr(eye), means4.data_ptr(), 1, sh.data_ptr(), sh.shape[1], degree, opacities.data_ptr(), n,
+                                             out.data_ptr()), cx.ctx)
+            fctx.save_for_backward(means4, sh, opacities)
+            fctx.eye, fctx.degree = eye, degree
+            return out
+
+        @staticmethod
+        def backward(fctx, grad_col):
+            means4, sh, opacities = fctx.saved_tensors
+            n = means4.shape[0]
+            cx = _context(means4)
+            g = _cuda_f32(grad_col, "grad_color_opacity", 4)
+            gsh = torch.zeros_like(sh)
+            gp = torch.empty((n, 4), device=means4.device, dtype=torch.float32)
+            gop = torch.empty(n, device=means4.device, dtype=torch.float32)
+            if n:
+                check(cx.lib.splat_sh_colors_backward(cx.ctx, _fptr(fctx.eye), means4.data_ptr(), 1, sh.data_ptr(), sh.shape[1], fctx.degree,
+                                                      opacities.data_ptr(), g.data_ptr(), n, gsh.data_ptr(), gp.data_ptr(), gop.data_ptr()), cx.ctx)
+            return None, gp, gsh, None, gop
+
+    class Rasterize(torch.autograd.Function):
+        @staticmethod
+        def forward(fctx, rec, col, aux, width, height):
+            cx = aux.ctx
+            n = aux.n
+            out = torch.empty((height, width, 4), device=rec.device, dtype=torch.float32)
+            alpha = torch.empty((height, width), device=rec.device, dtype=torch.float32)
+            gen = cx.bin(aux, width, height)
+            idx, cnt, off = cx.lists()
+            cfg = CompositeCfg(_lib.MODE_FRONT_TO_BACK, 1, TILE, 0, _lib.U32_MAX, _lib.RECORDS_PROJECTED, 1, _lib.FOOTPRINT_ELLIPSOID)
+            aov = _lib.Aov(None, alpha.data_ptr(), None)
+            check(cx.lib.splat_composite_aov(cx.ctx, C.byref(cfg), col.data_ptr(), 1, None, 1, rec.data_ptr(), idx, cnt, off, width, height,
+                                             None, out.data_ptr(), None, C.byref(aov)), cx.ctx)
+            fctx.save_for_backward(rec, col)
+            fctx.aux, fctx.gen, fctx.wh = aux, gen, (width, height)
+            rgb = out[..., :3]
+            return rgb, alpha
+
+        @staticmethod
+        def backward(fctx, grad_rgb, grad_alpha):
+            rec, col = fctx.saved_tensors
+            aux = fctx.aux
+            cx = aux.ctx
+            width, height = fctx.wh
+            n = aux.n
+            if cx.generation != fctx.gen:  # the binner has binned another frame since: rebuild this frame's lists (deterministic)
+                fctx.gen = cx.bin(aux, width, height)
+            idx, cnt, off = cx.lists()
+            g = torch.zeros((height, width, 4), device=rec.device, dtype=torch.float32)
+            if grad_rgb is not None:
+                g[..., :3] = grad_rgb
+            if grad_alpha is not None:
+                g[..., 3] = grad_alpha
+            grec = torch.zeros((n, 8), device=rec.device, dtype=torch.float32)
+            gcol = torch.zeros((n, 4), device=rec.device, dtype=torch.float32)
+            cfg = CompositeCfg(_lib.MODE_FRONT_TO_BACK, 1, TILE, 0, _lib.U32_MAX, _lib.RECORDS_PROJECTED, 1, _lib.FOOTPRINT_ELLIPSOID)
+            if n:
+                check(cx.lib.splat_composite_backward(cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr(), idx, cnt, off, width, height,
+                                                      g.data_ptr(), n, grec.data_ptr(), gcol.data_ptr()), cx.ctx)
+            return grec, gcol, None, None, None
+
+    fns = (Project, ShColors, Rasterize)
+    globals()["_fns"] = fns
+    return fns
+
+
+def project_ellipsoids(uniforms, means, scales, rotations, width=None, height=None):
+    """(rec (n, 8) differentiable records {c.x, c.y, B00, B01, 0, B11, 0, 0}, aux: ProjectedSplats).  uniforms: a Camera (then
+    width and height are required) or the 22-float block."""
+    u = _uniforms(uniforms, width, height)
+    means4 = _cuda_f32(_vec4(means, "means", 1.0), "means", 4)
+    scales4 = _cuda_f32(_vec4(scales, "scales"), "scales", 4)
+    rots = _cuda_f32(rotations, "rotations", 4)
+    if not (means4.shape[0] == scales4.shape[0] == rots.shape[0]):
+        raise SplatError(-1, "means, scales and rotations must hold the same number of splats")
+    return _functions()[0].apply(u, means4, scales4, rots)
+
+
+def sh_colors(eye, means, sh, degree, opacities):
+    """(n, 4): rgb = max(0.5 + sum_k Y_k(normalize(p - eye)) sh_k, 0) and the opacity; sh (n, (degree + 1)^2, 3) or (n, 3K)."""
+    e = np.ascontiguousarray(np.asarray(eye.detach().cpu() if hasattr(eye, "detach") else eye, np.float32).reshape(-1)[:3])
+    means4 = _cuda_f32(_vec4(means, "means", 1.0), "means", 4)
+    n = means4.shape[0]
+    if not 0 <= int(degree) <= 3:
+        raise SplatError(-1, "degree must be 0-3")
+    _cuda_f32(sh, "sh")
+    sh2 = _cuda_f32(sh.reshape(n, -1), "sh")
+    if sh2.shape[1] < 3 * (int(degree) + 1) ** 2:
+        raise SplatError(-1, f"sh holds {sh2.shape[1]} floats per splat; degree {degree} needs {3 * (int(degree) + 1) ** 2}")
+    op = _cuda_f32(opacities.reshape(-1), "opacities")
+    if op.shape[0] != n:
+        raise SplatError(-1, "opacities must hold one value per splat")
+    return _functions()[1].apply(e, means4, sh2, int(degree), op)
+
+
+def rasterize(rec, col, aux, width=None, height=None):
+    """(rgb (H, W, 3), alpha (H, W)) of the records and colours over the projection's lists; both differentiable."""
+    width = aux.width if width is None else int(width)
+    height = aux.height if height is None else int(height)
+    rec_c = _cuda_f32(rec, "rec", 8)
+    col_c = _cuda_f32(col, "col", 4)
+    if rec_c.shape[0] != aux.n or col_c.shape[0] != aux.n:
+        raise SplatError(-1, "rec, col and the projection must hold the same number of splats")
+    return _functions()[2].apply(rec_c, col_c, aux, width, height)
+
+
+def render_gaussians(camera_or_uniforms, means, scales, rotations, opacities, colors=None, sh=None, width=None, height=None, degree=None):
+    """The whole differentiable frame: project_ellipsoids, the colour (sh_colors when `sh` is given, else cat(colors,
+    opacities)), rasterize.  Returns (rgb (H, W, 3), alpha (H, W))."""
+    if width is None or height is None:
+        raise SplatError(-1, "render_gaussians needs width and height")
+    for name, t in (("means", means), ("scales", scales), ("rotations", rotations), ("opacities", opacities)):
+        _cuda_f32(t, name)
+    u = _uniforms(camera_or_uniforms, width, height)
+    rec, aux = project_ellipsoids(u, means, scales, rotations)
+    n = aux.n
+    if sh is not None:
+        k = sh.reshape(n, -1).shape[1] // 3
+        deg = {1: 0, 4: 1, 9: 2, 16: 3}.get(k) if degree is None else degree
+        if deg is None:
+            raise SplatError(-1, f"sh must hold 3 (degree + 1)^2 floats per splat, not {3 * k}")
+        col = sh_colors(u[16:19], means, sh, deg, opacities)
+    elif colors is not None:
+        _cuda_f32(colors, "colors", 3)
+        col = _t().cat([colors, opacities.reshape(-1, 1)], dim=1)
+    else:
+        raise SplatError(-1, "render_gaussians needs colors or sh")
+    return rasterize(rec, col, aux, width, height)

@@ -1,0 +1,485 @@
+// grad.hip — gradients of a frame of anisotropic 3D Gaussians (SPLAT_FOOTPRINT_ELLIPSOID; an extension, no reference
+// counterpart): the backward passes of the composite, of the ellipsoid projector and of the SH colour.
+//
+// k_composite_backward   one 256-thread workgroup per 16x16 tile, one pixel per lane (k_composite's pixel mapping).
+//   Walk 1, front to back over the tile's list in chunks of GCH entries staged in LDS, recomputes each pixel's forward in
+//   k_composite's operation order (this file is compiled with contraction on, as composite.hip is): L, the number of entries
+//   the pixel consumed (up to and including the one its early-out stopped at), T_{L-1} and T_L.
+//   Walk 2 goes back to front from the tile's largest L, chunk by chunk.  Per entry i < L a pixel recovers
+//   T_i = T_{i+1} / (1 - alpha_i) (except at its last entry, whose T_{L-1} it kept: only there may 1 - alpha be <= 0.01) and
+//   forms dL/dalpha_i = T_i (G.c_i - S_i), S the blend of everything behind the entry, with alpha as a fourth channel
+//   (colour 1, background 0).  Each wave sums its 64 lanes' nine numbers per entry with DPP (skipped when the ballot says no
+//   lane of the wave is inside the entry); the four waves' sums meet in LDS, and after the chunk one float atomic add per
+//   (entry, number) goes to grad_records (8 floats per splat: c.x, c.y, B00, B01, -, B11, -, -) and grad_color_opacity
+//   (4 per splat: r, g, b, opacity).  The sums depend on the atomics' arrival order: reproducible to rounding only.
+// k_project_ellipsoid_backward   one thread per splat: the record's gradient through B = U / 3, U(a, b, c), Sigma2 = T T^T + 0.3 I,
+//   T = J M, M = R S, the quaternion's normalisation and J's and the centre's dependence on the position, in float64.  The
+//   cull decisions are ellipsoid_record's own (binary32); a culled splat gets exact zeros.
+// k_sh_colors_backward   one thread per splat: sh.hip's basis and constants, dir = normalize(p - eye), zero where the
+//   forward's max(., 0) clamped.
+#include "common.h"
+#include "disc.h"
+#include "ellipsoid.h"
+
+namespace {
+
+constexpr int GT = 16;          // tile edge
+constexpr int GCH = 64;         // list entries per staged chunk
+constexpr int GNV = 9;          // numbers summed per entry: c.x, c.y, B00, B01, B11, r, g, b, opacity
+constexpr float G_T_STOP = 0x1.47ae4p-7f; // composite.h's T_STOP: the last transmittance that stops a pixel
+constexpr float G_EXP2_SCALE = -6.492127684000335f; // composite.h's ELLIPSOID_EXP2_SCALE: exp(-4.5 d2) = exp2(d2 * this)
+
+struct GradEntry {
+    float4 a;   // c.x, c.y, B00, B01
+    float4 b;   // B11, opacity, r, g
+    float4 c;   // b, -, -, -
+    float4 bnd; // the record's exact 3-sigma box (all zeros: covers no pixel)
+};
+
+// The sum of v over the wave's 64 lanes, valid in lane 63 (quad swaps, rotations by 4 and 8 in each row of 16, then the
+// row broadcasts 15 and 31 into rows 1, 3 and 2, 3)
+__device__ __forceinline__ float wave_sum63(float v) {
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xb1, 0xf, 0xf, false)); // quad_perm [1,0,3,2]
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4e, 0xf, 0xf, false)); // quad_perm [2,3,0,1]
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x124, 0xf, 0xf, false)); // row_ror:4
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xf, 0xf, false)); // row_ror:8
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x142, 0xa, 0xf, false)); // row_bcast:15
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x143, 0xc, 0xf, false)); // row_bcast:31
+    return v;
+}
+
+struct BackParams {
+    const float4 *color; uint32_t color_stride;
+    const float4 *records;
+    const uint32_t *indices, *counts, *offsets;
+    uint32_t width, height, ntx;
+    const float4 *grad_img;
+    float *grad_records;
+    float *grad_color;
+};
+
+// stages entries [c0, c0 + m) of the tile's list (threads 0 .. m-1)
+__device__ __forceinline__ void stage_chunk(const BackParams &p, uint32_t off, uint32_t c0, uint32_t m, GradEntry *s_ent, uint32_t *s_idx) {
+    const uint32_t t = threadIdx.x;
+    if (t < m) {
+        const uint32_t idx = p.indices[off + c0 + t];
+        const DiscRecord rec = {p.records[(size_t)idx * 2], p.records[(size_t)idx * 2 + 1]};
+        float4 bnd;
+        const bool ok = disc_bounds(rec, bnd); // all zeros when not: no pixel centre (>= 0.5) is inside
+        const float4 col = p.color[(size_t)idx * p.color_stride];
+        GradEntry e;
+        e.a = rec.a;
+        e.b = make_float4(rec.b.y, col.w, col.x, col.y);
+        e.c = make_float4(col.z, 0.0f, 0.0f, 0.0f);
+        e.bnd = ok ? bnd : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        s_ent[t] = e;
+        s_idx[t] = idx;
+    }
+}
+
+// alpha of entry e at pixel centre (pxf, pyf) in k_composite's operation order (ELL, q = 0: rd = 1); ge = the exponential,
+// d2, u, v and the pixel offset returned for the backward.  Outside the box or the cut: false.
+__device__ __forceinline__ bool entry_alpha(const GradEntry &e, float pxf, float pyf, float &alpha, float &ge, float &u, float &v, float &dx,
+                                            float &dy) {
+    const bool in_box = !(pxf < e.bnd.x || pxf > e.bnd.z || pyf < e.bnd.y || pyf > e.bnd.w);
+    dx = pxf - e.a.x;
+    dy = pyf - e.a.y;
+    u = e.a.z * dx + e.a.w * dy;
+    v = e.b.x * dy; // (B10 = 0: the forward's 0 dx + B11 dy, the same value for a finite dx)
+    const float d2 = u * u + v * v;
+    ge = (d2 <= 1.0f) ? __builtin_amdgcn_exp2f(d2 * G_EXP2_SCALE) : 0.0f;
+    alpha = ge;
+    alpha *= e.b.y;
+    return in_box && d2 <= 1.0f;
+}
+
+} // namespace
+
+__global__ __launch_bounds__(256) void k_composite_backward(BackParams p) {
+    __shared__ GradEntry s_ent[GCH];
+    __shared__ uint32_t s_idx[GCH];
+    __shared__ float s_part[4][GCH][GNV];
+    __shared__ uint32_t s_touch[GCH];
+    __shared__ uint32_t s_maxL;
+
+    const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const uint32_t tx = blockIdx.x, ty = blockIdx.y;
+    const uint32_t tile_idx = ty * p.ntx + tx;
+    const uint32_t count = p.counts[tile_idx], off = p.offsets[tile_idx];
+    const uint32_t px = tx * GT + (w & 1) * 8 + (lane & 7), py = ty * GT + (w >> 1) * 8 + (lane >> 3);
+    const bool pixel_ok = px < p.width && py < p.height;
+    const float pxf = (float)px + 0.5f, pyf = (float)py + 0.5f;
+
+    // ---- walk 1: front to back, the forward's stop rule ----
+    bool live = pixel_ok;
+    uint32_t L = 0;
+    float T = 1.0f, T_last = 1.0f; // T_L, T_{L-1}
+    if (tid == 0) s_maxL = 0;
+    for (uint32_t c0 = 0; c0 < count; c0 += GCH) {
+        const uint32_t m = min((uint32_t)GCH, count - c0);
+        __syncthreads();
+        stage_chunk(p, off, c0, m, s_ent, s_idx);
+        __syncthreads();
+        if (live) {
+            for (uint32_t j = 0; j < m; ++j) {
+                float alpha, ge, u, v, dx, dy;
+                const bool in = entry_alpha(s_ent[j], pxf, pyf, alpha, ge, u, v, dx, dy);
+                const float g = in ? alpha : 0.0f;
+                const float wgt = T * g;
+                T_last = T;
+                T -= wgt;
+                if (T <= G_T_STOP) {
+                    L = c0 + j + 1;
+                    live = false;
+                    break;
+                }
+            }
+        }
+        if (!__syncthreads_or(live)) break;
+    }
+    if (live) L = count; // never stopped: the whole list (T_last is the T before its last entry)
+    if (L) atomicMax(&s_maxL, L);
+
+    const float4 G = pixel_ok ? p.grad_img[(size_t)py * p.width + px] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float S = (G.x * 0.05f + G.y * 0.05f) + G.z * 0.1f; // G . bg (the background's alpha channel is 0)
+    float Tn = T;                                          // T_{i+1} on the way back
+    __syncthreads();
+    const uint32_t maxL = s_maxL;
+
+    // ---- walk 2: back to front from the tile's largest L ----
+    for (uint32_t cend = maxL; cend > 0;) {
+        const uint32_t c0 = cend > GCH ? cend - GCH : 0, m = cend - c0;
+        __syncthreads(); // the previous chunk's sums are added
+        stage_chunk(p, off, c0, m, s_ent, s_idx);
+        if (tid < GCH) s_touch[tid] = 0;
+        __syncthreads();
+        for (int j = (int)m - 1; j >= 0; --j) {
+            const uint32_t i = c0 + (uint32_t)j;
+            float alpha = 0.0f, ge = 0.0f, u = 0.0f, v = 0.0f, dx = 0.0f, dy = 0.0f;
+            bool in = false;
+            if (i < L) in = entry_alpha(s_ent[j], pxf, pyf, alpha, ge, u, v, dx, dy);
+            const unsigned long long hit = __ballot(in);
+            if (hit == 0) {
+                if (lane == 0) {
+#pragma unroll
+                    for (int k = 0; k < GNV; ++k) s_part[w][j][k] = 0.0f;
+                }
+                continue;
+            }
+            float vals[GNV];
+#pragma unroll
+            for (int k = 0; k < GNV; ++k) vals[k] = 0.0f;
+            if (in) {
+                const GradEntry &e = s_ent[j];
+                const float Ti = (i + 1 == L) ? T_last : Tn / (1.0f - alpha);
+                const float cg = ((G.x * e.b.z + G.y * e.b.w) + G.z * e.c.x) + G.w; // G . (c, 1)
+                const float dA = Ti * (cg - S);
+                const float wgt = Ti * alpha;
+                vals[5] = wgt * G.x;
+                vals[6] = wgt * G.y;
+                vals[7] = wgt * G.z;
+                vals[8] = ge * dA;
+                const float dd2 = -4.5f * alpha * dA;
+                const float du = 2.0f * u * dd2, dv = 2.0f * v * dd2;
+                vals[0] = -du * e.a.z;              // d2 / c.x
+                vals[1] = -(du * e.a.w + dv * e.b.x); // d2 / c.y
+                vals[2] = du * dx;                   // d2 / B00
+                vals[3] = du * dy;                   // d2 / B01
+                vals[4] = dv * dy;                   // d2 / B11
+                S = alpha * cg + (1.0f - alpha) * S;
+                Tn = Ti;
+            } else if (i + 1 == L) {
+                Tn = T_last;
+            }
+#pragma unroll
+            for (int k = 0; k < GNV; ++k) vals[k] = wave_sum63(vals[k]);
+            if (lane == 63) {
+#pragma unroll
+                for (int k = 0; k < GNV; ++k) s_part[w][j][k] = vals[k];
+                s_touch[j] = 1;
+            }
+        }
+        __syncthreads();
+        // one atomic add per touched (entry, number): the nine sums of an entry are its records row (20 of 32 bytes) and
+        // its colour row (16 bytes)
+        for (uint32_t q = tid; q < m * GNV; q += 256) {
+            const uint32_t e = q / GNV, k = q - e * GNV;
+            if (!s_touch[e]) continue;
+            const float sum = (s_part[0][e][k] + s_part[1][e][k]) + (s_part[2][e][k] + s_part[3][e][k]);
+            const size_t idx = s_idx[e];
+            float *dst = k < 5 ? p.grad_records + idx * 8 + (k < 4 ? k : 5u) : p.grad_color + idx * 4 + (k - 5);
+            atomicAdd(dst, sum);
+        }
+        cend = c0;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+struct GradUniforms {
+    float m[16];
+    float eye[3];
+    float time;
+    float w, h;
+};
+
+__global__ __launch_bounds__(256) void k_project_ellipsoid_backward(GradUniforms U, const float4 *__restrict__ pos, uint32_t ps,
+                                                                    const float4 *__restrict__ scl, uint32_t ss, const float4 *__restrict__ rot,
+                                                                    uint32_t rs, uint32_t n, const float4 *__restrict__ grec,
+                                                                    float4 *__restrict__ gpos, float4 *__restrict__ gscl, float4 *__restrict__ grot) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float4 pf = pos[(size_t)i * ps], sf = scl[(size_t)i * ss], qf = rot[(size_t)i * rs];
+    const DiscRecord r = ellipsoid_record(U.m, U.w, U.h, pf, sf, qf);
+    const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (r.b.y == 0.0f) { // culled (B11 = 1 / (3 sqrt(c)) > 0 in every record that is not)
+        gpos[i] = zero; gscl[i] = zero; grot[i] = zero;
+        return;
+    }
+    const float4 g0 = grec[(size_t)i * 2], g1 = grec[(size_t)i * 2 + 1];
+    double m[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) m[k] = (double)U.m[k];
+    const double W = U.w, H = U.h;
+    // forward in float64
+    const double qn = sqrt(((double)qf.x * qf.x + (double)qf.y * qf.y) + ((double)qf.z * qf.z + (double)qf.w * qf.w));
+    const double qr = qf.x / qn, qx = qf.y / qn, qy = qf.z / qn, qz = qf.w / qn;
+    const double R[3][3] = {{1.0 - 2.0 * (qy * qy + qz * qz), 2.0 * (qx * qy - qr * qz), 2.0 * (qx * qz + qr * qy)},
+                            {2.0 * (qx * qy + qr * qz), 1.0 - 2.0 * (qx * qx + qz * qz), 2.0 * (qy * qz - qr * qx)},
+                            {2.0 * (qx * qz - qr * qy), 2.0 * (qy * qz + qr * qx), 1.0 - 2.0 * (qx * qx + qy * qy)}};
+    const double s[3] = {sf.x, sf.y, sf.z};
+    double M[3][3];
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) M[a][b] = R[a][b] * s[b];
+    const double p[3] = {pf.x, pf.y, pf.z};
+    const double cx = m[0] * p[0] + m[4] * p[1] + m[8] * p[2] + m[12];
+    const double cy = m[1] * p[0] + m[5] * p[1] + m[9] * p[2] + m[13];
+    const double cw = m[3] * p[0] + m[7] * p[1] + m[11] * p[2] + m[15];
+    const double nx = cx / cw, ny = cy / cw;
+    const double ax = 0.5 * W / cw, ay = 0.5 * H / cw;
+    double J[2][3];
+    for (int k = 0; k < 3; ++k) {
+        J[0][k] = ax * (m[4 * k] - nx * m[4 * k + 3]);
+        J[1][k] = ay * (ny * m[4 * k + 3] - m[4 * k + 1]);
+    }
+    double T[2][3];
+    for (int a = 0; a < 2; ++a)
+        for (int b = 0; b < 3; ++b) T[a][b] = J[a][0] * M[0][b] + J[a][1] * M[1][b] + J[a][2] * M[2][b];
+    const double A = T[0][0] * T[0][0] + T[0][1] * T[0][1] + T[0][2] * T[0][2] + 0.3;
+    const double Bc = T[0][0] * T[1][0] + T[0][1] * T[1][1] + T[0][2] * T[1][2];
+    const double C = T[1][0] * T[1][0] + T[1][1] * T[1][1] + T[1][2] * T[1][2] + 0.3;
+    const double det = A * C - Bc * Bc;
+    const double b00 = sqrt(C / det) / 3.0, b01 = -Bc / sqrt(C * det) / 3.0, b11 = 1.0 / sqrt(C) / 3.0;
+    // backward: B -> (a, b, c)
+    const double gB00 = g0.z, gB01 = g0.w, gB11 = g1.y, gsx = g0.x, gsy = g0.y;
+    const double gdet = -(gB00 * b00 + gB01 * b01) / (2.0 * det);
+    const double gC = (gB00 * b00 - gB01 * b01 - gB11 * b11) / (2.0 * C) + gdet * A;
+    const double gA = gdet * C;
+    const double gB = gB01 * (-1.0 / (3.0 * sqrt(C * det))) - 2.0 * Bc * gdet;
+    double gT[2][3];
+    for (int k = 0; k < 3; ++k) {
+        gT[0][k] = 2.0 * gA * T[0][k] + gB * T[1][k];
+        gT[1][k] = 2.0 * gC * T[1][k] + gB * T[0][k];
+    }
+    // T = J M
+    double gJ[2][3], gM[3][3];
+    for (int a = 0; a < 2; ++a)
+        for (int k = 0; k < 3; ++k) gJ[a][k] = gT[a][0] * M[k][0] + gT[a][1] * M[k][1] + gT[a][2] * M[k][2];
+    for (int k = 0; k < 3; ++k)
+        for (int b = 0; b < 3; ++b) gM[k][b] = J[0][k] * gT[0][b] + J[1][k] * gT[1][b];
+    // M = R S
+    double gs[3] = {0.0, 0.0, 0.0}, gR[3][3];
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) {
+            gs[b] += gM[a][b] * R[a][b];
+            gR[a][b] = gM[a][b] * s[b];
+        }
+    // R(unit quaternion)
+    const double gqr = 2.0 * (-qz * gR[0][1] + qy * gR[0][2] + qz * gR[1][0] - qx * gR[1][2] - qy * gR[2][0] + qx * gR[2][1]);
+    const double gqx = 2.0 * (qy * gR[0][1] + qz * gR[0][2] + qy * gR[1][0] - 2.0 * qx * gR[1][1] - qr * gR[1][2] + qz * gR[2][0] +
+                              qr * gR[2][1] - 2.0 * qx * gR[2][2]);
+    const double gqy = 2.0 * (-2.0 * qy * gR[0][0] + qx * gR[0][1] + qr * gR[0][2] + qx * gR[1][0] + qz * gR[1][2] - qr * gR[2][0] +
+                              qz * gR[2][1] - 2.0 * qy * gR[2][2]);
+    const double gqz = 2.0 * (-2.0 * qz * gR[0][0] - qr * gR[0][1] + qx * gR[0][2] + qr * gR[1][0] - 2.0 * qz * gR[1][1] +
+                              qy * gR[1][2] + qx * gR[2][0] + qy * gR[2][1]);
+    // q / |q|
+    const double dotq = qr * gqr + qx * gqx + qy * gqy + qz * gqz;
+    grot[i] = make_float4((float)((gqr - qr * dotq) / qn), (float)((gqx - qx * dotq) / qn), (float)((gqy - qy * dotq) / qn),
+                          (float)((gqz - qz * dotq) / qn));
+    gscl[i] = make_float4((float)gs[0], (float)gs[1], (float)gs[2], 0.0f);
+    // J(nx, ny, cw) and the screen centre
+    double gax = 0.0, gay = 0.0, gnx = 0.5 * W * gsx, gny = -0.5 * H * gsy;
+    for (int k = 0; k < 3; ++k) {
+        gax += gJ[0][k] * (m[4 * k] - nx * m[4 * k + 3]);
+        gnx -= gJ[0][k] * ax * m[4 * k + 3];
+        gay += gJ[1][k] * (ny * m[4 * k + 3] - m[4 * k + 1]);
+        gny += gJ[1][k] * ay * m[4 * k + 3];
+    }
+    const double gcx = gnx / cw, gcy = gny / cw;
+    const double gcw = -(gax * ax + gay * ay) / cw - (gnx * nx + gny * ny) / cw;
+    double gp[3];
+    for (int k = 0; k < 3; ++k) gp[k] = gcx * m[4 * k] + gcy * m[4 * k + 1] + gcw * m[4 * k + 3];
+    gpos[i] = make_float4((float)gp[0], (float)gp[1], (float)gp[2], 0.0f);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr float GSH_C0 = 0.28209479177387814f;
+constexpr float GSH_C1 = 0.4886025119029199f;
+constexpr float GSH_C2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f, -1.0925484305920792f, 0.5462742152960396f};
+constexpr float GSH_C3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f, 0.3731763325901154f,
+                             -0.4570457994644658f, 1.445305721320277f, -0.5900435899266435f};
+
+template <int DEG>
+__global__ __launch_bounds__(256) void k_sh_colors_backward(float ex, float ey, float ez, const float4 *__restrict__ pos, uint32_t pos_stride,
+                                                            const float *__restrict__ sh, uint32_t sh_stride, const float4 *__restrict__ gcol,
+                                                            uint32_t n, float *__restrict__ gsh, float4 *__restrict__ gpos,
+                                                            float *__restrict__ gop) {
+    constexpr int NB = (DEG + 1) * (DEG + 1);
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float *row = sh + (size_t)i * sh_stride;
+    const float4 p = pos[(size_t)i * pos_stride];
+    const float4 gc = gcol[i];
+    float vx = p.x - ex, vy = p.y - ey, vz = p.z - ez;
+    const float len = sqrtf((vx * vx + vy * vy) + vz * vz);
+    const float il = 1.0f / len;
+    const float x = vx * il, y = vy * il, z = vz * il;
+    float Y[NB], Yx[NB], Yy[NB], Yz[NB];
+    Y[0] = GSH_C0; Yx[0] = 0.0f; Yy[0] = 0.0f; Yz[0] = 0.0f;
+    if (DEG > 0) {
+        Y[1] = -GSH_C1 * y; Yx[1] = 0.0f; Yy[1] = -GSH_C1; Yz[1] = 0.0f;
+        Y[2] = GSH_C1 * z;  Yx[2] = 0.0f; Yy[2] = 0.0f;    Yz[2] = GSH_C1;
+        Y[3] = -GSH_C1 * x; Yx[3] = -GSH_C1; Yy[3] = 0.0f; Yz[3] = 0.0f;
+    }
+    if (DEG > 1) {
+        const float xx = x * x, yy = y * y, zz = z * z;
+        Y[4] = GSH_C2[0] * (x * y);            Yx[4] = GSH_C2[0] * y;         Yy[4] = GSH_C2[0] * x;          Yz[4] = 0.0f;
+        Y[5] = GSH_C2[1] * (y * z);            Yx[5] = 0.0f;                  Yy[5] = GSH_C2[1] * z;          Yz[5] = GSH_C2[1] * y;
+        Y[6] = GSH_C2[2] * ((2.0f * zz - xx) - yy); Yx[6] = -2.0f * GSH_C2[2] * x; Yy[6] = -2.0f * GSH_C2[2] * y; Yz[6] = 4.0f * GSH_C2[2] * z;
+        Y[7] = GSH_C2[3] * (x * z);            Yx[7] = GSH_C2[3] * z;         Yy[7] = 0.0f;                   Yz[7] = GSH_C2[3] * x;
+        Y[8] = GSH_C2[4] * (xx - yy);          Yx[8] = 2.0f * GSH_C2[4] * x;  Yy[8] = -2.0f * GSH_C2[4] * y;  Yz[8] = 0.0f;
+        if (DEG > 2) {
+            Y[9] = GSH_C3[0] * (y * (3.0f * xx - yy));
+            Yx[9] = GSH_C3[0] * 6.0f * x * y; Yy[9] = GSH_C3[0] * 3.0f * (xx - yy); Yz[9] = 0.0f;
+            Y[10] = GSH_C3[1] * ((x * y) * z);
+            Yx[10] = GSH_C3[1] * y * z; Yy[10] = GSH_C3[1] * x * z; Yz[10] = GSH_C3[1] * x * y;
+            Y[11] = GSH_C3[2] * (y * ((4.0f * zz - xx) - yy));
+            Yx[11] = -2.0f * GSH_C3[2] * x * y; Yy[11] = GSH_C3[2] * ((4.0f * zz - xx) - 3.0f * yy); Yz[11] = 8.0f * GSH_C3[2] * y * z;
+            Y[12] = GSH_C3[3] * (z * ((2.0f * zz - 3.0f * xx) - 3.0f * yy));
+            Yx[12] = -6.0f * GSH_C3[3] * x * z; Yy[12] = -6.0f * GSH_C3[3] * y * z; Yz[12] = GSH_C3[3] * ((6.0f * zz - 3.0f * xx) - 3.0f * yy);
+            Y[13] = GSH_C3[4] * (x * ((4.0f * zz - xx) - yy));
+            Yx[13] = GSH_C3[4] * ((4.0f * zz - 3.0f * xx) - yy); Yy[13] = -2.0f * GSH_C3[4] * x * y; Yz[13] = 8.0f * GSH_C3[4] * x * z;
+            Y[14] = GSH_C3[5] * (z * (xx - yy));
+            Yx[14] = 2.0f * GSH_C3[5] * x * z; Yy[14] = -2.0f * GSH_C3[5] * y * z; Yz[14] = GSH_C3[5] * (xx - yy);
+            Y[15] = GSH_C3[6] * (x * (xx - 3.0f * yy));
+            Yx[15] = GSH_C3[6] * 3.0f * (xx - yy); Yy[15] = -6.0f * GSH_C3[6] * x * y; Yz[15] = 0.0f;
+        }
+    }
+    float r = 0.0f, g = 0.0f, b = 0.0f;
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {
+        r += Y[k] * row[3 * k];
+        g += Y[k] * row[3 * k + 1];
+        b += Y[k] * row[3 * k + 2];
+    }
+    // the clamp: no gradient where the forward's max(., 0) took the 0
+    const float gr = (r + 0.5f > 0.0f) ? gc.x : 0.0f, gg = (g + 0.5f > 0.0f) ? gc.y : 0.0f, gb = (b + 0.5f > 0.0f) ? gc.z : 0.0f;
+    float *orow = gsh + (size_t)i * sh_stride;
+    float gx = 0.0f, gy = 0.0f, gz = 0.0f;
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {
+        orow[3 * k] = Y[k] * gr;
+        orow[3 * k + 1] = Y[k] * gg;
+        orow[3 * k + 2] = Y[k] * gb;
+        const float gY = (gr * row[3 * k] + gg * row[3 * k + 1]) + gb * row[3 * k + 2];
+        gx += gY * Yx[k];
+        gy += gY * Yy[k];
+        gz += gY * Yz[k];
+    }
+    // dir = v / |v|:  dL/dv = (g - dir (dir . g)) / |v|
+    const float dg = (x * gx + y * gy) + z * gz;
+    gpos[i] = make_float4((gx - x * dg) * il, (gy - y * dg) * il, (gz - z * dg) * il, 0.0f);
+    gop[i] = gc.w;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+extern "C" int splat_composite_backward(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4,
+                                        const void *records, const void *tile_indices, const void *tile_counts, const void *tile_offsets,
+                                        uint32_t width, uint32_t height, const void *grad_rgba32f, uint32_t n, void *grad_records,
+                                        void *grad_color_opacity) {
+    if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
+    ARG_CHECK(ctx, cfg != nullptr);
+    if (cfg->footprint != SPLAT_FOOTPRINT_ELLIPSOID || cfg->mode != SPLAT_COMPOSITE_FRONT_TO_BACK || cfg->early_out != 1 ||
+        cfg->tile_size != GT || cfg->record_format != SPLAT_RECORDS_PROJECTED)
+        return ctx_fail(ctx, SPLAT_ERR_INVALID, "splat_composite_backward: footprint ELLIPSOID, FRONT_TO_BACK, early_out = 1, tile_size = 16 "
+                                                "and PROJECTED records only");
+    ARG_CHECK(ctx, width >= 1 && height >= 1 && width <= 65535u * GT && height <= 65535u * GT);
+    const uint32_t ntx = div_up(width, GT), nty = div_up(height, GT);
+    ARG_CHECK(ctx, cfg->tile_row0 == 0 && cfg->tile_row1 >= nty); // the whole screen: no strict band
+    ARG_CHECK(ctx, color_stride_vec4 >= 1);
+    ARG_CHECK(ctx, color_opacity && records && tile_indices && tile_counts && tile_offsets && grad_rgba32f);
+    ARG_CHECK(ctx, n == 0 || (grad_records && grad_color_opacity));
+    ARG_CHECK(ctx, (((uintptr_t)color_opacity | (uintptr_t)records | (uintptr_t)grad_rgba32f | (uintptr_t)grad_records |
+                     (uintptr_t)grad_color_opacity) & 15) == 0);
+    ARG_CHECK(ctx, (((uintptr_t)tile_indices | (uintptr_t)tile_counts | (uintptr_t)tile_offsets) & 3) == 0);
+    if (n == 0) return SPLAT_OK; // (no splat: every list is empty)
+    BackParams p;
+    p.color = (const float4 *)color_opacity;
+    p.color_stride = color_stride_vec4;
+    p.records = (const float4 *)records;
+    p.indices = (const uint32_t *)tile_indices;
+    p.counts = (const uint32_t *)tile_counts;
+    p.offsets = (const uint32_t *)tile_offsets;
+    p.width = width;
+    p.height = height;
+    p.ntx = ntx;
+    p.grad_img = (const float4 *)grad_rgba32f;
+    p.grad_records = (float *)grad_records;
+    p.grad_color = (float *)grad_color_opacity;
+    hipLaunchKernelGGL(k_composite_backward, dim3(ntx, nty), dim3(256), 0, ctx->stream, p);
+    LAUNCH_CHECK(ctx, "k_composite_backward");
+    return SPLAT_OK;
+}
+
+extern "C" int splat_project_ellipsoid_backward(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4,
+                                                const void *scales, uint32_t scale_stride_vec4, const void *rotations, uint32_t rot_stride_vec4,
+                                                uint32_t n, const void *grad_records, void *grad_positions, void *grad_scales, void *grad_rotations) {
+    if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
+    ARG_CHECK(ctx, uniforms && (n == 0 || (positions && scales && rotations && grad_records && grad_positions && grad_scales && grad_rotations)));
+    ARG_CHECK(ctx, pos_stride_vec4 >= 1 && scale_stride_vec4 >= 1 && rot_stride_vec4 >= 1);
+    ARG_CHECK(ctx, (((uintptr_t)positions | (uintptr_t)scales | (uintptr_t)rotations | (uintptr_t)grad_records | (uintptr_t)grad_positions |
+                     (uintptr_t)grad_scales | (uintptr_t)grad_rotations) & 15) == 0);
+    if (n == 0) return SPLAT_OK;
+    GradUniforms u;
+    for (int k = 0; k < 22; ++k) (&u.m[0])[k] = uniforms[k];
+    hipLaunchKernelGGL(k_project_ellipsoid_backward, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, u, (const float4 *)positions,
+                       pos_stride_vec4, (const float4 *)scales, scale_stride_vec4, (const float4 *)rotations, rot_stride_vec4, n,
+                       (const float4 *)grad_records, (float4 *)grad_positions, (float4 *)grad_scales, (float4 *)grad_rotations);
+    LAUNCH_CHECK(ctx, "k_project_ellipsoid_backward");
+    return SPLAT_OK;
+}
+
+extern "C" int splat_sh_colors_backward(splat_ctx *ctx, const float *eye3, const void *positions, uint32_t pos_stride_vec4, const void *sh,
+                                        uint32_t sh_stride_floats, uint32_t degree, const void *opacity_f32, const void *grad_color_opacity,
+                                        uint32_t n, void *grad_sh, void *grad_positions, void *grad_opacity) {
+    if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
+    ARG_CHECK(ctx, eye3 && degree <= 3 && pos_stride_vec4 >= 1);
+    ARG_CHECK(ctx, n == 0 || (positions && sh && grad_color_opacity && grad_sh && grad_positions && grad_opacity));
+    ARG_CHECK(ctx, sh_stride_floats >= 3 * (degree + 1) * (degree + 1));
+    ARG_CHECK(ctx, (((uintptr_t)positions | (uintptr_t)grad_color_opacity | (uintptr_t)grad_positions) & 15) == 0 &&
+                       (((uintptr_t)sh | (uintptr_t)grad_sh | (uintptr_t)grad_opacity | (uintptr_t)opacity_f32) & 3) == 0);
+    if (n == 0) return SPLAT_OK;
+    const dim3 grid(div_up(n, 256)), block(256);
+#define SPLAT_SHB_LAUNCH(D)                                                                                                                 \
+    hipLaunchKernelGGL((k_sh_colors_backward<D>), grid, block, 0, ctx->stream, eye3[0], eye3[1], eye3[2], (const float4 *)positions,       \
+                       pos_stride_vec4, (const float *)sh, sh_stride_floats, (const float4 *)grad_color_opacity, n, (float *)grad_sh,       \
+                       (float4 *)grad_positions, (float *)grad_opacity)
+    switch (degree) {
+    case 0: SPLAT_SHB_LAUNCH(0); break;
+    case 1: SPLAT_SHB_LAUNCH(1); break;
+    case 2: SPLAT_SHB_LAUNCH(2); break;
+    default: SPLAT_SHB_LAUNCH(3); break;
+    }
+#undef SPLAT_SHB_LAUNCH
+    LAUNCH_CHECK(ctx, "k_sh_colors_backward");
+    return SPLAT_OK;
+}

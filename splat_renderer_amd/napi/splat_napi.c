@@ -359,6 +359,30 @@ FN(sh_colors) { /* (ctx, Float32Array(3) eye, positions, posStride, sh, shStride
     if (eb < 3 * sizeof(float)) { napi_throw_range_error(env, NULL, "eye needs 3 floats"); return NULL; }
     return check(env, x, splat_sh_colors(x, eye, pos, ps, sh, shs, deg, op, n, out), mk_undefined(env));
 }
+FN(composite_backward) { /* (ctx, cfg[8], colorOpacity, cStride, records, indices, counts, offsets, W, H, gradRgba32f, n, gradRecords, gradColorOpacity) */
+    ARGS(14); splat_ctx *x = arg_external(&c, 0); splat_composite_cfg cfg; fill_cfg(&c, 1, &cfg);
+    void *col = arg_dptr(&c, 2); uint32_t cs = (uint32_t)arg_number(&c, 3); void *rec = arg_dptr(&c, 4);
+    void *idx = arg_dptr(&c, 5), *cnt = arg_dptr(&c, 6), *off = arg_dptr(&c, 7);
+    uint32_t w = (uint32_t)arg_number(&c, 8), h = (uint32_t)arg_number(&c, 9); void *gimg = arg_dptr(&c, 10);
+    uint32_t n = (uint32_t)arg_number(&c, 11); void *grec = arg_dptr(&c, 12), *gcol = arg_dptr(&c, 13); BAIL;
+    return check(env, x, splat_composite_backward(x, &cfg, col, cs, rec, idx, cnt, off, w, h, gimg, n, grec, gcol), mk_undefined(env));
+}
+FN(project_ellipsoid_backward) { /* (ctx, Float32Array(22), positions, posStride, scales, scaleStride, rotations, rotStride, n, gradRecords, gradPositions, gradScales, gradRotations) */
+    ARGS(13); splat_ctx *x = arg_external(&c, 0); size_t ub = 0; float *u = arg_hostbuf(&c, 1, &ub);
+    void *pos = arg_dptr(&c, 2); uint32_t ps = (uint32_t)arg_number(&c, 3); void *scl = arg_dptr(&c, 4); uint32_t ss = (uint32_t)arg_number(&c, 5);
+    void *rot = arg_dptr(&c, 6); uint32_t rs = (uint32_t)arg_number(&c, 7), n = (uint32_t)arg_number(&c, 8);
+    void *grec = arg_dptr(&c, 9), *gp = arg_dptr(&c, 10), *gs = arg_dptr(&c, 11), *gr = arg_dptr(&c, 12); BAIL;
+    if (ub < 22 * sizeof(float)) { napi_throw_range_error(env, NULL, "uniform block needs 22 floats"); return NULL; }
+    return check(env, x, splat_project_ellipsoid_backward(x, u, pos, ps, scl, ss, rot, rs, n, grec, gp, gs, gr), mk_undefined(env));
+}
+FN(sh_colors_backward) { /* (ctx, Float32Array(3) eye, positions, posStride, sh, shStrideFloats, degree, opacity|null, gradColorOpacity, n, gradSh, gradPositions, gradOpacity) */
+    ARGS(13); splat_ctx *x = arg_external(&c, 0); size_t eb = 0; float *eye = arg_hostbuf(&c, 1, &eb);
+    void *pos = arg_dptr(&c, 2); uint32_t ps = (uint32_t)arg_number(&c, 3); void *sh = arg_dptr(&c, 4);
+    uint32_t shs = (uint32_t)arg_number(&c, 5), deg = (uint32_t)arg_number(&c, 6); void *op = arg_dptr(&c, 7), *gcol = arg_dptr(&c, 8);
+    uint32_t n = (uint32_t)arg_number(&c, 9); void *gsh = arg_dptr(&c, 10), *gp = arg_dptr(&c, 11), *gop = arg_dptr(&c, 12); BAIL;
+    if (eb < 3 * sizeof(float)) { napi_throw_range_error(env, NULL, "eye needs 3 floats"); return NULL; }
+    return check(env, x, splat_sh_colors_backward(x, eye, pos, ps, sh, shs, deg, op, gcol, n, gsh, gp, gop), mk_undefined(env));
+}
 FN(render_frame_ellipsoids) { /* (ctx, sorter, binner, cfg[8], Float32Array(22), positions, scales, rotations, colorOpacity, n, W, H, projected|null, out8|null, outF|null, [depth, alpha, ids]|null) */
     ARGS(16); splat_ctx *x = arg_external(&c, 0); splat_sorter *s = arg_external(&c, 1); splat_binner *b = arg_external(&c, 2);
     splat_composite_cfg cfg; fill_cfg(&c, 3, &cfg); size_t ub = 0; float *u = arg_hostbuf(&c, 4, &ub);
@@ -621,6 +645,7 @@ static napi_value init(napi_env env, napi_value exports) {
         EXPORT(project_slice_disc), EXPORT(expand_compact), EXPORT(band_keys), EXPORT(band_kept), EXPORT(comm_rank), EXPORT(comm_count),
         EXPORT(allgather_records), EXPORT(sdf_gradients), EXPORT(sdf_update_positions), EXPORT(sdf_scale_factors), EXPORT(sdf_curvature), EXPORT(sdf_seed_positions), EXPORT(sdf_generate),
         EXPORT(point_frame), EXPORT(project_ellipsoid), EXPORT(sh_colors), EXPORT(render_frame_ellipsoids),
+        EXPORT(composite_backward), EXPORT(project_ellipsoid_backward), EXPORT(sh_colors_backward),
     };
     napi_define_properties(env, exports, sizeof d / sizeof d[0], d);
     return exports;
