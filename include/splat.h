@@ -371,6 +371,18 @@ int splat_composite_aov(splat_ctx *ctx, const splat_composite_cfg *cfg, const vo
                         const void *projected, const void *tile_indices, const void *tile_counts,
                         const void *tile_offsets, uint32_t width, uint32_t height, void *out_rgba8,
                         void *out_rgba32f, void *consumed_dptr, const splat_aov *aov);
+/* splat_composite_aov with the caller's per-splat depth: the AOV depth reads z_i = depth_f32[i * depth_stride_floats] instead
+ * of the records' own (ProjectedSplat records: projected + 4 floats with stride 8; a plain n-float array: stride 1).  Valid
+ * for every footprint and record format splat_composite_aov takes, the projector's 32-byte disc and ellipsoid records
+ * included.  The aov struct still decides which buffers are written; the image is splat_composite_aov's bit for bit.
+ * SPLAT_ERR_INVALID as for splat_composite_aov, and for depth_f32 NULL, depth_stride_floats 0 or depth_f32 not 4-byte
+ * aligned. */
+int splat_composite_aov_depth(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity,
+                              uint32_t color_stride_vec4, const void *normals, uint32_t normal_stride_vec4,
+                              const void *projected, const void *tile_indices, const void *tile_counts,
+                              const void *tile_offsets, uint32_t width, uint32_t height, void *out_rgba8,
+                              void *out_rgba32f, void *consumed_dptr, const splat_aov *aov, const void *depth_f32,
+                              uint32_t depth_stride_floats);
 
 /* ---- whole frame: project -> keys -> sort -> bin -> composite ----------------
  * With cfg->tile_row0/1 set to a strict band of tile rows (multi-GPU, no exchange: every rank renders its band from
@@ -463,6 +475,27 @@ int splat_composite_backward(splat_ctx *ctx, const splat_composite_cfg *cfg, con
                              const void *records, const void *tile_indices, const void *tile_counts, const void *tile_offsets,
                              uint32_t width, uint32_t height, const void *grad_rgba32f, uint32_t n, void *grad_records,
                              void *grad_color_opacity);
+/* Gradients of the depth map (splat_composite_aov_depth's AOV depth).  Per pixel, over the entries it consumed (the cut and the
+ * stop held fixed as above): w_i = T_i alpha_i, ws = sum w_i, zw = sum w_i z_i, D = zw / ws (+inf where ws = 0), z_i any
+ * per-splat float the caller supplies (the ProjectedSplat depth, the distance from the eye to the centre, by default; not
+ * view-space z).  With G_D = dL/dD:
+ *   dL/dz_i = G_D w_i / ws;
+ *   through alpha, D is a fifth channel of the recurrence above with colour z_i - D (centred), background 0 and upstream
+ *   G_D / ws: cg_i = G_rgb . c_i + G_A + (G_D / ws)(z_i - D), dL/dalpha_i = T_i (cg_i - S_i), S as before.  Centred, because
+ *   sum w_i (z_i - D) = 0 makes this the derivative of zw / ws, without the cancellation of G_A - (G_D / ws) D against
+ *   (G_D / ws) z_i where the depth spread is much smaller than the depth.
+ * G_D is not read where ws = 0: such a pixel has no gradient, and a NaN or inf upstream there is harmless.  Where ws is tiny the
+ * gradient is large: that is the function's own gradient.  Sums are float atomics as above, reproducible to rounding only.
+ *
+ * splat_composite_backward_depth: splat_composite_backward's arguments and checks (every screen the binner takes) plus
+ * depth_f32 / depth_stride_floats (the z the forward read: z_i = depth_f32[i * depth_stride_floats]), grad_depth_f32 (W*H
+ * floats, dL/dD) and grad_depth (n floats, dL/dz, ADDED into).  NULL depth_f32 / grad_depth_f32 / grad_depth (n > 0), stride 0,
+ * or one of the three not 4-byte aligned: SPLAT_ERR_INVALID. */
+int splat_composite_backward_depth(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4,
+                                   const void *records, const void *tile_indices, const void *tile_counts, const void *tile_offsets,
+                                   uint32_t width, uint32_t height, const void *grad_rgba32f, uint32_t n, void *grad_records,
+                                   void *grad_color_opacity, const void *depth_f32, uint32_t depth_stride_floats,
+                                   const void *grad_depth_f32, void *grad_depth);
 /* splat_project_ellipsoid's backward: dL/drecords (n x 8, splat_composite_backward's layout) -> dL/dposition (xyz, w = 0),
  * dL/dscale (xyz, w = 0) and dL/drotation (w, x, y, z of the quaternion as given, through its normalisation), all n x 4 f32,
  * OVERWRITTEN.  The centre and J move with the position.  The cull decisions are the forward's (csrc/ellipsoid.h); a culled
@@ -470,6 +503,14 @@ int splat_composite_backward(splat_ctx *ctx, const splat_composite_cfg *cfg, con
 int splat_project_ellipsoid_backward(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4,
                                      const void *scales, uint32_t scale_stride_vec4, const void *rotations, uint32_t rot_stride_vec4,
                                      uint32_t n, const void *grad_records, void *grad_positions, void *grad_scales, void *grad_rotations);
+/* splat_project_ellipsoid_backward plus grad_depth (n floats, 4-byte aligned): dL/dz of the ProjectedSplat depth z = |p - eye|
+ * (eye = uniforms[16..18]), whose term gz (p - eye) / |p - eye| is added, in float64, to dL/dposition.  A culled splat still
+ * gets exact zeros, its depth term included.  Where grad_depth[i] = 0 the outputs are splat_project_ellipsoid_backward's bit for
+ * bit. */
+int splat_project_ellipsoid_backward_depth(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4,
+                                           const void *scales, uint32_t scale_stride_vec4, const void *rotations, uint32_t rot_stride_vec4,
+                                           uint32_t n, const void *grad_records, void *grad_positions, void *grad_scales,
+                                           void *grad_rotations, const void *grad_depth);
 /* splat_sh_colors' backward: dL/dcolor_opacity (n x 4) -> dL/dsh (same layout and stride as sh; the floats past
  * 3 (degree + 1)^2 in a row are not written), dL/dposition (n x 4, through dir = normalize(p - eye); w = 0) and dL/dopacity
  * (n floats: the fourth column passed through), OVERWRITTEN.  Zero colour gradient where the forward's max(., 0) clamped.

@@ -85,6 +85,12 @@ SIGNATURES = {
     "splat_composite_backward": (_i, [_vp, C.POINTER(CompositeCfg), _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _vp, _vp]),
     "splat_project_ellipsoid_backward": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp]),
     "splat_sh_colors_backward": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _vp, _u32, _u32, _vp, _vp, _u32, _vp, _vp, _vp]),
+    "splat_composite_aov_depth": (_i, [_vp, C.POINTER(CompositeCfg), _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp,
+                                       C.POINTER(Aov), _vp, _u32]),
+    "splat_composite_backward_depth": (_i, [_vp, C.POINTER(CompositeCfg), _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _vp, _vp,
+                                            _vp, _u32, _vp, _vp]),
+    "splat_project_ellipsoid_backward_depth": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp,
+                                                    _vp]),
     "splat_extract_keys": (_i, [_vp, _vp, _u32, _u32, _vp, _vp]),
     "splat_sort_create": (_i, [_vp, _u32, _pvp]),
     "splat_sort_destroy": (None, [_vp]),

@@ -5,6 +5,22 @@
     rgb, alpha = rasterize(rec, col, aux, width, height)                  # (H, W, 3), (H, W)
     rgb, alpha = render_gaussians(camera_or_uniforms, means, scales, rotations, opacities, colors=None, sh=None, width=..., height=...)
 
+With a depth map (every result differentiable):
+
+    rec, depths, aux   = project_ellipsoids(uniforms, means, scales, rotations, return_depth=True)  # depths (n,) = aux.projected[:, 4]
+    rgb, alpha, depth  = rasterize(rec, col, aux, width, height, depths=depths)                      # depth (H, W)
+    rgb, alpha, depth  = render_gaussians(..., return_depth=True)
+
+depth is the AOV depth of include/splat.h: per pixel sum w_i z_i / sum w_i over the entries it consumed (w_i = T_i alpha_i,
+the colour's own weights), +inf where nothing contributed.  z_i is whatever (n,) tensor is passed as `depths`: the default,
+project_ellipsoids' depths, is the distance from the eye to each centre (the depth the sort orders by), not view-space z.  A
+caller who wants planar z computes it in torch from `means` (e.g. (means - eye) . forward) and passes that instead; its
+gradient flows back through torch.  3DGS's accumulated depth sum w_i z_i is depth * alpha where alpha > 0 (sum w_i = alpha up
+to rounding) and 0 elsewhere; torch.where(alpha > 0, depth, 0) * alpha computes it with a finite gradient everywhere (a
+gradient through depth * alpha at an empty pixel would multiply by its +inf).  The backward of the depth map is
+splat_composite_backward_depth and splat_project_ellipsoid_backward_depth; an upstream gradient at pixels where depth is +inf
+is not read, so NaN or inf there is harmless.
+
 Every kernel runs on torch's current stream (a Device created on it, cached per device and stream).  Tensors must be CUDA
 float32; there is no CPU path (SplatError).  The forward is the staged frame of include/splat.h (splat_project_ellipsoid ->
 sort -> splat_bin_run -> splat_composite_aov), so rasterize's image is Renderer(footprint="ellipsoid")'s bit for bit; the
@@ -182,7 +198,7 @@ def _functions():
 
     class Project(torch.autograd.Function):
         @staticmethod
-        def forward(fctx, u, means4, scales4, rots):
+        def forward(fctx, u, means4, scales4, rots, with_depth=False):
             cx = _context(means4)
             n = means4.shape[0]
             padded = cx.ensure_sorter(n)
@@ -196,19 +212,28 @@ def _functions():
             fctx.save_for_backward(means4, scales4, rots)
             fctx.u = u
             aux = ProjectedSplats(cx, u, n, proj, keys, pay)
+            if with_depth:  # (the ProjectedSplat depth, as a tensor of its own: bit for bit aux.projected[:, 4])
+                fctx.set_materialize_grads(False)  # (an unused depth: None, and the colour-only kernel)
+                return rec, proj[:, 4].contiguous(), aux
             return rec, aux
 
         @staticmethod
-        def backward(fctx, grad_rec, _grad_aux=None):
+        def backward(fctx, grad_rec, *grads):
+            grad_depth = grads[0] if len(grads) == 2 else None  # (rec, depths, aux) or (rec, aux)
             means4, scales4, rots = fctx.saved_tensors
             n = means4.shape[0]
             cx = _context(means4)
-            g = _cuda_f32(grad_rec, "grad_records", 8)
+            g = _cuda_f32(grad_rec, "grad_records", 8) if grad_rec is not None else torch.zeros((n, 8), device=means4.device, dtype=torch.float32)
             gp, gs, gr = (torch.empty((n, 4), device=means4.device, dtype=torch.float32) for _ in range(3))
-            if n:
+            if n and grad_depth is None:
                 check(cx.lib.splat_project_ellipsoid_backward(cx.ctx, _fptr(fctx.u), means4.data_ptr(), 1, scales4.data_ptr(), 1, rots.data_ptr(), 1,
                                                               n, g.data_ptr(), gp.data_ptr(), gs.data_ptr(), gr.data_ptr()), cx.ctx)
-            return None, gp, gs, gr
+            elif n:
+                gz = _cuda_f32(grad_depth.reshape(-1), "grad_depths")
+                check(cx.lib.splat_project_ellipsoid_backward_depth(cx.ctx, _fptr(fctx.u), means4.data_ptr(), 1, scales4.data_ptr(), 1, rots.data_ptr(),
+                                                                    1, n, g.data_ptr(), gp.data_ptr(), gs.data_ptr(), gr.data_ptr(), gz.data_ptr()),
+                      cx.ctx)
+            return None, gp, gs, gr, None
 
     class ShColors(torch.autograd.Function):
         @staticmethod
@@ -239,7 +264,7 @@ def _functions():
 
     class Rasterize(torch.autograd.Function):
         @staticmethod
-        def forward(fctx, rec, col, aux, width, height):
+        def forward(fctx, rec, col, aux, width, height, depths=None):
             cx = aux.ctx
             n = aux.n
             out = torch.empty((height, width, 4), device=rec.device, dtype=torch.float32)
@@ -247,17 +272,26 @@ def _functions():
             gen = cx.bin(aux, width, height)
             idx, cnt, off = cx.lists()
             cfg = CompositeCfg(_lib.MODE_FRONT_TO_BACK, 1, TILE, 0, _lib.U32_MAX, _lib.RECORDS_PROJECTED, 1, _lib.FOOTPRINT_ELLIPSOID)
-            aov = _lib.Aov(None, alpha.data_ptr(), None)
-            check(cx.lib.splat_composite_aov(cx.ctx, C.byref(cfg), col.data_ptr(), 1, None, 1, rec.data_ptr(), idx, cnt, off, width, height,
-                                             None, out.data_ptr(), None, C.byref(aov)), cx.ctx)
-            fctx.save_for_backward(rec, col)
+            if depths is None:
+                aov = _lib.Aov(None, alpha.data_ptr(), None)
+                check(cx.lib.splat_composite_aov(cx.ctx, C.byref(cfg), col.data_ptr(), 1, None, 1, rec.data_ptr(), idx, cnt, off, width, height,
+                                                 None, out.data_ptr(), None, C.byref(aov)), cx.ctx)
+                fctx.save_for_backward(rec, col)
+            else:
+                depth = torch.empty((height, width), device=rec.device, dtype=torch.float32)
+                aov = _lib.Aov(depth.data_ptr(), alpha.data_ptr(), None)
+                check(cx.lib.splat_composite_aov_depth(cx.ctx, C.byref(cfg), col.data_ptr(), 1, None, 1, rec.data_ptr(), idx, cnt, off, width,
+                                                       height, None, out.data_ptr(), None, C.byref(aov), depths.data_ptr(), 1), cx.ctx)
+                fctx.save_for_backward(rec, col, depths)
+                fctx.set_materialize_grads(False)  # (an unused depth map: None, and the colour-only kernel)
             fctx.aux, fctx.gen, fctx.wh = aux, gen, (width, height)
             rgb = out[..., :3]
-            return rgb, alpha
+            return (rgb, alpha) if depths is None else (rgb, alpha, depth)
 
         @staticmethod
-        def backward(fctx, grad_rgb, grad_alpha):
-            rec, col = fctx.saved_tensors
+        def backward(fctx, grad_rgb, grad_alpha, grad_depth_map=None):
+            rec, col = fctx.saved_tensors[:2]
+            depths = fctx.saved_tensors[2] if len(fctx.saved_tensors) == 3 else None
             aux = fctx.aux
             cx = aux.ctx
             width, height = fctx.wh
@@ -273,26 +307,35 @@ def _functions():
             grec = torch.zeros((n, 8), device=rec.device, dtype=torch.float32)
             gcol = torch.zeros((n, 4), device=rec.device, dtype=torch.float32)
             cfg = CompositeCfg(_lib.MODE_FRONT_TO_BACK, 1, TILE, 0, _lib.U32_MAX, _lib.RECORDS_PROJECTED, 1, _lib.FOOTPRINT_ELLIPSOID)
+            if depths is None or grad_depth_map is None:
+                if n:
+                    check(cx.lib.splat_composite_backward(cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr(), idx, cnt, off, width, height,
+                                                          g.data_ptr(), n, grec.data_ptr(), gcol.data_ptr()), cx.ctx)
+                return grec, gcol, None, None, None, None
+            gd = _cuda_f32(grad_depth_map, "grad_depth")
+            gz = torch.zeros(n, device=rec.device, dtype=torch.float32)
             if n:
-                check(cx.lib.splat_composite_backward(cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr(), idx, cnt, off, width, height,
-                                                      g.data_ptr(), n, grec.data_ptr(), gcol.data_ptr()), cx.ctx)
-            return grec, gcol, None, None, None
+                check(cx.lib.splat_composite_backward_depth(cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr(), idx, cnt, off, width, height,
+                                                            g.data_ptr(), n, grec.data_ptr(), gcol.data_ptr(), depths.data_ptr(), 1, gd.data_ptr(),
+                                                            gz.data_ptr()), cx.ctx)
+            return grec, gcol, None, None, None, gz
 
     fns = (Project, ShColors, Rasterize)
     globals()["_fns"] = fns
     return fns
 
 
-def project_ellipsoids(uniforms, means, scales, rotations, width=None, height=None):
+def project_ellipsoids(uniforms, means, scales, rotations, width=None, height=None, return_depth=False):
     """(rec (n, 8) differentiable records {c.x, c.y, B00, B01, 0, B11, 0, 0}, aux: ProjectedSplats).  uniforms: a Camera (then
-    width and height are required) or the 22-float block."""
+    width and height are required) or the 22-float block.  return_depth=True: (rec, depths, aux), depths (n,) the
+    differentiable ProjectedSplat depth |mean - eye| (aux.projected[:, 4] bit for bit; rasterize's `depths`)."""
     u = _uniforms(uniforms, width, height)
     means4 = _cuda_f32(_vec4(means, "means", 1.0), "means", 4)
     scales4 = _cuda_f32(_vec4(scales, "scales"), "scales", 4)
     rots = _cuda_f32(rotations, "rotations", 4)
     if not (means4.shape[0] == scales4.shape[0] == rots.shape[0]):
         raise SplatError(-1, "means, scales and rotations must hold the same number of splats")
-    return _functions()[0].apply(u, means4, scales4, rots)
+    return _functions()[0].apply(u, means4, scales4, rots, bool(return_depth))
 
 
 def sh_colors(eye, means, sh, degree, opacities):
@@ -312,26 +355,39 @@ def sh_colors(eye, means, sh, degree, opacities):
     return _functions()[1].apply(e, means4, sh2, int(degree), op)
 
 
-def rasterize(rec, col, aux, width=None, height=None):
-    """(rgb (H, W, 3), alpha (H, W)) of the records and colours over the projection's lists; both differentiable."""
+def rasterize(rec, col, aux, width=None, height=None, depths=None):
+    """(rgb (H, W, 3), alpha (H, W)) of the records and colours over the projection's lists; both differentiable.  With
+    depths ((n,) per-splat z, differentiable): (rgb, alpha, depth), depth (H, W) = sum w z / sum w per pixel, +inf where
+    nothing contributed."""
     width = aux.width if width is None else int(width)
     height = aux.height if height is None else int(height)
     rec_c = _cuda_f32(rec, "rec", 8)
     col_c = _cuda_f32(col, "col", 4)
     if rec_c.shape[0] != aux.n or col_c.shape[0] != aux.n:
         raise SplatError(-1, "rec, col and the projection must hold the same number of splats")
-    return _functions()[2].apply(rec_c, col_c, aux, width, height)
+    if depths is None:
+        return _functions()[2].apply(rec_c, col_c, aux, width, height)
+    z = _cuda_f32(depths, "depths")
+    if z.dim() != 1 or z.shape[0] != aux.n:
+        raise SplatError(-1, f"depths must have shape ({aux.n},), not {tuple(z.shape)}")
+    return _functions()[2].apply(rec_c, col_c, aux, width, height, z)
 
 
-def render_gaussians(camera_or_uniforms, means, scales, rotations, opacities, colors=None, sh=None, width=None, height=None, degree=None):
+def render_gaussians(camera_or_uniforms, means, scales, rotations, opacities, colors=None, sh=None, width=None, height=None, degree=None,
+                     return_depth=False):
     """The whole differentiable frame: project_ellipsoids, the colour (sh_colors when `sh` is given, else cat(colors,
-    opacities)), rasterize.  Returns (rgb (H, W, 3), alpha (H, W))."""
+    opacities)), rasterize.  Returns (rgb (H, W, 3), alpha (H, W)); return_depth=True: (rgb, alpha, depth (H, W)), the depth
+    map of the ProjectedSplat depths (the distance from the eye to each centre)."""
     if width is None or height is None:
         raise SplatError(-1, "render_gaussians needs width and height")
     for name, t in (("means", means), ("scales", scales), ("rotations", rotations), ("opacities", opacities)):
         _cuda_f32(t, name)
     u = _uniforms(camera_or_uniforms, width, height)
-    rec, aux = project_ellipsoids(u, means, scales, rotations)
+    if return_depth:
+        rec, depths, aux = project_ellipsoids(u, means, scales, rotations, return_depth=True)
+    else:
+        rec, aux = project_ellipsoids(u, means, scales, rotations)
+        depths = None
     n = aux.n
     if sh is not None:
         k = sh.reshape(n, -1).shape[1] // 3
@@ -344,4 +400,4 @@ def render_gaussians(camera_or_uniforms, means, scales, rotations, opacities, co
         col = _t().cat([colors, opacities.reshape(-1, 1)], dim=1)
     else:
         raise SplatError(-1, "render_gaussians needs colors or sh")
-    return rasterize(rec, col, aux, width, height)
+    return rasterize(rec, col, aux, width, height, depths=depths)

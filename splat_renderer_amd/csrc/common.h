@@ -303,7 +303,7 @@ int composite_launch(splat_ctx *ctx, const splat_composite_cfg *cfg, const void 
                      uint32_t normal_stride_vec4, const void *projected, const void *tile_indices, const void *tile_counts,
                      const void *tile_offsets, uint32_t width, uint32_t height, void *out_rgba8, void *out_rgba32f, void *consumed_dptr,
                      const uint32_t *frame_total, uint32_t *report, uint32_t report_seq, const splat_aov *aov = nullptr,
-                     const void *disc_depth = nullptr);
+                     const float *ext_z = nullptr, uint32_t ext_zstride = 0); // ext_z: the AOV depth of splat i is ext_z[i * ext_zstride]
 // The checks of a splat_aov request (aov == NULL: none) a frame makes before its first launch and the composite again:
 // a non-NULL buffer, 16-byte alignment, nearest on top, and for depth, records that carry it (has_depth).
 int aov_check(splat_ctx *ctx, const splat_composite_cfg *cfg, const splat_aov *aov, bool has_depth);

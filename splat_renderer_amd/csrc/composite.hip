@@ -1217,22 +1217,40 @@ extern "C" int splat_composite_aov(splat_ctx *ctx, const splat_composite_cfg *cf
                             tile_offsets, width, height, out_rgba8, out_rgba32f, consumed_dptr, nullptr, nullptr, 0u, aov);
 }
 
+// splat_composite_aov with the AOV depth of splat i read from depth_f32[i * depth_stride_floats], for every footprint and record
+// format splat_composite_aov takes (the caller's own z; the records need not carry one)
+extern "C" int splat_composite_aov_depth(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity,
+                                         uint32_t color_stride_vec4, const void *normals, uint32_t normal_stride_vec4,
+                                         const void *projected, const void *tile_indices, const void *tile_counts,
+                                         const void *tile_offsets, uint32_t width, uint32_t height, void *out_rgba8, void *out_rgba32f,
+                                         void *consumed_dptr, const splat_aov *aov, const void *depth_f32, uint32_t depth_stride_floats) {
+    if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
+    ARG_CHECK(ctx, depth_f32 != nullptr && depth_stride_floats >= 1 && ((uintptr_t)depth_f32 & 3) == 0);
+    if (cfg && (cfg->footprint == SPLAT_FOOTPRINT_DISC || cfg->footprint == SPLAT_FOOTPRINT_ELLIPSOID) && cfg->record_format == SPLAT_RECORDS_LIT32)
+        return ctx_fail(ctx, SPLAT_ERR_INVALID, "splat_composite_aov_depth: the oriented-disc footprint composites from SPLAT_RECORDS_PROJECTED "
+                                                "(32-byte disc records) or SPLAT_RECORDS_DISC48; lit disc records are internal to splat_render_frame");
+    return composite_launch(ctx, cfg, color_opacity, color_stride_vec4, normals, normal_stride_vec4, projected, tile_indices, tile_counts,
+                            tile_offsets, width, height, out_rgba8, out_rgba32f, consumed_dptr, nullptr, nullptr, 0u, aov,
+                            (const float *)depth_f32, depth_stride_floats);
+}
+
 static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4,
                                     const void *normals, uint32_t normal_stride_vec4, const void *projected, const void *tile_indices,
                                     const void *tile_counts, const void *tile_offsets, uint32_t width, uint32_t height, void *out_rgba8,
                                     void *out_rgba32f, void *consumed_dptr, const uint32_t *frame_total, uint32_t *report,
-                                    uint32_t report_seq, const splat_aov *aov, const void *disc_depth, bool *launched);
+                                    uint32_t report_seq, const splat_aov *aov, const float *ext_z, uint32_t ext_zstride, bool *launched);
 
 // The composite with the frame's report attached.  Whatever happens to the launch, a report that was promised is sent
 // (the host waits for it at its next call).
 int composite_launch(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4, const void *normals,
                      uint32_t normal_stride_vec4, const void *projected, const void *tile_indices, const void *tile_counts,
                      const void *tile_offsets, uint32_t width, uint32_t height, void *out_rgba8, void *out_rgba32f, void *consumed_dptr,
-                     const uint32_t *frame_total, uint32_t *report, uint32_t report_seq, const splat_aov *aov, const void *disc_depth) {
+                     const uint32_t *frame_total, uint32_t *report, uint32_t report_seq, const splat_aov *aov, const float *ext_z,
+                     uint32_t ext_zstride) {
     bool launched = false;
     const int rc = composite_launch_checked(ctx, cfg, color_opacity, color_stride_vec4, normals, normal_stride_vec4, projected, tile_indices,
                                             tile_counts, tile_offsets, width, height, out_rgba8, out_rgba32f, consumed_dptr, frame_total, report,
-                                            report_seq, aov, disc_depth, &launched);
+                                            report_seq, aov, ext_z, ext_zstride, &launched);
     if (ctx && report && !launched) { // an empty band of tile rows, or a rejected argument: the report goes out on its own
         hipLaunchKernelGGL(k_frame_report, dim3(1), dim3(1), 0, ctx->stream, frame_total, report, report_seq);
         (void)hipGetLastError();
@@ -1244,7 +1262,7 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
                                     const void *normals, uint32_t normal_stride_vec4, const void *projected, const void *tile_indices,
                                     const void *tile_counts, const void *tile_offsets, uint32_t width, uint32_t height, void *out_rgba8,
                                     void *out_rgba32f, void *consumed_dptr, const uint32_t *frame_total, uint32_t *report,
-                                    uint32_t report_seq, const splat_aov *aov, const void *disc_depth, bool *launched) {
+                                    uint32_t report_seq, const splat_aov *aov, const float *ext_z, uint32_t ext_zstride, bool *launched) {
     if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
     ARG_CHECK(ctx, cfg != nullptr);
     // 16x16 tiles: k_composite_px / k_composite, whose quadrant mapping is built for them; any other size the binner
@@ -1271,14 +1289,18 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
     ARG_CHECK(ctx, cfg->footprint == SPLAT_FOOTPRINT_ISOTROPIC ||
                        (cfg->mode == SPLAT_COMPOSITE_FRONT_TO_BACK && cfg->record_format != SPLAT_RECORDS_COMPACT));
     ARG_CHECK(ctx, cfg->record_format != SPLAT_RECORDS_DISC48 || cfg->footprint == SPLAT_FOOTPRINT_DISC);
-    ARG_CHECK(ctx, (((uintptr_t)disc_depth) & 15) == 0);
+    ARG_CHECK(ctx, !ext_z || (ext_zstride >= 1 && ((uintptr_t)ext_z & 3) == 0));
     // where the auxiliary outputs' depth comes from: float `off` of every record, `stride` floats apart — the ProjectedSplat's
     // depth (SplatProjector.ts:77), which the compact, lit and 48-byte disc records carry as well; the projector's 32-byte
-    // disc records carry none (a frame hands its ProjectedSplat records in as disc_depth when it writes them)
+    // disc records carry none (a frame hands its ProjectedSplat records' depth words in as ext_z when it writes them).  A
+    // caller's ext_z (splat_composite_aov_depth, a frame's ProjectedSplat depths) is read in place of the records' own.
     const bool is_disc = cfg->footprint != SPLAT_FOOTPRINT_ISOTROPIC;
     const float *zsrc = nullptr;
     uint32_t zoff = 0, zstride = 0;
-    if (!is_disc) {
+    if (ext_z) {
+        zsrc = ext_z;
+        zstride = ext_zstride;
+    } else if (!is_disc) {
         zsrc = (const float *)projected;
         zoff = cfg->record_format == SPLAT_RECORDS_PROJECTED ? 4u : 3u;
         zstride = cfg->record_format == SPLAT_RECORDS_COMPACT ? 4u : 8u;
@@ -1286,10 +1308,6 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
         zsrc = (const float *)projected; // {disc record, depth, -, -, -} / {disc record, lit r, g, b, depth}
         zoff = cfg->record_format == SPLAT_RECORDS_DISC48 ? 8u : 11u;
         zstride = 12u;
-    } else if (disc_depth) {
-        zsrc = (const float *)disc_depth;
-        zoff = 4u;
-        zstride = 8u;
     }
     if (aov) {
         const int arc = aov_check(ctx, cfg, aov, zsrc != nullptr);

@@ -827,7 +827,7 @@ static int render_frame_impl(splat_ctx *ctx, splat_sorter *sorter, splat_binner 
     binner->report_for_composite = nullptr;
     return composite_launch(ctx, cfg, color, color_stride, normals, 1, records, indices, counts, offsets, width, height, out_rgba8,
                             out_rgba32f, (ctx->timing && (ctx->timing_mask & SPLAT_TIMING_COUNT_ENTRIES)) ? (void *)ctx->d_consumed : nullptr, binner->d_total,
-                            report, binner->report_seq, aov, (disc && !disc_lit) ? projected : nullptr);
+                            report, binner->report_seq, aov, (disc && !disc_lit && projected) ? (const float *)projected + 4 : nullptr, 8u);
 }
 
 extern "C" {

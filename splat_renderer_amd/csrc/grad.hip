@@ -12,9 +12,14 @@
 //   lane of the wave is inside the entry); the four waves' sums meet in LDS, and after the chunk one float atomic add per
 //   (entry, number) goes to grad_records (8 floats per splat: c.x, c.y, B00, B01, -, B11, -, -) and grad_color_opacity
 //   (4 per splat: r, g, b, opacity).  The sums depend on the atomics' arrival order: reproducible to rounding only.
+//   <DEPTH = true> (splat_composite_backward_depth) also differentiates the AOV depth D = sum w z / sum w: walk 1 sums
+//   ws = sum w and zw = sum w z beside T, walk 2 carries D as a fifth channel of colour z_i - D, background 0 and upstream
+//   G_D / ws, and each entry sums a tenth number, w_i G_D / ws, into grad_depth (1 float per splat).  z_i is staged in the
+//   entry's unused c.y.
 // k_project_ellipsoid_backward   one thread per splat: the record's gradient through B = U / 3, U(a, b, c), Sigma2 = T T^T + 0.3 I,
 //   T = J M, M = R S, the quaternion's normalisation and J's and the centre's dependence on the position, in float64.  The
-//   cull decisions are ellipsoid_record's own (binary32); a culled splat gets exact zeros.
+//   cull decisions are ellipsoid_record's own (binary32); a culled splat gets exact zeros.  <DEPTH = true> adds the ProjectedSplat
+//   depth's term, dL/dz (p - eye) / |p - eye|, to dL/dposition.
 // k_sh_colors_backward   one thread per splat: sh.hip's basis and constants, dir = normalize(p - eye), zero where the
 //   forward's max(., 0) clamped.
 #include "common.h"
@@ -25,14 +30,14 @@ namespace {
 
 constexpr int GT = 16;          // tile edge
 constexpr int GCH = 64;         // list entries per staged chunk
-constexpr int GNV = 9;          // numbers summed per entry: c.x, c.y, B00, B01, B11, r, g, b, opacity
+constexpr int GNV = 9;          // numbers summed per entry: c.x, c.y, B00, B01, B11, r, g, b, opacity (DEPTH: and z)
 constexpr float G_T_STOP = 0x1.47ae4p-7f; // composite.h's T_STOP: the last transmittance that stops a pixel
 constexpr float G_EXP2_SCALE = -6.492127684000335f; // composite.h's ELLIPSOID_EXP2_SCALE: exp(-4.5 d2) = exp2(d2 * this)
 
 struct GradEntry {
     float4 a;   // c.x, c.y, B00, B01
     float4 b;   // B11, opacity, r, g
-    float4 c;   // b, -, -, -
+    float4 c;   // b, z (DEPTH; else 0), -, -
     float4 bnd; // the record's exact 3-sigma box (all zeros: covers no pixel)
 };
 
@@ -58,8 +63,16 @@ struct BackParams {
     float *grad_color;
 };
 
+// the depth variant's further arguments: z_i = z[i * z_stride], dL/dD per pixel (W*H), dL/dz_i added into grad_depth[i]
+struct BackDepthParams : BackParams {
+    const float *z; uint32_t z_stride;
+    const float *grad_depth_img;
+    float *grad_depth;
+};
+
 // stages entries [c0, c0 + m) of the tile's list (threads 0 .. m-1)
-__device__ __forceinline__ void stage_chunk(const BackParams &p, uint32_t off, uint32_t c0, uint32_t m, GradEntry *s_ent, uint32_t *s_idx) {
+template <bool DEPTH, typename P>
+__device__ __forceinline__ void stage_chunk(const P &p, uint32_t off, uint32_t c0, uint32_t m, GradEntry *s_ent, uint32_t *s_idx) {
     const uint32_t t = threadIdx.x;
     if (t < m) {
         const uint32_t idx = p.indices[off + c0 + t];
@@ -70,7 +83,8 @@ __device__ __forceinline__ void stage_chunk(const BackParams &p, uint32_t off, u
         GradEntry e;
         e.a = rec.a;
         e.b = make_float4(rec.b.y, col.w, col.x, col.y);
-        e.c = make_float4(col.z, 0.0f, 0.0f, 0.0f);
+        if constexpr (DEPTH) e.c = make_float4(col.z, p.z[(size_t)idx * p.z_stride], 0.0f, 0.0f);
+        else e.c = make_float4(col.z, 0.0f, 0.0f, 0.0f);
         e.bnd = ok ? bnd : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         s_ent[t] = e;
         s_idx[t] = idx;
@@ -95,10 +109,12 @@ __device__ __forceinline__ bool entry_alpha(const GradEntry &e, float pxf, float
 
 } // namespace
 
-__global__ __launch_bounds__(256) void k_composite_backward(BackParams p) {
+template <bool DEPTH>
+__global__ __launch_bounds__(256) void k_composite_backward(std::conditional_t<DEPTH, BackDepthParams, BackParams> p) {
+    constexpr int NV = DEPTH ? GNV + 1 : GNV; // (the tenth: dL/dz)
     __shared__ GradEntry s_ent[GCH];
     __shared__ uint32_t s_idx[GCH];
-    __shared__ float s_part[4][GCH][GNV];
+    __shared__ float s_part[4][GCH][NV];
     __shared__ uint32_t s_touch[GCH];
     __shared__ uint32_t s_maxL;
 
@@ -114,11 +130,12 @@ __global__ __launch_bounds__(256) void k_composite_backward(BackParams p) {
     bool live = pixel_ok;
     uint32_t L = 0;
     float T = 1.0f, T_last = 1.0f; // T_L, T_{L-1}
+    float zw = 0.0f, ws = 0.0f;    // (DEPTH) sum w z, sum w over the consumed entries, as AovPixel sums them
     if (tid == 0) s_maxL = 0;
     for (uint32_t c0 = 0; c0 < count; c0 += GCH) {
         const uint32_t m = min((uint32_t)GCH, count - c0);
         __syncthreads();
-        stage_chunk(p, off, c0, m, s_ent, s_idx);
+        stage_chunk<DEPTH>(p, off, c0, m, s_ent, s_idx);
         __syncthreads();
         if (live) {
             for (uint32_t j = 0; j < m; ++j) {
@@ -126,6 +143,10 @@ __global__ __launch_bounds__(256) void k_composite_backward(BackParams p) {
                 const bool in = entry_alpha(s_ent[j], pxf, pyf, alpha, ge, u, v, dx, dy);
                 const float g = in ? alpha : 0.0f;
                 const float wgt = T * g;
+                if constexpr (DEPTH) {
+                    zw += s_ent[j].c.y * wgt;
+                    ws += wgt;
+                }
                 T_last = T;
                 T -= wgt;
                 if (T <= G_T_STOP) {
@@ -141,7 +162,15 @@ __global__ __launch_bounds__(256) void k_composite_backward(BackParams p) {
     if (L) atomicMax(&s_maxL, L);
 
     const float4 G = pixel_ok ? p.grad_img[(size_t)py * p.width + px] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    float S = (G.x * 0.05f + G.y * 0.05f) + G.z * 0.1f; // G . bg (the background's alpha channel is 0)
+    float S = (G.x * 0.05f + G.y * 0.05f) + G.z * 0.1f; // G . bg (the background's alpha and depth channels are 0)
+    // (DEPTH) D and G_D / ws; no gradient, and G_D not read, where nothing contributed
+    float D = 0.0f, GDn = 0.0f;
+    if constexpr (DEPTH) {
+        if (pixel_ok && ws > 0.0f) {
+            D = zw / ws;
+            GDn = p.grad_depth_img[(size_t)py * p.width + px] / ws;
+        }
+    }
     float Tn = T;                                          // T_{i+1} on the way back
     __syncthreads();
     const uint32_t maxL = s_maxL;
@@ -150,7 +179,7 @@ __global__ __launch_bounds__(256) void k_composite_backward(BackParams p) {
     for (uint32_t cend = maxL; cend > 0;) {
         const uint32_t c0 = cend > GCH ? cend - GCH : 0, m = cend - c0;
         __syncthreads(); // the previous chunk's sums are added
-        stage_chunk(p, off, c0, m, s_ent, s_idx);
+        stage_chunk<DEPTH>(p, off, c0, m, s_ent, s_idx);
         if (tid < GCH) s_touch[tid] = 0;
         __syncthreads();
         for (int j = (int)m - 1; j >= 0; --j) {
@@ -162,23 +191,25 @@ __global__ __launch_bounds__(256) void k_composite_backward(BackParams p) {
             if (hit == 0) {
                 if (lane == 0) {
 #pragma unroll
-                    for (int k = 0; k < GNV; ++k) s_part[w][j][k] = 0.0f;
+                    for (int k = 0; k < NV; ++k) s_part[w][j][k] = 0.0f;
                 }
                 continue;
             }
-            float vals[GNV];
+            float vals[NV];
 #pragma unroll
-            for (int k = 0; k < GNV; ++k) vals[k] = 0.0f;
+            for (int k = 0; k < NV; ++k) vals[k] = 0.0f;
             if (in) {
                 const GradEntry &e = s_ent[j];
                 const float Ti = (i + 1 == L) ? T_last : Tn / (1.0f - alpha);
-                const float cg = ((G.x * e.b.z + G.y * e.b.w) + G.z * e.c.x) + G.w; // G . (c, 1)
+                float cg = ((G.x * e.b.z + G.y * e.b.w) + G.z * e.c.x) + G.w; // G . (c, 1)
+                if constexpr (DEPTH) cg += GDn * (e.c.y - D);                   // the centred depth channel
                 const float dA = Ti * (cg - S);
                 const float wgt = Ti * alpha;
                 vals[5] = wgt * G.x;
                 vals[6] = wgt * G.y;
                 vals[7] = wgt * G.z;
                 vals[8] = ge * dA;
+                if constexpr (DEPTH) vals[9] = wgt * GDn;
                 const float dd2 = -4.5f * alpha * dA;
                 const float du = 2.0f * u * dd2, dv = 2.0f * v * dd2;
                 vals[0] = -du * e.a.z;              // d2 / c.x
@@ -192,22 +223,23 @@ __global__ __launch_bounds__(256) void k_composite_backward(BackParams p) {
                 Tn = T_last;
             }
 #pragma unroll
-            for (int k = 0; k < GNV; ++k) vals[k] = wave_sum63(vals[k]);
+            for (int k = 0; k < NV; ++k) vals[k] = wave_sum63(vals[k]);
             if (lane == 63) {
 #pragma unroll
-                for (int k = 0; k < GNV; ++k) s_part[w][j][k] = vals[k];
+                for (int k = 0; k < NV; ++k) s_part[w][j][k] = vals[k];
                 s_touch[j] = 1;
             }
         }
         __syncthreads();
         // one atomic add per touched (entry, number): the nine sums of an entry are its records row (20 of 32 bytes) and
-        // its colour row (16 bytes)
-        for (uint32_t q = tid; q < m * GNV; q += 256) {
-            const uint32_t e = q / GNV, k = q - e * GNV;
+        // its colour row (16 bytes), the depth variant's tenth its grad_depth word
+        for (uint32_t q = tid; q < m * NV; q += 256) {
+            const uint32_t e = q / NV, k = q - e * NV;
             if (!s_touch[e]) continue;
             const float sum = (s_part[0][e][k] + s_part[1][e][k]) + (s_part[2][e][k] + s_part[3][e][k]);
             const size_t idx = s_idx[e];
             float *dst = k < 5 ? p.grad_records + idx * 8 + (k < 4 ? k : 5u) : p.grad_color + idx * 4 + (k - 5);
+            if constexpr (DEPTH) dst = k == GNV ? p.grad_depth + idx : dst;
             atomicAdd(dst, sum);
         }
         cend = c0;
@@ -222,10 +254,13 @@ struct GradUniforms {
     float w, h;
 };
 
+// (DEPTH: gdep[i] = dL/dz_i of the ProjectedSplat depth z = |p - eye|; not read otherwise)
+template <bool DEPTH>
 __global__ __launch_bounds__(256) void k_project_ellipsoid_backward(GradUniforms U, const float4 *__restrict__ pos, uint32_t ps,
                                                                     const float4 *__restrict__ scl, uint32_t ss, const float4 *__restrict__ rot,
                                                                     uint32_t rs, uint32_t n, const float4 *__restrict__ grec,
-                                                                    float4 *__restrict__ gpos, float4 *__restrict__ gscl, float4 *__restrict__ grot) {
+                                                                    float4 *__restrict__ gpos, float4 *__restrict__ gscl, float4 *__restrict__ grot,
+                                                                    const float *__restrict__ gdep) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     const float4 pf = pos[(size_t)i * ps], sf = scl[(size_t)i * ss], qf = rot[(size_t)i * rs];
@@ -318,6 +353,13 @@ __global__ __launch_bounds__(256) void k_project_ellipsoid_backward(GradUniforms
     const double gcw = -(gax * ax + gay * ay) / cw - (gnx * nx + gny * ny) / cw;
     double gp[3];
     for (int k = 0; k < 3; ++k) gp[k] = gcx * m[4 * k] + gcy * m[4 * k + 1] + gcw * m[4 * k + 3];
+    if constexpr (DEPTH) {
+        // z = |p - eye|: dz/dp = (p - eye) / z.  (gz = 0 leaves gp as it is, bit for bit: no -0 + 0)
+        const double gz = gdep[i];
+        const double d[3] = {p[0] - (double)U.eye[0], p[1] - (double)U.eye[1], p[2] - (double)U.eye[2]};
+        const double z = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+        for (int k = 0; k < 3; ++k) gp[k] = gz != 0.0 ? gp[k] + gz * (d[k] / z) : gp[k];
+    }
     gpos[i] = make_float4((float)gp[0], (float)gp[1], (float)gp[2], 0.0f);
 }
 
@@ -402,10 +444,13 @@ __global__ __launch_bounds__(256) void k_sh_colors_backward(float ex, float ey, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-extern "C" int splat_composite_backward(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4,
-                                        const void *records, const void *tile_indices, const void *tile_counts, const void *tile_offsets,
-                                        uint32_t width, uint32_t height, const void *grad_rgba32f, uint32_t n, void *grad_records,
-                                        void *grad_color_opacity) {
+// The checks both composite backwards make, and the colour-only kernel's parameters (rc != SPLAT_OK: refused; ntx == 0: nothing
+// to launch)
+static int composite_backward_setup(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4,
+                                    const void *records, const void *tile_indices, const void *tile_counts, const void *tile_offsets,
+                                    uint32_t width, uint32_t height, const void *grad_rgba32f, uint32_t n, void *grad_records,
+                                    void *grad_color_opacity, BackParams &p, uint32_t &nty) {
+    p.ntx = 0;
     if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
     ARG_CHECK(ctx, cfg != nullptr);
     if (cfg->footprint != SPLAT_FOOTPRINT_ELLIPSOID || cfg->mode != SPLAT_COMPOSITE_FRONT_TO_BACK || cfg->early_out != 1 ||
@@ -413,7 +458,8 @@ extern "C" int splat_composite_backward(splat_ctx *ctx, const splat_composite_cf
         return ctx_fail(ctx, SPLAT_ERR_INVALID, "splat_composite_backward: footprint ELLIPSOID, FRONT_TO_BACK, early_out = 1, tile_size = 16 "
                                                 "and PROJECTED records only");
     ARG_CHECK(ctx, width >= 1 && height >= 1 && width <= 65535u * GT && height <= 65535u * GT);
-    const uint32_t ntx = div_up(width, GT), nty = div_up(height, GT);
+    const uint32_t ntx = div_up(width, GT);
+    nty = div_up(height, GT);
     ARG_CHECK(ctx, cfg->tile_row0 == 0 && cfg->tile_row1 >= nty); // the whole screen: no strict band
     ARG_CHECK(ctx, color_stride_vec4 >= 1);
     ARG_CHECK(ctx, color_opacity && records && tile_indices && tile_counts && tile_offsets && grad_rgba32f);
@@ -422,7 +468,6 @@ extern "C" int splat_composite_backward(splat_ctx *ctx, const splat_composite_cf
                      (uintptr_t)grad_color_opacity) & 15) == 0);
     ARG_CHECK(ctx, (((uintptr_t)tile_indices | (uintptr_t)tile_counts | (uintptr_t)tile_offsets) & 3) == 0);
     if (n == 0) return SPLAT_OK; // (no splat: every list is empty)
-    BackParams p;
     p.color = (const float4 *)color_opacity;
     p.color_stride = color_stride_vec4;
     p.records = (const float4 *)records;
@@ -435,8 +480,42 @@ extern "C" int splat_composite_backward(splat_ctx *ctx, const splat_composite_cf
     p.grad_img = (const float4 *)grad_rgba32f;
     p.grad_records = (float *)grad_records;
     p.grad_color = (float *)grad_color_opacity;
-    hipLaunchKernelGGL(k_composite_backward, dim3(ntx, nty), dim3(256), 0, ctx->stream, p);
+    return SPLAT_OK;
+}
+
+extern "C" int splat_composite_backward(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4,
+                                        const void *records, const void *tile_indices, const void *tile_counts, const void *tile_offsets,
+                                        uint32_t width, uint32_t height, const void *grad_rgba32f, uint32_t n, void *grad_records,
+                                        void *grad_color_opacity) {
+    BackParams p;
+    uint32_t nty = 0;
+    const int rc = composite_backward_setup(ctx, cfg, color_opacity, color_stride_vec4, records, tile_indices, tile_counts, tile_offsets, width,
+                                            height, grad_rgba32f, n, grad_records, grad_color_opacity, p, nty);
+    if (rc != SPLAT_OK || p.ntx == 0) return rc;
+    hipLaunchKernelGGL(k_composite_backward<false>, dim3(p.ntx, nty), dim3(256), 0, ctx->stream, p);
     LAUNCH_CHECK(ctx, "k_composite_backward");
+    return SPLAT_OK;
+}
+
+extern "C" int splat_composite_backward_depth(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity,
+                                              uint32_t color_stride_vec4, const void *records, const void *tile_indices, const void *tile_counts,
+                                              const void *tile_offsets, uint32_t width, uint32_t height, const void *grad_rgba32f, uint32_t n,
+                                              void *grad_records, void *grad_color_opacity, const void *depth_f32, uint32_t depth_stride_floats,
+                                              const void *grad_depth_f32, void *grad_depth) {
+    BackDepthParams p;
+    uint32_t nty = 0;
+    const int rc = composite_backward_setup(ctx, cfg, color_opacity, color_stride_vec4, records, tile_indices, tile_counts, tile_offsets, width,
+                                            height, grad_rgba32f, n, grad_records, grad_color_opacity, p, nty);
+    if (rc != SPLAT_OK) return rc;
+    ARG_CHECK(ctx, depth_f32 && grad_depth_f32 && (n == 0 || grad_depth) && depth_stride_floats >= 1);
+    ARG_CHECK(ctx, (((uintptr_t)depth_f32 | (uintptr_t)grad_depth_f32 | (uintptr_t)grad_depth) & 3) == 0);
+    if (p.ntx == 0) return SPLAT_OK;
+    p.z = (const float *)depth_f32;
+    p.z_stride = depth_stride_floats;
+    p.grad_depth_img = (const float *)grad_depth_f32;
+    p.grad_depth = (float *)grad_depth;
+    hipLaunchKernelGGL(k_composite_backward<true>, dim3(p.ntx, nty), dim3(256), 0, ctx->stream, p);
+    LAUNCH_CHECK(ctx, "k_composite_backward<DEPTH>");
     return SPLAT_OK;
 }
 
@@ -451,10 +530,32 @@ extern "C" int splat_project_ellipsoid_backward(splat_ctx *ctx, const float *uni
     if (n == 0) return SPLAT_OK;
     GradUniforms u;
     for (int k = 0; k < 22; ++k) (&u.m[0])[k] = uniforms[k];
-    hipLaunchKernelGGL(k_project_ellipsoid_backward, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, u, (const float4 *)positions,
+    hipLaunchKernelGGL(k_project_ellipsoid_backward<false>, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, u, (const float4 *)positions,
                        pos_stride_vec4, (const float4 *)scales, scale_stride_vec4, (const float4 *)rotations, rot_stride_vec4, n,
-                       (const float4 *)grad_records, (float4 *)grad_positions, (float4 *)grad_scales, (float4 *)grad_rotations);
+                       (const float4 *)grad_records, (float4 *)grad_positions, (float4 *)grad_scales, (float4 *)grad_rotations,
+                       (const float *)nullptr);
     LAUNCH_CHECK(ctx, "k_project_ellipsoid_backward");
+    return SPLAT_OK;
+}
+
+extern "C" int splat_project_ellipsoid_backward_depth(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4,
+                                                      const void *scales, uint32_t scale_stride_vec4, const void *rotations,
+                                                      uint32_t rot_stride_vec4, uint32_t n, const void *grad_records, void *grad_positions,
+                                                      void *grad_scales, void *grad_rotations, const void *grad_depth) {
+    if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
+    ARG_CHECK(ctx, uniforms && (n == 0 || (positions && scales && rotations && grad_records && grad_positions && grad_scales && grad_rotations &&
+                                           grad_depth)));
+    ARG_CHECK(ctx, pos_stride_vec4 >= 1 && scale_stride_vec4 >= 1 && rot_stride_vec4 >= 1);
+    ARG_CHECK(ctx, (((uintptr_t)positions | (uintptr_t)scales | (uintptr_t)rotations | (uintptr_t)grad_records | (uintptr_t)grad_positions |
+                     (uintptr_t)grad_scales | (uintptr_t)grad_rotations) & 15) == 0 && ((uintptr_t)grad_depth & 3) == 0);
+    if (n == 0) return SPLAT_OK;
+    GradUniforms u;
+    for (int k = 0; k < 22; ++k) (&u.m[0])[k] = uniforms[k];
+    hipLaunchKernelGGL(k_project_ellipsoid_backward<true>, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, u, (const float4 *)positions,
+                       pos_stride_vec4, (const float4 *)scales, scale_stride_vec4, (const float4 *)rotations, rot_stride_vec4, n,
+                       (const float4 *)grad_records, (float4 *)grad_positions, (float4 *)grad_scales, (float4 *)grad_rotations,
+                       (const float *)grad_depth);
+    LAUNCH_CHECK(ctx, "k_project_ellipsoid_backward<DEPTH>");
     return SPLAT_OK;
 }
 

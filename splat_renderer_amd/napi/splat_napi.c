@@ -18,7 +18,7 @@
 
 #include "../../include/splat.h"
 
-#define MAX_ARGS 16
+#define MAX_ARGS 18
 
 typedef struct {
     napi_env env;
@@ -320,6 +320,15 @@ FN(composite_aov) { /* (ctx, cfg[5], color, cStride, normals, nStride, projected
     splat_aov a; const splat_aov *ap = fill_aov(&c, 14, &a);
     return check(env, x, splat_composite_aov(x, &cfg, col, cs, nrm, ns, proj, idx, cnt, off, w, h, o8, of, NULL, ap), mk_undefined(env));
 }
+FN(composite_aov_depth) { /* composite_aov's arguments, then depth (device pointer), depthStrideFloats */
+    ARGS(17); splat_ctx *x = arg_external(&c, 0); splat_composite_cfg cfg; fill_cfg(&c, 1, &cfg);
+    void *col = arg_dptr(&c, 2); uint32_t cs = (uint32_t)arg_number(&c, 3); void *nrm = arg_dptr(&c, 4); uint32_t ns = (uint32_t)arg_number(&c, 5);
+    void *proj = arg_dptr(&c, 6), *idx = arg_dptr(&c, 7), *cnt = arg_dptr(&c, 8), *off = arg_dptr(&c, 9);
+    uint32_t w = (uint32_t)arg_number(&c, 10), h = (uint32_t)arg_number(&c, 11); void *o8 = arg_dptr(&c, 12), *of = arg_dptr(&c, 13);
+    void *z = arg_dptr(&c, 15); uint32_t zs = (uint32_t)arg_number(&c, 16); BAIL;
+    splat_aov a; const splat_aov *ap = fill_aov(&c, 14, &a);
+    return check(env, x, splat_composite_aov_depth(x, &cfg, col, cs, nrm, ns, proj, idx, cnt, off, w, h, o8, of, NULL, ap, z, zs), mk_undefined(env));
+}
 FN(render_frame_aov) { /* render_frame's arguments, then [depth, alpha, ids] */
     ARGS(14); splat_ctx *x = arg_external(&c, 0); splat_sorter *s = arg_external(&c, 1); splat_binner *b = arg_external(&c, 2);
     splat_composite_cfg cfg; fill_cfg(&c, 3, &cfg); size_t ub = 0; float *u = arg_hostbuf(&c, 4, &ub);
@@ -367,6 +376,16 @@ FN(composite_backward) { /* (ctx, cfg[8], colorOpacity, cStride, records, indice
     uint32_t n = (uint32_t)arg_number(&c, 11); void *grec = arg_dptr(&c, 12), *gcol = arg_dptr(&c, 13); BAIL;
     return check(env, x, splat_composite_backward(x, &cfg, col, cs, rec, idx, cnt, off, w, h, gimg, n, grec, gcol), mk_undefined(env));
 }
+FN(composite_backward_depth) { /* composite_backward's arguments, then depth, depthStrideFloats, gradDepthImage, gradDepth */
+    ARGS(18); splat_ctx *x = arg_external(&c, 0); splat_composite_cfg cfg; fill_cfg(&c, 1, &cfg);
+    void *col = arg_dptr(&c, 2); uint32_t cs = (uint32_t)arg_number(&c, 3); void *rec = arg_dptr(&c, 4);
+    void *idx = arg_dptr(&c, 5), *cnt = arg_dptr(&c, 6), *off = arg_dptr(&c, 7);
+    uint32_t w = (uint32_t)arg_number(&c, 8), h = (uint32_t)arg_number(&c, 9); void *gimg = arg_dptr(&c, 10);
+    uint32_t n = (uint32_t)arg_number(&c, 11); void *grec = arg_dptr(&c, 12), *gcol = arg_dptr(&c, 13);
+    void *z = arg_dptr(&c, 14); uint32_t zs = (uint32_t)arg_number(&c, 15); void *gdimg = arg_dptr(&c, 16), *gz = arg_dptr(&c, 17); BAIL;
+    return check(env, x, splat_composite_backward_depth(x, &cfg, col, cs, rec, idx, cnt, off, w, h, gimg, n, grec, gcol, z, zs, gdimg, gz),
+                 mk_undefined(env));
+}
 FN(project_ellipsoid_backward) { /* (ctx, Float32Array(22), positions, posStride, scales, scaleStride, rotations, rotStride, n, gradRecords, gradPositions, gradScales, gradRotations) */
     ARGS(13); splat_ctx *x = arg_external(&c, 0); size_t ub = 0; float *u = arg_hostbuf(&c, 1, &ub);
     void *pos = arg_dptr(&c, 2); uint32_t ps = (uint32_t)arg_number(&c, 3); void *scl = arg_dptr(&c, 4); uint32_t ss = (uint32_t)arg_number(&c, 5);
@@ -374,6 +393,14 @@ FN(project_ellipsoid_backward) { /* (ctx, Float32Array(22), positions, posStride
     void *grec = arg_dptr(&c, 9), *gp = arg_dptr(&c, 10), *gs = arg_dptr(&c, 11), *gr = arg_dptr(&c, 12); BAIL;
     if (ub < 22 * sizeof(float)) { napi_throw_range_error(env, NULL, "uniform block needs 22 floats"); return NULL; }
     return check(env, x, splat_project_ellipsoid_backward(x, u, pos, ps, scl, ss, rot, rs, n, grec, gp, gs, gr), mk_undefined(env));
+}
+FN(project_ellipsoid_backward_depth) { /* project_ellipsoid_backward's arguments, then gradDepth */
+    ARGS(14); splat_ctx *x = arg_external(&c, 0); size_t ub = 0; float *u = arg_hostbuf(&c, 1, &ub);
+    void *pos = arg_dptr(&c, 2); uint32_t ps = (uint32_t)arg_number(&c, 3); void *scl = arg_dptr(&c, 4); uint32_t ss = (uint32_t)arg_number(&c, 5);
+    void *rot = arg_dptr(&c, 6); uint32_t rs = (uint32_t)arg_number(&c, 7), n = (uint32_t)arg_number(&c, 8);
+    void *grec = arg_dptr(&c, 9), *gp = arg_dptr(&c, 10), *gs = arg_dptr(&c, 11), *gr = arg_dptr(&c, 12), *gz = arg_dptr(&c, 13); BAIL;
+    if (ub < 22 * sizeof(float)) { napi_throw_range_error(env, NULL, "uniform block needs 22 floats"); return NULL; }
+    return check(env, x, splat_project_ellipsoid_backward_depth(x, u, pos, ps, scl, ss, rot, rs, n, grec, gp, gs, gr, gz), mk_undefined(env));
 }
 FN(sh_colors_backward) { /* (ctx, Float32Array(3) eye, positions, posStride, sh, shStrideFloats, degree, opacity|null, gradColorOpacity, n, gradSh, gradPositions, gradOpacity) */
     ARGS(13); splat_ctx *x = arg_external(&c, 0); size_t eb = 0; float *eye = arg_hostbuf(&c, 1, &eb);
@@ -646,6 +673,7 @@ static napi_value init(napi_env env, napi_value exports) {
         EXPORT(allgather_records), EXPORT(sdf_gradients), EXPORT(sdf_update_positions), EXPORT(sdf_scale_factors), EXPORT(sdf_curvature), EXPORT(sdf_seed_positions), EXPORT(sdf_generate),
         EXPORT(point_frame), EXPORT(project_ellipsoid), EXPORT(sh_colors), EXPORT(render_frame_ellipsoids),
         EXPORT(composite_backward), EXPORT(project_ellipsoid_backward), EXPORT(sh_colors_backward),
+        EXPORT(composite_aov_depth), EXPORT(composite_backward_depth), EXPORT(project_ellipsoid_backward_depth),
     };
     napi_define_properties(env, exports, sizeof d / sizeof d[0], d);
     return exports;
