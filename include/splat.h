@@ -470,7 +470,11 @@ int splat_render_frame_ellipsoids(splat_ctx *ctx, splat_sorter *sorter, splat_bi
  * dL/dalpha in w.  ADDS into grad_records (n x 8 f32 per splat: c.x, c.y, B00, B01, -, B11, -, -; the unused columns are not
  * touched) and grad_color_opacity (n x 4 f32: r, g, b, opacity).  cfg must say footprint ELLIPSOID, FRONT_TO_BACK, early_out =
  * 1, tile_size = 16, record_format PROJECTED and the whole screen (tile_row0 = 0, tile_row1 >= the tile rows); anything else,
- * or a buffer not 16-byte aligned, is SPLAT_ERR_INVALID.  Every screen the binner takes works. */
+ * or a buffer not 16-byte aligned, is SPLAT_ERR_INVALID.  Every screen the binner takes works.
+ * The backward follows the forward's kernel selection: it replays the transmittance updates and stop tests of the kernel
+ * splat_composite_aov picks for this ctx and screen (splat_composite_options, else SPLAT_COMPOSITE, else k_composite_px on
+ * screens of >= 2048 tiles), whose roundings differ where T lands within an ulp of the stop.  Differentiate on the ctx that
+ * drew the frame, with its options unchanged; splat_composite_backward_depth does the same. */
 int splat_composite_backward(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4,
                              const void *records, const void *tile_indices, const void *tile_counts, const void *tile_offsets,
                              uint32_t width, uint32_t height, const void *grad_rgba32f, uint32_t n, void *grad_records,

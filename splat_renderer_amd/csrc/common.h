@@ -73,6 +73,11 @@ struct splat_ctx {
 };
 
 int ctx_fail(splat_ctx *ctx, int code, const char *what, hipError_t e = hipSuccess);
+// Whether a nearest-on-top composite of a whole screen of ntx x nty 16-pixel tiles runs k_composite_px (else k_composite):
+// splat_composite_options' choice for the context, else SPLAT_COMPOSITE's, else ntx * nty >= 2048 (composite.hip).  The
+// composite backward asks the same rule, to replay the transmittance updates of the kernel that drew the frame.
+bool composite_uses_px(const splat_ctx *ctx, uint32_t ntx, uint32_t nty);
+
 int ctx_ensure_scan_ws(splat_ctx *ctx, size_t bytes);
 int ctx_ensure_pinned(splat_ctx *ctx, size_t bytes);
 int ctx_ensure_consumed(splat_ctx *ctx, uint32_t tiles); // per-tile counters for timed frames (zeroed when (re)allocated)

@@ -1103,6 +1103,17 @@ static int g_px_ahead = 0;          // SPLAT_PX_AHEAD=1 | 2: chunks the builder 
 // A context keeps PX_HISTORIES of them, found by `key` (the band, the screen, whose lists), least recently used evicted: two
 // frames in flight on one context, a band frame next to the whole frame, virtual ranks on one context each keep theirs
 // (with ONE slot they reset each other at every launch, and neither the order nor the bound ever engaged: ADVICE r4).
+bool composite_uses_px(const splat_ctx *ctx, uint32_t ntx, uint32_t nty) {
+    constexpr uint32_t PX_MIN_TILES = 2048;
+    static int s_px = -2; // SPLAT_COMPOSITE=pixel | quadrant: 1 | 0; unset: -1
+    if (s_px == -2) {
+        const char *e = getenv("SPLAT_COMPOSITE");
+        s_px = !e ? -1 : (e[0] == 'p' || e[0] == 'P') ? 1 : (e[0] == 'q' || e[0] == 'Q') ? 0 : -1;
+    }
+    const int kernel = ctx->opt_composite_kernel >= 0 ? ctx->opt_composite_kernel : s_px;
+    return kernel == 1 || (kernel == -1 && ntx * nty >= PX_MIN_TILES);
+}
+
 static int px_order_prepare(splat_ctx *ctx, uint32_t band_tiles, uint64_t key, CompositeParams &p) {
     p.tile_order = nullptr;
     p.tile_cost = nullptr;
@@ -1387,12 +1398,10 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
     // arithmetic for their bands to stitch into the single-GPU image bit for bit); below that (C0's 256 tiles: 18 against
     // 22 us) and for the oriented disc (its footprint is not separable) and the reference-
     // literal blend, round 2's k_composite (four waves per tile, each visiting every entry that touches its quadrant).
-    // SPLAT_COMPOSITE=pixel | quadrant forces one of them.
-    constexpr uint32_t PX_MIN_TILES = 2048;
-    static int s_px = -2;
-    if (s_px == -2) {
-        const char *e = getenv("SPLAT_COMPOSITE");
-        s_px = !e ? -1 : (e[0] == 'p' || e[0] == 'P') ? 1 : (e[0] == 'q' || e[0] == 'Q') ? 0 : -1;
+    // SPLAT_COMPOSITE=pixel | quadrant forces one of them (composite_uses_px: the ellipsoid backward asks the same rule).
+    static bool s_env = false;
+    if (!s_env) {
+        s_env = true;
         const char *o = getenv("SPLAT_TILE_ORDER"); // =0: workgroups take tiles row-major
         g_px_order_on = !(o && o[0] == '0');
         const char *pr = getenv("SPLAT_PX_PREDICT"); // =0: no look-ahead bound from the previous launch's costs
@@ -1400,7 +1409,6 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
         const char *ah = getenv("SPLAT_PX_AHEAD");
         g_px_ahead = !ah ? 0 : ah[0] == '1' ? 1 : 2;
     }
-    const int opt_kernel = ctx->opt_composite_kernel >= 0 ? ctx->opt_composite_kernel : s_px;
     // Two chunks ahead with lanes running ahead makes 27 % fewer trips, each four instructions longer, on five waves per
     // SIMD instead of eight (three table buffers): a gain where every list is walked to its end (early-out off: C2 319 ->
     // 298 us), a loss where most tiles stop after a few chunks and a tile's life is mostly latency (50.6 -> 52.8 us):
@@ -1408,7 +1416,7 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
     // (the oriented disc keeps eleven numbers per entry instead of tables: a third buffer costs it no resident workgroup)
     const int opt_ahead = ctx->opt_px_ahead > 0 ? ctx->opt_px_ahead : g_px_ahead > 0 ? g_px_ahead : ((cfg->early_out && !p.disc) ? 1 : 2);
     const uint32_t band_tiles = ntx * (r1 - r0);
-    const bool use_px = cfg->mode == SPLAT_COMPOSITE_FRONT_TO_BACK && (opt_kernel == 1 || (opt_kernel == -1 && ntx * nty >= PX_MIN_TILES));
+    const bool use_px = cfg->mode == SPLAT_COMPOSITE_FRONT_TO_BACK && composite_uses_px(ctx, ntx, nty);
     if (use_px) {
         // (the band, the screen, and whose lists these are: two binners on one context do not share a history)
         const uint64_t key = (((uint64_t)ntx << 40) ^ ((uint64_t)r0 << 20) ^ (uint64_t)r1 ^ ((uint64_t)width << 50) ^

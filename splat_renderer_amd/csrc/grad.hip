@@ -2,9 +2,11 @@
 // counterpart): the backward passes of the composite, of the ellipsoid projector and of the SH colour.
 //
 // k_composite_backward   one 256-thread workgroup per 16x16 tile, one pixel per lane (k_composite's pixel mapping).
-//   Walk 1, front to back over the tile's list in chunks of GCH entries staged in LDS, recomputes each pixel's forward in
-//   k_composite's operation order (this file is compiled with contraction on, as composite.hip is): L, the number of entries
-//   the pixel consumed (up to and including the one its early-out stopped at), T_{L-1} and T_L.
+//   Walk 1, front to back over the tile's list in chunks of GCH entries staged in LDS, recomputes each pixel's forward in the
+//   operation order of the kernel that drew the frame (composite_uses_px; this file is compiled with contraction on, as
+//   composite.hip is): L, the number of entries the pixel consumed (up to and including the one its early-out stopped at),
+//   T_{L-1} and T_L.  <PX = false> k_composite's T -= T (g o); <PX = true> k_composite_px's T = fma(-o, T g, T).  The two
+//   round differently, and where T lands within an ulp or two of T_STOP they stop a pixel at different entries.
 //   Walk 2 goes back to front from the tile's largest L, chunk by chunk.  Per entry i < L a pixel recovers
 //   T_i = T_{i+1} / (1 - alpha_i) (except at its last entry, whose T_{L-1} it kept: only there may 1 - alpha be <= 0.01) and
 //   forms dL/dalpha_i = T_i (G.c_i - S_i), S the blend of everything behind the entry, with alpha as a fourth channel
@@ -109,7 +111,7 @@ __device__ __forceinline__ bool entry_alpha(const GradEntry &e, float pxf, float
 
 } // namespace
 
-template <bool DEPTH>
+template <bool DEPTH, bool PX>
 __global__ __launch_bounds__(256) void k_composite_backward(std::conditional_t<DEPTH, BackDepthParams, BackParams> p) {
     constexpr int NV = DEPTH ? GNV + 1 : GNV; // (the tenth: dL/dz)
     __shared__ GradEntry s_ent[GCH];
@@ -141,14 +143,21 @@ __global__ __launch_bounds__(256) void k_composite_backward(std::conditional_t<D
             for (uint32_t j = 0; j < m; ++j) {
                 float alpha, ge, u, v, dx, dy;
                 const bool in = entry_alpha(s_ent[j], pxf, pyf, alpha, ge, u, v, dx, dy);
-                const float g = in ? alpha : 0.0f;
-                const float wgt = T * g;
+                float wgt;
+                T_last = T;
+                if constexpr (PX) { // k_composite_px: the colour premultiplied by the opacity, w = T g, T = fma(-opacity, w, T)
+                    const float w = T * (in ? ge : 0.0f);
+                    wgt = w * s_ent[j].b.y; // (its AOV's weight)
+                    T = __builtin_fmaf(-s_ent[j].b.y, w, T);
+                } else { // k_composite: alpha = g opacity, w = T alpha, T -= w
+                    const float g = in ? alpha : 0.0f;
+                    wgt = T * g;
+                    T -= wgt;
+                }
                 if constexpr (DEPTH) {
                     zw += s_ent[j].c.y * wgt;
                     ws += wgt;
                 }
-                T_last = T;
-                T -= wgt;
                 if (T <= G_T_STOP) {
                     L = c0 + j + 1;
                     live = false;
@@ -492,7 +501,8 @@ extern "C" int splat_composite_backward(splat_ctx *ctx, const splat_composite_cf
     const int rc = composite_backward_setup(ctx, cfg, color_opacity, color_stride_vec4, records, tile_indices, tile_counts, tile_offsets, width,
                                             height, grad_rgba32f, n, grad_records, grad_color_opacity, p, nty);
     if (rc != SPLAT_OK || p.ntx == 0) return rc;
-    hipLaunchKernelGGL(k_composite_backward<false>, dim3(p.ntx, nty), dim3(256), 0, ctx->stream, p);
+    if (composite_uses_px(ctx, p.ntx, nty)) hipLaunchKernelGGL((k_composite_backward<false, true>), dim3(p.ntx, nty), dim3(256), 0, ctx->stream, p);
+    else hipLaunchKernelGGL((k_composite_backward<false, false>), dim3(p.ntx, nty), dim3(256), 0, ctx->stream, p);
     LAUNCH_CHECK(ctx, "k_composite_backward");
     return SPLAT_OK;
 }
@@ -514,7 +524,8 @@ extern "C" int splat_composite_backward_depth(splat_ctx *ctx, const splat_compos
     p.z_stride = depth_stride_floats;
     p.grad_depth_img = (const float *)grad_depth_f32;
     p.grad_depth = (float *)grad_depth;
-    hipLaunchKernelGGL(k_composite_backward<true>, dim3(p.ntx, nty), dim3(256), 0, ctx->stream, p);
+    if (composite_uses_px(ctx, p.ntx, nty)) hipLaunchKernelGGL((k_composite_backward<true, true>), dim3(p.ntx, nty), dim3(256), 0, ctx->stream, p);
+    else hipLaunchKernelGGL((k_composite_backward<true, false>), dim3(p.ntx, nty), dim3(256), 0, ctx->stream, p);
     LAUNCH_CHECK(ctx, "k_composite_backward<DEPTH>");
     return SPLAT_OK;
 }

@@ -156,16 +156,20 @@ def decisions(rec, color_opacity, indices, counts, offsets, width, height, tile=
     return dict(steps=steps, alpha=alphas, rim=scatter(rim), near=scatter(near))
 
 
-def composite64(rec, col, steps, width, height):
-    """(rgb (H W, 3), alpha (H W)) float64 over the recorded pairs, differentiable in rec (n, 8) and col (n, 4)."""
-    P = width * height
-    pix_x = torch.arange(P, dtype=D) % width + 0.5
-    pix_y = torch.div(torch.arange(P), width, rounding_mode="floor").to(D) + 0.5
+def composite64(rec, col, steps, width, height, pixels=None):
+    """(rgb (H W, 3), alpha (H W)) float64 over the recorded pairs, differentiable in rec (n, 8) and col (n, 4).  pixels (sorted
+    flat pixel indices y W + x, optional): only those pixels, in that order — every pixel of `steps` must be one of them."""
+    flat = torch.arange(width * height) if pixels is None else torch.as_tensor(np.asarray(pixels, np.int64))
+    P = flat.shape[0]
+    pix_x = (flat % width).to(D) + 0.5
+    pix_y = torch.div(flat, width, rounding_mode="floor").to(D) + 0.5
     T = torch.ones(P, dtype=D)
     C = torch.zeros((P, 3), dtype=D)
     for pix, s, _stop in steps:
         if pix.size == 0:
             continue
+        if pixels is not None:
+            pix = np.searchsorted(np.asarray(pixels, np.int64), pix)
         pix_t, s_t = torch.as_tensor(pix, dtype=torch.long), torch.as_tensor(s, dtype=torch.long)
         r = rec[s_t]
         dx, dy = pix_x[pix_t] - r[:, 0], pix_y[pix_t] - r[:, 1]
@@ -187,11 +191,14 @@ def upstream(width, height, rim, near, seed):
     return g
 
 
-def composite_grads(rec32, col32, steps, width, height, g):
-    """dL/drec (n, 8) and dL/dcol (n, 4) of L = sum g . (rgb, alpha), by autograd over composite64."""
+def composite_grads(rec32, col32, steps, width, height, g, pixels=None):
+    """dL/drec (n, 8) and dL/dcol (n, 4) of L = sum g . (rgb, alpha), by autograd over composite64 (pixels: as there; g is zero
+    at every other pixel)."""
     rec = torch.tensor(np.asarray(rec32, np.float64), requires_grad=True)
     col = torch.tensor(np.asarray(col32, np.float64), requires_grad=True)
-    rgb, alpha = composite64(rec, col, steps, width, height)
+    rgb, alpha = composite64(rec, col, steps, width, height, pixels)
     gt = torch.as_tensor(np.asarray(g, np.float64).reshape(-1, 4))
+    if pixels is not None:
+        gt = gt[torch.as_tensor(np.asarray(pixels, np.int64))]
     ((rgb * gt[:, :3]).sum() + (alpha * gt[:, 3]).sum()).backward()
     return rec.grad.numpy(), col.grad.numpy()

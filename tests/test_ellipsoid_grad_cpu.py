@@ -57,6 +57,27 @@ def test_restatement_matches_binary32(seed):
     assert np.abs(alpha.numpy().reshape(h, w) - ref["alpha"]).max() <= 1e-5
 
 
+def test_composite_grads_on_a_sparse_pixel_set():
+    """composite_grads over a sparse pixel set (pixels=) equals the whole-frame one with g zero elsewhere, and steps at pixels
+    outside the set are not needed."""
+    n, w, h = 800, 64, 48
+    u, pos, scl, rot, col, rec, counts, offsets, idx = scene(n, w, h, 3)
+    dec = GR.decisions(rec, col, idx, counts, offsets, w, h)
+    rng = np.random.default_rng(3)
+    pixels = np.sort(rng.choice(w * h, 150, replace=False))
+    g = np.zeros((h, w, 4), np.float32)
+    g.reshape(-1, 4)[pixels] = rng.uniform(-1, 1, (pixels.size, 4))
+    want_rec, want_col = GR.composite_grads(rec, col, dec["steps"], w, h, g)
+    sub = []
+    for pix, s, stop in dec["steps"]:
+        m = np.isin(pix, pixels)
+        sub.append((pix[m], s[m], stop[m]))
+    got_rec, got_col = GR.composite_grads(rec, col, sub, w, h, g, pixels=pixels)
+    assert np.abs(want_col).max() > 0
+    np.testing.assert_allclose(got_rec, want_rec, rtol=1e-12, atol=1e-14)
+    np.testing.assert_allclose(got_col, want_col, rtol=1e-12, atol=1e-14)
+
+
 def test_gradcheck_composite():
     n, w, h = 60, 32, 32
     u, pos, scl, rot, col, rec, counts, offsets, idx = scene(n, w, h, 5, spread=0.3, scale=0.08, degenerate=False)
