@@ -522,6 +522,36 @@ int splat_project_ellipsoid_backward_depth(splat_ctx *ctx, const float *uniforms
 int splat_sh_colors_backward(splat_ctx *ctx, const float *eye3, const void *positions, uint32_t pos_stride_vec4, const void *sh,
                              uint32_t sh_stride_floats, uint32_t degree, const void *opacity_f32, const void *grad_color_opacity,
                              uint32_t n, void *grad_sh, void *grad_positions, void *grad_opacity);
+/* Gradients of the camera.  A frame reads its 22-float uniform block {VP (16, column-major, m[4 k + r]), eye (3), time, W, H}
+ * in three places: the records {c.x, c.y, B00, B01, B11} read rows 0, 1 and 3 of VP (through c = VP [p; 1] and the Jacobian J of
+ * the screen position; row 2 is not read), the ProjectedSplat depth z = |p - eye| reads the eye (dz/deye = -(p - eye) / z), and
+ * the SH direction normalize(p - eye) reads the eye (dL/deye = -sum_i dL/dp_i of the SH term).  time is not read; W and H are
+ * the screen's integers, not parameters: no gradient is offered for them.  Sort keys and tile lists are decisions, not
+ * differentiated; the cull, the cut and the stop are held fixed as above.
+ * Unlike the per-splat sums above, these sums over all splats are bit-reproducible from run to run: each splat's numbers are
+ * formed in float64 and summed in float64 in a fixed order (the 64 lanes of a wave; one partial per wave in a scratch buffer of
+ * the ctx; then one summing kernel for up to 1024 partials, two above that: 64 contiguous slices of the partials, each added in
+ * index order, then the slices in order) and rounded once to float32.  Which kernels run, and so the order, depends on n only.
+ * Each is ONE sum over every splat the projector did not cull: a single splat whose own gradient is huge (an ill-conditioned
+ * footprint, Sigma2 of condition number beyond 1e4, say) or a single non-finite upstream value reaches the whole camera
+ * gradient, where it would spoil only its own row of the per-splat outputs.  A caller refining a pose masks such splats'
+ * upstream (or makes them transparent) first.
+ *
+ * splat_project_ellipsoid_backward_camera: splat_project_ellipsoid_backward's arguments, checks and per-splat outputs
+ * (grad_positions / grad_scales / grad_rotations bit for bit those of splat_project_ellipsoid_backward when grad_depth is NULL,
+ * else of splat_project_ellipsoid_backward_depth), then grad_depth (n floats, 4-byte aligned, or NULL) and grad_uniforms: a
+ * DEVICE pointer to 22 floats, 16-byte aligned, OVERWRITTEN (for n = 0 too: all zeros), laid out as the uniform block:
+ * dL/dVP in [0, 16) (entries 2, 6, 10, 14, row 2, are exact zeros), dL/deye of the depth term in [16, 19) (zeros when grad_depth
+ * is NULL), zeros in [19, 22).  A culled splat contributes exact zeros.  NULL or misaligned grad_uniforms: SPLAT_ERR_INVALID. */
+int splat_project_ellipsoid_backward_camera(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4,
+                                            const void *scales, uint32_t scale_stride_vec4, const void *rotations, uint32_t rot_stride_vec4,
+                                            uint32_t n, const void *grad_records, void *grad_positions, void *grad_scales,
+                                            void *grad_rotations, const void *grad_depth, void *grad_uniforms);
+/* splat_sh_colors_backward's arguments, checks and outputs (bit for bit), then grad_eye: a DEVICE pointer to 4 floats, 16-byte
+ * aligned, OVERWRITTEN (for n = 0 too) with dL/deye in xyz and 0 in w: minus the float64 sum of the splats' grad_positions. */
+int splat_sh_colors_backward_camera(splat_ctx *ctx, const float *eye3, const void *positions, uint32_t pos_stride_vec4, const void *sh,
+                                    uint32_t sh_stride_floats, uint32_t degree, const void *opacity_f32, const void *grad_color_opacity,
+                                    uint32_t n, void *grad_sh, void *grad_positions, void *grad_opacity, void *grad_eye);
 
 /* ---- multi-GPU band path (no reference equivalent — the reference is single-device) */
 /* The oriented-disc projector (src/SequentialRenderer.ts:68-71,91-112): the splat is the disc

@@ -27,6 +27,20 @@ sort -> splat_bin_run -> splat_composite_aov), so rasterize's image is Renderer(
 backward is splat_composite_backward, splat_project_ellipsoid_backward and splat_sh_colors_backward, whose contract (the cut
 and the early-out stop held fixed; float atomic sums, reproducible to rounding) is stated in include/splat.h.
 
+The camera is differentiable too.  `uniforms` may be a torch tensor (CUDA or CPU, float32 or float64, 22 floats, or 20 with
+width= and height=) that requires grad: it is then an input of the projection and, through its [16:19] slice, of sh_colors,
+and backward() fills its .grad — dL/dVP in [0:16] (row 2, entries 2, 6, 10, 14, is not read by this footprint: exact zeros),
+dL/deye in [16:19] (through the depths and the SH direction), zeros in [19:22] (time is not read; W and H are the screen's
+integers, not parameters: no gradient is offered).  The sums over the splats are made by splat_project_ellipsoid_backward_camera
+and splat_sh_colors_backward_camera in float64 and in a fixed order: unlike the per-splat gradients they are bit-reproducible
+for the same upstream.  Each is one sum over every unculled splat: one ill-conditioned splat (Sigma2 of condition number
+beyond 1e4, say) or one NaN in the upstream reaches the whole camera gradient, not one splat's row; mask such splats (zero
+their opacity or their upstream) when refining a pose.  The forward still reads a host copy of the block (the C ABI takes host uniforms): one 88-byte
+device-to-host copy per frame when the tensor lives on the GPU.  A Camera, a NumPy array or a tensor that does not require
+grad takes the code path, the kernels and the results described above, unchanged.  A 4 x 4 VP is not what anyone optimises:
+pinhole_uniforms(R, t, fx, fy, cx, cy, width, height) builds the block from a pose and intrinsics in plain torch ops, so that
+gradients reach whatever parametrises R and t (axis-angle, quaternion: the caller's choice).
+
 `rec` is a real intermediate: rec.retain_grad() gives the screen-space gradient rec.grad[:, :2] that 3DGS densification reads.
 
 The background is the composite's fixed bg = (0.05, 0.05, 0.1).  A caller that wants background b uses
@@ -176,6 +190,23 @@ def _uniforms(camera_or_uniforms, width, height):
     return np.ascontiguousarray(u, np.float32)
 
 
+def _grad_uniforms(u, name="uniforms", sizes=(20, 22)):
+    """`u` itself when it is a torch tensor that requires grad (checked: float32 / float64, 20 or 22 floats), else None."""
+    if not getattr(u, "requires_grad", False):  # (a Camera, a NumPy array, a tensor that does not: the constant-camera path)
+        return None
+    torch = _t()
+    if u.dtype not in (torch.float32, torch.float64):
+        raise SplatError(-1, f"{name} that requires grad must be float32 or float64, not {u.dtype}")
+    if u.numel() not in sizes:
+        raise SplatError(-1, f"{name} that requires grad must hold {' or '.join(map(str, sizes))} floats, not {u.numel()}")
+    return u
+
+
+def _like(g, t):
+    """The first t.numel() floats of the float32 device vector g, as a gradient for t (its shape, dtype and device)."""
+    return g[:t.numel()].to(device=t.device, dtype=t.dtype).reshape(t.shape)
+
+
 def _fptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
@@ -198,7 +229,8 @@ def _functions():
 
     class Project(torch.autograd.Function):
         @staticmethod
-        def forward(fctx, u, means4, scales4, rots, with_depth=False):
+        def forward(fctx, u, means4, scales4, rots, with_depth=False, u_t=None):
+            # (u_t: the uniforms as the tensor that requires grad, or None; the kernels read the host copy u)
             cx = _context(means4)
             n = means4.shape[0]
             padded = cx.ensure_sorter(n)
@@ -210,7 +242,7 @@ def _functions():
                 check(cx.lib.splat_project_ellipsoid(cx.ctx, _fptr(u), means4.data_ptr(), 1, scales4.data_ptr(), 1, rots.data_ptr(), 1, n,
                                                      proj.data_ptr(), rec.data_ptr(), keys.data_ptr(), pay.data_ptr(), padded), cx.ctx)
             fctx.save_for_backward(means4, scales4, rots)
-            fctx.u = u
+            fctx.u, fctx.u_t = u, u_t
             aux = ProjectedSplats(cx, u, n, proj, keys, pay)
             if with_depth:  # (the ProjectedSplat depth, as a tensor of its own: bit for bit aux.projected[:, 4])
                 fctx.set_materialize_grads(False)  # (an unused depth: None, and the colour-only kernel)
@@ -225,6 +257,13 @@ def _functions():
             cx = _context(means4)
             g = _cuda_f32(grad_rec, "grad_records", 8) if grad_rec is not None else torch.zeros((n, 8), device=means4.device, dtype=torch.float32)
             gp, gs, gr = (torch.empty((n, 4), device=means4.device, dtype=torch.float32) for _ in range(3))
+            if len(fctx.needs_input_grad) > 5 and fctx.needs_input_grad[5]:
+                gz = _cuda_f32(grad_depth.reshape(-1), "grad_depths") if grad_depth is not None else None
+                gu = torch.empty(24, device=means4.device, dtype=torch.float32)  # (22, and a 16-byte multiple)
+                check(cx.lib.splat_project_ellipsoid_backward_camera(cx.ctx, _fptr(fctx.u), means4.data_ptr(), 1, scales4.data_ptr(), 1,
+                                                                     rots.data_ptr(), 1, n, g.data_ptr(), gp.data_ptr(), gs.data_ptr(), gr.data_ptr(),
+                                                                     gz.data_ptr() if gz is not None and n else None, gu.data_ptr()), cx.ctx)
+                return None, gp, gs, gr, None, _like(gu, fctx.u_t)
             if n and grad_depth is None:
                 check(cx.lib.splat_project_ellipsoid_backward(cx.ctx, _fptr(fctx.u), means4.data_ptr(), 1, scales4.data_ptr(), 1, rots.data_ptr(), 1,
                                                               n, g.data_ptr(), gp.data_ptr(), gs.data_ptr(), gr.data_ptr()), cx.ctx)
@@ -233,11 +272,12 @@ def _functions():
                 check(cx.lib.splat_project_ellipsoid_backward_depth(cx.ctx, _fptr(fctx.u), means4.data_ptr(), 1, scales4.data_ptr(), 1, rots.data_ptr(),
                                                                     1, n, g.data_ptr(), gp.data_ptr(), gs.data_ptr(), gr.data_ptr(), gz.data_ptr()),
                       cx.ctx)
-            return None, gp, gs, gr, None
+            return None, gp, gs, gr, None, None
 
     class ShColors(torch.autograd.Function):
         @staticmethod
-        def forward(fctx, eye, means4, sh, degree, opacities):
+        def forward(fctx, eye, means4, sh, degree, opacities, eye_t=None):
+            # (eye_t: the eye as the tensor that requires grad, or None; the kernels read the host copy eye)
             cx = _context(means4)
             n = means4.shape[0]
             out = torch.empty((n, 4), device=means4.device, dtype=torch.float32)
@@ -245,7 +285,7 @@ def _functions():
                 check(cx.lib.splat_sh_colors(cx.ctx, _fptr(eye), means4.data_ptr(), 1, sh.data_ptr(), sh.shape[1], degree, opacities.data_ptr(), n,
                                              out.data_ptr()), cx.ctx)
             fctx.save_for_backward(means4, sh, opacities)
-            fctx.eye, fctx.degree = eye, degree
+            fctx.eye, fctx.degree, fctx.eye_t = eye, degree, eye_t
             return out
 
         @staticmethod
@@ -257,10 +297,16 @@ def _functions():
             gsh = torch.zeros_like(sh)
             gp = torch.empty((n, 4), device=means4.device, dtype=torch.float32)
             gop = torch.empty(n, device=means4.device, dtype=torch.float32)
+            if len(fctx.needs_input_grad) > 5 and fctx.needs_input_grad[5]:
+                ge = torch.empty(4, device=means4.device, dtype=torch.float32)
+                check(cx.lib.splat_sh_colors_backward_camera(cx.ctx, _fptr(fctx.eye), means4.data_ptr(), 1, sh.data_ptr(), sh.shape[1], fctx.degree,
+                                                             opacities.data_ptr(), g.data_ptr(), n, gsh.data_ptr(), gp.data_ptr(), gop.data_ptr(),
+                                                             ge.data_ptr()), cx.ctx)
+                return None, gp, gsh, None, gop, _like(ge, fctx.eye_t)
             if n:
                 check(cx.lib.splat_sh_colors_backward(cx.ctx, _fptr(fctx.eye), means4.data_ptr(), 1, sh.data_ptr(), sh.shape[1], fctx.degree,
                                                       opacities.data_ptr(), g.data_ptr(), n, gsh.data_ptr(), gp.data_ptr(), gop.data_ptr()), cx.ctx)
-            return None, gp, gsh, None, gop
+            return None, gp, gsh, None, gop, None
 
     class Rasterize(torch.autograd.Function):
         @staticmethod
@@ -328,18 +374,24 @@ def _functions():
 def project_ellipsoids(uniforms, means, scales, rotations, width=None, height=None, return_depth=False):
     """(rec (n, 8) differentiable records {c.x, c.y, B00, B01, 0, B11, 0, 0}, aux: ProjectedSplats).  uniforms: a Camera (then
     width and height are required) or the 22-float block.  return_depth=True: (rec, depths, aux), depths (n,) the
-    differentiable ProjectedSplat depth |mean - eye| (aux.projected[:, 4] bit for bit; rasterize's `depths`)."""
+    differentiable ProjectedSplat depth |mean - eye| (aux.projected[:, 4] bit for bit; rasterize's `depths`).  A uniforms
+    tensor that requires grad receives its gradient (the module's docstring)."""
     u = _uniforms(uniforms, width, height)
+    u_t = _grad_uniforms(uniforms)
     means4 = _cuda_f32(_vec4(means, "means", 1.0), "means", 4)
     scales4 = _cuda_f32(_vec4(scales, "scales"), "scales", 4)
     rots = _cuda_f32(rotations, "rotations", 4)
     if not (means4.shape[0] == scales4.shape[0] == rots.shape[0]):
         raise SplatError(-1, "means, scales and rotations must hold the same number of splats")
+    if u_t is not None:
+        return _functions()[0].apply(u, means4, scales4, rots, bool(return_depth), u_t)
     return _functions()[0].apply(u, means4, scales4, rots, bool(return_depth))
 
 
 def sh_colors(eye, means, sh, degree, opacities):
-    """(n, 4): rgb = max(0.5 + sum_k Y_k(normalize(p - eye)) sh_k, 0) and the opacity; sh (n, (degree + 1)^2, 3) or (n, 3K)."""
+    """(n, 4): rgb = max(0.5 + sum_k Y_k(normalize(p - eye)) sh_k, 0) and the opacity; sh (n, (degree + 1)^2, 3) or (n, 3K).
+    An eye tensor (3 floats, float32 / float64, any device) that requires grad receives its gradient."""
+    e_t = _grad_uniforms(eye, "eye", (3,))
     e = np.ascontiguousarray(np.asarray(eye.detach().cpu() if hasattr(eye, "detach") else eye, np.float32).reshape(-1)[:3])
     means4 = _cuda_f32(_vec4(means, "means", 1.0), "means", 4)
     n = means4.shape[0]
@@ -352,6 +404,8 @@ def sh_colors(eye, means, sh, degree, opacities):
     op = _cuda_f32(opacities.reshape(-1), "opacities")
     if op.shape[0] != n:
         raise SplatError(-1, "opacities must hold one value per splat")
+    if e_t is not None:
+        return _functions()[1].apply(e, means4, sh2, int(degree), op, e_t)
     return _functions()[1].apply(e, means4, sh2, int(degree), op)
 
 
@@ -383,10 +437,12 @@ def render_gaussians(camera_or_uniforms, means, scales, rotations, opacities, co
     for name, t in (("means", means), ("scales", scales), ("rotations", rotations), ("opacities", opacities)):
         _cuda_f32(t, name)
     u = _uniforms(camera_or_uniforms, width, height)
+    u_t = _grad_uniforms(camera_or_uniforms)
+    pu = (camera_or_uniforms, means, scales, rotations, width, height) if u_t is not None else (u, means, scales, rotations)
     if return_depth:
-        rec, depths, aux = project_ellipsoids(u, means, scales, rotations, return_depth=True)
+        rec, depths, aux = project_ellipsoids(*pu, return_depth=True)
     else:
-        rec, aux = project_ellipsoids(u, means, scales, rotations)
+        rec, aux = project_ellipsoids(*pu)
         depths = None
     n = aux.n
     if sh is not None:
@@ -394,10 +450,35 @@ def render_gaussians(camera_or_uniforms, means, scales, rotations, opacities, co
         deg = {1: 0, 4: 1, 9: 2, 16: 3}.get(k) if degree is None else degree
         if deg is None:
             raise SplatError(-1, f"sh must hold 3 (degree + 1)^2 floats per splat, not {3 * k}")
-        col = sh_colors(u[16:19], means, sh, deg, opacities)
+        col = sh_colors(u[16:19] if u_t is None else u_t.reshape(-1)[16:19], means, sh, deg, opacities)
     elif colors is not None:
         _cuda_f32(colors, "colors", 3)
         col = _t().cat([colors, opacities.reshape(-1, 1)], dim=1)
     else:
         raise SplatError(-1, "render_gaussians needs colors or sh")
     return rasterize(rec, col, aux, width, height, depths=depths)
+
+
+def pinhole_uniforms(R, t, fx, fy, cx, cy, width, height, near=0.01, far=1000.0):
+    """The 22-float uniform block of a pinhole camera, in plain torch ops (any device; float64 allowed), differentiable in R
+    (3, 3), t (3,) and the intrinsics.  OpenCV / COLMAP convention: Xc = R X + t, x right, y down, z forward; a world point
+    lands at pixel (fx Xc.x / Xc.z + cx, fy Xc.y / Xc.z + cy) in the projector's continuous screen coordinates (those of a
+    record's c.x, c.y: (W / 2)(1 + c.x / c.w), (H / 2)(1 - c.y / c.w)), clip w = Xc.z, eye = -R^T t.  Row 2 of VP maps
+    [near, far] to depth [0, 1] and is not read by the ellipsoid footprint.  R is used as given (not re-orthonormalised): how the
+    pose is parametrised is the caller's choice.  fx, fy, cx, cy may be floats or 0-d tensors."""
+    torch = _t()
+    R = torch.as_tensor(R)
+    kw = dict(dtype=R.dtype, device=R.device)
+    t = torch.as_tensor(t, **kw).reshape(3)
+    fx, fy, cx, cy = (torch.as_tensor(v, **kw).reshape(()) for v in (fx, fy, cx, cy))
+    W, H = float(width), float(height)
+    zero, one = torch.zeros((), **kw), torch.ones((), **kw)
+    a, b = far / (far - near), -far * near / (far - near)
+    P = torch.stack([torch.stack([2.0 * fx / W, zero, 2.0 * cx / W - 1.0, zero]),
+                     torch.stack([zero, -2.0 * fy / H, 1.0 - 2.0 * cy / H, zero]),
+                     torch.stack([zero, zero, a * one, b * one]),
+                     torch.stack([zero, zero, one, zero])])
+    V = torch.cat([torch.cat([R, t.reshape(3, 1)], dim=1), torch.stack([zero, zero, zero, one]).reshape(1, 4)], dim=0)
+    VP = P @ V
+    eye = -(R.transpose(0, 1) @ t)
+    return torch.cat([VP.transpose(0, 1).reshape(16), eye, torch.zeros(1, **kw), torch.tensor([W, H], **kw)])

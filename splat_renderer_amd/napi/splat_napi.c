@@ -410,6 +410,24 @@ FN(sh_colors_backward) { /* (ctx, Float32Array(3) eye, positions, posStride, sh,
     if (eb < 3 * sizeof(float)) { napi_throw_range_error(env, NULL, "eye needs 3 floats"); return NULL; }
     return check(env, x, splat_sh_colors_backward(x, eye, pos, ps, sh, shs, deg, op, gcol, n, gsh, gp, gop), mk_undefined(env));
 }
+FN(project_ellipsoid_backward_camera) { /* project_ellipsoid_backward's arguments, then gradDepth|null, gradUniforms (device, 22 floats) */
+    ARGS(15); splat_ctx *x = arg_external(&c, 0); size_t ub = 0; float *u = arg_hostbuf(&c, 1, &ub);
+    void *pos = arg_dptr(&c, 2); uint32_t ps = (uint32_t)arg_number(&c, 3); void *scl = arg_dptr(&c, 4); uint32_t ss = (uint32_t)arg_number(&c, 5);
+    void *rot = arg_dptr(&c, 6); uint32_t rs = (uint32_t)arg_number(&c, 7), n = (uint32_t)arg_number(&c, 8);
+    void *grec = arg_dptr(&c, 9), *gp = arg_dptr(&c, 10), *gs = arg_dptr(&c, 11), *gr = arg_dptr(&c, 12), *gz = arg_dptr(&c, 13);
+    void *gu = arg_dptr(&c, 14); BAIL;
+    if (ub < 22 * sizeof(float)) { napi_throw_range_error(env, NULL, "uniform block needs 22 floats"); return NULL; }
+    return check(env, x, splat_project_ellipsoid_backward_camera(x, u, pos, ps, scl, ss, rot, rs, n, grec, gp, gs, gr, gz, gu), mk_undefined(env));
+}
+FN(sh_colors_backward_camera) { /* sh_colors_backward's arguments, then gradEye (device, 4 floats) */
+    ARGS(14); splat_ctx *x = arg_external(&c, 0); size_t eb = 0; float *eye = arg_hostbuf(&c, 1, &eb);
+    void *pos = arg_dptr(&c, 2); uint32_t ps = (uint32_t)arg_number(&c, 3); void *sh = arg_dptr(&c, 4);
+    uint32_t shs = (uint32_t)arg_number(&c, 5), deg = (uint32_t)arg_number(&c, 6); void *op = arg_dptr(&c, 7), *gcol = arg_dptr(&c, 8);
+    uint32_t n = (uint32_t)arg_number(&c, 9); void *gsh = arg_dptr(&c, 10), *gp = arg_dptr(&c, 11), *gop = arg_dptr(&c, 12);
+    void *ge = arg_dptr(&c, 13); BAIL;
+    if (eb < 3 * sizeof(float)) { napi_throw_range_error(env, NULL, "eye needs 3 floats"); return NULL; }
+    return check(env, x, splat_sh_colors_backward_camera(x, eye, pos, ps, sh, shs, deg, op, gcol, n, gsh, gp, gop, ge), mk_undefined(env));
+}
 FN(render_frame_ellipsoids) { /* (ctx, sorter, binner, cfg[8], Float32Array(22), positions, scales, rotations, colorOpacity, n, W, H, projected|null, out8|null, outF|null, [depth, alpha, ids]|null) */
     ARGS(16); splat_ctx *x = arg_external(&c, 0); splat_sorter *s = arg_external(&c, 1); splat_binner *b = arg_external(&c, 2);
     splat_composite_cfg cfg; fill_cfg(&c, 3, &cfg); size_t ub = 0; float *u = arg_hostbuf(&c, 4, &ub);
@@ -674,6 +692,7 @@ static napi_value init(napi_env env, napi_value exports) {
         EXPORT(point_frame), EXPORT(project_ellipsoid), EXPORT(sh_colors), EXPORT(render_frame_ellipsoids),
         EXPORT(composite_backward), EXPORT(project_ellipsoid_backward), EXPORT(sh_colors_backward),
         EXPORT(composite_aov_depth), EXPORT(composite_backward_depth), EXPORT(project_ellipsoid_backward_depth),
+        EXPORT(project_ellipsoid_backward_camera), EXPORT(sh_colors_backward_camera),
     };
     napi_define_properties(env, exports, sizeof d / sizeof d[0], d);
     return exports;

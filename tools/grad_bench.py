@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Gradients of ellipsoid frames (GPU box only): python tools/grad_bench.py [--depth] [C1,C2] [K] [R]
+"""Gradients of ellipsoid frames (GPU box only): python tools/grad_bench.py [--depth] [--camera] [C1,C2] [K] [R]
 
 tools/ellipsoid_bench.py's scenes and method (the scene's positions, sigma = radius / 2 per axis times a random factor in
 [e^-0.3, e^0.3], random rotations, SH of degree 3 with the scene's opacity; R rounds of K calls per kind, kinds alternating
@@ -13,7 +13,18 @@ the time they take at 1.3 TB/s.
 --depth adds, beside the colour-only figures: the forward with the depth map (rasterize(..., depths=)), its backward with a
 depth loss as well (loss += sum of depth * a fixed random image where depth is finite), the depth variant of the composite
 backward alone (splat_composite_backward_depth) and of the projector's (splat_project_ellipsoid_backward_depth); the atomic
-bytes then count 40 per consumed pair (the tenth sum, dL/dz)."""
+bytes then count 40 per consumed pair (the tenth sum, dL/dz).
+
+--camera adds the camera gradients: splat_project_ellipsoid_backward_camera without and with grad_depth (all of its launches:
+the per-splat kernel with the per-wave sums, then k_camera_sum_slices above 1024 partials, then k_camera_sum) beside
+splat_project_ellipsoid_backward(_depth), whose kernels are the parent commit's instruction for instruction;
+splat_sh_colors_backward_camera beside splat_sh_colors_backward; the alternative the fused sums replace, twice, each once per
+round: project_backward plus the twelve per-splat terms written out as plain float32 torch ops without autograd and summed
+(project_backward_plus_torch_terms: the kernel has no output for gJ, gcx, gcy, gcw, so the expression recomputes J, T, Sigma2
+and their gradients per splat), and, as an upper bound, project_backward plus a torch restatement of the whole record function
+differentiated by torch.autograd (project_backward_plus_torch_sum); and the whole frame's forward and backward with the
+uniform block as a CUDA tensor that requires grad (forward_camera, backward_camera) beside the
+NumPy block's (forward, backward).  Ratios camera / plain are printed per pair."""
 import ctypes as C
 import json
 import os
@@ -29,8 +40,76 @@ from splat_renderer_amd import autograd as AG
 
 ATOMIC_RATE = 1.3e12  # bytes / s of global float atomic adds, chip-wide
 
-argv = [a for a in sys.argv[1:] if a != "--depth"]
-depth_too = len(argv) != len(sys.argv) - 1
+def torch_camera_terms(U, pos, scl, rot, g, W, H):
+    """dL/dVP's twelve entries (column k = 0..3, rows 0, 1, 3: index 3 k + {0, 1, 2}) for dL/d{c.x, c.y, B00, B01, B11} = g (n, 5):
+    k_project_ellipsoid_backward's per-splat terms written out as plain float32 torch ops, without autograd, and summed (no cull)."""
+    q = rot / torch.sqrt((rot * rot).sum(dim=1, keepdim=True))
+    qr, qx, qy, qz = q.unbind(1)
+    R = [[1 - 2 * (qy * qy + qz * qz), 2 * (qx * qy - qr * qz), 2 * (qx * qz + qr * qy)],
+         [2 * (qx * qy + qr * qz), 1 - 2 * (qx * qx + qz * qz), 2 * (qy * qz - qr * qx)],
+         [2 * (qx * qz - qr * qy), 2 * (qy * qz + qr * qx), 1 - 2 * (qx * qx + qy * qy)]]
+    M = [[R[i][j] * scl[:, j] for j in range(3)] for i in range(3)]
+    p = [pos[:, 0], pos[:, 1], pos[:, 2]]
+    cx, cy, cw = (U[r] * p[0] + U[4 + r] * p[1] + U[8 + r] * p[2] + U[12 + r] for r in (0, 1, 3))
+    nx, ny = cx / cw, cy / cw
+    ax, ay = 0.5 * W / cw, 0.5 * H / cw
+    dj0 = [U[4 * k] - nx * U[4 * k + 3] for k in range(3)]
+    dj1 = [ny * U[4 * k + 3] - U[4 * k + 1] for k in range(3)]
+    t0 = [sum(ax * dj0[k] * M[k][c] for k in range(3)) for c in range(3)]
+    t1 = [sum(ay * dj1[k] * M[k][c] for k in range(3)) for c in range(3)]
+    A = t0[0] * t0[0] + t0[1] * t0[1] + t0[2] * t0[2] + 0.3
+    B = t0[0] * t1[0] + t0[1] * t1[1] + t0[2] * t1[2]
+    Cc = t1[0] * t1[0] + t1[1] * t1[1] + t1[2] * t1[2] + 0.3
+    det = A * Cc - B * B
+    b00, b01, b11 = torch.sqrt(Cc / det) / 3, -B / torch.sqrt(Cc * det) / 3, 1 / torch.sqrt(Cc) / 3
+    gdet = -(g[:, 2] * b00 + g[:, 3] * b01) / (2 * det)
+    gC = (g[:, 2] * b00 - g[:, 3] * b01 - g[:, 4] * b11) / (2 * Cc) + gdet * A
+    gA = gdet * Cc
+    gB = g[:, 3] * (-1 / (3 * torch.sqrt(Cc * det))) - 2 * B * gdet
+    gt0 = [2 * gA * t0[c] + gB * t1[c] for c in range(3)]
+    gt1 = [2 * gC * t1[c] + gB * t0[c] for c in range(3)]
+    gj0 = [sum(gt0[c] * M[k][c] for c in range(3)) for k in range(3)]
+    gj1 = [sum(gt1[c] * M[k][c] for c in range(3)) for k in range(3)]
+    gax = sum(gj0[k] * dj0[k] for k in range(3))
+    gay = sum(gj1[k] * dj1[k] for k in range(3))
+    gnx = 0.5 * W * g[:, 0] - sum(gj0[k] * ax * U[4 * k + 3] for k in range(3))
+    gny = -0.5 * H * g[:, 1] + sum(gj1[k] * ay * U[4 * k + 3] for k in range(3))
+    gcx, gcy = gnx / cw, gny / cw
+    gcw = -(gax * ax + gay * ay) / cw - (gnx * nx + gny * ny) / cw
+    terms = []
+    for k in range(3):
+        terms += [gcx * p[k] + gj0[k] * ax, gcy * p[k] - gj1[k] * ay, gcw * p[k] + (gj1[k] * ay * ny - gj0[k] * ax * nx)]
+    terms += [gcx, gcy, gcw]
+    return torch.stack(terms, dim=1).sum(dim=0)
+
+
+argv = [a for a in sys.argv[1:] if a not in ("--depth", "--camera")]
+depth_too = "--depth" in sys.argv[1:]
+camera_too = "--camera" in sys.argv[1:]
+
+
+def torch_records(U, pos, scl, rot, W, H):
+    """The records {c.x, c.y, B00, B01, B11} (n, 5) as plain float32 torch ops of the uniform block U (include/splat.h; no cull)."""
+    q = rot / torch.sqrt((rot * rot).sum(dim=1, keepdim=True))
+    qr, qx, qy, qz = q.unbind(1)
+    R = [[1 - 2 * (qy * qy + qz * qz), 2 * (qx * qy - qr * qz), 2 * (qx * qz + qr * qy)],
+         [2 * (qx * qy + qr * qz), 1 - 2 * (qx * qx + qz * qz), 2 * (qy * qz - qr * qx)],
+         [2 * (qx * qz - qr * qy), 2 * (qy * qz + qr * qx), 1 - 2 * (qx * qx + qy * qy)]]
+    M = [[R[i][j] * scl[:, j] for j in range(3)] for i in range(3)]
+    cx, cy, cw = (U[r] * pos[:, 0] + U[4 + r] * pos[:, 1] + U[8 + r] * pos[:, 2] + U[12 + r] for r in (0, 1, 3))
+    nx, ny = cx / cw, cy / cw
+    ax, ay = 0.5 * W / cw, 0.5 * H / cw
+    j0 = [ax * (U[4 * k] - nx * U[4 * k + 3]) for k in range(3)]
+    j1 = [ay * (ny * U[4 * k + 3] - U[4 * k + 1]) for k in range(3)]
+    t0 = [j0[0] * M[0][c] + j0[1] * M[1][c] + j0[2] * M[2][c] for c in range(3)]
+    t1 = [j1[0] * M[0][c] + j1[1] * M[1][c] + j1[2] * M[2][c] for c in range(3)]
+    a = t0[0] * t0[0] + t0[1] * t0[1] + t0[2] * t0[2] + 0.3
+    b = t0[0] * t1[0] + t0[1] * t1[1] + t0[2] * t1[2]
+    c = t1[0] * t1[0] + t1[1] * t1[1] + t1[2] * t1[2] + 0.3
+    det = a * c - b * b
+    return torch.stack([(nx + 1) * 0.5 * W, (1 - ny) * 0.5 * H, torch.sqrt(c / det) / 3, -b / torch.sqrt(c * det) / 3, 1 / torch.sqrt(c) / 3], dim=1)
+
+
 names = argv[0].split(",") if len(argv) > 0 else ["C1", "C2"]
 k = int(argv[1]) if len(argv) > 1 else 20
 rounds = int(argv[2]) if len(argv) > 2 else 7
@@ -121,12 +200,60 @@ for name in names:
                                                                                          gs.data_ptr(), gq.data_ptr(), gzp.data_ptr()),
         })
 
+    if camera_too:
+        ut = torch.tensor(u, device="cuda", requires_grad=True)
+        gu, ge = torch.empty(24, device="cuda"), torch.empty(4, device="cuda")
+        grec5 = torch.rand((n, 5), device="cuda") * 2 - 1
+
+        def forward_camera():
+            rec, depths, aux = AG.project_ellipsoids(ut, means, scales, rots, return_depth=True)
+            col = AG.sh_colors(ut[16:19], means, shs, 3, ops)
+            rgb, _, depth = AG.rasterize(rec, col, aux, w, h, depths=depths)
+            dz = torch.where(torch.isfinite(depth), depth, torch.zeros_like(depth))
+            state.update(rec=rec, col=col, aux=aux, depths=depths, loss=(rgb * gimg).sum() + (dz * gdimg).sum())
+
+        def plus_torch_sum():
+            work["project_backward"]()
+            U = ut.detach().clone().requires_grad_()
+            (torch_records(U, means.detach(), scales.detach(), rots.detach(), float(w), float(h)) * grec5).sum().backward()
+
+        def plus_torch_terms():
+            work["project_backward"]()
+            with torch.no_grad():
+                torch_camera_terms(ut.detach(), means.detach(), scales.detach(), rots.detach(), grec5, float(w), float(h))
+
+        def camera_entry(gzp_ptr):
+            return lambda: lib.splat_project_ellipsoid_backward_camera(cx.ctx, uf, m4.data_ptr(), 1, s4.data_ptr(), 1, rots.data_ptr(), 1, n,
+                                                                       grec.data_ptr(), gp.data_ptr(), gs.data_ptr(), gq.data_ptr(), gzp_ptr,
+                                                                       gu.data_ptr())
+        work.update({
+            "forward_depth": forward_depth,
+            "backward_depth": None,
+            "forward_camera": forward_camera,
+            "backward_camera": None,
+            "project_backward_depth": lambda: lib.splat_project_ellipsoid_backward_depth(cx.ctx, uf, m4.data_ptr(), 1, s4.data_ptr(), 1,
+                                                                                         rots.data_ptr(), 1, n, grec.data_ptr(), gp.data_ptr(),
+                                                                                         gs.data_ptr(), gq.data_ptr(), gzp.data_ptr()),
+            "project_backward_camera": camera_entry(None),
+            "project_backward_camera_depth": camera_entry(gzp.data_ptr()),
+            "sh3_backward_camera": lambda: lib.splat_sh_colors_backward_camera(cx.ctx, eye.ctypes.data_as(C.POINTER(C.c_float)), m4.data_ptr(), 1,
+                                                                               shs.data_ptr(), 48, 3, ops.data_ptr(), gcol.data_ptr(), n,
+                                                                               gsh.data_ptr(), gp.data_ptr(), gop.data_ptr(), ge.data_ptr()),
+            "project_backward_plus_torch_sum": plus_torch_sum,
+            "project_backward_plus_torch_terms": plus_torch_terms,
+        })
+    forwards = {"backward": forward, "backward_depth": forward_depth}
+    if camera_too:
+        forwards["backward_camera"] = forward_camera
+
     def run(kind, calls):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        if kind in ("backward", "backward_depth"):
+        if kind in ("project_backward_plus_torch_sum", "project_backward_plus_torch_terms"):
+            calls = 1  # (about a hundred elementwise launches over n splats and their autograd: once per round is enough)
+        if kind in forwards:
             tot = 0.0
             for _ in range(calls):
-                (forward if kind == "backward" else forward_depth)()
+                forwards[kind]()
                 e0.record(stream)
                 backward()
                 e1.record(stream)
@@ -152,6 +279,12 @@ for name in names:
     if depth_too:
         extra = {"atomic_bytes_bound_depth": 40 * consumed_pairs, "atomic_floor_ms_depth": round(40 * consumed_pairs / ATOMIC_RATE * 1e3, 4),
                  "composite_backward_depth_over_colour": round(med["composite_backward_depth"] / med["composite_backward"], 3)}
+    if camera_too:
+        extra.update({f"{a}_over_{b}": round(med[a] / med[b], 3) for a, b in (
+            ("project_backward_camera", "project_backward"), ("project_backward_camera_depth", "project_backward_depth"),
+            ("sh3_backward_camera", "sh3_backward"), ("backward_camera", "backward_depth"), ("forward_camera", "forward_depth"),
+            ("project_backward_plus_torch_sum", "project_backward_camera"),
+            ("project_backward_plus_torch_terms", "project_backward_camera"))})
     print(json.dumps({"config": name, "n": n, "calls_per_round": k, "rounds": rounds,
                       **{f"{kind}_ms": round(v, 4) for kind, v in med.items()},
                       **{f"{kind}_ms_min_max": [round(min(v), 4), round(max(v), 4)] for kind, v in ts.items()},
