@@ -553,6 +553,45 @@ int splat_sh_colors_backward_camera(splat_ctx *ctx, const float *eye3, const voi
                                     uint32_t sh_stride_floats, uint32_t degree, const void *opacity_f32, const void *grad_color_opacity,
                                     uint32_t n, void *grad_sh, void *grad_positions, void *grad_opacity, void *grad_eye);
 
+/* ---- Image loss: the photometric objective of 3D Gaussian splatting (an extension) -----------------------------------------
+ * How far a rendered image x is from a target y, both width x height pixels of 3 float32 channels:
+ *   loss = (1 - lambda) l1 + lambda (1 - ssim),   l1 = mean |x - y|,   ssim = mean m,   both means over all N = 3 W H values.
+ * With g the normalised 1-D window g[k] ~ exp(-(k - 5)^2 / (2 1.5^2)), k = 0..10, sum g = 1, and conv(.) the separable 11 x 11
+ * convolution with g (x) g, per channel, ZERO padding (same output size as its input; its own adjoint):
+ *   mu_x = conv(x), mu_y = conv(y), s_x = conv(x x) - mu_x^2, s_y = conv(y y) - mu_y^2, s_xy = conv(x y) - mu_x mu_y,
+ *   A = 2 mu_x mu_y + C1, B = 2 s_xy + C2, C = mu_x^2 + mu_y^2 + C1, D = s_x + s_y + C2, C1 = 0.01^2, C2 = 0.03^2,
+ *   m = A B / (C D).
+ * The gradient with respect to x (none is offered for the target):
+ *   dm/dmu_x = 2 mu_y B / (C D) - 2 mu_x m / C - 2 mu_y A / (C D) + 2 mu_x m / D,  dm/ds_x = -m / D,  dm/ds_xy = 2 A / (C D),
+ *   dloss/dx = (1 - lambda) sign(x - y) / N - (lambda / N) [conv(dm/dmu_x) + 2 x conv(dm/ds_x) + y conv(dm/ds_xy)],
+ * sign(0) = 0.  x is not clamped (a composite may exceed 1).  Images smaller than the window are legal, down to 1 x 1.
+ *
+ * An image is (pointer, pixel stride in floats >= 3): pixel p's channels are the first three floats at pointer + p * stride,
+ * pixels in row-major order without row padding.  The float4 image of splat_composite_aov is (out_rgba32f, 4), read in place; a
+ * packed RGB image is (ptr, 3).  A fourth word may be loaded but never enters a result (NaN there is harmless); of the
+ * gradient's pixels only the first three floats are written.  Pointers are 4-byte aligned, the workspace 16-byte.
+ *
+ * splat_image_loss writes out4 (DEVICE, 4 floats) = {loss, l1, ssim, 0}.  The two sums are made without atomics: each
+ * workgroup's float64 partial goes to a slot of its own in a scratch buffer of the ctx and one small kernel adds the slots in
+ * index order and rounds once, so the same inputs give the same bits.  `workspace` (DEVICE, at least
+ * splat_image_loss_workspace_bytes(width, height) = 36 W H bytes rounded up to 16) receives the three derivative maps for
+ * splat_image_loss_backward.  lambda = 0 with workspace == NULL runs the L1 part alone: ssim is then NaN (not computed) and
+ * loss = l1; lambda = 0 with a workspace computes all three.
+ * splat_image_loss_backward OVERWRITES the first three floats of every pixel of (grad_image, grad_stride) with `upstream[0]`
+ * (DEVICE, one float: dL/dloss, read on the device so that no caller has to synchronise) times dloss/dx.  image, target,
+ * strides, size and lambda must be those of the splat_image_loss call that filled `workspace`; with lambda = 0 the workspace
+ * is not read and may be NULL.  It is a gather with no atomics: bit-reproducible.
+ * Nothing here waits on the host; all work goes to the ctx's stream.
+ * SPLAT_ERR_INVALID: a NULL image, target, out4, upstream or grad_image; width or height 0 or above 65535; a stride below 3;
+ * lambda outside [0, 1] (or NaN); a misaligned pointer; a workspace that is needed and NULL or smaller than
+ * splat_image_loss_workspace_bytes. */
+uint64_t splat_image_loss_workspace_bytes(uint32_t width, uint32_t height);
+int splat_image_loss(splat_ctx *ctx, const void *image, uint32_t image_stride, const void *target, uint32_t target_stride,
+                     uint32_t width, uint32_t height, float lambda, void *workspace, uint64_t workspace_bytes, void *out4);
+int splat_image_loss_backward(splat_ctx *ctx, const void *image, uint32_t image_stride, const void *target, uint32_t target_stride,
+                              uint32_t width, uint32_t height, float lambda, const void *workspace, uint64_t workspace_bytes,
+                              const void *upstream, void *grad_image, uint32_t grad_stride);
+
 /* ---- multi-GPU band path (no reference equivalent — the reference is single-device) */
 /* The oriented-disc projector (src/SequentialRenderer.ts:68-71,91-112): the splat is the disc
  * p + r*(t*u + b*v), u^2+v^2 <= 1, in the tangent plane of its normal (t = normalize(cross(up, n)), b =

@@ -94,7 +94,10 @@ SIGNATURES = {
     "splat_project_ellipsoid_backward_camera": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp,
                                                      _vp, _vp]),
     "splat_sh_colors_backward_camera": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _vp, _u32, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
-    "splat_extract_keys": (_i, [_vp, _vp, _u32, _u32, _vp, _vp]),
+    "splat_image_loss_workspace_bytes": (C.c_uint64, [_u32, _u32]),
+    "splat_image_loss": (_i, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, C.c_float, _vp, C.c_uint64, _vp]),
+    "splat_image_loss_backward": (_i, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, C.c_float, _vp, C.c_uint64, _vp, _vp, _u32]),
+    "splat_extract_keys":(_i, [_vp, _vp, _u32, _u32, _vp, _vp]),
     "splat_sort_create": (_i, [_vp, _u32, _pvp]),
     "splat_sort_destroy": (None, [_vp]),
     "splat_sort_capacity": (_u32, [_vp]),

@@ -41,6 +41,20 @@ grad takes the code path, the kernels and the results described above, unchanged
 pinhole_uniforms(R, t, fx, fy, cx, cy, width, height) builds the block from a pose and intrinsics in plain torch ops, so that
 gradients reach whatever parametrises R and t (axis-angle, quaternion: the caller's choice).
 
+The objective (include/splat.h, "Image loss"):
+
+    loss            = photometric_loss(rgb, target, lambda_dssim=0.2)                     # 0-d tensor, differentiable in rgb
+    loss, l1, ssim  = photometric_loss(rgb, target, lambda_dssim=0.2, return_terms=True)  # l1, ssim detached
+
+loss = (1 - lambda) mean|rgb - target| + lambda (1 - SSIM), SSIM over 3DGS's 11 x 11 Gaussian window of sigma 1.5 with zero
+padding: one fused kernel forward (splat_image_loss), one backward (splat_image_loss_backward), instead of five grouped
+convolutions and their transposes.  rgb is (H, W, 3); the view rasterize returns (the first three channels of its (H, W, 4)
+buffer) is read in place with pixel stride 4, a contiguous (H, W, 3) tensor with stride 3, and any other layout is made
+contiguous first.  target is (H, W, 3) or (H, W, 4) and gets no gradient; rgb is not clamped.  The two means are summed in
+float64 in a fixed order and the backward is a gather: both are bit-reproducible.  The upstream gradient is read on the device,
+so backward() does not synchronise.  lambda_dssim = 0 is a plain L1: the SSIM part is not launched (unless return_terms asks
+for its value).  No masks: multiply both images by one in torch.
+
 `rec` is a real intermediate: rec.retain_grad() gives the screen-space gradient rec.grad[:, :2] that 3DGS densification reads.
 
 The background is the composite's fixed bg = (0.05, 0.05, 0.1).  A caller that wants background b uses
@@ -222,7 +236,7 @@ class ProjectedSplats:
 
 
 def _functions():
-    """The three autograd Functions, built on first use (torch imported then)."""
+    """The autograd Functions, built on first use (torch imported then)."""
     torch = _t()
     if "_fns" in globals():
         return globals()["_fns"]
@@ -366,7 +380,40 @@ def _functions():
                                                             gz.data_ptr()), cx.ctx)
             return grec, gcol, None, None, None, gz
 
-    fns = (Project, ShColors, Rasterize)
+    class PhotometricLoss(torch.autograd.Function):
+        @staticmethod
+        def forward(fctx, x, xs, y, ys, lam, want_ssim):
+            # (x, y: tensors whose data_ptr() is an image of pixel stride xs, ys floats; x (H, W, 3), perhaps a view)
+            cx = _context(x)
+            h, w = x.shape[0], x.shape[1]
+            out = torch.empty(4, device=x.device, dtype=torch.float32)
+            nbytes = int(cx.lib.splat_image_loss_workspace_bytes(w, h)) if (lam > 0.0 or want_ssim) else 0
+            ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32) if nbytes else None
+            check(cx.lib.splat_image_loss(cx.ctx, x.data_ptr(), xs, y.data_ptr(), ys, w, h, lam, ws.data_ptr() if nbytes else None, nbytes,
+                                          out.data_ptr()), cx.ctx)
+            fctx.save_for_backward(x, y, *([ws] if nbytes else []))
+            fctx.args = (xs, ys, lam, nbytes)
+            fctx.set_materialize_grads(False)
+            loss, l1, ssim = out[0], out[1], out[2]
+            fctx.mark_non_differentiable(l1, ssim)
+            return loss, l1, ssim
+
+        @staticmethod
+        def backward(fctx, grad_loss, *_):
+            if grad_loss is None:
+                return (None,) * 6
+            x, y = fctx.saved_tensors[:2]
+            xs, ys, lam, nbytes = fctx.args
+            cx = _context(x)
+            h, w = x.shape[0], x.shape[1]
+            up = grad_loss.to(torch.float32).reshape(1).contiguous()
+            g = torch.empty((h, w, 3), device=x.device, dtype=torch.float32)
+            check(cx.lib.splat_image_loss_backward(cx.ctx, x.data_ptr(), xs, y.data_ptr(), ys, w, h, lam,
+                                                   fctx.saved_tensors[2].data_ptr() if nbytes and lam > 0.0 else None, nbytes, up.data_ptr(),
+                                                   g.data_ptr(), 3), cx.ctx)
+            return g, None, None, None, None, None
+
+    fns = (Project, ShColors, Rasterize, PhotometricLoss)
     globals()["_fns"] = fns
     return fns
 
@@ -457,6 +504,39 @@ def render_gaussians(camera_or_uniforms, means, scales, rotations, opacities, co
     else:
         raise SplatError(-1, "render_gaussians needs colors or sh")
     return rasterize(rec, col, aux, width, height, depths=depths)
+
+
+def _image(t, name, channels):
+    """(tensor, pixel stride in floats) of an (H, W, 3 | 4) CUDA float32 image, without a copy where its layout is one the
+    kernels address: packed pixels of 3 floats, or of 4 (an (H, W, 4) tensor or its [..., :3] view)."""
+    torch = _t()
+    if not isinstance(t, torch.Tensor):
+        raise SplatError(-1, f"{name} must be a torch tensor")
+    if not t.is_cuda:
+        raise SplatError(-1, f"{name} is on {t.device}: splat_renderer_amd has no CPU path")
+    if t.dtype != torch.float32:
+        raise SplatError(-1, f"{name} must be float32, not {t.dtype}")
+    if t.dim() != 3 or t.shape[2] not in channels or t.shape[0] < 1 or t.shape[1] < 1:
+        raise SplatError(-1, f"{name} must have shape (H, W, {' or '.join(map(str, channels))}), not {tuple(t.shape)}")
+    h, w, c = t.shape
+    for s in ((3, 4) if c == 3 else (4,)):
+        if t.stride(2) == 1 and (w == 1 or t.stride(1) == s) and (h == 1 or t.stride(0) == w * s):
+            return t, s
+    return t.contiguous(), c
+
+
+def photometric_loss(rgb, target, lambda_dssim=0.2, return_terms=False):
+    """3DGS's objective (1 - lambda) L1 + lambda (1 - SSIM) between rgb (H, W, 3) and target (H, W, 3 or 4): a 0-d tensor,
+    differentiable in rgb; return_terms=True: (loss, l1, ssim), the two terms detached.  The module's docstring has the rest."""
+    x, xs = _image(rgb, "rgb", (3,))
+    y, ys = _image(target, "target", (3, 4))
+    if x.shape[:2] != y.shape[:2]:
+        raise SplatError(-1, f"rgb is {tuple(x.shape[:2])} pixels and target {tuple(y.shape[:2])}")
+    if x.device != y.device:
+        raise SplatError(-1, f"rgb is on {x.device} and target on {y.device}")
+    lam = float(lambda_dssim)
+    loss, l1, ssim = _functions()[3].apply(x, xs, y.detach(), ys, lam, bool(return_terms))
+    return (loss, l1, ssim) if return_terms else loss
 
 
 def pinhole_uniforms(R, t, fx, fy, cx, cy, width, height, near=0.01, far=1000.0):

@@ -428,6 +428,23 @@ FN(sh_colors_backward_camera) { /* sh_colors_backward's arguments, then gradEye 
     if (eb < 3 * sizeof(float)) { napi_throw_range_error(env, NULL, "eye needs 3 floats"); return NULL; }
     return check(env, x, splat_sh_colors_backward_camera(x, eye, pos, ps, sh, shs, deg, op, gcol, n, gsh, gp, gop, ge), mk_undefined(env));
 }
+FN(image_loss_workspace_bytes) { /* (W, H) -> bytes */
+    ARGS(2); uint32_t w = (uint32_t)arg_number(&c, 0), h = (uint32_t)arg_number(&c, 1); BAIL;
+    return mk_number(env, (double)splat_image_loss_workspace_bytes(w, h));
+}
+FN(image_loss) { /* (ctx, image, imageStride, target, targetStride, W, H, lambda, workspace|null, workspaceBytes, out4 (device: loss, l1, ssim, 0)) */
+    ARGS(11); splat_ctx *x = arg_external(&c, 0); void *img = arg_dptr(&c, 1); uint32_t is = (uint32_t)arg_number(&c, 2);
+    void *tgt = arg_dptr(&c, 3); uint32_t ts = (uint32_t)arg_number(&c, 4), w = (uint32_t)arg_number(&c, 5), h = (uint32_t)arg_number(&c, 6);
+    float lambda = (float)arg_number(&c, 7); void *ws = arg_dptr(&c, 8); uint64_t wb = (uint64_t)arg_number(&c, 9); void *out = arg_dptr(&c, 10); BAIL;
+    return check(env, x, splat_image_loss(x, img, is, tgt, ts, w, h, lambda, ws, wb, out), mk_undefined(env));
+}
+FN(image_loss_backward) { /* image_loss's arguments up to workspaceBytes, then upstream (device, 1 float), gradImage, gradStride */
+    ARGS(13); splat_ctx *x = arg_external(&c, 0); void *img = arg_dptr(&c, 1); uint32_t is = (uint32_t)arg_number(&c, 2);
+    void *tgt = arg_dptr(&c, 3); uint32_t ts = (uint32_t)arg_number(&c, 4), w = (uint32_t)arg_number(&c, 5), h = (uint32_t)arg_number(&c, 6);
+    float lambda = (float)arg_number(&c, 7); void *ws = arg_dptr(&c, 8); uint64_t wb = (uint64_t)arg_number(&c, 9);
+    void *up = arg_dptr(&c, 10), *g = arg_dptr(&c, 11); uint32_t gs = (uint32_t)arg_number(&c, 12); BAIL;
+    return check(env, x, splat_image_loss_backward(x, img, is, tgt, ts, w, h, lambda, ws, wb, up, g, gs), mk_undefined(env));
+}
 FN(render_frame_ellipsoids) { /* (ctx, sorter, binner, cfg[8], Float32Array(22), positions, scales, rotations, colorOpacity, n, W, H, projected|null, out8|null, outF|null, [depth, alpha, ids]|null) */
     ARGS(16); splat_ctx *x = arg_external(&c, 0); splat_sorter *s = arg_external(&c, 1); splat_binner *b = arg_external(&c, 2);
     splat_composite_cfg cfg; fill_cfg(&c, 3, &cfg); size_t ub = 0; float *u = arg_hostbuf(&c, 4, &ub);
@@ -693,6 +710,7 @@ static napi_value init(napi_env env, napi_value exports) {
         EXPORT(composite_backward), EXPORT(project_ellipsoid_backward), EXPORT(sh_colors_backward),
         EXPORT(composite_aov_depth), EXPORT(composite_backward_depth), EXPORT(project_ellipsoid_backward_depth),
         EXPORT(project_ellipsoid_backward_camera), EXPORT(sh_colors_backward_camera),
+        EXPORT(image_loss_workspace_bytes), EXPORT(image_loss), EXPORT(image_loss_backward),
     };
     napi_define_properties(env, exports, sizeof d / sizeof d[0], d);
     return exports;

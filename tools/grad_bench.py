@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Gradients of ellipsoid frames (GPU box only): python tools/grad_bench.py [--depth] [--camera] [C1,C2] [K] [R]
+"""Gradients of ellipsoid frames (GPU box only): python tools/grad_bench.py [--depth] [--camera | --loss] [C1,C2] [K] [R]
 
 tools/ellipsoid_bench.py's scenes and method (the scene's positions, sigma = radius / 2 per axis times a random factor in
 [e^-0.3, e^0.3], random rotations, SH of degree 3 with the scene's opacity; R rounds of K calls per kind, kinds alternating
@@ -24,7 +24,16 @@ round: project_backward plus the twelve per-splat terms written out as plain flo
 and their gradients per splat), and, as an upper bound, project_backward plus a torch restatement of the whole record function
 differentiated by torch.autograd (project_backward_plus_torch_sum); and the whole frame's forward and backward with the
 uniform block as a CUDA tensor that requires grad (forward_camera, backward_camera) beside the
-NumPy block's (forward, backward).  Ratios camera / plain are printed per pair."""
+NumPy block's (forward, backward).  Ratios camera / plain are printed per pair.
+
+--loss measures the image loss instead (one JSON line per config, nothing of the above): splat_image_loss and
+splat_image_loss_backward alone on the frame's own rgb (the stride-4 view rasterize returns) and a packed target
+(fused_loss_forward, fused_loss_backward); the route they replace on the same tensors, written out below (torch_loss: float32
+conv2d with the 11 x 11 window over three groups, five maps, and the .contiguous() conv2d needs of that view; forward, and
+its torch.autograd backward); the whole frame's forward + backward with each of the two losses (frame_fused, frame_torch);
+and the bytes each fused kernel must move (forward: x at 16 B and y at 12 B per pixel read, 36 B of derivative maps written;
+backward: the same reads, the maps read, 12 B of gradient written) with the time they take at 5.1 TB/s, the copy rate
+DESIGN.md uses."""
 import ctypes as C
 import json
 import os
@@ -83,9 +92,115 @@ def torch_camera_terms(U, pos, scl, rot, g, W, H):
     return torch.stack(terms, dim=1).sum(dim=0)
 
 
-argv = [a for a in sys.argv[1:] if a not in ("--depth", "--camera")]
+argv = [a for a in sys.argv[1:] if a not in ("--depth", "--camera", "--loss")]
 depth_too = "--depth" in sys.argv[1:]
 camera_too = "--camera" in sys.argv[1:]
+loss_only = "--loss" in sys.argv[1:]
+COPY_RATE = 5.1e12  # bytes / s, read + write: the box's device-to-device copy rate
+
+
+def torch_loss(rgb, target, lam=0.2):
+    """(1 - lam) L1 + lam (1 - SSIM) in float32 torch ops: what a user wrote before the fused kernel."""
+    import torch.nn.functional as F
+    kk = torch.arange(11, device=rgb.device, dtype=torch.float32)
+    g = torch.exp(-((kk - 5) ** 2) / (2 * 1.5 ** 2))
+    g = g / g.sum()
+    k2 = torch.outer(g, g)[None, None].expand(3, 1, -1, -1).contiguous()
+    a, b = rgb.contiguous().permute(2, 0, 1)[None], target.permute(2, 0, 1)[None]
+    conv = lambda t: F.conv2d(t, k2, padding=5, groups=3)  # noqa: E731
+    mx, my = conv(a), conv(b)
+    sx, sy, sxy = conv(a * a) - mx * mx, conv(b * b) - my * my, conv(a * b) - mx * my
+    m = ((2 * mx * my + 1e-4) * (2 * sxy + 9e-4)) / ((mx * mx + my * my + 1e-4) * (sx + sy + 9e-4))
+    return (1 - lam) * (a - b).abs().mean() + lam * (1 - m.mean())
+
+
+def loss_bench(name, k, rounds, stream):
+    n, w, h = sr.scene.CONFIGS[name]
+    props, _ = sr.scene.make_scene(n)
+    rng = np.random.default_rng(0)
+    scl = (props[:, 3:4] * 0.5 * np.exp(rng.uniform(-0.3, 0.3, (n, 3)))).astype(np.float32)
+    rot = rng.normal(size=(n, 4)).astype(np.float32)
+    sh = rng.normal(0, 0.3, (n, 16, 3)).astype(np.float32)
+    cam = sr.Camera()
+    cam.setAspect(w / h)
+    u = cam.uniforms(w, h)
+    t = lambda a: torch.tensor(np.ascontiguousarray(a, np.float32), device="cuda", requires_grad=True)  # noqa: E731
+    means, scales, rots, ops, shs = t(props[:, :3]), t(scl), t(rot), t(props[:, 7]), t(sh)
+
+    def frame():
+        rec, aux = AG.project_ellipsoids(u, means, scales, rots)
+        col = AG.sh_colors(u[16:19], means, shs, 3, ops)
+        return AG.rasterize(rec, col, aux, w, h)[0]
+
+    with torch.no_grad():
+        rgb = frame()  # (the (H, W, 3) view of an (H, W, 4) buffer)
+    target = (rgb + 0.1 * torch.randn_like(rgb)).clamp(0, 1).contiguous()
+    x = rgb.detach().requires_grad_()
+    cx = AG._context(rgb)
+    lib = cx.lib
+    nbytes = int(lib.splat_image_loss_workspace_bytes(w, h))
+    ws, out4, up = torch.empty(nbytes // 4, device="cuda"), torch.empty(4, device="cuda"), torch.ones(1, device="cuda")
+    grad = torch.empty((h, w, 3), device="cuda")
+    state = {}
+
+    def frame_with(loss_fn):
+        def go():
+            state["loss"] = loss_fn(frame(), target)
+            state["loss"].backward()
+        return go
+
+    def torch_forward():
+        state["loss"] = torch_loss(x, target)
+
+    work = {
+        "fused_loss_forward": lambda: lib.splat_image_loss(cx.ctx, rgb.data_ptr(), 4, target.data_ptr(), 3, w, h, 0.2, ws.data_ptr(), nbytes,
+                                                           out4.data_ptr()),
+        "fused_loss_backward": lambda: lib.splat_image_loss_backward(cx.ctx, rgb.data_ptr(), 4, target.data_ptr(), 3, w, h, 0.2, ws.data_ptr(),
+                                                                     nbytes, up.data_ptr(), grad.data_ptr(), 3),
+        "torch_loss_forward": torch_forward,
+        "torch_loss_backward": None,  # (a forward, then its backward alone)
+        "frame_fused": frame_with(AG.photometric_loss),
+        "frame_torch": frame_with(torch_loss),
+    }
+
+    def run(kind, calls):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        if kind == "torch_loss_backward":
+            tot = 0.0
+            for _ in range(calls):
+                torch_forward()
+                x.grad = None
+                e0.record(stream)
+                state["loss"].backward()
+                e1.record(stream)
+                e1.synchronize()
+                tot += e0.elapsed_time(e1)
+            return tot / calls
+        e0.record(stream)
+        for _ in range(calls):
+            work[kind]()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / calls
+
+    for kind in list(work) * 2:
+        run(kind, 3)
+    ts = {kind: [] for kind in work}
+    for _ in range(rounds):
+        for kind in work:
+            ts[kind].append(run(kind, k))
+    med = {kind: sorted(v)[len(v) // 2] for kind, v in ts.items()}
+    fwd_bytes, bwd_bytes = (16 + 12 + 36) * w * h, (16 + 12 + 36 + 12) * w * h
+    fused, torch_ms = med["fused_loss_forward"] + med["fused_loss_backward"], med["torch_loss_forward"] + med["torch_loss_backward"]
+    print(json.dumps({"config": name, "n": n, "width": w, "height": h, "calls_per_round": k, "rounds": rounds,
+                      **{f"{kind}_ms": round(v, 4) for kind, v in med.items()},
+                      **{f"{kind}_ms_min_max": [round(min(v), 4), round(max(v), 4)] for kind, v in ts.items()},
+                      "fused_loss_ms": round(fused, 4), "torch_loss_ms": round(torch_ms, 4), "torch_over_fused": round(torch_ms / fused, 2),
+                      "frame_torch_over_frame_fused": round(med["frame_torch"] / med["frame_fused"], 3),
+                      "fused_forward_bytes": fwd_bytes, "fused_forward_floor_ms": round(fwd_bytes / COPY_RATE * 1e3, 4),
+                      "fused_forward_over_floor": round(med["fused_loss_forward"] / (fwd_bytes / COPY_RATE * 1e3), 2),
+                      "fused_backward_bytes": bwd_bytes, "fused_backward_floor_ms": round(bwd_bytes / COPY_RATE * 1e3, 4),
+                      "fused_backward_over_floor": round(med["fused_loss_backward"] / (bwd_bytes / COPY_RATE * 1e3), 2)}), flush=True)
 
 
 def torch_records(U, pos, scl, rot, W, H):
@@ -114,6 +229,10 @@ names = argv[0].split(",") if len(argv) > 0 else ["C1", "C2"]
 k = int(argv[1]) if len(argv) > 1 else 20
 rounds = int(argv[2]) if len(argv) > 2 else 7
 stream = torch.cuda.current_stream()
+if loss_only:
+    for name in names:
+        loss_bench(name, k, rounds, stream)
+    names = []
 for name in names:
     n, w, h = sr.scene.CONFIGS[name]
     props, _ = sr.scene.make_scene(n)
