@@ -440,7 +440,10 @@ int splat_project_ellipsoid(splat_ctx *ctx, const float *uniforms, const void *p
                             uint32_t n, void *projected, void *records, void *keys, void *payload, uint32_t n_padded);
 /* View-dependent colour from spherical harmonics of degree 0-3 (the real basis and constants of 3D Gaussian splatting):
  * color_opacity_out[i] = vec4(max(0.5 + sum_k Y_k(dir) sh_k, 0), opacity_f32[i]), dir = normalize(p_i - eye), with the
- * coefficient of basis k < (degree + 1)^2 and channel c at sh[i * sh_stride_floats + 3 k + c].  eye3 is a host pointer. */
+ * coefficient of basis k < (degree + 1)^2 and channel c at sh[i * sh_stride_floats + 3 k + c].  eye3 is a host pointer.
+ * Where |p_i - eye| (binary32) is not a positive finite number - a splat at the eye - dir = (0, 0, 0): the colour is
+ * max(0.5 + C0 sh_0, 0), finite.  Its backward then writes C0 g into row 0 of dL/dsh and zeros into the other rows, zeros into
+ * dL/dposition, adds nothing to dL/deye, and passes dL/dopacity through as for any splat. */
 int splat_sh_colors(splat_ctx *ctx, const float *eye3, const void *positions, uint32_t pos_stride_vec4, const void *sh,
                     uint32_t sh_stride_floats, uint32_t degree, const void *opacity_f32, uint32_t n, void *color_opacity_out);
 /* The whole frame of anisotropic Gaussians: splat_render_frame_planes_aov with cfg->footprint = SPLAT_FOOTPRINT_ELLIPSOID,

@@ -557,8 +557,11 @@ __global__ __launch_bounds__(256) void k_sh_colors_backward(float ex, float ey, 
         const float4 gc = gcol[i];
         float vx = p.x - ex, vy = p.y - ey, vz = p.z - ez;
         const float len = sqrtf((vx * vx + vy * vy) + vz * vz);
-        const float il = 1.0f / len;
-        const float x = vx * il, y = vy * il, z = vz * il;
+        // the forward's rule: no direction where |p - eye| is not a positive finite number (a splat at the eye).  Then Y_0 alone
+        // is non-zero, and il = 0 makes grad_positions and the term of dL/deye zeros
+        const bool has_dir = len > 0.0f && len < INFINITY;
+        const float il = has_dir ? 1.0f / len : 0.0f;
+        const float x = has_dir ? vx * il : 0.0f, y = has_dir ? vy * il : 0.0f, z = has_dir ? vz * il : 0.0f;
         float Y[NB], Yx[NB], Yy[NB], Yz[NB];
         Y[0] = GSH_C0; Yx[0] = 0.0f; Yy[0] = 0.0f; Yz[0] = 0.0f;
         if (DEG > 0) {

@@ -2,6 +2,7 @@
 // real spherical harmonics of degree 0-3 in the basis and constants of 3D Gaussian splatting, evaluated towards the camera.
 //
 //   dir = normalize(p - eye),  rgb = max(0.5 + sum_k Y_k(dir) sh_k, 0),  w = opacity
+//   (dir = (0, 0, 0) where |p - eye| is not a positive finite number — a splat at the eye: rgb = max(0.5 + C0 sh_0, 0))
 //
 // Roofline: HBM.  Per splat 16 B of position + 12 (deg + 1)^2 B of coefficients + 4 B opacity in, 16 B out (degree 3: 228 B);
 // one lane per splat.  Coefficient rows whose stride and base allow it are read as float4s (the row's 48 floats at degree 3
@@ -36,8 +37,11 @@ __global__ __launch_bounds__(256) void k_sh_colors(float ex, float ey, float ez,
     const float4 p = pos[(size_t)i * pos_stride];
     const float op = opacity[i];
     float x = p.x - ex, y = p.y - ey, z = p.z - ez;
-    const float il = 1.0f / sqrtf((x * x + y * y) + z * z);
-    x *= il; y *= il; z *= il;
+    // a splat at the eye (or a length that is not a positive finite number) has no direction: (0, 0, 0), not 0 * inf
+    const float len = sqrtf((x * x + y * y) + z * z);
+    const bool has_dir = len > 0.0f && len < INFINITY;
+    const float il = has_dir ? 1.0f / len : 0.0f;
+    x = has_dir ? x * il : 0.0f; y = has_dir ? y * il : 0.0f; z = has_dir ? z * il : 0.0f;
     float Y[NB];
     Y[0] = SH_C0;
     if (DEG > 0) {

@@ -65,7 +65,10 @@ def sh_colors64(eye, pos, sh, degree, opacity, pass_mask):
     """GR.sh_colors64 with eye a (3,) float64 tensor: (n, 4), rgb = 0.5 + sum_k Y_k(normalize(p - eye)) sh_k where pass_mask
     (the binary32 forward did not clamp), 0 elsewhere; differentiable in eye, pos, sh, opacity."""
     d = pos[:, :3] - eye[None, :]
-    d = d / torch.sqrt((d * d).sum(dim=1, keepdim=True))
+    # no direction (the binary32 decision: a splat at the eye, a position that is not finite): (0, 0, 0), and no gradient through it
+    ok = torch.as_tensor(ER.has_direction(eye.detach().numpy(), pos.detach().numpy()))[:, None]
+    d = torch.where(ok, d, torch.ones_like(d))
+    d = torch.where(ok, d / torch.sqrt((d * d).sum(dim=1, keepdim=True)), torch.zeros_like(d))
     x, y, z = d[:, 0], d[:, 1], d[:, 2]
     Y = [torch.full_like(x, ER.SH_C0)]
     if degree > 0:

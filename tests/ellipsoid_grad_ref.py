@@ -80,7 +80,10 @@ def sh_colors64(eye, pos, sh, degree, opacity, pass_mask):
     """(n, 4) float64: rgb = 0.5 + sum_k Y_k(dir) sh_k where pass_mask (the binary32 forward did not clamp), 0 elsewhere."""
     e = torch.as_tensor(np.asarray(eye, np.float64)[:3])
     d = pos[:, :3] - e[None, :]
-    d = d / torch.sqrt((d * d).sum(dim=1, keepdim=True))
+    # no direction (the binary32 decision: a splat at the eye, a position that is not finite): (0, 0, 0), and no gradient through it
+    ok = torch.as_tensor(ER.has_direction(eye, pos.detach().numpy()))[:, None]
+    d = torch.where(ok, d, torch.ones_like(d))
+    d = torch.where(ok, d / torch.sqrt((d * d).sum(dim=1, keepdim=True)), torch.zeros_like(d))
     x, y, z = d[:, 0], d[:, 1], d[:, 2]
     Y = [torch.full_like(x, ER.SH_C0)]
     if degree > 0:

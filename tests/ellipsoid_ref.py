@@ -103,11 +103,24 @@ def sh_basis(d, degree, dtype=np.float64):
     return np.stack(Y, axis=1)
 
 
+def has_direction(eye, pos):
+    """(n,) bool, the kernels' binary32 decision: |p - eye| is a positive finite number.  Where it is not (a splat at the eye,
+    a position that is not finite), the direction is (0, 0, 0)."""
+    p = np.asarray(pos, F)[:, :3]
+    e = np.asarray(eye, F).reshape(-1)[:3]
+    with np.errstate(all="ignore"):
+        x, y, z = p[:, 0] - e[0], p[:, 1] - e[1], p[:, 2] - e[2]
+        ln = np.sqrt((x * x + y * y) + z * z)
+        return (ln > 0) & (ln < np.inf)
+
+
 def sh_colors(eye, pos, sh, degree, opacity, dtype=np.float64):
-    """(n, 4): max(0.5 + sum_k Y_k(normalize(p - eye)) sh_k, 0), opacity.  sh: (n, K, 3) basis-major."""
+    """(n, 4): max(0.5 + sum_k Y_k(normalize(p - eye)) sh_k, 0), opacity.  sh: (n, K, 3) basis-major.  A splat without a
+    direction (has_direction) takes (0, 0, 0) for it: max(0.5 + C0 sh_0, 0)."""
     p = np.asarray(pos, dtype)[:, :3]
-    d = p - np.asarray(eye, dtype)[None, :3]
-    d = d / np.sqrt((d * d).sum(axis=1, keepdims=True))
+    ok = has_direction(eye, pos)[:, None]
+    d = np.where(ok, p - np.asarray(eye, dtype)[None, :3], dtype(1))
+    d = np.where(ok, d / np.sqrt((d * d).sum(axis=1, keepdims=True)), dtype(0))
     nb = (degree + 1) ** 2
     Y = sh_basis(d, degree, dtype)
     coef = np.asarray(sh, dtype).reshape(p.shape[0], -1, 3)[:, :nb, :]

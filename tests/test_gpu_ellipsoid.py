@@ -76,8 +76,15 @@ def check_image8(got8, ref, what):
 def test_projector_bit_exact(device, n, w, h, seed, spread, scale):
     pos, scl, rot, col = ER.make_cloud(n, seed, spread, scale)
     u = camera_u(w, h)
-    rec, proj, keys = ER.project(u, pos, scl, rot)
+    rec, _, _ = ER.project(u, pos, scl, rot)
     assert (rec[:8] == 0).all(axis=1)[[2, 3, 4, 5]].all() and (rec != 0).any(axis=1).sum() > n // 2
+    projector_bit_exact(device, u, pos, scl, rot, col)
+
+
+def projector_bit_exact(device, u, pos, scl, rot, col):
+    """splat_project_ellipsoid under the uniform block u against ER.project, bit for bit; returns the restated records."""
+    n = pos.shape[0]
+    rec, proj, keys = ER.project(u, pos, scl, rot)
     cloud = cloud_of(device, pos, scl, rot, col)
     p = sr.SplatProjector(device, n, footprint="ellipsoid")
     sorter = sr.RadixSorter(device, n)
@@ -96,6 +103,7 @@ def test_projector_bit_exact(device, n, w, h, seed, spread, scale):
     assert_same(bits(p.getDiscBuffer().read(np.float32, n * 8)), bits(rec).reshape(-1), f"records -2q {n}")
     for o in (p, sorter, cloud, cloud2):
         o.destroy()
+    return rec
 
 
 @pytest.mark.parametrize("degree", [0, 1, 2, 3])
@@ -208,9 +216,13 @@ FRAMES = [  # frame order, records, write projected, tile, w, h
 
 @pytest.mark.parametrize("order,records,write,tile,w,h", FRAMES)
 def test_whole_frames(device, order, records, write, tile, w, h):
-    n = 6000
-    pos, scl, rot, col = ER.make_cloud(n, 11, 1.0, 0.03)
-    u = camera_u(w, h)
+    pos, scl, rot, col = ER.make_cloud(6000, 11, 1.0, 0.03)
+    whole_frame(device, camera_u(w, h), pos, scl, rot, col, order, records, write, tile, w, h)
+
+
+def whole_frame(device, u, pos, scl, rot, col, order, records, write, tile, w, h):
+    """One Renderer(footprint="ellipsoid") frame under the uniform block u against the restated frame; returns the restatement."""
+    n = pos.shape[0]
     ref = restated(u, pos, scl, rot, col, w, h, tile, early_out=True)
     cloud = cloud_of(device, pos, scl, rot, col)
     r = sr.Renderer(device, None, "rgba8unorm", n, tileSize=tile, frameOrder=order, footprint="ellipsoid", writeProjected=write,
@@ -232,6 +244,7 @@ def test_whole_frames(device, order, records, write, tile, w, h):
         with pytest.raises(sr.SplatError):
             r.render(u, cloud, None, None, w, h, wantAov=True)
     cloud.destroy()
+    return ref
 
 
 def test_sh_frame_and_frames_alternate(device):

@@ -198,12 +198,21 @@ def test_sh_backward_camera(device, degree, n):
 # ---- end to end ----------------------------------------------------------------------------------------------------------------
 def _reference_chain_camera(u, pos, scl, rot, op, sh, degree, w, h, g, gd):
     """TD._reference_chain_depth extended to the camera: dL/du (22,) float64."""
+    U = CR.utensor(u)
+    P, S, Q, OP, SH = (torch.as_tensor(a.astype(np.float64)) for a in (pos, scl, rot, op, sh))
+    _reference_chain_camera_loss(u, U, P, S, Q, OP, SH, degree, w, h, g, gd).backward()
+    return U.grad.numpy()
+
+
+def _reference_chain_camera_loss(u, U, P, S, Q, OP, SH, degree, w, h, g, gd):
+    """The float64 chain's loss as a function of the block U (a (22,) float64 tensor, a leaf or the result of a graph) and of
+    the splats' float64 tensors, any of which may require grad; every decision comes from the binary32 pass under the binary32
+    block u."""
+    pos, scl, rot, op, sh = (a.detach().numpy().astype(np.float32) for a in (P, S, Q, OP, SH))
     rec32, counts, offsets, idx = TG.lists(u, pos, scl, rot, w, h)
     col32 = ER.sh_colors(u[16:19], pos, sh, degree, op, dtype=np.float32).astype(np.float32)
     dec = GR.decisions(rec32, col32, idx, counts, offsets, w, h)
     passed = col32[:, :3] > 0
-    U = CR.utensor(u)
-    P, S, Q, OP, SH = (torch.as_tensor(a.astype(np.float64)) for a in (pos, scl, rot, op, sh))
     rec = CR.records64(U, GR._v(P, 4, 1.0), GR._v(S), Q, ~GR.culled(u, pos, scl, rot))
     col = CR.sh_colors64(U[16:19], P, SH, degree, OP, passed)
     z = CR.depth64(U, P)
@@ -212,8 +221,7 @@ def _reference_chain_camera(u, pos, scl, rot, op, sh, degree, w, h, g, gd):
     gdt = torch.as_tensor(gd.astype(np.float64).reshape(-1))
     some = ws > 0
     Dz = torch.where(some, D, torch.zeros_like(D))
-    ((rgb * gt[:, :3]).sum() + (alpha * gt[:, 3]).sum() + (Dz * torch.where(some, gdt, torch.zeros_like(gdt))).sum()).backward()
-    return U.grad.numpy()
+    return (rgb * gt[:, :3]).sum() + (alpha * gt[:, 3]).sum() + (Dz * torch.where(some, gdt, torch.zeros_like(gdt))).sum()
 
 
 @pytest.mark.parametrize("where,dtype", [("cuda", torch.float32), ("cpu", torch.float64)])
