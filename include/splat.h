@@ -595,6 +595,82 @@ int splat_image_loss_backward(splat_ctx *ctx, const void *image, uint32_t image_
                               uint32_t width, uint32_t height, float lambda, const void *workspace, uint64_t workspace_bytes,
                               const void *upstream, void *grad_image, uint32_t grad_stride);
 
+/* ---- Density control and optimiser: what fitting a cloud of 3D Gaussians needs beside the frame (an extension) --------------
+ * The parameters are 3DGS's raw ones, contiguous float32 DEVICE planes: means (n, 3), log_scales (n, 3), rotations (n, 4) as
+ * (w, x, y, z), unnormalised, opacity_logits (n), sh (n, 3 K) basis-major as splat_sh_colors takes it.  The activations
+ * (scale = exp, opacity = sigmoid) are the caller's.  Everything here goes to the ctx's stream; only splat_densify_plan waits
+ * on the host.  No kernel uses atomics: the same inputs give the same bits.
+ *
+ * splat_adam_step: one fused Adam update (torch's, without amsgrad or weight decay) of ONE plane of rows x floats_per_row
+ * floats, per element
+ *   m = beta1 m + (1 - beta1) g,   v = beta2 v + (1 - beta2) g^2,   p -= step m / (sqrt(v) inv_sqrt_bc2 + eps),
+ * where the caller computes step = lr / (1 - beta1^t) and inv_sqrt_bc2 = 1 / sqrt(1 - beta2^t) for its step count t.  The
+ * hyperparameters cross as doubles and are rounded to binary32 once (1 - beta is formed in double first); the arithmetic is
+ * binary32.  Columns < head_floats of a row use step_head, the others step_tail (the SH plane's two learning rates, DC and
+ * rest, without splitting the tensor); pass head_floats = floats_per_row for one rate.  visible_u8 (`rows` bytes, or NULL): a
+ * row whose byte is 0 keeps param, m and v bit for bit and its state is not loaded; the other rows get the bits the unmasked
+ * call gives them.  Planes that are all 16-byte aligned are moved with 16-byte loads and stores, others (4-byte aligned) with
+ * scalar ones; both give the same bits.  rows = 0: success, nothing launched.  SPLAT_ERR_INVALID: a NULL or misaligned plane,
+ * floats_per_row = 0, head_floats > floats_per_row, rows x floats_per_row above 2^32 - 257, a beta outside [0, 1). */
+int splat_adam_step(splat_ctx *ctx, void *param, const void *grad, void *m, void *v, uint32_t rows, uint32_t floats_per_row,
+                    uint32_t head_floats, double step_head, double step_tail, double beta1, double beta2, double inv_sqrt_bc2,
+                    double eps, const void *visible_u8);
+/* splat_density_accumulate: one frame's statistics.  records: the forward's n x 8 floats {c.x, c.y, B00, B01, 0, B11, 0, 0}
+ * (splat_project_ellipsoid); grad_records: dL/drecords, n x 8 floats of which [0], [1] are read (both 16-byte aligned).  Splat i
+ * is VISIBLE when its record is not the culled all-zero record and its 3-sigma box c -/+ (hx, hy) overlaps the screen:
+ *   hx = sqrt(B01^2 + B11^2) / (B00 B11),  hy = 1 / B11   (disc_bounds()'s half-widths),
+ *   c.x + hx > 0, c.x - hx < W, c.y + hy > 0, c.y - hy < H,
+ * evaluated in binary32, one rounding per operation as written.  A visible splat gets
+ *   grad_accum[i] += hypot(g.x W / 2, g.y H / 2)   (3DGS's NDC scaling: its 2e-4 threshold carries over),
+ *   denom[i] += 1,   max_radius[i] = max(max_radius[i], max(hx, hy));
+ * an invisible one keeps all three.  visible_u8[i] is WRITTEN 1 or 0 for every splat: this frame's mask, the one
+ * splat_adam_step takes.  grad_accum, denom, max_radius: n floats each, zeroed by the caller before the first frame. */
+int splat_density_accumulate(splat_ctx *ctx, const void *records, const void *grad_records, uint32_t n, uint32_t width,
+                             uint32_t height, void *grad_accum, void *denom, void *max_radius, void *visible_u8);
+/* splat_densify_plan: decide, count and lay out the next cloud.  Per splat, in binary32:
+ *   g = denom > 0 ? grad_accum / denom : 0,  s = exp(max log-scale) (NaN if any is),  o = sigmoid(logit),  r = max_radius;
+ *   DEAD       when !(o >= min_opacity), or max_screen_radius > 0 && r > max_screen_radius, or max_world_scale > 0 &&
+ *              !(s <= max_world_scale): no rows, never densified (a NaN logit or scale is dead, where that rule is on);
+ *   WANTS MORE otherwise when g >= grad_threshold (false for a NaN): SPLIT when s > scale_threshold (two new rows, the parent
+ *              dropped), else CLONE (the parent and one copy);
+ *   the cap    a clone and a split each add one row.  With max_splats > 0 they are granted in index order while
+ *              survivors + extras granted so far < max_splats; a refused splat is kept as it is.  So the output never exceeds
+ *              max_splats when the survivors alone fit, and is the survivors otherwise.
+ * rows (DEVICE, room for 2 n uint32) receives one word per output row, parent index in bits 0-29, kind in bits 30-31: 0 a kept
+ * original, 1 a clone's copy, 2 and 3 the children of a split; rows are in parent order, a clone's original before its copy.
+ * *n_out_host and counts4_host = {pruned, kept, cloned, split} (splats, not rows: n_out = kept + 2 cloned + 2 split) are HOST
+ * words: THIS CALL SYNCHRONISES THE STREAM ONCE to fill them (it runs every hundred steps or so).  workspace: DEVICE, 16-byte
+ * aligned, at least splat_densify_plan_workspace_bytes(n).  The scans are splat_scan_u32's kernels.  n = 0: zeros, nothing
+ * launched.  SPLAT_ERR_INVALID: n >= 2^30, a NULL or misaligned pointer, a workspace that is too small. */
+typedef struct splat_densify_cfg {
+    float grad_threshold, scale_threshold, min_opacity;
+    float max_screen_radius; /* 0 = off */
+    float max_world_scale;   /* 0 = off */
+    uint32_t max_splats;     /* 0 = no cap */
+    uint64_t seed;           /* read by splat_densify_geometry */
+} splat_densify_cfg;
+uint64_t splat_densify_plan_workspace_bytes(uint32_t n);
+int splat_densify_plan(splat_ctx *ctx, const void *log_scales, const void *opacity_logits, const void *grad_accum, const void *denom,
+                       const void *max_radius, uint32_t n, const splat_densify_cfg *cfg, void *workspace, uint64_t workspace_bytes,
+                       void *rows, uint32_t *n_out_host, uint32_t *counts4_host);
+/* Apply a plan: gathers over OUTPUT rows (contiguous writes); `rows` and n_out are splat_densify_plan's, the input planes the
+ * ones it planned for (a row's parent index is not checked against them).  Outputs must not alias inputs.
+ * splat_densify_geometry writes means_out and log_scales_out (n_out x 3 floats): kinds 0 and 1 copy their parent's; child
+ * k = kind - 2 of a split gets log sigma - log 1.6 (rounded once) and mu + R(q) (sigma (.) xi_k), R the rotation matrix of the
+ * normalised quaternion as csrc/ellipsoid.h forms it, sigma = exp(log_scales), xi_k a standard normal 3-vector from
+ * Philox4x32-10 with key (seed low word, seed high word) and counter (parent, k, 0, 0): with its four words x_j,
+ *   u_j = (x_j + 0.5) 2^-32,  xi = (sqrt(-2 ln u0) cos 2 pi u1, sqrt(-2 ln u0) sin 2 pi u1, sqrt(-2 ln u2) cos 2 pi u3).
+ * The same seed gives the same cloud.  rotations: 16-byte aligned.
+ * splat_densify_rows moves any other plane of floats_per_row floats per splat: SPLAT_DENSIFY_COPY gives every row its parent's
+ * (parameters); SPLAT_DENSIFY_ZERO_NEW copies for kind 0 and writes zeros for kinds 1-3 (Adam's moments: as in 3DGS, kept
+ * splats keep theirs and new ones start at zero).  n_out x floats_per_row must not exceed 2^32 - 257. */
+#define SPLAT_DENSIFY_COPY 0
+#define SPLAT_DENSIFY_ZERO_NEW 1
+int splat_densify_geometry(splat_ctx *ctx, const void *rows, uint32_t n_out, const void *means, const void *log_scales,
+                           const void *rotations, const splat_densify_cfg *cfg, void *means_out, void *log_scales_out);
+int splat_densify_rows(splat_ctx *ctx, const void *rows, uint32_t n_out, const void *in, void *out, uint32_t floats_per_row,
+                       uint32_t mode);
+
 /* ---- multi-GPU band path (no reference equivalent — the reference is single-device) */
 /* The oriented-disc projector (src/SequentialRenderer.ts:68-71,91-112): the splat is the disc
  * p + r*(t*u + b*v), u^2+v^2 <= 1, in the tangent plane of its normal (t = normalize(cross(up, n)), b =

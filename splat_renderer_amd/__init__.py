@@ -13,5 +13,6 @@ from .host import (Buffer, CommandEncoder, ComputeShaderRenderer, DepthKeyExtrac
                    SplatProjector, SplatPropertyManager, TileRenderer)
 from .frameloop import FrameLoop, MouseEvent, OrbitCameraController, SdfSplatSource, read_png, write_png  # noqa: F401
 from . import sdf  # noqa: F401
-from .ply import load_gaussian_ply  # noqa: F401
+from .ply import load_gaussian_ply, save_gaussian_ply  # noqa: F401
+from .fit import GaussianFit  # noqa: F401
 from .sdf import CurvatureSampler, GradientSampler, PositionUpdater, SDFScene  # noqa: F401

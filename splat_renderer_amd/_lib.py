@@ -50,9 +50,17 @@ class CompositeCfg(C.Structure):
                 ("prelit", C.c_uint32), ("footprint", C.c_uint32)]
 
 
+class DensifyCfg(C.Structure):
+    """splat_densify_cfg: the thresholds of splat_densify_plan and the seed of splat_densify_geometry."""
+    _fields_ = [("grad_threshold", C.c_float), ("scale_threshold", C.c_float), ("min_opacity", C.c_float),
+                ("max_screen_radius", C.c_float), ("max_world_scale", C.c_float), ("max_splats", C.c_uint32), ("seed", C.c_uint64)]
+
+
+DENSIFY_COPY, DENSIFY_ZERO_NEW = 0, 1
+
 # name -> (restype, argtypes); the single source of truth checked against include/splat.h by
 # tests/test_abi_cpu.py
-_vp, _u32, _sz, _i = C.c_void_p, C.c_uint32, C.c_size_t, C.c_int
+_vp, _u32, _sz, _i, _f64 = C.c_void_p, C.c_uint32, C.c_size_t, C.c_int, C.c_double
 _pvp = C.POINTER(C.c_void_p)
 SIGNATURES = {
     "splat_abi_version": (_i, []),
@@ -97,6 +105,13 @@ SIGNATURES = {
     "splat_image_loss_workspace_bytes": (C.c_uint64, [_u32, _u32]),
     "splat_image_loss": (_i, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, C.c_float, _vp, C.c_uint64, _vp]),
     "splat_image_loss_backward": (_i, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, C.c_float, _vp, C.c_uint64, _vp, _vp, _u32]),
+    "splat_adam_step": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _f64, _f64, _f64, _f64, _f64, _f64, _vp]),
+    "splat_density_accumulate": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "splat_densify_plan_workspace_bytes": (C.c_uint64, [_u32]),
+    "splat_densify_plan": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, C.POINTER(DensifyCfg), _vp, C.c_uint64, _vp, C.POINTER(_u32),
+                                C.POINTER(_u32)]),
+    "splat_densify_geometry": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, C.POINTER(DensifyCfg), _vp, _vp]),
+    "splat_densify_rows": (_i, [_vp, _vp, _u32, _vp, _vp, _u32, _u32]),
     "splat_extract_keys":(_i, [_vp, _vp, _u32, _u32, _vp, _vp]),
     "splat_sort_create": (_i, [_vp, _u32, _pvp]),
     "splat_sort_destroy": (None, [_vp]),

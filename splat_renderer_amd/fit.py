@@ -1,0 +1,185 @@
+"""Fitting a cloud of anisotropic 3D Gaussians to images (footprint="ellipsoid"; an extension, no reference counterpart): the
+parameters, a fused Adam step whose state survives a change of the splat count, and 3DGS's adaptive density control.
+
+    fit = GaussianFit(means, scales, rotations, opacity, sh)           # activated values, as load_gaussian_ply returns them
+    for step in range(steps):
+        rgb, alpha = fit.render(camera_or_uniforms, width, height)
+        photometric_loss(rgb, target).backward()
+        fit.step()                                                      # statistics of this frame, Adam, gradients zeroed
+        if step % 100 == 99:
+            counts = fit.densify_and_prune(max_splats=...)              # {"pruned", "kept", "cloned", "split", "n"}
+    fit.save_ply(path)
+
+GaussianFit holds 3DGS's raw parameters as contiguous float32 CUDA leaves that require grad: means (n, 3), log_scales (n, 3),
+rotations (n, 4) as (w, x, y, z), unnormalised, opacity_logits (n,), sh (n, 3 K) basis-major; beside each its two Adam
+moments, and the three statistics planes of density control (grad_accum, denom, max_radius).  render() applies the
+activations in torch (exp, sigmoid) and calls autograd's project_ellipsoids, sh_colors and rasterize, so everything of
+splat_renderer_amd.autograd holds for its results; it keeps the records and retains their gradient, which step() hands to
+splat_density_accumulate.  step() is five splat_adam_step launches (include/splat.h, "Density control and optimiser"), with
+sparse=True (the default) masked by that frame's visibility: a splat the frame did not see keeps its parameters and moments,
+as in the "sparse Adam" of the faster 3DGS trainers (its gradient is exactly zero; a dense Adam would still let its momentum
+move it).  densify_and_prune() is splat_densify_plan, splat_densify_geometry and splat_densify_rows: it replaces the tensors
+(callers must not hold on to the old ones), moves the moments with them (new splats start at zero) and resets the statistics.
+Every kernel runs on torch's current stream; only densify_and_prune waits on the host (once, for the new count).
+"""
+import ctypes as C
+import math
+
+from . import _lib
+from . import autograd as AG
+from ._lib import SplatError, check
+
+# 3DGS's learning rates: position (its initial rate; callers schedule it through step(lr=...)), scaling, rotation, opacity,
+# SH DC, SH rest (DC / 20)
+DEFAULT_LR = {"means": 1.6e-4, "log_scales": 5e-3, "rotations": 1e-3, "opacity_logits": 5e-2, "sh": 2.5e-3, "sh_rest": 1.25e-4}
+PLANES = ("means", "log_scales", "rotations", "opacity_logits", "sh")
+
+
+class GaussianFit:
+    def __init__(self, means, scales, rotations, opacity, sh, degree=None, lr=None, betas=(0.9, 0.999), eps=1e-15, sparse=True,
+                 device="cuda"):
+        """means (n, 3), scales (n, 3) > 0, rotations (n, 4), opacity (n,) in (0, 1), sh (n, K, 3) or (n, 3 K), K = (degree +
+        1)^2: arrays or tensors of activated values.  lr: a dict that overrides entries of DEFAULT_LR."""
+        torch = AG._t()
+        t = lambda a: torch.as_tensor(a, dtype=torch.float32).to(device).detach()  # noqa: E731
+        means, scales, rotations, opacity, sh = t(means), t(scales), t(rotations), t(opacity).reshape(-1), t(sh)
+        n = means.shape[0]
+        sh = sh.reshape(n, -1)
+        k = sh.shape[1] // 3
+        self.degree = {1: 0, 4: 1, 9: 2, 16: 3}.get(k) if degree is None else int(degree)
+        if self.degree is None or sh.shape[1] != 3 * (self.degree + 1) ** 2:
+            raise SplatError(-1, f"sh must hold 3 (degree + 1)^2 floats per splat, degree 0-3, not {sh.shape[1]}")
+        if means.shape != (n, 3) or scales.shape != (n, 3) or rotations.shape != (n, 4) or opacity.shape != (n,):
+            raise SplatError(-1, "means (n, 3), scales (n, 3), rotations (n, 4) and opacity (n,) are expected")
+        self.lr = dict(DEFAULT_LR, **(lr or {}))
+        self.betas, self.eps, self.sparse = (float(betas[0]), float(betas[1])), float(eps), bool(sparse)
+        self.steps = 0
+        self.densifications = 0
+        self._set(means[:, :3].clone(), torch.log(scales), rotations.clone(), torch.logit(opacity), sh.clone())
+        self.m = {k: torch.zeros_like(getattr(self, k)) for k in PLANES}
+        self.v = {k: torch.zeros_like(getattr(self, k)) for k in PLANES}
+        self._reset_statistics()
+        # 3DGS's percent_dense x scene extent: the default scale_threshold of densify_and_prune
+        centre = means.mean(dim=0, keepdim=True) if n else means
+        self.extent = float(1.1 * (means - centre).norm(dim=1).max()) if n else 1.0
+        self._frame = None
+
+    def _set(self, *tensors):
+        for name, value in zip(PLANES, tensors):
+            setattr(self, name, value.contiguous().requires_grad_())
+
+    def _reset_statistics(self):
+        torch = AG._t()
+        dev = self.means.device
+        self.grad_accum, self.denom, self.max_radius = (torch.zeros(self.n, device=dev, dtype=torch.float32) for _ in range(3))
+        self.visible = torch.zeros(self.n, device=dev, dtype=torch.uint8)
+
+    @property
+    def n(self):
+        return self.means.shape[0]
+
+    def parameters(self):
+        return [getattr(self, k) for k in PLANES]
+
+    def render(self, camera_or_uniforms, width, height, return_depth=False):
+        """(rgb (H, W, 3), alpha (H, W)), or with return_depth (rgb, alpha, depth): autograd.render_gaussians of the activated
+        parameters.  The frame's records are kept for the next step()."""
+        torch = AG._t()
+        u = AG._uniforms(camera_or_uniforms, width, height)
+        scales, opacity = torch.exp(self.log_scales), torch.sigmoid(self.opacity_logits)
+        if return_depth:
+            rec, depths, aux = AG.project_ellipsoids(u, self.means, scales, self.rotations, return_depth=True)
+        else:
+            rec, aux = AG.project_ellipsoids(u, self.means, scales, self.rotations)
+            depths = None
+        col = AG.sh_colors(u[16:19], self.means, self.sh, self.degree, opacity)
+        if rec.requires_grad:
+            rec.retain_grad()
+        self._frame = (rec, int(width), int(height))
+        return AG.rasterize(rec, col, aux, width, height, depths=depths)
+
+    def step(self, lr=None):
+        """One optimiser step after backward(): this frame's density statistics and visibility mask, five Adam launches, the
+        gradients zeroed.  lr: a dict that overrides per-plane rates for this step (e.g. {"means": scheduled_rate})."""
+        if self._frame is None or self._frame[0].grad is None:
+            raise SplatError(-5, "GaussianFit.step: call render() and backward() first")
+        rec, width, height = self._frame
+        n = self.n
+        cx = AG._context(self.means)
+        lib = cx.lib
+        grec = AG._cuda_f32(rec.grad, "grad_records", 8)
+        check(lib.splat_density_accumulate(cx.ctx, rec.data_ptr(), grec.data_ptr(), n, width, height, self.grad_accum.data_ptr(),
+                                           self.denom.data_ptr(), self.max_radius.data_ptr(), self.visible.data_ptr()), cx.ctx)
+        self.steps += 1
+        rates = dict(self.lr, **(lr or {}))
+        b1, b2 = self.betas
+        bc1, isbc2 = 1.0 - b1 ** self.steps, 1.0 / math.sqrt(1.0 - b2 ** self.steps)
+        mask = self.visible.data_ptr() if self.sparse and n else None
+        for name in PLANES:
+            p = getattr(self, name)
+            if p.grad is None:  # (a plane the loss does not reach)
+                continue
+            g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+            fpr = p.shape[1] if p.dim() == 2 else 1
+            head, tail = rates[name] / bc1, rates["sh_rest" if name == "sh" else name] / bc1
+            check(lib.splat_adam_step(cx.ctx, p.data_ptr(), g.data_ptr(), self.m[name].data_ptr(), self.v[name].data_ptr(), n, fpr,
+                                      3 if name == "sh" else fpr, head, tail, b1, b2, isbc2, self.eps, mask), cx.ctx)
+            p.grad = None
+        self._frame = None
+
+    def densify_and_prune(self, grad_threshold=2e-4, scale_threshold=None, min_opacity=0.005, max_screen_radius=0.0, max_world_scale=0.0,
+                          max_splats=0, seed=None):
+        """Clone the under-reconstructed splats, split the over-large ones, prune the transparent ones (the rules: include/splat.h,
+        splat_densify_plan), from the statistics accumulated since the last call.  scale_threshold defaults to 0.01 x the extent
+        of the initial cloud; seed to the number of earlier calls.  Returns {"pruned", "kept", "cloned", "split", "n"}."""
+        torch = AG._t()
+        n = self.n
+        cx = AG._context(self.means)
+        lib = cx.lib
+        dev = self.means.device
+        cfg = _lib.DensifyCfg(float(grad_threshold), float(0.01 * self.extent if scale_threshold is None else scale_threshold),
+                              float(min_opacity), float(max_screen_radius), float(max_world_scale), int(max_splats),
+                              int(self.densifications if seed is None else seed) & 0xFFFFFFFFFFFFFFFF)
+        self.densifications += 1
+        nbytes = int(lib.splat_densify_plan_workspace_bytes(n))
+        ws = torch.empty(nbytes // 4, device=dev, dtype=torch.int32)
+        rows = torch.empty(max(2 * n, 1), device=dev, dtype=torch.int32)
+        n_out, counts = C.c_uint32(), (C.c_uint32 * 4)()
+        with torch.no_grad():
+            check(lib.splat_densify_plan(cx.ctx, self.log_scales.data_ptr(), self.opacity_logits.data_ptr(), self.grad_accum.data_ptr(),
+                                         self.denom.data_ptr(), self.max_radius.data_ptr(), n, C.byref(cfg), ws.data_ptr(), nbytes,
+                                         rows.data_ptr(), C.byref(n_out), counts), cx.ctx)
+            k = int(n_out.value)
+            new = {name: torch.empty((k,) + tuple(getattr(self, name).shape[1:]), device=dev, dtype=torch.float32) for name in PLANES}
+            check(lib.splat_densify_geometry(cx.ctx, rows.data_ptr(), k, self.means.data_ptr(), self.log_scales.data_ptr(),
+                                             self.rotations.data_ptr(), C.byref(cfg), new["means"].data_ptr(), new["log_scales"].data_ptr()),
+                  cx.ctx)
+
+            def move(src, mode):
+                out = torch.empty((k,) + tuple(src.shape[1:]), device=dev, dtype=torch.float32)
+                check(lib.splat_densify_rows(cx.ctx, rows.data_ptr(), k, src.data_ptr(), out.data_ptr(), src.shape[1] if src.dim() == 2 else 1,
+                                             mode), cx.ctx)
+                return out
+            for name in PLANES[2:]:
+                new[name] = move(getattr(self, name), _lib.DENSIFY_COPY)
+            self.m = {name: move(self.m[name], _lib.DENSIFY_ZERO_NEW) for name in PLANES}
+            self.v = {name: move(self.v[name], _lib.DENSIFY_ZERO_NEW) for name in PLANES}
+        self._set(*(new[name] for name in PLANES))
+        self._reset_statistics()
+        self._frame = None
+        return {"pruned": int(counts[0]), "kept": int(counts[1]), "cloned": int(counts[2]), "split": int(counts[3]), "n": k}
+
+    def reset_opacity(self, value=0.01):
+        """3DGS's opacity reset: no opacity above `value`, and the logits' moments zeroed."""
+        torch = AG._t()
+        with torch.no_grad():
+            self.opacity_logits.clamp_(max=math.log(value / (1.0 - value)))
+            self.m["opacity_logits"].zero_()
+            self.v["opacity_logits"].zero_()
+
+    def save_ply(self, path):
+        """The cloud as a 3D Gaussian splatting PLY file (ply.save_gaussian_ply): the raw parameters, bit for bit."""
+        from .ply import save_gaussian_ply
+        c = lambda t: t.detach().cpu().numpy()  # noqa: E731
+        save_gaussian_ply(path, c(self.means), None, c(self.rotations), None, c(self.sh).reshape(self.n, -1, 3), log_scales=c(self.log_scales),
+                          opacity_logits=c(self.opacity_logits))

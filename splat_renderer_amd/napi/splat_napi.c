@@ -445,6 +445,62 @@ FN(image_loss_backward) { /* image_loss's arguments up to workspaceBytes, then u
     void *up = arg_dptr(&c, 10), *g = arg_dptr(&c, 11); uint32_t gs = (uint32_t)arg_number(&c, 12); BAIL;
     return check(env, x, splat_image_loss_backward(x, img, is, tgt, ts, w, h, lambda, ws, wb, up, g, gs), mk_undefined(env));
 }
+/* splat_densify_cfg from [gradThreshold, scaleThreshold, minOpacity, maxScreenRadius, maxWorldScale, maxSplats, seed (integer < 2^53)] */
+static void fill_densify_cfg(call_t *c, size_t i, splat_densify_cfg *cfg) {
+    memset(cfg, 0, sizeof *cfg);
+    double v[7] = {0, 0, 0, 0, 0, 0, 0};
+    bool is = false;
+    napi_is_array(c->env, c->argv[i], &is);
+    if (!is) { c->failed = 1; napi_throw_type_error(c->env, NULL, "expected the densify config as an array of 7 numbers"); return; }
+    for (uint32_t k = 0; k < 7; ++k) {
+        napi_value e;
+        double d;
+        if (napi_get_element(c->env, c->argv[i], k, &e) == napi_ok && napi_get_value_double(c->env, e, &d) == napi_ok) v[k] = d;
+    }
+    cfg->grad_threshold = (float)v[0]; cfg->scale_threshold = (float)v[1]; cfg->min_opacity = (float)v[2];
+    cfg->max_screen_radius = (float)v[3]; cfg->max_world_scale = (float)v[4]; cfg->max_splats = (uint32_t)v[5]; cfg->seed = (uint64_t)v[6];
+}
+FN(adam_step) { /* (ctx, param, grad, m, v, rows, floatsPerRow, headFloats, stepHead, stepTail, beta1, beta2, invSqrtBc2, eps, visible|null) */
+    ARGS(15); splat_ctx *x = arg_external(&c, 0); void *p = arg_dptr(&c, 1), *g = arg_dptr(&c, 2), *m = arg_dptr(&c, 3), *v = arg_dptr(&c, 4);
+    uint32_t rows = (uint32_t)arg_number(&c, 5), fpr = (uint32_t)arg_number(&c, 6), head = (uint32_t)arg_number(&c, 7);
+    double sh = arg_number(&c, 8), st = arg_number(&c, 9), b1 = arg_number(&c, 10), b2 = arg_number(&c, 11), bc = arg_number(&c, 12);
+    double eps = arg_number(&c, 13); void *vis = arg_dptr(&c, 14); BAIL;
+    return check(env, x, splat_adam_step(x, p, g, m, v, rows, fpr, head, sh, st, b1, b2, bc, eps, vis), mk_undefined(env));
+}
+FN(density_accumulate) { /* (ctx, records, gradRecords, n, W, H, gradAccum, denom, maxRadius, visible) */
+    ARGS(10); splat_ctx *x = arg_external(&c, 0); void *rec = arg_dptr(&c, 1), *gr = arg_dptr(&c, 2);
+    uint32_t n = (uint32_t)arg_number(&c, 3), w = (uint32_t)arg_number(&c, 4), h = (uint32_t)arg_number(&c, 5);
+    void *ga = arg_dptr(&c, 6), *dn = arg_dptr(&c, 7), *mr = arg_dptr(&c, 8), *vis = arg_dptr(&c, 9); BAIL;
+    return check(env, x, splat_density_accumulate(x, rec, gr, n, w, h, ga, dn, mr, vis), mk_undefined(env));
+}
+FN(densify_plan_workspace_bytes) { /* (n) -> bytes */
+    ARGS(1); uint32_t n = (uint32_t)arg_number(&c, 0); BAIL;
+    return mk_number(env, (double)splat_densify_plan_workspace_bytes(n));
+}
+FN(densify_plan) { /* (ctx, logScales, opacityLogits, gradAccum, denom, maxRadius, n, cfg[7], workspace, workspaceBytes, rows) -> [nOut, pruned, kept, cloned, split] (waits) */
+    ARGS(11); splat_ctx *x = arg_external(&c, 0); void *ls = arg_dptr(&c, 1), *ol = arg_dptr(&c, 2), *ga = arg_dptr(&c, 3), *dn = arg_dptr(&c, 4);
+    void *mr = arg_dptr(&c, 5); uint32_t n = (uint32_t)arg_number(&c, 6); splat_densify_cfg cfg; fill_densify_cfg(&c, 7, &cfg);
+    void *ws = arg_dptr(&c, 8); uint64_t wb = (uint64_t)arg_number(&c, 9); void *rows = arg_dptr(&c, 10); BAIL;
+    uint32_t n_out = 0, counts[4] = {0, 0, 0, 0};
+    int rc = splat_densify_plan(x, ls, ol, ga, dn, mr, n, &cfg, ws, wb, rows, &n_out, counts);
+    if (rc != SPLAT_OK) return check(env, x, rc, NULL);
+    napi_value arr;
+    if (napi_create_array_with_length(env, 5, &arr) != napi_ok) return NULL;
+    napi_set_element(env, arr, 0, mk_number(env, n_out));
+    for (uint32_t k = 0; k < 4; ++k) napi_set_element(env, arr, k + 1, mk_number(env, counts[k]));
+    return arr;
+}
+FN(densify_geometry) { /* (ctx, rows, nOut, means, logScales, rotations, cfg[7], meansOut, logScalesOut) */
+    ARGS(9); splat_ctx *x = arg_external(&c, 0); void *rows = arg_dptr(&c, 1); uint32_t n = (uint32_t)arg_number(&c, 2);
+    void *mu = arg_dptr(&c, 3), *ls = arg_dptr(&c, 4), *rot = arg_dptr(&c, 5); splat_densify_cfg cfg; fill_densify_cfg(&c, 6, &cfg);
+    void *mo = arg_dptr(&c, 7), *lo = arg_dptr(&c, 8); BAIL;
+    return check(env, x, splat_densify_geometry(x, rows, n, mu, ls, rot, &cfg, mo, lo), mk_undefined(env));
+}
+FN(densify_rows) { /* (ctx, rows, nOut, in, out, floatsPerRow, mode: 0 copy, 1 zero the new rows) */
+    ARGS(7); splat_ctx *x = arg_external(&c, 0); void *rows = arg_dptr(&c, 1); uint32_t n = (uint32_t)arg_number(&c, 2);
+    void *in = arg_dptr(&c, 3), *out = arg_dptr(&c, 4); uint32_t fpr = (uint32_t)arg_number(&c, 5), mode = (uint32_t)arg_number(&c, 6); BAIL;
+    return check(env, x, splat_densify_rows(x, rows, n, in, out, fpr, mode), mk_undefined(env));
+}
 FN(render_frame_ellipsoids) { /* (ctx, sorter, binner, cfg[8], Float32Array(22), positions, scales, rotations, colorOpacity, n, W, H, projected|null, out8|null, outF|null, [depth, alpha, ids]|null) */
     ARGS(16); splat_ctx *x = arg_external(&c, 0); splat_sorter *s = arg_external(&c, 1); splat_binner *b = arg_external(&c, 2);
     splat_composite_cfg cfg; fill_cfg(&c, 3, &cfg); size_t ub = 0; float *u = arg_hostbuf(&c, 4, &ub);
@@ -711,6 +767,8 @@ static napi_value init(napi_env env, napi_value exports) {
         EXPORT(composite_aov_depth), EXPORT(composite_backward_depth), EXPORT(project_ellipsoid_backward_depth),
         EXPORT(project_ellipsoid_backward_camera), EXPORT(sh_colors_backward_camera),
         EXPORT(image_loss_workspace_bytes), EXPORT(image_loss), EXPORT(image_loss_backward),
+        EXPORT(adam_step), EXPORT(density_accumulate), EXPORT(densify_plan_workspace_bytes), EXPORT(densify_plan),
+        EXPORT(densify_geometry), EXPORT(densify_rows),
     };
     napi_define_properties(env, exports, sizeof d / sizeof d[0], d);
     return exports;

@@ -6,6 +6,9 @@ applies the activations the renderer expects: scale = exp(scale_k), opacity = si
 (w, x, y, z) = (rot_0, rot_1, rot_2, rot_3).  The file stores the higher SH coefficients channel-major (all of red, then
 green, then blue); they are returned basis-major, sh[i, k, c], with the DC term as k = 0.  The degree follows from the
 number of f_rest properties: 0, 9, 24 or 45 for degrees 0-3.
+
+save_gaussian_ply is its exact inverse: the same file 3D Gaussian splatting writes (x y z, zero nx ny nz, f_dc, channel-major
+f_rest, opacity as a logit, log scales, rot), from the arrays load_gaussian_ply returns.
 """
 import numpy as np
 
@@ -90,9 +93,45 @@ def load_gaussian_ply(path):
     op = cols(["opacity"])[:, 0]
     return {
         "positions": cols(["x", "y", "z"]),
-        "scales": np.exp(cols(["scale_0", "scale_1", "scale_2"])).astype(np.float32),
+        # (both activations in float64, rounded once: the same arrays on every host, whatever its NumPy's float32 exp)
+        "scales": np.exp(cols(["scale_0", "scale_1", "scale_2"]).astype(np.float64)).astype(np.float32),
         "rotations": cols(["rot_0", "rot_1", "rot_2", "rot_3"]),
         "opacity": (1.0 / (1.0 + np.exp(-op.astype(np.float64)))).astype(np.float32),
         "sh": sh,
         "degree": degree,
     }
+
+
+def save_gaussian_ply(path, positions, scales, rotations, opacity, sh, log_scales=None, opacity_logits=None):
+    """Writes the cloud as 3D Gaussian splatting does (binary_little_endian float properties in its order: x y z, nx ny nz = 0,
+    f_dc_0..2, f_rest_* channel-major, opacity, scale_0..2, rot_0..3): load_gaussian_ply's inverse.  positions (n, 3), scales
+    (n, 3) > 0, rotations (n, 4) as (w, x, y, z), opacity (n,) in (0, 1), sh (n, (degree + 1)^2, 3) or (n, 3 (degree + 1)^2)
+    basis-major.  The file stores log(scales) and logit(opacity), formed in float64 and rounded once.  A caller that holds the
+    raw parameters passes them as log_scales / opacity_logits (scales / opacity may then be None): they are stored as they are,
+    bit for bit.  Positions, rotations and SH are stored bit for bit."""
+    pos = np.asarray(positions, np.float32)
+    n = pos.shape[0]
+    rot = np.asarray(rotations, np.float32)
+    coef = np.asarray(sh, np.float32).reshape(n, -1, 3)
+    nb = coef.shape[1]
+    degree = {1: 0, 4: 1, 9: 2, 16: 3}.get(nb)
+    if degree is None:
+        raise SplatError(-1, f"save_gaussian_ply: sh must hold 3 (degree + 1)^2 floats per splat, degree 0-3, not {3 * nb}")
+    with np.errstate(all="ignore"):
+        ls = (np.asarray(log_scales, np.float32) if log_scales is not None
+              else np.log(np.asarray(scales, np.float32).astype(np.float64)).astype(np.float32))
+        if opacity_logits is not None:
+            ol = np.asarray(opacity_logits, np.float32).reshape(-1)
+        else:
+            o = np.asarray(opacity, np.float32).reshape(-1).astype(np.float64)
+            ol = (np.log(o) - np.log1p(-o)).astype(np.float32)
+    if pos.shape != (n, 3) or ls.shape != (n, 3) or rot.shape != (n, 4) or ol.shape != (n,):
+        raise SplatError(-1, "save_gaussian_ply: positions (n, 3), scales (n, 3), rotations (n, 4) and opacity (n,) are expected")
+    rest = coef[:, 1:, :].transpose(0, 2, 1).reshape(n, 3 * (nb - 1))  # channel-major: f_rest_{c (nb - 1) + (k - 1)}
+    names = (["x", "y", "z", "nx", "ny", "nz", "f_dc_0", "f_dc_1", "f_dc_2"] + [f"f_rest_{j}" for j in range(rest.shape[1])]
+             + ["opacity", "scale_0", "scale_1", "scale_2", "rot_0", "rot_1", "rot_2", "rot_3"])
+    table = np.concatenate([pos, np.zeros((n, 3), np.float32), coef[:, 0, :], rest, ol[:, None], ls, rot], axis=1).astype("<f4")
+    header = "ply\nformat binary_little_endian 1.0\n" + f"element vertex {n}\n" + "".join(f"property float {k}\n" for k in names) + "end_header\n"
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(np.ascontiguousarray(table).tobytes())

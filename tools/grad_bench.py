@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Gradients of ellipsoid frames (GPU box only): python tools/grad_bench.py [--depth] [--camera | --loss] [C1,C2] [K] [R]
+"""Gradients of ellipsoid frames (GPU box only): python tools/grad_bench.py [--depth] [--camera | --loss | --optimizer] [C1,C2] [K] [R]
 
 tools/ellipsoid_bench.py's scenes and method (the scene's positions, sigma = radius / 2 per axis times a random factor in
 [e^-0.3, e^0.3], random rotations, SH of degree 3 with the scene's opacity; R rounds of K calls per kind, kinds alternating
@@ -33,7 +33,16 @@ conv2d with the 11 x 11 window over three groups, five maps, and the .contiguous
 its torch.autograd backward); the whole frame's forward + backward with each of the two losses (frame_fused, frame_torch);
 and the bytes each fused kernel must move (forward: x at 16 B and y at 12 B per pixel read, 36 B of derivative maps written;
 backward: the same reads, the maps read, 12 B of gradient written) with the time they take at 5.1 TB/s, the copy rate
-DESIGN.md uses."""
+DESIGN.md uses.
+
+--optimizer measures the optimiser step and density control instead (one JSON line per config, nothing of the above), on the
+raw parameters of a fit (means, log-scales, rotations, opacity logits, SH of degree 3: 59 floats per splat) with the gradients
+and the visibility mask of one real frame: torch.optim.Adam(foreach=True) and torch.optim.Adam(fused=True) over the five
+tensors (one rate per tensor: torch cannot give the SH plane two without splitting it), five splat_adam_step launches dense
+and the same five masked with the frame's visibility, alternating in one process; per contender the bytes it moves by the
+28 B-per-parameter count (the masked step: that count over the visible rows, plus the mask) and the share of the 5.1 TB/s copy
+rate that is; and splat_density_accumulate, splat_densify_plan (with its one synchronisation: a host clock around it) and the
+apply pass (splat_densify_geometry, three COPY and ten ZERO_NEW splat_densify_rows) at 3DGS's default thresholds."""
 import ctypes as C
 import json
 import os
@@ -92,7 +101,8 @@ def torch_camera_terms(U, pos, scl, rot, g, W, H):
     return torch.stack(terms, dim=1).sum(dim=0)
 
 
-argv = [a for a in sys.argv[1:] if a not in ("--depth", "--camera", "--loss")]
+argv = [a for a in sys.argv[1:] if a not in ("--depth", "--camera", "--loss", "--optimizer")]
+optimizer_only = "--optimizer" in sys.argv[1:]
 depth_too = "--depth" in sys.argv[1:]
 camera_too = "--camera" in sys.argv[1:]
 loss_only = "--loss" in sys.argv[1:]
@@ -203,6 +213,126 @@ def loss_bench(name, k, rounds, stream):
                       "fused_backward_over_floor": round(med["fused_loss_backward"] / (bwd_bytes / COPY_RATE * 1e3), 2)}), flush=True)
 
 
+def optimizer_bench(name, k, rounds, stream):
+    import time
+    from splat_renderer_amd.fit import DEFAULT_LR, PLANES, GaussianFit
+    n, w, h = sr.scene.CONFIGS[name]
+    props, _ = sr.scene.make_scene(n)
+    rng = np.random.default_rng(0)
+    scl = (props[:, 3:4] * 0.5 * np.exp(rng.uniform(-0.3, 0.3, (n, 3)))).astype(np.float32)
+    rot = rng.normal(size=(n, 4)).astype(np.float32)
+    sh = rng.normal(0, 0.3, (n, 16, 3)).astype(np.float32)
+    cam = sr.Camera()
+    cam.setAspect(w / h)
+    u = cam.uniforms(w, h)
+    fit = GaussianFit(props[:, :3], scl, rot, np.clip(props[:, 7], 1e-4, 1 - 1e-4), sh)
+    target = torch.rand((h, w, 3), device="cuda")
+    rgb, _ = fit.render(u, w, h)
+    AG.photometric_loss(rgb, target).backward()
+    rec, _, _ = fit._frame
+    grec = rec.grad.contiguous()
+    grads = {p: getattr(fit, p).grad.contiguous() for p in PLANES}
+    cx = AG._context(fit.means)
+    lib = cx.lib
+    ga, dn, mr = (torch.zeros(n, device="cuda") for _ in range(3))
+    vis = torch.zeros(n, device="cuda", dtype=torch.uint8)
+
+    def accumulate():
+        _lib.check(lib.splat_density_accumulate(cx.ctx, rec.data_ptr(), grec.data_ptr(), n, w, h, ga.data_ptr(), dn.data_ptr(), mr.data_ptr(),
+                                                vis.data_ptr()), cx.ctx)
+    accumulate()
+    visible = float(vis.float().mean())
+    params = sum(g.numel() for g in grads.values())
+    visible_params = int(visible * n + 0.5) * 59
+
+    def copies():
+        return {p: getattr(fit, p).detach().clone() for p in PLANES}
+    sets = {}
+    for kind, kw in (("torch_foreach", dict(foreach=True)), ("torch_fused", dict(fused=True))):
+        ps = copies()
+        for p in PLANES:
+            ps[p].requires_grad_()
+            ps[p].grad = grads[p]
+        sets[kind] = torch.optim.Adam([{"params": [ps[p]], "lr": DEFAULT_LR[p]} for p in PLANES], eps=1e-15, **kw)
+    ours = copies()
+    m, v = {p: torch.zeros_like(ours[p]) for p in PLANES}, {p: torch.zeros_like(ours[p]) for p in PLANES}
+    t = {"step": 0}
+
+    def splat_step(mask):
+        t["step"] += 1
+        bc1, isbc2 = 1.0 - 0.9 ** t["step"], 1.0 / (1.0 - 0.999 ** t["step"]) ** 0.5
+        for p in PLANES:
+            fpr = ours[p].shape[1] if ours[p].dim() == 2 else 1
+            _lib.check(lib.splat_adam_step(cx.ctx, ours[p].data_ptr(), grads[p].data_ptr(), m[p].data_ptr(), v[p].data_ptr(), n, fpr,
+                                           3 if p == "sh" else fpr, DEFAULT_LR[p] / bc1, DEFAULT_LR["sh_rest" if p == "sh" else p] / bc1, 0.9, 0.999,
+                                           isbc2, 1e-15, mask), cx.ctx)
+
+    cfg = _lib.DensifyCfg(2e-4, 0.01 * fit.extent, 0.005, 0.0, 0.0, 0, 1)
+    nbytes = int(lib.splat_densify_plan_workspace_bytes(n))
+    ws = torch.empty(nbytes // 4, device="cuda", dtype=torch.int32)
+    rows = torch.empty(2 * n, device="cuda", dtype=torch.int32)
+    n_out, counts = C.c_uint32(), (C.c_uint32 * 4)()
+
+    def plan():
+        _lib.check(lib.splat_densify_plan(cx.ctx, fit.log_scales.data_ptr(), fit.opacity_logits.data_ptr(), ga.data_ptr(), dn.data_ptr(),
+                                          mr.data_ptr(), n, C.byref(cfg), ws.data_ptr(), nbytes, rows.data_ptr(), C.byref(n_out), counts), cx.ctx)
+    plan()
+    kout = int(n_out.value)
+    outs = {p: torch.empty((kout,) + tuple(ours[p].shape[1:]), device="cuda") for p in PLANES}
+
+    def apply():
+        _lib.check(lib.splat_densify_geometry(cx.ctx, rows.data_ptr(), kout, ours["means"].data_ptr(), ours["log_scales"].data_ptr(),
+                                              ours["rotations"].data_ptr(), C.byref(cfg), outs["means"].data_ptr(), outs["log_scales"].data_ptr()),
+                   cx.ctx)
+        for p in PLANES:
+            fpr = ours[p].shape[1] if ours[p].dim() == 2 else 1
+            if p in PLANES[2:]:
+                _lib.check(lib.splat_densify_rows(cx.ctx, rows.data_ptr(), kout, ours[p].data_ptr(), outs[p].data_ptr(), fpr, 0), cx.ctx)
+            for mom in (m, v):
+                _lib.check(lib.splat_densify_rows(cx.ctx, rows.data_ptr(), kout, mom[p].data_ptr(), outs[p].data_ptr(), fpr, 1), cx.ctx)
+
+    work = {"torch_foreach": sets["torch_foreach"].step, "torch_fused": sets["torch_fused"].step, "splat_dense": lambda: splat_step(None),
+            "splat_masked": lambda: splat_step(vis.data_ptr()), "accumulate": accumulate, "apply": apply}
+
+    def run(kind, calls):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(calls):
+            work[kind]()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / calls
+
+    def run_plan(calls):  # (it synchronises: a host clock, the stream idle before and after)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(calls):
+            plan()
+        return (time.perf_counter() - t0) * 1e3 / calls
+
+    for kind in list(work) * 2:
+        run(kind, 3)
+    run_plan(3)
+    ts = {kind: [] for kind in list(work) + ["plan"]}
+    for _ in range(rounds):
+        for kind in work:
+            ts[kind].append(run(kind, k))
+        ts["plan"].append(run_plan(max(k // 4, 1)))
+    med = {kind: sorted(x)[len(x) // 2] for kind, x in ts.items()}
+    moved = {"torch_foreach": 28 * params, "torch_fused": 28 * params, "splat_dense": 28 * params, "splat_masked": 28 * visible_params + 5 * n}
+    print(json.dumps({"config": name, "n": n, "width": w, "height": h, "calls_per_round": k, "rounds": rounds, "parameters": params,
+                      "visible_fraction": round(visible, 4),
+                      **{f"{kind}_ms": round(x, 4) for kind, x in med.items()},
+                      **{f"{kind}_ms_min_max": [round(min(x), 4), round(max(x), 4)] for kind, x in ts.items()},
+                      **{f"{kind}_bytes": b for kind, b in moved.items()},
+                      **{f"{kind}_share_of_copy_rate": round(b / (med[kind] * 1e-3) / COPY_RATE, 3) for kind, b in moved.items()},
+                      "dense_floor_ms": round(28 * params / COPY_RATE * 1e3, 4),
+                      "torch_fused_over_splat_dense": round(med["torch_fused"] / med["splat_dense"], 3),
+                      "torch_foreach_over_splat_dense": round(med["torch_foreach"] / med["splat_dense"], 3),
+                      "splat_dense_over_splat_masked": round(med["splat_dense"] / med["splat_masked"], 3),
+                      "plan_counts": {"pruned": counts[0], "kept": counts[1], "cloned": counts[2], "split": counts[3], "rows": kout}}), flush=True)
+
+
 def torch_records(U, pos, scl, rot, W, H):
     """The records {c.x, c.y, B00, B01, B11} (n, 5) as plain float32 torch ops of the uniform block U (include/splat.h; no cull)."""
     q = rot / torch.sqrt((rot * rot).sum(dim=1, keepdim=True))
@@ -232,6 +362,10 @@ stream = torch.cuda.current_stream()
 if loss_only:
     for name in names:
         loss_bench(name, k, rounds, stream)
+    names = []
+if optimizer_only:
+    for name in names:
+        optimizer_bench(name, k, rounds, stream)
     names = []
 for name in names:
     n, w, h = sr.scene.CONFIGS[name]
