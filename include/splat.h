@@ -671,6 +671,67 @@ int splat_densify_geometry(splat_ctx *ctx, const void *rows, uint32_t n_out, con
 int splat_densify_rows(splat_ctx *ctx, const void *rows, uint32_t n_out, const void *in, void *out, uint32_t floats_per_row,
                        uint32_t mode);
 
+/* ---- MCMC relocation: 3DGS-MCMC's way of deciding where the splats live (Kheradmand et al., "3D Gaussian Splatting as Markov
+ * Chain Monte Carlo", 2024; an extension) -----------------------------------------------------------------------------------------
+ * The other strategy beside splat_densify_*: dead splats are moved onto live ones drawn in proportion to opacity, with opacity
+ * and scale corrected so that the rendered image does not change; the cloud grows to an exact budget the same way; and the
+ * means get opacity-gated noise at every step.  No gradient statistics, no screen-space thresholds, no opacity reset.  The
+ * planes are the density block's (contiguous float32 DEVICE planes, 4-byte aligned unless said otherwise), everything goes to the
+ * ctx's stream, and only splat_mcmc_sample waits on the host.  splat_mcmc_sample counts the draws per source with unsigned
+ * integer atomic adds, whose result does not depend on their order; no kernel uses a floating-point atomic: the same inputs and
+ * seed give the same bits.
+ *
+ * splat_mcmc_sample: who is dead, who is drawn, how often.  Per splat, in binary64:
+ *   o = 1 / (1 + exp(-(double)logit)),   q = (uint32) floor(o 2^24)  (0 for a NaN logit),   q_min = ceil(min_opacity 2^24);
+ *   DEAD when q < q_min, ALIVE otherwise; its weight is q when alive and 0 when dead.
+ * The weights are summed exactly in uint64: C_i their inclusive prefix sum, T the total.  mode SPLAT_MCMC_RELOCATE: there is one
+ * draw per dead splat, draw j belongs to the j-th dead splat in index order and targets[j] is its index (n_draws is ignored).
+ * mode SPLAT_MCMC_ADD: n_draws draws, targets[j] = n + j.  Draw j: Philox4x32-10 with key (seed low word, seed high word) and
+ * counter (j, 0, mode, 0) (a split's is (parent, k, 0, 0) and the noise's (i, step, 3, 0): none is shared), r = x0 | x1 << 32,
+ * t = floor(r T / 2^64), sources[j] = the smallest i with C_i > t; counts[i] = the draws whose source is i.
+ * targets, sources (DEVICE): room for n uint32 when relocating, n_draws when adding; counts (DEVICE): n uint32, all written.
+ * counts3_host = {dead, alive, draws made} are HOST words: THIS CALL SYNCHRONISES THE STREAM ONCE to fill them.  With T = 0
+ * (nobody alive) no draw is made: counts are zeros, draws made = 0, targets and sources are not written.  workspace: DEVICE,
+ * 16-byte aligned, at least splat_mcmc_sample_workspace_bytes(n).  n = 0: zeros, nothing launched.  SPLAT_ERR_INVALID: n >= 2^30
+ * (or n + n_draws above 2^30), an unknown mode, min_opacity outside [0, 1], a NULL or misaligned pointer, a workspace that is
+ * too small. */
+#define SPLAT_MCMC_RELOCATE 1
+#define SPLAT_MCMC_ADD 2
+uint64_t splat_mcmc_sample_workspace_bytes(uint32_t n);
+int splat_mcmc_sample(splat_ctx *ctx, const void *opacity_logits, uint32_t n, uint32_t mode, uint32_t n_draws, double min_opacity,
+                      uint64_t seed, void *workspace, uint64_t workspace_bytes, void *targets, void *sources, void *counts,
+                      uint32_t *counts3_host);
+/* splat_mcmc_apply: move the draws and correct the sources, in place.  targets, sources, counts, n and n_draws (the draws made)
+ * are splat_mcmc_sample's; the planes hold `rows` rows: n when relocating, n + n_draws when adding (the first n filled by the
+ * caller).  For a source i with c = counts[i] > 0, N = min(c + 1, 51), in binary64 from the source's OLD values:
+ *   o' = 1 - (1 - o)^(1/N),
+ *   D  = sum_{a=1..N} sum_{k=0..a-1} binom(a-1, k) (-1)^k o'^(k+1) / sqrt(k+1)      (o' unclamped; a 51 x 51 table of doubles),
+ *   new logit      = logit(clamp(o', min_opacity, 1 - 2^-23)), rounded to binary32 once,
+ *   new log_scales = (double)log_scale + log(o / D) per axis, rounded once.
+ * (A) per draw j, row targets[j] of the five parameter planes gets row sources[j]: means, rotations and sh bit for bit, logit
+ * and log_scales the new values; then (B) every source with c > 0 gets the same new values (the same bits).  Sources are alive
+ * and a relocation's targets dead, so this is race-free in place.  Moments: both Adam moments of all five planes are ZEROED for
+ * every target row AND every source with c > 0 (the paper's code zeroes only the sources; a moved row's old momentum belongs to
+ * a splat that no longer exists).  m[k] / v[k] may be NULL (no such plane).  Rows that are neither target nor source are not
+ * written.  A draw whose target is not below `rows` or whose source is not below n is skipped.  n_draws = 0: nothing launched.
+ * SPLAT_ERR_INVALID: a NULL or misaligned pointer, rows < n, sh_floats outside 1-48, n_draws x (11 + sh_floats) above 2^32 - 257. */
+typedef struct splat_mcmc_planes {
+    void *param[5], *m[5], *v[5]; /* means, log_scales, rotations, opacity_logits, sh: 3, 3, 4, 1 and sh_floats floats per row */
+    uint32_t sh_floats;
+} splat_mcmc_planes;
+int splat_mcmc_apply(splat_ctx *ctx, const void *targets, const void *sources, const void *counts, uint32_t n, uint32_t n_draws,
+                     uint32_t rows, double min_opacity, const splat_mcmc_planes *planes);
+/* splat_mcmc_noise: the per-step exploration term, one pass over the cloud (44 bytes read, 12 written per splat).  Per splat, in
+ * binary32, R the rotation matrix of the normalised quaternion as csrc/ellipsoid.h forms it:
+ *   o = sigmoid(logit),   g = 1 / (1 + exp(-100 (0.005 - o)))   (the paper's op_sigmoid(1 - o, k = 100, x0 = 0.995)),
+ *   Sigma = R diag(exp(2 log_scales)) R^T,   xi = splat_densify_geometry's three normals from counter (i, step, 3, 0),
+ *   means[i] += Sigma xi g scale.
+ * scale (the caller's noise_lr x lr_means) crosses as a double and is rounded to binary32 once.  Planes that are all 16-byte
+ * aligned are moved with 16-byte loads and stores, others with scalar ones; both give the same bits.  n = 0: nothing launched.
+ * SPLAT_ERR_INVALID: n >= 2^30, a NULL or misaligned plane. */
+int splat_mcmc_noise(splat_ctx *ctx, void *means, const void *log_scales, const void *rotations, const void *opacity_logits, uint32_t n,
+                     double scale, uint32_t step, uint64_t seed);
+
 /* ---- multi-GPU band path (no reference equivalent — the reference is single-device) */
 /* The oriented-disc projector (src/SequentialRenderer.ts:68-71,91-112): the splat is the disc
  * p + r*(t*u + b*v), u^2+v^2 <= 1, in the tangent plane of its normal (t = normalize(cross(up, n)), b =

@@ -58,6 +58,15 @@ class DensifyCfg(C.Structure):
 
 DENSIFY_COPY, DENSIFY_ZERO_NEW = 0, 1
 
+
+class McmcPlanes(C.Structure):
+    """splat_mcmc_planes: the five parameter planes of a fit (means, log_scales, rotations, opacity_logits, sh), their Adam
+    moments (device pointers; a moment may be 0) and the floats per row of the SH plane."""
+    _fields_ = [("param", C.c_void_p * 5), ("m", C.c_void_p * 5), ("v", C.c_void_p * 5), ("sh_floats", C.c_uint32)]
+
+
+MCMC_RELOCATE, MCMC_ADD = 1, 2
+
 # name -> (restype, argtypes); the single source of truth checked against include/splat.h by
 # tests/test_abi_cpu.py
 _vp, _u32, _sz, _i, _f64 = C.c_void_p, C.c_uint32, C.c_size_t, C.c_int, C.c_double
@@ -112,6 +121,10 @@ SIGNATURES = {
                                 C.POINTER(_u32)]),
     "splat_densify_geometry": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, C.POINTER(DensifyCfg), _vp, _vp]),
     "splat_densify_rows": (_i, [_vp, _vp, _u32, _vp, _vp, _u32, _u32]),
+    "splat_mcmc_sample_workspace_bytes": (C.c_uint64, [_u32]),
+    "splat_mcmc_sample": (_i, [_vp, _vp, _u32, _u32, _u32, _f64, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, C.POINTER(_u32)]),
+    "splat_mcmc_apply": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _f64, C.POINTER(McmcPlanes)]),
+    "splat_mcmc_noise": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _f64, _u32, C.c_uint64]),
     "splat_extract_keys":(_i, [_vp, _vp, _u32, _u32, _vp, _vp]),
     "splat_sort_create": (_i, [_vp, _u32, _pvp]),
     "splat_sort_destroy": (None, [_vp]),

@@ -13,7 +13,7 @@
 // k_density_accumulate    one thread per splat: visibility of the record's 3-sigma box, the three running statistics, the mask.
 // k_densify_classify ..   splat_densify_plan: classify -> scan(alive), scan(wants) -> grant under the cap -> scan(rows per
 // k_densify_fill          splat), scan(granted clones) -> one thread per splat writes its rows.  The scans are scan.hip's.
-// k_densify_geometry      one thread per OUTPUT row: means and log-scales, the split children drawn with Philox4x32-10.
+// k_densify_geometry      one thread per OUTPUT row: means and log-scales, the split children drawn with Philox4x32-10 (philox.h).
 // k_densify_rows<VEC>     one thread per float (float4) of the OUTPUT plane: a gather, contiguous writes.
 // No atomics anywhere: the same inputs give the same bits.
 //
@@ -21,6 +21,7 @@
 // with SH of degree 3, 1.6 ms at the 5.1 TB/s copy rate ("Density control and optimiser";
 // tools/grad_bench.py --optimizer measures the step against that floor).
 #include "common.h"
+#include "philox.h"
 
 namespace {
 
@@ -185,21 +186,6 @@ __global__ __launch_bounds__(DT) void k_densify_fill(const uint32_t *__restrict_
     }
 }
 
-// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11)
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t lo0 = 0xD2511F53u * c.x, hi0 = __umulhi(0xD2511F53u, c.x);
-        const uint32_t lo1 = 0xCD9E8D57u * c.z, hi1 = __umulhi(0xCD9E8D57u, c.z);
-        c = make_uint4(hi1 ^ c.y ^ k.x, lo1, hi0 ^ c.w ^ k.y, lo0);
-        k.x += 0x9E3779B9u;
-        k.y += 0xBB67AE85u;
-    }
-    return c;
-}
-
-__device__ __forceinline__ float philox_unit(uint32_t x) { return (float)(((double)x + 0.5) * 0x1p-32); } // (0, 1]
-
 constexpr double LOG_SPLIT_SHRINK = 0.47000362924573555; // log 1.6
 
 __global__ __launch_bounds__(DT) void k_densify_geometry(const uint32_t *__restrict__ rows, uint32_t n_out, const float *__restrict__ means,
@@ -213,11 +199,8 @@ __global__ __launch_bounds__(DT) void k_densify_geometry(const uint32_t *__restr
     float lx = log_scales[src], ly = log_scales[src + 1], lz = log_scales[src + 2];
     if (kind >= 2u) {
         const uint4 x = philox4x32_10(make_uint4(parent, kind - 2u, 0u, 0u), key);
-        const float ra = sqrtf(-2.0f * logf(philox_unit(x.x))), rb = sqrtf(-2.0f * logf(philox_unit(x.z)));
-        float sa, ca;
-        sincosf(6.283185307179586f * philox_unit(x.y), &sa, &ca);
-        const float cb = cosf(6.283185307179586f * philox_unit(x.w));
-        const float ex = expf(lx) * (ra * ca), ey = expf(ly) * (ra * sa), ez = expf(lz) * (rb * cb);
+        const float3 xi = philox_normals3(x);
+        const float ex = expf(lx) * xi.x, ey = expf(ly) * xi.y, ez = expf(lz) * xi.z;
         const float4 q = rotations[parent]; // (w, x, y, z), normalised as ellipsoid_record() does
         const float k = 1.0f / sqrtf(((q.x * q.x + q.y * q.y) + q.z * q.z) + q.w * q.w);
         const float qr = q.x * k, qx = q.y * k, qy = q.z * k, qz = q.w * k;

@@ -21,6 +21,21 @@ as in the "sparse Adam" of the faster 3DGS trainers (its gradient is exactly zer
 move it).  densify_and_prune() is splat_densify_plan, splat_densify_geometry and splat_densify_rows: it replaces the tensors
 (callers must not hold on to the old ones), moves the moments with them (new splats start at zero) and resets the statistics.
 Every kernel runs on torch's current stream; only densify_and_prune waits on the host (once, for the new count).
+
+The other strategy is 3DGS-MCMC (include/splat.h, "MCMC relocation"), for a fit whose splat count is a budget:
+
+    fit = GaussianFit(..., sparse=False)
+    for step in range(steps):
+        rgb, alpha = fit.render(camera_or_uniforms, width, height)
+        (photometric_loss(rgb, target) + fit.regularizer()).backward()
+        fit.step()
+        fit.inject_noise()                                              # opacity-gated noise on the means, every step
+        if step % 100 == 99:
+            fit.relocate()                                              # dead splats onto live ones, the image unchanged
+            fit.add_new(max_splats=...)                                 # 5 % more, up to exactly max_splats
+
+relocate() and add_new() replace densify_and_prune() and reset_opacity() and are not used beside them.  The regularisers reach
+splats the frame did not see, whose gradient a masked Adam step would drop: an MCMC fit wants sparse=False.
 """
 import ctypes as C
 import math
@@ -37,9 +52,12 @@ PLANES = ("means", "log_scales", "rotations", "opacity_logits", "sh")
 
 class GaussianFit:
     def __init__(self, means, scales, rotations, opacity, sh, degree=None, lr=None, betas=(0.9, 0.999), eps=1e-15, sparse=True,
-                 device="cuda"):
+                 device="cuda", exact_activations=False):
         """means (n, 3), scales (n, 3) > 0, rotations (n, 4), opacity (n,) in (0, 1), sh (n, K, 3) or (n, 3 K), K = (degree +
-        1)^2: arrays or tensors of activated values.  lr: a dict that overrides entries of DEFAULT_LR."""
+        1)^2: arrays or tensors of activated values.  lr: a dict that overrides entries of DEFAULT_LR.  exact_activations:
+        render() forms exp and sigmoid in float64 and rounds once, as load_gaussian_ply does, so the frame the fit renders is the
+        frame its saved PLY renders; with the default float32 activations the two differ by an ulp in some scales and opacities,
+        which now and then carries one pixel across a splat's 3-sigma cut (a step of up to 0.011 x opacity in that pixel)."""
         torch = AG._t()
         t = lambda a: torch.as_tensor(a, dtype=torch.float32).to(device).detach()  # noqa: E731
         means, scales, rotations, opacity, sh = t(means), t(scales), t(rotations), t(opacity).reshape(-1), t(sh)
@@ -53,8 +71,10 @@ class GaussianFit:
             raise SplatError(-1, "means (n, 3), scales (n, 3), rotations (n, 4) and opacity (n,) are expected")
         self.lr = dict(DEFAULT_LR, **(lr or {}))
         self.betas, self.eps, self.sparse = (float(betas[0]), float(betas[1])), float(eps), bool(sparse)
+        self.exact_activations = bool(exact_activations)
         self.steps = 0
         self.densifications = 0
+        self.relocations = self.additions = self.noises = 0
         self._set(means[:, :3].clone(), torch.log(scales), rotations.clone(), torch.logit(opacity), sh.clone())
         self.m = {k: torch.zeros_like(getattr(self, k)) for k in PLANES}
         self.v = {k: torch.zeros_like(getattr(self, k)) for k in PLANES}
@@ -86,7 +106,10 @@ class GaussianFit:
         parameters.  The frame's records are kept for the next step()."""
         torch = AG._t()
         u = AG._uniforms(camera_or_uniforms, width, height)
-        scales, opacity = torch.exp(self.log_scales), torch.sigmoid(self.opacity_logits)
+        if self.exact_activations:
+            scales, opacity = torch.exp(self.log_scales.double()).float(), torch.sigmoid(self.opacity_logits.double()).float()
+        else:
+            scales, opacity = torch.exp(self.log_scales), torch.sigmoid(self.opacity_logits)
         if return_depth:
             rec, depths, aux = AG.project_ellipsoids(u, self.means, scales, self.rotations, return_depth=True)
         else:
@@ -176,6 +199,110 @@ class GaussianFit:
             self.opacity_logits.clamp_(max=math.log(value / (1.0 - value)))
             self.m["opacity_logits"].zero_()
             self.v["opacity_logits"].zero_()
+
+    # ---- 3DGS-MCMC (include/splat.h, "MCMC relocation") ---------------------------------------------------------------------
+
+    def _mcmc_planes(self, params=None, m=None, v=None):
+        params = params or {name: getattr(self, name) for name in PLANES}
+        m, v = m or self.m, v or self.v
+        pl = _lib.McmcPlanes()
+        for k, name in enumerate(PLANES):
+            pl.param[k], pl.m[k], pl.v[k] = params[name].data_ptr(), m[name].data_ptr(), v[name].data_ptr()
+        pl.sh_floats = self.sh.shape[1]
+        return pl
+
+    def _mcmc_sample(self, mode, n_draws, min_opacity, seed):
+        """splat_mcmc_sample on the current logits: (targets, sources, counts, (dead, alive, draws made))."""
+        torch = AG._t()
+        n = self.n
+        cx = AG._context(self.means)
+        dev = self.means.device
+        nbytes = int(cx.lib.splat_mcmc_sample_workspace_bytes(n))
+        ws = torch.empty(nbytes // 4, device=dev, dtype=torch.int32)
+        room = max(n if mode == _lib.MCMC_RELOCATE else n_draws, 1)
+        targets, sources = (torch.empty(room, device=dev, dtype=torch.int32) for _ in range(2))
+        counts = torch.empty(max(n, 1), device=dev, dtype=torch.int32)
+        words = (C.c_uint32 * 3)()
+        check(cx.lib.splat_mcmc_sample(cx.ctx, self.opacity_logits.data_ptr(), n, mode, int(n_draws), float(min_opacity),
+                                       int(seed) & 0xFFFFFFFFFFFFFFFF, ws.data_ptr(), nbytes, targets.data_ptr(), sources.data_ptr(),
+                                       counts.data_ptr(), words), cx.ctx)
+        return targets, sources, counts, tuple(int(x) for x in words)
+
+    def relocate(self, min_opacity=0.005, seed=None):
+        """3DGS-MCMC's relocation, in place: every dead splat (opacity below min_opacity, or a NaN logit) becomes a copy of a live
+        one drawn in proportion to opacity, and the opacity and scales of the source and its copies are corrected so that the
+        rendered image does not change (splat_mcmc_sample, splat_mcmc_apply); the Adam moments of moved rows and of drawn sources
+        are zeroed.  seed defaults to the number of earlier calls.  Returns {"dead", "alive", "relocated", "sources"}: "sources"
+        is the number of distinct splats drawn.  With densify_and_prune()/reset_opacity() this is not used: it replaces them."""
+        torch = AG._t()
+        n = self.n
+        seed, self.relocations = (self.relocations if seed is None else seed), self.relocations + 1
+        with torch.no_grad():
+            targets, sources, counts, (dead, alive, draws) = self._mcmc_sample(_lib.MCMC_RELOCATE, 0, min_opacity, seed)
+            drawn = 0
+            if draws:
+                cx = AG._context(self.means)
+                pl = self._mcmc_planes()
+                check(cx.lib.splat_mcmc_apply(cx.ctx, targets.data_ptr(), sources.data_ptr(), counts.data_ptr(), n, draws, n, float(min_opacity),
+                                              C.byref(pl)), cx.ctx)
+                drawn = int((counts[:n] > 0).sum())
+        self._frame = None
+        return {"dead": dead, "alive": alive, "relocated": draws, "sources": drawn}
+
+    def add_new(self, max_splats, growth=0.05, min_opacity=0.005, seed=None):
+        """3DGS-MCMC's growth: k = max(0, min(max_splats, floor((1 + growth) n)) - n) new splats, each a copy of a live one drawn
+        in proportion to opacity, corrected as relocate() corrects (so the count reaches max_splats exactly and never passes it).
+        Like densify_and_prune() it replaces the tensors and moves the moments (new rows and drawn sources start at zero); the
+        three statistics planes are resized with zeros for the new rows.  seed defaults to the number of earlier calls.  Returns
+        {"added", "n"}.  With densify_and_prune()/reset_opacity() this is not used: it replaces them."""
+        torch = AG._t()
+        n = self.n
+        k = max(0, min(int(max_splats), int(math.floor((1.0 + float(growth)) * n))) - n)
+        seed, self.additions = (self.additions if seed is None else seed), self.additions + 1
+        if k == 0 or n == 0:
+            return {"added": 0, "n": n}
+        with torch.no_grad():
+            targets, sources, counts, (_, _, draws) = self._mcmc_sample(_lib.MCMC_ADD, k, min_opacity, seed)
+            if draws == 0:  # (nobody alive)
+                return {"added": 0, "n": n}
+
+            def grown(src, fill_old=True):
+                out = torch.zeros((n + k,) + tuple(src.shape[1:]), device=src.device, dtype=src.dtype)
+                if fill_old:
+                    out[:n].copy_(src.detach())
+                return out
+            new = {name: grown(getattr(self, name)) for name in PLANES}
+            m = {name: grown(self.m[name]) for name in PLANES}
+            v = {name: grown(self.v[name]) for name in PLANES}
+            cx = AG._context(self.means)
+            pl = self._mcmc_planes(new, m, v)
+            check(cx.lib.splat_mcmc_apply(cx.ctx, targets.data_ptr(), sources.data_ptr(), counts.data_ptr(), n, k, n + k, float(min_opacity),
+                                          C.byref(pl)), cx.ctx)
+            self.m, self.v = m, v
+            self.grad_accum, self.denom, self.max_radius, self.visible = (grown(x) for x in (self.grad_accum, self.denom, self.max_radius,
+                                                                                             self.visible))
+        self._set(*(new[name] for name in PLANES))
+        self._frame = None
+        return {"added": k, "n": n + k}
+
+    def inject_noise(self, noise_lr=5e5, lr_means=None, seed=None):
+        """3DGS-MCMC's exploration term, after every step(): means += Sigma xi g noise_lr lr_means, xi standard normal, g a gate
+        that is ~1 for nearly transparent splats and below 1e-20 from opacity 0.5 on (splat_mcmc_noise).  lr_means defaults to
+        this fit's rate for the means; the random stream is counted by fit.steps, seed defaults to the number of earlier calls."""
+        n = self.n
+        seed, self.noises = (self.noises if seed is None else seed), self.noises + 1
+        if n == 0:
+            return
+        cx = AG._context(self.means)
+        scale = float(noise_lr) * float(self.lr["means"] if lr_means is None else lr_means)
+        check(cx.lib.splat_mcmc_noise(cx.ctx, self.means.data_ptr(), self.log_scales.data_ptr(), self.rotations.data_ptr(),
+                                      self.opacity_logits.data_ptr(), n, scale, int(self.steps) & 0xFFFFFFFF, int(seed) & 0xFFFFFFFFFFFFFFFF), cx.ctx)
+
+    def regularizer(self, opacity_reg=0.01, scale_reg=0.01):
+        """3DGS-MCMC's two regularisers as a 0-d tensor to add to the loss: opacity_reg mean(opacity) + scale_reg mean(scale), in
+        plain torch.  They reach splats the frame did not see, so a fit that uses them wants sparse=False."""
+        torch = AG._t()
+        return opacity_reg * torch.sigmoid(self.opacity_logits).mean() + scale_reg * torch.exp(self.log_scales).mean()
 
     def save_ply(self, path):
         """The cloud as a 3D Gaussian splatting PLY file (ply.save_gaussian_ply): the raw parameters, bit for bit."""

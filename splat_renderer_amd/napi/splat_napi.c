@@ -501,6 +501,50 @@ FN(densify_rows) { /* (ctx, rows, nOut, in, out, floatsPerRow, mode: 0 copy, 1 z
     void *in = arg_dptr(&c, 3), *out = arg_dptr(&c, 4); uint32_t fpr = (uint32_t)arg_number(&c, 5), mode = (uint32_t)arg_number(&c, 6); BAIL;
     return check(env, x, splat_densify_rows(x, rows, n, in, out, fpr, mode), mk_undefined(env));
 }
+FN(mcmc_sample_workspace_bytes) { /* (n) -> bytes */
+    ARGS(1); uint32_t n = (uint32_t)arg_number(&c, 0); BAIL;
+    return mk_number(env, (double)splat_mcmc_sample_workspace_bytes(n));
+}
+FN(mcmc_sample) { /* (ctx, opacityLogits, n, mode: 1 relocate, 2 add, nDraws, minOpacity, seed (integer < 2^53), workspace, workspaceBytes, targets, sources, counts) -> [dead, alive, draws] (waits) */
+    ARGS(12); splat_ctx *x = arg_external(&c, 0); void *ol = arg_dptr(&c, 1); uint32_t n = (uint32_t)arg_number(&c, 2);
+    uint32_t mode = (uint32_t)arg_number(&c, 3), nd = (uint32_t)arg_number(&c, 4); double mo = arg_number(&c, 5);
+    uint64_t seed = (uint64_t)arg_number(&c, 6); void *ws = arg_dptr(&c, 7); uint64_t wb = (uint64_t)arg_number(&c, 8);
+    void *tg = arg_dptr(&c, 9), *sr = arg_dptr(&c, 10), *ct = arg_dptr(&c, 11); BAIL;
+    uint32_t words[3] = {0, 0, 0};
+    int rc = splat_mcmc_sample(x, ol, n, mode, nd, mo, seed, ws, wb, tg, sr, ct, words);
+    if (rc != SPLAT_OK) return check(env, x, rc, NULL);
+    napi_value arr;
+    if (napi_create_array_with_length(env, 3, &arr) != napi_ok) return NULL;
+    for (uint32_t k = 0; k < 3; ++k) napi_set_element(env, arr, k, mk_number(env, (double)words[k]));
+    return arr;
+}
+FN(mcmc_apply) { /* (ctx, targets, sources, counts, n, nDraws, rows, minOpacity, planes[15]: 5 parameters, 5 m, 5 v (device pointers or null), shFloats) */
+    ARGS(10); splat_ctx *x = arg_external(&c, 0); void *tg = arg_dptr(&c, 1), *sr = arg_dptr(&c, 2), *ct = arg_dptr(&c, 3);
+    uint32_t n = (uint32_t)arg_number(&c, 4), nd = (uint32_t)arg_number(&c, 5), rows = (uint32_t)arg_number(&c, 6); double mo = arg_number(&c, 7);
+    splat_mcmc_planes pl; memset(&pl, 0, sizeof pl);
+    bool is = false; uint32_t len = 0;
+    napi_is_array(env, c.argv[8], &is);
+    if (is) napi_get_array_length(env, c.argv[8], &len);
+    if (!is || len != 15) { napi_throw_type_error(env, NULL, "expected the planes as an array of 15 device pointers"); return NULL; }
+    for (uint32_t k = 0; k < 15; ++k) {
+        napi_value e; napi_valuetype t; double d = 0;
+        napi_get_element(env, c.argv[8], k, &e);
+        napi_typeof(env, e, &t);
+        if (t != napi_null && t != napi_undefined && napi_get_value_double(env, e, &d) != napi_ok) {
+            napi_throw_type_error(env, NULL, "expected the planes as an array of 15 device pointers"); return NULL;
+        }
+        void *p = (void *)(uintptr_t)d;
+        if (k < 5) pl.param[k] = p; else if (k < 10) pl.m[k - 5] = p; else pl.v[k - 10] = p;
+    }
+    pl.sh_floats = (uint32_t)arg_number(&c, 9); BAIL;
+    return check(env, x, splat_mcmc_apply(x, tg, sr, ct, n, nd, rows, mo, &pl), mk_undefined(env));
+}
+FN(mcmc_noise) { /* (ctx, means, logScales, rotations, opacityLogits, n, scale, step, seed (integer < 2^53)) */
+    ARGS(9); splat_ctx *x = arg_external(&c, 0); void *mu = arg_dptr(&c, 1), *ls = arg_dptr(&c, 2), *rot = arg_dptr(&c, 3), *ol = arg_dptr(&c, 4);
+    uint32_t n = (uint32_t)arg_number(&c, 5); double scale = arg_number(&c, 6); uint32_t step = (uint32_t)arg_number(&c, 7);
+    uint64_t seed = (uint64_t)arg_number(&c, 8); BAIL;
+    return check(env, x, splat_mcmc_noise(x, mu, ls, rot, ol, n, scale, step, seed), mk_undefined(env));
+}
 FN(render_frame_ellipsoids) { /* (ctx, sorter, binner, cfg[8], Float32Array(22), positions, scales, rotations, colorOpacity, n, W, H, projected|null, out8|null, outF|null, [depth, alpha, ids]|null) */
     ARGS(16); splat_ctx *x = arg_external(&c, 0); splat_sorter *s = arg_external(&c, 1); splat_binner *b = arg_external(&c, 2);
     splat_composite_cfg cfg; fill_cfg(&c, 3, &cfg); size_t ub = 0; float *u = arg_hostbuf(&c, 4, &ub);
@@ -769,6 +813,7 @@ static napi_value init(napi_env env, napi_value exports) {
         EXPORT(image_loss_workspace_bytes), EXPORT(image_loss), EXPORT(image_loss_backward),
         EXPORT(adam_step), EXPORT(density_accumulate), EXPORT(densify_plan_workspace_bytes), EXPORT(densify_plan),
         EXPORT(densify_geometry), EXPORT(densify_rows),
+        EXPORT(mcmc_sample_workspace_bytes), EXPORT(mcmc_sample), EXPORT(mcmc_apply), EXPORT(mcmc_noise),
     };
     napi_define_properties(env, exports, sizeof d / sizeof d[0], d);
     return exports;

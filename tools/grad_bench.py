@@ -42,7 +42,11 @@ tensors (one rate per tensor: torch cannot give the SH plane two without splitti
 and the same five masked with the frame's visibility, alternating in one process; per contender the bytes it moves by the
 28 B-per-parameter count (the masked step: that count over the visible rows, plus the mask) and the share of the 5.1 TB/s copy
 rate that is; and splat_density_accumulate, splat_densify_plan (with its one synchronisation: a host clock around it) and the
-apply pass (splat_densify_geometry, three COPY and ten ZERO_NEW splat_densify_rows) at 3DGS's default thresholds."""
+apply pass (splat_densify_geometry, three COPY and ten ZERO_NEW splat_densify_rows) at 3DGS's default thresholds; and the three
+MCMC kernels on the same cloud: splat_mcmc_noise (the per-step one: 56 B per splat, its GB/s beside a device-to-device copy of the
+same planes timed in the same rounds, the line's measured copy ceiling), splat_mcmc_sample in relocate mode (host clock: it
+synchronises) and splat_mcmc_apply of that sample, on logits drawn N(-1, 2.5), 4 % of them below min_opacity = 0.005 (the bench
+scene itself is opaque)."""
 import ctypes as C
 import json
 import os
@@ -291,7 +295,41 @@ def optimizer_bench(name, k, rounds, stream):
             for mom in (m, v):
                 _lib.check(lib.splat_densify_rows(cx.ctx, rows.data_ptr(), kout, mom[p].data_ptr(), outs[p].data_ptr(), fpr, 1), cx.ctx)
 
-    work = {"torch_foreach": sets["torch_foreach"].step, "torch_fused": sets["torch_fused"].step, "splat_dense": lambda: splat_step(None),
+    # MCMC: the per-step noise, a relocation of the 3 % most transparent splats, and a plain copy of the noise's planes as the ceiling
+    # (the bench scene is opaque: the MCMC kernels get logits of their own, N(-1, 2.5), of which 4 % are below min_opacity = 0.005)
+    mcmc_min_opacity = 0.005
+    mlogits = torch.randn(n, device="cuda", generator=torch.Generator(device="cuda").manual_seed(2)) * 2.5 - 1.0
+    alogits = mlogits.clone()  # (the apply's own: it rewrites the drawn sources' logits at every call)
+    mws_bytes = int(lib.splat_mcmc_sample_workspace_bytes(n))
+    mws = torch.empty(mws_bytes // 4, device="cuda", dtype=torch.int32)
+    mt, ms, mc = (torch.empty(n, device="cuda", dtype=torch.int32) for _ in range(3))
+    mwords = (C.c_uint32 * 3)()
+    mpl = _lib.McmcPlanes()
+    for i, p in enumerate(PLANES):
+        mpl.param[i], mpl.m[i], mpl.v[i] = (alogits if p == "opacity_logits" else ours[p]).data_ptr(), m[p].data_ptr(), v[p].data_ptr()
+    mpl.sh_floats = ours["sh"].shape[1]
+    noise_step = {"t": 0}
+
+    def mcmc_sample():
+        _lib.check(lib.splat_mcmc_sample(cx.ctx, mlogits.data_ptr(), n, _lib.MCMC_RELOCATE, 0, mcmc_min_opacity, 1, mws.data_ptr(),
+                                         mws_bytes, mt.data_ptr(), ms.data_ptr(), mc.data_ptr(), mwords), cx.ctx)
+    mcmc_sample()
+    mcmc_draws, mcmc_counts = int(mwords[2]), {"dead": int(mwords[0]), "alive": int(mwords[1]), "draws": int(mwords[2])}
+
+    def mcmc_apply():  # (in place on the bench's own copies: the same rows every call)
+        _lib.check(lib.splat_mcmc_apply(cx.ctx, mt.data_ptr(), ms.data_ptr(), mc.data_ptr(), n, mcmc_draws, n, mcmc_min_opacity, C.byref(mpl)), cx.ctx)
+
+    def mcmc_noise():
+        noise_step["t"] += 1
+        _lib.check(lib.splat_mcmc_noise(cx.ctx, ours["means"].data_ptr(), ours["log_scales"].data_ptr(), ours["rotations"].data_ptr(),
+                                        mlogits.data_ptr(), n, 5e5 * DEFAULT_LR["means"], noise_step["t"], 1), cx.ctx)
+    copy_src = torch.empty(14 * n, device="cuda")  # 56 B per splat: as much read and written as the noise reads and writes
+    copy_dst = torch.empty_like(copy_src)
+
+    def copy_planes():
+        copy_dst[:7 * n].copy_(copy_src[:7 * n])  # 28 B read + 28 B written per splat
+
+    work = {"mcmc_noise": mcmc_noise, "copy56": copy_planes, "mcmc_apply": mcmc_apply, "torch_foreach": sets["torch_foreach"].step, "torch_fused": sets["torch_fused"].step, "splat_dense": lambda: splat_step(None),
             "splat_masked": lambda: splat_step(vis.data_ptr()), "accumulate": accumulate, "apply": apply}
 
     def run(kind, calls):
@@ -303,21 +341,26 @@ def optimizer_bench(name, k, rounds, stream):
         e1.synchronize()
         return e0.elapsed_time(e1) / calls
 
-    def run_plan(calls):  # (it synchronises: a host clock, the stream idle before and after)
+    def run_host(fn, calls):  # (it synchronises: a host clock, the stream idle before and after)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(calls):
-            plan()
+            fn()
         return (time.perf_counter() - t0) * 1e3 / calls
+
+    def run_plan(calls):
+        return run_host(plan, calls)
 
     for kind in list(work) * 2:
         run(kind, 3)
     run_plan(3)
-    ts = {kind: [] for kind in list(work) + ["plan"]}
+    run_host(mcmc_sample, 3)
+    ts = {kind: [] for kind in list(work) + ["plan", "mcmc_sample"]}
     for _ in range(rounds):
         for kind in work:
             ts[kind].append(run(kind, k))
         ts["plan"].append(run_plan(max(k // 4, 1)))
+        ts["mcmc_sample"].append(run_host(mcmc_sample, max(k // 4, 1)))
     med = {kind: sorted(x)[len(x) // 2] for kind, x in ts.items()}
     moved = {"torch_foreach": 28 * params, "torch_fused": 28 * params, "splat_dense": 28 * params, "splat_masked": 28 * visible_params + 5 * n}
     print(json.dumps({"config": name, "n": n, "width": w, "height": h, "calls_per_round": k, "rounds": rounds, "parameters": params,
@@ -330,6 +373,12 @@ def optimizer_bench(name, k, rounds, stream):
                       "torch_fused_over_splat_dense": round(med["torch_fused"] / med["splat_dense"], 3),
                       "torch_foreach_over_splat_dense": round(med["torch_foreach"] / med["splat_dense"], 3),
                       "splat_dense_over_splat_masked": round(med["splat_dense"] / med["splat_masked"], 3),
+                      "mcmc_noise_us": round(med["mcmc_noise"] * 1e3, 2), "mcmc_noise_GBps": round(56 * n / (med["mcmc_noise"] * 1e-3) / 1e9, 1),
+                      "copy56_us": round(med["copy56"] * 1e3, 2), "copy56_GBps": round(56 * n / (med["copy56"] * 1e-3) / 1e9, 1),
+                      "mcmc_noise_share_of_measured_copy": round(med["copy56"] / med["mcmc_noise"], 3),
+                      "splat_dense_GBps": round(28 * params / (med["splat_dense"] * 1e-3) / 1e9, 1),
+                      "mcmc_min_opacity": mcmc_min_opacity, "mcmc_counts": mcmc_counts,
+                      "mcmc_sample_us": round(med["mcmc_sample"] * 1e3, 1), "mcmc_apply_us": round(med["mcmc_apply"] * 1e3, 2),
                       "plan_counts": {"pruned": counts[0], "kept": counts[1], "cloned": counts[2], "split": counts[3], "rows": kout}}), flush=True)
 
 
