@@ -302,13 +302,25 @@ int tile_sort_launch(splat_ctx *ctx, const uint32_t *offsets, uint32_t tiles, ui
                      uint32_t *counts, uint32_t *frame_flags, uint32_t mean_list, uint32_t band_tiles = 0,
                      uint32_t long_tiles_hint = 0xffffffffu, uint32_t *short_class_io = nullptr); // frame_flags: FRAME_FLAG_ORDER is raised if a list fails the order check
 int binner_settle(splat_binner *b); // resolves a pending report; SPLAT_ERR_CAPACITY if that frame overflowed, SPLAT_ERR_RETRY if its lists failed the order check
-// composite.hip: splat_composite with the frame's report attached (report != NULL: the launch's first workgroup stores
-// {frame_total[0], frame_total[1], seq} into the host-mapped report words; see tile_report)
-int composite_launch(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4, const void *normals,
-                     uint32_t normal_stride_vec4, const void *projected, const void *tile_indices, const void *tile_counts,
-                     const void *tile_offsets, uint32_t width, uint32_t height, void *out_rgba8, void *out_rgba32f, void *consumed_dptr,
-                     const uint32_t *frame_total, uint32_t *report, uint32_t report_seq, const splat_aov *aov = nullptr,
-                     const float *ext_z = nullptr, uint32_t ext_zstride = 0); // ext_z: the AOV depth of splat i is ext_z[i * ext_zstride]
+// composite.hip: what a composite reads and writes — splat_composite_aov's arguments, and for a frame its report and the AOV
+// depth's source
+struct CompositeArgs {
+    const void *color_opacity = nullptr, *normals = nullptr;
+    uint32_t color_stride_vec4 = 1, normal_stride_vec4 = 1;
+    const void *projected = nullptr, *tile_indices = nullptr, *tile_counts = nullptr, *tile_offsets = nullptr;
+    uint32_t width = 0, height = 0;
+    void *out_rgba8 = nullptr, *out_rgba32f = nullptr;
+    void *consumed = nullptr; // per tile {entries staged, entries consumed}, accumulated (or NULL)
+    // report != NULL: the launch's first workgroup stores {frame_total[0], frame_total[1], seq} into the host-mapped report
+    // words (tile_report)
+    const uint32_t *frame_total = nullptr;
+    uint32_t *report = nullptr;
+    uint32_t report_seq = 0;
+    const splat_aov *aov = nullptr;
+    const float *ext_z = nullptr; // the AOV depth of splat i is ext_z[i * ext_zstride] (NULL: the records' own)
+    uint32_t ext_zstride = 0;
+};
+int composite_launch(splat_ctx *ctx, const splat_composite_cfg *cfg, const CompositeArgs &a);
 // The checks of a splat_aov request (aov == NULL: none) a frame makes before its first launch and the composite again:
 // a non-NULL buffer, 16-byte alignment, nearest on top, and for depth, records that carry it (has_depth).
 int aov_check(splat_ctx *ctx, const splat_composite_cfg *cfg, const splat_aov *aov, bool has_depth);

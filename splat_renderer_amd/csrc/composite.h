@@ -5,6 +5,7 @@
 #include "common.h"
 #include "disc.h"
 #include "shade.h"
+#include "variant.h"
 
 typedef float v2f __attribute__((ext_vector_type(2))); // maps onto the packed FP32 instructions (v_pk_*_f32)
 
@@ -169,7 +170,15 @@ __device__ __forceinline__ void fetch_entry(const CompositeParams &p, uint32_t i
     if (!p.prelit) f_n = p.normals[(size_t)idx * p.normal_stride];
 }
 
-// composite_tile.hip: the composite for tile sizes other than CT (p is filled in by composite_launch_checked; rows
-// [r0, r1) of the ntx x nty tiles of cfg->tile_size pixels).  *launched as composite_launch_checked's.
+// Which instantiations of k_composite and k_composite_tile <MODE, EARLY_OUT, DISC, LIT32, AOV, ELL> exist (EARLY_OUT: both):
+// the reference-literal blend is the isotropic footprint's alone and has no auxiliary outputs (aov_check and
+// composite_launch's argument checks refuse the rest); a disc record's lit colour is found at run time (p.disc_lit), not
+// by LIT32; the ellipsoid's records are disc records.
+constexpr bool composite_variant_exists(int mode, bool disc, bool lit32, bool aov, bool ell) {
+    return (mode == SPLAT_COMPOSITE_FRONT_TO_BACK || !(aov || disc)) && !(disc && lit32) && (disc || !ell);
+}
+
+// composite_tile.hip: the composite for tile sizes other than CT (p is filled in by composite_launch; rows [r0, r1) of the
+// ntx x nty tiles of cfg->tile_size pixels).  *launched: whether the launch that carries the frame's report went out.
 int composite_tile_launch(splat_ctx *ctx, const splat_composite_cfg *cfg, const CompositeParams &p, uint32_t nty, uint32_t r0,
                           uint32_t r1, bool *launched);

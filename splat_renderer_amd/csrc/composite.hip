@@ -24,7 +24,6 @@
 // Compiled with -ffp-contract=fast; compared with the oracle within a stated tolerance.
 #include "composite.h"
 
-#include <hip/hip_ext.h>
 
 #include <cstdlib>
 
@@ -1114,12 +1113,8 @@ bool composite_uses_px(const splat_ctx *ctx, uint32_t ntx, uint32_t nty) {
     return kernel == 1 || (kernel == -1 && ntx * nty >= PX_MIN_TILES);
 }
 
+// (p's hint pointers come in as composite_launch initialised them: NULL)
 static int px_order_prepare(splat_ctx *ctx, uint32_t band_tiles, uint64_t key, CompositeParams &p) {
-    p.tile_order = nullptr;
-    p.tile_cost = nullptr;
-    p.order_src = nullptr;
-    p.order_dst = nullptr;
-    p.cost_prev = nullptr;
     const bool predict_on = ctx->opt_px_predict >= 0 ? ctx->opt_px_predict != 0 : g_px_predict_on;
     if (!g_px_order_on && !predict_on) return SPLAT_OK;
     PxHistory *h = nullptr, *lru = &ctx->px_hist[0];
@@ -1212,20 +1207,32 @@ extern "C" int splat_composite(splat_ctx *ctx, const splat_composite_cfg *cfg, c
                                tile_offsets, width, height, out_rgba8, out_rgba32f, consumed_dptr, nullptr);
 }
 
+// lit DISC records (48 bytes: the lit colour behind each disc record) exist only inside a frame's binner; a public caller's
+// disc records are the projector's 32-byte ones (splat_project_disc) or 48-byte exchange records (taken at its
+// word this pair would read idx * 48 out of an n * 32 allocation)
+static bool lit_disc_records(const splat_composite_cfg *cfg) {
+    return cfg && (cfg->footprint == SPLAT_FOOTPRINT_DISC || cfg->footprint == SPLAT_FOOTPRINT_ELLIPSOID) &&
+           cfg->record_format == SPLAT_RECORDS_LIT32;
+}
+
 extern "C" int splat_composite_aov(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity,
                                    uint32_t color_stride_vec4, const void *normals, uint32_t normal_stride_vec4,
                                    const void *projected, const void *tile_indices, const void *tile_counts,
                                    const void *tile_offsets, uint32_t width, uint32_t height, void *out_rgba8, void *out_rgba32f,
                                    void *consumed_dptr, const splat_aov *aov) {
-    // lit DISC records (48 bytes: the lit colour behind each disc record) exist only inside a frame's binner; a public caller's
-    // disc records are the projector's 32-byte ones (splat_project_disc) or 48-byte exchange records (taken at its
-    // word this pair would read idx * 48 out of an n * 32 allocation)
-    if (ctx && cfg && (cfg->footprint == SPLAT_FOOTPRINT_DISC || cfg->footprint == SPLAT_FOOTPRINT_ELLIPSOID) &&
-        cfg->record_format == SPLAT_RECORDS_LIT32)
+    if (ctx && lit_disc_records(cfg))
         return ctx_fail(ctx, SPLAT_ERR_INVALID, "splat_composite: the oriented-disc footprint composites from SPLAT_RECORDS_PROJECTED (32-byte disc "
                                                 "records) or SPLAT_RECORDS_DISC48; lit disc records are internal to splat_render_frame");
-    return composite_launch(ctx, cfg, color_opacity, color_stride_vec4, normals, normal_stride_vec4, projected, tile_indices, tile_counts,
-                            tile_offsets, width, height, out_rgba8, out_rgba32f, consumed_dptr, nullptr, nullptr, 0u, aov);
+    CompositeArgs a;
+    a.color_opacity = color_opacity, a.color_stride_vec4 = color_stride_vec4;
+    a.normals = normals, a.normal_stride_vec4 = normal_stride_vec4;
+    a.projected = projected;
+    a.tile_indices = tile_indices, a.tile_counts = tile_counts, a.tile_offsets = tile_offsets;
+    a.width = width, a.height = height;
+    a.out_rgba8 = out_rgba8, a.out_rgba32f = out_rgba32f;
+    a.consumed = consumed_dptr;
+    a.aov = aov;
+    return composite_launch(ctx, cfg, a);
 }
 
 // splat_composite_aov with the AOV depth of splat i read from depth_f32[i * depth_stride_floats], for every footprint and record
@@ -1237,48 +1244,39 @@ extern "C" int splat_composite_aov_depth(splat_ctx *ctx, const splat_composite_c
                                          void *consumed_dptr, const splat_aov *aov, const void *depth_f32, uint32_t depth_stride_floats) {
     if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
     ARG_CHECK(ctx, depth_f32 != nullptr && depth_stride_floats >= 1 && ((uintptr_t)depth_f32 & 3) == 0);
-    if (cfg && (cfg->footprint == SPLAT_FOOTPRINT_DISC || cfg->footprint == SPLAT_FOOTPRINT_ELLIPSOID) && cfg->record_format == SPLAT_RECORDS_LIT32)
+    if (lit_disc_records(cfg))
         return ctx_fail(ctx, SPLAT_ERR_INVALID, "splat_composite_aov_depth: the oriented-disc footprint composites from SPLAT_RECORDS_PROJECTED "
                                                 "(32-byte disc records) or SPLAT_RECORDS_DISC48; lit disc records are internal to splat_render_frame");
-    return composite_launch(ctx, cfg, color_opacity, color_stride_vec4, normals, normal_stride_vec4, projected, tile_indices, tile_counts,
-                            tile_offsets, width, height, out_rgba8, out_rgba32f, consumed_dptr, nullptr, nullptr, 0u, aov,
-                            (const float *)depth_f32, depth_stride_floats);
+    CompositeArgs a;
+    a.color_opacity = color_opacity, a.color_stride_vec4 = color_stride_vec4;
+    a.normals = normals, a.normal_stride_vec4 = normal_stride_vec4;
+    a.projected = projected;
+    a.tile_indices = tile_indices, a.tile_counts = tile_counts, a.tile_offsets = tile_offsets;
+    a.width = width, a.height = height;
+    a.out_rgba8 = out_rgba8, a.out_rgba32f = out_rgba32f;
+    a.consumed = consumed_dptr;
+    a.aov = aov;
+    a.ext_z = (const float *)depth_f32, a.ext_zstride = depth_stride_floats;
+    return composite_launch(ctx, cfg, a);
 }
 
-static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4,
-                                    const void *normals, uint32_t normal_stride_vec4, const void *projected, const void *tile_indices,
-                                    const void *tile_counts, const void *tile_offsets, uint32_t width, uint32_t height, void *out_rgba8,
-                                    void *out_rgba32f, void *consumed_dptr, const uint32_t *frame_total, uint32_t *report,
-                                    uint32_t report_seq, const splat_aov *aov, const float *ext_z, uint32_t ext_zstride, bool *launched);
-
-// The composite with the frame's report attached.  Whatever happens to the launch, a report that was promised is sent
-// (the host waits for it at its next call).
-int composite_launch(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4, const void *normals,
-                     uint32_t normal_stride_vec4, const void *projected, const void *tile_indices, const void *tile_counts,
-                     const void *tile_offsets, uint32_t width, uint32_t height, void *out_rgba8, void *out_rgba32f, void *consumed_dptr,
-                     const uint32_t *frame_total, uint32_t *report, uint32_t report_seq, const splat_aov *aov, const float *ext_z,
-                     uint32_t ext_zstride) {
-    bool launched = false;
-    const int rc = composite_launch_checked(ctx, cfg, color_opacity, color_stride_vec4, normals, normal_stride_vec4, projected, tile_indices,
-                                            tile_counts, tile_offsets, width, height, out_rgba8, out_rgba32f, consumed_dptr, frame_total, report,
-                                            report_seq, aov, ext_z, ext_zstride, &launched);
-    if (ctx && report && !launched) { // an empty band of tile rows, or a rejected argument: the report goes out on its own
-        hipLaunchKernelGGL(k_frame_report, dim3(1), dim3(1), 0, ctx->stream, frame_total, report, report_seq);
-        (void)hipGetLastError();
-    }
-    return rc;
-}
-
-static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4,
-                                    const void *normals, uint32_t normal_stride_vec4, const void *projected, const void *tile_indices,
-                                    const void *tile_counts, const void *tile_offsets, uint32_t width, uint32_t height, void *out_rgba8,
-                                    void *out_rgba32f, void *consumed_dptr, const uint32_t *frame_total, uint32_t *report,
-                                    uint32_t report_seq, const splat_aov *aov, const float *ext_z, uint32_t ext_zstride, bool *launched) {
+// The composite with the frame's report attached.  Whatever happens to the launch — an empty band of tile rows, a rejected
+// argument, a launch that did not go out — a report that was promised is sent (the host waits for it at its next call): on
+// its own, when this function is left without a composite kernel carrying it.
+int composite_launch(splat_ctx *ctx, const splat_composite_cfg *cfg, const CompositeArgs &a) {
+    struct Promise {
+        splat_ctx *ctx;
+        const CompositeArgs &a;
+        bool launched = false;
+        ~Promise() {
+            if (!ctx || !a.report || launched) return;
+            hipLaunchKernelGGL(k_frame_report, dim3(1), dim3(1), 0, ctx->stream, a.frame_total, a.report, a.report_seq);
+            (void)hipGetLastError();
+        }
+    } report{ctx, a};
     if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
     ARG_CHECK(ctx, cfg != nullptr);
-    // 16x16 tiles: k_composite_px / k_composite, whose quadrant mapping is built for them; any other size the binner
-    // accepts: k_composite_tile (composite_tile.hip)
-    const uint32_t T = cfg->tile_size;
+    const uint32_t T = cfg->tile_size, width = a.width, height = a.height;
     ARG_CHECK(ctx, T >= 1 && T <= 4096);
     ARG_CHECK(ctx, cfg->mode == SPLAT_COMPOSITE_FRONT_TO_BACK || cfg->mode == SPLAT_COMPOSITE_REFERENCE_LITERAL);
     ARG_CHECK(ctx, cfg->record_format <= SPLAT_RECORDS_LIT32);
@@ -1288,11 +1286,11 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
                            : (div_up64(width, T) * div_up(T, CT) <= 65535u && div_up64(height, T) * div_up(T, CT) <= 65535u));
     // the records carry the lit colour (isotropic: 32-byte lit composite records; disc: the colour behind each disc record): no colour / normal arrays
     const bool lit32 = cfg->record_format == SPLAT_RECORDS_LIT32;
-    ARG_CHECK(ctx, lit32 || (color_opacity && (normals || cfg->prelit)));
-    ARG_CHECK(ctx, projected && tile_indices && tile_counts && tile_offsets);
-    ARG_CHECK(ctx, color_stride_vec4 >= 1 && normal_stride_vec4 >= 1);
-    ARG_CHECK(ctx, out_rgba8 || out_rgba32f);
-    ARG_CHECK(ctx, (((uintptr_t)color_opacity | (uintptr_t)normals | (uintptr_t)projected | (uintptr_t)out_rgba32f) & 15) == 0);
+    ARG_CHECK(ctx, lit32 || (a.color_opacity && (a.normals || cfg->prelit)));
+    ARG_CHECK(ctx, a.projected && a.tile_indices && a.tile_counts && a.tile_offsets);
+    ARG_CHECK(ctx, a.color_stride_vec4 >= 1 && a.normal_stride_vec4 >= 1);
+    ARG_CHECK(ctx, a.out_rgba8 || a.out_rgba32f);
+    ARG_CHECK(ctx, (((uintptr_t)a.color_opacity | (uintptr_t)a.normals | (uintptr_t)a.projected | (uintptr_t)a.out_rgba32f) & 15) == 0);
     ARG_CHECK(ctx, cfg->prelit <= 1 && cfg->footprint <= SPLAT_FOOTPRINT_ELLIPSOID);
     // the oriented disc is SequentialRenderer's footprint: nearest-on-top "over" is its only blend, and its
     // records are the projector's 32-byte disc records.  The ellipsoid's records are disc records (ellipsoid.h) under the
@@ -1300,7 +1298,7 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
     ARG_CHECK(ctx, cfg->footprint == SPLAT_FOOTPRINT_ISOTROPIC ||
                        (cfg->mode == SPLAT_COMPOSITE_FRONT_TO_BACK && cfg->record_format != SPLAT_RECORDS_COMPACT));
     ARG_CHECK(ctx, cfg->record_format != SPLAT_RECORDS_DISC48 || cfg->footprint == SPLAT_FOOTPRINT_DISC);
-    ARG_CHECK(ctx, !ext_z || (ext_zstride >= 1 && ((uintptr_t)ext_z & 3) == 0));
+    ARG_CHECK(ctx, !a.ext_z || (a.ext_zstride >= 1 && ((uintptr_t)a.ext_z & 3) == 0));
     // where the auxiliary outputs' depth comes from: float `off` of every record, `stride` floats apart — the ProjectedSplat's
     // depth (SplatProjector.ts:77), which the compact, lit and 48-byte disc records carry as well; the projector's 32-byte
     // disc records carry none (a frame hands its ProjectedSplat records' depth words in as ext_z when it writes them).  A
@@ -1308,18 +1306,19 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
     const bool is_disc = cfg->footprint != SPLAT_FOOTPRINT_ISOTROPIC;
     const float *zsrc = nullptr;
     uint32_t zoff = 0, zstride = 0;
-    if (ext_z) {
-        zsrc = ext_z;
-        zstride = ext_zstride;
+    if (a.ext_z) {
+        zsrc = a.ext_z;
+        zstride = a.ext_zstride;
     } else if (!is_disc) {
-        zsrc = (const float *)projected;
+        zsrc = (const float *)a.projected;
         zoff = cfg->record_format == SPLAT_RECORDS_PROJECTED ? 4u : 3u;
         zstride = cfg->record_format == SPLAT_RECORDS_COMPACT ? 4u : 8u;
     } else if (cfg->record_format == SPLAT_RECORDS_DISC48 || lit32) {
-        zsrc = (const float *)projected; // {disc record, depth, -, -, -} / {disc record, lit r, g, b, depth}
+        zsrc = (const float *)a.projected; // {disc record, depth, -, -, -} / {disc record, lit r, g, b, depth}
         zoff = cfg->record_format == SPLAT_RECORDS_DISC48 ? 8u : 11u;
         zstride = 12u;
     }
+    const splat_aov *aov = a.aov;
     if (aov) {
         const int arc = aov_check(ctx, cfg, aov, zsrc != nullptr);
         if (arc != SPLAT_OK) return arc;
@@ -1328,31 +1327,31 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
     uint32_t r0 = cfg->tile_row0, r1 = cfg->tile_row1 > nty ? nty : cfg->tile_row1;
     if (r0 >= r1) return SPLAT_OK;
     CompositeParams p;
-    p.color = (const float4 *)color_opacity;
-    p.color_stride = color_stride_vec4;
-    p.normals = (const float4 *)normals;
-    p.normal_stride = normal_stride_vec4;
-    p.projected = (const float4 *)projected;
+    p.color = (const float4 *)a.color_opacity;
+    p.color_stride = a.color_stride_vec4;
+    p.normals = (const float4 *)a.normals;
+    p.normal_stride = a.normal_stride_vec4;
+    p.projected = (const float4 *)a.projected;
     p.compact = cfg->record_format == SPLAT_RECORDS_COMPACT;
-    p.lit32 = cfg->record_format == SPLAT_RECORDS_LIT32;
+    p.lit32 = lit32;
     p.prelit = cfg->prelit != 0;
-    p.disc = cfg->footprint != SPLAT_FOOTPRINT_ISOTROPIC;
+    p.disc = is_disc;
     p.disc_stride = (cfg->record_format == SPLAT_RECORDS_DISC48 || (p.disc && lit32)) ? 3u : 2u;
     p.disc_lit = p.disc && lit32;
-    p.indices = (const uint32_t *)tile_indices;
-    p.counts = (const uint32_t *)tile_counts;
-    p.offsets = (const uint32_t *)tile_offsets;
+    p.indices = (const uint32_t *)a.tile_indices;
+    p.counts = (const uint32_t *)a.tile_counts;
+    p.offsets = (const uint32_t *)a.tile_offsets;
     p.width = width;
     p.height = height;
     p.ntx = ntx;
     p.tile_row0 = r0;
-    p.out_rgba8 = (uint32_t *)out_rgba8;
-    p.out_rgba32f = (float4 *)out_rgba32f;
-    p.consumed = (unsigned long long *)consumed_dptr;
-    p.frame_total = frame_total;
-    p.report = report;
-    p.report_seq = report_seq;
-    p.tile_order = nullptr;
+    p.out_rgba8 = (uint32_t *)a.out_rgba8;
+    p.out_rgba32f = (float4 *)a.out_rgba32f;
+    p.consumed = (unsigned long long *)a.consumed;
+    p.frame_total = a.frame_total;
+    p.report = a.report;
+    p.report_seq = a.report_seq;
+    p.tile_order = nullptr; // (k_composite_px's hints: px_order_prepare sets the ones it has)
     p.tile_cost = nullptr;
     p.order_src = nullptr;
     p.order_dst = nullptr;
@@ -1364,41 +1363,19 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
     p.aov_alpha = aov ? (float *)aov->alpha_f32 : nullptr;
     p.aov_id = aov ? (uint32_t *)aov->id_u32 : nullptr;
     // (without a depth to gather the kernels still read one word per entry: stride 0 keeps it on a valid one)
-    p.aov_z = (aov && aov->depth_f32) ? zsrc + zoff : (const float *)tile_counts;
+    p.aov_z = (aov && aov->depth_f32) ? zsrc + zoff : (const float *)a.tile_counts;
     p.aov_zstride = (aov && aov->depth_f32) ? zstride : 0u;
-    const bool want_aov = aov != nullptr;
-    const bool ell = cfg->footprint == SPLAT_FOOTPRINT_ELLIPSOID;
-    if (T != CT) return composite_tile_launch(ctx, cfg, p, nty, r0, r1, launched);
-    dim3 grid(ntx, r1 - r0), block(256);
-    const bool eo = cfg->early_out != 0;
-    // timed runs attach the event pair to the launch itself (no marker packets around the kernel).  The pair is taken right
-    // before the launch, after everything that can fail: a pair that was handed out and never recorded would be read by
-    // splat_stage_time_stats
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
-#define SPLAT_COMPOSITE_LAUNCH1(MODE, EO, DISC, LIT, AOV) SPLAT_COMPOSITE_LAUNCH1_E(MODE, EO, DISC, LIT, AOV, false)
-#define SPLAT_COMPOSITE_LAUNCH1_E(MODE, EO, DISC, LIT, AOV, ELL)                                                                      \
-    do {                                                                                                                        \
-        if (timed) hipExtLaunchKernelGGL((k_composite<MODE, EO, DISC, LIT, AOV, ELL>), grid, block, 0, ctx->stream, ev0, ev1, 0, p); \
-        else hipLaunchKernelGGL((k_composite<MODE, EO, DISC, LIT, AOV, ELL>), grid, block, 0, ctx->stream, p);                     \
-    } while (0)
-    // (the reference-literal blend has no auxiliary outputs: aov_check refused them)
-#define SPLAT_COMPOSITE_LAUNCH(MODE, EO, DISC, LIT)                                                         \
-    do {                                                                                                    \
-        if (MODE == SPLAT_COMPOSITE_FRONT_TO_BACK && want_aov) SPLAT_COMPOSITE_LAUNCH1(SPLAT_COMPOSITE_FRONT_TO_BACK, EO, DISC, LIT, true); \
-        else SPLAT_COMPOSITE_LAUNCH1(MODE, EO, DISC, LIT, false);                                            \
-    } while (0)
-    // Which kernel composites the isotropic footprint nearest-on-top (the frame's default): k_composite_px — one wave per
-    // tile, every lane walking its own entries — unless SPLAT_COMPOSITE=quadrant asks for round 2's k_composite (one
-    // 8x8-pixel wave per quadrant visiting every entry of the tile), which also serves the oriented disc (its footprint is
-    // not separable) and the reference-literal blend.
-    // Which kernel composites the isotropic footprint nearest-on-top (the frame's default): k_composite_px — a builder and
-    // a consumer wave per tile, every lane walking its own entries — on screens of at least PX_MIN_TILES tiles (the whole
-    // screen decides, not the band of tile rows this call renders: the ranks of a multi-GPU frame must run the same
-    // arithmetic for their bands to stitch into the single-GPU image bit for bit); below that (C0's 256 tiles: 18 against
-    // 22 us) and for the oriented disc (its footprint is not separable) and the reference-
-    // literal blend, round 2's k_composite (four waves per tile, each visiting every entry that touches its quadrant).
-    // SPLAT_COMPOSITE=pixel | quadrant forces one of them (composite_uses_px: the ellipsoid backward asks the same rule).
+    // 16x16 tiles: k_composite_px / k_composite, whose quadrant mapping is built for them; any other size the binner
+    // accepts: k_composite_tile (composite_tile.hip)
+    if (T != CT) return composite_tile_launch(ctx, cfg, p, nty, r0, r1, &report.launched);
+    // Which kernel composites 16x16 tiles.  Nearest on top, on screens of at least PX_MIN_TILES tiles: k_composite_px — a
+    // builder and a consumer wave per tile, every lane walking its own entries; the oriented disc and the ellipsoid as well,
+    // their footprint evaluated per queued pixel.  The whole screen decides, not the band of tile rows this call renders: the
+    // ranks of a multi-GPU frame must run the same arithmetic for their bands to stitch into the single-GPU image bit for
+    // bit.  Below that (C0's 256 tiles: 18 against 22 us), and for the reference-literal blend on every screen: round 2's
+    // k_composite — four waves per tile, one per 8x8-pixel quadrant, each visiting every entry that touches its quadrant.
+    // SPLAT_COMPOSITE=pixel | quadrant or splat_composite_options force one of them for the nearest-on-top blend
+    // (composite_uses_px: the ellipsoid backward asks the same rule).
     static bool s_env = false;
     if (!s_env) {
         s_env = true;
@@ -1409,97 +1386,52 @@ static int composite_launch_checked(splat_ctx *ctx, const splat_composite_cfg *c
         const char *ah = getenv("SPLAT_PX_AHEAD");
         g_px_ahead = !ah ? 0 : ah[0] == '1' ? 1 : 2;
     }
-    // Two chunks ahead with lanes running ahead makes 27 % fewer trips, each four instructions longer, on five waves per
-    // SIMD instead of eight (three table buffers): a gain where every list is walked to its end (early-out off: C2 319 ->
-    // 298 us), a loss where most tiles stop after a few chunks and a tile's life is mostly latency (50.6 -> 52.8 us):
-    // profiles/r04_b_px_ab_C2.txt
-    // (the oriented disc keeps eleven numbers per entry instead of tables: a third buffer costs it no resident workgroup)
-    const int opt_ahead = ctx->opt_px_ahead > 0 ? ctx->opt_px_ahead : g_px_ahead > 0 ? g_px_ahead : ((cfg->early_out && !p.disc) ? 1 : 2);
-    const uint32_t band_tiles = ntx * (r1 - r0);
-    const bool use_px = cfg->mode == SPLAT_COMPOSITE_FRONT_TO_BACK && composite_uses_px(ctx, ntx, nty);
-    if (use_px) {
+    const bool eo = cfg->early_out != 0, want_aov = aov != nullptr, ell = cfg->footprint == SPLAT_FOOTPRINT_ELLIPSOID;
+    if (cfg->mode == SPLAT_COMPOSITE_FRONT_TO_BACK && composite_uses_px(ctx, ntx, nty)) {
+        // Two chunks ahead with lanes running ahead makes 27 % fewer trips, each four instructions longer, on five waves per
+        // SIMD instead of eight (three table buffers): a gain where every list is walked to its end (early-out off: C2 319 ->
+        // 298 us), a loss where most tiles stop after a few chunks and a tile's life is mostly latency (50.6 -> 52.8 us):
+        // profiles/r04_b_px_ab_C2.txt
+        // (the oriented disc keeps eleven numbers per entry instead of tables: a third buffer costs it no resident workgroup)
+        const int ahead = ctx->opt_px_ahead > 0 ? ctx->opt_px_ahead : g_px_ahead > 0 ? g_px_ahead : ((eo && !p.disc) ? 1 : 2);
+        const uint32_t band_tiles = ntx * (r1 - r0);
         // (the band, the screen, and whose lists these are: two binners on one context do not share a history)
         const uint64_t key = (((uint64_t)ntx << 40) ^ ((uint64_t)r0 << 20) ^ (uint64_t)r1 ^ ((uint64_t)width << 50) ^
-                              ((uint64_t)(uintptr_t)tile_counts * 0x9E3779B97F4A7C15ull)) | 1u;
-        int orc = px_order_prepare(ctx, band_tiles, key, p);
+                              ((uint64_t)(uintptr_t)a.tile_counts * 0x9E3779B97F4A7C15ull)) | 1u;
+        const int orc = px_order_prepare(ctx, band_tiles, key, p);
         if (orc != SPLAT_OK) return orc;
 #ifdef SPLAT_TEST_HOOKS
         if (ctx->debug_tile_order) p.tile_order = ctx->debug_tile_order;
 #endif
-        timed = stage_event_pair(ctx, SPLAT_STAGE_COMPOSITE, &ev0, &ev1);
         // one workgroup of two waves (consumer, builder) per tile, behind workgroup 0 (report, next launch's tile order)
-        const dim3 pgrid(band_tiles + 1u), pblock(128);
-#define SPLAT_COMPOSITE_PX_LAUNCH3(EO, LIT, CNT, AH, DISC, AOV)                                                                  \
-    do {                                                                                                                        \
-        if (ell) {                                                                                                              \
-            if (timed) hipExtLaunchKernelGGL((k_composite_px<EO, LIT, CNT, AH, DISC, AOV, true>), pgrid, pblock, 0, ctx->stream, ev0, ev1, 0, p, band_tiles); \
-            else hipLaunchKernelGGL((k_composite_px<EO, LIT, CNT, AH, DISC, AOV, true>), pgrid, pblock, 0, ctx->stream, p, band_tiles);                       \
-        } else if (timed) hipExtLaunchKernelGGL((k_composite_px<EO, LIT, CNT, AH, DISC, AOV>), pgrid, pblock, 0, ctx->stream, ev0, ev1, 0, p, band_tiles); \
-        else hipLaunchKernelGGL((k_composite_px<EO, LIT, CNT, AH, DISC, AOV>), pgrid, pblock, 0, ctx->stream, p, band_tiles);                       \
-    } while (0)
-#define SPLAT_COMPOSITE_PX_LAUNCH2(EO, LIT, CNT, AH, DISC)                          \
-    do {                                                                           \
-        if (want_aov) SPLAT_COMPOSITE_PX_LAUNCH3(EO, LIT, CNT, AH, DISC, true);    \
-        else          SPLAT_COMPOSITE_PX_LAUNCH3(EO, LIT, CNT, AH, DISC, false);   \
-    } while (0)
-#define SPLAT_COMPOSITE_PX_LAUNCH(EO, LIT, DISC)                                       \
-    do {                                                                               \
-        if (opt_ahead == 2) {                                                          \
-            if (p.consumed) SPLAT_COMPOSITE_PX_LAUNCH2(EO, LIT, true, 2, DISC);        \
-            else            SPLAT_COMPOSITE_PX_LAUNCH2(EO, LIT, false, 2, DISC);       \
-        } else {                                                                       \
-            if (p.consumed) SPLAT_COMPOSITE_PX_LAUNCH2(EO, LIT, true, 1, DISC);        \
-            else            SPLAT_COMPOSITE_PX_LAUNCH2(EO, LIT, false, 1, DISC);       \
-        }                                                                              \
-    } while (0)
-        if (p.disc) { // the oriented disc (and the ellipsoid): per-lane queues as well, the footprint evaluated per queued pixel
-            if (eo) SPLAT_COMPOSITE_PX_LAUNCH(true, false, true);
-            else    SPLAT_COMPOSITE_PX_LAUNCH(false, false, true);
-        } else if (lit32) {
-            if (eo) SPLAT_COMPOSITE_PX_LAUNCH(true, true, false);
-            else    SPLAT_COMPOSITE_PX_LAUNCH(false, true, false);
-        } else {
-            if (eo) SPLAT_COMPOSITE_PX_LAUNCH(true, false, false);
-            else    SPLAT_COMPOSITE_PX_LAUNCH(false, false, false);
-        }
-#undef SPLAT_COMPOSITE_PX_LAUNCH3
-#undef SPLAT_COMPOSITE_PX_LAUNCH2
-#undef SPLAT_COMPOSITE_PX_LAUNCH
-        *launched = hipPeekAtLastError() == hipSuccess; // (only a launch that went out carries the frame's report: composite_launch sends it otherwise)
+        const bool ok = variant_dispatch(
+            [&](auto eo_, auto lit, auto cnt, auto ah, auto disc, auto aov_, auto ell_) {
+                // a disc record's lit colour is found at run time (p.disc_lit), not by LIT.  (ELL is left free, as it has always
+                // been: it is instantiated for DISC = false as well — 32 kernels no call reaches, the ellipsoid's records being
+                // disc records — which keeps this file's device code what it was)
+                if constexpr (!(disc.value && lit.value)) {
+                    launch_kernel(ctx, SPLAT_STAGE_COMPOSITE, k_composite_px<eo_.value, lit.value, cnt.value, ah.value, disc.value, aov_.value, ell_.value>,
+                                  dim3(band_tiles + 1u), dim3(128), p, band_tiles);
+                    return true;
+                } else return false;
+            },
+            eo, lit32 && !p.disc, p.consumed != nullptr, OneOf<1, 2>{ahead == 2 ? 2 : 1}, p.disc != 0, want_aov, ell);
+        if (!ok) return ctx_fail(ctx, SPLAT_ERR_INVALID, "k_composite_px: no kernel for this footprint and record format");
+        report.launched = hipPeekAtLastError() == hipSuccess; // (only a launch that went out carries the frame's report)
         LAUNCH_CHECK(ctx, "k_composite_px");
         return SPLAT_OK;
     }
-    timed = stage_event_pair(ctx, SPLAT_STAGE_COMPOSITE, &ev0, &ev1);
-    if (ell) {
-        constexpr int F2B = SPLAT_COMPOSITE_FRONT_TO_BACK;
-        if (eo && want_aov) SPLAT_COMPOSITE_LAUNCH1_E(F2B, true, true, false, true, true);
-        else if (eo)        SPLAT_COMPOSITE_LAUNCH1_E(F2B, true, true, false, false, true);
-        else if (want_aov)  SPLAT_COMPOSITE_LAUNCH1_E(F2B, false, true, false, true, true);
-        else                SPLAT_COMPOSITE_LAUNCH1_E(F2B, false, true, false, false, true);
-    } else if (p.disc) {
-        if (eo) SPLAT_COMPOSITE_LAUNCH(SPLAT_COMPOSITE_FRONT_TO_BACK, true, true, false);
-        else    SPLAT_COMPOSITE_LAUNCH(SPLAT_COMPOSITE_FRONT_TO_BACK, false, true, false);
-    } else if (cfg->mode == SPLAT_COMPOSITE_FRONT_TO_BACK) {
-        if (lit32) {
-            if (eo) SPLAT_COMPOSITE_LAUNCH(SPLAT_COMPOSITE_FRONT_TO_BACK, true, false, true);
-            else    SPLAT_COMPOSITE_LAUNCH(SPLAT_COMPOSITE_FRONT_TO_BACK, false, false, true);
-        } else {
-            if (eo) SPLAT_COMPOSITE_LAUNCH(SPLAT_COMPOSITE_FRONT_TO_BACK, true, false, false);
-            else    SPLAT_COMPOSITE_LAUNCH(SPLAT_COMPOSITE_FRONT_TO_BACK, false, false, false);
-        }
-    } else {
-        if (lit32) {
-            if (eo) SPLAT_COMPOSITE_LAUNCH(SPLAT_COMPOSITE_REFERENCE_LITERAL, true, false, true);
-            else    SPLAT_COMPOSITE_LAUNCH(SPLAT_COMPOSITE_REFERENCE_LITERAL, false, false, true);
-        } else {
-            if (eo) SPLAT_COMPOSITE_LAUNCH(SPLAT_COMPOSITE_REFERENCE_LITERAL, true, false, false);
-            else    SPLAT_COMPOSITE_LAUNCH(SPLAT_COMPOSITE_REFERENCE_LITERAL, false, false, false);
-        }
-    }
-#undef SPLAT_COMPOSITE_LAUNCH1
-#undef SPLAT_COMPOSITE_LAUNCH1_E
-#undef SPLAT_COMPOSITE_LAUNCH
-    *launched = hipPeekAtLastError() == hipSuccess;
+    const bool ok = variant_dispatch(
+        [&](auto mode, auto eo_, auto disc, auto lit, auto aov_, auto ell_) {
+            if constexpr (composite_variant_exists(mode.value, disc.value, lit.value, aov_.value, ell_.value)) {
+                launch_kernel(ctx, SPLAT_STAGE_COMPOSITE, k_composite<mode.value, eo_.value, disc.value, lit.value, aov_.value, ell_.value>,
+                              dim3(ntx, r1 - r0), dim3(256), p);
+                return true;
+            } else return false;
+        },
+        OneOf<SPLAT_COMPOSITE_FRONT_TO_BACK, SPLAT_COMPOSITE_REFERENCE_LITERAL>{(int)cfg->mode}, eo, p.disc != 0, lit32 && !p.disc, want_aov, ell);
+    if (!ok) return ctx_fail(ctx, SPLAT_ERR_INVALID, "k_composite: no kernel for this footprint, record format, blend and outputs");
+    report.launched = hipPeekAtLastError() == hipSuccess;
     LAUNCH_CHECK(ctx, "k_composite");
     return SPLAT_OK;
 }

@@ -16,7 +16,6 @@
 // Compiled with -ffp-contract=on as composite.hip; compared with the oracle within the same tolerance.
 #include "composite.h"
 
-#include <hip/hip_ext.h>
 
 // AOV: also the auxiliary outputs (splat_aov; nearest-on-top only): per staged entry {depth, splat index} beside its
 // parameters, per pixel an AovPixel fed with the colour's own weight
@@ -341,55 +340,19 @@ int composite_tile_launch(splat_ctx *ctx, const splat_composite_cfg *cfg, const 
         }
         win_counts = ctx->d_window_counts;
     }
-    const bool eo = cfg->early_out != 0, lit32 = cfg->record_format == SPLAT_RECORDS_LIT32;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    const bool timed = stage_event_pair(ctx, SPLAT_STAGE_COMPOSITE, &ev0, &ev1); // (after everything that can fail: composite.hip)
-#define SPLAT_COMPOSITE_TILE_LAUNCH1(MODE, EO, DISC, LIT, AOV)                                                                         \
-    do {                                                                                                                              \
-        if (timed) hipExtLaunchKernelGGL((k_composite_tile<MODE, EO, DISC, LIT, AOV>), grid, block, 0, ctx->stream, ev0, ev1, 0, p, T, wpt, win_counts); \
-        else hipLaunchKernelGGL((k_composite_tile<MODE, EO, DISC, LIT, AOV>), grid, block, 0, ctx->stream, p, T, wpt, win_counts);                       \
-    } while (0)
     // (the auxiliary outputs are nearest-on-top only: composite.hip's aov_check refused them for the reference-literal blend)
     const bool want_aov = p.aov_depth || p.aov_alpha || p.aov_id;
-#define SPLAT_COMPOSITE_TILE_LAUNCH(MODE, EO, DISC, LIT)                                                                  \
-    do {                                                                                                                  \
-        if (MODE == SPLAT_COMPOSITE_FRONT_TO_BACK && want_aov) SPLAT_COMPOSITE_TILE_LAUNCH1(SPLAT_COMPOSITE_FRONT_TO_BACK, EO, DISC, LIT, true); \
-        else SPLAT_COMPOSITE_TILE_LAUNCH1(MODE, EO, DISC, LIT, false);                                                     \
-    } while (0)
-    if (cfg->footprint == SPLAT_FOOTPRINT_ELLIPSOID) {
-        constexpr int F2B = SPLAT_COMPOSITE_FRONT_TO_BACK;
-#define SPLAT_COMPOSITE_TILE_LAUNCH_ELL(EO, AOV)                                                                                                       \
-    do {                                                                                                                                               \
-        if (timed) hipExtLaunchKernelGGL((k_composite_tile<F2B, EO, true, false, AOV, true>), grid, block, 0, ctx->stream, ev0, ev1, 0, p, T, wpt, win_counts); \
-        else hipLaunchKernelGGL((k_composite_tile<F2B, EO, true, false, AOV, true>), grid, block, 0, ctx->stream, p, T, wpt, win_counts);                       \
-    } while (0)
-        if (eo && want_aov) SPLAT_COMPOSITE_TILE_LAUNCH_ELL(true, true);
-        else if (eo)        SPLAT_COMPOSITE_TILE_LAUNCH_ELL(true, false);
-        else if (want_aov)  SPLAT_COMPOSITE_TILE_LAUNCH_ELL(false, true);
-        else                SPLAT_COMPOSITE_TILE_LAUNCH_ELL(false, false);
-#undef SPLAT_COMPOSITE_TILE_LAUNCH_ELL
-    } else if (p.disc) {
-        if (eo) SPLAT_COMPOSITE_TILE_LAUNCH(SPLAT_COMPOSITE_FRONT_TO_BACK, true, true, false);
-        else    SPLAT_COMPOSITE_TILE_LAUNCH(SPLAT_COMPOSITE_FRONT_TO_BACK, false, true, false);
-    } else if (cfg->mode == SPLAT_COMPOSITE_FRONT_TO_BACK) {
-        if (lit32) {
-            if (eo) SPLAT_COMPOSITE_TILE_LAUNCH(SPLAT_COMPOSITE_FRONT_TO_BACK, true, false, true);
-            else    SPLAT_COMPOSITE_TILE_LAUNCH(SPLAT_COMPOSITE_FRONT_TO_BACK, false, false, true);
-        } else {
-            if (eo) SPLAT_COMPOSITE_TILE_LAUNCH(SPLAT_COMPOSITE_FRONT_TO_BACK, true, false, false);
-            else    SPLAT_COMPOSITE_TILE_LAUNCH(SPLAT_COMPOSITE_FRONT_TO_BACK, false, false, false);
-        }
-    } else {
-        if (lit32) {
-            if (eo) SPLAT_COMPOSITE_TILE_LAUNCH(SPLAT_COMPOSITE_REFERENCE_LITERAL, true, false, true);
-            else    SPLAT_COMPOSITE_TILE_LAUNCH(SPLAT_COMPOSITE_REFERENCE_LITERAL, false, false, true);
-        } else {
-            if (eo) SPLAT_COMPOSITE_TILE_LAUNCH(SPLAT_COMPOSITE_REFERENCE_LITERAL, true, false, false);
-            else    SPLAT_COMPOSITE_TILE_LAUNCH(SPLAT_COMPOSITE_REFERENCE_LITERAL, false, false, false);
-        }
-    }
-#undef SPLAT_COMPOSITE_TILE_LAUNCH1
-#undef SPLAT_COMPOSITE_TILE_LAUNCH
+    const bool ok = variant_dispatch(
+        [&](auto mode, auto eo, auto disc, auto lit, auto aov, auto ell) {
+            if constexpr (composite_variant_exists(mode.value, disc.value, lit.value, aov.value, ell.value)) {
+                launch_kernel(ctx, SPLAT_STAGE_COMPOSITE, k_composite_tile<mode.value, eo.value, disc.value, lit.value, aov.value, ell.value>,
+                              grid, block, p, T, wpt, win_counts);
+                return true;
+            } else return false;
+        },
+        OneOf<SPLAT_COMPOSITE_FRONT_TO_BACK, SPLAT_COMPOSITE_REFERENCE_LITERAL>{(int)cfg->mode}, cfg->early_out != 0, p.disc != 0,
+        p.lit32 && !p.disc, want_aov, cfg->footprint == SPLAT_FOOTPRINT_ELLIPSOID);
+    if (!ok) return ctx_fail(ctx, SPLAT_ERR_INVALID, "k_composite_tile: no kernel for this footprint, record format, blend and outputs");
     *launched = hipPeekAtLastError() == hipSuccess;
     LAUNCH_CHECK(ctx, "k_composite_tile");
     if (win_counts) {

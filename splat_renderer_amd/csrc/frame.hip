@@ -566,8 +566,16 @@ int splat_band_frame(splat_ctx *ctx, splat_sorter *sorter, splat_binner *binner,
         c2.tile_row1 = row1;
         uint32_t *report = binner->report_for_composite; // (the frame's last kernel reports it: common.h)
         binner->report_for_composite = nullptr;
-        return composite_launch(ctx, &c2, band_color, band_color_stride, normals, 1, records, binner->pairs.payload, binner->counts, binner->offsets, width, height, out_rgba8, out_rgba32f, consumed_dptr,
-                                binner->d_total, report, binner->report_seq);
+        CompositeArgs a;
+        a.color_opacity = band_color, a.color_stride_vec4 = band_color_stride;
+        a.normals = normals;
+        a.projected = records;
+        a.tile_indices = binner->pairs.payload, a.tile_counts = binner->counts, a.tile_offsets = binner->offsets;
+        a.width = width, a.height = height;
+        a.out_rgba8 = out_rgba8, a.out_rgba32f = out_rgba32f;
+        a.consumed = consumed_dptr;
+        a.frame_total = binner->d_total, a.report = report, a.report_seq = binner->report_seq;
+        return composite_launch(ctx, &c2, a);
     }
     sorter->kept_blocks = 0;
     // keep -> sort -> bin with the kept count living on the device: no host round trip in here
@@ -825,9 +833,19 @@ static int render_frame_impl(splat_ctx *ctx, splat_sorter *sorter, splat_binner 
     const void *records = disc ? (n ? (const void *)binner->discs : (projected ? projected : (const void *)counts)) : projected;
     uint32_t *report = binner->report_for_composite; // (tile-first frames: the frame's last kernel reports it: common.h)
     binner->report_for_composite = nullptr;
-    return composite_launch(ctx, cfg, color, color_stride, normals, 1, records, indices, counts, offsets, width, height, out_rgba8,
-                            out_rgba32f, (ctx->timing && (ctx->timing_mask & SPLAT_TIMING_COUNT_ENTRIES)) ? (void *)ctx->d_consumed : nullptr, binner->d_total,
-                            report, binner->report_seq, aov, (disc && !disc_lit && projected) ? (const float *)projected + 4 : nullptr, 8u);
+    CompositeArgs a;
+    a.color_opacity = color, a.color_stride_vec4 = color_stride;
+    a.normals = normals;
+    a.projected = records;
+    a.tile_indices = indices, a.tile_counts = counts, a.tile_offsets = offsets;
+    a.width = width, a.height = height;
+    a.out_rgba8 = out_rgba8, a.out_rgba32f = out_rgba32f;
+    a.consumed = (ctx->timing && (ctx->timing_mask & SPLAT_TIMING_COUNT_ENTRIES)) ? (void *)ctx->d_consumed : nullptr;
+    a.frame_total = binner->d_total, a.report = report, a.report_seq = binner->report_seq;
+    a.aov = aov;
+    // (32-byte disc records carry no depth: the ProjectedSplat records' depth words, when the frame writes them)
+    a.ext_z = (disc && !disc_lit && projected) ? (const float *)projected + 4 : nullptr, a.ext_zstride = 8u;
+    return composite_launch(ctx, cfg, a);
 }
 
 extern "C" {

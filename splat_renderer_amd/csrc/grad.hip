@@ -30,6 +30,7 @@
 //   same bits on every run.  The instantiations without CAM are the kernels above,
 //   instruction for instruction.
 #include "common.h"
+#include "variant.h"
 #include "disc.h"
 #include "ellipsoid.h"
 
@@ -627,13 +628,13 @@ __global__ __launch_bounds__(256) void k_sh_colors_backward(float ex, float ey, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The checks both composite backwards make, and the colour-only kernel's parameters (rc != SPLAT_OK: refused; ntx == 0: nothing
-// to launch)
-static int composite_backward_setup(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4,
-                                    const void *records, const void *tile_indices, const void *tile_counts, const void *tile_offsets,
-                                    uint32_t width, uint32_t height, const void *grad_rgba32f, uint32_t n, void *grad_records,
-                                    void *grad_color_opacity, BackParams &p, uint32_t &nty) {
-    p.ntx = 0;
+// The two composite backwards: their checks, the kernel's parameters and the launch.  depth: splat_composite_backward_depth,
+// with its four further arguments.
+static int composite_backward_launch(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4,
+                                     const void *records, const void *tile_indices, const void *tile_counts, const void *tile_offsets,
+                                     uint32_t width, uint32_t height, const void *grad_rgba32f, uint32_t n, void *grad_records,
+                                     void *grad_color_opacity, bool depth, const void *depth_f32, uint32_t depth_stride_floats,
+                                     const void *grad_depth_f32, void *grad_depth) {
     if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
     ARG_CHECK(ctx, cfg != nullptr);
     if (cfg->footprint != SPLAT_FOOTPRINT_ELLIPSOID || cfg->mode != SPLAT_COMPOSITE_FRONT_TO_BACK || cfg->early_out != 1 ||
@@ -641,8 +642,7 @@ static int composite_backward_setup(splat_ctx *ctx, const splat_composite_cfg *c
         return ctx_fail(ctx, SPLAT_ERR_INVALID, "splat_composite_backward: footprint ELLIPSOID, FRONT_TO_BACK, early_out = 1, tile_size = 16 "
                                                 "and PROJECTED records only");
     ARG_CHECK(ctx, width >= 1 && height >= 1 && width <= 65535u * GT && height <= 65535u * GT);
-    const uint32_t ntx = div_up(width, GT);
-    nty = div_up(height, GT);
+    const uint32_t ntx = div_up(width, GT), nty = div_up(height, GT);
     ARG_CHECK(ctx, cfg->tile_row0 == 0 && cfg->tile_row1 >= nty); // the whole screen: no strict band
     ARG_CHECK(ctx, color_stride_vec4 >= 1);
     ARG_CHECK(ctx, color_opacity && records && tile_indices && tile_counts && tile_offsets && grad_rgba32f);
@@ -650,7 +650,12 @@ static int composite_backward_setup(splat_ctx *ctx, const splat_composite_cfg *c
     ARG_CHECK(ctx, (((uintptr_t)color_opacity | (uintptr_t)records | (uintptr_t)grad_rgba32f | (uintptr_t)grad_records |
                      (uintptr_t)grad_color_opacity) & 15) == 0);
     ARG_CHECK(ctx, (((uintptr_t)tile_indices | (uintptr_t)tile_counts | (uintptr_t)tile_offsets) & 3) == 0);
+    if (depth) {
+        ARG_CHECK(ctx, depth_f32 && grad_depth_f32 && (n == 0 || grad_depth) && depth_stride_floats >= 1);
+        ARG_CHECK(ctx, (((uintptr_t)depth_f32 | (uintptr_t)grad_depth_f32 | (uintptr_t)grad_depth) & 3) == 0);
+    }
     if (n == 0) return SPLAT_OK; // (no splat: every list is empty)
+    BackDepthParams p;
     p.color = (const float4 *)color_opacity;
     p.color_stride = color_stride_vec4;
     p.records = (const float4 *)records;
@@ -663,22 +668,22 @@ static int composite_backward_setup(splat_ctx *ctx, const splat_composite_cfg *c
     p.grad_img = (const float4 *)grad_rgba32f;
     p.grad_records = (float *)grad_records;
     p.grad_color = (float *)grad_color_opacity;
-    return SPLAT_OK;
+    p.z = (const float *)depth_f32;
+    p.z_stride = depth_stride_floats;
+    p.grad_depth_img = (const float *)grad_depth_f32;
+    p.grad_depth = (float *)grad_depth;
+    // (<DEPTH, PX>: the kernel without DEPTH takes the BackParams part of p)
+    variant_dispatch([&](auto d, auto px) { launch_kernel(ctx, NO_STAGE, k_composite_backward<d.value, px.value>, dim3(ntx, nty), dim3(256), p); },
+                     depth, composite_uses_px(ctx, ntx, nty));
+    return launch_check(ctx, depth ? "launch k_composite_backward<DEPTH>" : "launch k_composite_backward");
 }
 
 extern "C" int splat_composite_backward(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4,
                                         const void *records, const void *tile_indices, const void *tile_counts, const void *tile_offsets,
                                         uint32_t width, uint32_t height, const void *grad_rgba32f, uint32_t n, void *grad_records,
                                         void *grad_color_opacity) {
-    BackParams p;
-    uint32_t nty = 0;
-    const int rc = composite_backward_setup(ctx, cfg, color_opacity, color_stride_vec4, records, tile_indices, tile_counts, tile_offsets, width,
-                                            height, grad_rgba32f, n, grad_records, grad_color_opacity, p, nty);
-    if (rc != SPLAT_OK || p.ntx == 0) return rc;
-    if (composite_uses_px(ctx, p.ntx, nty)) hipLaunchKernelGGL((k_composite_backward<false, true>), dim3(p.ntx, nty), dim3(256), 0, ctx->stream, p);
-    else hipLaunchKernelGGL((k_composite_backward<false, false>), dim3(p.ntx, nty), dim3(256), 0, ctx->stream, p);
-    LAUNCH_CHECK(ctx, "k_composite_backward");
-    return SPLAT_OK;
+    return composite_backward_launch(ctx, cfg, color_opacity, color_stride_vec4, records, tile_indices, tile_counts, tile_offsets, width, height,
+                                     grad_rgba32f, n, grad_records, grad_color_opacity, false, nullptr, 0, nullptr, nullptr);
 }
 
 extern "C" int splat_composite_backward_depth(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity,
@@ -686,96 +691,16 @@ extern "C" int splat_composite_backward_depth(splat_ctx *ctx, const splat_compos
                                               const void *tile_offsets, uint32_t width, uint32_t height, const void *grad_rgba32f, uint32_t n,
                                               void *grad_records, void *grad_color_opacity, const void *depth_f32, uint32_t depth_stride_floats,
                                               const void *grad_depth_f32, void *grad_depth) {
-    BackDepthParams p;
-    uint32_t nty = 0;
-    const int rc = composite_backward_setup(ctx, cfg, color_opacity, color_stride_vec4, records, tile_indices, tile_counts, tile_offsets, width,
-                                            height, grad_rgba32f, n, grad_records, grad_color_opacity, p, nty);
-    if (rc != SPLAT_OK) return rc;
-    ARG_CHECK(ctx, depth_f32 && grad_depth_f32 && (n == 0 || grad_depth) && depth_stride_floats >= 1);
-    ARG_CHECK(ctx, (((uintptr_t)depth_f32 | (uintptr_t)grad_depth_f32 | (uintptr_t)grad_depth) & 3) == 0);
-    if (p.ntx == 0) return SPLAT_OK;
-    p.z = (const float *)depth_f32;
-    p.z_stride = depth_stride_floats;
-    p.grad_depth_img = (const float *)grad_depth_f32;
-    p.grad_depth = (float *)grad_depth;
-    if (composite_uses_px(ctx, p.ntx, nty)) hipLaunchKernelGGL((k_composite_backward<true, true>), dim3(p.ntx, nty), dim3(256), 0, ctx->stream, p);
-    else hipLaunchKernelGGL((k_composite_backward<true, false>), dim3(p.ntx, nty), dim3(256), 0, ctx->stream, p);
-    LAUNCH_CHECK(ctx, "k_composite_backward<DEPTH>");
-    return SPLAT_OK;
-}
-
-extern "C" int splat_project_ellipsoid_backward(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4,
-                                                const void *scales, uint32_t scale_stride_vec4, const void *rotations, uint32_t rot_stride_vec4,
-                                                uint32_t n, const void *grad_records, void *grad_positions, void *grad_scales, void *grad_rotations) {
-    if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
-    ARG_CHECK(ctx, uniforms && (n == 0 || (positions && scales && rotations && grad_records && grad_positions && grad_scales && grad_rotations)));
-    ARG_CHECK(ctx, pos_stride_vec4 >= 1 && scale_stride_vec4 >= 1 && rot_stride_vec4 >= 1);
-    ARG_CHECK(ctx, (((uintptr_t)positions | (uintptr_t)scales | (uintptr_t)rotations | (uintptr_t)grad_records | (uintptr_t)grad_positions |
-                     (uintptr_t)grad_scales | (uintptr_t)grad_rotations) & 15) == 0);
-    if (n == 0) return SPLAT_OK;
-    GradUniforms u;
-    for (int k = 0; k < 22; ++k) (&u.m[0])[k] = uniforms[k];
-    hipLaunchKernelGGL(k_project_ellipsoid_backward<false>, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, u, (const float4 *)positions,
-                       pos_stride_vec4, (const float4 *)scales, scale_stride_vec4, (const float4 *)rotations, rot_stride_vec4, n,
-                       (const float4 *)grad_records, (float4 *)grad_positions, (float4 *)grad_scales, (float4 *)grad_rotations,
-                       (const float *)nullptr);
-    LAUNCH_CHECK(ctx, "k_project_ellipsoid_backward");
-    return SPLAT_OK;
-}
-
-extern "C" int splat_project_ellipsoid_backward_depth(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4,
-                                                      const void *scales, uint32_t scale_stride_vec4, const void *rotations,
-                                                      uint32_t rot_stride_vec4, uint32_t n, const void *grad_records, void *grad_positions,
-                                                      void *grad_scales, void *grad_rotations, const void *grad_depth) {
-    if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
-    ARG_CHECK(ctx, uniforms && (n == 0 || (positions && scales && rotations && grad_records && grad_positions && grad_scales && grad_rotations &&
-                                           grad_depth)));
-    ARG_CHECK(ctx, pos_stride_vec4 >= 1 && scale_stride_vec4 >= 1 && rot_stride_vec4 >= 1);
-    ARG_CHECK(ctx, (((uintptr_t)positions | (uintptr_t)scales | (uintptr_t)rotations | (uintptr_t)grad_records | (uintptr_t)grad_positions |
-                     (uintptr_t)grad_scales | (uintptr_t)grad_rotations) & 15) == 0 && ((uintptr_t)grad_depth & 3) == 0);
-    if (n == 0) return SPLAT_OK;
-    GradUniforms u;
-    for (int k = 0; k < 22; ++k) (&u.m[0])[k] = uniforms[k];
-    hipLaunchKernelGGL(k_project_ellipsoid_backward<true>, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, u, (const float4 *)positions,
-                       pos_stride_vec4, (const float4 *)scales, scale_stride_vec4, (const float4 *)rotations, rot_stride_vec4, n,
-                       (const float4 *)grad_records, (float4 *)grad_positions, (float4 *)grad_scales, (float4 *)grad_rotations,
-                       (const float *)grad_depth);
-    LAUNCH_CHECK(ctx, "k_project_ellipsoid_backward<DEPTH>");
-    return SPLAT_OK;
-}
-
-extern "C" int splat_sh_colors_backward(splat_ctx *ctx, const float *eye3, const void *positions, uint32_t pos_stride_vec4, const void *sh,
-                                        uint32_t sh_stride_floats, uint32_t degree, const void *opacity_f32, const void *grad_color_opacity,
-                                        uint32_t n, void *grad_sh, void *grad_positions, void *grad_opacity) {
-    if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
-    ARG_CHECK(ctx, eye3 && degree <= 3 && pos_stride_vec4 >= 1);
-    ARG_CHECK(ctx, n == 0 || (positions && sh && grad_color_opacity && grad_sh && grad_positions && grad_opacity));
-    ARG_CHECK(ctx, sh_stride_floats >= 3 * (degree + 1) * (degree + 1));
-    ARG_CHECK(ctx, (((uintptr_t)positions | (uintptr_t)grad_color_opacity | (uintptr_t)grad_positions) & 15) == 0 &&
-                       (((uintptr_t)sh | (uintptr_t)grad_sh | (uintptr_t)grad_opacity | (uintptr_t)opacity_f32) & 3) == 0);
-    if (n == 0) return SPLAT_OK;
-    const dim3 grid(div_up(n, 256)), block(256);
-#define SPLAT_SHB_LAUNCH(D)                                                                                                                 \
-    hipLaunchKernelGGL((k_sh_colors_backward<D>), grid, block, 0, ctx->stream, eye3[0], eye3[1], eye3[2], (const float4 *)positions,       \
-                       pos_stride_vec4, (const float *)sh, sh_stride_floats, (const float4 *)grad_color_opacity, n, (float *)grad_sh,       \
-                       (float4 *)grad_positions, (float *)grad_opacity)
-    switch (degree) {
-    case 0: SPLAT_SHB_LAUNCH(0); break;
-    case 1: SPLAT_SHB_LAUNCH(1); break;
-    case 2: SPLAT_SHB_LAUNCH(2); break;
-    default: SPLAT_SHB_LAUNCH(3); break;
-    }
-#undef SPLAT_SHB_LAUNCH
-    LAUNCH_CHECK(ctx, "k_sh_colors_backward");
-    return SPLAT_OK;
+    return composite_backward_launch(ctx, cfg, color_opacity, color_stride_vec4, records, tile_indices, tile_counts, tile_offsets, width, height,
+                                     grad_rgba32f, n, grad_records, grad_color_opacity, true, depth_f32, depth_stride_floats, grad_depth_f32,
+                                     grad_depth);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The camera variants' grid and partials: ceil(n / 256) workgroups, one 128-byte line of the context's scratch per wave, and
 // CAM_SLICES more lines for k_camera_sum_slices
-static int camera_partials(splat_ctx *ctx, uint32_t n, uint32_t &groups, uint32_t &nparts, double *&part) {
-    groups = div_up(n, 256);
-    nparts = groups * 4u; // (n <= 2^32 - 1: at most 2^26 lines)
+static int camera_partials(splat_ctx *ctx, uint32_t n, uint32_t &nparts, double *&part) {
+    nparts = div_up(n, 256) * 4u; // (n <= 2^32 - 1: at most 2^26 lines)
     const int rc = ctx_ensure_scan_ws(ctx, ((size_t)nparts + CAM_SLICES) * CAM_SLOTS * sizeof(double));
     part = (double *)ctx->scan_ws;
     return rc;
@@ -794,72 +719,120 @@ static void camera_sum_launch(splat_ctx *ctx, const double *part, uint32_t npart
     hipLaunchKernelGGL(k_camera_sum<MODE>, dim3(1), dim3(16 * CAM_SLICES), 0, ctx->stream, part, nparts, out);
 }
 
-extern "C" int splat_project_ellipsoid_backward_camera(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4,
-                                                       const void *scales, uint32_t scale_stride_vec4, const void *rotations,
-                                                       uint32_t rot_stride_vec4, uint32_t n, const void *grad_records, void *grad_positions,
-                                                       void *grad_scales, void *grad_rotations, const void *grad_depth, void *grad_uniforms) {
+// The three ellipsoid projector backwards.  need_depth: grad_depth is required (else optional: NULL = none); cam: also
+// dL/duniforms into grad_uniforms, summed from per-wave partials.  what: the launch's name in an error.
+static int project_ellipsoid_backward(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4,
+                                      const void *scales, uint32_t scale_stride_vec4, const void *rotations, uint32_t rot_stride_vec4, uint32_t n,
+                                      const void *grad_records, void *grad_positions, void *grad_scales, void *grad_rotations,
+                                      const void *grad_depth, bool need_depth, void *grad_uniforms, bool cam, const char *what) {
     if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
-    ARG_CHECK(ctx, uniforms && grad_uniforms &&
-                       (n == 0 || (positions && scales && rotations && grad_records && grad_positions && grad_scales && grad_rotations)));
+    ARG_CHECK(ctx, uniforms && (!cam || grad_uniforms) &&
+                       (n == 0 || (positions && scales && rotations && grad_records && grad_positions && grad_scales && grad_rotations &&
+                                   (!need_depth || grad_depth))));
     ARG_CHECK(ctx, pos_stride_vec4 >= 1 && scale_stride_vec4 >= 1 && rot_stride_vec4 >= 1);
     ARG_CHECK(ctx, (((uintptr_t)positions | (uintptr_t)scales | (uintptr_t)rotations | (uintptr_t)grad_records | (uintptr_t)grad_positions |
                      (uintptr_t)grad_scales | (uintptr_t)grad_rotations | (uintptr_t)grad_uniforms) & 15) == 0 &&
                        ((uintptr_t)grad_depth & 3) == 0);
-    uint32_t groups = 0, nparts = 0;
-    double *part = nullptr;
-    const int rc = camera_partials(ctx, n, groups, nparts, part);
-    if (rc != SPLAT_OK) return rc;
-    if (n) {
-        GradUniformsCam u;
-        for (int k = 0; k < 22; ++k) (&u.m[0])[k] = uniforms[k];
-        u.part = part;
-#define SPLAT_PBC_LAUNCH(DEPTH)                                                                                                                \
-    hipLaunchKernelGGL((k_project_ellipsoid_backward<DEPTH, true>), dim3(groups), dim3(256), 0, ctx->stream, u, (const float4 *)positions,     \
-                       pos_stride_vec4, (const float4 *)scales, scale_stride_vec4, (const float4 *)rotations, rot_stride_vec4, n,              \
-                       (const float4 *)grad_records, (float4 *)grad_positions, (float4 *)grad_scales, (float4 *)grad_rotations,                \
-                       (const float *)grad_depth)
-        if (grad_depth) SPLAT_PBC_LAUNCH(true);
-        else SPLAT_PBC_LAUNCH(false);
-#undef SPLAT_PBC_LAUNCH
-        LAUNCH_CHECK(ctx, "k_project_ellipsoid_backward<CAM>");
+    GradUniformsCam u;
+    uint32_t nparts = 0;
+    u.part = nullptr;
+    if (cam) {
+        const int rc = camera_partials(ctx, n, nparts, u.part);
+        if (rc != SPLAT_OK) return rc;
     }
+    if (n) {
+        for (int k = 0; k < 22; ++k) (&u.m[0])[k] = uniforms[k];
+        // (<DEPTH, CAM>: the kernel without CAM takes the GradUniforms part of u)
+        variant_dispatch(
+            [&](auto depth, auto cam_) {
+                launch_kernel(ctx, NO_STAGE, k_project_ellipsoid_backward<depth.value, cam_.value>, dim3(div_up(n, 256)), dim3(256), u,
+                              (const float4 *)positions, pos_stride_vec4, (const float4 *)scales, scale_stride_vec4, (const float4 *)rotations,
+                              rot_stride_vec4, n, (const float4 *)grad_records, (float4 *)grad_positions, (float4 *)grad_scales,
+                              (float4 *)grad_rotations, (const float *)grad_depth);
+            },
+            grad_depth != nullptr, cam);
+        const int rc = launch_check(ctx, what);
+        if (rc != SPLAT_OK) return rc;
+    }
+    if (!cam) return SPLAT_OK;
     // (without grad_depth the kernel leaves numbers 12-14 of its partials unwritten: the sum reads 12 then)
-    if (grad_depth || n == 0) camera_sum_launch<0>(ctx, part, nparts, (float *)grad_uniforms);
-    else camera_sum_launch<1>(ctx, part, nparts, (float *)grad_uniforms);
+    if (grad_depth || n == 0) camera_sum_launch<0>(ctx, u.part, nparts, (float *)grad_uniforms);
+    else camera_sum_launch<1>(ctx, u.part, nparts, (float *)grad_uniforms);
     LAUNCH_CHECK(ctx, "k_camera_sum");
     return SPLAT_OK;
+}
+
+extern "C" int splat_project_ellipsoid_backward(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4,
+                                                const void *scales, uint32_t scale_stride_vec4, const void *rotations, uint32_t rot_stride_vec4,
+                                                uint32_t n, const void *grad_records, void *grad_positions, void *grad_scales, void *grad_rotations) {
+    return project_ellipsoid_backward(ctx, uniforms, positions, pos_stride_vec4, scales, scale_stride_vec4, rotations, rot_stride_vec4, n,
+                                      grad_records, grad_positions, grad_scales, grad_rotations, nullptr, false, nullptr, false,
+                                      "launch k_project_ellipsoid_backward");
+}
+
+extern "C" int splat_project_ellipsoid_backward_depth(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4,
+                                                      const void *scales, uint32_t scale_stride_vec4, const void *rotations,
+                                                      uint32_t rot_stride_vec4, uint32_t n, const void *grad_records, void *grad_positions,
+                                                      void *grad_scales, void *grad_rotations, const void *grad_depth) {
+    return project_ellipsoid_backward(ctx, uniforms, positions, pos_stride_vec4, scales, scale_stride_vec4, rotations, rot_stride_vec4, n,
+                                      grad_records, grad_positions, grad_scales, grad_rotations, grad_depth, true, nullptr, false,
+                                      "launch k_project_ellipsoid_backward<DEPTH>");
+}
+
+extern "C" int splat_project_ellipsoid_backward_camera(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4,
+                                                       const void *scales, uint32_t scale_stride_vec4, const void *rotations,
+                                                       uint32_t rot_stride_vec4, uint32_t n, const void *grad_records, void *grad_positions,
+                                                       void *grad_scales, void *grad_rotations, const void *grad_depth, void *grad_uniforms) {
+    return project_ellipsoid_backward(ctx, uniforms, positions, pos_stride_vec4, scales, scale_stride_vec4, rotations, rot_stride_vec4, n,
+                                      grad_records, grad_positions, grad_scales, grad_rotations, grad_depth, false, grad_uniforms, true,
+                                      "launch k_project_ellipsoid_backward<CAM>");
+}
+
+// The two SH backwards.  cam: also dL/deye into grad_eye, summed from per-wave partials.
+static int sh_colors_backward(splat_ctx *ctx, const float *eye3, const void *positions, uint32_t pos_stride_vec4, const void *sh,
+                              uint32_t sh_stride_floats, uint32_t degree, const void *opacity_f32, const void *grad_color_opacity, uint32_t n,
+                              void *grad_sh, void *grad_positions, void *grad_opacity, void *grad_eye, bool cam) {
+    if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
+    ARG_CHECK(ctx, eye3 && (!cam || grad_eye) && degree <= 3 && pos_stride_vec4 >= 1);
+    ARG_CHECK(ctx, n == 0 || (positions && sh && grad_color_opacity && grad_sh && grad_positions && grad_opacity));
+    ARG_CHECK(ctx, sh_stride_floats >= 3 * (degree + 1) * (degree + 1));
+    ARG_CHECK(ctx, (((uintptr_t)positions | (uintptr_t)grad_color_opacity | (uintptr_t)grad_positions | (uintptr_t)grad_eye) & 15) == 0 &&
+                       (((uintptr_t)sh | (uintptr_t)grad_sh | (uintptr_t)grad_opacity | (uintptr_t)opacity_f32) & 3) == 0);
+    ShOpacityCam gop = {(float *)grad_opacity, nullptr};
+    uint32_t nparts = 0;
+    if (cam) {
+        const int rc = camera_partials(ctx, n, nparts, gop.part);
+        if (rc != SPLAT_OK) return rc;
+    }
+    if (n) {
+        variant_dispatch(
+            [&](auto deg, auto cam_) {
+                const auto last = [&] { if constexpr (cam_.value) return gop; else return gop.gop; }(); // (<CAM>: with the partials)
+                launch_kernel(ctx, NO_STAGE, k_sh_colors_backward<deg.value, cam_.value>, dim3(div_up(n, 256)), dim3(256), eye3[0], eye3[1], eye3[2],
+                              (const float4 *)positions, pos_stride_vec4, (const float *)sh, sh_stride_floats, (const float4 *)grad_color_opacity,
+                              n, (float *)grad_sh, (float4 *)grad_positions, last);
+            },
+            OneOf<0, 1, 2, 3>{(int)degree}, cam);
+        const int rc = launch_check(ctx, cam ? "launch k_sh_colors_backward<CAM>" : "launch k_sh_colors_backward");
+        if (rc != SPLAT_OK) return rc;
+    }
+    if (!cam) return SPLAT_OK;
+    camera_sum_launch<2>(ctx, gop.part, nparts, (float *)grad_eye);
+    LAUNCH_CHECK(ctx, "k_camera_sum");
+    return SPLAT_OK;
+}
+
+extern "C" int splat_sh_colors_backward(splat_ctx *ctx, const float *eye3, const void *positions, uint32_t pos_stride_vec4, const void *sh,
+                                        uint32_t sh_stride_floats, uint32_t degree, const void *opacity_f32, const void *grad_color_opacity,
+                                        uint32_t n, void *grad_sh, void *grad_positions, void *grad_opacity) {
+    return sh_colors_backward(ctx, eye3, positions, pos_stride_vec4, sh, sh_stride_floats, degree, opacity_f32, grad_color_opacity, n, grad_sh,
+                              grad_positions, grad_opacity, nullptr, false);
 }
 
 extern "C" int splat_sh_colors_backward_camera(splat_ctx *ctx, const float *eye3, const void *positions, uint32_t pos_stride_vec4, const void *sh,
                                                uint32_t sh_stride_floats, uint32_t degree, const void *opacity_f32,
                                                const void *grad_color_opacity, uint32_t n, void *grad_sh, void *grad_positions,
                                                void *grad_opacity, void *grad_eye) {
-    if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
-    ARG_CHECK(ctx, eye3 && grad_eye && degree <= 3 && pos_stride_vec4 >= 1);
-    ARG_CHECK(ctx, n == 0 || (positions && sh && grad_color_opacity && grad_sh && grad_positions && grad_opacity));
-    ARG_CHECK(ctx, sh_stride_floats >= 3 * (degree + 1) * (degree + 1));
-    ARG_CHECK(ctx, (((uintptr_t)positions | (uintptr_t)grad_color_opacity | (uintptr_t)grad_positions | (uintptr_t)grad_eye) & 15) == 0 &&
-                       (((uintptr_t)sh | (uintptr_t)grad_sh | (uintptr_t)grad_opacity | (uintptr_t)opacity_f32) & 3) == 0);
-    uint32_t groups = 0, nparts = 0;
-    double *part = nullptr;
-    const int rc = camera_partials(ctx, n, groups, nparts, part);
-    if (rc != SPLAT_OK) return rc;
-    if (n) {
-        const dim3 grid(groups), block(256);
-#define SPLAT_SHBC_LAUNCH(D)                                                                                                                  \
-    hipLaunchKernelGGL((k_sh_colors_backward<D, true>), grid, block, 0, ctx->stream, eye3[0], eye3[1], eye3[2], (const float4 *)positions,  \
-                       pos_stride_vec4, (const float *)sh, sh_stride_floats, (const float4 *)grad_color_opacity, n, (float *)grad_sh,         \
-                       (float4 *)grad_positions, ShOpacityCam{(float *)grad_opacity, part})
-        switch (degree) {
-        case 0: SPLAT_SHBC_LAUNCH(0); break;
-        case 1: SPLAT_SHBC_LAUNCH(1); break;
-        case 2: SPLAT_SHBC_LAUNCH(2); break;
-        default: SPLAT_SHBC_LAUNCH(3); break;
-        }
-#undef SPLAT_SHBC_LAUNCH
-        LAUNCH_CHECK(ctx, "k_sh_colors_backward<CAM>");
-    }
-    camera_sum_launch<2>(ctx, part, nparts, (float *)grad_eye);
-    LAUNCH_CHECK(ctx, "k_camera_sum");
-    return SPLAT_OK;
+    return sh_colors_backward(ctx, eye3, positions, pos_stride_vec4, sh, sh_stride_floats, degree, opacity_f32, grad_color_opacity, n, grad_sh,
+                              grad_positions, grad_opacity, grad_eye, true);
 }

@@ -10,6 +10,7 @@
 // This file is compiled with -ffp-contract=off: every float op below is one IEEE binary32 op in
 // the order written, identical to oracle/oracle.c, so records and keys are bit-exact.
 #include "common.h"
+#include "variant.h"
 #include "tile_range.h"
 #include "disc.h"
 #include "ellipsoid.h"
@@ -571,87 +572,74 @@ int project_launch(splat_ctx *ctx, const float *uniforms, const void *pos_radius
     }
     const LitIO lio = (with_lit || disc_lit) ? *lit : LitIO{};
     stage_begin(ctx, SPLAT_STAGE_PROJECT);
-    dim3 grid(div_up(work, 256)), block(256);
-#define SPLAT_PROJECT_LAUNCH_E(K, R, D, L, E, RANGE, BP)                                                                                \
-    hipLaunchKernelGGL((k_project<K, R, D, L, E>), grid, block, 0, ctx->stream, u, src, pr_stride_vec4, n, keys ? n_padded : n, index_base, \
-                       (float4 *)projected, (uint32_t *)keys, (uint32_t *)payload, RANGE, BP, dio, lio)
-#define SPLAT_PROJECT_LAUNCH(K, R, D, L, RANGE, BP) SPLAT_PROJECT_LAUNCH_E(K, R, D, L, false, RANGE, BP)
-#define SPLAT_PROJECT_HIST_LAUNCH(KERNEL, D, L)                                                                               \
-    hipLaunchKernelGGL((KERNEL<D, L>), dim3(div_up(work, 1024)), block, 0, ctx->stream, u, src, pr_stride_vec4, n, n_padded, \
-                       (float4 *)projected, (uint32_t *)keys, range32, *bp, *hist_out, dio, lio)
-#define SPLAT_PROJECT_HIST_LAUNCH_PER(D, L) SPLAT_PROJECT_HIST_LAUNCH_PER_E(D, L, false)
-#define SPLAT_PROJECT_HIST_LAUNCH_PER_E(D, L, E)                                                                                           \
-    do {                                                                                                                                   \
-        TfHistOut ho_ = *hist_out;                                                                                                         \
-        const uint32_t blocks_ = div_up(work, hist_out->block == TF_BLOCK_SMALL ? 256u : 1024u);                                           \
-        ho_.xcd_per = blocks_ >= 64u ? div_up(blocks_, 8u) : 0u; /* the blocks dealt as k_tf_scatter's are (common.h: xcd_block_of) */      \
-        const dim3 grid_(ho_.xcd_per ? 8u * ho_.xcd_per : blocks_);                                                                        \
-        if (hist_out->block == TF_BLOCK_SMALL)                                                                                             \
-            hipLaunchKernelGGL((k_project_hist<D, L, 1, 1, E>), grid_, block, 0, ctx->stream, u, src, pr_stride_vec4, n, n_padded,               \
-                               (float4 *)projected, (uint32_t *)keys, range32, *bp, ho_, dio, lio);                                        \
-        else                                                                                                                               \
-            hipLaunchKernelGGL((k_project_hist<D, L, 4, 1, E>), grid_, block, 0, ctx->stream, u, src, pr_stride_vec4, n, n_padded,               \
-                               (float4 *)projected, (uint32_t *)keys, range32, *bp, ho_, dio, lio);                                        \
-    } while (0)
-    if (hist_out && hist_out->cidx && bp->skip_outside && keys && range32 && !payload && index_base == 0) {
-        // a strict band of a fraction of the screen: groups of 4096 splats, the survivors left compacted (hist_out->num_parts = groups)
-        TfHistOut ho_ = *hist_out;
-        ho_.xcd_per = ho_.num_parts >= 64u ? div_up(ho_.num_parts, 8u) : 0u;
-        const dim3 grid_(ho_.xcd_per ? 8u * ho_.xcd_per : ho_.num_parts);
-#define SPLAT_PROJECT_BANDC(D, L)                                                                                                      \
-    hipLaunchKernelGGL((k_project_hist_bandc<D, L>), grid_, dim3(PBC_THREADS), 0, ctx->stream, u, src, pr_stride_vec4, n, (float4 *)projected, \
-                       (uint32_t *)keys, range32, *bp, ho_, dio, lio)
-        if (disc_lit) SPLAT_PROJECT_BANDC(true, true);
-        else if (disc) SPLAT_PROJECT_BANDC(true, false);
-        else if (with_lit) SPLAT_PROJECT_BANDC(false, true);
-        else SPLAT_PROJECT_BANDC(false, false);
-#undef SPLAT_PROJECT_BANDC
-    } else if (hist_out && keys && range32 && !payload && index_base == 0) {
-        // (a strict band's kernel works in 1024-splat blocks only: the caller keeps hist_out->block at TF_BLOCK_LARGE for it)
-        if (el && disc_lit) SPLAT_PROJECT_HIST_LAUNCH_PER_E(true, true, true);
-        else if (el) SPLAT_PROJECT_HIST_LAUNCH_PER_E(true, false, true);
-        else if (disc_lit && bp->skip_outside) SPLAT_PROJECT_HIST_LAUNCH(k_project_hist_band, true, true);
-        else if (disc_lit) SPLAT_PROJECT_HIST_LAUNCH_PER(true, true);
-        else if (disc && bp->skip_outside) SPLAT_PROJECT_HIST_LAUNCH(k_project_hist_band, true, false);
-        else if (disc) SPLAT_PROJECT_HIST_LAUNCH_PER(true, false);
-        else if (bp->skip_outside && with_lit) SPLAT_PROJECT_HIST_LAUNCH(k_project_hist_band, false, true);
-        else if (bp->skip_outside) SPLAT_PROJECT_HIST_LAUNCH(k_project_hist_band, false, false);
-        else if (with_lit) SPLAT_PROJECT_HIST_LAUNCH_PER(false, true);
-        else SPLAT_PROJECT_HIST_LAUNCH_PER(false, false);
-    } else if (keys && range_wide && !payload && index_base == 0) {
-#define SPLAT_PROJECT_WIDE(D, L) SPLAT_PROJECT_WIDE_E(D, L, false)
-#define SPLAT_PROJECT_WIDE_E(D, L, E)                                                                                              \
-    hipLaunchKernelGGL((k_project_wide<D, L, E>), grid, block, 0, ctx->stream, u, src, pr_stride_vec4, n, n_padded, (float4 *)projected, \
-                       (uint32_t *)keys, range_wide, *bp, dio, lio)
-        if (el && disc_lit) SPLAT_PROJECT_WIDE_E(true, true, true);
-        else if (el) SPLAT_PROJECT_WIDE_E(true, false, true);
-        else if (disc_lit) SPLAT_PROJECT_WIDE(true, true);
-        else if (disc) SPLAT_PROJECT_WIDE(true, false);
-        else if (with_lit) SPLAT_PROJECT_WIDE(false, true);
-        else SPLAT_PROJECT_WIDE(false, false);
-#undef SPLAT_PROJECT_WIDE
-#undef SPLAT_PROJECT_WIDE_E
-    } else if (keys && range32) {
-        if (el && disc_lit) SPLAT_PROJECT_LAUNCH_E(true, true, true, true, true, range32, *bp);
-        else if (el) SPLAT_PROJECT_LAUNCH_E(true, true, true, false, true, range32, *bp);
-        else if (disc_lit) SPLAT_PROJECT_LAUNCH(true, true, true, true, range32, *bp);
-        else if (disc) SPLAT_PROJECT_LAUNCH(true, true, true, false, range32, *bp);
-        else if (with_lit) SPLAT_PROJECT_LAUNCH(true, true, false, true, range32, *bp);
-        else SPLAT_PROJECT_LAUNCH(true, true, false, false, range32, *bp);
-    } else if (keys) {
-        if (el) SPLAT_PROJECT_LAUNCH_E(true, false, true, false, true, nullptr, none);
-        else if (disc) SPLAT_PROJECT_LAUNCH(true, false, true, false, nullptr, none);
-        else SPLAT_PROJECT_LAUNCH(true, false, false, false, nullptr, none);
+    const dim3 block(256);
+    const bool lit_out = with_lit || disc_lit;
+    const bool frame_keys = keys && !payload && index_base == 0; // the frame's projector: keys in splat order, the payload implied
+    // Every projector kernel takes the footprint as <DISC, ..., ELL> (the ellipsoid's records are disc records: no ELL without
+    // DISC) and LIT: whether it writes lit colours as well.
+    bool ok = false;
+    if (hist_out && frame_keys && range32 && bp->skip_outside) {
+        // a strict band (no ellipsoid: refused above), in 1024-splat blocks only: the caller keeps hist_out->block at TF_BLOCK_LARGE for it
+        TfHistOut ho = *hist_out;
+        if (hist_out->cidx) { // ... of a fraction of the screen: groups of 4096 splats, the survivors left compacted (num_parts = groups)
+            ho.xcd_per = ho.num_parts >= 64u ? div_up(ho.num_parts, 8u) : 0u;
+            const dim3 grid(ho.xcd_per ? 8u * ho.xcd_per : ho.num_parts);
+            ok = variant_dispatch(
+                [&](auto d, auto l) {
+                    launch_kernel(ctx, NO_STAGE, k_project_hist_bandc<d.value, l.value>, grid, dim3(PBC_THREADS), u, src, pr_stride_vec4, n,
+                                  (float4 *)projected, (uint32_t *)keys, range32, *bp, ho, dio, lio);
+                    return true;
+                },
+                disc, lit_out);
+        } else {
+            ok = variant_dispatch(
+                [&](auto d, auto l) {
+                    launch_kernel(ctx, NO_STAGE, k_project_hist_band<d.value, l.value>, dim3(div_up(work, 1024)), block, u, src, pr_stride_vec4, n,
+                                  n_padded, (float4 *)projected, (uint32_t *)keys, range32, *bp, ho, dio, lio);
+                    return true;
+                },
+                disc, lit_out);
+        }
+    } else if (hist_out && frame_keys && range32) {
+        TfHistOut ho = *hist_out;
+        const bool small = hist_out->block == TF_BLOCK_SMALL;
+        const uint32_t blocks = div_up(work, small ? 256u : 1024u);
+        ho.xcd_per = blocks >= 64u ? div_up(blocks, 8u) : 0u; // the blocks dealt as k_tf_scatter's are (common.h: xcd_block_of)
+        const dim3 grid(ho.xcd_per ? 8u * ho.xcd_per : blocks);
+        ok = variant_dispatch(
+            [&](auto d, auto l, auto per, auto e) {
+                if constexpr (d.value || !e.value) {
+                    launch_kernel(ctx, NO_STAGE, k_project_hist<d.value, l.value, per.value, 1, e.value>, grid, block, u, src, pr_stride_vec4, n,
+                                  n_padded, (float4 *)projected, (uint32_t *)keys, range32, *bp, ho, dio, lio);
+                    return true;
+                } else return false;
+            },
+            disc, lit_out, OneOf<1, 4>{small ? 1 : 4}, el);
+    } else if (frame_keys && range_wide) {
+        ok = variant_dispatch(
+            [&](auto d, auto l, auto e) {
+                if constexpr (d.value || !e.value) {
+                    launch_kernel(ctx, NO_STAGE, k_project_wide<d.value, l.value, e.value>, dim3(div_up(work, 256)), block, u, src, pr_stride_vec4, n,
+                                  n_padded, (float4 *)projected, (uint32_t *)keys, range_wide, *bp, dio, lio);
+                    return true;
+                } else return false;
+            },
+            disc, lit_out, el);
     } else {
-        if (el) SPLAT_PROJECT_LAUNCH_E(false, false, true, false, true, nullptr, none);
-        else if (disc) SPLAT_PROJECT_LAUNCH(false, false, true, false, nullptr, none);
-        else SPLAT_PROJECT_LAUNCH(false, false, false, false, nullptr, none);
+        // the staged projector: <WITH_KEYS, WITH_RANGE, ...>; tile ranges go with keys, lit colours with tile ranges
+        const bool with_keys = keys != nullptr, with_range = keys && range32;
+        ok = variant_dispatch(
+            [&](auto k, auto r, auto d, auto l, auto e) {
+                if constexpr ((k.value || !r.value) && (r.value || !l.value) && (d.value || !e.value)) {
+                    launch_kernel(ctx, NO_STAGE, k_project<k.value, r.value, d.value, l.value, e.value>, dim3(div_up(work, 256)), block, u, src,
+                                  pr_stride_vec4, n, with_keys ? n_padded : n, index_base, (float4 *)projected, (uint32_t *)keys,
+                                  (uint32_t *)payload, with_range ? range32 : nullptr, with_range ? *bp : none, dio, lio);
+                    return true;
+                } else return false;
+            },
+            with_keys, with_range, disc, with_range && lit_out, el);
     }
-#undef SPLAT_PROJECT_LAUNCH
-#undef SPLAT_PROJECT_LAUNCH_E
-#undef SPLAT_PROJECT_HIST_LAUNCH
-#undef SPLAT_PROJECT_HIST_LAUNCH_PER
-#undef SPLAT_PROJECT_HIST_LAUNCH_PER_E
+    if (!ok) return ctx_fail(ctx, SPLAT_ERR_INVALID, "project_launch: no kernel for this footprint and these outputs");
     LAUNCH_CHECK(ctx, "k_project");
     stage_end(ctx, SPLAT_STAGE_PROJECT);
     return SPLAT_OK;

@@ -8,6 +8,7 @@
 // one lane per splat.  Coefficient rows whose stride and base allow it are read as float4s (the row's 48 floats at degree 3
 // are twelve 16-byte loads instead of 48 scalar ones).
 #include "common.h"
+#include "variant.h"
 
 constexpr float SH_C0 = 0.28209479177387814f;
 constexpr float SH_C1 = 0.4886025119029199f;
@@ -88,22 +89,12 @@ extern "C" int splat_sh_colors(splat_ctx *ctx, const float *eye3, const void *po
     // float4 rows: every row 16-byte aligned and its rounded-up length inside the stride
     const bool vec4 = (sh_stride_floats % 4) == 0 && (((uintptr_t)sh) & 15) == 0 && sh_stride_floats >= (nf + 3) / 4 * 4;
     const dim3 grid(div_up(n, 256)), block(256);
-#define SPLAT_SH_LAUNCH(D, V)                                                                                                           \
-    hipLaunchKernelGGL((k_sh_colors<D, V>), grid, block, 0, ctx->stream, eye3[0], eye3[1], eye3[2], (const float4 *)positions, pos_stride_vec4, \
-                       (const float *)sh, sh_stride_floats, (const float *)opacity_f32, n, (float4 *)color_opacity_out)
-#define SPLAT_SH_DEG(D)                      \
-    do {                                     \
-        if (vec4) SPLAT_SH_LAUNCH(D, true);  \
-        else SPLAT_SH_LAUNCH(D, false);      \
-    } while (0)
-    switch (degree) {
-    case 0: SPLAT_SH_DEG(0); break;
-    case 1: SPLAT_SH_DEG(1); break;
-    case 2: SPLAT_SH_DEG(2); break;
-    default: SPLAT_SH_DEG(3); break;
-    }
-#undef SPLAT_SH_DEG
-#undef SPLAT_SH_LAUNCH
+    variant_dispatch(
+        [&](auto deg, auto v4) {
+            launch_kernel(ctx, NO_STAGE, k_sh_colors<deg.value, v4.value>, grid, block, eye3[0], eye3[1], eye3[2], (const float4 *)positions,
+                          pos_stride_vec4, (const float *)sh, sh_stride_floats, (const float *)opacity_f32, n, (float4 *)color_opacity_out);
+        },
+        OneOf<0, 1, 2, 3>{(int)degree}, vec4);
     LAUNCH_CHECK(ctx, "k_sh_colors");
     return SPLAT_OK;
 }
