@@ -732,6 +732,39 @@ int splat_mcmc_apply(splat_ctx *ctx, const void *targets, const void *sources, c
 int splat_mcmc_noise(splat_ctx *ctx, void *means, const void *log_scales, const void *rotations, const void *opacity_logits, uint32_t n,
                      double scale, uint32_t step, uint64_t seed);
 
+/* ---- Initialisation from a point cloud: the scale 3DGS gives a new splat (simple_knn's distCUDA2; an extension) ----------------
+ * What every fit starts from is a sparse point cloud; 3DGS sets the scale of the splat at each point to the root of the mean
+ * squared distance to the point's three nearest neighbours.  splat_knn_mean_sq computes that mean, exactly as stated here, for
+ * every point, without the n x n distances: the points are sorted along a 63-bit Morton curve with the caller's sorter, cut into
+ * blocks of 64 with a bounding box each, and a block is left out of a query's search only when its box proves that none of its
+ * members can change the result.  Everything goes to the ctx's stream and nothing waits on the host.
+ *
+ * THE CONTRACT, in binary32, every operator one correctly rounded operation, no contraction:
+ *   d(i, j)    = ((dx dx + dy dy) + dz dz),   dx = x_i - x_j, dy = y_i - y_j, dz = z_i - z_j;
+ *   the candidates of i are the j != i whose d(i, j) is finite (a duplicate of point i is a candidate, at distance 0);
+ *   b0 <= b1 <= b2 are the three smallest candidate values, padded with +inf when there are fewer than three;
+ *   mean_sq[i] = ((b0 + b1) + b2) / 3.0f.
+ * So: n < 4 gives +inf in every row; a point with a NaN or an infinite coordinate gets +inf and is nobody's neighbour (every
+ * distance to it is NaN or infinite), and so does a point so far out that its squares overflow; ties need no rule, because only
+ * the values enter; and the result is a function of the input alone, bit for bit, on every run and whatever the search skipped.
+ * Why skipping is exact: for a box [lo, hi] and a query x, g = max(lo - x, x - hi, 0) per axis and lb = ((gx gx + gy gy) + gz gz),
+ * in d's operation order.  Rounding is monotone: for a member q <= hi < x, fl(x - q) >= fl(x - hi), squares and sums of
+ * non-negative terms in the same order keep the inequality, so lb <= d(i, j) for every member j.  A block is skipped only when
+ * lb > b2 (equality is visited, and so is a NaN bound, which compares false); nothing depends on the Morton codes but the order
+ * of the visits.
+ *
+ * points: DEVICE float32, 4-byte aligned; point i is the three floats at points + i * stride_floats, stride_floats >= 3 (3: a
+ * fit's means; 4: a pos_radius plane, whose fourth word is not read).  mean_sq: DEVICE, n floats, all written.  sorter: capacity
+ * >= n; its buffers are overwritten.  workspace: DEVICE, 16-byte aligned, at least splat_knn_workspace_bytes(n).
+ * evaluations: NULL, or a DEVICE uint64 (8-byte aligned) that the call zeroes on the stream and that receives the number of
+ * d(i, j) evaluations any lane performed, those done only because a wave runs its 64 queries in lockstep included (unsigned
+ * integer atomic adds, one per wave: the sum does not depend on their order).  Brute force performs n (n - 1).
+ * n = 0: success, nothing launched (evaluations is not written either).  SPLAT_ERR_INVALID: a NULL or misaligned pointer,
+ * stride_floats < 3, n >= 2^30, a workspace that is too small or not 16-byte aligned.  SPLAT_ERR_CAPACITY: a sorter smaller than n. */
+uint64_t splat_knn_workspace_bytes(uint32_t n);
+int splat_knn_mean_sq(splat_ctx *ctx, splat_sorter *sorter, const void *points, uint32_t stride_floats, uint32_t n,
+                      void *workspace, uint64_t workspace_bytes, void *mean_sq, void *evaluations);
+
 /* ---- multi-GPU band path (no reference equivalent — the reference is single-device) */
 /* The oriented-disc projector (src/SequentialRenderer.ts:68-71,91-112): the splat is the disc
  * p + r*(t*u + b*v), u^2+v^2 <= 1, in the tangent plane of its normal (t = normalize(cross(up, n)), b =

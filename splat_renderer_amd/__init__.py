@@ -13,6 +13,14 @@ from .host import (Buffer, CommandEncoder, ComputeShaderRenderer, DepthKeyExtrac
                    SplatProjector, SplatPropertyManager, TileRenderer)
 from .frameloop import FrameLoop, MouseEvent, OrbitCameraController, SdfSplatSource, read_png, write_png  # noqa: F401
 from . import sdf  # noqa: F401
-from .ply import load_gaussian_ply, save_gaussian_ply  # noqa: F401
+from .ply import load_gaussian_ply, load_point_ply, save_gaussian_ply  # noqa: F401
 from .fit import GaussianFit  # noqa: F401
+
+
+def knn_mean_sq_distance(points, return_evaluations=False):
+    """autograd.knn_mean_sq_distance (torch is imported when it is first called)."""
+    from .autograd import knn_mean_sq_distance as f
+    return f(points, return_evaluations)
+
+
 from .sdf import CurvatureSampler, GradientSampler, PositionUpdater, SDFScene  # noqa: F401

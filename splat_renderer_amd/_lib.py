@@ -125,6 +125,8 @@ SIGNATURES = {
     "splat_mcmc_sample": (_i, [_vp, _vp, _u32, _u32, _u32, _f64, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, C.POINTER(_u32)]),
     "splat_mcmc_apply": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _f64, C.POINTER(McmcPlanes)]),
     "splat_mcmc_noise": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _f64, _u32, C.c_uint64]),
+    "splat_knn_workspace_bytes": (C.c_uint64, [_u32]),
+    "splat_knn_mean_sq": (_i, [_vp, _vp, _vp, _u32, _u32, _vp, C.c_uint64, _vp, _vp]),
     "splat_extract_keys":(_i, [_vp, _vp, _u32, _u32, _vp, _vp]),
     "splat_sort_create": (_i, [_vp, _u32, _pvp]),
     "splat_sort_destroy": (None, [_vp]),

@@ -60,6 +60,14 @@ for its value).  No masks: multiply both images by one in torch.
 The background is the composite's fixed bg = (0.05, 0.05, 0.1).  A caller that wants background b uses
 rgb + (b - bg) * (1 - alpha)[..., None], which is exact and differentiable.
 
+Where a fit starts (include/splat.h, "Initialisation from a point cloud"):
+
+    mean_sq = knn_mean_sq_distance(points)   # (n,): per point the mean squared distance to its three nearest neighbours
+
+points is (n, 3) or (n, 4) (the fourth column is not read); the result is the header's contract bit for bit, +inf for a point
+with fewer than three usable neighbours or a non-finite coordinate.  No gradient: it is an initialisation.  One call of
+splat_knn_mean_sq on torch's current stream, with this module's per-device context and sorter; nothing waits on the host.
+
 torch is imported when a function here is first called, so `import splat_renderer_amd` does not need it.
 """
 import ctypes as C
@@ -562,3 +570,24 @@ def pinhole_uniforms(R, t, fx, fy, cx, cy, width, height, near=0.01, far=1000.0)
     VP = P @ V
     eye = -(R.transpose(0, 1) @ t)
     return torch.cat([VP.transpose(0, 1).reshape(16), eye, torch.zeros(1, **kw), torch.tensor([W, H], **kw)])
+
+
+def knn_mean_sq_distance(points, return_evaluations=False):
+    """Per point the mean of the squared distances to its three nearest neighbours (splat_knn_mean_sq; the module's docstring
+    has the rest): points (n, 3) or (n, 4) CUDA float32 -> (n,) float32.  return_evaluations=True: (mean_sq, evaluations), the
+    second a 0-d int64 tensor on the device with the number of distance evaluations the search performed."""
+    torch = _t()
+    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] not in (3, 4):
+        raise SplatError(-1, "points must be a tensor of shape (n, 3) or (n, 4)")
+    pts = _cuda_f32(points.detach(), "points")
+    n, stride = int(pts.shape[0]), int(pts.shape[1])
+    out = torch.empty(n, device=pts.device, dtype=torch.float32)
+    evals = torch.zeros((), device=pts.device, dtype=torch.int64) if return_evaluations else None
+    if n:
+        cx = _context(pts)
+        cx.ensure_sorter(n)
+        nbytes = int(cx.lib.splat_knn_workspace_bytes(n))
+        ws = torch.empty((nbytes + 15) // 16 * 4, device=pts.device, dtype=torch.int32)
+        check(cx.lib.splat_knn_mean_sq(cx.ctx, cx.sorter, pts.data_ptr(), stride, n, ws.data_ptr(), nbytes, out.data_ptr(),
+                                       evals.data_ptr() if evals is not None else None), cx.ctx)
+    return (out, evals) if return_evaluations else out

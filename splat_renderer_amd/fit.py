@@ -1,6 +1,10 @@
 """Fitting a cloud of anisotropic 3D Gaussians to images (footprint="ellipsoid"; an extension, no reference counterpart): the
-parameters, a fused Adam step whose state survives a change of the splat count, and 3DGS's adaptive density control.
+parameters, their initialisation from a point cloud, a fused Adam step whose state survives a change of the splat count, and
+3DGS's adaptive density control.
 
+    xyz, rgb = load_point_ply("sparse/0/points3D.ply")                  # what structure from motion leaves
+    fit = GaussianFit.from_points(xyz, rgb)                             # 3DGS's initialisation (below)
+    # or, from an existing cloud:
     fit = GaussianFit(means, scales, rotations, opacity, sh)           # activated values, as load_gaussian_ply returns them
     for step in range(steps):
         rgb, alpha = fit.render(camera_or_uniforms, width, height)
@@ -21,6 +25,11 @@ as in the "sparse Adam" of the faster 3DGS trainers (its gradient is exactly zer
 move it).  densify_and_prune() is splat_densify_plan, splat_densify_geometry and splat_densify_rows: it replaces the tensors
 (callers must not hold on to the old ones), moves the moments with them (new splats start at zero) and resets the statistics.
 Every kernel runs on torch's current stream; only densify_and_prune waits on the host (once, for the new count).
+
+from_points() is 3DGS's start: every point becomes an isotropic splat whose scale is the root of the mean squared distance to the
+point's three nearest neighbours (splat_knn_mean_sq: include/splat.h, "Initialisation from a point cloud"; exact, and not the
+n x n distances), floored at sqrt(min_sq_distance); identity rotations, one opacity, the colour as the SH DC term.  It waits on
+the host once, to refuse a cloud in which some point has no three usable neighbours.
 
 The other strategy is 3DGS-MCMC (include/splat.h, "MCMC relocation"), for a fit whose splat count is a budget:
 
@@ -83,6 +92,35 @@ class GaussianFit:
         centre = means.mean(dim=0, keepdim=True) if n else means
         self.extent = float(1.1 * (means - centre).norm(dim=1).max()) if n else 1.0
         self._frame = None
+
+    @classmethod
+    def from_points(cls, points, colors, degree=3, opacity=0.1, min_sq_distance=1e-7, **kw):
+        """3DGS's initialisation from a coloured point cloud: points (n, 3), colors (n, 3) in [0, 1] (arrays or tensors, as
+        load_point_ply returns them).  scales = sqrt(max(mean_sq, min_sq_distance)) on all three axes, mean_sq the mean squared
+        distance to the three nearest neighbours (autograd.knn_mean_sq_distance); rotations (1, 0, 0, 0); the given opacity;
+        sh[:, 0] = (rgb - 0.5) / 0.28209479177387814 and the higher coefficients zero.  **kw goes to GaussianFit.  SplatError
+        when a row of mean_sq is not finite: fewer than four usable points, or a point with a NaN or infinite coordinate."""
+        torch = AG._t()
+        device = kw.get("device", "cuda")
+        t = lambda a: torch.as_tensor(a, dtype=torch.float32).to(device).detach()  # noqa: E731
+        points, colors = t(points), t(colors)
+        n = points.shape[0]
+        if points.dim() != 2 or points.shape[1] != 3 or tuple(colors.shape) != (n, 3):
+            raise SplatError(-1, "from_points: points (n, 3) and colors (n, 3) are expected")
+        if not 0 <= int(degree) <= 3:
+            raise SplatError(-1, f"from_points: degree must be 0-3, not {degree}")
+        mean_sq = AG.knn_mean_sq_distance(points.contiguous())
+        bad = int((~torch.isfinite(mean_sq)).sum())  # (the one host sync)
+        if bad or n == 0:
+            raise SplatError(-1, f"from_points: {bad} of {n} points have no three usable neighbours (fewer than four points, or "
+                                 "NaN or infinite coordinates): no scale can be given to them")
+        scales = torch.sqrt(torch.clamp(mean_sq, min=float(min_sq_distance)))[:, None].repeat(1, 3)
+        rotations = torch.zeros((n, 4), device=points.device, dtype=torch.float32)
+        rotations[:, 0] = 1.0
+        sh = torch.zeros((n, (int(degree) + 1) ** 2, 3), device=points.device, dtype=torch.float32)
+        sh[:, 0] = ((colors.double() - 0.5) / 0.28209479177387814).float()  # (in float64, rounded once)
+        return cls(points, scales, rotations, torch.full((n,), float(opacity), device=points.device, dtype=torch.float32), sh,
+                   degree=int(degree), **kw)
 
     def _set(self, *tensors):
         for name, value in zip(PLANES, tensors):

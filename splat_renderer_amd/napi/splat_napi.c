@@ -545,6 +545,16 @@ FN(mcmc_noise) { /* (ctx, means, logScales, rotations, opacityLogits, n, scale, 
     uint64_t seed = (uint64_t)arg_number(&c, 8); BAIL;
     return check(env, x, splat_mcmc_noise(x, mu, ls, rot, ol, n, scale, step, seed), mk_undefined(env));
 }
+FN(knn_workspace_bytes) { /* (n) -> bytes */
+    ARGS(1); uint32_t n = (uint32_t)arg_number(&c, 0); BAIL;
+    return mk_number(env, (double)splat_knn_workspace_bytes(n));
+}
+FN(knn_mean_sq) { /* (ctx, sorter, points, strideFloats, n, workspace, workspaceBytes, meanSq, evaluations|null) */
+    ARGS(9); splat_ctx *x = arg_external(&c, 0); splat_sorter *s = arg_external(&c, 1); void *pts = arg_dptr(&c, 2);
+    uint32_t stride = (uint32_t)arg_number(&c, 3), n = (uint32_t)arg_number(&c, 4); void *ws = arg_dptr(&c, 5);
+    uint64_t wb = (uint64_t)arg_number(&c, 6); void *out = arg_dptr(&c, 7), *ev = arg_dptr(&c, 8); BAIL;
+    return check(env, x, splat_knn_mean_sq(x, s, pts, stride, n, ws, wb, out, ev), mk_undefined(env));
+}
 FN(render_frame_ellipsoids) { /* (ctx, sorter, binner, cfg[8], Float32Array(22), positions, scales, rotations, colorOpacity, n, W, H, projected|null, out8|null, outF|null, [depth, alpha, ids]|null) */
     ARGS(16); splat_ctx *x = arg_external(&c, 0); splat_sorter *s = arg_external(&c, 1); splat_binner *b = arg_external(&c, 2);
     splat_composite_cfg cfg; fill_cfg(&c, 3, &cfg); size_t ub = 0; float *u = arg_hostbuf(&c, 4, &ub);
@@ -814,6 +824,7 @@ static napi_value init(napi_env env, napi_value exports) {
         EXPORT(adam_step), EXPORT(density_accumulate), EXPORT(densify_plan_workspace_bytes), EXPORT(densify_plan),
         EXPORT(densify_geometry), EXPORT(densify_rows),
         EXPORT(mcmc_sample_workspace_bytes), EXPORT(mcmc_sample), EXPORT(mcmc_apply), EXPORT(mcmc_noise),
+        EXPORT(knn_workspace_bytes), EXPORT(knn_mean_sq),
     };
     napi_define_properties(env, exports, sizeof d / sizeof d[0], d);
     return exports;

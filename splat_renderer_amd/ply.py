@@ -7,6 +7,8 @@ applies the activations the renderer expects: scale = exp(scale_k), opacity = si
 green, then blue); they are returned basis-major, sh[i, k, c], with the DC term as k = 0.  The degree follows from the
 number of f_rest properties: 0, 9, 24 or 45 for degrees 0-3.
 
+load_point_ply reads what a fit starts from instead: a coloured point cloud, x y z and red green blue per vertex.
+
 save_gaussian_ply is its exact inverse: the same file 3D Gaussian splatting writes (x y z, zero nx ny nz, f_dc, channel-major
 f_rest, opacity as a logit, log scales, rot), from the arrays load_gaussian_ply returns.
 """
@@ -24,49 +26,92 @@ def _bad(path, why):
     return SplatError(-1, f"{path}: not a 3D Gaussian splatting PLY file: {why}")
 
 
+def _bad_points(path, why):
+    return SplatError(-1, f"{path}: not a point-cloud PLY file: {why}")
+
+
+def _read_vertex_header(f, path, bad):
+    """The header of a binary_little_endian PLY whose vertex element is the first and only element with data, f left at the
+    first vertex: (n, [(property name, NumPy type), ...]).  bad(path, why) makes the error."""
+    if f.readline().rstrip(b"\r\n") != b"ply":
+        raise bad(path, "no 'ply' magic line")
+    fmt, n, props, in_vertex, other = None, None, [], False, False
+    while True:
+        line = f.readline()
+        if not line:
+            raise bad(path, "the header has no end_header line")
+        words = line.decode("ascii", "replace").split()
+        if not words or words[0] in ("comment", "obj_info"):
+            continue
+        if words[0] == "end_header":
+            break
+        if words[0] == "format":
+            fmt = words[1] if len(words) > 1 else None
+        elif words[0] == "element":
+            if len(words) != 3:
+                raise bad(path, f"malformed element line {line!r}")
+            in_vertex = words[1] == "vertex"
+            if in_vertex:
+                if n is not None or other:
+                    raise bad(path, "the vertex element must be the first and only element with data")
+                n = int(words[2])
+            elif int(words[2]) > 0:
+                other = True
+        elif words[0] == "property":
+            if len(words) != 3 or words[1] == "list":
+                raise bad(path, f"unsupported property {line!r} (list properties are not vertex attributes)")
+            if words[1] not in _PLY_TYPES:
+                raise bad(path, f"unknown property type {words[1]!r}")
+            if in_vertex:
+                props.append((words[2], "<" + _PLY_TYPES[words[1]]))
+    if fmt != "binary_little_endian":
+        raise bad(path, f"format {fmt!r}; only binary_little_endian is read")
+    if n is None:
+        raise bad(path, "no vertex element")
+    names = [p[0] for p in props]
+    if len(set(names)) != len(names):
+        raise bad(path, "a property name repeats")
+    return n, props
+
+
+def _read_vertices(f, path, bad, n, props):
+    dtype = np.dtype(props)
+    raw = f.read(n * dtype.itemsize)
+    if len(raw) != n * dtype.itemsize:
+        raise bad(path, f"the file ends after {len(raw) // dtype.itemsize} of {n} vertices")
+    return np.frombuffer(raw, dtype=dtype, count=n)
+
+
+def load_point_ply(path):
+    """A coloured point cloud, what structure from motion leaves (COLMAP's points3D.ply): (xyz float32 (n, 3), rgb float32 (n, 3)
+    in [0, 1]) from a binary_little_endian PLY whose vertices carry x y z as float or double and red green blue as uchar.  Other
+    properties (normals, errors, track lengths) are skipped.  GaussianFit.from_points takes the pair."""
+    with open(path, "rb") as f:
+        n, props = _read_vertex_header(f, path, _bad_points)
+        types = dict(props)
+        missing = [k for k in ("x", "y", "z", "red", "green", "blue") if k not in types]
+        if missing:
+            raise _bad_points(path, f"missing properties {missing}")
+        for k in ("x", "y", "z"):
+            if types[k] not in ("<f4", "<f8"):
+                raise _bad_points(path, f"property {k} is {types[k]!r}; float or double is expected")
+        for k in ("red", "green", "blue"):
+            if types[k] != "<u1":
+                raise _bad_points(path, f"property {k} is {types[k]!r}; uchar is expected")
+        v = _read_vertices(f, path, _bad_points, n, props)
+    xyz = np.ascontiguousarray(np.stack([v[k].astype(np.float32) for k in ("x", "y", "z")], axis=1), dtype=np.float32).reshape(n, 3)
+    rgb = np.ascontiguousarray(np.stack([v[k].astype(np.float32) / np.float32(255.0) for k in ("red", "green", "blue")], axis=1),
+                               dtype=np.float32).reshape(n, 3)
+    return xyz, rgb
+
+
 def load_gaussian_ply(path):
     """Returns a dict of float32 arrays: positions (n, 3), scales (n, 3), rotations (n, 4) as (w, x, y, z), opacity (n,),
     sh (n, (degree + 1)^2, 3), and the int degree.  Pass them to GaussianCloud.fromArrays(device, positions, scales,
     rotations, opacity=opacity, sh=sh)."""
     with open(path, "rb") as f:
-        if f.readline().rstrip(b"\r\n") != b"ply":
-            raise _bad(path, "no 'ply' magic line")
-        fmt, n, props, in_vertex, other = None, None, [], False, False
-        while True:
-            line = f.readline()
-            if not line:
-                raise _bad(path, "the header has no end_header line")
-            words = line.decode("ascii", "replace").split()
-            if not words or words[0] in ("comment", "obj_info"):
-                continue
-            if words[0] == "end_header":
-                break
-            if words[0] == "format":
-                fmt = words[1] if len(words) > 1 else None
-            elif words[0] == "element":
-                if len(words) != 3:
-                    raise _bad(path, f"malformed element line {line!r}")
-                in_vertex = words[1] == "vertex"
-                if in_vertex:
-                    if n is not None or other:
-                        raise _bad(path, "the vertex element must be the first and only element with data")
-                    n = int(words[2])
-                elif int(words[2]) > 0:
-                    other = True
-            elif words[0] == "property":
-                if len(words) != 3 or words[1] == "list":
-                    raise _bad(path, f"unsupported property {line!r} (list properties are not Gaussian attributes)")
-                if words[1] not in _PLY_TYPES:
-                    raise _bad(path, f"unknown property type {words[1]!r}")
-                if in_vertex:
-                    props.append((words[2], "<" + _PLY_TYPES[words[1]]))
-        if fmt != "binary_little_endian":
-            raise _bad(path, f"format {fmt!r}; only binary_little_endian is read")
-        if n is None:
-            raise _bad(path, "no vertex element")
+        n, props = _read_vertex_header(f, path, _bad)
         names = [p[0] for p in props]
-        if len(set(names)) != len(names):
-            raise _bad(path, "a property name repeats")
         need = ["x", "y", "z", "f_dc_0", "f_dc_1", "f_dc_2", "opacity", "scale_0", "scale_1", "scale_2",
                 "rot_0", "rot_1", "rot_2", "rot_3"]
         missing = [k for k in need if k not in names]
@@ -75,11 +120,7 @@ def load_gaussian_ply(path):
         rest = sorted((k for k in names if k.startswith("f_rest_")), key=lambda k: int(k[len("f_rest_"):]))
         if len(rest) not in _REST_TO_DEGREE or rest != [f"f_rest_{j}" for j in range(len(rest))]:
             raise _bad(path, f"{len(rest)} f_rest properties; 0, 9, 24 or 45 (f_rest_0 ... in order) are expected")
-        dtype = np.dtype(props)
-        raw = f.read(n * dtype.itemsize)
-        if len(raw) != n * dtype.itemsize:
-            raise _bad(path, f"the file ends after {len(raw) // dtype.itemsize} of {n} vertices")
-    v = np.frombuffer(raw, dtype=dtype, count=n)
+        v = _read_vertices(f, path, _bad, n, props)
 
     def cols(keys):
         return np.stack([v[k].astype(np.float32) for k in keys], axis=1) if keys else np.zeros((n, 0), np.float32)
