@@ -466,7 +466,7 @@ int splat_render_frame_ellipsoids(splat_ctx *ctx, splat_sorter *sorter, splat_bi
  * consumed entry but a pixel's last has 1 - alpha > 0.01 (T_{i+1} > 0.01 and T_{i+1} <= 1 - alpha_i), and the last one's
  * T_{L-1} is recomputed front to back, never divided for.
  * The per-splat sums are float atomic adds whose order of arrival varies: gradients are reproducible to rounding, not bit for
- * bit, from run to run.
+ * bit, from run to run (splat_composite_backward_det, below, is the fixed-order form).
  *
  * splat_composite_backward: the lists (tile_indices / counts / offsets) must be the ones the forward composited, for the same
  * records (splat_project_ellipsoid's 32-byte records), color_opacity and screen.  grad_rgba32f: W*H float4, dL/drgb in xyz and
@@ -503,6 +503,41 @@ int splat_composite_backward_depth(splat_ctx *ctx, const splat_composite_cfg *cf
                                    uint32_t width, uint32_t height, const void *grad_rgba32f, uint32_t n, void *grad_records,
                                    void *grad_color_opacity, const void *depth_f32, uint32_t depth_stride_floats,
                                    const void *grad_depth_f32, void *grad_depth);
+/* The two functions above with the per-splat sums in a fixed order: no float atomics anywhere, and the same inputs give the same
+ * bits on every run, on every ctx.  Opt-in: it costs a workspace and a second pass, and the atomic entry points are unchanged.
+ *
+ * Arguments, checks and kernel selection are splat_composite_backward's (and, when any of depth_f32 / depth_stride_floats /
+ * grad_depth_f32 / grad_depth is given, splat_composite_backward_depth's: all four NULL / 0 is the colour-only variant), plus
+ *   projected    the ProjectedSplat array the lists were binned from (its bounds give each splat's tile rectangle, its depth
+ *                the list order); 16-byte aligned;
+ *   total_pairs  tile_offsets[num_tiles] (splat_bin_total); at most 2^32 - 1;
+ *   workspace    a DEVICE pointer, 16-byte aligned, of workspace_bytes >= splat_composite_backward_det_workspace_bytes(
+ *                total_pairs, num_tiles, n, with_depth) = 16 num_tiles + 16 ceil(n / 4) + 4 NV total_pairs bytes, NV = 9, or 10
+ *                with depth (num_tiles = ceil(W / 16) ceil(H / 16)): a table row per tile, a slot index per splat and NV
+ *                floats per pair.  Its content before the call does not matter and is unspecified after it.
+ * A NULL projected, a NULL, misaligned or too small workspace, or total_pairs >= 2^32: SPLAT_ERR_INVALID, and nothing is launched.
+ *
+ * The sums.  Let P(i, t, k) be what one tile t adds for splat i and number k (k over c.x, c.y, B00, B01, B11, r, g, b, opacity,
+ * and dL/dz with depth): the sum over the tile's 256 pixels that splat_composite_backward hands to its atomic add, formed in the
+ * same order as there (each wave's DPP tree, then (w0 + w1) + (w2 + w3)).  Let [tx0, tx1] x [ty0, ty1] be splat i's tile
+ * rectangle, the binner's: the tile range of projected[i].bounds on the whole screen, ntx tiles wide.  In binary32, one rounding
+ * per add:
+ *   row(ty)   = (((+0 + P(i, ty ntx + tx0, k)) + P(i, ty ntx + tx0 + 1, k)) + ...) + P(i, ty ntx + tx1, k)
+ *   total     = ((+0 + row(ty0)) + row(ty0 + 1)) + ... + row(ty1)
+ *   out[i][k] = prior[i][k] + total           (the "ADDS into" above, in one add)
+ * A tile that did not consume splat i's entry (its position in the tile's list is at or past the largest L of the tile's
+ * pixels) adds nothing.  A splat no tile consumed keeps its prior bits; so do the unused record columns.
+ *
+ * Lists that were not binned from this `projected` give unspecified gradients but no error and no store outside the buffers:
+ * a list entry whose tile lies outside its splat's rectangle is dropped, and every slot index is bounded by total_pairs.
+ * All work goes to the ctx's stream; nothing waits on the host. */
+uint64_t splat_composite_backward_det_workspace_bytes(uint64_t total_pairs, uint32_t num_tiles, uint32_t n, int with_depth);
+int splat_composite_backward_det(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4,
+                                 const void *records, const void *projected, const void *tile_indices, const void *tile_counts,
+                                 const void *tile_offsets, uint64_t total_pairs, uint32_t width, uint32_t height,
+                                 const void *grad_rgba32f, uint32_t n, void *grad_records, void *grad_color_opacity,
+                                 const void *depth_f32, uint32_t depth_stride_floats, const void *grad_depth_f32, void *grad_depth,
+                                 void *workspace, uint64_t workspace_bytes);
 /* splat_project_ellipsoid's backward: dL/drecords (n x 8, splat_composite_backward's layout) -> dL/dposition (xyz, w = 0),
  * dL/dscale (xyz, w = 0) and dL/drotation (w, x, y, z of the quaternion as given, through its normalisation), all n x 4 f32,
  * OVERWRITTEN.  The centre and J move with the position.  The cull decisions are the forward's (csrc/ellipsoid.h); a culled

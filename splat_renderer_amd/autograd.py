@@ -27,6 +27,16 @@ sort -> splat_bin_run -> splat_composite_aov), so rasterize's image is Renderer(
 backward is splat_composite_backward, splat_project_ellipsoid_backward and splat_sh_colors_backward, whose contract (the cut
 and the early-out stop held fixed; float atomic sums, reproducible to rounding) is stated in include/splat.h.
 
+rasterize(..., deterministic=True) and render_gaussians(..., deterministic=True) make the backward bit-reproducible: the
+composite's backward is then splat_composite_backward_det, which stores each tile's share of a splat's sums to a workspace and
+adds them per splat in a documented order (the tiles of each tile row of the splat's rectangle left to right, then the rows
+top to bottom, then once into the gradient: include/splat.h) with no float atomics.  Every other kernel of the chain already
+sums in a fixed order, so with the flag the same inputs give the same .grad bits on every run, the camera's included.  The
+price: the workspace, a torch tensor allocated in backward() and freed after it, of 16 bytes per tile + 4 per splat + 36 per
+(tile, splat) pair of the frame's lists (40 with a depth gradient) - about 0.5 GB where the lists hold 12.5 M pairs - and the
+time of the stores and the second pass (DESIGN.md section 4 has the measurement).  The default, deterministic=False, is the
+atomic path, unchanged: no workspace, reproducible to rounding.
+
 The camera is differentiable too.  `uniforms` may be a torch tensor (CUDA or CPU, float32 or float64, 22 floats, or 20 with
 width= and height=) that requires grad: it is then an input of the projection and, through its [16:19] slice, of sh_colors,
 and backward() fills its .grad — dL/dVP in [0:16] (row 2, entries 2, 6, 10, 14, is not read by this footprint: exact zeros),
@@ -107,6 +117,7 @@ class _Ctx:
         check(self.lib.splat_bin_create(self.device.ctx, TILE, C.byref(b)), self.device.ctx)
         self.binner = b
         self.generation = 0
+        self.total = 0
 
     @property
     def ctx(self):
@@ -144,6 +155,7 @@ class _Ctx:
             check(lib.splat_bin_run(*args), ctx)
             rc = lib.splat_bin_total(self.binner, C.byref(total))
         check(rc, ctx)
+        self.total = int(total.value)  # (the lists' pairs: what sizes the deterministic backward's workspace)
         self.generation += 1
         return self.generation
 
@@ -332,7 +344,7 @@ def _functions():
 
     class Rasterize(torch.autograd.Function):
         @staticmethod
-        def forward(fctx, rec, col, aux, width, height, depths=None):
+        def forward(fctx, rec, col, aux, width, height, depths=None, deterministic=False):
             cx = aux.ctx
             n = aux.n
             out = torch.empty((height, width, 4), device=rec.device, dtype=torch.float32)
@@ -353,6 +365,7 @@ def _functions():
                 fctx.save_for_backward(rec, col, depths)
                 fctx.set_materialize_grads(False)  # (an unused depth map: None, and the colour-only kernel)
             fctx.aux, fctx.gen, fctx.wh = aux, gen, (width, height)
+            fctx.deterministic = bool(deterministic)
             rgb = out[..., :3]
             return (rgb, alpha) if depths is None else (rgb, alpha, depth)
 
@@ -375,6 +388,20 @@ def _functions():
             grec = torch.zeros((n, 8), device=rec.device, dtype=torch.float32)
             gcol = torch.zeros((n, 4), device=rec.device, dtype=torch.float32)
             cfg = CompositeCfg(_lib.MODE_FRONT_TO_BACK, 1, TILE, 0, _lib.U32_MAX, _lib.RECORDS_PROJECTED, 1, _lib.FOOTPRINT_ELLIPSOID)
+            if fctx.deterministic:  # the fixed-order sums: splat_composite_backward_det over a workspace sized from the lists' pairs
+                with_depth = depths is not None and grad_depth_map is not None
+                gd = _cuda_f32(grad_depth_map, "grad_depth") if with_depth else None
+                gz = torch.zeros(n, device=rec.device, dtype=torch.float32) if with_depth else None
+                if n:
+                    tiles = ((width + TILE - 1) // TILE) * ((height + TILE - 1) // TILE)
+                    nbytes = int(cx.lib.splat_composite_backward_det_workspace_bytes(cx.total, tiles, n, int(with_depth)))
+                    ws = torch.empty((nbytes + 15) // 16 * 4, device=rec.device, dtype=torch.int32)
+                    check(cx.lib.splat_composite_backward_det(cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr(), aux.projected.data_ptr(),
+                                                              idx, cnt, off, cx.total, width, height, g.data_ptr(), n, grec.data_ptr(),
+                                                              gcol.data_ptr(), depths.data_ptr() if with_depth else None,
+                                                              1 if with_depth else 0, gd.data_ptr() if with_depth else None,
+                                                              gz.data_ptr() if with_depth else None, ws.data_ptr(), nbytes), cx.ctx)
+                return grec, gcol, None, None, None, gz, None
             if depths is None or grad_depth_map is None:
                 if n:
                     check(cx.lib.splat_composite_backward(cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr(), idx, cnt, off, width, height,
@@ -464,10 +491,10 @@ def sh_colors(eye, means, sh, degree, opacities):
     return _functions()[1].apply(e, means4, sh2, int(degree), op)
 
 
-def rasterize(rec, col, aux, width=None, height=None, depths=None):
+def rasterize(rec, col, aux, width=None, height=None, depths=None, deterministic=False):
     """(rgb (H, W, 3), alpha (H, W)) of the records and colours over the projection's lists; both differentiable.  With
     depths ((n,) per-splat z, differentiable): (rgb, alpha, depth), depth (H, W) = sum w z / sum w per pixel, +inf where
-    nothing contributed."""
+    nothing contributed.  deterministic=True: the backward sums in a fixed order (the module's docstring)."""
     width = aux.width if width is None else int(width)
     height = aux.height if height is None else int(height)
     rec_c = _cuda_f32(rec, "rec", 8)
@@ -475,18 +502,23 @@ def rasterize(rec, col, aux, width=None, height=None, depths=None):
     if rec_c.shape[0] != aux.n or col_c.shape[0] != aux.n:
         raise SplatError(-1, "rec, col and the projection must hold the same number of splats")
     if depths is None:
+        if deterministic:
+            return _functions()[2].apply(rec_c, col_c, aux, width, height, None, True)
         return _functions()[2].apply(rec_c, col_c, aux, width, height)
     z = _cuda_f32(depths, "depths")
     if z.dim() != 1 or z.shape[0] != aux.n:
         raise SplatError(-1, f"depths must have shape ({aux.n},), not {tuple(z.shape)}")
+    if deterministic:
+        return _functions()[2].apply(rec_c, col_c, aux, width, height, z, True)
     return _functions()[2].apply(rec_c, col_c, aux, width, height, z)
 
 
 def render_gaussians(camera_or_uniforms, means, scales, rotations, opacities, colors=None, sh=None, width=None, height=None, degree=None,
-                     return_depth=False):
+                     return_depth=False, deterministic=False):
     """The whole differentiable frame: project_ellipsoids, the colour (sh_colors when `sh` is given, else cat(colors,
     opacities)), rasterize.  Returns (rgb (H, W, 3), alpha (H, W)); return_depth=True: (rgb, alpha, depth (H, W)), the depth
-    map of the ProjectedSplat depths (the distance from the eye to each centre)."""
+    map of the ProjectedSplat depths (the distance from the eye to each centre).  deterministic=True: every gradient is the
+    same bits on every run (rasterize's fixed-order backward; the module's docstring)."""
     if width is None or height is None:
         raise SplatError(-1, "render_gaussians needs width and height")
     for name, t in (("means", means), ("scales", scales), ("rotations", rotations), ("opacities", opacities)):
@@ -511,7 +543,7 @@ def render_gaussians(camera_or_uniforms, means, scales, rotations, opacities, co
         col = _t().cat([colors, opacities.reshape(-1, 1)], dim=1)
     else:
         raise SplatError(-1, "render_gaussians needs colors or sh")
-    return rasterize(rec, col, aux, width, height, depths=depths)
+    return rasterize(rec, col, aux, width, height, depths=depths, deterministic=deterministic)
 
 
 def _image(t, name, channels):

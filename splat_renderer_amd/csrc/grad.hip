@@ -18,6 +18,13 @@
 //   ws = sum w and zw = sum w z beside T, walk 2 carries D as a fifth channel of colour z_i - D, background 0 and upstream
 //   G_D / ws, and each entry sums a tenth number, w_i G_D / ws, into grad_depth (1 float per splat).  z_i is staged in the
 //   entry's unused c.y.
+//   <DET = true> (splat_composite_backward_det) hands the same per-(entry, number) sums to no atomic: it stores them to slots
+//   of the caller's workspace, splat-major (k_det_rect_count and the scan give every splat the first slot of its tile
+//   rectangle; a tile's slot is its row-major position in it), and writes per tile {largest L, depth key and index of its last
+//   consumed entry}.  k_det_gather then adds, per splat, the slots of the tiles that consumed it - lists ascend in (key,
+//   index), so one compare with the tile's row decides - each tile row left to right, the rows top to bottom, and the total
+//   once into the splat's row: the order include/splat.h states, the same bits on every run.  The instantiations without DET
+//   are the kernel as it was, instruction for instruction.
 // k_project_ellipsoid_backward   one thread per splat: the record's gradient through B = U / 3, U(a, b, c), Sigma2 = T T^T + 0.3 I,
 //   T = J M, M = R S, the quaternion's normalisation and J's and the centre's dependence on the position, in float64.  The
 //   cull decisions are ellipsoid_record's own (binary32); a culled splat gets exact zeros.  <DEPTH = true> adds the ProjectedSplat
@@ -31,6 +38,7 @@
 //   instruction for instruction.
 #include "common.h"
 #include "variant.h"
+#include "tile_range.h"
 #include "disc.h"
 #include "ellipsoid.h"
 
@@ -78,6 +86,35 @@ struct BackDepthParams : BackParams {
     float *grad_depth;
 };
 
+// the fixed-order variant's further arguments (splat_composite_backward_det): the ProjectedSplats the lists were binned from
+// and the three parts of the caller's workspace.  It does not write grad_records / grad_color / grad_depth: k_det_gather does.
+struct BackDetParams : BackDepthParams {
+    const float4 *projected;    // 2 float4 per splat: bounds, then depth in .x
+    const uint32_t *slot_base;  // per splat: its first slot (the exclusive scan of the rectangles' tile counts)
+    float *slots;               // slot_cap slots of NV floats, splat-major
+    uint4 *tile_table;          // per tile {largest L, depth key and splat index of the last consumed entry, 0}
+    uint32_t slot_cap, nty;
+};
+
+constexpr uint32_t DET_NO_SLOT = 0xffffffffu;
+
+// extract-depth-keys' key of a ProjectedSplat depth (project.hip's depth_key): the lists ascend in (key, index)
+__device__ __forceinline__ uint32_t det_depth_key(float depth) {
+    const uint32_t bits = __float_as_uint(depth);
+    return bits ^ (((bits >> 31) == 1u) ? 0xffffffffu : 0x80000000u);
+}
+
+// Splat idx's slot for tile (tx, ty): slot_base[idx] + the tile's row-major position in the splat's tile rectangle (the
+// binner's tile_range of its bounds over the whole screen).  DET_NO_SLOT for a tile outside the rectangle (lists that were
+// not binned from this `projected`) or a slot at or past slot_cap: nothing is stored then.
+__device__ __forceinline__ uint32_t det_slot(const BackDetParams &p, uint32_t idx, uint32_t tx, uint32_t ty) {
+    uint32_t tx0, tx1, ty0, ty1;
+    if (!tile_range(p.projected[(size_t)idx * 2], p.width, p.height, GT, p.ntx, p.nty, 0u, p.nty, tx0, tx1, ty0, ty1)) return DET_NO_SLOT;
+    if (tx < tx0 || tx > tx1 || ty < ty0 || ty > ty1) return DET_NO_SLOT;
+    const uint64_t slot = (uint64_t)p.slot_base[idx] + (uint64_t)(ty - ty0) * (tx1 - tx0 + 1u) + (tx - tx0);
+    return slot < p.slot_cap ? (uint32_t)slot : DET_NO_SLOT;
+}
+
 // stages entries [c0, c0 + m) of the tile's list (threads 0 .. m-1)
 template <bool DEPTH, typename P>
 __device__ __forceinline__ void stage_chunk(const P &p, uint32_t off, uint32_t c0, uint32_t m, GradEntry *s_ent, uint32_t *s_idx) {
@@ -117,14 +154,29 @@ __device__ __forceinline__ bool entry_alpha(const GradEntry &e, float pxf, float
 
 } // namespace
 
-template <bool DEPTH, bool PX>
-__global__ __launch_bounds__(256) void k_composite_backward(std::conditional_t<DEPTH, BackDepthParams, BackParams> p) {
+// (DET) per staged entry its slot; no LDS in the instantiations without
+template <bool DET>
+__device__ __forceinline__ uint32_t *det_slot_lds() {
+    if constexpr (DET) {
+        __shared__ uint32_t s_slot[GCH];
+        return s_slot;
+    } else {
+        return nullptr;
+    }
+}
+
+// <DET = true> (splat_composite_backward_det): the same sums, stored to the splat-major slots of BackDetParams for k_det_gather
+// to add in a fixed order, where <DET = false> hands them to float atomic adds into the splats' rows.
+template <bool DEPTH, bool PX, bool DET = false>
+__global__ __launch_bounds__(256) void k_composite_backward(
+    std::conditional_t<DET, BackDetParams, std::conditional_t<DEPTH, BackDepthParams, BackParams>> p) {
     constexpr int NV = DEPTH ? GNV + 1 : GNV; // (the tenth: dL/dz)
     __shared__ GradEntry s_ent[GCH];
     __shared__ uint32_t s_idx[GCH];
     __shared__ float s_part[4][GCH][NV];
     __shared__ uint32_t s_touch[GCH];
     __shared__ uint32_t s_maxL;
+    uint32_t *const s_slot = det_slot_lds<DET>();
 
     const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const uint32_t tx = blockIdx.x, ty = blockIdx.y;
@@ -189,12 +241,25 @@ __global__ __launch_bounds__(256) void k_composite_backward(std::conditional_t<D
     float Tn = T;                                          // T_{i+1} on the way back
     __syncthreads();
     const uint32_t maxL = s_maxL;
+    if constexpr (DET) { // the tile's row of the table: which of its entries have a slot that walk 2 stores
+        if (tid == 0) {
+            uint4 row = make_uint4(maxL, 0u, 0u, 0u);
+            if (maxL) {
+                row.z = p.indices[off + maxL - 1];
+                row.y = det_depth_key(p.projected[(size_t)row.z * 2 + 1].x);
+            }
+            p.tile_table[tile_idx] = row;
+        }
+    }
 
     // ---- walk 2: back to front from the tile's largest L ----
     for (uint32_t cend = maxL; cend > 0;) {
         const uint32_t c0 = cend > GCH ? cend - GCH : 0, m = cend - c0;
         __syncthreads(); // the previous chunk's sums are added
         stage_chunk<DEPTH>(p, off, c0, m, s_ent, s_idx);
+        if constexpr (DET) {
+            if (tid < m) s_slot[tid] = det_slot(p, s_idx[tid], tx, ty); // (s_idx[tid]: this thread's own store)
+        }
         if (tid < GCH) s_touch[tid] = 0;
         __syncthreads();
         for (int j = (int)m - 1; j >= 0; --j) {
@@ -246,19 +311,129 @@ __global__ __launch_bounds__(256) void k_composite_backward(std::conditional_t<D
             }
         }
         __syncthreads();
-        // one atomic add per touched (entry, number): the nine sums of an entry are its records row (20 of 32 bytes) and
-        // its colour row (16 bytes), the depth variant's tenth its grad_depth word
-        for (uint32_t q = tid; q < m * NV; q += 256) {
-            const uint32_t e = q / NV, k = q - e * NV;
-            if (!s_touch[e]) continue;
-            const float sum = (s_part[0][e][k] + s_part[1][e][k]) + (s_part[2][e][k] + s_part[3][e][k]);
-            const size_t idx = s_idx[e];
-            float *dst = k < 5 ? p.grad_records + idx * 8 + (k < 4 ? k : 5u) : p.grad_color + idx * 4 + (k - 5);
-            if constexpr (DEPTH) dst = k == GNV ? p.grad_depth + idx : dst;
-            atomicAdd(dst, sum);
+        if constexpr (DET) {
+            // one store per (entry, number), touched or not (an untouched entry's four partials are zeros): every slot below
+            // the tile's largest L is written, NV contiguous floats each
+            for (uint32_t q = tid; q < m * NV; q += 256) {
+                const uint32_t e = q / NV, k = q - e * NV;
+                const float sum = (s_part[0][e][k] + s_part[1][e][k]) + (s_part[2][e][k] + s_part[3][e][k]);
+                const uint32_t slot = s_slot[e];
+                if (slot != DET_NO_SLOT) p.slots[(size_t)slot * NV + k] = sum;
+            }
+        } else {
+            // one atomic add per touched (entry, number): the nine sums of an entry are its records row (20 of 32 bytes) and
+            // its colour row (16 bytes), the depth variant's tenth its grad_depth word
+            for (uint32_t q = tid; q < m * NV; q += 256) {
+                const uint32_t e = q / NV, k = q - e * NV;
+                if (!s_touch[e]) continue;
+                const float sum = (s_part[0][e][k] + s_part[1][e][k]) + (s_part[2][e][k] + s_part[3][e][k]);
+                const size_t idx = s_idx[e];
+                float *dst = k < 5 ? p.grad_records + idx * 8 + (k < 4 ? k : 5u) : p.grad_color + idx * 4 + (k - 5);
+                if constexpr (DEPTH) dst = k == GNV ? p.grad_depth + idx : dst;
+                atomicAdd(dst, sum);
+            }
         }
         cend = c0;
     }
+}
+
+// The number of tiles in every splat's tile rectangle (0: it bins nowhere); their exclusive scan is slot_base.
+__global__ __launch_bounds__(256) void k_det_rect_count(const float4 *__restrict__ projected, uint32_t n, uint32_t width, uint32_t height,
+                                                        uint32_t ntx, uint32_t nty, uint32_t *__restrict__ count) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    uint32_t tx0, tx1, ty0, ty1;
+    const bool ok = tile_range(projected[(size_t)i * 2], width, height, GT, ntx, nty, 0u, nty, tx0, tx1, ty0, ty1);
+    count[i] = ok ? (tx1 - tx0 + 1u) * (ty1 - ty0 + 1u) : 0u; // (at most 65535^2)
+}
+
+// One tile row of a splat's rectangle: (((+0 + P(tile 0)) + P(tile 1)) + ...) over the `cols` tiles from `tile0`, whose slots
+// start at slot0.  A slot holds a sum exactly when its tile consumed the splat's entry: lists ascend strictly in (depth key,
+// index), so that is when (key, idx) is not past the tile's last consumed entry.  Other tiles add nothing.
+template <int NV>
+__device__ __forceinline__ bool det_row_sum(const BackDetParams &p, uint32_t tile0, uint32_t cols, uint64_t slot0, uint32_t key, uint32_t idx,
+                                            float (&row)[NV]) {
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) row[k] = 0.0f;
+    for (uint32_t c = 0; c < cols; ++c) {
+        const uint4 t = p.tile_table[tile0 + c];
+        const uint64_t slot = slot0 + c;
+        if (t.x == 0u || key > t.y || (key == t.y && idx > t.z) || slot >= p.slot_cap) continue;
+        const float *src = p.slots + (size_t)slot * NV;
+        any = true;
+#pragma unroll
+        for (int k = 0; k < NV; ++k) row[k] += src[k];
+    }
+    return any;
+}
+
+// k_det_gather   one thread per splat: the slots of its rectangle added in the contract's order (include/splat.h) — each tile
+//   row left to right from +0, the rows top to bottom from +0 — and the total added once to the splat's prior row.  A
+//   rectangle of more than DET_WIDE tiles in more than one row is taken by its whole wave in turn: lane r sums row r (and r +
+//   64, ...), and the row sums are then added in row order, read lane by lane.  Which lanes add what changes; the order of
+//   the additions does not.  A splat with no consumed entry keeps its prior bits.
+constexpr uint32_t DET_WIDE = 64;
+
+template <bool DEPTH>
+__global__ __launch_bounds__(256) void k_det_gather(BackDetParams p, uint32_t n) {
+    constexpr int NV = DEPTH ? GNV + 1 : GNV;
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
+    uint32_t tx0 = 0, tx1 = 0, ty0 = 0, ty1 = 0, key = 0, base = 0;
+    bool ok = false;
+    if (i < n) {
+        ok = tile_range(p.projected[(size_t)i * 2], p.width, p.height, GT, p.ntx, p.nty, 0u, p.nty, tx0, tx1, ty0, ty1);
+        key = det_depth_key(p.projected[(size_t)i * 2 + 1].x);
+        base = p.slot_base[i];
+    }
+    const uint32_t cols = ok ? tx1 - tx0 + 1u : 0u, rows = ok ? ty1 - ty0 + 1u : 0u;
+    const bool wide = rows > 1u && cols * rows > DET_WIDE;
+    float total[NV];
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) total[k] = 0.0f;
+    if (ok && !wide) {
+        for (uint32_t r = 0; r < rows; ++r) {
+            float row[NV];
+            any |= det_row_sum<NV>(p, (ty0 + r) * p.ntx + tx0, cols, (uint64_t)base + (uint64_t)r * cols, key, i, row);
+#pragma unroll
+            for (int k = 0; k < NV; ++k) total[k] += row[k];
+        }
+    }
+    for (unsigned long long todo = __ballot(wide); todo; todo &= todo - 1ull) {
+        const int src = __ffsll((long long)todo) - 1;
+        const uint32_t s_tx0 = __shfl(tx0, src), s_ty0 = __shfl(ty0, src), s_cols = __shfl(cols, src), s_rows = __shfl(rows, src);
+        const uint32_t s_key = __shfl(key, src), s_base = __shfl(base, src), s_idx = (i - lane) + (uint32_t)src;
+        float tot[NV];
+        bool mine = false;
+#pragma unroll
+        for (int k = 0; k < NV; ++k) tot[k] = 0.0f;
+        for (uint32_t r0 = 0; r0 < s_rows; r0 += 64u) {
+            const uint32_t r = r0 + lane, cnt = min(64u, s_rows - r0);
+            float row[NV];
+#pragma unroll
+            for (int k = 0; k < NV; ++k) row[k] = 0.0f;
+            if (r < s_rows)
+                mine |= det_row_sum<NV>(p, (s_ty0 + r) * p.ntx + s_tx0, s_cols, (uint64_t)s_base + (uint64_t)r * s_cols, s_key, s_idx, row);
+            for (uint32_t q = 0; q < cnt; ++q) {
+#pragma unroll
+                for (int k = 0; k < NV; ++k) tot[k] += __shfl(row[k], (int)q);
+            }
+        }
+        const bool hit = __ballot(mine) != 0ull;
+        if ((int)lane == src) {
+            any = hit;
+#pragma unroll
+            for (int k = 0; k < NV; ++k) total[k] = tot[k];
+        }
+    }
+    if (!any) return;
+    float *grec = p.grad_records + (size_t)i * 8, *gcol = p.grad_color + (size_t)i * 4;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) grec[k < 4 ? k : 5] += total[k];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) gcol[k] += total[5 + k];
+    if constexpr (DEPTH) p.grad_depth[i] += total[GNV];
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -630,11 +805,34 @@ __global__ __launch_bounds__(256) void k_sh_colors_backward(float ex, float ey, 
 // ---------------------------------------------------------------------------------------------------------------------
 // The two composite backwards: their checks, the kernel's parameters and the launch.  depth: splat_composite_backward_depth,
 // with its four further arguments.
+// det: splat_composite_backward_det's further arguments, or NULL for the two atomic entry points.
+struct DetArgs {
+    const void *projected;
+    uint64_t total_pairs;
+    void *workspace;
+    uint64_t workspace_bytes;
+};
+
+// The workspace of splat_composite_backward_det: the tile table (16 bytes per tile), slot_base (4 bytes per splat, rounded up
+// to 16) and the slots (4 NV bytes per pair, NV = 9, or 10 with depth).  0 where it would not fit 64 bits.
+static uint64_t det_workspace_bytes(uint64_t total_pairs, uint32_t num_tiles, uint32_t n, bool depth, uint64_t *slot_base_off = nullptr,
+                                    uint64_t *slots_off = nullptr) {
+    const uint64_t table = (uint64_t)num_tiles * 16u, base = ((uint64_t)n * 4u + 15u) & ~15ull;
+    if (slot_base_off) *slot_base_off = table;
+    if (slots_off) *slots_off = table + base;
+    if (total_pairs > (~0ull - table - base) / 40u) return 0;
+    return table + base + total_pairs * 4u * (depth ? GNV + 1 : GNV);
+}
+
+extern "C" uint64_t splat_composite_backward_det_workspace_bytes(uint64_t total_pairs, uint32_t num_tiles, uint32_t n, int with_depth) {
+    return det_workspace_bytes(total_pairs, num_tiles, n, with_depth != 0);
+}
+
 static int composite_backward_launch(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4,
                                      const void *records, const void *tile_indices, const void *tile_counts, const void *tile_offsets,
                                      uint32_t width, uint32_t height, const void *grad_rgba32f, uint32_t n, void *grad_records,
                                      void *grad_color_opacity, bool depth, const void *depth_f32, uint32_t depth_stride_floats,
-                                     const void *grad_depth_f32, void *grad_depth) {
+                                     const void *grad_depth_f32, void *grad_depth, const DetArgs *det = nullptr) {
     if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
     ARG_CHECK(ctx, cfg != nullptr);
     if (cfg->footprint != SPLAT_FOOTPRINT_ELLIPSOID || cfg->mode != SPLAT_COMPOSITE_FRONT_TO_BACK || cfg->early_out != 1 ||
@@ -654,8 +852,15 @@ static int composite_backward_launch(splat_ctx *ctx, const splat_composite_cfg *
         ARG_CHECK(ctx, depth_f32 && grad_depth_f32 && (n == 0 || grad_depth) && depth_stride_floats >= 1);
         ARG_CHECK(ctx, (((uintptr_t)depth_f32 | (uintptr_t)grad_depth_f32 | (uintptr_t)grad_depth) & 3) == 0);
     }
+    uint64_t slot_base_off = 0, slots_off = 0;
+    if (det) {
+        // (a slot index is a u32, as a list offset is)
+        ARG_CHECK(ctx, det->projected && ((uintptr_t)det->projected & 15) == 0 && det->total_pairs <= 0xffffffffull);
+        const uint64_t need = det_workspace_bytes(det->total_pairs, ntx * nty, n, depth, &slot_base_off, &slots_off);
+        ARG_CHECK(ctx, det->workspace && ((uintptr_t)det->workspace & 15) == 0 && need != 0 && det->workspace_bytes >= need);
+    }
     if (n == 0) return SPLAT_OK; // (no splat: every list is empty)
-    BackDepthParams p;
+    BackDetParams p;
     p.color = (const float4 *)color_opacity;
     p.color_stride = color_stride_vec4;
     p.records = (const float4 *)records;
@@ -672,6 +877,25 @@ static int composite_backward_launch(splat_ctx *ctx, const splat_composite_cfg *
     p.z_stride = depth_stride_floats;
     p.grad_depth_img = (const float *)grad_depth_f32;
     p.grad_depth = (float *)grad_depth;
+    if (det) {
+        // slot_base (the scan of the rectangles' tile counts), the tile kernel storing its sums to the slots, the gather
+        p.projected = (const float4 *)det->projected;
+        p.tile_table = (uint4 *)det->workspace;
+        uint32_t *slot_base = (uint32_t *)((char *)det->workspace + slot_base_off);
+        p.slot_base = slot_base;
+        p.slots = (float *)((char *)det->workspace + slots_off);
+        p.slot_cap = (uint32_t)det->total_pairs;
+        p.nty = nty;
+        launch_kernel(ctx, NO_STAGE, k_det_rect_count, dim3(div_up(n, 256)), dim3(256), p.projected, n, width, height, ntx, nty, slot_base);
+        LAUNCH_CHECK(ctx, "launch k_det_rect_count");
+        const int rc = splat_scan_u32(ctx, slot_base, slot_base, n, nullptr);
+        if (rc != SPLAT_OK) return rc;
+        variant_dispatch([&](auto d, auto px) { launch_kernel(ctx, NO_STAGE, k_composite_backward<d.value, px.value, true>, dim3(ntx, nty), dim3(256), p); },
+                         depth, composite_uses_px(ctx, ntx, nty));
+        LAUNCH_CHECK(ctx, "launch k_composite_backward<DET>");
+        variant_dispatch([&](auto d) { launch_kernel(ctx, NO_STAGE, k_det_gather<d.value>, dim3(div_up(n, 256)), dim3(256), p, n); }, depth);
+        return launch_check(ctx, "launch k_det_gather");
+    }
     // (<DEPTH, PX>: the kernel without DEPTH takes the BackParams part of p)
     variant_dispatch([&](auto d, auto px) { launch_kernel(ctx, NO_STAGE, k_composite_backward<d.value, px.value>, dim3(ntx, nty), dim3(256), p); },
                      depth, composite_uses_px(ctx, ntx, nty));
@@ -694,6 +918,20 @@ extern "C" int splat_composite_backward_depth(splat_ctx *ctx, const splat_compos
     return composite_backward_launch(ctx, cfg, color_opacity, color_stride_vec4, records, tile_indices, tile_counts, tile_offsets, width, height,
                                      grad_rgba32f, n, grad_records, grad_color_opacity, true, depth_f32, depth_stride_floats, grad_depth_f32,
                                      grad_depth);
+}
+
+extern "C" int splat_composite_backward_det(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity,
+                                            uint32_t color_stride_vec4, const void *records, const void *projected, const void *tile_indices,
+                                            const void *tile_counts, const void *tile_offsets, uint64_t total_pairs, uint32_t width,
+                                            uint32_t height, const void *grad_rgba32f, uint32_t n, void *grad_records, void *grad_color_opacity,
+                                            const void *depth_f32, uint32_t depth_stride_floats, const void *grad_depth_f32, void *grad_depth,
+                                            void *workspace, uint64_t workspace_bytes) {
+    // (colour only: the four depth arguments all NULL / 0; any of them given asks for the depth variant, with its checks)
+    const bool depth = depth_f32 || depth_stride_floats || grad_depth_f32 || grad_depth;
+    const DetArgs det = {projected, total_pairs, workspace, workspace_bytes};
+    return composite_backward_launch(ctx, cfg, color_opacity, color_stride_vec4, records, tile_indices, tile_counts, tile_offsets, width, height,
+                                     grad_rgba32f, n, grad_records, grad_color_opacity, depth, depth_f32, depth_stride_floats, grad_depth_f32,
+                                     grad_depth, &det);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -45,6 +45,13 @@ The other strategy is 3DGS-MCMC (include/splat.h, "MCMC relocation"), for a fit 
 
 relocate() and add_new() replace densify_and_prune() and reset_opacity() and are not used beside them.  The regularisers reach
 splats the frame did not see, whose gradient a masked Adam step would drop: an MCMC fit wants sparse=False.
+
+GaussianFit(..., deterministic=True) makes a fit repeatable bit for bit: two runs from the same arrays, targets, cameras and
+seeds end in the same parameters, the same moments and the same PLY bytes.  Every kernel of a step sums in a fixed order or
+not at all, except the composite's backward, whose float atomics arrive in a varying order; the flag replaces it with
+autograd.rasterize's deterministic=True (splat_composite_backward_det).  It costs a workspace per backward of 16 bytes per
+tile + 4 per splat + 36 per (tile, splat) pair of the frame's lists (40 with a depth gradient), and the time of a second pass
+over it.  The default is the atomic path: two runs then drift apart after the first step.
 """
 import ctypes as C
 import math
@@ -61,12 +68,14 @@ PLANES = ("means", "log_scales", "rotations", "opacity_logits", "sh")
 
 class GaussianFit:
     def __init__(self, means, scales, rotations, opacity, sh, degree=None, lr=None, betas=(0.9, 0.999), eps=1e-15, sparse=True,
-                 device="cuda", exact_activations=False):
+                 device="cuda", exact_activations=False, deterministic=False):
         """means (n, 3), scales (n, 3) > 0, rotations (n, 4), opacity (n,) in (0, 1), sh (n, K, 3) or (n, 3 K), K = (degree +
         1)^2: arrays or tensors of activated values.  lr: a dict that overrides entries of DEFAULT_LR.  exact_activations:
         render() forms exp and sigmoid in float64 and rounds once, as load_gaussian_ply does, so the frame the fit renders is the
         frame its saved PLY renders; with the default float32 activations the two differ by an ulp in some scales and opacities,
-        which now and then carries one pixel across a splat's 3-sigma cut (a step of up to 0.011 x opacity in that pixel)."""
+        which now and then carries one pixel across a splat's 3-sigma cut (a step of up to 0.011 x opacity in that pixel).
+        deterministic: render() asks autograd.rasterize for its fixed-order backward, so that the whole fit is bit-reproducible
+        (the module's docstring)."""
         torch = AG._t()
         t = lambda a: torch.as_tensor(a, dtype=torch.float32).to(device).detach()  # noqa: E731
         means, scales, rotations, opacity, sh = t(means), t(scales), t(rotations), t(opacity).reshape(-1), t(sh)
@@ -81,6 +90,7 @@ class GaussianFit:
         self.lr = dict(DEFAULT_LR, **(lr or {}))
         self.betas, self.eps, self.sparse = (float(betas[0]), float(betas[1])), float(eps), bool(sparse)
         self.exact_activations = bool(exact_activations)
+        self.deterministic = bool(deterministic)
         self.steps = 0
         self.densifications = 0
         self.relocations = self.additions = self.noises = 0
@@ -157,7 +167,7 @@ class GaussianFit:
         if rec.requires_grad:
             rec.retain_grad()
         self._frame = (rec, int(width), int(height))
-        return AG.rasterize(rec, col, aux, width, height, depths=depths)
+        return AG.rasterize(rec, col, aux, width, height, depths=depths, deterministic=self.deterministic)
 
     def step(self, lr=None):
         """One optimiser step after backward(): this frame's density statistics and visibility mask, five Adam launches, the

@@ -18,7 +18,7 @@
 
 #include "../../include/splat.h"
 
-#define MAX_ARGS 18
+#define MAX_ARGS 22
 
 typedef struct {
     napi_env env;
@@ -385,6 +385,22 @@ FN(composite_backward_depth) { /* composite_backward's arguments, then depth, de
     void *z = arg_dptr(&c, 14); uint32_t zs = (uint32_t)arg_number(&c, 15); void *gdimg = arg_dptr(&c, 16), *gz = arg_dptr(&c, 17); BAIL;
     return check(env, x, splat_composite_backward_depth(x, &cfg, col, cs, rec, idx, cnt, off, w, h, gimg, n, grec, gcol, z, zs, gdimg, gz),
                  mk_undefined(env));
+}
+FN(composite_backward_det_workspace_bytes) { /* (totalPairs, numTiles, n, withDepth) -> bytes */
+    ARGS(4); uint64_t pairs = (uint64_t)arg_number(&c, 0); uint32_t tiles = (uint32_t)arg_number(&c, 1), n = (uint32_t)arg_number(&c, 2);
+    int depth = (int)arg_number(&c, 3); BAIL;
+    return mk_number(env, (double)splat_composite_backward_det_workspace_bytes(pairs, tiles, n, depth));
+}
+FN(composite_backward_det) { /* (ctx, cfg[8], colorOpacity, cStride, records, projected, indices, counts, offsets, totalPairs, W, H, gradRgba32f, n, gradRecords, gradColorOpacity, depth|null, depthStrideFloats, gradDepthImage|null, gradDepth|null, workspace, workspaceBytes) */
+    ARGS(22); splat_ctx *x = arg_external(&c, 0); splat_composite_cfg cfg; fill_cfg(&c, 1, &cfg);
+    void *col = arg_dptr(&c, 2); uint32_t cs = (uint32_t)arg_number(&c, 3); void *rec = arg_dptr(&c, 4), *proj = arg_dptr(&c, 5);
+    void *idx = arg_dptr(&c, 6), *cnt = arg_dptr(&c, 7), *off = arg_dptr(&c, 8); uint64_t pairs = (uint64_t)arg_number(&c, 9);
+    uint32_t w = (uint32_t)arg_number(&c, 10), h = (uint32_t)arg_number(&c, 11); void *gimg = arg_dptr(&c, 12);
+    uint32_t n = (uint32_t)arg_number(&c, 13); void *grec = arg_dptr(&c, 14), *gcol = arg_dptr(&c, 15);
+    void *z = arg_dptr(&c, 16); uint32_t zs = (uint32_t)arg_number(&c, 17); void *gdimg = arg_dptr(&c, 18), *gz = arg_dptr(&c, 19);
+    void *ws = arg_dptr(&c, 20); uint64_t wb = (uint64_t)arg_number(&c, 21); BAIL;
+    return check(env, x, splat_composite_backward_det(x, &cfg, col, cs, rec, proj, idx, cnt, off, pairs, w, h, gimg, n, grec, gcol, z, zs, gdimg, gz,
+                                                      ws, wb), mk_undefined(env));
 }
 FN(project_ellipsoid_backward) { /* (ctx, Float32Array(22), positions, posStride, scales, scaleStride, rotations, rotStride, n, gradRecords, gradPositions, gradScales, gradRotations) */
     ARGS(13); splat_ctx *x = arg_external(&c, 0); size_t ub = 0; float *u = arg_hostbuf(&c, 1, &ub);
@@ -819,6 +835,7 @@ static napi_value init(napi_env env, napi_value exports) {
         EXPORT(point_frame), EXPORT(project_ellipsoid), EXPORT(sh_colors), EXPORT(render_frame_ellipsoids),
         EXPORT(composite_backward), EXPORT(project_ellipsoid_backward), EXPORT(sh_colors_backward),
         EXPORT(composite_aov_depth), EXPORT(composite_backward_depth), EXPORT(project_ellipsoid_backward_depth),
+        EXPORT(composite_backward_det_workspace_bytes), EXPORT(composite_backward_det),
         EXPORT(project_ellipsoid_backward_camera), EXPORT(sh_colors_backward_camera),
         EXPORT(image_loss_workspace_bytes), EXPORT(image_loss), EXPORT(image_loss_backward),
         EXPORT(adam_step), EXPORT(density_accumulate), EXPORT(densify_plan_workspace_bytes), EXPORT(densify_plan),

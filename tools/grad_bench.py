@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Gradients of ellipsoid frames (GPU box only): python tools/grad_bench.py [--depth] [--camera | --loss | --optimizer] [C1,C2] [K] [R]
+"""Gradients of ellipsoid frames (GPU box only): python tools/grad_bench.py [--depth] [--deterministic] [--camera | --loss | --optimizer] [C1,C2] [K] [R]
 
 tools/ellipsoid_bench.py's scenes and method (the scene's positions, sigma = radius / 2 per axis times a random factor in
 [e^-0.3, e^0.3], random rotations, SH of degree 3 with the scene's opacity; R rounds of K calls per kind, kinds alternating
@@ -14,6 +14,13 @@ the time they take at 1.3 TB/s.
 depth loss as well (loss += sum of depth * a fixed random image where depth is finite), the depth variant of the composite
 backward alone (splat_composite_backward_depth) and of the projector's (splat_project_ellipsoid_backward_depth); the atomic
 bytes then count 40 per consumed pair (the tenth sum, dL/dz).
+
+--deterministic adds the fixed-order composite backward beside the atomic one, alternating in the same rounds:
+splat_composite_backward_det alone (composite_backward_det; with --depth also its depth variant) - all of its launches: the
+rectangle count, its scan, the tile kernel storing to the slots, the gather - and the whole frame's backward with
+rasterize(..., deterministic=True) (backward_det); their ratios to the atomic path; the workspace bytes; the slots the tile
+kernel wrote (the sum of the tile table's largest L, read back from the workspace) and the time the gather's bytes - every
+written slot once out and once in, 36 or 40 B each, plus the 16 B table rows - take at the 5.1 TB/s copy rate.
 
 --camera adds the camera gradients: splat_project_ellipsoid_backward_camera without and with grad_depth (all of its launches:
 the per-splat kernel with the per-wave sums, then k_camera_sum_slices above 1024 partials, then k_camera_sum) beside
@@ -105,7 +112,8 @@ def torch_camera_terms(U, pos, scl, rot, g, W, H):
     return torch.stack(terms, dim=1).sum(dim=0)
 
 
-argv = [a for a in sys.argv[1:] if a not in ("--depth", "--camera", "--loss", "--optimizer")]
+argv = [a for a in sys.argv[1:] if a not in ("--depth", "--camera", "--loss", "--optimizer", "--deterministic")]
+det_too = "--deterministic" in sys.argv[1:]
 optimizer_only = "--optimizer" in sys.argv[1:]
 depth_too = "--depth" in sys.argv[1:]
 camera_too = "--camera" in sys.argv[1:]
@@ -502,6 +510,26 @@ for name in names:
                                                                                          gs.data_ptr(), gq.data_ptr(), gzp.data_ptr()),
         })
 
+    if det_too:
+        det_bytes = {d: int(lib.splat_composite_backward_det_workspace_bytes(pairs, tiles, n, d)) for d in (0, 1)}
+        det_ws = torch.empty(det_bytes[1] // 4 + 4, dtype=torch.int32, device="cuda")
+        projected = state["aux"].projected
+
+        def forward_det():
+            rec, aux = AG.project_ellipsoids(u, means, scales, rots)
+            col = AG.sh_colors(u[16:19], means, shs, 3, ops)
+            rgb, _ = AG.rasterize(rec, col, aux, w, h, deterministic=True)
+            state.update(rec=rec, col=col, aux=aux, loss=(rgb * gimg).sum())
+
+        def det_entry(depth):
+            tail = (zs.data_ptr(), 1, gdimg.data_ptr(), gz.data_ptr()) if depth else (None, 0, None, None)
+            return lambda: lib.splat_composite_backward_det(cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr(), projected.data_ptr(), idx, cnt,
+                                                            off, pairs, w, h, g4.data_ptr(), n, grec.data_ptr(), gcol.data_ptr(), *tail,
+                                                            det_ws.data_ptr(), det_bytes[int(depth)])
+        work.update({"forward_det": forward_det, "backward_det": None, "composite_backward_det": det_entry(False)})
+        if depth_too:
+            work["composite_backward_det_depth"] = det_entry(True)
+
     if camera_too:
         ut = torch.tensor(u, device="cuda", requires_grad=True)
         gu, ge = torch.empty(24, device="cuda"), torch.empty(4, device="cuda")
@@ -547,6 +575,8 @@ for name in names:
     forwards = {"backward": forward, "backward_depth": forward_depth}
     if camera_too:
         forwards["backward_camera"] = forward_camera
+    if det_too:
+        forwards["backward_det"] = forward_det
 
     def run(kind, calls):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -581,6 +611,18 @@ for name in names:
     if depth_too:
         extra = {"atomic_bytes_bound_depth": 40 * consumed_pairs, "atomic_floor_ms_depth": round(40 * consumed_pairs / ATOMIC_RATE * 1e3, 4),
                  "composite_backward_depth_over_colour": round(med["composite_backward_depth"] / med["composite_backward"], 3)}
+    if det_too:
+        _lib.check(work["composite_backward_det"](), cx.ctx)
+        torch.cuda.synchronize()
+        written = int(det_ws[:4 * tiles].reshape(tiles, 4)[:, 0].to(torch.int64).sum())  # (the tile table's largest L: the slots stored)
+        extra.update({"det_workspace_bytes": det_bytes[0], "det_slots_written": written,
+                      "det_gather_floor_ms": round((2 * 36 * written + 16 * tiles) / COPY_RATE * 1e3, 4),
+                      "composite_backward_det_over_atomic": round(med["composite_backward_det"] / med["composite_backward"], 3),
+                      "backward_det_over_atomic": round(med["backward_det"] / med["backward"], 3)})
+        if depth_too:
+            extra.update({"det_workspace_bytes_depth": det_bytes[1],
+                          "det_gather_floor_ms_depth": round((2 * 40 * written + 16 * tiles) / COPY_RATE * 1e3, 4),
+                          "composite_backward_det_depth_over_atomic": round(med["composite_backward_det_depth"] / med["composite_backward_depth"], 3)})
     if camera_too:
         extra.update({f"{a}_over_{b}": round(med[a] / med[b], 3) for a, b in (
             ("project_backward_camera", "project_backward"), ("project_backward_camera_depth", "project_backward_depth"),
