@@ -456,6 +456,49 @@ int splat_render_frame_ellipsoids(splat_ctx *ctx, splat_sorter *sorter, splat_bi
                                   uint32_t width, uint32_t height, void *projected, void *out_rgba8, void *out_rgba32f,
                                   const splat_aov *aov);
 
+/* ---- antialiased frames of anisotropic 3D Gaussians: the 2D Mip filter (an extension; opt-in, nothing above changes) ----
+ * Sigma2 = J Sigma3 J^T + 0.3 I draws a splat whose projected variance is far below a pixel with variance 0.3 px^2 and its
+ * full opacity: many times the energy it should deposit.  The antialiased mode (Mip-Splatting's 2D filter, gsplat's
+ * rasterize_mode = "antialiased") keeps the footprint and scales the opacity by
+ *     rho = sqrt(det(Sigma2 - 0.3 I) / det Sigma2)
+ * so that opacity * rho * 2 pi sqrt(det Sigma2) = opacity * 2 pi sqrt(det(Sigma2 - 0.3 I)): what the undilated Gaussian holds.
+ * In binary32, from the projector's own a, b, c (csrc/ellipsoid.h states the order): a0 = |T0|^2 and c0 = |T1|^2
+ * (a and c before their 0.3), det0 = a0 c0 - b b, rho = det0 > 0 ? sqrt(det0 / det) : 0; one rounding per operator, no contraction.
+ * rho <= 1 always (no clamp is needed); rho = 0 for every splat whose record is all zeros (culled) and where det0 <= 0, which
+ * binary32 cancellation produces for needle splats whose true det0 is tiny against a0 c0 (gsplat's float32 has the same).
+ * The dilation stays 0.3 px^2.  The drawn opacity is fl32(opacity * rho); the record, the cut, the bounds, the keys and the
+ * blend are the classic mode's.
+ *
+ * splat_project_ellipsoid_aa: splat_project_ellipsoid's arguments, checks and outputs (projected, records, keys and payload
+ * byte for byte), then
+ *   rho_out            n floats, 4-byte aligned, or NULL: rho per splat;
+ *   color_opacity      (r, g, b, opacity) per splat, color_stride_vec4 float4s apart, 16-byte aligned, or NULL;
+ *   color_opacity_out  n x float4, 16-byte aligned, or NULL: (r, g, b, fl32(opacity * rho)).  It requires color_opacity
+ *                      (else SPLAT_ERR_INVALID).
+ * One kernel, one thread per splat. */
+int splat_project_ellipsoid_aa(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4,
+                               const void *scales, uint32_t scale_stride_vec4, const void *rotations, uint32_t rot_stride_vec4,
+                               uint32_t n, void *projected, void *records, void *keys, void *payload, uint32_t n_padded,
+                               void *rho_out, const void *color_opacity, uint32_t color_stride_vec4, void *color_opacity_out);
+/* splat_render_frame_ellipsoids' arguments, checks and outputs (the AOVs included), antialiased: image and AOVs are bit for bit
+ * those of splat_render_frame_ellipsoids given the plane (r, g, b, fl32(opacity * rho)).  That plane (16 bytes per splat) is
+ * written by one pass of the antialiased projector into a buffer the ctx owns, then the classic frame runs on it.  With stage
+ * timing on, a frame still records one SPLAT_STAGE_PROJECT interval (its projector's); the compensation pass is in no stage. */
+int splat_render_frame_ellipsoids_aa(splat_ctx *ctx, splat_sorter *sorter, splat_binner *binner,
+                                     const splat_composite_cfg *cfg, const float *uniforms, const void *positions,
+                                     const void *scales, const void *rotations, const void *color_opacity, uint32_t n,
+                                     uint32_t width, uint32_t height, void *projected, void *out_rgba8, void *out_rgba32f,
+                                     const splat_aov *aov);
+/* The sampling rate Mip-Splatting's 3D smoothing filter is sized by (its compute_3D_filter), one camera per call:
+ * with c = VP [p_i; 1] and the screen centre (sx, sy) formed as splat_project forms them (W = uniforms[20], H = uniforms[21]),
+ *     rate_inout[i] = fmaxf(rate_inout[i], focal_px / c.w)   if c.w > near, fl32(-margin W) <= sx <= fl32((1 + margin) W) and
+ *                                                             fl32(-margin H) <= sy <= fl32((1 + margin) H),
+ * and rate_inout[i] is left as it is otherwise (a NaN fails the comparisons).  All binary32, one rounding per operator.
+ * rate_inout: n floats, 4-byte aligned, read and written; positions: vec4 per splat, 16-byte aligned.  One thread per splat,
+ * no atomics.  Start from zeros, call once per training camera; the 3D filter's sigma is then sqrt(variance) / rate. */
+int splat_sampling_rate_max(splat_ctx *ctx, const float *uniforms, float focal_px, float near, float margin, const void *positions,
+                            uint32_t pos_stride_vec4, uint32_t n, void *rate_inout);
+
 /* ---- gradients of a frame of anisotropic 3D Gaussians (SPLAT_FOOTPRINT_ELLIPSOID; an extension) ------------------------
  * The backward of the staged ellipsoid frame: splat_project_ellipsoid -> sort -> splat_bin_run -> splat_composite_aov.  L is
  * the loss, G = (dL/drgb, dL/dalpha) per pixel.  Per pixel the forward takes its list in order with T_0 = 1, T_{i+1} =
@@ -585,6 +628,20 @@ int splat_project_ellipsoid_backward_camera(splat_ctx *ctx, const float *uniform
                                             const void *scales, uint32_t scale_stride_vec4, const void *rotations, uint32_t rot_stride_vec4,
                                             uint32_t n, const void *grad_records, void *grad_positions, void *grad_scales,
                                             void *grad_rotations, const void *grad_depth, void *grad_uniforms);
+/* The backward of splat_project_ellipsoid_aa: splat_project_ellipsoid_backward_camera's arguments, of which grad_depth AND
+ * grad_uniforms may be NULL here (NULL grad_uniforms: no camera sums run), then grad_rho: n floats, 4-byte aligned, dL/drho.
+ * The same float64-per-splat kernel; with rho^2 = det0 / det, A0 = A - 0.3, C0 = C - 0.3 the term
+ *     drho/dA = (C0 / det - rho^2 C / det) / (2 rho),  drho/dC = (A0 / det - rho^2 A / det) / (2 rho),
+ *     drho/dB = (-2 B / det)(1 - rho^2) / (2 rho)
+ * times grad_rho joins dL/d(A, B, C) and the existing chain carries it to position, scale, rotation and the camera sums (rho
+ * reads VP through J only).  Where the forward's binary32 rho is 0 (culled, or det0 <= 0) the term is exactly zero: rho is not
+ * differentiable there.  Where grad_rho[i] = 0 the per-splat outputs are bit for bit those of the entry point above with the
+ * same grad_depth / grad_uniforms choice; with all of grad_rho zero so is grad_uniforms.  The camera sums keep their fixed
+ * order: bit-reproducible from run to run. */
+int splat_project_ellipsoid_backward_aa(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4,
+                                        const void *scales, uint32_t scale_stride_vec4, const void *rotations, uint32_t rot_stride_vec4,
+                                        uint32_t n, const void *grad_records, void *grad_positions, void *grad_scales,
+                                        void *grad_rotations, const void *grad_depth, void *grad_uniforms, const void *grad_rho);
 /* splat_sh_colors_backward's arguments, checks and outputs (bit for bit), then grad_eye: a DEVICE pointer to 4 floats, 16-byte
  * aligned, OVERWRITTEN (for n = 0 too) with dL/deye in xyz and 0 in w: minus the float64 sum of the splats' grad_positions. */
 int splat_sh_colors_backward_camera(splat_ctx *ctx, const float *eye3, const void *positions, uint32_t pos_stride_vec4, const void *sh,

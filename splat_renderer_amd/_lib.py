@@ -96,6 +96,13 @@ SIGNATURES = {
     "splat_project": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _u32, _vp, _vp, _vp, _u32]),
     "splat_project_disc": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u32]),
     "splat_project_ellipsoid": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u32]),
+    "splat_project_ellipsoid_aa": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u32,
+                                        _vp, _vp, _u32, _vp]),
+    "splat_render_frame_ellipsoids_aa": (_i, [_vp, _vp, _vp, C.POINTER(CompositeCfg), C.POINTER(C.c_float), _vp, _vp, _vp, _vp, _u32,
+                                              _u32, _u32, _vp, _vp, _vp, C.POINTER(Aov)]),
+    "splat_sampling_rate_max": (_i, [_vp, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, _vp, _u32, _u32, _vp]),
+    "splat_project_ellipsoid_backward_aa": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp,
+                                                 _vp, _vp, _vp]),
     "splat_sh_colors": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _vp, _u32, _u32, _vp, _u32, _vp]),
     "splat_render_frame_ellipsoids": (_i, [_vp, _vp, _vp, C.POINTER(CompositeCfg), C.POINTER(C.c_float), _vp, _vp, _vp, _vp, _u32,
                                            _u32, _u32, _vp, _vp, _vp, C.POINTER(Aov)]),

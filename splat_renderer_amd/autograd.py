@@ -37,6 +37,20 @@ price: the workspace, a torch tensor allocated in backward() and freed after it,
 time of the stores and the second pass (DESIGN.md section 4 has the measurement).  The default, deterministic=False, is the
 atomic path, unchanged: no workspace, reproducible to rounding.
 
+Antialiased frames (include/splat.h, "antialiased frames"; Mip-Splatting's 2D filter, gsplat's rasterize_mode="antialiased"):
+
+    rec, rho, aux          = project_ellipsoids(uniforms, means, scales, rotations, antialiased=True)
+    rec, rho, depths, aux  = project_ellipsoids(..., return_depth=True, antialiased=True)
+    rgb, alpha             = rasterize(rec, compensate_opacity(col, rho), aux, width, height)
+    rgb, alpha             = render_gaussians(..., antialiased=True)
+
+rho (n,) = sqrt(det(Sigma2 - 0.3 I) / det Sigma2) in the projector's binary32 arithmetic, 0 for a culled splat and where the
+binary32 det(Sigma2 - 0.3 I) is not positive (needle splats: it cancels); it is differentiable (splat_project_ellipsoid_aa
+and splat_project_ellipsoid_backward_aa, one autograd Function; the term is zero where rho is 0), honours return_depth and a
+uniforms tensor that requires grad, and keeps the camera sums' fixed order.  render_gaussians multiplies the opacity column by
+it with a torch op; the composite, its backward, deterministic=True and photometric_loss are untouched.  antialiased=False,
+the default, is the code path described above, call for call.
+
 The camera is differentiable too.  `uniforms` may be a torch tensor (CUDA or CPU, float32 or float64, 22 floats, or 20 with
 width= and height=) that requires grad: it is then an input of the projection and, through its [16:19] slice, of sh_colors,
 and backward() fills its .grad — dL/dVP in [0:16] (row 2, entries 2, 6, 10, 14, is not read by this footprint: exact zeros),
@@ -308,6 +322,51 @@ def _functions():
                       cx.ctx)
             return None, gp, gs, gr, None, None
 
+    class ProjectAA(torch.autograd.Function):
+        """Project with the 2D Mip filter's factor beside the records: splat_project_ellipsoid_aa and its backward."""
+
+        @staticmethod
+        def forward(fctx, u, means4, scales4, rots, with_depth=False, u_t=None):
+            cx = _context(means4)
+            n = means4.shape[0]
+            padded = cx.ensure_sorter(n)
+            rec = torch.empty((n, 8), device=means4.device, dtype=torch.float32)
+            proj = torch.empty((n, 8), device=means4.device, dtype=torch.float32)
+            rho = torch.empty(n, device=means4.device, dtype=torch.float32)
+            keys = torch.empty(padded, device=means4.device, dtype=torch.int32)
+            pay = torch.empty(padded, device=means4.device, dtype=torch.int32)
+            if n:
+                check(cx.lib.splat_project_ellipsoid_aa(cx.ctx, _fptr(u), means4.data_ptr(), 1, scales4.data_ptr(), 1, rots.data_ptr(), 1, n,
+                                                        proj.data_ptr(), rec.data_ptr(), keys.data_ptr(), pay.data_ptr(), padded, rho.data_ptr(),
+                                                        None, 1, None), cx.ctx)
+            fctx.save_for_backward(means4, scales4, rots)
+            fctx.u, fctx.u_t, fctx.with_depth = u, u_t, bool(with_depth)
+            fctx.set_materialize_grads(False)  # (an unused rho or depth: None)
+            aux = ProjectedSplats(cx, u, n, proj, keys, pay)
+            if with_depth:
+                return rec, rho, proj[:, 4].contiguous(), aux
+            return rec, rho, aux
+
+        @staticmethod
+        def backward(fctx, grad_rec, grad_rho, *grads):
+            grad_depth = grads[0] if fctx.with_depth else None  # (rec, rho, depths, aux) or (rec, rho, aux)
+            means4, scales4, rots = fctx.saved_tensors
+            n = means4.shape[0]
+            cx = _context(means4)
+            dev = means4.device
+            g = _cuda_f32(grad_rec, "grad_records", 8) if grad_rec is not None else torch.zeros((n, 8), device=dev, dtype=torch.float32)
+            grho = _cuda_f32(grad_rho.reshape(-1), "grad_rho") if grad_rho is not None else torch.zeros(n, device=dev, dtype=torch.float32)
+            gz = _cuda_f32(grad_depth.reshape(-1), "grad_depths") if grad_depth is not None else None
+            gp, gs, gr = (torch.empty((n, 4), device=dev, dtype=torch.float32) for _ in range(3))
+            cam = len(fctx.needs_input_grad) > 5 and fctx.needs_input_grad[5]
+            gu = torch.empty(24, device=dev, dtype=torch.float32) if cam else None  # (22, and a 16-byte multiple)
+            if n or cam:
+                check(cx.lib.splat_project_ellipsoid_backward_aa(cx.ctx, _fptr(fctx.u), means4.data_ptr(), 1, scales4.data_ptr(), 1,
+                                                                 rots.data_ptr(), 1, n, g.data_ptr(), gp.data_ptr(), gs.data_ptr(), gr.data_ptr(),
+                                                                 gz.data_ptr() if gz is not None and n else None,
+                                                                 gu.data_ptr() if cam else None, grho.data_ptr()), cx.ctx)
+            return None, gp, gs, gr, None, (_like(gu, fctx.u_t) if cam else None)
+
     class ShColors(torch.autograd.Function):
         @staticmethod
         def forward(fctx, eye, means4, sh, degree, opacities, eye_t=None):
@@ -448,16 +507,18 @@ def _functions():
                                                    g.data_ptr(), 3), cx.ctx)
             return g, None, None, None, None, None
 
-    fns = (Project, ShColors, Rasterize, PhotometricLoss)
+    fns = (Project, ShColors, Rasterize, PhotometricLoss, ProjectAA)
     globals()["_fns"] = fns
     return fns
 
 
-def project_ellipsoids(uniforms, means, scales, rotations, width=None, height=None, return_depth=False):
+def project_ellipsoids(uniforms, means, scales, rotations, width=None, height=None, return_depth=False, antialiased=False):
     """(rec (n, 8) differentiable records {c.x, c.y, B00, B01, 0, B11, 0, 0}, aux: ProjectedSplats).  uniforms: a Camera (then
     width and height are required) or the 22-float block.  return_depth=True: (rec, depths, aux), depths (n,) the
     differentiable ProjectedSplat depth |mean - eye| (aux.projected[:, 4] bit for bit; rasterize's `depths`).  A uniforms
-    tensor that requires grad receives its gradient (the module's docstring)."""
+    tensor that requires grad receives its gradient (the module's docstring).  antialiased=True: (rec, rho, aux) or (rec, rho,
+    depths, aux), rho (n,) the differentiable 2D Mip filter factor (splat_project_ellipsoid_aa; rec, depths and aux are the
+    same bits either way)."""
     u = _uniforms(uniforms, width, height)
     u_t = _grad_uniforms(uniforms)
     means4 = _cuda_f32(_vec4(means, "means", 1.0), "means", 4)
@@ -465,6 +526,10 @@ def project_ellipsoids(uniforms, means, scales, rotations, width=None, height=No
     rots = _cuda_f32(rotations, "rotations", 4)
     if not (means4.shape[0] == scales4.shape[0] == rots.shape[0]):
         raise SplatError(-1, "means, scales and rotations must hold the same number of splats")
+    if antialiased:
+        if u_t is not None:
+            return _functions()[4].apply(u, means4, scales4, rots, bool(return_depth), u_t)
+        return _functions()[4].apply(u, means4, scales4, rots, bool(return_depth))
     if u_t is not None:
         return _functions()[0].apply(u, means4, scales4, rots, bool(return_depth), u_t)
     return _functions()[0].apply(u, means4, scales4, rots, bool(return_depth))
@@ -514,11 +579,12 @@ def rasterize(rec, col, aux, width=None, height=None, depths=None, deterministic
 
 
 def render_gaussians(camera_or_uniforms, means, scales, rotations, opacities, colors=None, sh=None, width=None, height=None, degree=None,
-                     return_depth=False, deterministic=False):
+                     return_depth=False, deterministic=False, antialiased=False):
     """The whole differentiable frame: project_ellipsoids, the colour (sh_colors when `sh` is given, else cat(colors,
     opacities)), rasterize.  Returns (rgb (H, W, 3), alpha (H, W)); return_depth=True: (rgb, alpha, depth (H, W)), the depth
     map of the ProjectedSplat depths (the distance from the eye to each centre).  deterministic=True: every gradient is the
-    same bits on every run (rasterize's fixed-order backward; the module's docstring)."""
+    same bits on every run (rasterize's fixed-order backward; the module's docstring).  antialiased=True: the opacity column is
+    multiplied by project_ellipsoids' rho (a torch op) before rasterize: the 2D Mip filter."""
     if width is None or height is None:
         raise SplatError(-1, "render_gaussians needs width and height")
     for name, t in (("means", means), ("scales", scales), ("rotations", rotations), ("opacities", opacities)):
@@ -526,7 +592,13 @@ def render_gaussians(camera_or_uniforms, means, scales, rotations, opacities, co
     u = _uniforms(camera_or_uniforms, width, height)
     u_t = _grad_uniforms(camera_or_uniforms)
     pu = (camera_or_uniforms, means, scales, rotations, width, height) if u_t is not None else (u, means, scales, rotations)
-    if return_depth:
+    rho = None
+    if antialiased and return_depth:
+        rec, rho, depths, aux = project_ellipsoids(*pu, return_depth=True, antialiased=True)
+    elif antialiased:
+        rec, rho, aux = project_ellipsoids(*pu, antialiased=True)
+        depths = None
+    elif return_depth:
         rec, depths, aux = project_ellipsoids(*pu, return_depth=True)
     else:
         rec, aux = project_ellipsoids(*pu)
@@ -543,7 +615,15 @@ def render_gaussians(camera_or_uniforms, means, scales, rotations, opacities, co
         col = _t().cat([colors, opacities.reshape(-1, 1)], dim=1)
     else:
         raise SplatError(-1, "render_gaussians needs colors or sh")
+    if rho is not None:
+        col = compensate_opacity(col, rho)
     return rasterize(rec, col, aux, width, height, depths=depths, deterministic=deterministic)
+
+
+def compensate_opacity(col, rho):
+    """(n, 4) (r, g, b, opacity * rho): the antialiased mode's colour plane, in torch ops (one binary32 product per splat, as
+    splat_project_ellipsoid_aa's color_opacity_out)."""
+    return _t().cat([col[:, :3], col[:, 3:] * rho.reshape(-1, 1)], dim=1)
 
 
 def _image(t, name, channels):

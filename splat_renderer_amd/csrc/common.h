@@ -70,6 +70,9 @@ struct splat_ctx {
     // pinned host staging for uploads / tiny readbacks
     void *pinned = nullptr;
     size_t pinned_bytes = 0;
+    // the antialiased ellipsoid frame's compensated colour plane (splat_render_frame_ellipsoids_aa): n x float4
+    void *aa_color = nullptr;
+    uint32_t aa_color_cap = 0; // splats allocated
 };
 
 int ctx_fail(splat_ctx *ctx, int code, const char *what, hipError_t e = hipSuccess);
@@ -332,4 +335,8 @@ int project_launch(splat_ctx *ctx, const float *uniforms, const void *pos_radius
                    const struct LitIO *lit = nullptr,                      // lit->records != NULL: also write lit composite records (shade.h)
                    uint2 *range_wide = nullptr, // instead of range32 (screens beyond 256 x 256 tiles): the 8-byte range, sort-first
                    const struct EllIO *ell = nullptr); // with discs: the anisotropic Gaussian (ellipsoid.h) instead of the disc
+// project.hip internal: the antialiased ellipsoid projector (every output optional; rho_out n floats, color_opacity_out n x float4)
+int project_ellipsoid_aa_launch(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4, const struct EllIO &ell,
+                                uint32_t n, void *projected, void *records, void *keys, void *payload, uint32_t n_padded, float *rho_out,
+                                const void *color_opacity, uint32_t color_stride_vec4, void *color_opacity_out, bool timed);
 int binner_reserve_range_wide(splat_binner *b, uint32_t n_splats); // the range32 buffer, grown to 8 bytes per splat; its uint2s

@@ -144,6 +144,7 @@ void splat_ctx_destroy(splat_ctx *ctx) {
     for (auto &h : ctx->px_hist)
         if (h.mem) (void)hipFree(h.mem);
     if (ctx->scan_ws) (void)hipFree(ctx->scan_ws);
+    if (ctx->aa_color) (void)hipFree(ctx->aa_color);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;

@@ -22,6 +22,15 @@
 //   B            U / 3 (three IEEE divides); culled when anything is not finite
 // Sums of three are ((t0 + t1) + t2).  q and -q give the same bits (every product of two components keeps them), and so
 // does 2q (scaling by a power of two is exact throughout the normalisation).
+//
+// <RHO = true> (the antialiased mode: splat_project_ellipsoid_aa and its backward) also hands out the 2D Mip filter's
+// compensation factor, from the values above and in the same arithmetic:
+//   a0 = |T0|^2, c0 = |T1|^2 (so a = a0 + 0.3, c = c0 + 0.3: the sums the record itself forms),  det0 = a0 c0 - b b
+//   rho = det0 > 0 ? sqrt(det0 / det) : 0;  0 for every splat whose record is all zeros
+// rho^2 = det(Sigma2 - 0.3 I) / det Sigma2: the dilated Gaussian drawn at opacity * rho deposits what the undilated one would.
+// a >= a0 and c >= c0 in binary32 (adding 0.3 rounds monotonically) and the b b is the same number, so det >= det0 and
+// rho <= 1 with no clamp.  det0 cancels on needle splats (a0 c0 and b b agree in their leading digits): rho is then 0 or
+// carries few correct digits; the record does not read it.  Without RHO the function is the one it was.
 #pragma once
 #include "disc.h"
 
@@ -33,8 +42,10 @@ struct EllIO {
     uint32_t rot_stride;
 };
 
-__device__ __forceinline__ DiscRecord ellipsoid_record(const float *m, float w, float h, float4 p, float4 s, float4 q) {
+template <bool RHO = false>
+__device__ __forceinline__ DiscRecord ellipsoid_record(const float *m, float w, float h, float4 p, float4 s, float4 q, float *rho = nullptr) {
 #pragma clang fp contract(off)
+    if (RHO) *rho = 0.0f;
     DiscRecord zero = {make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0)};
     const float n2 = ((q.x * q.x + q.y * q.y) + q.z * q.z) + q.w * q.w;
     const float k = 1.0f / sqrtf(n2);
@@ -71,5 +82,10 @@ __device__ __forceinline__ DiscRecord ellipsoid_record(const float *m, float w, 
     o.a = make_float4(scx, scy, b00, b01);
     o.b = make_float4(0.0f, b11, 0.0f, 0.0f);
     if (!disc_finite4(scx, scy, b00, b01) || !disc_finite4(b11, det, 0.0f, 0.0f)) return zero;
+    if (RHO) { // (a0, c0: the sums a and c were formed from, the same bits)
+        const float a0 = (t00 * t00 + t01 * t01) + t02 * t02, c0 = (t10 * t10 + t11 * t11) + t12 * t12;
+        const float det0 = a0 * c0 - b * b;
+        *rho = det0 > 0.0f ? sqrtf(det0 / det) : 0.0f;
+    }
     return o;
 }

@@ -894,4 +894,34 @@ int splat_render_frame_ellipsoids(splat_ctx *ctx, splat_sorter *sorter, splat_bi
                              out_rgba8, out_rgba32f, aov, &ell);
 }
 
+// The antialiased frame: one pass of the antialiased projector writes (r, g, b, fl32(opacity rho)) into a plane the context
+// owns, then the frame above runs on that plane: its kernels, and so its bits, are splat_render_frame_ellipsoids' own.
+int splat_render_frame_ellipsoids_aa(splat_ctx *ctx, splat_sorter *sorter, splat_binner *binner, const splat_composite_cfg *cfg,
+                                     const float *uniforms, const void *positions, const void *scales, const void *rotations,
+                                     const void *color_opacity, uint32_t n, uint32_t width, uint32_t height, void *projected, void *out_rgba8,
+                                     void *out_rgba32f, const splat_aov *aov) {
+    if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
+    if (n == 0) // (nothing to compensate: the frame's own checks and its empty image)
+        return splat_render_frame_ellipsoids(ctx, sorter, binner, cfg, uniforms, positions, scales, rotations, color_opacity, n, width, height,
+                                             projected, out_rgba8, out_rgba32f, aov);
+    // (what the compensation pass reads, checked before it runs; everything else is the frame's to check)
+    ARG_CHECK(ctx, cfg && cfg->footprint == SPLAT_FOOTPRINT_ELLIPSOID);
+    ARG_CHECK(ctx, uniforms && positions && color_opacity && scales && rotations);
+    ARG_CHECK(ctx, (((uintptr_t)positions | (uintptr_t)scales | (uintptr_t)rotations | (uintptr_t)color_opacity) & 15) == 0);
+    if (n > ctx->aa_color_cap) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->aa_color) (void)hipFree(ctx->aa_color);
+        ctx->aa_color = nullptr;
+        ctx->aa_color_cap = 0;
+        if (hipMalloc(&ctx->aa_color, (size_t)n * 16) != hipSuccess) return ctx_fail(ctx, SPLAT_ERR_OOM, "antialiased colour plane hipMalloc");
+        ctx->aa_color_cap = n;
+    }
+    const EllIO ell = {(const float4 *)scales, 1u, (const float4 *)rotations, 1u};
+    const int rc = project_ellipsoid_aa_launch(ctx, uniforms, positions, 1, ell, n, nullptr, nullptr, nullptr, nullptr, 0, nullptr, color_opacity,
+                                               1, ctx->aa_color, false); // (untimed: the frame's projector is the PROJECT stage's one interval)
+    if (rc != SPLAT_OK) return rc;
+    return splat_render_frame_ellipsoids(ctx, sorter, binner, cfg, uniforms, positions, scales, rotations, ctx->aa_color, n, width, height,
+                                         projected, out_rgba8, out_rgba32f, aov);
+}
+
 } // extern "C"

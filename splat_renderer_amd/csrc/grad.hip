@@ -557,14 +557,23 @@ struct GradUniformsCam : GradUniforms {
     double *part;
 };
 
+// the antialiased variant's further argument (splat_project_ellipsoid_backward_aa): dL/drho, n floats
+struct GradUniformsAa : GradUniformsCam {
+    const float *grho;
+};
+
 // (DEPTH: gdep[i] = dL/dz_i of the ProjectedSplat depth z = |p - eye|; not read otherwise)
 // <CAM = true> (splat_project_ellipsoid_backward_camera): the same per-splat work, and each splat's own dL/d(VP, eye), still in
 // float64, summed over each wave into U.part[4 blockIdx.x + wave] (12 numbers, 15 with DEPTH; a culled splat adds zeros).  One
 // splat per thread there too: a loop over several splats per thread would shrink the partials, but the compiler then keeps
 // the loop's invariants (VP in float64 among them) in registers across it: 208 / 216 VGPRs and two waves per SIMD, where one
 // splat per thread holds the three of the kernel without the sums (the launch bound asks for them: 165 / 166 VGPRs).
-template <bool DEPTH, bool CAM = false>
-__global__ __launch_bounds__(256, CAM ? 3 : 1) void k_project_ellipsoid_backward(std::conditional_t<CAM, GradUniformsCam, GradUniforms> U,
+// <AA = true> (splat_project_ellipsoid_backward_aa): the record's gradient and that of the 2D Mip filter's factor rho
+// (ellipsoid.h: <RHO>), whose term joins dL/d(A, B, C) before gT is formed; the chain from there, the camera's numbers
+// included, is the one below (rho reads VP through J only).  Zero where the forward's binary32 rho is 0.
+template <bool DEPTH, bool CAM = false, bool AA = false>
+__global__ __launch_bounds__(256, CAM ? 3 : 1) void k_project_ellipsoid_backward(
+                                                                    std::conditional_t<AA, GradUniformsAa, std::conditional_t<CAM, GradUniformsCam, GradUniforms>> U,
                                                                     const float4 *__restrict__ pos, uint32_t ps,
                                                                     const float4 *__restrict__ scl, uint32_t ss, const float4 *__restrict__ rot,
                                                                     uint32_t rs, uint32_t n, const float4 *__restrict__ grec,
@@ -583,7 +592,10 @@ __global__ __launch_bounds__(256, CAM ? 3 : 1) void k_project_ellipsoid_backward
             else return;
         }
         const float4 pf = pos[(size_t)i * ps], sf = scl[(size_t)i * ss], qf = rot[(size_t)i * rs];
-        const DiscRecord r = ellipsoid_record(U.m, U.w, U.h, pf, sf, qf);
+        float rho32 = 0.0f; // (AA) the forward's own rho
+        DiscRecord r;
+        if constexpr (AA) r = ellipsoid_record<true>(U.m, U.w, U.h, pf, sf, qf, &rho32);
+        else r = ellipsoid_record(U.m, U.w, U.h, pf, sf, qf);
         const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (r.b.y == 0.0f) { // culled (B11 = 1 / (3 sqrt(c)) > 0 in every record that is not)
             gpos[i] = zero; gscl[i] = zero; grot[i] = zero;
@@ -627,9 +639,25 @@ __global__ __launch_bounds__(256, CAM ? 3 : 1) void k_project_ellipsoid_backward
         // backward: B -> (a, b, c)
         const double gB00 = g0.z, gB01 = g0.w, gB11 = g1.y, gsx = g0.x, gsy = g0.y;
         const double gdet = -(gB00 * b00 + gB01 * b01) / (2.0 * det);
-        const double gC = (gB00 * b00 - gB01 * b01 - gB11 * b11) / (2.0 * C) + gdet * A;
-        const double gA = gdet * C;
-        const double gB = gB01 * (-1.0 / (3.0 * sqrt(C * det))) - 2.0 * Bc * gdet;
+        double gC = (gB00 * b00 - gB01 * b01 - gB11 * b11) / (2.0 * C) + gdet * A;
+        double gA = gdet * C;
+        double gB = gB01 * (-1.0 / (3.0 * sqrt(C * det))) - 2.0 * Bc * gdet;
+        if constexpr (AA) {
+            // rho^2 = det0 / det, det0 = A0 C0 - B^2, A0 = |T0|^2, C0 = |T1|^2 (A = A0 + 0.3, C = C0 + 0.3):  d(rho^2) = d(det0) / det - rho^2 d(det) / det.
+            // (grho = 0 leaves gA, gB, gC as they are, bit for bit; so does a splat whose binary32 rho is 0: not differentiable
+            // there.  det0 <= 0 in float64 beside a binary32 rho > 0 is the needle splats' cancellation: no term either.)
+            // (A0, C0: the undilated sums A and C were formed from, not A - 0.3: a strongly minified splat's |T0|^2 would lose
+            // its low bits under the 0.3)
+            const double gr = U.grho[i];
+            const double A0 = T[0][0] * T[0][0] + T[0][1] * T[0][1] + T[0][2] * T[0][2];
+            const double C0 = T[1][0] * T[1][0] + T[1][1] * T[1][1] + T[1][2] * T[1][2];
+            const double rho2 = (A0 * C0 - Bc * Bc) / det;
+            const bool on = gr != 0.0 && rho32 > 0.0f && rho2 > 0.0;
+            const double h = gr / (2.0 * sqrt(rho2));
+            gA = on ? gA + h * (C0 / det - rho2 * C / det) : gA;
+            gC = on ? gC + h * (A0 / det - rho2 * A / det) : gC;
+            gB = on ? gB + h * ((-2.0 * Bc / det) * (1.0 - rho2)) : gB;
+        }
         double gT[2][3];
         for (int k = 0; k < 3; ++k) {
             gT[0][k] = 2.0 * gA * T[0][k] + gB * T[1][k];
@@ -962,16 +990,18 @@ static void camera_sum_launch(splat_ctx *ctx, const double *part, uint32_t npart
 static int project_ellipsoid_backward(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4,
                                       const void *scales, uint32_t scale_stride_vec4, const void *rotations, uint32_t rot_stride_vec4, uint32_t n,
                                       const void *grad_records, void *grad_positions, void *grad_scales, void *grad_rotations,
-                                      const void *grad_depth, bool need_depth, void *grad_uniforms, bool cam, const char *what) {
+                                      const void *grad_depth, bool need_depth, void *grad_uniforms, bool cam, const char *what,
+                                      const void *grad_rho = nullptr, bool aa = false) {
     if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
     ARG_CHECK(ctx, uniforms && (!cam || grad_uniforms) &&
                        (n == 0 || (positions && scales && rotations && grad_records && grad_positions && grad_scales && grad_rotations &&
-                                   (!need_depth || grad_depth))));
+                                   (!need_depth || grad_depth) && (!aa || grad_rho))));
     ARG_CHECK(ctx, pos_stride_vec4 >= 1 && scale_stride_vec4 >= 1 && rot_stride_vec4 >= 1);
     ARG_CHECK(ctx, (((uintptr_t)positions | (uintptr_t)scales | (uintptr_t)rotations | (uintptr_t)grad_records | (uintptr_t)grad_positions |
                      (uintptr_t)grad_scales | (uintptr_t)grad_rotations | (uintptr_t)grad_uniforms) & 15) == 0 &&
-                       ((uintptr_t)grad_depth & 3) == 0);
-    GradUniformsCam u;
+                       (((uintptr_t)grad_depth | (uintptr_t)grad_rho) & 3) == 0);
+    GradUniformsAa u;
+    u.grho = (const float *)grad_rho;
     uint32_t nparts = 0;
     u.part = nullptr;
     if (cam) {
@@ -980,15 +1010,15 @@ static int project_ellipsoid_backward(splat_ctx *ctx, const float *uniforms, con
     }
     if (n) {
         for (int k = 0; k < 22; ++k) (&u.m[0])[k] = uniforms[k];
-        // (<DEPTH, CAM>: the kernel without CAM takes the GradUniforms part of u)
+        // (<DEPTH, CAM, AA>: the kernel without AA takes the GradUniformsCam part of u, the one without CAM its GradUniforms part)
         variant_dispatch(
-            [&](auto depth, auto cam_) {
-                launch_kernel(ctx, NO_STAGE, k_project_ellipsoid_backward<depth.value, cam_.value>, dim3(div_up(n, 256)), dim3(256), u,
+            [&](auto depth, auto cam_, auto aa_) {
+                launch_kernel(ctx, NO_STAGE, k_project_ellipsoid_backward<depth.value, cam_.value, aa_.value>, dim3(div_up(n, 256)), dim3(256), u,
                               (const float4 *)positions, pos_stride_vec4, (const float4 *)scales, scale_stride_vec4, (const float4 *)rotations,
                               rot_stride_vec4, n, (const float4 *)grad_records, (float4 *)grad_positions, (float4 *)grad_scales,
                               (float4 *)grad_rotations, (const float *)grad_depth);
             },
-            grad_depth != nullptr, cam);
+            grad_depth != nullptr, cam, aa);
         const int rc = launch_check(ctx, what);
         if (rc != SPLAT_OK) return rc;
     }
@@ -1024,6 +1054,15 @@ extern "C" int splat_project_ellipsoid_backward_camera(splat_ctx *ctx, const flo
     return project_ellipsoid_backward(ctx, uniforms, positions, pos_stride_vec4, scales, scale_stride_vec4, rotations, rot_stride_vec4, n,
                                       grad_records, grad_positions, grad_scales, grad_rotations, grad_depth, false, grad_uniforms, true,
                                       "launch k_project_ellipsoid_backward<CAM>");
+}
+
+extern "C" int splat_project_ellipsoid_backward_aa(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4,
+                                                   const void *scales, uint32_t scale_stride_vec4, const void *rotations, uint32_t rot_stride_vec4,
+                                                   uint32_t n, const void *grad_records, void *grad_positions, void *grad_scales,
+                                                   void *grad_rotations, const void *grad_depth, void *grad_uniforms, const void *grad_rho) {
+    return project_ellipsoid_backward(ctx, uniforms, positions, pos_stride_vec4, scales, scale_stride_vec4, rotations, rot_stride_vec4, n,
+                                      grad_records, grad_positions, grad_scales, grad_rotations, grad_depth, false, grad_uniforms,
+                                      grad_uniforms != nullptr, "launch k_project_ellipsoid_backward<AA>", grad_rho, true);
 }
 
 // The two SH backwards.  cam: also dL/deye into grad_eye, summed from per-wave partials.

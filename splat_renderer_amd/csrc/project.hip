@@ -495,6 +495,70 @@ __global__ __launch_bounds__(PBC_THREADS) void k_project_hist_bandc(FrameUniform
     }
 }
 
+// The antialiased ellipsoid projector (splat_project_ellipsoid_aa): k_project<WITH_KEYS, false, true, false, true>'s outputs, from
+// the same functions in the same order, and beside them the 2D Mip filter's factor rho (ellipsoid.h: <RHO>) and the colour
+// plane with its opacity compensated, fl32(opacity * rho).  Every output is optional here (the whole antialiased frame asks for
+// the colour plane alone); one thread per splat.
+struct AaIO {
+    float *rho;              // n floats, or NULL
+    const float4 *color;     // (r, g, b, opacity), color_stride float4s apart; read only with color_out
+    uint32_t color_stride;
+    float4 *color_out;       // n x float4 (r, g, b, fl32(opacity * rho)), or NULL
+};
+__global__ __launch_bounds__(256) void k_project_ellipsoid_aa(FrameUniforms u, const float4 *__restrict__ pos, uint32_t stride_vec4, uint32_t n,
+                                                              uint32_t n_padded, float4 *__restrict__ projected, float4 *__restrict__ records,
+                                                              uint32_t *__restrict__ keys, uint32_t *__restrict__ payload, EllIO ell, AaIO aa) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) {
+        if (keys && i < n_padded) { // extract-depth-keys.wgsl:46-50
+            keys[i] = 0xffffffffu;
+            payload[i] = 0xffffffffu;
+        }
+        return;
+    }
+    const float4 pr = pos[(size_t)i * stride_vec4];
+    const float4 scl = ell.scales[(size_t)i * ell.scale_stride], rot = ell.rotations[(size_t)i * ell.rot_stride];
+    float4 col = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (aa.color_out) col = aa.color[(size_t)i * aa.color_stride];
+    float rho;
+    const DiscRecord d = ellipsoid_record<true>(u.m, u.w, u.h, pr, scl, rot, &rho);
+    if (records) {
+        records[(size_t)i * 2] = d.a;
+        records[(size_t)i * 2 + 1] = d.b;
+    }
+    if (projected || keys) { // project_one's DISC branch
+        const float dx = pr.x - u.eye[0], dy = pr.y - u.eye[1], dz = pr.z - u.eye[2];
+        const float depth = sqrtf((dx * dx + dy * dy) + dz * dz); // SplatProjector.ts:77
+        if (projected) {
+            float4 a;
+            disc_bounds(d, a);
+            projected[(size_t)i * 2] = a;
+            projected[(size_t)i * 2 + 1] = make_float4(depth, 0.5f * fmaxf(a.z - a.x, a.w - a.y), __uint_as_float(i), 0.0f);
+        }
+        if (keys) {
+            keys[i] = depth_key(depth);
+            payload[i] = i;
+        }
+    }
+    if (aa.rho) aa.rho[i] = rho;
+    if (aa.color_out) aa.color_out[i] = make_float4(col.x, col.y, col.z, col.w * rho);
+}
+
+// splat_sampling_rate_max: one thread per splat, no atomics.  c = VP [p; 1] and the screen centre exactly as to_screen();
+// a splat in front of `near` and inside the screen widened by `margin` of its size on every side raises its rate to
+// focal_px / c.w (Mip-Splatting's compute_3D_filter, one camera per call).  A NaN anywhere fails a comparison: unchanged.
+__global__ __launch_bounds__(256) void k_sampling_rate_max(FrameUniforms u, float focal_px, float near, float margin, const float4 *__restrict__ pos,
+                                                           uint32_t stride_vec4, uint32_t n, float *__restrict__ rate) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float4 p = pos[(size_t)i * stride_vec4];
+    const float cw = ((u.m[3] * p.x + u.m[7] * p.y) + u.m[11] * p.z) + u.m[15]; // to_screen()'s own c.w
+    float scx, scy;
+    to_screen(u, p.x, p.y, p.z, scx, scy);
+    const float lo_x = (-margin) * u.w, hi_x = (1.0f + margin) * u.w, lo_y = (-margin) * u.h, hi_y = (1.0f + margin) * u.h;
+    if (cw > near && scx >= lo_x && scx <= hi_x && scy >= lo_y && scy <= hi_y) rate[i] = fmaxf(rate[i], focal_px / cw);
+}
+
 __global__ __launch_bounds__(256) void k_extract_keys(const float4 *__restrict__ projected, uint32_t n, uint32_t n_padded,
                                                       uint32_t *__restrict__ keys, uint32_t *__restrict__ payload) {
     uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -645,6 +709,26 @@ int project_launch(splat_ctx *ctx, const float *uniforms, const void *pos_radius
     return SPLAT_OK;
 }
 
+// The antialiased projector's launch, for splat_project_ellipsoid_aa and for the antialiased frame (frame.hip), which asks
+// for the compensated colour plane only.  timed: the launch is a SPLAT_STAGE_PROJECT interval of its own (the staged entry point);
+// the frame passes false, so that a timed antialiased frame still records one PROJECT interval, its projector's: the
+// compensation pass runs before it and outside every stage.
+int project_ellipsoid_aa_launch(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4, const EllIO &ell,
+                                uint32_t n, void *projected, void *records, void *keys, void *payload, uint32_t n_padded, float *rho_out,
+                                const void *color_opacity, uint32_t color_stride_vec4, void *color_opacity_out, bool timed) {
+    const uint32_t work = keys ? n_padded : n;
+    if (work == 0) return SPLAT_OK;
+    FrameUniforms u;
+    load_uniforms(u, uniforms);
+    const AaIO aa = {rho_out, (const float4 *)color_opacity, color_stride_vec4, (float4 *)color_opacity_out};
+    if (timed) stage_begin(ctx, SPLAT_STAGE_PROJECT);
+    hipLaunchKernelGGL(k_project_ellipsoid_aa, dim3(div_up(work, 256)), dim3(256), 0, ctx->stream, u, (const float4 *)positions, pos_stride_vec4, n,
+                       keys ? n_padded : n, (float4 *)projected, (float4 *)records, (uint32_t *)keys, (uint32_t *)payload, ell, aa);
+    LAUNCH_CHECK(ctx, "k_project_ellipsoid_aa");
+    if (timed) stage_end(ctx, SPLAT_STAGE_PROJECT);
+    return SPLAT_OK;
+}
+
 extern "C" {
 
 int splat_project(splat_ctx *ctx, const float *uniforms, const void *pos_radius, uint32_t pr_stride_vec4, uint32_t n,
@@ -684,6 +768,37 @@ int splat_project_ellipsoid(splat_ctx *ctx, const float *uniforms, const void *p
     const EllIO ell = {(const float4 *)scales, scale_stride_vec4, (const float4 *)rotations, rot_stride_vec4};
     return project_launch(ctx, uniforms, positions, pos_stride_vec4, n, 0, projected, keys, payload, n_padded, nullptr, nullptr, nullptr,
                           nullptr, 1, n ? records : nullptr, nullptr, nullptr, &ell);
+}
+
+int splat_project_ellipsoid_aa(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4, const void *scales,
+                               uint32_t scale_stride_vec4, const void *rotations, uint32_t rot_stride_vec4, uint32_t n, void *projected,
+                               void *records, void *keys, void *payload, uint32_t n_padded, void *rho_out, const void *color_opacity,
+                               uint32_t color_stride_vec4, void *color_opacity_out) {
+    if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
+    ARG_CHECK(ctx, uniforms && (n == 0 || (positions && scales && rotations && projected && records)));
+    ARG_CHECK(ctx, pos_stride_vec4 >= 1 && scale_stride_vec4 >= 1 && rot_stride_vec4 >= 1);
+    ARG_CHECK(ctx, (keys == nullptr) == (payload == nullptr));
+    ARG_CHECK(ctx, keys == nullptr || n_padded >= n);
+    ARG_CHECK(ctx, color_opacity_out == nullptr || (color_opacity && color_stride_vec4 >= 1));
+    ARG_CHECK(ctx, (((uintptr_t)positions | (uintptr_t)scales | (uintptr_t)rotations | (uintptr_t)projected | (uintptr_t)records |
+                     (uintptr_t)color_opacity | (uintptr_t)color_opacity_out) & 15) == 0 && ((uintptr_t)rho_out & 3) == 0);
+    const EllIO ell = {(const float4 *)scales, scale_stride_vec4, (const float4 *)rotations, rot_stride_vec4};
+    return project_ellipsoid_aa_launch(ctx, uniforms, positions, pos_stride_vec4, ell, n, projected, records, keys, payload, n_padded,
+                                       (float *)rho_out, color_opacity, color_stride_vec4, color_opacity_out, true);
+}
+
+int splat_sampling_rate_max(splat_ctx *ctx, const float *uniforms, float focal_px, float near, float margin, const void *positions,
+                            uint32_t pos_stride_vec4, uint32_t n, void *rate_inout) {
+    if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
+    ARG_CHECK(ctx, uniforms && (n == 0 || (positions && rate_inout)) && pos_stride_vec4 >= 1);
+    ARG_CHECK(ctx, ((uintptr_t)positions & 15) == 0 && ((uintptr_t)rate_inout & 3) == 0);
+    if (n == 0) return SPLAT_OK;
+    FrameUniforms u;
+    load_uniforms(u, uniforms);
+    hipLaunchKernelGGL(k_sampling_rate_max, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, u, focal_px, near, margin, (const float4 *)positions,
+                       pos_stride_vec4, n, (float *)rate_inout);
+    LAUNCH_CHECK(ctx, "k_sampling_rate_max");
+    return SPLAT_OK;
 }
 
 int splat_project_slice(splat_ctx *ctx, const float *uniforms, const void *pos_radius, uint32_t pr_stride_vec4, uint32_t first,

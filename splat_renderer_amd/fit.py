@@ -52,6 +52,24 @@ not at all, except the composite's backward, whose float atomics arrive in a var
 autograd.rasterize's deterministic=True (splat_composite_backward_det).  It costs a workspace per backward of 16 bytes per
 tile + 4 per splat + 36 per (tile, splat) pair of the frame's lists (40 with a depth gradient), and the time of a second pass
 over it.  The default is the atomic path: two runs then drift apart after the first step.
+
+Antialiasing (Mip-Splatting's two filters; both off by default, and a fit that uses neither computes the bytes it always did):
+
+    fit = GaussianFit(..., antialiased=True)                            # the 2D Mip filter: render() draws opacity x rho
+    fit.update_filter_3d(train_cameras, width, height)                  # the 3D smoothing filter, from the training cameras
+    ...
+    fit.densify_and_prune(...); fit.update_filter_3d(train_cameras, width, height)
+
+antialiased=True makes render() call autograd.project_ellipsoids(antialiased=True) and multiply the opacity by its rho
+(include/splat.h, "antialiased frames").  update_filter_3d() gives every splat the largest sampling rate focal / depth any of the
+cameras sees it at (splat_sampling_rate_max, one launch per camera) and from it the filter's sigma f = sqrt(variance) / rate;
+render() then draws s_eff = sqrt(s^2 + f^2) per axis and o_eff = o sqrt(prod s^2 / prod s_eff^2), in torch ops, so the
+gradients reach log_scales and opacity_logits through them.  A splat no camera saw gets f = 0, no smoothing (Mip-Splatting
+gives such splats the largest filter of the seen ones; a splat outside every training view is not constrained by any of them
+either way, and 0 leaves it as the optimiser has it).  The filter belongs to the rows it was computed for:
+densify_and_prune(), relocate() and add_new() clear it, and the caller computes it again after them, as Mip-Splatting does
+after every densification.  save_ply() writes the fused values (log s_eff, logit o_eff), so that any viewer draws the cloud
+the fit drew; without a filter it writes the raw parameters bit for bit, as before.
 """
 import ctypes as C
 import math
@@ -68,14 +86,15 @@ PLANES = ("means", "log_scales", "rotations", "opacity_logits", "sh")
 
 class GaussianFit:
     def __init__(self, means, scales, rotations, opacity, sh, degree=None, lr=None, betas=(0.9, 0.999), eps=1e-15, sparse=True,
-                 device="cuda", exact_activations=False, deterministic=False):
+                 device="cuda", exact_activations=False, deterministic=False, antialiased=False):
         """means (n, 3), scales (n, 3) > 0, rotations (n, 4), opacity (n,) in (0, 1), sh (n, K, 3) or (n, 3 K), K = (degree +
         1)^2: arrays or tensors of activated values.  lr: a dict that overrides entries of DEFAULT_LR.  exact_activations:
         render() forms exp and sigmoid in float64 and rounds once, as load_gaussian_ply does, so the frame the fit renders is the
         frame its saved PLY renders; with the default float32 activations the two differ by an ulp in some scales and opacities,
         which now and then carries one pixel across a splat's 3-sigma cut (a step of up to 0.011 x opacity in that pixel).
         deterministic: render() asks autograd.rasterize for its fixed-order backward, so that the whole fit is bit-reproducible
-        (the module's docstring)."""
+        (the module's docstring).  antialiased: render() draws every opacity times the 2D Mip filter's rho (the module's
+        docstring)."""
         torch = AG._t()
         t = lambda a: torch.as_tensor(a, dtype=torch.float32).to(device).detach()  # noqa: E731
         means, scales, rotations, opacity, sh = t(means), t(scales), t(rotations), t(opacity).reshape(-1), t(sh)
@@ -91,6 +110,8 @@ class GaussianFit:
         self.betas, self.eps, self.sparse = (float(betas[0]), float(betas[1])), float(eps), bool(sparse)
         self.exact_activations = bool(exact_activations)
         self.deterministic = bool(deterministic)
+        self.antialiased = bool(antialiased)
+        self.filter_3d = None  # (n,) sigma of the 3D smoothing filter per splat (update_filter_3d), or None
         self.steps = 0
         self.densifications = 0
         self.relocations = self.additions = self.noises = 0
@@ -151,23 +172,72 @@ class GaussianFit:
 
     def render(self, camera_or_uniforms, width, height, return_depth=False):
         """(rgb (H, W, 3), alpha (H, W)), or with return_depth (rgb, alpha, depth): autograd.render_gaussians of the activated
-        parameters.  The frame's records are kept for the next step()."""
+        parameters (with the 3D filter fused into scales and opacity when one is set, and the opacity times rho when the fit is
+        antialiased).  The frame's records are kept for the next step()."""
         torch = AG._t()
         u = AG._uniforms(camera_or_uniforms, width, height)
-        if self.exact_activations:
-            scales, opacity = torch.exp(self.log_scales.double()).float(), torch.sigmoid(self.opacity_logits.double()).float()
-        else:
-            scales, opacity = torch.exp(self.log_scales), torch.sigmoid(self.opacity_logits)
-        if return_depth:
+        scales, opacity = self._activated()
+        rho = None
+        if self.antialiased and return_depth:
+            rec, rho, depths, aux = AG.project_ellipsoids(u, self.means, scales, self.rotations, return_depth=True, antialiased=True)
+        elif self.antialiased:
+            rec, rho, aux = AG.project_ellipsoids(u, self.means, scales, self.rotations, antialiased=True)
+            depths = None
+        elif return_depth:
             rec, depths, aux = AG.project_ellipsoids(u, self.means, scales, self.rotations, return_depth=True)
         else:
             rec, aux = AG.project_ellipsoids(u, self.means, scales, self.rotations)
             depths = None
         col = AG.sh_colors(u[16:19], self.means, self.sh, self.degree, opacity)
+        if rho is not None:
+            col = AG.compensate_opacity(col, rho)
         if rec.requires_grad:
             rec.retain_grad()
         self._frame = (rec, int(width), int(height))
         return AG.rasterize(rec, col, aux, width, height, depths=depths, deterministic=self.deterministic)
+
+    def _activated(self):
+        """(scales (n, 3), opacity (n,)) as render() draws them: exp and sigmoid (in float64, rounded once, with
+        exact_activations), and with a 3D filter f the fused s_eff = sqrt(s^2 + f^2), o_eff = o sqrt(prod s^2 / prod s_eff^2)
+        (formed in the activations' precision)."""
+        torch = AG._t()
+        if self.exact_activations:
+            scales, opacity = torch.exp(self.log_scales.double()), torch.sigmoid(self.opacity_logits.double())
+        else:
+            scales, opacity = torch.exp(self.log_scales), torch.sigmoid(self.opacity_logits)
+        if self.filter_3d is not None:
+            s2 = scales * scales
+            e2 = s2 + (self.filter_3d.to(scales.dtype) ** 2)[:, None]
+            scales, opacity = torch.sqrt(e2), opacity * torch.sqrt(s2.prod(dim=1) / e2.prod(dim=1))
+        return (scales.float(), opacity.float()) if self.exact_activations else (scales, opacity)
+
+    def update_filter_3d(self, cameras, width, height, focal_px=None, near=0.2, margin=0.15, variance=0.2):
+        """Mip-Splatting's 3D smoothing filter from the training cameras (Cameras or uniform blocks): the rate is reset to zero,
+        splat_sampling_rate_max runs once per camera (a splat counts for a camera when its clip w exceeds `near` and its screen
+        centre lies inside the screen widened by `margin` of its size on every side), and filter_3d = sqrt(variance) / rate, 0
+        (no smoothing) where no camera saw the splat.  focal_px: the focal length in pixels, one value or one per camera; the
+        default is 0.5 W |(m0, m4, m8)| of each camera's VP, formed in float64 on the host: exact for a centred pinhole (row 0
+        of VP is then (2 fx / W) times a unit row of the rotation), an approximation when the principal point is off centre.
+        Returns filter_3d (n,).  densify_and_prune(), relocate() and add_new() clear it: call this again after them."""
+        torch = AG._t()
+        n = self.n
+        cameras = list(cameras)
+        focals = list(focal_px) if hasattr(focal_px, "__len__") else [focal_px] * len(cameras)
+        if len(focals) != len(cameras):
+            raise SplatError(-1, "update_filter_3d: focal_px must be one value or one per camera")
+        rate = torch.zeros(n, device=self.means.device, dtype=torch.float32)
+        if n:
+            cx = AG._context(self.means)
+            pos = AG._cuda_f32(AG._vec4(self.means.detach(), "means", 1.0), "means", 4)
+            for cam, focal in zip(cameras, focals):
+                u = AG._uniforms(cam, width, height)
+                if focal is None:
+                    focal = 0.5 * float(u[20]) * math.sqrt(float(u[0]) ** 2 + float(u[4]) ** 2 + float(u[8]) ** 2)
+                check(cx.lib.splat_sampling_rate_max(cx.ctx, AG._fptr(u), float(focal), float(near), float(margin), pos.data_ptr(), 1, n,
+                                                     rate.data_ptr()), cx.ctx)
+        self.filter_3d = torch.where(rate > 0, math.sqrt(float(variance)) / rate, torch.zeros_like(rate))
+        self._frame = None
+        return self.filter_3d
 
     def step(self, lr=None):
         """One optimiser step after backward(): this frame's density statistics and visibility mask, five Adam launches, the
@@ -238,6 +308,7 @@ class GaussianFit:
         self._set(*(new[name] for name in PLANES))
         self._reset_statistics()
         self._frame = None
+        self.filter_3d = None  # (it belonged to the old rows: update_filter_3d() again)
         return {"pruned": int(counts[0]), "kept": int(counts[1]), "cloned": int(counts[2]), "split": int(counts[3]), "n": k}
 
     def reset_opacity(self, value=0.01):
@@ -295,6 +366,7 @@ class GaussianFit:
                                               C.byref(pl)), cx.ctx)
                 drawn = int((counts[:n] > 0).sum())
         self._frame = None
+        self.filter_3d = None  # (moved rows: update_filter_3d() again)
         return {"dead": dead, "alive": alive, "relocated": draws, "sources": drawn}
 
     def add_new(self, max_splats, growth=0.05, min_opacity=0.005, seed=None):
@@ -331,6 +403,7 @@ class GaussianFit:
                                                                                              self.visible))
         self._set(*(new[name] for name in PLANES))
         self._frame = None
+        self.filter_3d = None  # (new rows: update_filter_3d() again)
         return {"added": k, "n": n + k}
 
     def inject_noise(self, noise_lr=5e5, lr_means=None, seed=None):
@@ -353,8 +426,20 @@ class GaussianFit:
         return opacity_reg * torch.sigmoid(self.opacity_logits).mean() + scale_reg * torch.exp(self.log_scales).mean()
 
     def save_ply(self, path):
-        """The cloud as a 3D Gaussian splatting PLY file (ply.save_gaussian_ply): the raw parameters, bit for bit."""
+        """The cloud as a 3D Gaussian splatting PLY file (ply.save_gaussian_ply): the raw parameters, bit for bit; with a 3D
+        filter set, the fused scales and opacities (log s_eff and logit o_eff, formed in float64 and rounded once), so that a
+        viewer that knows nothing of the filter draws the cloud render() draws."""
         from .ply import save_gaussian_ply
         c = lambda t: t.detach().cpu().numpy()  # noqa: E731
+        if self.filter_3d is not None:
+            torch = AG._t()
+            with torch.no_grad():
+                s2 = torch.exp(self.log_scales.double()) ** 2
+                e2 = s2 + (self.filter_3d.double() ** 2)[:, None]
+                o = torch.sigmoid(self.opacity_logits.double()) * torch.sqrt(s2.prod(dim=1) / e2.prod(dim=1))
+                log_scales, logits = (0.5 * torch.log(e2)).float(), torch.logit(o).float()
+            save_gaussian_ply(path, c(self.means), None, c(self.rotations), None, c(self.sh).reshape(self.n, -1, 3), log_scales=c(log_scales),
+                              opacity_logits=c(logits))
+            return
         save_gaussian_ply(path, c(self.means), None, c(self.rotations), None, c(self.sh).reshape(self.n, -1, 3), log_scales=c(self.log_scales),
                           opacity_logits=c(self.opacity_logits))

@@ -447,11 +447,17 @@ class SplatProjector:
     isotropic screen-space Gaussian — project() then needs the normals, the ProjectedSplat bounds are the disc's
     exact screen extent and getDiscBuffer() holds the 32-byte disc records the composite evaluates.
     footprint="ellipsoid" (extension): project anisotropic 3D Gaussians — project(..., cloud=GaussianCloud) writes their
-    ProjectedSplat records (the exact 3-sigma box) and, in getDiscBuffer(), their 32-byte records (splat_project_ellipsoid)."""
+    ProjectedSplat records (the exact 3-sigma box) and, in getDiscBuffer(), their 32-byte records (splat_project_ellipsoid).
+    antialiased=True (ellipsoid only): the same through splat_project_ellipsoid_aa, which also leaves the 2D Mip filter's
+    factor rho (one float per splat) in getCompensationBuffer()."""
 
-    def __init__(self, device, numSplats, footprint="isotropic"):
+    def __init__(self, device, numSplats, footprint="isotropic", antialiased=False):
         self.device, self.numSplats = device, numSplats
         self.footprint = _footprint(footprint)
+        self.antialiased = bool(antialiased)
+        if self.antialiased and self.footprint != _lib.FOOTPRINT_ELLIPSOID:
+            raise SplatError(-1, "antialiased=True is the ellipsoid footprint's mode")
+        self.compensationBuffer = device.createBuffer(max(numSplats, 1) * 4) if self.antialiased else None
         self.projectedBuffer = device.createBuffer(numSplats * 32)  # :19-23
         self.contents = "projected"  # what projectedBuffer holds: ProjectedSplat records, or a frame's lit composite records
         self.discBuffer = device.createBuffer(numSplats * 32) if self.footprint != _lib.FOOTPRINT_ISOTROPIC else None
@@ -473,6 +479,11 @@ class SplatProjector:
                 raise SplatError(-1, "SplatProjector(footprint='ellipsoid').project needs cloud (a GaussianCloud)")
             if cloud.n > self.numSplats:
                 raise SplatError(-1, "the cloud holds more splats than this projector was created for")
+            if self.antialiased:
+                check(d.lib.splat_project_ellipsoid_aa(d.ctx, uptr, cloud.positions.ptr, 1, cloud.scales.ptr, 1, cloud.rotations.ptr, 1, cloud.n,
+                                                       self.projectedBuffer.ptr, self.discBuffer.ptr, keys, payload, paddedSize,
+                                                       self.compensationBuffer.ptr, None, 1, None), d.ctx)
+                return
             check(d.lib.splat_project_ellipsoid(d.ctx, uptr, cloud.positions.ptr, 1, cloud.scales.ptr, 1, cloud.rotations.ptr, 1, cloud.n,
                                                 self.projectedBuffer.ptr, self.discBuffer.ptr, keys, payload, paddedSize), d.ctx)
             return
@@ -505,9 +516,17 @@ class SplatProjector:
             raise SplatError(-5, "getDiscBuffer: this projector was not created with footprint='disc' or 'ellipsoid'")
         return self.discBuffer
 
+    def getCompensationBuffer(self):
+        """rho per splat (float32) of the last antialiased projection: the factor the drawn opacity is multiplied by."""
+        if self.compensationBuffer is None:
+            raise SplatError(-5, "getCompensationBuffer: this projector was not created with antialiased=True")
+        return self.compensationBuffer
+
     def destroy(self):  # :200-202
         if self.device.lastProjector is self:
             self.device.lastProjector = None
+        if self.compensationBuffer is not None:
+            self.compensationBuffer.destroy()
         self.projectedBuffer.destroy()
         if self.discBuffer is not None:
             self.discBuffer.destroy()
@@ -912,7 +931,7 @@ class Renderer:
 
     def __init__(self, device, context=None, presentationFormat="rgba8unorm", numPoints=0, tileSize=16,
                  mode=_lib.MODE_FRONT_TO_BACK, earlyOut=True, frameOrder=None, footprint="isotropic", writeProjected=True,
-                 records="lit"):
+                 records="lit", antialiased=False):
         # footprint="disc": the frame is drawn with SequentialRenderer's oriented discs (normalsBuffer is then
         # required in render() even with pre-lit planes: the projector reads it).  writeProjected=False (disc
         # frames only): the ProjectedSplat records, which a disc frame's composite does not read, are not written.
@@ -924,7 +943,11 @@ class Renderer:
         # every screen the binner takes.
         # footprint="ellipsoid": anisotropic 3D Gaussians — render(u, cloud, None, None, w, h) with a GaussianCloud, whose SH colour
         # (when it has one) is evaluated towards the camera first; the frame is a disc frame in every other respect
+        # antialiased=True (ellipsoid frames): the 2D Mip filter — every opacity is drawn times rho (splat_render_frame_ellipsoids_aa)
         self.footprint = _footprint(footprint)
+        self.antialiased = bool(antialiased)
+        if self.antialiased and self.footprint != _lib.FOOTPRINT_ELLIPSOID:
+            raise SplatError(-1, "antialiased=True is the ellipsoid footprint's mode")
         if not writeProjected and self.footprint == _lib.FOOTPRINT_ISOTROPIC:
             raise SplatError(-1, "writeProjected=False: the isotropic composite reads the records the projector writes")
         if records not in ("lit", "lit-always", "projected"):
@@ -1002,7 +1025,8 @@ class Renderer:
         if ell:
             propertyBuffer.updateColors(u[16:19])
             tail = (propertyBuffer.n,) + tail[2:]
-            fn, args = d.lib.splat_render_frame_ellipsoids, head + (propertyBuffer.positions.ptr, propertyBuffer.scales.ptr,
+            frame = d.lib.splat_render_frame_ellipsoids_aa if self.antialiased else d.lib.splat_render_frame_ellipsoids
+            fn, args = frame, head + (propertyBuffer.positions.ptr, propertyBuffer.scales.ptr,
                                                                     propertyBuffer.rotations.ptr, propertyBuffer.colorOpacity.ptr) + tail
         elif isinstance(propertyBuffer, PropertyPlanes):  # the native layout: SplatPropertyManager.getPropertyPlanes()
             fn, args = d.lib.splat_render_frame_planes_aov, head + (propertyBuffer.posRadius.ptr, propertyBuffer.colorOpacity.ptr) + tail

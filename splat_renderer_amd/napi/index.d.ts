@@ -271,8 +271,10 @@ export class GaussianCloud {
   destroy(): void;
 }
 export class Renderer {
-  constructor(device: Device, context?: unknown, presentationFormat?: string, numPoints?: number, tileSize?: number, options?: { footprint?: Footprint; records?: "lit" | "lit-always" | "projected" });
+  constructor(device: Device, context?: unknown, presentationFormat?: string, numPoints?: number, tileSize?: number, options?: { footprint?: Footprint; records?: "lit" | "lit-always" | "projected"; antialiased?: boolean });
   recordFormat: number;
+  /** ellipsoid frames only: the 2D Mip filter, every opacity drawn times rho (include/splat.h splat_render_frame_ellipsoids_aa) */
+  antialiased: boolean;
   /** wantAov: also the depth, alpha and splat-id buffers (include/splat.h splat_aov).  footprint 'ellipsoid': a GaussianCloud, normalsBuffer null */
   render(uniformData: Float32Array | Buffer, propertyBuffer: Buffer | PropertyPlanes | GaussianCloud, normalsBuffer: Buffer | null, scaleFactorsBuffer: Buffer | null, width: number, height: number, wantAov?: boolean): Buffer;
   finish(): number;

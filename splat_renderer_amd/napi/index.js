@@ -555,6 +555,9 @@ class Renderer {
     this.numPoints = numPoints;
     this.tileSize = tileSize;
     this.footprint = footprintCode(options.footprint);
+    // antialiased (ellipsoid frames): the 2D Mip filter — every opacity is drawn times rho (render_frame_ellipsoids_aa)
+    this.antialiased = !!options.antialiased;
+    if (this.antialiased && this.footprint !== FOOTPRINT_ELLIPSOID) throw new Error("antialiased: true is the ellipsoid footprint's mode");
     // 'disc': SequentialRenderer's oriented discs (normalsBuffer then always required)
     // records 'lit' (default, isotropic frames): the projector leaves 32-byte lit composite records (centre, radius, depth |
     // lit colour) in projector.getProjectedBuffer() and the composite gathers ONE line per staged list entry;
@@ -605,7 +608,8 @@ class Renderer {
     this.aov.written = false;
     if (propertyBuffer instanceof GaussianCloud) {
       propertyBuffer.updateColors(u.subarray(16, 19));
-      native.render_frame_ellipsoids(this.device.ctx, this.sorter.handle, this.binner.handle, cfg, u, propertyBuffer.positions.ptr, propertyBuffer.scales.ptr,
+      const frame = this.antialiased ? native.render_frame_ellipsoids_aa : native.render_frame_ellipsoids;
+      frame(this.device.ctx, this.sorter.handle, this.binner.handle, cfg, u, propertyBuffer.positions.ptr, propertyBuffer.scales.ptr,
         propertyBuffer.rotations.ptr, propertyBuffer.colorOpacity.ptr, propertyBuffer.n, width, height, this.projector.projectedBuffer.ptr, this.output.ptr, null, aov);
     } else if (propertyBuffer.isPlanes) { // SplatPropertyManager.getPropertyPlanes()
       native.render_frame_planes_aov(this.device.ctx, this.sorter.handle, this.binner.handle, cfg, u, propertyBuffer.posRadius.ptr, propertyBuffer.colorOpacity.ptr,

@@ -360,6 +360,22 @@ FN(project_ellipsoid) { /* (ctx, Float32Array(22), positions, posStride, scales,
     if (ub < 22 * sizeof(float)) { napi_throw_range_error(env, NULL, "uniform block needs 22 floats"); return NULL; }
     return check(env, x, splat_project_ellipsoid(x, u, pos, ps, scl, ss, rot, rs, n, proj, rec, keys, pay, np), mk_undefined(env));
 }
+FN(project_ellipsoid_aa) { /* project_ellipsoid's arguments, then rho|null, colorOpacity|null, colorStride, colorOpacityOut|null */
+    ARGS(18); splat_ctx *x = arg_external(&c, 0); size_t ub = 0; float *u = arg_hostbuf(&c, 1, &ub);
+    void *pos = arg_dptr(&c, 2); uint32_t ps = (uint32_t)arg_number(&c, 3); void *scl = arg_dptr(&c, 4); uint32_t ss = (uint32_t)arg_number(&c, 5);
+    void *rot = arg_dptr(&c, 6); uint32_t rs = (uint32_t)arg_number(&c, 7), n = (uint32_t)arg_number(&c, 8);
+    void *proj = arg_dptr(&c, 9), *rec = arg_dptr(&c, 10), *keys = arg_dptr(&c, 11), *pay = arg_dptr(&c, 12); uint32_t np = (uint32_t)arg_number(&c, 13);
+    void *rho = arg_dptr(&c, 14), *co = arg_dptr(&c, 15); uint32_t cs = (uint32_t)arg_number(&c, 16); void *coo = arg_dptr(&c, 17); BAIL;
+    if (ub < 22 * sizeof(float)) { napi_throw_range_error(env, NULL, "uniform block needs 22 floats"); return NULL; }
+    return check(env, x, splat_project_ellipsoid_aa(x, u, pos, ps, scl, ss, rot, rs, n, proj, rec, keys, pay, np, rho, co, cs, coo), mk_undefined(env));
+}
+FN(sampling_rate_max) { /* (ctx, Float32Array(22), focalPx, near, margin, positions, posStride, n, rateInOut) */
+    ARGS(9); splat_ctx *x = arg_external(&c, 0); size_t ub = 0; float *u = arg_hostbuf(&c, 1, &ub);
+    float focal = (float)arg_number(&c, 2), near_ = (float)arg_number(&c, 3), margin = (float)arg_number(&c, 4);
+    void *pos = arg_dptr(&c, 5); uint32_t ps = (uint32_t)arg_number(&c, 6), n = (uint32_t)arg_number(&c, 7); void *rate = arg_dptr(&c, 8); BAIL;
+    if (ub < 22 * sizeof(float)) { napi_throw_range_error(env, NULL, "uniform block needs 22 floats"); return NULL; }
+    return check(env, x, splat_sampling_rate_max(x, u, focal, near_, margin, pos, ps, n, rate), mk_undefined(env));
+}
 FN(sh_colors) { /* (ctx, Float32Array(3) eye, positions, posStride, sh, shStrideFloats, degree, opacity, n, colorOpacityOut) */
     ARGS(10); splat_ctx *x = arg_external(&c, 0); size_t eb = 0; float *eye = arg_hostbuf(&c, 1, &eb);
     void *pos = arg_dptr(&c, 2); uint32_t ps = (uint32_t)arg_number(&c, 3); void *sh = arg_dptr(&c, 4);
@@ -434,6 +450,15 @@ FN(project_ellipsoid_backward_camera) { /* project_ellipsoid_backward's argument
     void *gu = arg_dptr(&c, 14); BAIL;
     if (ub < 22 * sizeof(float)) { napi_throw_range_error(env, NULL, "uniform block needs 22 floats"); return NULL; }
     return check(env, x, splat_project_ellipsoid_backward_camera(x, u, pos, ps, scl, ss, rot, rs, n, grec, gp, gs, gr, gz, gu), mk_undefined(env));
+}
+FN(project_ellipsoid_backward_aa) { /* project_ellipsoid_backward's arguments, then gradDepth|null, gradUniforms|null (device, 22 floats), gradRho */
+    ARGS(16); splat_ctx *x = arg_external(&c, 0); size_t ub = 0; float *u = arg_hostbuf(&c, 1, &ub);
+    void *pos = arg_dptr(&c, 2); uint32_t ps = (uint32_t)arg_number(&c, 3); void *scl = arg_dptr(&c, 4); uint32_t ss = (uint32_t)arg_number(&c, 5);
+    void *rot = arg_dptr(&c, 6); uint32_t rs = (uint32_t)arg_number(&c, 7), n = (uint32_t)arg_number(&c, 8);
+    void *grec = arg_dptr(&c, 9), *gp = arg_dptr(&c, 10), *gs = arg_dptr(&c, 11), *gr = arg_dptr(&c, 12), *gz = arg_dptr(&c, 13);
+    void *gu = arg_dptr(&c, 14), *grho = arg_dptr(&c, 15); BAIL;
+    if (ub < 22 * sizeof(float)) { napi_throw_range_error(env, NULL, "uniform block needs 22 floats"); return NULL; }
+    return check(env, x, splat_project_ellipsoid_backward_aa(x, u, pos, ps, scl, ss, rot, rs, n, grec, gp, gs, gr, gz, gu, grho), mk_undefined(env));
 }
 FN(sh_colors_backward_camera) { /* sh_colors_backward's arguments, then gradEye (device, 4 floats) */
     ARGS(14); splat_ctx *x = arg_external(&c, 0); size_t eb = 0; float *eye = arg_hostbuf(&c, 1, &eb);
@@ -581,6 +606,18 @@ FN(render_frame_ellipsoids) { /* (ctx, sorter, binner, cfg[8], Float32Array(22),
     if (ub < 22 * sizeof(float)) { napi_throw_range_error(env, NULL, "uniform block needs 22 floats"); return NULL; }
     int rc = splat_render_frame_ellipsoids(x, s, b, &cfg, u, pos, scl, rot, co, n, w, h, proj, o8, of, ap);
     if (AGAIN(rc)) rc = splat_render_frame_ellipsoids(x, s, b, &cfg, u, pos, scl, rot, co, n, w, h, proj, o8, of, ap);
+    return check(env, x, rc, mk_undefined(env));
+}
+FN(render_frame_ellipsoids_aa) { /* render_frame_ellipsoids' arguments: the antialiased frame */
+    ARGS(16); splat_ctx *x = arg_external(&c, 0); splat_sorter *s = arg_external(&c, 1); splat_binner *b = arg_external(&c, 2);
+    splat_composite_cfg cfg; fill_cfg(&c, 3, &cfg); size_t ub = 0; float *u = arg_hostbuf(&c, 4, &ub);
+    void *pos = arg_dptr(&c, 5), *scl = arg_dptr(&c, 6), *rot = arg_dptr(&c, 7), *co = arg_dptr(&c, 8);
+    uint32_t n = (uint32_t)arg_number(&c, 9), w = (uint32_t)arg_number(&c, 10), h = (uint32_t)arg_number(&c, 11);
+    void *proj = arg_dptr(&c, 12), *o8 = arg_dptr(&c, 13), *of = arg_dptr(&c, 14); BAIL;
+    splat_aov a; const splat_aov *ap = fill_aov(&c, 15, &a);
+    if (ub < 22 * sizeof(float)) { napi_throw_range_error(env, NULL, "uniform block needs 22 floats"); return NULL; }
+    int rc = splat_render_frame_ellipsoids_aa(x, s, b, &cfg, u, pos, scl, rot, co, n, w, h, proj, o8, of, ap);
+    if (AGAIN(rc)) rc = splat_render_frame_ellipsoids_aa(x, s, b, &cfg, u, pos, scl, rot, co, n, w, h, proj, o8, of, ap);
     return check(env, x, rc, mk_undefined(env));
 }
 FN(render_frame) { /* (ctx, sorter, binner, cfg[5], Float32Array(22), props, normals, n, W, H, projected, out8|null, outF|null) */
@@ -842,6 +879,7 @@ static napi_value init(napi_env env, napi_value exports) {
         EXPORT(densify_geometry), EXPORT(densify_rows),
         EXPORT(mcmc_sample_workspace_bytes), EXPORT(mcmc_sample), EXPORT(mcmc_apply), EXPORT(mcmc_noise),
         EXPORT(knn_workspace_bytes), EXPORT(knn_mean_sq),
+        EXPORT(project_ellipsoid_aa), EXPORT(render_frame_ellipsoids_aa), EXPORT(project_ellipsoid_backward_aa), EXPORT(sampling_rate_max),
     };
     napi_define_properties(env, exports, sizeof d / sizeof d[0], d);
     return exports;

@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
-"""Anisotropic Gaussians against the other footprints (GPU box only): python tools/ellipsoid_bench.py [C1,C2] [K] [R]
+"""Anisotropic Gaussians against the other footprints (GPU box only): python tools/ellipsoid_bench.py [C1,C2] [K] [R] [--antialiased]
 
 Per config one JSON line: device ms of splat_project_ellipsoid (with the fused keys), of splat_sh_colors at degree 3, and of
 whole ellipsoid, disc and isotropic frames (Renderer, default settings) on the same positions — the scene's, with sigma =
 radius / 2 per axis times a random factor in [e^-0.3, e^0.3], random rotations and the scene's colours — R rounds of K calls
 each, the kinds alternating round by round in one process, timed with device events after a warm-up.  The frames' tile-list
-pair totals are printed beside them: the composite's cost follows the pairs, so frames compare by pairs."""
+pair totals are printed beside them: the composite's cost follows the pairs, so frames compare by pairs.
+--antialiased: also splat_project_ellipsoid_aa with every output ("project_aa") and the antialiased whole frame ("ellipsoid_aa",
+splat_render_frame_ellipsoids_aa), in the same rounds as their classic twins."""
 import json
 import os
 import sys
@@ -16,9 +18,11 @@ import torch
 
 import splat_renderer_amd as sr
 
-names = sys.argv[1].split(",") if len(sys.argv) > 1 else ["C1", "C2"]
-k = int(sys.argv[2]) if len(sys.argv) > 2 else 50
-rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 7
+antialiased = "--antialiased" in sys.argv[1:]
+argv = [a for a in sys.argv if not a.startswith("--")]
+names = argv[1].split(",") if len(argv) > 1 else ["C1", "C2"]
+k = int(argv[2]) if len(argv) > 2 else 50
+rounds = int(argv[3]) if len(argv) > 3 else 7
 stream = torch.cuda.current_stream()
 dev = sr.Device(0, stream=stream.cuda_stream)
 for name in names:
@@ -47,6 +51,23 @@ for name in names:
         "isotropic": lambda: rs["isotropic"].render(u, pbuf, nbuf, None, w, h),
     }
 
+    extra = []
+    if antialiased:
+        proj_aa = sr.SplatProjector(dev, n, footprint="ellipsoid", antialiased=True)
+        rs["ellipsoid_aa"] = sr.Renderer(dev, None, "rgba8unorm", n, footprint="ellipsoid", antialiased=True)
+        comp = dev.createBuffer(n * 16)
+        lib = dev.lib
+
+        def project_aa():  # every output: records, ProjectedSplats, keys, rho and the compensated colour plane
+            import ctypes as C
+            sr._lib.check(lib.splat_project_ellipsoid_aa(dev.ctx, u.ctypes.data_as(C.POINTER(C.c_float)), cloud.positions.ptr, 1, cloud.scales.ptr, 1,
+                                                         cloud.rotations.ptr, 1, n, proj_aa.projectedBuffer.ptr, proj_aa.discBuffer.ptr,
+                                                         sorter.getKeysBuffer().ptr, sorter.getPayloadBuffer().ptr, sorter.paddedSize,
+                                                         proj_aa.compensationBuffer.ptr, cloud.colorOpacity.ptr, 1, comp.ptr), dev.ctx)
+        work["project_aa"] = project_aa
+        work["ellipsoid_aa"] = lambda: rs["ellipsoid_aa"].render(u, cloud, None, None, w, h)
+        extra = [proj_aa, comp]
+
     def run(kind, calls):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(stream)
@@ -70,6 +91,6 @@ for name in names:
                       **{f"{kind}_ms": round(v, 4) for kind, v in med.items()},
                       **{f"{kind}_ms_min_max": [round(min(v), 4), round(max(v), 4)] for kind, v in t.items()},
                       "pairs": pairs}), flush=True)
-    for o in (proj, sorter, pm, nbuf, cloud, shcloud):
+    for o in [proj, sorter, pm, nbuf, cloud, shcloud] + extra:
         o.destroy()
 dev.destroy()

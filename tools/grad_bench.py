@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Gradients of ellipsoid frames (GPU box only): python tools/grad_bench.py [--depth] [--deterministic] [--camera | --loss | --optimizer] [C1,C2] [K] [R]
+"""Gradients of ellipsoid frames (GPU box only): python tools/grad_bench.py [--depth] [--deterministic] [--antialiased] [--camera | --loss | --optimizer] [C1,C2] [K] [R]
 
 tools/ellipsoid_bench.py's scenes and method (the scene's positions, sigma = radius / 2 per axis times a random factor in
 [e^-0.3, e^0.3], random rotations, SH of degree 3 with the scene's opacity; R rounds of K calls per kind, kinds alternating
@@ -21,6 +21,11 @@ rectangle count, its scan, the tile kernel storing to the slots, the gather - an
 rasterize(..., deterministic=True) (backward_det); their ratios to the atomic path; the workspace bytes; the slots the tile
 kernel wrote (the sum of the tile table's largest L, read back from the workspace) and the time the gather's bytes - every
 written slot once out and once in, 36 or 40 B each, plus the 16 B table rows - take at the 5.1 TB/s copy rate.
+
+--antialiased adds the antialiased mode beside the classic one, alternating in the same rounds: the staged forward with
+project_ellipsoids(antialiased=True) and the opacity column times rho (forward_aa), its backward (backward_aa), and
+splat_project_ellipsoid_backward_aa alone with a random grad_rho and no camera sums (project_backward_aa) beside
+splat_project_ellipsoid_backward; their ratios to the classic path.
 
 --camera adds the camera gradients: splat_project_ellipsoid_backward_camera without and with grad_depth (all of its launches:
 the per-splat kernel with the per-wave sums, then k_camera_sum_slices above 1024 partials, then k_camera_sum) beside
@@ -112,7 +117,8 @@ def torch_camera_terms(U, pos, scl, rot, g, W, H):
     return torch.stack(terms, dim=1).sum(dim=0)
 
 
-argv = [a for a in sys.argv[1:] if a not in ("--depth", "--camera", "--loss", "--optimizer", "--deterministic")]
+argv = [a for a in sys.argv[1:] if a not in ("--depth", "--camera", "--loss", "--optimizer", "--deterministic", "--antialiased")]
+aa_too = "--antialiased" in sys.argv[1:]
 det_too = "--deterministic" in sys.argv[1:]
 optimizer_only = "--optimizer" in sys.argv[1:]
 depth_too = "--depth" in sys.argv[1:]
@@ -573,6 +579,22 @@ for name in names:
             "project_backward_plus_torch_terms": plus_torch_terms,
         })
     forwards = {"backward": forward, "backward_depth": forward_depth}
+    if aa_too:
+        grho = torch.rand(n, device="cuda") * 2 - 1
+
+        def forward_aa():
+            rec, rho, aux = AG.project_ellipsoids(u, means, scales, rots, antialiased=True)
+            col = AG.compensate_opacity(AG.sh_colors(u[16:19], means, shs, 3, ops), rho)
+            rgb, _ = AG.rasterize(rec, col, aux, w, h)
+            state.update(rec=rec, col=col, aux=aux, loss=(rgb * gimg).sum())
+        work.update({
+            "forward_aa": forward_aa,
+            "backward_aa": None,
+            "project_backward_aa": lambda: lib.splat_project_ellipsoid_backward_aa(cx.ctx, uf, m4.data_ptr(), 1, s4.data_ptr(), 1, rots.data_ptr(), 1,
+                                                                                   n, grec.data_ptr(), gp.data_ptr(), gs.data_ptr(), gq.data_ptr(),
+                                                                                   None, None, grho.data_ptr()),
+        })
+        forwards["backward_aa"] = forward_aa
     if camera_too:
         forwards["backward_camera"] = forward_camera
     if det_too:
@@ -623,6 +645,9 @@ for name in names:
             extra.update({"det_workspace_bytes_depth": det_bytes[1],
                           "det_gather_floor_ms_depth": round((2 * 40 * written + 16 * tiles) / COPY_RATE * 1e3, 4),
                           "composite_backward_det_depth_over_atomic": round(med["composite_backward_det_depth"] / med["composite_backward_depth"], 3)})
+    if aa_too:
+        extra.update({f"{a}_over_{b}": round(med[a] / med[b], 3) for a, b in (
+            ("forward_aa", "forward"), ("backward_aa", "backward"), ("project_backward_aa", "project_backward"))})
     if camera_too:
         extra.update({f"{a}_over_{b}": round(med[a] / med[b], 3) for a, b in (
             ("project_backward_camera", "project_backward"), ("project_backward_camera_depth", "project_backward_depth"),
