@@ -648,6 +648,42 @@ int splat_sh_colors_backward_camera(splat_ctx *ctx, const float *eye3, const voi
                                     uint32_t sh_stride_floats, uint32_t degree, const void *opacity_f32, const void *grad_color_opacity,
                                     uint32_t n, void *grad_sh, void *grad_positions, void *grad_opacity, void *grad_eye);
 
+/* ---- Contribution of every splat to a frame: hit count, largest and summed blend weight (an extension) --------------------
+ * Which splats does a view actually see, and how much?  RadSplat prunes a fit on the largest blend weight a splat reaches in any
+ * training view, LightGaussian on hit counts, Mini-Splatting on summed weights: all three are per-splat reductions of one
+ * forward walk of the frame's tile lists.  One call scores one view; the outputs ACCUMULATE, so a call per view builds the
+ * statistic over views (the caller zeroes the buffers before the first).
+ *
+ * The pair and its weight.  Per pixel, over the entries it consumed (up to and including the one its early-out stopped at, as
+ * for the gradients above): w_i = T_i alpha_i for an entry inside the record's cut.  (pixel, entry) is then a pair.  An entry
+ * outside the cut or past the stop is no pair.  w_i is formed in the operation order of the kernel that draws this frame on this
+ * ctx (splat_composite_backward's rule, above: k_composite's w = T (g opacity), or k_composite_px's w = (T g) opacity with
+ * T = fma(-opacity, T g, T)): score a view on the ctx that draws it, with its options unchanged.
+ * The pixel mask.  m = pixel_weight_f32[y W + x] clamped to [0, 1], NaN -> 0; m = 1 everywhere when the pointer is NULL.
+ * wm = m w in binary32 (clamped to [0, 1], NaN -> 0: that changes nothing for opacities in [0, 1]).  A pixel with m = 0
+ * contributes to no output and counts no hit.
+ * The outputs, n entries each; each may be NULL (not wanted), not all three:
+ *   weight_max_f32[i] = max(prior, max over the splat's pairs of wm)                                   (float32)
+ *   weight_sum_u64[i] += sum over its pairs of q, q = (uint32) rintf(wm 2^24): fixed point in units of 2^-24  (uint64; q <= 2^24)
+ *   hits_u32[i]       += the number of its pairs with wm >= min_weight; the count wraps at 2^32         (uint32)
+ * min_weight >= 0 (0: every pair is a hit); negative or NaN is SPLAT_ERR_INVALID.  A splat in no pair with m > 0 keeps its prior
+ * bytes in all three.
+ * Bit reproducibility.  The maximum of non-negative floats (taken on their bit patterns, which order as the values do), integer
+ * sums and integer counts do not depend on the order they are formed in: the same inputs give the same bytes on every run.  That
+ * is why the sum is fixed point and not a float: a float sum over atomics would depend on their arrival order.  No float atomic
+ * is used anywhere.  (Each pair's q is within 2^-25 of wm; a sum of P pairs is within P 2^-25 of the sum of the wm.)
+ *
+ * splat_composite_contribution: splat_composite_backward's frame arguments and checks (footprint ELLIPSOID, FRONT_TO_BACK,
+ * early_out = 1, tile_size = 16, PROJECTED records, the whole screen; the lists the forward composited, on the ctx that drew the
+ * frame; every screen the binner takes).  color_opacity / records 16-byte aligned, weight_sum_u64 8-byte, the lists,
+ * pixel_weight_f32, hits_u32 and weight_max_f32 4-byte; a misaligned or NULL required pointer, or all three outputs NULL, is
+ * SPLAT_ERR_INVALID and nothing is launched.  n = 0: success, nothing launched.  All work goes to the ctx's stream; nothing
+ * waits on the host. */
+int splat_composite_contribution(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4,
+                                 const void *records, const void *tile_indices, const void *tile_counts, const void *tile_offsets,
+                                 uint32_t width, uint32_t height, const void *pixel_weight_f32 /* W*H floats or NULL */, float min_weight,
+                                 uint32_t n, void *hits_u32, void *weight_max_f32, void *weight_sum_u64);
+
 /* ---- Image loss: the photometric objective of 3D Gaussian splatting (an extension) -----------------------------------------
  * How far a rendered image x is from a target y, both width x height pixels of 3 float32 channels:
  *   loss = (1 - lambda) l1 + lambda (1 - ssim),   l1 = mean |x - y|,   ssim = mean m,   both means over all N = 3 W H values.

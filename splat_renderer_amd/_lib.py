@@ -116,6 +116,8 @@ SIGNATURES = {
     "splat_composite_backward_det_workspace_bytes": (C.c_uint64, [C.c_uint64, _u32, _u32, _i]),
     "splat_composite_backward_det": (_i, [_vp, C.POINTER(CompositeCfg), _vp, _u32, _vp, _vp, _vp, _vp, _vp, C.c_uint64, _u32, _u32, _vp, _u32,
                                           _vp, _vp, _vp, _u32, _vp, _vp, _vp, C.c_uint64]),
+    "splat_composite_contribution": (_i, [_vp, C.POINTER(CompositeCfg), _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, C.c_float, _u32,
+                                          _vp, _vp, _vp]),
     "splat_project_ellipsoid_backward_depth": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp,
                                                     _vp]),
     "splat_project_ellipsoid_backward_camera": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp,

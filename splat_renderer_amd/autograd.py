@@ -92,8 +92,22 @@ points is (n, 3) or (n, 4) (the fourth column is not read); the result is the he
 with fewer than three usable neighbours or a non-finite coordinate.  No gradient: it is an initialisation.  One call of
 splat_knn_mean_sq on torch's current stream, with this module's per-device context and sorter; nothing waits on the host.
 
+What a view sees of every splat (include/splat.h, "Contribution of every splat to a frame"):
+
+    hits, weight_max, weight_sum = contribution(rec, col, aux, width, height, pixel_weight=None, min_weight=0.0, out=None)
+
+Per splat, over the (pixel, consumed entry inside the cut) pairs of the frame rasterize would draw from the same arguments: the
+number of pairs whose blend weight w = T alpha (times the pixel's mask) is at least min_weight (int32 holding the uint32 bits),
+the largest weight (float32: RadSplat's score once taken over views) and the sum of the weights in units of 2^-24 (int64;
+weight_sum.double() * 2 ** -24 is the sum).  A named tuple of three (n,) tensors; out= an earlier result to accumulate into
+(one call per view builds the statistic over views: sums add, the maximum is kept).  pixel_weight (H, W) float32 in [0, 1]
+masks pixels.  One call of splat_composite_contribution on torch's current stream with this module's per-device context, binned
+through the same sorter and binner as rasterize (a pending backward of an earlier rasterize re-bins its own lists, as after any
+other frame).  Integer sums and a maximum: the same inputs give the same bytes on every run.  Inputs are detached; no gradient.
+
 torch is imported when a function here is first called, so `import splat_renderer_amd` does not need it.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -624,6 +638,47 @@ def compensate_opacity(col, rho):
     """(n, 4) (r, g, b, opacity * rho): the antialiased mode's colour plane, in torch ops (one binary32 product per splat, as
     splat_project_ellipsoid_aa's color_opacity_out)."""
     return _t().cat([col[:, :3], col[:, 3:] * rho.reshape(-1, 1)], dim=1)
+
+
+Contribution = collections.namedtuple("Contribution", ("hits", "weight_max", "weight_sum"))
+
+
+def contribution(rec, col, aux, width=None, height=None, pixel_weight=None, min_weight=0.0, out=None):
+    """Contribution(hits (n,) int32, weight_max (n,) float32, weight_sum (n,) int64 in units of 2^-24) of the frame
+    rasterize(rec, col, aux, width, height) draws (the module's docstring; splat_composite_contribution).  pixel_weight: (H, W)
+    CUDA float32 or None; out: an earlier Contribution to accumulate into (returned), else fresh zeros.  No gradient."""
+    torch = _t()
+    width = aux.width if width is None else int(width)
+    height = aux.height if height is None else int(height)
+    rec_c = _cuda_f32(rec.detach(), "rec", 8)
+    col_c = _cuda_f32(col.detach(), "col", 4)
+    n = aux.n
+    if rec_c.shape[0] != n or col_c.shape[0] != n:
+        raise SplatError(-1, "rec, col and the projection must hold the same number of splats")
+    if not float(min_weight) >= 0.0:
+        raise SplatError(-1, f"min_weight must be >= 0, not {min_weight}")
+    pw = None
+    if pixel_weight is not None:
+        pw = _cuda_f32(pixel_weight.detach(), "pixel_weight")
+        if tuple(pw.shape) != (height, width):
+            raise SplatError(-1, f"pixel_weight must have shape ({height}, {width}), not {tuple(pw.shape)}")
+    if out is None:
+        out = Contribution(torch.zeros(n, device=rec_c.device, dtype=torch.int32), torch.zeros(n, device=rec_c.device, dtype=torch.float32),
+                           torch.zeros(n, device=rec_c.device, dtype=torch.int64))
+    else:
+        out = Contribution(*out)
+        for t, dt, name in zip(out, (torch.int32, torch.float32, torch.int64), Contribution._fields):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != (n,) or not t.is_contiguous():
+                raise SplatError(-1, f"out.{name} must be a contiguous CUDA {dt} tensor of shape ({n},)")
+    if n:
+        cx = aux.ctx
+        cx.bin(aux, width, height)
+        idx, cnt, off = cx.lists()
+        cfg = CompositeCfg(_lib.MODE_FRONT_TO_BACK, 1, TILE, 0, _lib.U32_MAX, _lib.RECORDS_PROJECTED, 1, _lib.FOOTPRINT_ELLIPSOID)
+        check(cx.lib.splat_composite_contribution(cx.ctx, C.byref(cfg), col_c.data_ptr(), 1, rec_c.data_ptr(), idx, cnt, off, width, height,
+                                                  pw.data_ptr() if pw is not None else None, float(min_weight), n, out.hits.data_ptr(),
+                                                  out.weight_max.data_ptr(), out.weight_sum.data_ptr()), cx.ctx)
+    return out
 
 
 def _image(t, name, channels):

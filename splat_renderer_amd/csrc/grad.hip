@@ -25,6 +25,12 @@
 //   index), so one compare with the tile's row decides - each tile row left to right, the rows top to bottom, and the total
 //   once into the splat's row: the order include/splat.h states, the same bits on every run.  The instantiations without DET
 //   are the kernel as it was, instruction for instruction.
+// k_composite_contribution   (splat_composite_contribution) walk 1 alone, with every lane kept in the loop: per consumed entry
+//   inside the cut a pixel's blend weight w = T alpha, in the drawing kernel's operation order as above (<PX>), times the
+//   pixel's mask.  Per entry and wave a ballot counts the hits and two integer DPP trees give the largest weight (non-negative
+//   floats order as their bit patterns) and the sum of the weights in fixed point; the four waves' partials meet in LDS, and
+//   after the chunk at most one integer atomic per (entry, output) goes to global memory.  Integer max, sum and count do not
+//   depend on the order of arrival: the same bits on every run.
 // k_project_ellipsoid_backward   one thread per splat: the record's gradient through B = U / 3, U(a, b, c), Sigma2 = T T^T + 0.3 I,
 //   T = J M, M = R S, the quaternion's normalisation and J's and the centre's dependence on the position, in float64.  The
 //   cull decisions are ellipsoid_record's own (binary32); a culled splat gets exact zeros.  <DEPTH = true> adds the ProjectedSplat
@@ -69,6 +75,26 @@ __device__ __forceinline__ float wave_sum63(float v) {
     return v;
 }
 
+// wave_sum63 and its unsigned maximum on 32-bit integers (lanes a row mask leaves out read 0: neutral for both)
+__device__ __forceinline__ uint32_t wave_add63_u32(uint32_t v) {
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xb1, 0xf, 0xf, false);  // quad_perm [1,0,3,2]
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4e, 0xf, 0xf, false);  // quad_perm [2,3,0,1]
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x124, 0xf, 0xf, false); // row_ror:4
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xf, 0xf, false); // row_ror:8
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false); // row_bcast:15
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false); // row_bcast:31
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_max63_u32(uint32_t v) {
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xb1, 0xf, 0xf, false));
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4e, 0xf, 0xf, false));
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x124, 0xf, 0xf, false));
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xf, 0xf, false));
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false));
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false));
+    return v;
+}
+
 struct BackParams {
     const float4 *color; uint32_t color_stride;
     const float4 *records;
@@ -97,6 +123,16 @@ struct BackDetParams : BackDepthParams {
 };
 
 constexpr uint32_t DET_NO_SLOT = 0xffffffffu;
+
+// splat_composite_contribution's arguments: the frame's (the gradient pointers of BackParams are not read), the pixel mask (NULL:
+// 1 everywhere) and the three per-splat outputs (each NULL: not wanted)
+struct ContribParams : BackParams {
+    const float *pixel_weight;
+    float min_weight;
+    uint32_t *hits;
+    uint32_t *weight_max;          // binary32 bit patterns
+    unsigned long long *weight_sum; // units of 2^-24
+};
 
 // extract-depth-keys' key of a ProjectedSplat depth (project.hip's depth_key): the lists ascend in (key, index)
 __device__ __forceinline__ uint32_t det_depth_key(float depth) {
@@ -334,6 +370,92 @@ __global__ __launch_bounds__(256) void k_composite_backward(
             }
         }
         cend = c0;
+    }
+}
+
+// k_composite_contribution   (file header) the blend weight of every (pixel, consumed entry inside the cut) pair, reduced per splat
+//   to a hit count, a maximum and a fixed-point sum, all ACCUMULATED into the caller's buffers.  Walk 1's arithmetic, but its
+//   per-lane break at the stop would take lanes out of the wave-wide reductions: here the loop over a chunk is uniform and a
+//   stopped pixel is a predicate, as walk 2's i < L is.  A wave with no live pixel skips the chunk (its partials were zeroed
+//   with the staging); the workgroup leaves after the chunk in which its last pixel stopped.
+//   wm = clamp(m T alpha, 0, 1) (the clamp acts only on an opacity outside [0, 1] or not finite: NaN -> 0), q = rint(wm 2^24) <=
+//   2^24: a wave's 64 fit 32 bits (2^30), the tile's four waves are added in 64.
+template <bool PX>
+__global__ __launch_bounds__(256) void k_composite_contribution(ContribParams p) {
+    __shared__ GradEntry s_ent[GCH];
+    __shared__ uint32_t s_idx[GCH];
+    __shared__ uint32_t s_part[3][4][GCH]; // hits, largest weight's bits, sum of q: per wave and entry
+
+    const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const uint32_t tx = blockIdx.x, ty = blockIdx.y;
+    const uint32_t tile_idx = ty * p.ntx + tx;
+    const uint32_t count = p.counts[tile_idx], off = p.offsets[tile_idx];
+    const uint32_t px = tx * GT + (w & 1) * 8 + (lane & 7), py = ty * GT + (w >> 1) * 8 + (lane >> 3);
+    const bool pixel_ok = px < p.width && py < p.height;
+    const float pxf = (float)px + 0.5f, pyf = (float)py + 0.5f;
+    float msk = pixel_ok ? 1.0f : 0.0f;
+    if (pixel_ok && p.pixel_weight) msk = __builtin_fminf(__builtin_fmaxf(p.pixel_weight[(size_t)py * p.width + px], 0.0f), 1.0f); // (NaN -> 0)
+
+    bool live = pixel_ok;
+    float T = 1.0f;
+    for (uint32_t c0 = 0; c0 < count; c0 += GCH) {
+        const uint32_t m = min((uint32_t)GCH, count - c0);
+        __syncthreads(); // the previous chunk's partials are added
+        stage_chunk<false>(p, off, c0, m, s_ent, s_idx);
+        (&s_part[0][0][0])[tid] = 0u;
+        (&s_part[0][0][0])[tid + 256] = 0u;
+        (&s_part[0][0][0])[tid + 512] = 0u;
+        __syncthreads();
+        if (__ballot(live) != 0ull) {
+            for (uint32_t j = 0; j < m; ++j) {
+                bool has = false, hit = false;
+                float wm = 0.0f;
+                if (live) {
+                    float alpha, ge, u, v, dx, dy;
+                    const bool in = entry_alpha(s_ent[j], pxf, pyf, alpha, ge, u, v, dx, dy);
+                    float wgt;
+                    if constexpr (PX) { // k_composite_px: w = T g, T = fma(-opacity, w, T); its AOV's weight w opacity
+                        const float wg = T * (in ? ge : 0.0f);
+                        wgt = wg * s_ent[j].b.y;
+                        T = __builtin_fmaf(-s_ent[j].b.y, wg, T);
+                    } else { // k_composite: alpha = g opacity, w = T alpha, T -= w
+                        const float g = in ? alpha : 0.0f;
+                        wgt = T * g;
+                        T -= wgt;
+                    }
+                    live = !(T <= G_T_STOP); // (this entry, the one the pixel stops at, is still consumed)
+                    has = in && msk > 0.0f;
+                    wm = has ? __builtin_fminf(__builtin_fmaxf(msk * wgt, 0.0f), 1.0f) : 0.0f;
+                    hit = has && wm >= p.min_weight;
+                }
+                if (__ballot(has) == 0ull) continue;
+                const uint32_t nhit = (uint32_t)__popcll(__ballot(hit));
+                const uint32_t mx = wave_max63_u32(__float_as_uint(wm));
+                const uint32_t sm = wave_add63_u32((uint32_t)__builtin_rintf(wm * 0x1p24f));
+                if (lane == 63) {
+                    s_part[0][w][j] = nhit;
+                    s_part[1][w][j] = mx;
+                    s_part[2][w][j] = sm;
+                }
+            }
+        }
+        const int any = __syncthreads_or(live);
+        // wave k adds output k of the chunk's entries: at most one atomic per (entry, output), none for a zero partial
+        if (tid < 3 * GCH && lane < m) {
+            const uint32_t a = s_part[w][0][lane], b = s_part[w][1][lane], c = s_part[w][2][lane], d = s_part[w][3][lane];
+            const size_t idx = s_idx[lane];
+            if (w == 0) {
+                const uint32_t hits = (a + b) + (c + d);
+                if (hits && p.hits) atomicAdd(p.hits + idx, hits);
+            } else if (w == 1) {
+                const uint32_t mx = max(max(a, b), max(c, d));
+                if (mx && p.weight_max) atomicMax(p.weight_max + idx, mx);
+            } else {
+                const unsigned long long sum = ((unsigned long long)a + b) + ((unsigned long long)c + d);
+                if (sum && p.weight_sum) atomicAdd(p.weight_sum + idx, sum);
+            }
+        }
+        if (!any) break;
     }
 }
 
@@ -960,6 +1082,50 @@ extern "C" int splat_composite_backward_det(splat_ctx *ctx, const splat_composit
     return composite_backward_launch(ctx, cfg, color_opacity, color_stride_vec4, records, tile_indices, tile_counts, tile_offsets, width, height,
                                      grad_rgba32f, n, grad_records, grad_color_opacity, depth, depth_f32, depth_stride_floats, grad_depth_f32,
                                      grad_depth, &det);
+}
+
+extern "C" int splat_composite_contribution(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4,
+                                            const void *records, const void *tile_indices, const void *tile_counts, const void *tile_offsets,
+                                            uint32_t width, uint32_t height, const void *pixel_weight_f32, float min_weight, uint32_t n,
+                                            void *hits_u32, void *weight_max_f32, void *weight_sum_u64) {
+    if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
+    ARG_CHECK(ctx, cfg != nullptr);
+    if (cfg->footprint != SPLAT_FOOTPRINT_ELLIPSOID || cfg->mode != SPLAT_COMPOSITE_FRONT_TO_BACK || cfg->early_out != 1 ||
+        cfg->tile_size != GT || cfg->record_format != SPLAT_RECORDS_PROJECTED)
+        return ctx_fail(ctx, SPLAT_ERR_INVALID, "splat_composite_contribution: footprint ELLIPSOID, FRONT_TO_BACK, early_out = 1, tile_size = 16 "
+                                                "and PROJECTED records only");
+    ARG_CHECK(ctx, width >= 1 && height >= 1 && width <= 65535u * GT && height <= 65535u * GT);
+    const uint32_t ntx = div_up(width, GT), nty = div_up(height, GT);
+    ARG_CHECK(ctx, cfg->tile_row0 == 0 && cfg->tile_row1 >= nty); // the whole screen: no strict band
+    ARG_CHECK(ctx, color_stride_vec4 >= 1);
+    ARG_CHECK(ctx, min_weight >= 0.0f); // (NaN fails it)
+    ARG_CHECK(ctx, color_opacity && records && tile_indices && tile_counts && tile_offsets);
+    ARG_CHECK(ctx, hits_u32 || weight_max_f32 || weight_sum_u64);
+    ARG_CHECK(ctx, (((uintptr_t)color_opacity | (uintptr_t)records) & 15) == 0 && ((uintptr_t)weight_sum_u64 & 7) == 0);
+    ARG_CHECK(ctx, (((uintptr_t)tile_indices | (uintptr_t)tile_counts | (uintptr_t)tile_offsets | (uintptr_t)pixel_weight_f32 |
+                     (uintptr_t)hits_u32 | (uintptr_t)weight_max_f32) & 3) == 0);
+    if (n == 0) return SPLAT_OK; // (no splat: every list is empty)
+    ContribParams p;
+    p.color = (const float4 *)color_opacity;
+    p.color_stride = color_stride_vec4;
+    p.records = (const float4 *)records;
+    p.indices = (const uint32_t *)tile_indices;
+    p.counts = (const uint32_t *)tile_counts;
+    p.offsets = (const uint32_t *)tile_offsets;
+    p.width = width;
+    p.height = height;
+    p.ntx = ntx;
+    p.grad_img = nullptr;
+    p.grad_records = nullptr;
+    p.grad_color = nullptr;
+    p.pixel_weight = (const float *)pixel_weight_f32;
+    p.min_weight = min_weight;
+    p.hits = (uint32_t *)hits_u32;
+    p.weight_max = (uint32_t *)weight_max_f32;
+    p.weight_sum = (unsigned long long *)weight_sum_u64;
+    variant_dispatch([&](auto px) { launch_kernel(ctx, NO_STAGE, k_composite_contribution<px.value>, dim3(ntx, nty), dim3(256), p); },
+                     composite_uses_px(ctx, ntx, nty));
+    return launch_check(ctx, "launch k_composite_contribution");
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

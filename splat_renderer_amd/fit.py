@@ -70,9 +70,28 @@ either way, and 0 leaves it as the optimiser has it).  The filter belongs to the
 densify_and_prune(), relocate() and add_new() clear it, and the caller computes it again after them, as Mip-Splatting does
 after every densification.  save_ply() writes the fused values (log s_eff, logit o_eff), so that any viewer draws the cloud
 the fit drew; without a filter it writes the raw parameters bit for bit, as before.
+
+Pruning a finished fit by what the training views see of it (include/splat.h, "Contribution of every splat to a frame"):
+
+    for cam in train_cameras:
+        fit.accumulate_importance(cam, width, height)                   # one forward walk per view; no gradient, no image
+    fit.prune_by_importance(threshold=0.01)                             # RadSplat's rule: {"pruned", "kept", "n"}
+    # or: fit.prune_by_importance(keep=0.5, kind="sum")                  # the better half by summed blend weight
+
+accumulate_importance() forms the frame's records and colours exactly as render() does (activations, 3D filter, rho) under
+no_grad and hands them to autograd.contribution, which adds into three persistent planes: per splat the hit count, the largest
+blend weight T alpha any pixel of any view gave it, and the summed weight in fixed point.  It does not touch the pending
+frame, so it may sit between backward() and step().  importance(kind) turns the planes into a score: "max" (RadSplat), "sum"
+(Mini-Splatting's summed weights), "hits" (the count) or "lightgaussian" (below); prune_by_importance() keeps the rows the score
+selects, in index order, moving all five parameter planes and both Adam moments with splat_densify_rows (every row a kept
+original: moments are copied, not zeroed), then resets the statistics, the importance planes, the 3D filter and the pending
+frame.  It waits on the host once, for the count.  The planes are integer sums and a maximum: the same views give the same
+scores, and so the same pruned cloud, bit for bit, on every run.  densify_and_prune(), relocate() and add_new() clear the planes
+too: the rows they were accumulated for are gone.
 """
 import ctypes as C
 import math
+import numbers
 
 from . import _lib
 from . import autograd as AG
@@ -82,6 +101,31 @@ from ._lib import SplatError, check
 # SH DC, SH rest (DC / 20)
 DEFAULT_LR = {"means": 1.6e-4, "log_scales": 5e-3, "rotations": 1e-3, "opacity_logits": 5e-2, "sh": 2.5e-3, "sh_rest": 1.25e-4}
 PLANES = ("means", "log_scales", "rotations", "opacity_logits", "sh")
+
+
+def select_by_importance(score, threshold=None, keep=None):
+    """The rows prune_by_importance keeps, as ascending int64 indices into `score` (a 1-D torch tensor, any device).  Exactly one
+    of threshold (keep score >= threshold) and keep (the highest scores: an int is a count, clamped to [0, n]; a float in (0, 1]
+    a fraction of n rounded down, at least 1) is given.  Equal scores go to the lower index: a stable descending sort."""
+    torch = AG._t()
+    if (threshold is None) == (keep is None):
+        raise SplatError(-1, "prune_by_importance: give exactly one of threshold and keep")
+    n = int(score.shape[0])
+    if threshold is not None:
+        return torch.nonzero(score.double() >= float(threshold)).reshape(-1)  # (in float64: a threshold below binary32's range still cuts at > 0)
+    if isinstance(keep, bool) or not isinstance(keep, (numbers.Integral, numbers.Real)):
+        raise SplatError(-1, f"prune_by_importance: keep must be an int count or a float fraction, not {keep!r}")
+    if not isinstance(keep, numbers.Integral):
+        keep = float(keep)
+        if not 0.0 < keep <= 1.0:
+            raise SplatError(-1, f"prune_by_importance: a fractional keep must lie in (0, 1], not {keep}")
+        k = min(n, max(1, int(math.floor(keep * n))))
+    else:
+        if keep < 0:
+            raise SplatError(-1, f"prune_by_importance: keep must be >= 0, not {keep}")
+        k = min(n, int(keep))
+    order = torch.sort(score, descending=True, stable=True).indices[:k]
+    return torch.sort(order).values
 
 
 class GaussianFit:
@@ -119,6 +163,7 @@ class GaussianFit:
         self.m = {k: torch.zeros_like(getattr(self, k)) for k in PLANES}
         self.v = {k: torch.zeros_like(getattr(self, k)) for k in PLANES}
         self._reset_statistics()
+        self.reset_importance()
         # 3DGS's percent_dense x scene extent: the default scale_threshold of densify_and_prune
         centre = means.mean(dim=0, keepdim=True) if n else means
         self.extent = float(1.1 * (means - centre).norm(dim=1).max()) if n else 1.0
@@ -307,6 +352,7 @@ class GaussianFit:
             self.v = {name: move(self.v[name], _lib.DENSIFY_ZERO_NEW) for name in PLANES}
         self._set(*(new[name] for name in PLANES))
         self._reset_statistics()
+        self.reset_importance()
         self._frame = None
         self.filter_3d = None  # (it belonged to the old rows: update_filter_3d() again)
         return {"pruned": int(counts[0]), "kept": int(counts[1]), "cloned": int(counts[2]), "split": int(counts[3]), "n": k}
@@ -365,6 +411,7 @@ class GaussianFit:
                 check(cx.lib.splat_mcmc_apply(cx.ctx, targets.data_ptr(), sources.data_ptr(), counts.data_ptr(), n, draws, n, float(min_opacity),
                                               C.byref(pl)), cx.ctx)
                 drawn = int((counts[:n] > 0).sum())
+        self.reset_importance()
         self._frame = None
         self.filter_3d = None  # (moved rows: update_filter_3d() again)
         return {"dead": dead, "alive": alive, "relocated": draws, "sources": drawn}
@@ -402,9 +449,98 @@ class GaussianFit:
             self.grad_accum, self.denom, self.max_radius, self.visible = (grown(x) for x in (self.grad_accum, self.denom, self.max_radius,
                                                                                              self.visible))
         self._set(*(new[name] for name in PLANES))
+        self.reset_importance()
         self._frame = None
         self.filter_3d = None  # (new rows: update_filter_3d() again)
         return {"added": k, "n": n + k}
+
+    # ---- importance: what the training views see of every splat (include/splat.h, "Contribution of every splat to a frame") ----
+
+    def reset_importance(self):
+        """Forget the views accumulated so far (the planes are allocated by the next accumulate_importance)."""
+        self._importance = None
+        self.importance_views = 0
+
+    def accumulate_importance(self, camera_or_uniforms, width, height, pixel_weight=None, min_weight=0.0):
+        """Score one view: autograd.contribution of the frame render() would draw from this camera, added into the fit's three
+        importance planes (hit count, largest blend weight, summed weight in units of 2^-24).  pixel_weight (H, W) in [0, 1]
+        masks pixels; a pair counts as a hit when its weight is at least min_weight.  No gradient, no image, and the pending
+        frame of render() is left alone.  Returns the number of views accumulated."""
+        torch = AG._t()
+        with torch.no_grad():
+            u = AG._uniforms(camera_or_uniforms, width, height)
+            scales, opacity = self._activated()
+            if self.antialiased:
+                rec, rho, aux = AG.project_ellipsoids(u, self.means, scales, self.rotations, antialiased=True)
+            else:
+                rec, aux = AG.project_ellipsoids(u, self.means, scales, self.rotations)
+                rho = None
+            col = AG.sh_colors(u[16:19], self.means, self.sh, self.degree, opacity)
+            if rho is not None:
+                col = AG.compensate_opacity(col, rho)
+            self._importance = AG.contribution(rec, col, aux, width, height, pixel_weight=pixel_weight, min_weight=min_weight,
+                                               out=self._importance)
+        self.importance_views += 1
+        return self.importance_views
+
+    def importance(self, kind="max"):
+        """(n,) float32 score from the views accumulated so far; a splat no view scored gets 0.
+          "max"            the largest blend weight T alpha over all pixels of all views (RadSplat)
+          "sum"            the summed blend weight: weight_sum 2^-24, formed in float64 and rounded once (Mini-Splatting)
+          "hits"           the number of (pixel, view) pairs with a weight of at least min_weight
+          "lightgaussian"  hits x opacity x clamp(V / V90, 0, 1)^0.1, V the product of the activated scales and V90 its 90th
+                           percentile over the cloud (LightGaussian's global significance, with its volume power 0.1)
+        SplatError when no view was accumulated."""
+        torch = AG._t()
+        if self._importance is None or self.importance_views == 0:
+            raise SplatError(-5, "GaussianFit.importance: call accumulate_importance() first")
+        hits, wmax, wsum = self._importance
+        with torch.no_grad():
+            if kind == "max":
+                return wmax.clone()
+            if kind == "sum":
+                return (wsum.double() * 2.0 ** -24).float()
+            count = (hits.long() & 0xFFFFFFFF).double()  # (the uint32 bits)
+            if kind == "hits":
+                return count.float()
+            if kind == "lightgaussian":
+                scales, opacity = self._activated()
+                vol = scales.double().prod(dim=1)
+                v90 = torch.quantile(vol, 0.9) if self.n else vol.sum()
+                vnorm = torch.clamp(vol / v90, 0.0, 1.0) ** 0.1
+                return (count * opacity.double() * vnorm).float()
+        raise SplatError(-1, f"importance: kind must be max, sum, hits or lightgaussian, not {kind!r}")
+
+    def prune_by_importance(self, threshold=None, keep=None, kind="max"):
+        """Keep the splats importance(kind) selects (select_by_importance: score >= threshold, or the `keep` highest scores - an int
+        is a count, a float in (0, 1] a fraction of n rounded down, at least 1 - with ties going to the lower index), in index
+        order.  All five parameter planes and both Adam moments are compacted with splat_densify_rows (copies: every row is a
+        kept original); the density statistics, the importance planes, the 3D filter and the pending frame are reset.  One host
+        sync, for the count.  Returns {"pruned", "kept", "n"}.  SplatError when no view was accumulated."""
+        torch = AG._t()
+        score = self.importance(kind)
+        n = self.n
+        with torch.no_grad():
+            rows = select_by_importance(score, threshold=threshold, keep=keep).to(torch.int32).contiguous()  # (kind 0: the kept index)
+            k = int(rows.shape[0])  # (the host sync)
+            cx = AG._context(self.means)
+            dev = self.means.device
+
+            def move(src):
+                out = torch.empty((k,) + tuple(src.shape[1:]), device=dev, dtype=torch.float32)
+                if k:
+                    check(cx.lib.splat_densify_rows(cx.ctx, rows.data_ptr(), k, src.data_ptr(), out.data_ptr(),
+                                                    src.shape[1] if src.dim() == 2 else 1, _lib.DENSIFY_COPY), cx.ctx)
+                return out
+            new = {name: move(getattr(self, name)) for name in PLANES}
+            self.m = {name: move(self.m[name]) for name in PLANES}
+            self.v = {name: move(self.v[name]) for name in PLANES}
+        self._set(*(new[name] for name in PLANES))
+        self._reset_statistics()
+        self.reset_importance()
+        self._frame = None
+        self.filter_3d = None  # (it belonged to the old rows: update_filter_3d() again)
+        return {"pruned": n - k, "kept": k, "n": k}
 
     def inject_noise(self, noise_lr=5e5, lr_means=None, seed=None):
         """3DGS-MCMC's exploration term, after every step(): means += Sigma xi g noise_lr lr_means, xi standard normal, g a gate

@@ -418,6 +418,15 @@ FN(composite_backward_det) { /* (ctx, cfg[8], colorOpacity, cStride, records, pr
     return check(env, x, splat_composite_backward_det(x, &cfg, col, cs, rec, proj, idx, cnt, off, pairs, w, h, gimg, n, grec, gcol, z, zs, gdimg, gz,
                                                       ws, wb), mk_undefined(env));
 }
+FN(composite_contribution) { /* (ctx, cfg[8], colorOpacity, cStride, records, indices, counts, offsets, W, H, pixelWeight|null, minWeight, n, hits|null, weightMax|null, weightSum|null) */
+    ARGS(16); splat_ctx *x = arg_external(&c, 0); splat_composite_cfg cfg; fill_cfg(&c, 1, &cfg);
+    void *col = arg_dptr(&c, 2); uint32_t cs = (uint32_t)arg_number(&c, 3); void *rec = arg_dptr(&c, 4);
+    void *idx = arg_dptr(&c, 5), *cnt = arg_dptr(&c, 6), *off = arg_dptr(&c, 7);
+    uint32_t w = (uint32_t)arg_number(&c, 8), h = (uint32_t)arg_number(&c, 9); void *pw = arg_dptr(&c, 10);
+    float mw = (float)arg_number(&c, 11); uint32_t n = (uint32_t)arg_number(&c, 12);
+    void *hits = arg_dptr(&c, 13), *wmax = arg_dptr(&c, 14), *wsum = arg_dptr(&c, 15); BAIL;
+    return check(env, x, splat_composite_contribution(x, &cfg, col, cs, rec, idx, cnt, off, w, h, pw, mw, n, hits, wmax, wsum), mk_undefined(env));
+}
 FN(project_ellipsoid_backward) { /* (ctx, Float32Array(22), positions, posStride, scales, scaleStride, rotations, rotStride, n, gradRecords, gradPositions, gradScales, gradRotations) */
     ARGS(13); splat_ctx *x = arg_external(&c, 0); size_t ub = 0; float *u = arg_hostbuf(&c, 1, &ub);
     void *pos = arg_dptr(&c, 2); uint32_t ps = (uint32_t)arg_number(&c, 3); void *scl = arg_dptr(&c, 4); uint32_t ss = (uint32_t)arg_number(&c, 5);
@@ -872,7 +881,7 @@ static napi_value init(napi_env env, napi_value exports) {
         EXPORT(point_frame), EXPORT(project_ellipsoid), EXPORT(sh_colors), EXPORT(render_frame_ellipsoids),
         EXPORT(composite_backward), EXPORT(project_ellipsoid_backward), EXPORT(sh_colors_backward),
         EXPORT(composite_aov_depth), EXPORT(composite_backward_depth), EXPORT(project_ellipsoid_backward_depth),
-        EXPORT(composite_backward_det_workspace_bytes), EXPORT(composite_backward_det),
+        EXPORT(composite_backward_det_workspace_bytes), EXPORT(composite_backward_det), EXPORT(composite_contribution),
         EXPORT(project_ellipsoid_backward_camera), EXPORT(sh_colors_backward_camera),
         EXPORT(image_loss_workspace_bytes), EXPORT(image_loss), EXPORT(image_loss_backward),
         EXPORT(adam_step), EXPORT(density_accumulate), EXPORT(densify_plan_workspace_bytes), EXPORT(densify_plan),

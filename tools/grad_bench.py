@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Gradients of ellipsoid frames (GPU box only): python tools/grad_bench.py [--depth] [--deterministic] [--antialiased] [--camera | --loss | --optimizer] [C1,C2] [K] [R]
+"""Gradients of ellipsoid frames (GPU box only): python tools/grad_bench.py [--depth] [--deterministic] [--antialiased] [--importance] [--camera | --loss | --optimizer] [C1,C2] [K] [R]
 
 tools/ellipsoid_bench.py's scenes and method (the scene's positions, sigma = radius / 2 per axis times a random factor in
 [e^-0.3, e^0.3], random rotations, SH of degree 3 with the scene's opacity; R rounds of K calls per kind, kinds alternating
@@ -26,6 +26,12 @@ written slot once out and once in, 36 or 40 B each, plus the 16 B table rows - t
 project_ellipsoids(antialiased=True) and the opacity column times rho (forward_aa), its backward (backward_aa), and
 splat_project_ellipsoid_backward_aa alone with a random grad_rho and no camera sums (project_backward_aa) beside
 splat_project_ellipsoid_backward; their ratios to the classic path.
+
+--importance adds the per-splat contribution pass beside the composite backward, alternating in the same rounds:
+splat_composite_contribution alone with all three outputs and no mask (composite_contribution: hit count, largest and summed
+blend weight per splat, integer atomics), and the one thing the library offered for the summed weight before it,
+splat_composite_backward with an upstream of ones in (r, g, b) and zero in alpha, whose colour column is that sum
+(composite_backward_ones: two walks, nine float sums per entry, float atomics); their ratio.
 
 --camera adds the camera gradients: splat_project_ellipsoid_backward_camera without and with grad_depth (all of its launches:
 the per-splat kernel with the per-wave sums, then k_camera_sum_slices above 1024 partials, then k_camera_sum) beside
@@ -117,8 +123,9 @@ def torch_camera_terms(U, pos, scl, rot, g, W, H):
     return torch.stack(terms, dim=1).sum(dim=0)
 
 
-argv = [a for a in sys.argv[1:] if a not in ("--depth", "--camera", "--loss", "--optimizer", "--deterministic", "--antialiased")]
+argv = [a for a in sys.argv[1:] if a not in ("--depth", "--camera", "--loss", "--optimizer", "--deterministic", "--antialiased", "--importance")]
 aa_too = "--antialiased" in sys.argv[1:]
+importance_too = "--importance" in sys.argv[1:]
 det_too = "--deterministic" in sys.argv[1:]
 optimizer_only = "--optimizer" in sys.argv[1:]
 depth_too = "--depth" in sys.argv[1:]
@@ -536,6 +543,19 @@ for name in names:
         if depth_too:
             work["composite_backward_det_depth"] = det_entry(True)
 
+    if importance_too:
+        ones4 = torch.zeros((h, w, 4), device="cuda")
+        ones4[..., :3] = 1.0
+        hits, wmax = torch.zeros(n, dtype=torch.int32, device="cuda"), torch.zeros(n, device="cuda")
+        wsum = torch.zeros(n, dtype=torch.int64, device="cuda")
+        work.update({
+            "composite_contribution": lambda: lib.splat_composite_contribution(cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr(), idx, cnt, off,
+                                                                               w, h, None, 0.0, n, hits.data_ptr(), wmax.data_ptr(),
+                                                                               wsum.data_ptr()),
+            "composite_backward_ones": lambda: lib.splat_composite_backward(cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr(), idx, cnt, off, w,
+                                                                            h, ones4.data_ptr(), n, grec.data_ptr(), gcol.data_ptr()),
+        })
+
     if camera_too:
         ut = torch.tensor(u, device="cuda", requires_grad=True)
         gu, ge = torch.empty(24, device="cuda"), torch.empty(4, device="cuda")
@@ -645,6 +665,9 @@ for name in names:
             extra.update({"det_workspace_bytes_depth": det_bytes[1],
                           "det_gather_floor_ms_depth": round((2 * 40 * written + 16 * tiles) / COPY_RATE * 1e3, 4),
                           "composite_backward_det_depth_over_atomic": round(med["composite_backward_det_depth"] / med["composite_backward_depth"], 3)})
+    if importance_too:
+        _lib.check(work["composite_contribution"](), cx.ctx)
+        extra.update({"composite_contribution_over_backward_ones": round(med["composite_contribution"] / med["composite_backward_ones"], 3)})
     if aa_too:
         extra.update({f"{a}_over_{b}": round(med[a] / med[b], 3) for a, b in (
             ("forward_aa", "forward"), ("backward_aa", "backward"), ("project_backward_aa", "project_backward"))})
