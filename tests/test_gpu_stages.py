@@ -1062,6 +1062,36 @@ def test_long_class_launch_is_skipped_only_while_no_tile_needs_it():
     assert p.returncode == 0 and "long_class_skip ok: 6 frames" in p.stdout, p.stdout[-2000:] + p.stderr[-3000:]
 
 
+@pytest.mark.parametrize("short", [8, 12, 16])
+def test_each_short_class_sorts_an_outgrown_tile_as_the_last_class(short):
+    """The same sequence with the short class forced (SPLAT_TILE_SORT_SHORT, read once per process): the piled frame is sorted
+    by k_tile_sort<_, 8 | 12 | 16, true> alone, whose global-memory passes take the outgrown tile in chunks of
+    min(K, 16) * 256 pairs — more than two of them and a ragged last one (asserted from the oracle's counts in the child).
+    The launch counts 2, 1, 1, 2, 2, 1 hold for every class."""
+    import subprocess
+    import sys
+    if os.environ.get("SPLAT_BIN_SYNC") == "1":
+        pytest.skip("SPLAT_BIN_SYNC=1: no frame is sync-free")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, SPLAT_LIB_PATH=_lib.HOOKS_LIB_PATH, SPLAT_TILE_SORT_SHORT=str(short))
+    p = subprocess.run([sys.executable, os.path.join(root, "tests", "hooks_child.py"), "long_class_skip"], cwd=root, env=env,
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert p.returncode == 0 and f"long_class_skip ok: 6 frames, short class {short} (forced)" in p.stdout, p.stdout[-2000:] + p.stderr[-3000:]
+
+
+def test_one_launch_sorts_every_tile_up_to_4200_tiles_and_two_beyond():
+    """tile_sort_launch's class boundary, on the list-length edge scene of tests/tile_lists.py: 70 x 60 tiles take one launch
+    (k_tile_sort<_, 24, true> for every tile), 71 x 60 take two, with the oracle's lists and no order fault both times."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, SPLAT_LIB_PATH=_lib.HOOKS_LIB_PATH)
+    env.pop("SPLAT_TILE_SORT_SHORT", None)
+    p = subprocess.run([sys.executable, os.path.join(root, "tests", "hooks_child.py"), "class_boundary"], cwd=root, env=env,
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert p.returncode == 0 and "class_boundary ok: 4200 tiles 1 launch, 4260 tiles 2 launches" in p.stdout, p.stdout[-2000:] + p.stderr[-3000:]
+
+
 def device_lib_has_hooks():
     return bool(getattr(_lib.load(), "has_hooks", False))
 
