@@ -48,6 +48,47 @@ def mean_sq_f64(points):
     return b.sum(axis=1) / 3.0, b
 
 
+AXIS_BITS, BLOCK, GROUP, NEAR = 21, 64, 64, 64  # knn.hip's KNN_AXIS_BITS, KB, KG, KNN_NEAR
+
+
+def morton_order(points):
+    """(order, codes): k_knn_codes and the two stable sorts restated in float64.  codes[i] is point i's 63-bit code, the box of
+    the finite points cut into 2^21 cells per axis, bit k of axis a's cell at bit 3 k + a, 2^63 - 1 for a point with a non-finite
+    coordinate; order[pos] is the point at sorted position pos, ties by index.  The search's results do not depend on the order:
+    the tests use it to prove that a cloud reaches the blocks and groups it is there for, and for nothing else."""
+    p = np.asarray(points, F)[:, :3]
+    n = p.shape[0]
+    fin = np.isfinite(p).all(axis=1)
+    codes = np.full(n, 0x7fffffffffffffff, np.uint64)
+    if fin.any():
+        q = p[fin].astype(np.float64)
+        lo, ext = q.min(axis=0), q.max(axis=0) - q.min(axis=0)
+        cells = float(1 << AXIS_BITS)
+        code = np.zeros(q.shape[0], np.uint64)
+        for a in range(3):
+            t = (q[:, a] - lo[a]) / ext[a] * cells if ext[a] > 0.0 else np.zeros(q.shape[0])
+            cell = np.clip(t, 0.0, cells - 1.0).astype(np.uint64)  # (truncation, as the kernel's cast)
+            for k in range(AXIS_BITS):
+                code |= ((cell >> np.uint64(k)) & np.uint64(1)) << np.uint64(3 * k + a)
+        codes[fin] = code
+    return np.argsort(codes, kind="stable"), codes
+
+
+def block_of(order):
+    """block[i]: the 64-point block of the sorted array that point i lies in."""
+    block = np.empty(order.shape[0], np.int64)
+    block[order] = np.arange(order.shape[0]) // BLOCK
+    return block
+
+
+def second_far_trip(block, rows, neighbours):
+    """Which of the queries `rows`, with neighbour indices `neighbours` (len(rows), 3), have a neighbour that only the search's
+    second trip over the groups can find: one in a block more than NEAR blocks from the query's own (so not met in the near
+    rounds) and in a group of index 64 or higher (so not in the first trip's 64 groups).  `block` is block_of(order)."""
+    nb, qb = block[np.asarray(neighbours, np.int64)], block[np.asarray(rows, np.int64)][:, None]
+    return ((np.abs(nb - qb) > NEAR) & (nb // GROUP >= 64)).any(axis=1)
+
+
 # ---- scenes (seeds fixed here) -------------------------------------------------------------------------------------------------
 
 def uniform(n, seed, lo=-1.0, hi=1.0):
@@ -104,6 +145,28 @@ def pruning_scene(name, n=32768):
         p[:8] = rng.uniform(-1000, 1000, (8, 3)).astype(F)
     elif name != "cube":
         raise KeyError(name)
+    return p
+
+
+FAR_N, FAR_HEAD = 300000, 262144  # 4688 blocks in 74 groups; 64 groups of 64 blocks of 64 points, the first trip's reach
+
+
+def nonfinite_tail():
+    """(points, rows): uniform(FAR_N, 21) with 6000 rows (default_rng(22)) given a NaN, a +inf or a -inf in one coordinate.  They
+    sort to the end: the last 94 blocks, among them all of group 72, hold no finite point."""
+    p = uniform(FAR_N, 21)
+    rng = np.random.default_rng(22)
+    rows = np.sort(rng.choice(FAR_N, 6000, replace=False))
+    p[rows, rng.integers(0, 3, rows.size)] = np.array([np.nan, np.inf, -np.inf], F)[np.arange(rows.size) % 3]
+    return p, rows
+
+
+def shifted_tail():
+    """Rows below FAR_HEAD uniform in [-1, 1)^3, the rows from there on uniform in [9, 11) x [-1, 1)^2 (default_rng(23)): the
+    first trip of k_knn_bbox's 1024 workgroups sees x below 1 only."""
+    rng = np.random.default_rng(23)
+    p = rng.uniform(-1, 1, (FAR_N, 3)).astype(F)
+    p[FAR_HEAD:, 0] = rng.uniform(9, 11, FAR_N - FAR_HEAD).astype(F)
     return p
 
 

@@ -132,3 +132,71 @@ def noise(log_scales, rotations, logits, scale, step, seed):
     delta = np.einsum("nij,nj->ni", cov, xi) * (g * s)[:, None]
     magnitude = np.exp(2.0 * ls).max(axis=1) * np.sqrt((xi * xi).sum(axis=1)) * g * s
     return delta, magnitude, g, o
+
+
+# ---- clouds past 256 block sums: the second and third trip of the 64-bit scan of the block sums --------------------------------
+
+SCAN_TILE, SCAN_TRIP = 2048, 256 * 2048  # weights per block sum; weights per trip of k_scan64_sums (256 block sums): 524 288
+FAR_SIZES = (SCAN_TRIP, SCAN_TRIP + 1, 1229577)  # 256 block sums (one trip, full), 257, 601 (three trips, the last partial)
+FAR_CASES = tuple(f"n={n}" for n in FAR_SIZES) + ("saturated", "alive past two trips", "alive in the first block")
+
+
+def normal_logits(n, seed):
+    return np.random.default_rng(seed).normal(-1.0, 2.5, n).astype(np.float32)
+
+
+def off_integers(logits, margin=1e-6):
+    """(logits, moved): the logits with every finite one whose 2^24 o lies within `margin` of an integer replaced by the next
+    float32 above it, until none is left.  Among a million random logits about two lie that close (2 margin each), and floor()
+    of such a value is the one thing two correct implementations may disagree on (tests/test_gpu_mcmc.py, "sample"): the
+    clouds are kept clear of it instead of excusing it.  One float32 step moves 2^24 o by thousands of margins."""
+    logits = np.array(logits, np.float32)
+    moved = 0
+    while True:
+        x = scaled_opacity(logits)
+        near = np.flatnonzero(np.isfinite(logits) & (np.abs(x - np.round(x)) < margin))
+        if near.size == 0:
+            return logits, moved
+        logits[near] = np.nextafter(logits[near], np.float32(np.inf))
+        moved += near.size
+
+
+def far_case(name):
+    """(logits, (lo, hi) of the rows that may be alive) of the clouds of FAR_CASES.  The sized ones are normal_logits(n, 100 + n);
+    `saturated`: every logit 17, every weight 2^24 - 1; the last two: N(1, 1) logits on [2^20, n) or on [0, 2048) and -20 (dead,
+    weight 0) everywhere else, so that the first two trips' totals, or every block sum after the first, are 0."""
+    n = FAR_SIZES[2]
+    if name.startswith("n="):
+        n = int(name[2:])
+        return off_integers(normal_logits(n, 100 + n))[0], (0, n)
+    if name == "saturated":
+        return np.full(n, 17.0, np.float32), (0, n)
+    lo, hi = {"alive past two trips": (2 * SCAN_TRIP, n), "alive in the first block": (0, SCAN_TILE)}[name]
+    logits = np.full(n, -20.0, np.float32)
+    logits[lo:hi] = np.random.default_rng(300 + lo).normal(1.0, 1.0, hi - lo).astype(np.float32)
+    return off_integers(logits)[0], (lo, hi)
+
+
+def far_case_regime(name, logits, alive, sources, min_opacity):
+    """Asserts, from the restatement alone, that a cloud of FAR_CASES with the `sources` of its 5000 added draws reaches what it
+    is there for; returns (cumulative weight at the end of the first trip, total weight, draws with a source past the first
+    trip).  The draws past the first trip are asked for from n = 1 229 577 on: at 524 289 ONE splat lies past it."""
+    n = len(logits)
+    q, dead, w = weights(logits, min_opacity)
+    first, total = int(w[:SCAN_TRIP].sum()), int(w.sum())
+    past = int((sources >= SCAN_TRIP).sum())
+    blocks = -(-n // SCAN_TILE)
+    lo, hi = alive
+    assert not w[:lo].any() and not w[hi:].any() and ((sources >= lo) & (sources < hi)).all(), f"{name}: a source outside [{lo}, {hi})"
+    if name.startswith("n="):
+        assert blocks == {FAR_SIZES[0]: 256, FAR_SIZES[1]: 257, FAR_SIZES[2]: 601}[n]
+        assert first > 2 ** 32, f"{name}: the carry out of the first trip fits 32 bits"
+        if n == FAR_SIZES[2]:
+            assert past >= 1000, f"{name}: {past} of {len(sources)} draws have a source past the first trip"
+    elif name == "saturated":
+        assert (q == 2 ** 24 - 1).all() and total == n * (2 ** 24 - 1) and total > 2e13 and past >= 1000
+    elif name == "alive past two trips":
+        assert int(w[:2 * SCAN_TRIP].sum()) == 0 and total > 2 ** 32 and past == len(sources)
+    else:
+        assert int(w[SCAN_TILE:].sum()) == 0 and first == total > 2 ** 32 and past == 0 and blocks == 601
+    return first, total, past

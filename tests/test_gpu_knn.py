@@ -4,7 +4,8 @@ against the restatement of tests/knn_ref.py, with the sentinel-tail buffers of t
 Bounds (none taken from the code under test):
   mean_sq      EXACT: the bits of the restatement, on every scene, size and stride.  The contract is a function of the input
                alone, every operator one rounding, and a skipped block provably cannot lower a third distance: there is nothing
-               to tolerate.
+               to tolerate.  Past 262 144 points (the far loop's and the box's second trip) the reference over every row is a
+               brute force in torch on the device, itself held to the restatement's bits on 1024 rows or more of each cloud.
   evaluations  <= n / 4 per query: a condition that tells a search that prunes from one that does not (brute force performs
                n - 1 per query; a prototype with 10-bit Morton codes 27 207 on the cloud with eight outliers), not a measurement.
   from_points  log_scales within 1e-6 relative of 0.5 log(max(ref, 1e-7)) in float64: the binary32 sqrt and log each round to
@@ -127,6 +128,132 @@ def test_pruning(device, name):
     assert_exact(got[rows], want, f"{name}, {rows.size} rows")
     assert np.isfinite(got).all()
     assert per_query <= n / 4
+
+
+# ---- past 64 groups: the far loop's and the box's second trip ---------------------------------------------------------------------
+# k_knn_search's far loop takes 64 groups (of 64 blocks of 64 points) per trip and k_knn_bbox's grid is capped at 1024 workgroups of
+# 256: both make a second trip only above n = 262 144.  KR.mean_sq cannot serve every row there (about 6 s per 1024 rows on a CPU), so
+# the reference over ALL rows is a brute force in torch on the device, which is itself held to KR.mean_sq's bits on PIN_ROWS rows of
+# every cloud.  It shares nothing with the kernel: no sort, no boxes, no pruning.
+
+PIN_ROWS = 1024
+BRUTE_CHUNK = 512  # query rows per pass: three (512, n) float32 temporaries and topk's, under 2 GB at n = 300 000
+
+
+def brute_force(points, dev="cuda"):
+    """(distances (n, 3) float32 ascending, neighbours (n, 3) int64): the three nearest candidates of every row by the header's
+    rule, each operator one eager float32 op (one rounding, no contraction): dx dx, dy dy, their sum, dz dz, the final sum;
+    non-finite distances +inf, the query's own index out."""
+    p = torch.from_numpy(np.ascontiguousarray(np.asarray(points, F)[:, :3])).to(dev)
+    n = p.shape[0]
+    need = 5 * BRUTE_CHUNK * n * 4 + (64 << 20)
+    free = torch.cuda.mem_get_info()[0] if dev == "cuda" else need
+    if free < need:
+        pytest.skip(f"the brute-force reference needs {need >> 20} MB of device memory, {free >> 20} MB are free")
+    x, y, z = (p[:, a].contiguous() for a in range(3))
+    dist = torch.empty((n, 3), device=dev, dtype=torch.float32)
+    nbr = torch.empty((n, 3), device=dev, dtype=torch.int64)
+    for s in range(0, n, BRUTE_CHUNK):
+        e = min(s + BRUTE_CHUNK, n)
+        dx, dy, dz = x[s:e, None] - x[None, :], y[s:e, None] - y[None, :], z[s:e, None] - z[None, :]
+        dx.mul_(dx)   # dx dx
+        dy.mul_(dy)   # dy dy
+        dx.add_(dy)   # dx dx + dy dy
+        dz.mul_(dz)   # dz dz
+        dx.add_(dz)   # (dx dx + dy dy) + dz dz
+        assert dx.dtype == torch.float32
+        d = dx.nan_to_num_(nan=float("inf"), posinf=float("inf"), neginf=float("inf"))
+        r = torch.arange(s, e, device=dev)
+        d[r - s, r] = float("inf")  # j != i
+        b, j = torch.topk(d, 3, dim=1, largest=False)
+        b, o = torch.sort(b, dim=1)
+        dist[s:e], nbr[s:e] = b, torch.gather(j, 1, o)
+    return dist.cpu().numpy(), nbr.cpu().numpy()
+
+
+def brute_mean_sq(dist):
+    """The mean in NumPy, as KR.mean_sq forms it: the division never goes through a device kernel."""
+    return ((dist[:, 0] + dist[:, 1]) + dist[:, 2]) / F(3.0)
+
+
+def far_reference(points, label, regime_rows=()):
+    """(mean_sq of every row, neighbours, order, codes, second-trip queries) of a cloud past 64 groups: the device brute force,
+    pinned to KR.mean_sq on the rows a case is there for (every query that only the second far trip serves, and `regime_rows`),
+    topped up with seeded random rows: at least 256 of those, and PIN_ROWS rows in all."""
+    n = points.shape[0]
+    dist, nbr = brute_force(points)
+    want = brute_mean_sq(dist)
+    order, codes = KR.morton_order(points)
+    fin = np.flatnonzero(np.isfinite(want))
+    second = fin[KR.second_far_trip(KR.block_of(order), fin, nbr[fin])]
+    regime = np.unique(np.concatenate([second, np.asarray(regime_rows, np.int64)]))
+    others = np.random.default_rng(41).choice(np.setdiff1d(np.arange(n), regime), max(PIN_ROWS - regime.size, 256), replace=False)
+    rows = np.sort(np.concatenate([regime, others]))
+    pin = KR.mean_sq(points, rows=rows, chunk=4)
+    bad = np.flatnonzero(bits(want[rows]) != bits(pin))
+    print(f"{label}: the device brute force against KR.mean_sq on {rows.size} rows ({regime.size} regime rows and {others.size} random ones): "
+          f"{bad.size} differ; {second.size} queries served by the second far trip")
+    assert np.unique(rows).size == rows.size >= PIN_ROWS and bad.size == 0, \
+        f"{label}: the REFERENCE (torch brute force) differs from KR.mean_sq on {bad.size} rows, first {rows[bad[:4]]}: not the kernel"
+    return want, nbr, order, codes, second
+
+
+@pytest.mark.parametrize("n", [KR.FAR_HEAD, KR.FAR_HEAD + 1, KR.FAR_N])
+def test_far_groups_uniform(device, n):
+    """262 144 points are 64 groups and 1024 workgroups of k_knn_bbox: the last size with one trip of either loop.  262 145 is
+    the boundary.  At 300 000 (4688 blocks, 74 groups) at least 1000 queries have a neighbour that only the second far trip
+    can reach (KR.second_far_trip, from the reference's neighbours and the restated order): a far loop that stopped after 64
+    groups would leave those rows too large.  Every row is compared."""
+    p = KR.uniform(n, 21)
+    want, _, order, _, second = far_reference(p, f"cube n={n}")
+    groups = -(-(-(-n // KR.BLOCK)) // KR.GROUP)
+    got, ev = knn_gpu(p, 3)
+    print(f"cube n={n}: {groups} groups, {ev / n:.1f} evaluations per query (cap n / 4 = {n // 4})")
+    assert groups == {KR.FAR_HEAD: 64, KR.FAR_HEAD + 1: 65, KR.FAR_N: 74}[n]
+    if n == KR.FAR_N:
+        assert second.size >= 1000, f"only {second.size} queries need the second far trip"
+    assert_exact(got, want, f"cube n={n}")
+    assert np.isfinite(got).all() and ev / n <= n / 4
+
+
+def test_far_groups_non_finite_tail(device):
+    """6000 points with a NaN, +inf or -inf coordinate sort to the end: the last blocks hold nobody, and a whole group of the
+    second trip (index 64 or higher) is empty boxes.  Their rows are +inf, every other row is the reference's bits."""
+    p, rows = KR.nonfinite_tail()
+    want, _, order, _, _ = far_reference(p, "non-finite tail", regime_rows=rows[:256])
+    block = KR.block_of(order)
+    blocks = -(-p.shape[0] // KR.BLOCK)
+    fin = np.isfinite(p).all(axis=1)
+    assert np.array_equal(np.flatnonzero(~fin), rows)
+    held = np.bincount(block[fin] // KR.GROUP, minlength=-(-blocks // KR.GROUP))
+    empty = np.flatnonzero(held == 0)
+    print(f"non-finite tail: the finite points end in block {int(block[fin].max())} of {blocks}; groups without a finite point: {empty}")
+    assert empty.size >= 1 and empty.min() >= 64
+    got, ev = knn_gpu(p, 3)
+    print(f"non-finite tail: {ev / p.shape[0]:.1f} evaluations per query")
+    assert np.isposinf(got[rows]).all() and np.isfinite(got[fin]).all()
+    assert_exact(got, want, "non-finite tail")
+
+
+def test_far_box_shifted_tail(device):
+    """The rows from 262 144 on lie at x in [9, 11): the first trip of k_knn_bbox's grid-stride loop sees x < 1 only, the second
+    brings the cloud's true extent.  The box feeds the codes, and the codes only order the visits: a wrong box cannot change
+    mean_sq, it changes `evaluations`.  So the check is metamorphic: the same cloud with its rows reversed puts the shifted rows
+    into the first trip.  With all codes distinct (asserted) the sorted array, the blocks and every wave's work are the same
+    in both, and the counter is an integer sum: the two counts must be equal, and mean_sq equal under the permutation."""
+    p = KR.shifted_tail()
+    n = p.shape[0]
+    want, _, _, codes, _ = far_reference(p, "shifted tail", regime_rows=np.arange(KR.FAR_HEAD, KR.FAR_HEAD + 256))
+    assert np.unique(codes).size == n, "two points share a Morton code: the reversed cloud may sort its ties differently"
+    assert p[:KR.FAR_HEAD, 0].max() < 1 and p[KR.FAR_HEAD:, 0].min() >= 9
+    fwd, ev_fwd = knn_gpu(p, 3)
+    rev, ev_rev = knn_gpu(np.ascontiguousarray(p[::-1]), 3)
+    print(f"shifted tail: {ev_fwd / n:.1f} evaluations per query forward, {ev_rev / n:.1f} reversed (cap n / 4 = {n // 4})")
+    assert_exact(fwd, want, "shifted tail, forward")
+    assert_exact(rev[::-1], want, "shifted tail, reversed")
+    assert np.array_equal(bits(rev[::-1]), bits(fwd))
+    assert ev_fwd == ev_rev, f"evaluations {ev_fwd} forward and {ev_rev} reversed: the two clouds were not ordered alike"
+    assert ev_fwd / n <= n / 4
 
 
 def test_two_calls_give_the_same_bits(device):

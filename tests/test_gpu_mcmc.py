@@ -5,7 +5,8 @@ Bounds (none taken from the code under test):
   sample   targets, sources, counts and the host words EXACT.  The one place two correct implementations may differ is
            floor(2^24 sigmoid(logit)) between two binary64 exp()s, which can happen only within ~1e-9 of an integer: the tests
            assert on the REFERENCE that every input's 2^24 o is at least 1e-6 from an integer (seeds chosen on the CPU so that it
-           holds), and drop nothing.
+           holds), and drop nothing.  Among the million logits of a cloud past 256 block sums two or three do lie that close:
+           MR.off_integers moves those to the next float32, and the same assertion then holds there too.
   apply    copies bit for bit, moments exact zeros or kept bits, new logits and log-scales within 1 binary32 ulp (taken at
            max(|x|, 2^-10)) of the float64 restatement: the binary64 error of the sum, below 1e-12, can only flip the final
            rounding.
@@ -64,12 +65,15 @@ def sample_gpu(logits, mode, n_draws, seed, min_opacity=MIN_OPACITY):
     return t[:draws], s[:draws], _host(*Cn, np.uint32, (max(n, 1),))[:n], tuple(int(x) for x in words)
 
 
-def check_sample(logits, label, seed=SEED, min_opacity=MIN_OPACITY, add=None):
+def check_sample(logits, label, seed=SEED, min_opacity=MIN_OPACITY, add=None, modes=(MR.RELOCATE, MR.ADD), known=None):
+    """Both modes (or `modes`) against MR.sample; known: {mode: MR.sample's result} where the caller has formed it already."""
     d = assert_away_from_integers(logits, label)
     n = logits.shape[0]
     out = {}
     for mode, k in ((MR.RELOCATE, 0), (MR.ADD, n // 20 + 3 if add is None else add)):
-        want = MR.sample(logits, mode, k, seed, min_opacity)
+        if mode not in modes:
+            continue
+        want = known[mode] if known and mode in known else MR.sample(logits, mode, k, seed, min_opacity)
         got = sample_gpu(logits, mode, k, seed, min_opacity)
         name = "relocate" if mode == MR.RELOCATE else "add"
         print(f"{label} {name}: (dead, alive, draws) {got[3]}, reference {want[3]}; {int((got[2] > 0).sum())} sources; "
@@ -81,8 +85,7 @@ def check_sample(logits, label, seed=SEED, min_opacity=MIN_OPACITY, add=None):
     return out
 
 
-def normal_logits(n, seed):
-    return np.random.default_rng(seed).normal(-1.0, 2.5, n).astype(np.float32)
+normal_logits = MR.normal_logits
 
 
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 257, 4097, 70001])
@@ -107,6 +110,31 @@ def test_sample_needs_64_bit_sums(device):
     q, _, _ = MR.weights(full, MIN_OPACITY)
     assert (q == 2 ** 24 - 1).all()
     check_sample(full, "weights 2^24 - 1", add=5000)
+
+
+@pytest.mark.parametrize("name", MR.FAR_CASES)
+def test_sample_past_256_block_sums(device, name):
+    """k_scan64_sums scans the block sums (one per 2048 weights) 256 at a time and carries a 64-bit total from trip to trip: a
+    second trip needs n > 524 288.  MR.far_case's clouds: 256 block sums (one trip, full), 257, and 601 (three trips, the last
+    partial) of normal logits, whose first trip alone sums past 2^32, so the carry needs its high word; every weight 2^24 - 1;
+    and two clouds whose carries are zeros: nobody alive before the third trip, and nobody alive after the first block sum (the
+    first trip's total must still arrive unchanged in the last).  MR.far_case_regime asserts all that, and that at least 1000 of
+    the 5000 added draws have a source past the first trip, from the restatement before the device is asked (the draws from
+    n = 1 229 577 on: at 524 289 one splat lies past the first trip).  Then targets, sources, counts and the host words are
+    MR.sample's, in both modes; the two clouds with more than a million dead splats in the add mode only (their relocation
+    would be a million draws of Python integers, through the same scan)."""
+    logits, alive = MR.far_case(name)
+    n = logits.shape[0]
+    want = MR.sample(logits, MR.ADD, 5000, SEED, MIN_OPACITY)
+    first, total, past = MR.far_case_regime(name, logits, alive, want[1], MIN_OPACITY)
+    print(f"{name}: n = {n}, {-(-n // MR.SCAN_TILE)} block sums; weight up to the end of the first trip {first} = 2^{np.log2(max(first, 1)):.1f}, "
+          f"total {total}; {past} of 5000 added draws have a source past the first trip")
+    modes = (MR.ADD,) if name.startswith("alive") else (MR.RELOCATE, MR.ADD)
+    got = check_sample(logits, name, add=5000, modes=modes, known={MR.ADD: want})
+    s = got["add"][1]
+    assert got["add"][3][2] == 5000 and ((s >= alive[0]) & (s < alive[1])).all()
+    if name == "saturated":
+        assert got["relocate"][3] == (0, n, 0)
 
 
 def boundary_logits(min_opacity):
@@ -280,7 +308,8 @@ def noise_gpu(planes, step, seed, offset=0, scale=NOISE_SCALE):
     return _host(*D["means"], np.float32, (n, 3))
 
 
-@pytest.mark.parametrize("n", [1, 65, 4097])
+# (n & 3 = 1, 0, 2, 3 leftover splats after the vector kernel's whole fours; n = 1 takes the scalar kernel, n = 4 is the first vector size)
+@pytest.mark.parametrize("n", [1, 4, 6, 7, 8, 65, 4096, 4097, 4098, 4099])
 def test_noise_against_float64(device, n):
     logits = normal_logits(n, 200 + n)
     if n == 1:

@@ -142,6 +142,30 @@ def test_radix_sort_bit_ranges(device, bits_range):
     s.destroy()
 
 
+def test_radix_sort_row_scan_second_trip(device):
+    """k_radix_rowscan takes 8 rounds of 1024 partitions per outer trip and carries each digit row's running count into the next:
+    a second trip needs more than 8192 partitions of 4096 keys.  8192 * 4096 + 4097 keys are 8194 partitions, two of them in the
+    second trip.  One pass over bits (0, 8) (the row scan is the same kernel in every pass); nine keys in ten have digit 0x00, so
+    that row's carry into the second trip is above 2^24 while the other rows' stay near 13 000 each.  A carry that is lost or
+    wrong there scatters the last 4097 keys into other digits' ranges.  The sorter holds 0.54 GB of device memory (two sides of keys and payloads), and 134 MB travel four times."""
+    n = 8192 * 4096 + 4097
+    rng = np.random.default_rng(8194)
+    keys = rng.integers(0, 2**32, size=n, dtype=np.uint64).astype(np.uint32)
+    keys[rng.random(n) < 0.9] &= np.uint32(0xFFFFFF00)
+    digit = (keys & np.uint32(0xFF)).astype(np.uint8)
+    carried = np.bincount(digit[:8192 * 4096], minlength=256)
+    print(f"{n} keys, {-(-n // 4096)} partitions; carries into the second trip: digit 0 {carried[0]}, the others {carried[1:].min()} to {carried[1:].max()}")
+    assert -(-n // 4096) == 8194 and carried[0] > 2**24 and carried[1:].max() < 2**16 and carried[1:].min() > 0
+    s = sr.RadixSorter(device, n)
+    s.getKeysBuffer().write(keys)
+    s.getPayloadBuffer().write(np.arange(n, dtype=np.uint32))
+    s.sort(n, 0, 8)
+    order = np.argsort(digit, kind="stable").astype(np.uint32)
+    assert_same(s.getSortedIndicesBuffer().read(np.uint32, n), order, "row scan, second trip: indices")
+    assert_same(s.getSortedKeysBuffer().read(np.uint32, n), keys[order], "row scan, second trip: keys")
+    s.destroy()
+
+
 def test_lds_atomic_order_probe(device):
     """The fast ranking path rests on a measured hardware property; the probe must report it."""
     import ctypes as C

@@ -83,6 +83,67 @@ def test_non_finite_points():
     assert np.isposinf(got[40]) and np.array_equal(got[:40], clean)
 
 
+def test_morton_order_on_known_cells():
+    """KR.morton_order on a cloud whose cells can be read off: the box is [0, 8]^3, a coordinate c falls in cell
+    floor(c / 8 * 2^21) (the maximum in the last cell), bit k of axis a's cell sits at bit 3 k + a, a non-finite point gets the
+    largest code, and equal codes keep their index order."""
+    p = np.array([[0, 0, 0], [8, 8, 8], [4, 0, 0], [0, 4, 0], [0, 0, 4], [np.nan, 1, 1], [4, 0, 0], [1, 2, np.inf], [8, 0, 0],
+                  [2.0 ** -18, 0, 0], [0, 2.0 ** -18, 0]], F)
+    order, codes = KR.morton_order(p)
+    top, full = 1 << 20, (1 << 21) - 1
+    spread = lambda v: sum(((v >> k) & 1) << (3 * k) for k in range(21))  # noqa: E731
+    want = [0, spread(full) * 7, spread(top), spread(top) << 1, spread(top) << 2, 2 ** 63 - 1, spread(top), 2 ** 63 - 1, spread(full), 1, 2]
+    assert codes.dtype == np.uint64 and codes.tolist() == want
+    assert order.tolist() == [0, 9, 10, 2, 6, 8, 3, 4, 1, 5, 7], order
+    assert KR.block_of(np.arange(130)[::-1]).tolist() == [2, 2] + [1] * 64 + [0] * 64
+    # a degenerate axis (no extent) is cell 0, and a cloud with no finite point is all the largest code, in index order
+    flat = KR.uniform(50, 27)
+    flat[:, 1] = 0.5
+    assert not (KR.morton_order(flat)[1] & np.uint64(0x2492492492492492)).any()
+    order, codes = KR.morton_order(np.full((5, 3), np.nan, F))
+    assert (codes == np.uint64(2 ** 63 - 1)).all() and order.tolist() == [0, 1, 2, 3, 4]
+    # the rows only the second trip over the groups serves: a neighbour more than 64 blocks away and in a group from 64 on
+    block = np.array([0, 4095, 4096, 4160, 4161, 4700])
+    assert KR.second_far_trip(block, [0, 2, 3, 4, 5], [[0, 1, 1], [1, 3, 3], [2, 2, 2], [2, 3, 4], [1, 1, 2]]).tolist() == \
+        [False, False, False, True, True]
+
+
+def test_clouds_past_64_groups_reach_the_second_trip():
+    """What tests/test_gpu_knn.py's clouds above 262 144 points are there for, counted without a GPU (the neighbours from scipy's
+    cKDTree in float64: an approximation of the binary32 rule that is good enough for counts this far from their bounds).
+    uniform(300 000, 21): at least 1000 queries have a neighbour that only k_knn_search's second far trip reaches (measured:
+    3345; 467 at n = 270 336; 0 at 262 145 and at 262 144, where there is no such trip or one group of one block)."""
+    cKDTree = pytest.importorskip("scipy.spatial").cKDTree
+
+    def second_trip_queries(p):
+        order, codes = KR.morton_order(p)
+        fin = np.flatnonzero(np.isfinite(p).all(axis=1))
+        q = p[fin].astype(np.float64)
+        nb = fin[cKDTree(q).query(q, k=4)[1][:, 1:]]
+        return int(KR.second_far_trip(KR.block_of(order), fin, nb).sum()), order, codes
+
+    counts = {n: second_trip_queries(KR.uniform(n, 21))[0] for n in (KR.FAR_HEAD, KR.FAR_HEAD + 1, KR.FAR_N)}
+    print(f"queries served by the second far trip: {counts}")
+    assert counts[KR.FAR_HEAD] == 0 and counts[KR.FAR_HEAD + 1] == 0 and counts[KR.FAR_N] >= 1000
+    # the non-finite tail: 6000 rows, one coordinate each, of the three kinds; a whole group of the second trip holds nobody
+    p, rows = KR.nonfinite_tail()
+    assert rows.size == 6000 and np.array_equal(np.flatnonzero(~np.isfinite(p).all(axis=1)), rows)
+    assert ((~np.isfinite(p)).sum(axis=1)[rows] == 1).all()
+    assert all(k.sum() >= 1000 for k in (np.isnan(p).any(axis=1), np.isposinf(p).any(axis=1), np.isneginf(p).any(axis=1)))
+    count, order, codes = second_trip_queries(p)
+    assert (codes[rows] == np.uint64(2 ** 63 - 1)).all() and np.array_equal(np.sort(order[-6000:]), rows)
+    fin = np.isfinite(p).all(axis=1)
+    held = np.bincount(KR.block_of(order)[fin] // KR.GROUP, minlength=74)
+    print(f"non-finite tail: {count} second-trip queries; finite points per group from 64 on: {held[64:]}")
+    assert held.size == 74 and count >= 1000 and held[72] == 0 and held[:71].min() == KR.BLOCK * KR.GROUP
+    # the shifted tail: all codes distinct (what the evaluation counts' equality under a row reversal rests on)
+    p = KR.shifted_tail()
+    count, order, codes = second_trip_queries(p)
+    print(f"shifted tail: {count} second-trip queries")
+    assert np.unique(codes).size == KR.FAR_N and count >= 1000
+    assert p[:KR.FAR_HEAD, 0].max() < 1 and p[KR.FAR_HEAD:, 0].min() >= 9 and np.abs(p[:, 1:]).max() <= 1
+
+
 def test_header_declares_the_section():
     text = open(os.path.join(ROOT, "include", "splat.h")).read()
     assert "Initialisation from a point cloud" in text

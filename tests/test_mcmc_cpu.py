@@ -77,6 +77,27 @@ def test_sample_edges():
     assert words == (7, 0, 0) and not counts.any()
 
 
+@pytest.mark.parametrize("name", MR.FAR_CASES)
+def test_clouds_past_256_block_sums_reach_their_trips(name):
+    """What tests/test_gpu_mcmc.py's clouds above 524 288 splats are there for, from the restatement alone: the trip counts of the
+    block sums' scan, a first trip that sums past 2^32, at least 1000 of 5000 added draws with a source past the first trip (from
+    n = 1 229 577 on), zero totals where a case wants them, every source in the alive range, and every input's 2^24 o at least 1e-6
+    from an integer (MR.off_integers moved the few that were not)."""
+    logits, alive = MR.far_case(name)
+    n = len(logits)
+    x = MR.scaled_opacity(logits)
+    assert float(np.abs(x - np.round(x)).min()) >= 1e-6
+    if name.startswith("n="):
+        raw = MR.normal_logits(n, 100 + n)
+        moved = np.flatnonzero(raw != logits)
+        print(f"{name}: {moved.size} logits moved off an integer: rows {moved}")
+        assert moved.size <= 8 and np.array_equal(logits[moved], np.nextafter(raw[moved], np.float32(np.inf)))
+    targets, sources, counts, words = MR.sample(logits, MR.ADD, 5000, 0xC0FFEE_0000_0002, 0.005)
+    first, total, past = MR.far_case_regime(name, logits, alive, sources, 0.005)
+    print(f"{name}: n = {n}; weight up to the end of the first trip {first}, total {total}; {past} of 5000 draws past the first trip")
+    assert words[2] == 5000 and int(counts.sum()) == 5000 and np.array_equal(targets, n + np.arange(5000))
+
+
 def test_header_declares_the_entries_and_keeps_the_abi():
     names = declared_functions()
     assert all(n in names for n in ENTRIES)
