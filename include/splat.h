@@ -581,6 +581,42 @@ int splat_composite_backward_det(splat_ctx *ctx, const splat_composite_cfg *cfg,
                                  const void *grad_rgba32f, uint32_t n, void *grad_records, void *grad_color_opacity,
                                  const void *depth_f32, uint32_t depth_stride_floats, const void *grad_depth_f32, void *grad_depth,
                                  void *workspace, uint64_t workspace_bytes);
+/* The composite backwards with AbsGS's absolute screen-space gradient beside the signed one (Ye et al. 2024, "homodirectional
+ * gradient"; gsplat's absgrad).  3DGS densifies by the norm of a splat's summed dL/dc; the sum is signed, so a large splat whose
+ * pixels pull its centre in opposite directions cancels to a small statistic and is never split.  Summing |term| does not cancel.
+ * Opt-in: the four functions above are unchanged, and these give their outputs plus
+ *   grad_center_abs   n x 2 f32, 8-byte aligned, ADDED into: [i][0] = sum |term_cx|, [i][1] = sum |term_cy| over the (pixel,
+ *                     consumed entry inside the cut) pairs of splat i, term_cx / term_cy being exactly the per-pair terms whose
+ *                     signed sums go to grad_records[i][0] and [i][1] (so [i][k] >= |grad_records[i][k]| up to rounding).  A
+ *                     splat no pixel consumed keeps its prior bits.  NULL with n > 0, or not 8-byte aligned: SPLAT_ERR_INVALID,
+ *                     and nothing is launched.
+ *
+ * splat_composite_backward_abs: splat_composite_backward_depth's arguments plus grad_center_abs; as with the det entry point,
+ * the four depth arguments all NULL / 0 select the colour-only variant (then splat_composite_backward's checks), any of them
+ * given the depth variant with its checks.  The two absolute sums take the path of the other numbers (each wave's DPP tree under
+ * the same ballot, (w0 + w1) + (w2 + w3), one float atomic add per touched (entry, number)): reproducible to rounding.
+ *
+ * splat_composite_backward_det_abs: splat_composite_backward_det's arguments plus grad_center_abs, the workspace sized by
+ * splat_composite_backward_det_abs_workspace_bytes(total_pairs, num_tiles, n, with_depth) = 16 num_tiles + 16 ceil(n / 4) +
+ * 4 NV total_pairs bytes with NV = 11, or 12 with depth (a smaller one: SPLAT_ERR_INVALID).  The numbers of a pair, in slot
+ * order: c.x, c.y, B00, B01, B11, r, g, b, opacity, (dL/dz,) |c.x|, |c.y|.  The two new ones are summed as "The sums" above
+ * states for the others: rows left to right from +0, the rows top to bottom from +0, then one add into grad_center_abs.  The
+ * signed outputs are formed by the same additions in the same order as splat_composite_backward_det's: the same bits.
+ *
+ * All other checks, the kernel selection and the stream behaviour are those of the functions above.  The price: two more wave
+ * sums per entry on top of nine or ten, and 8 more bytes per pair of the det workspace. */
+int splat_composite_backward_abs(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4,
+                                 const void *records, const void *tile_indices, const void *tile_counts, const void *tile_offsets,
+                                 uint32_t width, uint32_t height, const void *grad_rgba32f, uint32_t n, void *grad_records,
+                                 void *grad_color_opacity, const void *depth_f32, uint32_t depth_stride_floats,
+                                 const void *grad_depth_f32, void *grad_depth, void *grad_center_abs);
+uint64_t splat_composite_backward_det_abs_workspace_bytes(uint64_t total_pairs, uint32_t num_tiles, uint32_t n, int with_depth);
+int splat_composite_backward_det_abs(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4,
+                                     const void *records, const void *projected, const void *tile_indices, const void *tile_counts,
+                                     const void *tile_offsets, uint64_t total_pairs, uint32_t width, uint32_t height,
+                                     const void *grad_rgba32f, uint32_t n, void *grad_records, void *grad_color_opacity,
+                                     const void *depth_f32, uint32_t depth_stride_floats, const void *grad_depth_f32, void *grad_depth,
+                                     void *workspace, uint64_t workspace_bytes, void *grad_center_abs);
 /* splat_project_ellipsoid's backward: dL/drecords (n x 8, splat_composite_backward's layout) -> dL/dposition (xyz, w = 0),
  * dL/dscale (xyz, w = 0) and dL/drotation (w, x, y, z of the quaternion as given, through its normalisation), all n x 4 f32,
  * OVERWRITTEN.  The centre and J move with the position.  The cull decisions are the forward's (csrc/ellipsoid.h); a culled
@@ -755,6 +791,13 @@ int splat_adam_step(splat_ctx *ctx, void *param, const void *grad, void *m, void
  * splat_adam_step takes.  grad_accum, denom, max_radius: n floats each, zeroed by the caller before the first frame. */
 int splat_density_accumulate(splat_ctx *ctx, const void *records, const void *grad_records, uint32_t n, uint32_t width,
                              uint32_t height, void *grad_accum, void *denom, void *max_radius, void *visible_u8);
+/* splat_density_accumulate_abs: splat_density_accumulate with the gradient read from grad_center_abs, the n x 2 plane of
+ * splat_composite_backward_abs (g.x = [i][0], g.y = [i][1]; 8-byte aligned), instead of columns 0 and 1 of the n x 8 plane: the
+ * same visibility rule, the same hypot(g.x W / 2, g.y H / 2), the same updates of denom, max_radius and visible_u8, by the same
+ * kernel.  A plane that copies columns 0 and 1 of a grad_records gives splat_density_accumulate's bits.  The absolute statistic
+ * is several times the signed one (it does not cancel): gsplat recommends a densification threshold of 8e-4 with it, not 2e-4. */
+int splat_density_accumulate_abs(splat_ctx *ctx, const void *records, const void *grad_center_abs, uint32_t n, uint32_t width,
+                                 uint32_t height, void *grad_accum, void *denom, void *max_radius, void *visible_u8);
 /* splat_densify_plan: decide, count and lay out the next cloud.  Per splat, in binary32:
  *   g = denom > 0 ? grad_accum / denom : 0,  s = exp(max log-scale) (NaN if any is),  o = sigmoid(logit),  r = max_radius;
  *   DEAD       when !(o >= min_opacity), or max_screen_radius > 0 && r > max_screen_radius, or max_world_scale > 0 &&

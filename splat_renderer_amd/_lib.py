@@ -116,6 +116,11 @@ SIGNATURES = {
     "splat_composite_backward_det_workspace_bytes": (C.c_uint64, [C.c_uint64, _u32, _u32, _i]),
     "splat_composite_backward_det": (_i, [_vp, C.POINTER(CompositeCfg), _vp, _u32, _vp, _vp, _vp, _vp, _vp, C.c_uint64, _u32, _u32, _vp, _u32,
                                           _vp, _vp, _vp, _u32, _vp, _vp, _vp, C.c_uint64]),
+    "splat_composite_backward_abs": (_i, [_vp, C.POINTER(CompositeCfg), _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _vp, _vp,
+                                          _vp, _u32, _vp, _vp, _vp]),
+    "splat_composite_backward_det_abs_workspace_bytes": (C.c_uint64, [C.c_uint64, _u32, _u32, _i]),
+    "splat_composite_backward_det_abs": (_i, [_vp, C.POINTER(CompositeCfg), _vp, _u32, _vp, _vp, _vp, _vp, _vp, C.c_uint64, _u32, _u32, _vp,
+                                              _u32, _vp, _vp, _vp, _u32, _vp, _vp, _vp, C.c_uint64, _vp]),
     "splat_composite_contribution": (_i, [_vp, C.POINTER(CompositeCfg), _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, C.c_float, _u32,
                                           _vp, _vp, _vp]),
     "splat_project_ellipsoid_backward_depth": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp,
@@ -128,6 +133,7 @@ SIGNATURES = {
     "splat_image_loss_backward": (_i, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, C.c_float, _vp, C.c_uint64, _vp, _vp, _u32]),
     "splat_adam_step": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _f64, _f64, _f64, _f64, _f64, _f64, _vp]),
     "splat_density_accumulate": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "splat_density_accumulate_abs": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
     "splat_densify_plan_workspace_bytes": (C.c_uint64, [_u32]),
     "splat_densify_plan": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, C.POINTER(DensifyCfg), _vp, C.c_uint64, _vp, C.POINTER(_u32),
                                 C.POINTER(_u32)]),

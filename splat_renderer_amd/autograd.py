@@ -37,6 +37,25 @@ price: the workspace, a torch tensor allocated in backward() and freed after it,
 time of the stores and the second pass (DESIGN.md section 4 has the measurement).  The default, deterministic=False, is the
 atomic path, unchanged: no workspace, reproducible to rounding.
 
+AbsGS's absolute screen-space gradient (include/splat.h, splat_composite_backward_abs; Ye et al. 2024; gsplat's absgrad):
+
+    rgb, alpha       = rasterize(rec, col, aux, width, height, absgrad=True)
+    loss.backward();   aux.absgrad                                             # (n, 2): sum |term c.x|, sum |term c.y|
+    rgb, alpha, aux  = render_gaussians(..., absgrad=True, return_aux=True);  loss.backward();  aux.absgrad
+
+3DGS densifies by the norm of rec.grad[:, :2], a signed sum over a splat's pixels: where a large splat covers two
+under-fitted regions its pixels pull the centre in opposite directions, the sum cancels and the splat is never split.  With
+absgrad=True the composite's backward is splat_composite_backward_abs (splat_composite_backward_det_abs with
+deterministic=True; the depth variant of either when a depth gradient arrives), which sums the absolute values of the very
+per-pixel terms beside the signed sums.  backward() leaves them in aux.absgrad on the ProjectedSplats: a fresh (n, 2) float32
+tensor holding this backward's values, zeros for splats no pixel consumed; None before any backward.  It is a statistic, not
+a gradient: nothing flows through it, and rec.grad, col.grad and the image are what absgrad=False gives (bit for bit under
+deterministic=True, where the signed sums are made by the same additions).  render_gaussians builds its ProjectedSplats
+itself, so return_aux=True appends it to the tuple it returns; by default it returns what it always did.  The price: two more
+wave sums per list entry on top of nine or ten in the backward's second walk, and 44 (48) instead of 36 (40) bytes per pair of
+the deterministic workspace (DESIGN.md section 4 has the measurement).  absgrad=False, the default, is the code path
+described above, call for call.
+
 Antialiased frames (include/splat.h, "antialiased frames"; Mip-Splatting's 2D filter, gsplat's rasterize_mode="antialiased"):
 
     rec, rho, aux          = project_ellipsoids(uniforms, means, scales, rotations, antialiased=True)
@@ -275,10 +294,13 @@ def _fptr(a):
 
 class ProjectedSplats:
     """What rasterize needs of a projection beside its records: ProjectedSplat records (n, 8), depth keys and payload (padded
-    to the sorter's capacity), the uniforms and the inputs (for the projector's backward).  No gradient flows through it."""
+    to the sorter's capacity), the uniforms and the inputs (for the projector's backward).  No gradient flows through it.
+    absgrad: None, or after the backward of a rasterize(absgrad=True) over this projection the (n, 2) sums of |term c.x|,
+    |term c.y| (the module's docstring)."""
 
     def __init__(self, ctx, u, n, projected, keys, payload):
         self.ctx, self.u, self.n = ctx, u, n
+        self.absgrad = None
         self.projected, self.keys, self.payload = projected, keys, payload
         self.width, self.height = int(u[20]), int(u[21])
 
@@ -417,7 +439,7 @@ def _functions():
 
     class Rasterize(torch.autograd.Function):
         @staticmethod
-        def forward(fctx, rec, col, aux, width, height, depths=None, deterministic=False):
+        def forward(fctx, rec, col, aux, width, height, depths=None, deterministic=False, absgrad=False):
             cx = aux.ctx
             n = aux.n
             out = torch.empty((height, width, 4), device=rec.device, dtype=torch.float32)
@@ -439,6 +461,7 @@ def _functions():
                 fctx.set_materialize_grads(False)  # (an unused depth map: None, and the colour-only kernel)
             fctx.aux, fctx.gen, fctx.wh = aux, gen, (width, height)
             fctx.deterministic = bool(deterministic)
+            fctx.absgrad = bool(absgrad)
             rgb = out[..., :3]
             return (rgb, alpha) if depths is None else (rgb, alpha, depth)
 
@@ -461,20 +484,30 @@ def _functions():
             grec = torch.zeros((n, 8), device=rec.device, dtype=torch.float32)
             gcol = torch.zeros((n, 4), device=rec.device, dtype=torch.float32)
             cfg = CompositeCfg(_lib.MODE_FRONT_TO_BACK, 1, TILE, 0, _lib.U32_MAX, _lib.RECORDS_PROJECTED, 1, _lib.FOOTPRINT_ELLIPSOID)
-            if fctx.deterministic:  # the fixed-order sums: splat_composite_backward_det over a workspace sized from the lists' pairs
+            if fctx.deterministic or fctx.absgrad:
+                # deterministic: the fixed-order sums, splat_composite_backward_det over a workspace sized from the lists' pairs;
+                # absgrad: the signed sums and beside them sum |term c.x|, sum |term c.y|, the _abs twin of either entry point
+                sfx = "_abs" if fctx.absgrad else ""
                 with_depth = depths is not None and grad_depth_map is not None
                 gd = _cuda_f32(grad_depth_map, "grad_depth") if with_depth else None
                 gz = torch.zeros(n, device=rec.device, dtype=torch.float32) if with_depth else None
-                if n:
+                gabs = torch.zeros((n, 2), device=rec.device, dtype=torch.float32) if fctx.absgrad else None
+                dargs = (depths.data_ptr() if with_depth else None, 1 if with_depth else 0, gd.data_ptr() if with_depth else None,
+                         gz.data_ptr() if with_depth else None)
+                tail = (gabs.data_ptr(),) if fctx.absgrad else ()
+                if n and fctx.deterministic:
                     tiles = ((width + TILE - 1) // TILE) * ((height + TILE - 1) // TILE)
-                    nbytes = int(cx.lib.splat_composite_backward_det_workspace_bytes(cx.total, tiles, n, int(with_depth)))
+                    nbytes = int(getattr(cx.lib, f"splat_composite_backward_det{sfx}_workspace_bytes")(cx.total, tiles, n, int(with_depth)))
                     ws = torch.empty((nbytes + 15) // 16 * 4, device=rec.device, dtype=torch.int32)
-                    check(cx.lib.splat_composite_backward_det(cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr(), aux.projected.data_ptr(),
-                                                              idx, cnt, off, cx.total, width, height, g.data_ptr(), n, grec.data_ptr(),
-                                                              gcol.data_ptr(), depths.data_ptr() if with_depth else None,
-                                                              1 if with_depth else 0, gd.data_ptr() if with_depth else None,
-                                                              gz.data_ptr() if with_depth else None, ws.data_ptr(), nbytes), cx.ctx)
-                return grec, gcol, None, None, None, gz, None
+                    check(getattr(cx.lib, f"splat_composite_backward_det{sfx}")(
+                        cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr(), aux.projected.data_ptr(), idx, cnt, off, cx.total, width, height,
+                        g.data_ptr(), n, grec.data_ptr(), gcol.data_ptr(), *dargs, ws.data_ptr(), nbytes, *tail), cx.ctx)
+                elif n:
+                    check(cx.lib.splat_composite_backward_abs(cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr(), idx, cnt, off, width, height,
+                                                              g.data_ptr(), n, grec.data_ptr(), gcol.data_ptr(), *dargs, *tail), cx.ctx)
+                if fctx.absgrad:
+                    aux.absgrad = gabs
+                return (grec, gcol, None, None, None, gz, None) + (None,) * len(tail)
             if depths is None or grad_depth_map is None:
                 if n:
                     check(cx.lib.splat_composite_backward(cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr(), idx, cnt, off, width, height,
@@ -570,35 +603,42 @@ def sh_colors(eye, means, sh, degree, opacities):
     return _functions()[1].apply(e, means4, sh2, int(degree), op)
 
 
-def rasterize(rec, col, aux, width=None, height=None, depths=None, deterministic=False):
+def rasterize(rec, col, aux, width=None, height=None, depths=None, deterministic=False, absgrad=False):
     """(rgb (H, W, 3), alpha (H, W)) of the records and colours over the projection's lists; both differentiable.  With
     depths ((n,) per-splat z, differentiable): (rgb, alpha, depth), depth (H, W) = sum w z / sum w per pixel, +inf where
-    nothing contributed.  deterministic=True: the backward sums in a fixed order (the module's docstring)."""
+    nothing contributed.  deterministic=True: the backward sums in a fixed order (the module's docstring).  absgrad=True: the
+    backward also leaves the (n, 2) absolute sums of the centre's terms in aux.absgrad (the module's docstring)."""
     width = aux.width if width is None else int(width)
     height = aux.height if height is None else int(height)
     rec_c = _cuda_f32(rec, "rec", 8)
     col_c = _cuda_f32(col, "col", 4)
     if rec_c.shape[0] != aux.n or col_c.shape[0] != aux.n:
         raise SplatError(-1, "rec, col and the projection must hold the same number of splats")
-    if depths is None:
+    z = None
+    if depths is not None:
+        z = _cuda_f32(depths, "depths")
+        if z.dim() != 1 or z.shape[0] != aux.n:
+            raise SplatError(-1, f"depths must have shape ({aux.n},), not {tuple(z.shape)}")
+    if absgrad:
+        return _functions()[2].apply(rec_c, col_c, aux, width, height, z, bool(deterministic), True)
+    if z is None:
         if deterministic:
             return _functions()[2].apply(rec_c, col_c, aux, width, height, None, True)
         return _functions()[2].apply(rec_c, col_c, aux, width, height)
-    z = _cuda_f32(depths, "depths")
-    if z.dim() != 1 or z.shape[0] != aux.n:
-        raise SplatError(-1, f"depths must have shape ({aux.n},), not {tuple(z.shape)}")
     if deterministic:
         return _functions()[2].apply(rec_c, col_c, aux, width, height, z, True)
     return _functions()[2].apply(rec_c, col_c, aux, width, height, z)
 
 
 def render_gaussians(camera_or_uniforms, means, scales, rotations, opacities, colors=None, sh=None, width=None, height=None, degree=None,
-                     return_depth=False, deterministic=False, antialiased=False):
+                     return_depth=False, deterministic=False, antialiased=False, absgrad=False, return_aux=False):
     """The whole differentiable frame: project_ellipsoids, the colour (sh_colors when `sh` is given, else cat(colors,
     opacities)), rasterize.  Returns (rgb (H, W, 3), alpha (H, W)); return_depth=True: (rgb, alpha, depth (H, W)), the depth
     map of the ProjectedSplat depths (the distance from the eye to each centre).  deterministic=True: every gradient is the
     same bits on every run (rasterize's fixed-order backward; the module's docstring).  antialiased=True: the opacity column is
-    multiplied by project_ellipsoids' rho (a torch op) before rasterize: the 2D Mip filter."""
+    multiplied by project_ellipsoids' rho (a torch op) before rasterize: the 2D Mip filter.  absgrad=True: rasterize's
+    absgrad; return_aux=True appends the frame's ProjectedSplats to the returned tuple, whose .absgrad backward() fills (the
+    module's docstring)."""
     if width is None or height is None:
         raise SplatError(-1, "render_gaussians needs width and height")
     for name, t in (("means", means), ("scales", scales), ("rotations", rotations), ("opacities", opacities)):
@@ -631,7 +671,11 @@ def render_gaussians(camera_or_uniforms, means, scales, rotations, opacities, co
         raise SplatError(-1, "render_gaussians needs colors or sh")
     if rho is not None:
         col = compensate_opacity(col, rho)
-    return rasterize(rec, col, aux, width, height, depths=depths, deterministic=deterministic)
+    if absgrad:
+        out = rasterize(rec, col, aux, width, height, depths=depths, deterministic=deterministic, absgrad=True)
+    else:
+        out = rasterize(rec, col, aux, width, height, depths=depths, deterministic=deterministic)
+    return (*out, aux) if return_aux else out
 
 
 def compensate_opacity(col, rho):

@@ -11,6 +11,8 @@
 //                         whose roundings are written out (explicit fmaf, no contraction), so the four instantiations give one
 //                         element the same bits.
 // k_density_accumulate    one thread per splat: visibility of the record's 3-sigma box, the three running statistics, the mask.
+//                         <PLANE2>: the gradient read from an n x 2 plane (splat_density_accumulate_abs) instead of columns 0, 1
+//                         of the n x 8 plane; everything else the same code.
 // k_densify_classify ..   splat_densify_plan: classify -> scan(alive), scan(wants) -> grant under the cap -> scan(rows per
 // k_densify_fill          splat), scan(granted clones) -> one thread per splat writes its rows.  The scans are scan.hip's.
 // k_densify_geometry      one thread per OUTPUT row: means and log-scales, the split children drawn with Philox4x32-10 (philox.h).
@@ -120,7 +122,8 @@ __device__ __forceinline__ bool density_visible(float4 ra, float4 rb, float w, f
     return !culled && ra.x + hx > 0.0f && ra.x - hx < w && ra.y + hy > 0.0f && ra.y - hy < h; // (false for a NaN)
 }
 
-__global__ __launch_bounds__(DT) void k_density_accumulate(const float4 *__restrict__ rec, const float4 *__restrict__ grec, uint32_t n, float w,
+template <bool PLANE2>
+__global__ __launch_bounds__(DT) void k_density_accumulate(const float4 *__restrict__ rec, const void *__restrict__ grad, uint32_t n, float w,
                                                            float h, float *__restrict__ grad_accum, float *__restrict__ denom,
                                                            float *__restrict__ max_radius, uint8_t *__restrict__ vis) {
     const uint32_t i = blockIdx.x * DT + threadIdx.x;
@@ -130,8 +133,17 @@ __global__ __launch_bounds__(DT) void k_density_accumulate(const float4 *__restr
     const bool on = density_visible(ra, rb, w, h, radius);
     vis[i] = on ? 1 : 0;
     if (!on) return;
-    const float4 g = grec[2 * (size_t)i];
-    grad_accum[i] += hypotf(g.x * (0.5f * w), g.y * (0.5f * h));
+    float gx, gy;
+    if constexpr (PLANE2) {
+        const float2 g = static_cast<const float2 *>(grad)[i];
+        gx = g.x;
+        gy = g.y;
+    } else {
+        const float4 g = static_cast<const float4 *>(grad)[2 * (size_t)i];
+        gx = g.x;
+        gy = g.y;
+    }
+    grad_accum[i] += hypotf(gx * (0.5f * w), gy * (0.5f * h));
     denom[i] += 1.0f;
     max_radius[i] = fmaxf(max_radius[i], radius);
 }
@@ -267,17 +279,33 @@ extern "C" int splat_adam_step(splat_ctx *ctx, void *param, const void *grad, vo
     return SPLAT_OK;
 }
 
-extern "C" int splat_density_accumulate(splat_ctx *ctx, const void *records, const void *grad_records, uint32_t n, uint32_t width,
-                                        uint32_t height, void *grad_accum, void *denom, void *max_radius, void *visible_u8) {
+// splat_density_accumulate (grad: the n x 8 plane, 16-byte aligned) and splat_density_accumulate_abs (plane2: the n x 2 plane,
+// 8-byte aligned): one kernel, the gradient's layout its template argument
+static int density_accumulate(splat_ctx *ctx, const void *records, const void *grad, bool plane2, uint32_t n, uint32_t width, uint32_t height,
+                              void *grad_accum, void *denom, void *max_radius, void *visible_u8) {
     if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
     if (n == 0) return SPLAT_OK;
-    ARG_CHECK(ctx, records && grad_records && grad_accum && denom && max_radius && visible_u8 && width >= 1 && height >= 1);
-    ARG_CHECK(ctx, (((uintptr_t)records | (uintptr_t)grad_records) & 15) == 0);
+    ARG_CHECK(ctx, records && grad && grad_accum && denom && max_radius && visible_u8 && width >= 1 && height >= 1);
+    ARG_CHECK(ctx, ((uintptr_t)records & 15) == 0 && ((uintptr_t)grad & (plane2 ? 7 : 15)) == 0);
     ARG_CHECK(ctx, (((uintptr_t)grad_accum | (uintptr_t)denom | (uintptr_t)max_radius) & 3) == 0);
-    hipLaunchKernelGGL(k_density_accumulate, dim3(div_up(n, DT)), dim3(DT), 0, ctx->stream, (const float4 *)records, (const float4 *)grad_records,
-                       n, (float)width, (float)height, (float *)grad_accum, (float *)denom, (float *)max_radius, (uint8_t *)visible_u8);
+    if (plane2)
+        hipLaunchKernelGGL(k_density_accumulate<true>, dim3(div_up(n, DT)), dim3(DT), 0, ctx->stream, (const float4 *)records, grad, n, (float)width,
+                           (float)height, (float *)grad_accum, (float *)denom, (float *)max_radius, (uint8_t *)visible_u8);
+    else
+        hipLaunchKernelGGL(k_density_accumulate<false>, dim3(div_up(n, DT)), dim3(DT), 0, ctx->stream, (const float4 *)records, grad, n, (float)width,
+                           (float)height, (float *)grad_accum, (float *)denom, (float *)max_radius, (uint8_t *)visible_u8);
     LAUNCH_CHECK(ctx, "k_density_accumulate");
     return SPLAT_OK;
+}
+
+extern "C" int splat_density_accumulate(splat_ctx *ctx, const void *records, const void *grad_records, uint32_t n, uint32_t width,
+                                        uint32_t height, void *grad_accum, void *denom, void *max_radius, void *visible_u8) {
+    return density_accumulate(ctx, records, grad_records, false, n, width, height, grad_accum, denom, max_radius, visible_u8);
+}
+
+extern "C" int splat_density_accumulate_abs(splat_ctx *ctx, const void *records, const void *grad_center_abs, uint32_t n, uint32_t width,
+                                            uint32_t height, void *grad_accum, void *denom, void *max_radius, void *visible_u8) {
+    return density_accumulate(ctx, records, grad_center_abs, true, n, width, height, grad_accum, denom, max_radius, visible_u8);
 }
 
 extern "C" uint64_t splat_densify_plan_workspace_bytes(uint32_t n) { return 4 * (uint64_t)plan_plane_bytes(n) + 256; }

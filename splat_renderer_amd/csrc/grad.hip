@@ -25,6 +25,13 @@
 //   index), so one compare with the tile's row decides - each tile row left to right, the rows top to bottom, and the total
 //   once into the splat's row: the order include/splat.h states, the same bits on every run.  The instantiations without DET
 //   are the kernel as it was, instruction for instruction.
+//   <ABS = true> (splat_composite_backward_abs, splat_composite_backward_det_abs) sums two more numbers per entry, |term c.x| and
+//   |term c.y|: the absolute values of the very terms numbers 0 and 1 add (AbsGS's homodirectional gradient: a splat whose
+//   pixels pull its centre in opposite directions keeps a large statistic where the signed sum cancels).  They take the path
+//   of the others - a DPP sum per wave under the same ballot, the partials in LDS, (w0 + w1) + (w2 + w3), then a float atomic
+//   add or a slot store - into grad_center_abs (2 floats per splat).  The order of an entry's numbers: c.x, c.y, B00, B01,
+//   B11, r, g, b, opacity, (DEPTH: z,) (ABS: |c.x|, |c.y|): the two new ones last, so that k < GNV means what it meant; a det
+//   slot then holds 11 (12) floats.  The instantiations without ABS are the kernel as it was, instruction for instruction.
 // k_composite_contribution   (splat_composite_contribution) walk 1 alone, with every lane kept in the loop: per consumed entry
 //   inside the cut a pixel's blend weight w = T alpha, in the drawing kernel's operation order as above (<PX>), times the
 //   pixel's mask.  Per entry and wave a ballot counts the hits and two integer DPP trees give the largest weight (non-negative
@@ -53,6 +60,10 @@ namespace {
 constexpr int GT = 16;          // tile edge
 constexpr int GCH = 64;         // list entries per staged chunk
 constexpr int GNV = 9;          // numbers summed per entry: c.x, c.y, B00, B01, B11, r, g, b, opacity (DEPTH: and z)
+constexpr int GNABS = 2;        // (ABS) and, after all of those, |term c.x|, |term c.y|
+// numbers per entry of a variant, and of it without the absolute sums (the index of |term c.x| where it has them)
+constexpr int grad_nv_base(bool depth) { return depth ? GNV + 1 : GNV; }
+constexpr int grad_nv(bool depth, bool abs) { return grad_nv_base(depth) + (abs ? GNABS : 0); }
 constexpr float G_T_STOP = 0x1.47ae4p-7f; // composite.h's T_STOP: the last transmittance that stops a pixel
 constexpr float G_EXP2_SCALE = -6.492127684000335f; // composite.h's ELLIPSOID_EXP2_SCALE: exp(-4.5 d2) = exp2(d2 * this)
 
@@ -120,6 +131,11 @@ struct BackDetParams : BackDepthParams {
     float *slots;               // slot_cap slots of NV floats, splat-major
     uint4 *tile_table;          // per tile {largest L, depth key and splat index of the last consumed entry, 0}
     uint32_t slot_cap, nty;
+};
+
+// the absolute-sum variants' further argument (splat_composite_backward_abs, _det_abs): 2 floats per splat, ADDED into
+struct BackAbsParams : BackDetParams {
+    float *grad_abs;
 };
 
 constexpr uint32_t DET_NO_SLOT = 0xffffffffu;
@@ -203,10 +219,13 @@ __device__ __forceinline__ uint32_t *det_slot_lds() {
 
 // <DET = true> (splat_composite_backward_det): the same sums, stored to the splat-major slots of BackDetParams for k_det_gather
 // to add in a fixed order, where <DET = false> hands them to float atomic adds into the splats' rows.
-template <bool DEPTH, bool PX, bool DET = false>
+// <ABS = true>: two more sums per entry, |term c.x| and |term c.y|, after the others (file header); the argument is then
+// BackAbsParams, with or without DET.
+template <bool DEPTH, bool PX, bool DET = false, bool ABS = false>
 __global__ __launch_bounds__(256) void k_composite_backward(
-    std::conditional_t<DET, BackDetParams, std::conditional_t<DEPTH, BackDepthParams, BackParams>> p) {
-    constexpr int NV = DEPTH ? GNV + 1 : GNV; // (the tenth: dL/dz)
+    std::conditional_t<ABS, BackAbsParams, std::conditional_t<DET, BackDetParams, std::conditional_t<DEPTH, BackDepthParams, BackParams>>> p) {
+    constexpr int NV = grad_nv(DEPTH, ABS); // (the tenth: dL/dz; ABS: the last two)
+    constexpr int NVB = grad_nv_base(DEPTH);
     __shared__ GradEntry s_ent[GCH];
     __shared__ uint32_t s_idx[GCH];
     __shared__ float s_part[4][GCH][NV];
@@ -333,6 +352,10 @@ __global__ __launch_bounds__(256) void k_composite_backward(
                 vals[2] = du * dx;                   // d2 / B00
                 vals[3] = du * dy;                   // d2 / B01
                 vals[4] = dv * dy;                   // d2 / B11
+                if constexpr (ABS) {
+                    vals[NVB] = fabsf(vals[0]);
+                    vals[NVB + 1] = fabsf(vals[1]);
+                }
                 S = alpha * cg + (1.0f - alpha) * S;
                 Tn = Ti;
             } else if (i + 1 == L) {
@@ -366,6 +389,7 @@ __global__ __launch_bounds__(256) void k_composite_backward(
                 const size_t idx = s_idx[e];
                 float *dst = k < 5 ? p.grad_records + idx * 8 + (k < 4 ? k : 5u) : p.grad_color + idx * 4 + (k - 5);
                 if constexpr (DEPTH) dst = k == GNV ? p.grad_depth + idx : dst;
+                if constexpr (ABS) dst = k >= (uint32_t)NVB ? p.grad_abs + idx * 2 + (k - NVB) : dst;
                 atomicAdd(dst, sum);
             }
         }
@@ -497,9 +521,10 @@ __device__ __forceinline__ bool det_row_sum(const BackDetParams &p, uint32_t til
 //   the additions does not.  A splat with no consumed entry keeps its prior bits.
 constexpr uint32_t DET_WIDE = 64;
 
-template <bool DEPTH>
-__global__ __launch_bounds__(256) void k_det_gather(BackDetParams p, uint32_t n) {
-    constexpr int NV = DEPTH ? GNV + 1 : GNV;
+// <ABS = true>: the slots' last two numbers too, in the same order, into grad_abs.
+template <bool DEPTH, bool ABS = false>
+__global__ __launch_bounds__(256) void k_det_gather(std::conditional_t<ABS, BackAbsParams, BackDetParams> p, uint32_t n) {
+    constexpr int NV = grad_nv(DEPTH, ABS);
     const uint32_t i = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
     uint32_t tx0 = 0, tx1 = 0, ty0 = 0, ty1 = 0, key = 0, base = 0;
     bool ok = false;
@@ -556,6 +581,11 @@ __global__ __launch_bounds__(256) void k_det_gather(BackDetParams p, uint32_t n)
 #pragma unroll
     for (int k = 0; k < 4; ++k) gcol[k] += total[5 + k];
     if constexpr (DEPTH) p.grad_depth[i] += total[GNV];
+    if constexpr (ABS) {
+        float *gabs = p.grad_abs + (size_t)i * 2;
+#pragma unroll
+        for (int k = 0; k < GNABS; ++k) gabs[k] += total[grad_nv_base(DEPTH) + k];
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -956,6 +986,7 @@ __global__ __launch_bounds__(256) void k_sh_colors_backward(float ex, float ey, 
 // The two composite backwards: their checks, the kernel's parameters and the launch.  depth: splat_composite_backward_depth,
 // with its four further arguments.
 // det: splat_composite_backward_det's further arguments, or NULL for the two atomic entry points.
+// abs: the _abs entry points, with grad_center_abs (n x 2 floats, 8-byte aligned, ADDED into).
 struct DetArgs {
     const void *projected;
     uint64_t total_pairs;
@@ -964,25 +995,31 @@ struct DetArgs {
 };
 
 // The workspace of splat_composite_backward_det: the tile table (16 bytes per tile), slot_base (4 bytes per splat, rounded up
-// to 16) and the slots (4 NV bytes per pair, NV = 9, or 10 with depth).  0 where it would not fit 64 bits.
+// to 16) and the slots (4 NV bytes per pair, NV = 9, or 10 with depth; the _abs entry points: 11, or 12).  0 where it would
+// not fit 64 bits (judged by the largest slot of the family: 40 bytes, 48 with the absolute sums).
 static uint64_t det_workspace_bytes(uint64_t total_pairs, uint32_t num_tiles, uint32_t n, bool depth, uint64_t *slot_base_off = nullptr,
-                                    uint64_t *slots_off = nullptr) {
+                                    uint64_t *slots_off = nullptr, bool abs = false) {
     const uint64_t table = (uint64_t)num_tiles * 16u, base = ((uint64_t)n * 4u + 15u) & ~15ull;
     if (slot_base_off) *slot_base_off = table;
     if (slots_off) *slots_off = table + base;
-    if (total_pairs > (~0ull - table - base) / 40u) return 0;
-    return table + base + total_pairs * 4u * (depth ? GNV + 1 : GNV);
+    if (total_pairs > (~0ull - table - base) / (4u * (uint64_t)grad_nv(true, abs))) return 0;
+    return table + base + total_pairs * 4u * (uint64_t)grad_nv(depth, abs);
 }
 
 extern "C" uint64_t splat_composite_backward_det_workspace_bytes(uint64_t total_pairs, uint32_t num_tiles, uint32_t n, int with_depth) {
     return det_workspace_bytes(total_pairs, num_tiles, n, with_depth != 0);
 }
 
+extern "C" uint64_t splat_composite_backward_det_abs_workspace_bytes(uint64_t total_pairs, uint32_t num_tiles, uint32_t n, int with_depth) {
+    return det_workspace_bytes(total_pairs, num_tiles, n, with_depth != 0, nullptr, nullptr, true);
+}
+
 static int composite_backward_launch(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4,
                                      const void *records, const void *tile_indices, const void *tile_counts, const void *tile_offsets,
                                      uint32_t width, uint32_t height, const void *grad_rgba32f, uint32_t n, void *grad_records,
                                      void *grad_color_opacity, bool depth, const void *depth_f32, uint32_t depth_stride_floats,
-                                     const void *grad_depth_f32, void *grad_depth, const DetArgs *det = nullptr) {
+                                     const void *grad_depth_f32, void *grad_depth, const DetArgs *det = nullptr, bool abs = false,
+                                     void *grad_center_abs = nullptr) {
     if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
     ARG_CHECK(ctx, cfg != nullptr);
     if (cfg->footprint != SPLAT_FOOTPRINT_ELLIPSOID || cfg->mode != SPLAT_COMPOSITE_FRONT_TO_BACK || cfg->early_out != 1 ||
@@ -1002,15 +1039,17 @@ static int composite_backward_launch(splat_ctx *ctx, const splat_composite_cfg *
         ARG_CHECK(ctx, depth_f32 && grad_depth_f32 && (n == 0 || grad_depth) && depth_stride_floats >= 1);
         ARG_CHECK(ctx, (((uintptr_t)depth_f32 | (uintptr_t)grad_depth_f32 | (uintptr_t)grad_depth) & 3) == 0);
     }
+    if (abs) ARG_CHECK(ctx, (n == 0 || grad_center_abs) && ((uintptr_t)grad_center_abs & 7) == 0);
     uint64_t slot_base_off = 0, slots_off = 0;
     if (det) {
         // (a slot index is a u32, as a list offset is)
         ARG_CHECK(ctx, det->projected && ((uintptr_t)det->projected & 15) == 0 && det->total_pairs <= 0xffffffffull);
-        const uint64_t need = det_workspace_bytes(det->total_pairs, ntx * nty, n, depth, &slot_base_off, &slots_off);
+        const uint64_t need = det_workspace_bytes(det->total_pairs, ntx * nty, n, depth, &slot_base_off, &slots_off, abs);
         ARG_CHECK(ctx, det->workspace && ((uintptr_t)det->workspace & 15) == 0 && need != 0 && det->workspace_bytes >= need);
     }
     if (n == 0) return SPLAT_OK; // (no splat: every list is empty)
-    BackDetParams p;
+    BackAbsParams p{}; // (every kernel takes the base of it that it reads; what a launch does not set is zero)
+    p.grad_abs = (float *)grad_center_abs;
     p.color = (const float4 *)color_opacity;
     p.color_stride = color_stride_vec4;
     p.records = (const float4 *)records;
@@ -1040,15 +1079,18 @@ static int composite_backward_launch(splat_ctx *ctx, const splat_composite_cfg *
         LAUNCH_CHECK(ctx, "launch k_det_rect_count");
         const int rc = splat_scan_u32(ctx, slot_base, slot_base, n, nullptr);
         if (rc != SPLAT_OK) return rc;
-        variant_dispatch([&](auto d, auto px) { launch_kernel(ctx, NO_STAGE, k_composite_backward<d.value, px.value, true>, dim3(ntx, nty), dim3(256), p); },
-                         depth, composite_uses_px(ctx, ntx, nty));
+        variant_dispatch([&](auto d, auto px, auto ab) {
+            launch_kernel(ctx, NO_STAGE, k_composite_backward<d.value, px.value, true, ab.value>, dim3(ntx, nty), dim3(256), p);
+        }, depth, composite_uses_px(ctx, ntx, nty), abs);
         LAUNCH_CHECK(ctx, "launch k_composite_backward<DET>");
-        variant_dispatch([&](auto d) { launch_kernel(ctx, NO_STAGE, k_det_gather<d.value>, dim3(div_up(n, 256)), dim3(256), p, n); }, depth);
+        variant_dispatch([&](auto d, auto ab) { launch_kernel(ctx, NO_STAGE, k_det_gather<d.value, ab.value>, dim3(div_up(n, 256)), dim3(256), p, n); },
+                         depth, abs);
         return launch_check(ctx, "launch k_det_gather");
     }
-    // (<DEPTH, PX>: the kernel without DEPTH takes the BackParams part of p)
-    variant_dispatch([&](auto d, auto px) { launch_kernel(ctx, NO_STAGE, k_composite_backward<d.value, px.value>, dim3(ntx, nty), dim3(256), p); },
-                     depth, composite_uses_px(ctx, ntx, nty));
+    // (<DEPTH, PX, ABS>: the kernel without DEPTH or ABS takes the BackParams part of p)
+    variant_dispatch([&](auto d, auto px, auto ab) {
+        launch_kernel(ctx, NO_STAGE, k_composite_backward<d.value, px.value, false, ab.value>, dim3(ntx, nty), dim3(256), p);
+    }, depth, composite_uses_px(ctx, ntx, nty), abs);
     return launch_check(ctx, depth ? "launch k_composite_backward<DEPTH>" : "launch k_composite_backward");
 }
 
@@ -1082,6 +1124,32 @@ extern "C" int splat_composite_backward_det(splat_ctx *ctx, const splat_composit
     return composite_backward_launch(ctx, cfg, color_opacity, color_stride_vec4, records, tile_indices, tile_counts, tile_offsets, width, height,
                                      grad_rgba32f, n, grad_records, grad_color_opacity, depth, depth_f32, depth_stride_floats, grad_depth_f32,
                                      grad_depth, &det);
+}
+
+extern "C" int splat_composite_backward_abs(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4,
+                                            const void *records, const void *tile_indices, const void *tile_counts, const void *tile_offsets,
+                                            uint32_t width, uint32_t height, const void *grad_rgba32f, uint32_t n, void *grad_records,
+                                            void *grad_color_opacity, const void *depth_f32, uint32_t depth_stride_floats,
+                                            const void *grad_depth_f32, void *grad_depth, void *grad_center_abs) {
+    // (the det convention: colour only when the four depth arguments are all NULL / 0)
+    const bool depth = depth_f32 || depth_stride_floats || grad_depth_f32 || grad_depth;
+    return composite_backward_launch(ctx, cfg, color_opacity, color_stride_vec4, records, tile_indices, tile_counts, tile_offsets, width, height,
+                                     grad_rgba32f, n, grad_records, grad_color_opacity, depth, depth_f32, depth_stride_floats, grad_depth_f32,
+                                     grad_depth, nullptr, true, grad_center_abs);
+}
+
+extern "C" int splat_composite_backward_det_abs(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity,
+                                                uint32_t color_stride_vec4, const void *records, const void *projected, const void *tile_indices,
+                                                const void *tile_counts, const void *tile_offsets, uint64_t total_pairs, uint32_t width,
+                                                uint32_t height, const void *grad_rgba32f, uint32_t n, void *grad_records,
+                                                void *grad_color_opacity, const void *depth_f32, uint32_t depth_stride_floats,
+                                                const void *grad_depth_f32, void *grad_depth, void *workspace, uint64_t workspace_bytes,
+                                                void *grad_center_abs) {
+    const bool depth = depth_f32 || depth_stride_floats || grad_depth_f32 || grad_depth;
+    const DetArgs det = {projected, total_pairs, workspace, workspace_bytes};
+    return composite_backward_launch(ctx, cfg, color_opacity, color_stride_vec4, records, tile_indices, tile_counts, tile_offsets, width, height,
+                                     grad_rgba32f, n, grad_records, grad_color_opacity, depth, depth_f32, depth_stride_floats, grad_depth_f32,
+                                     grad_depth, &det, true, grad_center_abs);
 }
 
 extern "C" int splat_composite_contribution(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4,

@@ -18,7 +18,7 @@
 
 #include "../../include/splat.h"
 
-#define MAX_ARGS 22
+#define MAX_ARGS 24
 
 typedef struct {
     napi_env env;
@@ -418,6 +418,33 @@ FN(composite_backward_det) { /* (ctx, cfg[8], colorOpacity, cStride, records, pr
     return check(env, x, splat_composite_backward_det(x, &cfg, col, cs, rec, proj, idx, cnt, off, pairs, w, h, gimg, n, grec, gcol, z, zs, gdimg, gz,
                                                       ws, wb), mk_undefined(env));
 }
+FN(composite_backward_abs) { /* composite_backward_depth's arguments (depth|null, depthStrideFloats, gradDepthImage|null, gradDepth|null), then gradCenterAbs */
+    ARGS(19); splat_ctx *x = arg_external(&c, 0); splat_composite_cfg cfg; fill_cfg(&c, 1, &cfg);
+    void *col = arg_dptr(&c, 2); uint32_t cs = (uint32_t)arg_number(&c, 3); void *rec = arg_dptr(&c, 4);
+    void *idx = arg_dptr(&c, 5), *cnt = arg_dptr(&c, 6), *off = arg_dptr(&c, 7);
+    uint32_t w = (uint32_t)arg_number(&c, 8), h = (uint32_t)arg_number(&c, 9); void *gimg = arg_dptr(&c, 10);
+    uint32_t n = (uint32_t)arg_number(&c, 11); void *grec = arg_dptr(&c, 12), *gcol = arg_dptr(&c, 13);
+    void *z = arg_dptr(&c, 14); uint32_t zs = (uint32_t)arg_number(&c, 15); void *gdimg = arg_dptr(&c, 16), *gz = arg_dptr(&c, 17);
+    void *gabs = arg_dptr(&c, 18); BAIL;
+    return check(env, x, splat_composite_backward_abs(x, &cfg, col, cs, rec, idx, cnt, off, w, h, gimg, n, grec, gcol, z, zs, gdimg, gz, gabs),
+                 mk_undefined(env));
+}
+FN(composite_backward_det_abs_workspace_bytes) { /* (totalPairs, numTiles, n, withDepth) -> bytes */
+    ARGS(4); uint64_t pairs = (uint64_t)arg_number(&c, 0); uint32_t tiles = (uint32_t)arg_number(&c, 1), n = (uint32_t)arg_number(&c, 2);
+    int depth = (int)arg_number(&c, 3); BAIL;
+    return mk_number(env, (double)splat_composite_backward_det_abs_workspace_bytes(pairs, tiles, n, depth));
+}
+FN(composite_backward_det_abs) { /* composite_backward_det's arguments, then gradCenterAbs */
+    ARGS(23); splat_ctx *x = arg_external(&c, 0); splat_composite_cfg cfg; fill_cfg(&c, 1, &cfg);
+    void *col = arg_dptr(&c, 2); uint32_t cs = (uint32_t)arg_number(&c, 3); void *rec = arg_dptr(&c, 4), *proj = arg_dptr(&c, 5);
+    void *idx = arg_dptr(&c, 6), *cnt = arg_dptr(&c, 7), *off = arg_dptr(&c, 8); uint64_t pairs = (uint64_t)arg_number(&c, 9);
+    uint32_t w = (uint32_t)arg_number(&c, 10), h = (uint32_t)arg_number(&c, 11); void *gimg = arg_dptr(&c, 12);
+    uint32_t n = (uint32_t)arg_number(&c, 13); void *grec = arg_dptr(&c, 14), *gcol = arg_dptr(&c, 15);
+    void *z = arg_dptr(&c, 16); uint32_t zs = (uint32_t)arg_number(&c, 17); void *gdimg = arg_dptr(&c, 18), *gz = arg_dptr(&c, 19);
+    void *ws = arg_dptr(&c, 20); uint64_t wb = (uint64_t)arg_number(&c, 21); void *gabs = arg_dptr(&c, 22); BAIL;
+    return check(env, x, splat_composite_backward_det_abs(x, &cfg, col, cs, rec, proj, idx, cnt, off, pairs, w, h, gimg, n, grec, gcol, z, zs, gdimg,
+                                                          gz, ws, wb, gabs), mk_undefined(env));
+}
 FN(composite_contribution) { /* (ctx, cfg[8], colorOpacity, cStride, records, indices, counts, offsets, W, H, pixelWeight|null, minWeight, n, hits|null, weightMax|null, weightSum|null) */
     ARGS(16); splat_ctx *x = arg_external(&c, 0); splat_composite_cfg cfg; fill_cfg(&c, 1, &cfg);
     void *col = arg_dptr(&c, 2); uint32_t cs = (uint32_t)arg_number(&c, 3); void *rec = arg_dptr(&c, 4);
@@ -522,6 +549,12 @@ FN(density_accumulate) { /* (ctx, records, gradRecords, n, W, H, gradAccum, deno
     uint32_t n = (uint32_t)arg_number(&c, 3), w = (uint32_t)arg_number(&c, 4), h = (uint32_t)arg_number(&c, 5);
     void *ga = arg_dptr(&c, 6), *dn = arg_dptr(&c, 7), *mr = arg_dptr(&c, 8), *vis = arg_dptr(&c, 9); BAIL;
     return check(env, x, splat_density_accumulate(x, rec, gr, n, w, h, ga, dn, mr, vis), mk_undefined(env));
+}
+FN(density_accumulate_abs) { /* (ctx, records, gradCenterAbs, n, W, H, gradAccum, denom, maxRadius, visible) */
+    ARGS(10); splat_ctx *x = arg_external(&c, 0); void *rec = arg_dptr(&c, 1), *gr = arg_dptr(&c, 2);
+    uint32_t n = (uint32_t)arg_number(&c, 3), w = (uint32_t)arg_number(&c, 4), h = (uint32_t)arg_number(&c, 5);
+    void *ga = arg_dptr(&c, 6), *dn = arg_dptr(&c, 7), *mr = arg_dptr(&c, 8), *vis = arg_dptr(&c, 9); BAIL;
+    return check(env, x, splat_density_accumulate_abs(x, rec, gr, n, w, h, ga, dn, mr, vis), mk_undefined(env));
 }
 FN(densify_plan_workspace_bytes) { /* (n) -> bytes */
     ARGS(1); uint32_t n = (uint32_t)arg_number(&c, 0); BAIL;
@@ -889,6 +922,8 @@ static napi_value init(napi_env env, napi_value exports) {
         EXPORT(mcmc_sample_workspace_bytes), EXPORT(mcmc_sample), EXPORT(mcmc_apply), EXPORT(mcmc_noise),
         EXPORT(knn_workspace_bytes), EXPORT(knn_mean_sq),
         EXPORT(project_ellipsoid_aa), EXPORT(render_frame_ellipsoids_aa), EXPORT(project_ellipsoid_backward_aa), EXPORT(sampling_rate_max),
+        EXPORT(composite_backward_abs), EXPORT(composite_backward_det_abs_workspace_bytes), EXPORT(composite_backward_det_abs),
+        EXPORT(density_accumulate_abs),
     };
     napi_define_properties(env, exports, sizeof d / sizeof d[0], d);
     return exports;

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Gradients of ellipsoid frames (GPU box only): python tools/grad_bench.py [--depth] [--deterministic] [--antialiased] [--importance] [--camera | --loss | --optimizer] [C1,C2] [K] [R]
+"""Gradients of ellipsoid frames (GPU box only): python tools/grad_bench.py [--depth] [--deterministic] [--antialiased] [--importance] [--absgrad] [--camera | --loss | --optimizer] [C1,C2] [K] [R]
 
 tools/ellipsoid_bench.py's scenes and method (the scene's positions, sigma = radius / 2 per axis times a random factor in
 [e^-0.3, e^0.3], random rotations, SH of degree 3 with the scene's opacity; R rounds of K calls per kind, kinds alternating
@@ -32,6 +32,13 @@ splat_composite_contribution alone with all three outputs and no mask (composite
 blend weight per splat, integer atomics), and the one thing the library offered for the summed weight before it,
 splat_composite_backward with an upstream of ones in (r, g, b) and zero in alpha, whose colour column is that sum
 (composite_backward_ones: two walks, nine float sums per entry, float atomics); their ratio.
+
+--absgrad adds AbsGS's absolute screen-space gradient beside the plain backward, alternating in the same rounds:
+splat_composite_backward_abs alone, colour only (composite_backward_abs: the two extra wave sums per entry and their atomics
+into the n x 2 plane), with --depth also its depth variant (composite_backward_abs_depth), with --deterministic also
+splat_composite_backward_det_abs over its own, larger workspace (composite_backward_det_abs, and _depth with both), and the
+whole frame's backward with rasterize(..., absgrad=True) (backward_abs; with --deterministic backward_det_abs); each one's
+ratio to the entry point without the absolute sums, timed in the same rounds; the det workspaces' bytes.
 
 --camera adds the camera gradients: splat_project_ellipsoid_backward_camera without and with grad_depth (all of its launches:
 the per-splat kernel with the per-wave sums, then k_camera_sum_slices above 1024 partials, then k_camera_sum) beside
@@ -123,7 +130,8 @@ def torch_camera_terms(U, pos, scl, rot, g, W, H):
     return torch.stack(terms, dim=1).sum(dim=0)
 
 
-argv = [a for a in sys.argv[1:] if a not in ("--depth", "--camera", "--loss", "--optimizer", "--deterministic", "--antialiased", "--importance")]
+argv = [a for a in sys.argv[1:] if a not in ("--depth", "--camera", "--loss", "--optimizer", "--deterministic", "--antialiased", "--importance", "--absgrad")]
+abs_too = "--absgrad" in sys.argv[1:]
 aa_too = "--antialiased" in sys.argv[1:]
 importance_too = "--importance" in sys.argv[1:]
 det_too = "--deterministic" in sys.argv[1:]
@@ -543,6 +551,38 @@ for name in names:
         if depth_too:
             work["composite_backward_det_depth"] = det_entry(True)
 
+    if abs_too:
+        gabs = torch.zeros((n, 2), device="cuda")
+
+        def forward_abs(deterministic=False):
+            def go():
+                rec, aux = AG.project_ellipsoids(u, means, scales, rots)
+                col = AG.sh_colors(u[16:19], means, shs, 3, ops)
+                rgb, _ = AG.rasterize(rec, col, aux, w, h, deterministic=deterministic, absgrad=True)
+                state.update(rec=rec, col=col, aux=aux, loss=(rgb * gimg).sum())
+            return go
+
+        def abs_entry(depth):
+            tail = (zs.data_ptr(), 1, gdimg.data_ptr(), gz.data_ptr()) if depth else (None, 0, None, None)
+            return lambda: lib.splat_composite_backward_abs(cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr(), idx, cnt, off, w, h,
+                                                            g4.data_ptr(), n, grec.data_ptr(), gcol.data_ptr(), *tail, gabs.data_ptr())
+        work.update({"forward_abs": forward_abs(), "backward_abs": None, "composite_backward_abs": abs_entry(False)})
+        if depth_too:
+            work["composite_backward_abs_depth"] = abs_entry(True)
+        if det_too:
+            det_abs_bytes = {d: int(lib.splat_composite_backward_det_abs_workspace_bytes(pairs, tiles, n, d)) for d in (0, 1)}
+            det_abs_ws = torch.empty(det_abs_bytes[1] // 4 + 4, dtype=torch.int32, device="cuda")
+
+            def det_abs_entry(depth):
+                tail = (zs.data_ptr(), 1, gdimg.data_ptr(), gz.data_ptr()) if depth else (None, 0, None, None)
+                return lambda: lib.splat_composite_backward_det_abs(cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr(),
+                                                                    state["aux"].projected.data_ptr(), idx, cnt, off, pairs, w, h, g4.data_ptr(), n,
+                                                                    grec.data_ptr(), gcol.data_ptr(), *tail, det_abs_ws.data_ptr(),
+                                                                    det_abs_bytes[int(depth)], gabs.data_ptr())
+            work.update({"forward_det_abs": forward_abs(True), "backward_det_abs": None, "composite_backward_det_abs": det_abs_entry(False)})
+            if depth_too:
+                work["composite_backward_det_abs_depth"] = det_abs_entry(True)
+
     if importance_too:
         ones4 = torch.zeros((h, w, 4), device="cuda")
         ones4[..., :3] = 1.0
@@ -619,6 +659,10 @@ for name in names:
         forwards["backward_camera"] = forward_camera
     if det_too:
         forwards["backward_det"] = forward_det
+    if abs_too:
+        forwards["backward_abs"] = work["forward_abs"]
+        if det_too:
+            forwards["backward_det_abs"] = work["forward_det_abs"]
 
     def run(kind, calls):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -665,6 +709,20 @@ for name in names:
             extra.update({"det_workspace_bytes_depth": det_bytes[1],
                           "det_gather_floor_ms_depth": round((2 * 40 * written + 16 * tiles) / COPY_RATE * 1e3, 4),
                           "composite_backward_det_depth_over_atomic": round(med["composite_backward_det_depth"] / med["composite_backward_depth"], 3)})
+    if abs_too:
+        pairs_of = [("composite_backward_abs", "composite_backward"), ("backward_abs", "backward")]
+        if depth_too:
+            pairs_of.append(("composite_backward_abs_depth", "composite_backward_depth"))
+        if det_too:
+            pairs_of += [("composite_backward_det_abs", "composite_backward_det"), ("backward_det_abs", "backward_det")]
+            extra.update({"det_abs_workspace_bytes": det_abs_bytes[0]})
+            if depth_too:
+                pairs_of.append(("composite_backward_det_abs_depth", "composite_backward_det_depth"))
+                extra.update({"det_abs_workspace_bytes_depth": det_abs_bytes[1]})
+        for a, b in pairs_of:
+            if a.startswith("composite_"):
+                _lib.check(work[a](), cx.ctx)  # (the timed calls' return codes were not looked at)
+            extra[f"{a}_over_{b}"] = round(med[a] / med[b], 3)
     if importance_too:
         _lib.check(work["composite_contribution"](), cx.ctx)
         extra.update({"composite_contribution_over_backward_ones": round(med["composite_contribution"] / med["composite_backward_ones"], 3)})
