@@ -128,6 +128,7 @@ torch is imported when a function here is first called, so `import splat_rendere
 """
 import collections
 import ctypes as C
+import types
 
 import numpy as np
 
@@ -305,107 +306,92 @@ class ProjectedSplats:
         self.width, self.height = int(u[20]), int(u[21])
 
 
+def _ellipsoid_cfg():
+    """The one composite configuration the ellipsoid footprint's backward and contribution kernels accept."""
+    return CompositeCfg(_lib.MODE_FRONT_TO_BACK, 1, TILE, 0, _lib.U32_MAX, _lib.RECORDS_PROJECTED, 1, _lib.FOOTPRINT_ELLIPSOID)
+
+
+# Rasterize.backward's entry point: (deterministic, absgrad, a depth gradient arrived) -> its name.  The _det and _abs entry
+# points take the four depth arguments always (all NULL / 0: colour only).
+_COMPOSITE_BACKWARD = {
+    (False, False, False): "splat_composite_backward", (False, False, True): "splat_composite_backward_depth",
+    (False, True, False): "splat_composite_backward_abs", (False, True, True): "splat_composite_backward_abs",
+    (True, False, False): "splat_composite_backward_det", (True, False, True): "splat_composite_backward_det",
+    (True, True, False): "splat_composite_backward_det_abs", (True, True, True): "splat_composite_backward_det_abs",
+}
+
+
 def _functions():
-    """The autograd Functions, built on first use (torch imported then)."""
+    """The autograd Functions, by name, built on first use (torch imported then).  Each is applied with its full argument
+    list, and each backward returns one entry per argument (None for what is no tensor or needs no gradient)."""
     torch = _t()
     if "_fns" in globals():
         return globals()["_fns"]
 
     class Project(torch.autograd.Function):
+        """splat_project_ellipsoid, or with antialiased splat_project_ellipsoid_aa (the 2D Mip filter's factor rho beside the
+        records), and their backwards.  Returns (rec, [rho,] [depths,] aux)."""
+
         @staticmethod
-        def forward(fctx, u, means4, scales4, rots, with_depth=False, u_t=None):
+        def forward(fctx, u, means4, scales4, rots, with_depth, u_t, antialiased):
             # (u_t: the uniforms as the tensor that requires grad, or None; the kernels read the host copy u)
             cx = _context(means4)
             n = means4.shape[0]
+            dev = means4.device
             padded = cx.ensure_sorter(n)
-            rec = torch.empty((n, 8), device=means4.device, dtype=torch.float32)
-            proj = torch.empty((n, 8), device=means4.device, dtype=torch.float32)
-            keys = torch.empty(padded, device=means4.device, dtype=torch.int32)
-            pay = torch.empty(padded, device=means4.device, dtype=torch.int32)
-            if n:
-                check(cx.lib.splat_project_ellipsoid(cx.ctx, _fptr(u), means4.data_ptr(), 1, scales4.data_ptr(), 1, rots.data_ptr(), 1, n,
-                                                     proj.data_ptr(), rec.data_ptr(), keys.data_ptr(), pay.data_ptr(), padded), cx.ctx)
+            rec = torch.empty((n, 8), device=dev, dtype=torch.float32)
+            proj = torch.empty((n, 8), device=dev, dtype=torch.float32)
+            rho = torch.empty(n, device=dev, dtype=torch.float32) if antialiased else None
+            keys = torch.empty(padded, device=dev, dtype=torch.int32)
+            pay = torch.empty(padded, device=dev, dtype=torch.int32)
+            args = (cx.ctx, _fptr(u), means4.data_ptr(), 1, scales4.data_ptr(), 1, rots.data_ptr(), 1, n, proj.data_ptr(), rec.data_ptr(),
+                    keys.data_ptr(), pay.data_ptr(), padded)
+            if n and antialiased:
+                check(cx.lib.splat_project_ellipsoid_aa(*args, rho.data_ptr(), None, 1, None), cx.ctx)
+            elif n:
+                check(cx.lib.splat_project_ellipsoid(*args), cx.ctx)
             fctx.save_for_backward(means4, scales4, rots)
-            fctx.u, fctx.u_t = u, u_t
-            aux = ProjectedSplats(cx, u, n, proj, keys, pay)
+            fctx.u, fctx.u_t, fctx.with_depth, fctx.antialiased = u, u_t, with_depth, antialiased
+            fctx.set_materialize_grads(False)  # (an unused rho or depth: None, and the kernel without it)
+            out = [rec]
+            if antialiased:
+                out.append(rho)
             if with_depth:  # (the ProjectedSplat depth, as a tensor of its own: bit for bit aux.projected[:, 4])
-                fctx.set_materialize_grads(False)  # (an unused depth: None, and the colour-only kernel)
-                return rec, proj[:, 4].contiguous(), aux
-            return rec, aux
+                out.append(proj[:, 4].contiguous())
+            return (*out, ProjectedSplats(cx, u, n, proj, keys, pay))
 
         @staticmethod
         def backward(fctx, grad_rec, *grads):
-            grad_depth = grads[0] if len(grads) == 2 else None  # (rec, depths, aux) or (rec, aux)
-            means4, scales4, rots = fctx.saved_tensors
-            n = means4.shape[0]
-            cx = _context(means4)
-            g = _cuda_f32(grad_rec, "grad_records", 8) if grad_rec is not None else torch.zeros((n, 8), device=means4.device, dtype=torch.float32)
-            gp, gs, gr = (torch.empty((n, 4), device=means4.device, dtype=torch.float32) for _ in range(3))
-            if len(fctx.needs_input_grad) > 5 and fctx.needs_input_grad[5]:
-                gz = _cuda_f32(grad_depth.reshape(-1), "grad_depths") if grad_depth is not None else None
-                gu = torch.empty(24, device=means4.device, dtype=torch.float32)  # (22, and a 16-byte multiple)
-                check(cx.lib.splat_project_ellipsoid_backward_camera(cx.ctx, _fptr(fctx.u), means4.data_ptr(), 1, scales4.data_ptr(), 1,
-                                                                     rots.data_ptr(), 1, n, g.data_ptr(), gp.data_ptr(), gs.data_ptr(), gr.data_ptr(),
-                                                                     gz.data_ptr() if gz is not None and n else None, gu.data_ptr()), cx.ctx)
-                return None, gp, gs, gr, None, _like(gu, fctx.u_t)
-            if n and grad_depth is None:
-                check(cx.lib.splat_project_ellipsoid_backward(cx.ctx, _fptr(fctx.u), means4.data_ptr(), 1, scales4.data_ptr(), 1, rots.data_ptr(), 1,
-                                                              n, g.data_ptr(), gp.data_ptr(), gs.data_ptr(), gr.data_ptr()), cx.ctx)
-            elif n:
-                gz = _cuda_f32(grad_depth.reshape(-1), "grad_depths")
-                check(cx.lib.splat_project_ellipsoid_backward_depth(cx.ctx, _fptr(fctx.u), means4.data_ptr(), 1, scales4.data_ptr(), 1, rots.data_ptr(),
-                                                                    1, n, g.data_ptr(), gp.data_ptr(), gs.data_ptr(), gr.data_ptr(), gz.data_ptr()),
-                      cx.ctx)
-            return None, gp, gs, gr, None, None
-
-    class ProjectAA(torch.autograd.Function):
-        """Project with the 2D Mip filter's factor beside the records: splat_project_ellipsoid_aa and its backward."""
-
-        @staticmethod
-        def forward(fctx, u, means4, scales4, rots, with_depth=False, u_t=None):
-            cx = _context(means4)
-            n = means4.shape[0]
-            padded = cx.ensure_sorter(n)
-            rec = torch.empty((n, 8), device=means4.device, dtype=torch.float32)
-            proj = torch.empty((n, 8), device=means4.device, dtype=torch.float32)
-            rho = torch.empty(n, device=means4.device, dtype=torch.float32)
-            keys = torch.empty(padded, device=means4.device, dtype=torch.int32)
-            pay = torch.empty(padded, device=means4.device, dtype=torch.int32)
-            if n:
-                check(cx.lib.splat_project_ellipsoid_aa(cx.ctx, _fptr(u), means4.data_ptr(), 1, scales4.data_ptr(), 1, rots.data_ptr(), 1, n,
-                                                        proj.data_ptr(), rec.data_ptr(), keys.data_ptr(), pay.data_ptr(), padded, rho.data_ptr(),
-                                                        None, 1, None), cx.ctx)
-            fctx.save_for_backward(means4, scales4, rots)
-            fctx.u, fctx.u_t, fctx.with_depth = u, u_t, bool(with_depth)
-            fctx.set_materialize_grads(False)  # (an unused rho or depth: None)
-            aux = ProjectedSplats(cx, u, n, proj, keys, pay)
-            if with_depth:
-                return rec, rho, proj[:, 4].contiguous(), aux
-            return rec, rho, aux
-
-        @staticmethod
-        def backward(fctx, grad_rec, grad_rho, *grads):
-            grad_depth = grads[0] if fctx.with_depth else None  # (rec, rho, depths, aux) or (rec, rho, aux)
+            grads = list(grads[:-1])  # ([rho,] [depths]; the last is aux's)
+            grad_rho = grads.pop(0) if fctx.antialiased else None
+            grad_depth = grads.pop(0) if fctx.with_depth else None
             means4, scales4, rots = fctx.saved_tensors
             n = means4.shape[0]
             cx = _context(means4)
             dev = means4.device
+            cam = fctx.needs_input_grad[5]
             g = _cuda_f32(grad_rec, "grad_records", 8) if grad_rec is not None else torch.zeros((n, 8), device=dev, dtype=torch.float32)
-            grho = _cuda_f32(grad_rho.reshape(-1), "grad_rho") if grad_rho is not None else torch.zeros(n, device=dev, dtype=torch.float32)
             gz = _cuda_f32(grad_depth.reshape(-1), "grad_depths") if grad_depth is not None else None
             gp, gs, gr = (torch.empty((n, 4), device=dev, dtype=torch.float32) for _ in range(3))
-            cam = len(fctx.needs_input_grad) > 5 and fctx.needs_input_grad[5]
             gu = torch.empty(24, device=dev, dtype=torch.float32) if cam else None  # (22, and a 16-byte multiple)
-            if n or cam:
-                check(cx.lib.splat_project_ellipsoid_backward_aa(cx.ctx, _fptr(fctx.u), means4.data_ptr(), 1, scales4.data_ptr(), 1,
-                                                                 rots.data_ptr(), 1, n, g.data_ptr(), gp.data_ptr(), gs.data_ptr(), gr.data_ptr(),
-                                                                 gz.data_ptr() if gz is not None and n else None,
-                                                                 gu.data_ptr() if cam else None, grho.data_ptr()), cx.ctx)
-            return None, gp, gs, gr, None, (_like(gu, fctx.u_t) if cam else None)
+            args = (cx.ctx, _fptr(fctx.u), means4.data_ptr(), 1, scales4.data_ptr(), 1, rots.data_ptr(), 1, n, g.data_ptr(), gp.data_ptr(),
+                    gs.data_ptr(), gr.data_ptr())
+            gz_ptr = gz.data_ptr() if gz is not None and n else None
+            if fctx.antialiased:
+                grho = _cuda_f32(grad_rho.reshape(-1), "grad_rho") if grad_rho is not None else torch.zeros(n, device=dev, dtype=torch.float32)
+                if n or cam:
+                    check(cx.lib.splat_project_ellipsoid_backward_aa(*args, gz_ptr, gu.data_ptr() if cam else None, grho.data_ptr()), cx.ctx)
+            elif cam:
+                check(cx.lib.splat_project_ellipsoid_backward_camera(*args, gz_ptr, gu.data_ptr()), cx.ctx)
+            elif n and gz is None:
+                check(cx.lib.splat_project_ellipsoid_backward(*args), cx.ctx)
+            elif n:
+                check(cx.lib.splat_project_ellipsoid_backward_depth(*args, gz_ptr), cx.ctx)
+            return None, gp, gs, gr, None, (_like(gu, fctx.u_t) if cam else None), None
 
     class ShColors(torch.autograd.Function):
         @staticmethod
-        def forward(fctx, eye, means4, sh, degree, opacities, eye_t=None):
+        def forward(fctx, eye, means4, sh, degree, opacities, eye_t):
             # (eye_t: the eye as the tensor that requires grad, or None; the kernels read the host copy eye)
             cx = _context(means4)
             n = means4.shape[0]
@@ -422,104 +408,90 @@ def _functions():
             means4, sh, opacities = fctx.saved_tensors
             n = means4.shape[0]
             cx = _context(means4)
+            cam = fctx.needs_input_grad[5]
             g = _cuda_f32(grad_col, "grad_color_opacity", 4)
             gsh = torch.zeros_like(sh)
             gp = torch.empty((n, 4), device=means4.device, dtype=torch.float32)
             gop = torch.empty(n, device=means4.device, dtype=torch.float32)
-            if len(fctx.needs_input_grad) > 5 and fctx.needs_input_grad[5]:
-                ge = torch.empty(4, device=means4.device, dtype=torch.float32)
-                check(cx.lib.splat_sh_colors_backward_camera(cx.ctx, _fptr(fctx.eye), means4.data_ptr(), 1, sh.data_ptr(), sh.shape[1], fctx.degree,
-                                                             opacities.data_ptr(), g.data_ptr(), n, gsh.data_ptr(), gp.data_ptr(), gop.data_ptr(),
-                                                             ge.data_ptr()), cx.ctx)
-                return None, gp, gsh, None, gop, _like(ge, fctx.eye_t)
-            if n:
-                check(cx.lib.splat_sh_colors_backward(cx.ctx, _fptr(fctx.eye), means4.data_ptr(), 1, sh.data_ptr(), sh.shape[1], fctx.degree,
-                                                      opacities.data_ptr(), g.data_ptr(), n, gsh.data_ptr(), gp.data_ptr(), gop.data_ptr()), cx.ctx)
-            return None, gp, gsh, None, gop, None
+            ge = torch.empty(4, device=means4.device, dtype=torch.float32) if cam else None
+            args = (cx.ctx, _fptr(fctx.eye), means4.data_ptr(), 1, sh.data_ptr(), sh.shape[1], fctx.degree, opacities.data_ptr(), g.data_ptr(), n,
+                    gsh.data_ptr(), gp.data_ptr(), gop.data_ptr())
+            if cam:
+                check(cx.lib.splat_sh_colors_backward_camera(*args, ge.data_ptr()), cx.ctx)
+            elif n:
+                check(cx.lib.splat_sh_colors_backward(*args), cx.ctx)
+            return None, gp, gsh, None, gop, (_like(ge, fctx.eye_t) if cam else None)
 
     class Rasterize(torch.autograd.Function):
         @staticmethod
-        def forward(fctx, rec, col, aux, width, height, depths=None, deterministic=False, absgrad=False):
+        def forward(fctx, rec, col, aux, width, height, depths, deterministic, absgrad):
             cx = aux.ctx
-            n = aux.n
             out = torch.empty((height, width, 4), device=rec.device, dtype=torch.float32)
             alpha = torch.empty((height, width), device=rec.device, dtype=torch.float32)
             gen = cx.bin(aux, width, height)
             idx, cnt, off = cx.lists()
-            cfg = CompositeCfg(_lib.MODE_FRONT_TO_BACK, 1, TILE, 0, _lib.U32_MAX, _lib.RECORDS_PROJECTED, 1, _lib.FOOTPRINT_ELLIPSOID)
+            cfg = _ellipsoid_cfg()
+            depth = torch.empty((height, width), device=rec.device, dtype=torch.float32) if depths is not None else None
+            aov = _lib.Aov(depth.data_ptr() if depth is not None else None, alpha.data_ptr(), None)
+            args = (cx.ctx, C.byref(cfg), col.data_ptr(), 1, None, 1, rec.data_ptr(), idx, cnt, off, width, height, None, out.data_ptr(), None,
+                    C.byref(aov))
             if depths is None:
-                aov = _lib.Aov(None, alpha.data_ptr(), None)
-                check(cx.lib.splat_composite_aov(cx.ctx, C.byref(cfg), col.data_ptr(), 1, None, 1, rec.data_ptr(), idx, cnt, off, width, height,
-                                                 None, out.data_ptr(), None, C.byref(aov)), cx.ctx)
-                fctx.save_for_backward(rec, col)
+                check(cx.lib.splat_composite_aov(*args), cx.ctx)
             else:
-                depth = torch.empty((height, width), device=rec.device, dtype=torch.float32)
-                aov = _lib.Aov(depth.data_ptr(), alpha.data_ptr(), None)
-                check(cx.lib.splat_composite_aov_depth(cx.ctx, C.byref(cfg), col.data_ptr(), 1, None, 1, rec.data_ptr(), idx, cnt, off, width,
-                                                       height, None, out.data_ptr(), None, C.byref(aov), depths.data_ptr(), 1), cx.ctx)
-                fctx.save_for_backward(rec, col, depths)
-                fctx.set_materialize_grads(False)  # (an unused depth map: None, and the colour-only kernel)
+                check(cx.lib.splat_composite_aov_depth(*args, depths.data_ptr(), 1), cx.ctx)
+            fctx.save_for_backward(rec, col, depths)
+            fctx.set_materialize_grads(False)  # (an unused depth map: None, and the colour-only kernel)
             fctx.aux, fctx.gen, fctx.wh = aux, gen, (width, height)
-            fctx.deterministic = bool(deterministic)
-            fctx.absgrad = bool(absgrad)
+            fctx.deterministic, fctx.absgrad = deterministic, absgrad
             rgb = out[..., :3]
             return (rgb, alpha) if depths is None else (rgb, alpha, depth)
 
         @staticmethod
         def backward(fctx, grad_rgb, grad_alpha, grad_depth_map=None):
-            rec, col = fctx.saved_tensors[:2]
-            depths = fctx.saved_tensors[2] if len(fctx.saved_tensors) == 3 else None
+            rec, col, depths = fctx.saved_tensors
             aux = fctx.aux
             cx = aux.ctx
+            dev = rec.device
             width, height = fctx.wh
             n = aux.n
             if cx.generation != fctx.gen:  # the binner has binned another frame since: rebuild this frame's lists (deterministic)
                 fctx.gen = cx.bin(aux, width, height)
             idx, cnt, off = cx.lists()
-            g = torch.zeros((height, width, 4), device=rec.device, dtype=torch.float32)
+            g = torch.zeros((height, width, 4), device=dev, dtype=torch.float32)
             if grad_rgb is not None:
                 g[..., :3] = grad_rgb
             if grad_alpha is not None:
                 g[..., 3] = grad_alpha
-            grec = torch.zeros((n, 8), device=rec.device, dtype=torch.float32)
-            gcol = torch.zeros((n, 4), device=rec.device, dtype=torch.float32)
-            cfg = CompositeCfg(_lib.MODE_FRONT_TO_BACK, 1, TILE, 0, _lib.U32_MAX, _lib.RECORDS_PROJECTED, 1, _lib.FOOTPRINT_ELLIPSOID)
-            if fctx.deterministic or fctx.absgrad:
-                # deterministic: the fixed-order sums, splat_composite_backward_det over a workspace sized from the lists' pairs;
-                # absgrad: the signed sums and beside them sum |term c.x|, sum |term c.y|, the _abs twin of either entry point
-                sfx = "_abs" if fctx.absgrad else ""
-                with_depth = depths is not None and grad_depth_map is not None
-                gd = _cuda_f32(grad_depth_map, "grad_depth") if with_depth else None
-                gz = torch.zeros(n, device=rec.device, dtype=torch.float32) if with_depth else None
-                gabs = torch.zeros((n, 2), device=rec.device, dtype=torch.float32) if fctx.absgrad else None
-                dargs = (depths.data_ptr() if with_depth else None, 1 if with_depth else 0, gd.data_ptr() if with_depth else None,
-                         gz.data_ptr() if with_depth else None)
-                tail = (gabs.data_ptr(),) if fctx.absgrad else ()
-                if n and fctx.deterministic:
-                    tiles = ((width + TILE - 1) // TILE) * ((height + TILE - 1) // TILE)
-                    nbytes = int(getattr(cx.lib, f"splat_composite_backward_det{sfx}_workspace_bytes")(cx.total, tiles, n, int(with_depth)))
-                    ws = torch.empty((nbytes + 15) // 16 * 4, device=rec.device, dtype=torch.int32)
-                    check(getattr(cx.lib, f"splat_composite_backward_det{sfx}")(
-                        cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr(), aux.projected.data_ptr(), idx, cnt, off, cx.total, width, height,
-                        g.data_ptr(), n, grec.data_ptr(), gcol.data_ptr(), *dargs, ws.data_ptr(), nbytes, *tail), cx.ctx)
-                elif n:
-                    check(cx.lib.splat_composite_backward_abs(cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr(), idx, cnt, off, width, height,
-                                                              g.data_ptr(), n, grec.data_ptr(), gcol.data_ptr(), *dargs, *tail), cx.ctx)
-                if fctx.absgrad:
-                    aux.absgrad = gabs
-                return (grec, gcol, None, None, None, gz, None) + (None,) * len(tail)
-            if depths is None or grad_depth_map is None:
-                if n:
-                    check(cx.lib.splat_composite_backward(cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr(), idx, cnt, off, width, height,
-                                                          g.data_ptr(), n, grec.data_ptr(), gcol.data_ptr()), cx.ctx)
-                return grec, gcol, None, None, None, None
-            gd = _cuda_f32(grad_depth_map, "grad_depth")
-            gz = torch.zeros(n, device=rec.device, dtype=torch.float32)
+            grec = torch.zeros((n, 8), device=dev, dtype=torch.float32)
+            gcol = torch.zeros((n, 4), device=dev, dtype=torch.float32)
+            det, absgrad = fctx.deterministic, fctx.absgrad
+            with_depth = depths is not None and grad_depth_map is not None
+            gd = _cuda_f32(grad_depth_map, "grad_depth") if with_depth else None
+            gz = torch.zeros(n, device=dev, dtype=torch.float32) if with_depth else None
+            # absgrad: beside the signed sums, sum |term c.x| and sum |term c.y|, left on the projection
+            gabs = torch.zeros((n, 2), device=dev, dtype=torch.float32) if absgrad else None
             if n:
-                check(cx.lib.splat_composite_backward_depth(cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr(), idx, cnt, off, width, height,
-                                                            g.data_ptr(), n, grec.data_ptr(), gcol.data_ptr(), depths.data_ptr(), 1, gd.data_ptr(),
-                                                            gz.data_ptr()), cx.ctx)
-            return grec, gcol, None, None, None, gz
+                name = _COMPOSITE_BACKWARD[det, absgrad, with_depth]
+                cfg = _ellipsoid_cfg()
+                head, lists = [cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr()], [idx, cnt, off]
+                frame = [width, height, g.data_ptr(), n, grec.data_ptr(), gcol.data_ptr()]
+                if with_depth:
+                    frame += [depths.data_ptr(), 1, gd.data_ptr(), gz.data_ptr()]
+                elif det or absgrad:
+                    frame += [None, 0, None, None]
+                if det:  # the fixed-order sums: the ProjectedSplats, the lists' pairs and a workspace sized from them
+                    tiles = ((width + TILE - 1) // TILE) * ((height + TILE - 1) // TILE)
+                    nbytes = int(getattr(cx.lib, name + "_workspace_bytes")(cx.total, tiles, n, int(with_depth)))
+                    ws = torch.empty((nbytes + 15) // 16 * 4, device=dev, dtype=torch.int32)
+                    args = head + [aux.projected.data_ptr()] + lists + [cx.total] + frame + [ws.data_ptr(), nbytes]
+                else:
+                    args = head + lists + frame
+                if absgrad:
+                    args.append(gabs.data_ptr())
+                check(getattr(cx.lib, name)(*args), cx.ctx)
+            if absgrad:
+                aux.absgrad = gabs
+            return grec, gcol, None, None, None, gz, None, None
 
     class PhotometricLoss(torch.autograd.Function):
         @staticmethod
@@ -532,7 +504,7 @@ def _functions():
             ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32) if nbytes else None
             check(cx.lib.splat_image_loss(cx.ctx, x.data_ptr(), xs, y.data_ptr(), ys, w, h, lam, ws.data_ptr() if nbytes else None, nbytes,
                                           out.data_ptr()), cx.ctx)
-            fctx.save_for_backward(x, y, *([ws] if nbytes else []))
+            fctx.save_for_backward(x, y, ws)
             fctx.args = (xs, ys, lam, nbytes)
             fctx.set_materialize_grads(False)
             loss, l1, ssim = out[0], out[1], out[2]
@@ -543,19 +515,17 @@ def _functions():
         def backward(fctx, grad_loss, *_):
             if grad_loss is None:
                 return (None,) * 6
-            x, y = fctx.saved_tensors[:2]
+            x, y, ws = fctx.saved_tensors
             xs, ys, lam, nbytes = fctx.args
             cx = _context(x)
             h, w = x.shape[0], x.shape[1]
             up = grad_loss.to(torch.float32).reshape(1).contiguous()
             g = torch.empty((h, w, 3), device=x.device, dtype=torch.float32)
             check(cx.lib.splat_image_loss_backward(cx.ctx, x.data_ptr(), xs, y.data_ptr(), ys, w, h, lam,
-                                                   fctx.saved_tensors[2].data_ptr() if nbytes and lam > 0.0 else None, nbytes, up.data_ptr(),
-                                                   g.data_ptr(), 3), cx.ctx)
+                                                   ws.data_ptr() if nbytes and lam > 0.0 else None, nbytes, up.data_ptr(), g.data_ptr(), 3), cx.ctx)
             return g, None, None, None, None, None
 
-    fns = (Project, ShColors, Rasterize, PhotometricLoss, ProjectAA)
-    globals()["_fns"] = fns
+    fns = globals()["_fns"] = types.SimpleNamespace(Project=Project, ShColors=ShColors, Rasterize=Rasterize, PhotometricLoss=PhotometricLoss)
     return fns
 
 
@@ -573,13 +543,7 @@ def project_ellipsoids(uniforms, means, scales, rotations, width=None, height=No
     rots = _cuda_f32(rotations, "rotations", 4)
     if not (means4.shape[0] == scales4.shape[0] == rots.shape[0]):
         raise SplatError(-1, "means, scales and rotations must hold the same number of splats")
-    if antialiased:
-        if u_t is not None:
-            return _functions()[4].apply(u, means4, scales4, rots, bool(return_depth), u_t)
-        return _functions()[4].apply(u, means4, scales4, rots, bool(return_depth))
-    if u_t is not None:
-        return _functions()[0].apply(u, means4, scales4, rots, bool(return_depth), u_t)
-    return _functions()[0].apply(u, means4, scales4, rots, bool(return_depth))
+    return _functions().Project.apply(u, means4, scales4, rots, bool(return_depth), u_t, bool(antialiased))
 
 
 def sh_colors(eye, means, sh, degree, opacities):
@@ -598,9 +562,7 @@ def sh_colors(eye, means, sh, degree, opacities):
     op = _cuda_f32(opacities.reshape(-1), "opacities")
     if op.shape[0] != n:
         raise SplatError(-1, "opacities must hold one value per splat")
-    if e_t is not None:
-        return _functions()[1].apply(e, means4, sh2, int(degree), op, e_t)
-    return _functions()[1].apply(e, means4, sh2, int(degree), op)
+    return _functions().ShColors.apply(e, means4, sh2, int(degree), op, e_t)
 
 
 def rasterize(rec, col, aux, width=None, height=None, depths=None, deterministic=False, absgrad=False):
@@ -619,15 +581,7 @@ def rasterize(rec, col, aux, width=None, height=None, depths=None, deterministic
         z = _cuda_f32(depths, "depths")
         if z.dim() != 1 or z.shape[0] != aux.n:
             raise SplatError(-1, f"depths must have shape ({aux.n},), not {tuple(z.shape)}")
-    if absgrad:
-        return _functions()[2].apply(rec_c, col_c, aux, width, height, z, bool(deterministic), True)
-    if z is None:
-        if deterministic:
-            return _functions()[2].apply(rec_c, col_c, aux, width, height, None, True)
-        return _functions()[2].apply(rec_c, col_c, aux, width, height)
-    if deterministic:
-        return _functions()[2].apply(rec_c, col_c, aux, width, height, z, True)
-    return _functions()[2].apply(rec_c, col_c, aux, width, height, z)
+    return _functions().Rasterize.apply(rec_c, col_c, aux, width, height, z, bool(deterministic), bool(absgrad))
 
 
 def render_gaussians(camera_or_uniforms, means, scales, rotations, opacities, colors=None, sh=None, width=None, height=None, degree=None,
@@ -646,17 +600,10 @@ def render_gaussians(camera_or_uniforms, means, scales, rotations, opacities, co
     u = _uniforms(camera_or_uniforms, width, height)
     u_t = _grad_uniforms(camera_or_uniforms)
     pu = (camera_or_uniforms, means, scales, rotations, width, height) if u_t is not None else (u, means, scales, rotations)
-    rho = None
-    if antialiased and return_depth:
-        rec, rho, depths, aux = project_ellipsoids(*pu, return_depth=True, antialiased=True)
-    elif antialiased:
-        rec, rho, aux = project_ellipsoids(*pu, antialiased=True)
-        depths = None
-    elif return_depth:
-        rec, depths, aux = project_ellipsoids(*pu, return_depth=True)
-    else:
-        rec, aux = project_ellipsoids(*pu)
-        depths = None
+    out = project_ellipsoids(*pu, return_depth=return_depth, antialiased=antialiased)  # (rec, [rho,] [depths,] aux)
+    rec, aux = out[0], out[-1]
+    rho = out[1] if antialiased else None
+    depths = out[-2] if return_depth else None
     n = aux.n
     if sh is not None:
         k = sh.reshape(n, -1).shape[1] // 3
@@ -671,10 +618,7 @@ def render_gaussians(camera_or_uniforms, means, scales, rotations, opacities, co
         raise SplatError(-1, "render_gaussians needs colors or sh")
     if rho is not None:
         col = compensate_opacity(col, rho)
-    if absgrad:
-        out = rasterize(rec, col, aux, width, height, depths=depths, deterministic=deterministic, absgrad=True)
-    else:
-        out = rasterize(rec, col, aux, width, height, depths=depths, deterministic=deterministic)
+    out = rasterize(rec, col, aux, width, height, depths=depths, deterministic=deterministic, absgrad=absgrad)
     return (*out, aux) if return_aux else out
 
 
@@ -718,7 +662,7 @@ def contribution(rec, col, aux, width=None, height=None, pixel_weight=None, min_
         cx = aux.ctx
         cx.bin(aux, width, height)
         idx, cnt, off = cx.lists()
-        cfg = CompositeCfg(_lib.MODE_FRONT_TO_BACK, 1, TILE, 0, _lib.U32_MAX, _lib.RECORDS_PROJECTED, 1, _lib.FOOTPRINT_ELLIPSOID)
+        cfg = _ellipsoid_cfg()
         check(cx.lib.splat_composite_contribution(cx.ctx, C.byref(cfg), col_c.data_ptr(), 1, rec_c.data_ptr(), idx, cnt, off, width, height,
                                                   pw.data_ptr() if pw is not None else None, float(min_weight), n, out.hits.data_ptr(),
                                                   out.weight_max.data_ptr(), out.weight_sum.data_ptr()), cx.ctx)
@@ -754,7 +698,7 @@ def photometric_loss(rgb, target, lambda_dssim=0.2, return_terms=False):
     if x.device != y.device:
         raise SplatError(-1, f"rgb is on {x.device} and target on {y.device}")
     lam = float(lambda_dssim)
-    loss, l1, ssim = _functions()[3].apply(x, xs, y.detach(), ys, lam, bool(return_terms))
+    loss, l1, ssim = _functions().PhotometricLoss.apply(x, xs, y.detach(), ys, lam, bool(return_terms))
     return (loss, l1, ssim) if return_terms else loss
 
 

@@ -135,7 +135,7 @@ def symmetric_perturbation(w=SYM_W, h=SYM_H):
 def one_splat_sums(rec, col, g, w=SYM_W, h=SYM_H):
     """(signed (2,), absolute (2,)) float64: the sums over the pixels inside the cut of term c.x, term c.y and of their absolute
     values, added one by one in pixel order, of a frame of ONE splat with record rec (8,) and colour col (4,) under the
-    upstream g (h, w, 4).  Every pixel has T = 1 and S = G . bg (nothing is behind the splat): grad.hip's formulas with T_i = 1."""
+    upstream g (h, w, 4).  Every pixel has T = 1 and S = G . bg (nothing is behind the splat): composite_grad.hip's formulas with T_i = 1."""
     r, c = np.asarray(rec, np.float64), np.asarray(col, np.float64)
     y, x = np.mgrid[0:h, 0:w].astype(np.float64) + 0.5
     dx, dy = x - r[0], y - r[1]

@@ -1,4 +1,4 @@
-"""The composite backward pair by pair (csrc/grad.hip, k_composite_backward's second walk), in NumPy, over the pairs that
+"""The composite backward pair by pair (csrc/composite_grad.hip, k_composite_backward's second walk), in NumPy, over the pairs that
 tests/ellipsoid_grad_ref.decisions records: what every (pixel, splat) pair adds to the splat's nine gradient numbers (c.x, c.y,
 B00, B01, B11, r, g, b, opacity) and, with a depth map, to a tenth (dL/dz).
 
@@ -17,7 +17,7 @@ scene()     four scenes with everything the tests need, computed once and shared
             pairs and the early-out rarely fires), `veil` (hazy in front of an opaque backdrop: pixels stop deep in their lists,
             off the 64-entry chunk boundaries) and `needle` (two axes of 0.0005: cond(Sigma2) up to 1.6e4).
 
-The depth variant carries D = sum w z / sum w as grad.hip's header describes: a fifth channel of colour z_i - D, background 0 and
+The depth variant carries D = sum w z / sum w as composite_grad.hip's header describes: a fifth channel of colour z_i - D, background 0 and
 upstream G_D / ws, and the tenth number w_i G_D / ws.
 """
 import functools
@@ -36,7 +36,7 @@ REC_COLS = (0, 1, 2, 3, 5)           # the columns of grad_records that sums[:, 
 NAMES = ("c.x", "c.y", "B00", "B01", "B11", "r", "g", "b", "opacity", "z")
 EXP2_SCALE = F(-6.492127684000335)   # composite.h's ELLIPSOID_EXP2_SCALE: exp(-4.5 d2) = exp2(d2 * this)
 TILE = 16
-GCH = 64                             # grad.hip's chunk of staged entries
+GCH = 64                             # composite_grad.hip's chunk of staged entries
 SCENES = ("hazy", "veil", "needle", "classic")
 ORDERS = ("quadrant", "px")
 

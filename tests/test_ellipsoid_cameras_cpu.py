@@ -17,7 +17,7 @@ from tests.test_ellipsoid_cpu import screen64, sigma2_64
 W, H = 160, 120
 MAX_EXCLUDED = 0.10   # of the frame's pixels may be rim | near (skipped by the image tests)
 MIN_ON_SCREEN = 400   # splats whose 3 sigma box meets the screen
-GCH = 64              # grad.hip's staged chunk: one tile list must be longer, so the composite backward's chunk loop turns over
+GCH = 64              # composite_grad.hip's staged chunk: one tile list must be longer, so the composite backward's chunk loop turns over
 # the scenes tests/test_gpu_ellipsoid_cameras.py renders and differentiates: name -> (n, w, h, seed, spread, scale, degenerate)
 SCENES = {
     "frames": (3000, W, H, 1, 1.0, 0.03, True),

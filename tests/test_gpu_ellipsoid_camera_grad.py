@@ -92,7 +92,7 @@ def _check_block(got, want, eye_expected, label):
         assert (bits(g[16:19]) == 0).all(), f"{label}: eye not zero without grad_depth"
 
 
-# grad.hip sums up to CAM_DIRECT = 1024 per-wave partials (4 per 256 splats) with k_camera_sum alone and more through
+# splat_grad.hip sums up to CAM_DIRECT = 1024 per-wave partials (4 per 256 splats) with k_camera_sum alone and more through
 # k_camera_sum_slices first: 70 001 splats give 1096 partials, slices of 18 in sixteenths of 2, ragged and empty tails
 TWO_LEVEL = (70001, 333, 200, 12, 1.0, 0.02)
 assert 4 * -(-TWO_LEVEL[0] // 256) > 1024 >= 4 * -(-max(c[0] for c in TG.CASES[:4]) // 256)
