@@ -275,15 +275,7 @@ static void sorter_free_members(splat_sorter *s) {
 }
 
 int binner_reserve_range32(splat_binner *b, uint32_t n_splats) {
-    splat_ctx *ctx = b->ctx;
-    if (n_splats <= b->range32_cap) return SPLAT_OK;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (b->range32) (void)hipFree(b->range32);
-    b->range32 = nullptr;
-    b->range32_cap = 0;
-    if (hipMalloc((void **)&b->range32, (size_t)n_splats * 4 + 16) != hipSuccess) return ctx_fail(ctx, SPLAT_ERR_OOM, "binner hipMalloc");
-    b->range32_cap = n_splats;
-    return SPLAT_OK;
+    return device_reserve(b->ctx, &b->range32, &b->range32_cap, n_splats, (size_t)n_splats * 4 + 16, "binner hipMalloc");
 }
 
 // (one buffer for both: a binner renders one screen at a time)
@@ -351,10 +343,13 @@ int binner_reserve(splat_binner *b, uint32_t tiles, uint32_t n_sorted) {
 // same BinParams (frame path); otherwise ranges are derived from the projected bounds here.
 // depth_keys (frame path, with range32): per splat index, its depth key — selects the tile-first
 // order of work (tile_first.hip): `sorted` is then unused, the lists are depth-sorted per tile.
-int binner_run(splat_binner *b, const void *projected, uint32_t n_splats, const void *sorted, uint32_t n_sorted, uint32_t width,
-               uint32_t height, uint32_t tile_row0, uint32_t tile_row1, const uint32_t *range32, const uint32_t *n_sorted_dev,
-               const uint32_t *depth_keys, const uint2 *range_wide) {
+int binner_run(splat_binner *b, const BinRunArgs &a) {
     splat_ctx *ctx = b->ctx;
+    // (under the names the argument checks quote)
+    const void *projected = a.projected, *sorted = a.sorted;
+    const uint32_t n_splats = a.n_splats, n_sorted = a.n_sorted, width = a.width, height = a.height;
+    const uint32_t *range32 = a.range32, *n_sorted_dev = a.n_sorted_dev, *depth_keys = a.depth_keys;
+    const uint2 *range_wide = a.range_wide;
     const bool tile_first = depth_keys != nullptr;
     // what the caller prepared for THIS run (its projector's histogram; a band's compacted splats) is taken and cleared before
     // anything can return: a call that fails below must not leave it for another frame function's run
@@ -367,11 +362,10 @@ int binner_run(splat_binner *b, const void *projected, uint32_t n_splats, const 
     ARG_CHECK(ctx, n_sorted == 0 || (projected && (sorted || tile_first)));
     ARG_CHECK(ctx, !tile_first || (range32 && n_sorted == n_splats && !n_sorted_dev));
     ARG_CHECK(ctx, !range_wide || (!range32 && !tile_first));
-    const uint32_t ntx = div_up(width, b->tile), nty = div_up(height, b->tile); // GPUTileBinner.ts:198-200
+    const TileBand band = tile_band(width, height, b->tile, a.tile_row0, a.tile_row1);
+    const uint32_t ntx = band.ntx, nty = band.nty, tile_row0 = band.row0, tile_row1 = band.row1;
     ARG_CHECK(ctx, ntx <= 65535 && nty <= 65535 && (uint64_t)ntx * nty <= (1u << 24));
-    const uint32_t tiles = ntx * nty;
-    if (tile_row1 > nty) tile_row1 = nty;
-    if (tile_row0 > tile_row1) tile_row0 = tile_row1;
+    const uint32_t tiles = band.tiles();
     const uint32_t blocks = div_up(n_sorted, BIN_BLOCK);
 
     int rc = binner_reserve(b, tiles, n_sorted);
@@ -379,7 +373,7 @@ int binner_run(splat_binner *b, const void *projected, uint32_t n_splats, const 
     b->ntx = ntx;
     b->nty = nty;
     b->ran = false;
-    const BinParams bp = {width, height, b->tile, ntx, nty, tile_row0, tile_row1};
+    const BinParams bp = bin_params(width, height, b->tile, band, false);
 
     // the previous frame's async readback (if any): learn its pair total, detect overflow
     rc = binner_settle(b);
@@ -449,18 +443,26 @@ int binner_run(splat_binner *b, const void *projected, uint32_t n_splats, const 
         // kernel, the composite (report_for_composite): the flags then include the per-tile sort's order check, which is
         // what allows these kernels to rank with returning LDS atomics (common.h: rank_atomic_ok).  The report is examined
         // at the next call (binner_settle).
+        TfScatterArgs sc;
+        sc.range32 = range32, sc.depth_keys = depth_keys, sc.n = n_splats, sc.ntx = ntx, sc.mask = (1u << tf_lo_bits) - 1u;
+        sc.hist = b->tf_hist, sc.d_total = b->d_total, sc.pair_limit = b->pair_limit, sc.overflow = b->d_total + 1;
+        sc.out_hi = b->tf_hi, sc.out_val = b->wide_a;
+        sc.block_splats = b->tf_block, sc.lo_bits = tf_lo_bits, sc.second_pass = tf_hi_bits > 0;
+        sc.runs = &b->tf_runs, sc.offsets_if_final = b->offsets, sc.tiles = tiles;
+        sc.cidx = tf_cidx, sc.kept = tf_kept;
         stage_begin(ctx, SPLAT_STAGE_BIN_SCATTER); // (the row scan in front of it ran above: a few us not in this interval)
-        rc = tf_scatter_launch(ctx, range32, depth_keys, n_splats, ntx, (1u << tf_lo_bits) - 1u, b->tf_hist, b->d_total, b->pair_limit,
-                               b->d_total + 1, b->tf_hi, b->wide_a, b->tf_block, tf_lo_bits, tf_hi_bits > 0, &b->tf_runs, b->offsets, tiles,
-                               nullptr, 0u, tf_cidx, tf_kept);
+        rc = tf_scatter_launch(ctx, sc);
         stage_end(ctx, SPLAT_STAGE_BIN_SCATTER);
         if (rc != SPLAT_OK) return rc;
         // second pass (high digit) into wide_b, and the tile offsets out of its histogram; a screen of at most 256
         // tiles is sorted by the first pass alone (which then writes the offsets too)
         const bool primary = tf_hi_bits == 0;
+        TfSecondPassArgs sp;
+        sp.hi = b->tf_hi, sp.val_in = b->wide_a, sp.val_out = b->wide_b, sp.runs = &b->tf_runs;
+        sp.pairs_bound = total32, sp.tiles = tiles, sp.lo_bits = tf_lo_bits, sp.hi_bits = tf_hi_bits;
+        sp.hist = b->tf2_hist, sp.offsets = b->offsets, sp.d_total = b->d_total;
         stage_begin(ctx, SPLAT_STAGE_BIN_PASS2);
-        rc = tf_second_pass_launch(ctx, b->tf_hi, b->wide_a, b->wide_b, &b->tf_runs, total32, tiles, tf_lo_bits, tf_hi_bits, b->tf2_hist,
-                                   b->offsets, b->d_total);
+        rc = tf_second_pass_launch(ctx, sp);
         stage_end(ctx, SPLAT_STAGE_BIN_PASS2);
         if (rc != SPLAT_OK) return rc;
         // PerTileSorter: depth order inside every tile; the index lists land in the primary payload array
@@ -470,10 +472,15 @@ int binner_run(splat_binner *b, const void *projected, uint32_t n_splats, const 
         //  profiles/r04_u_tile_sort_classes.txt)
         const uint32_t band_tiles = tile_row1 > tile_row0 ? (tile_row1 - tile_row0) * ntx : 1u;
         const uint64_t band_key = ((uint64_t)tile_row0 << 48) ^ ((uint64_t)tile_row1 << 32) ^ tiles; // (same screen, same band)
+        TileSortArgs ts;
+        ts.offsets = b->offsets, ts.tiles = tiles;
+        ts.vals = primary ? b->wide_a : b->wide_b, ts.scratch = primary ? b->wide_b : b->wide_a;
+        ts.out_idx = b->pairs.payload, ts.counts = b->counts, ts.frame_flags = b->d_total + 1;
+        ts.mean_list = band_tiles >= 6144u ? (uint32_t)(b->total / band_tiles) : 0u, ts.band_tiles = band_tiles;
+        ts.long_tiles_hint = (async && b->last_band_key == band_key) ? b->last_long_tiles : 0xffffffffu;
+        ts.short_class_io = &b->last_short_class;
         stage_begin(ctx, SPLAT_STAGE_BIN_TILE_SORT);
-        rc = tile_sort_launch(ctx, b->offsets, tiles, primary ? b->wide_a : b->wide_b, primary ? b->wide_b : b->wide_a, b->pairs.payload,
-                              b->counts, b->d_total + 1, band_tiles >= 6144u ? (uint32_t)(b->total / band_tiles) : 0u, band_tiles,
-                              (async && b->last_band_key == band_key) ? b->last_long_tiles : 0xffffffffu, &b->last_short_class);
+        rc = tile_sort_launch(ctx, ts);
         stage_end(ctx, SPLAT_STAGE_BIN_TILE_SORT);
         if (rc != SPLAT_OK) return rc;
         b->pairs.result_in_primary = true;
@@ -590,8 +597,12 @@ int splat_debug_rerun_tile_sort(splat_ctx *ctx, splat_binner *b) {
     ARG_CHECK(ctx, b->ran && b->wide_a && b->wide_b && b->ntx && b->nty);
     const uint32_t tiles = b->ntx * b->nty;
     const bool primary = tile_id_bits(tiles) - tile_id_low_bits(tiles) == 0;
-    return tile_sort_launch(ctx, b->offsets, tiles, primary ? b->wide_a : b->wide_b, primary ? b->wide_b : b->wide_a, b->pairs.payload_b,
-                            nullptr, b->d_total + 4, tiles >= 6144u ? (uint32_t)(b->total / tiles) : 0u); // (flags and counters of its own: words 4..6)
+    TileSortArgs ts;
+    ts.offsets = b->offsets, ts.tiles = tiles;
+    ts.vals = primary ? b->wide_a : b->wide_b, ts.scratch = primary ? b->wide_b : b->wide_a;
+    ts.out_idx = b->pairs.payload_b, ts.frame_flags = b->d_total + 4; // (flags and counters of its own: words 4..6)
+    ts.mean_list = tiles >= 6144u ? (uint32_t)(b->total / tiles) : 0u;
+    return tile_sort_launch(ctx, ts);
 }
 #endif
 
@@ -640,7 +651,10 @@ void splat_bin_destroy(splat_binner *b) {
 int splat_bin_run(splat_binner *b, const void *projected, uint32_t n_splats, const void *sorted, uint32_t n_sorted,
                   uint32_t width, uint32_t height, uint32_t tile_row0, uint32_t tile_row1) {
     if (!b) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "binner is NULL");
-    return binner_run(b, projected, n_splats, sorted, n_sorted, width, height, tile_row0, tile_row1, nullptr);
+    BinRunArgs a;
+    a.projected = projected, a.n_splats = n_splats, a.sorted = sorted, a.n_sorted = n_sorted;
+    a.width = width, a.height = height, a.tile_row0 = tile_row0, a.tile_row1 = tile_row1;
+    return binner_run(b, a);
 }
 
 uint32_t splat_bin_tile_size(const splat_binner *b) { return b ? b->tile : 0; }

@@ -83,6 +83,17 @@ bool composite_uses_px(const splat_ctx *ctx, uint32_t ntx, uint32_t nty);
 
 int ctx_ensure_scan_ws(splat_ctx *ctx, size_t bytes);
 int ctx_ensure_pinned(splat_ctx *ctx, size_t bytes);
+// The one grow-only buffer: returns at once when want <= *cap; otherwise waits for the stream (a frame in flight may still
+// read the old buffer), frees it and allocates `bytes` (host: pinned host memory).  Contents are never preserved.  On failure
+// SPLAT_ERR_OOM with `what`, the pointer NULL and the capacity 0.  The size formula (padding, headroom, floors) is the caller's.
+int device_reserve_bytes(splat_ctx *ctx, void **ptr, size_t bytes, const char *what, bool host);
+template <class T, class Cap>
+int device_reserve(splat_ctx *ctx, T **ptr, Cap *cap, Cap want, size_t bytes, const char *what, bool host = false) {
+    if (want <= *cap) return SPLAT_OK;
+    const int rc = device_reserve_bytes(ctx, (void **)ptr, bytes, what, host);
+    *cap = rc == SPLAT_OK ? want : *ptr ? *cap : 0; // (a failed wait leaves the old buffer as it was)
+    return rc;
+}
 int ctx_ensure_consumed(splat_ctx *ctx, uint32_t tiles); // per-tile counters for timed frames (zeroed when (re)allocated)
 void stage_begin(splat_ctx *ctx, int stage);
 void stage_end(splat_ctx *ctx, int stage);
@@ -229,6 +240,25 @@ struct BinParams {
     uint32_t width, height, tile, ntx, nty, row0, row1;
     uint32_t skip_outside; // frame of a strict band of tile rows: splats that provably cannot reach it are not projected in full
 };
+// The tile grid of a screen and the band of tile rows [row0, row1) a call works on, clamped to it.  Which packed tile range a
+// frame of n splats carries per splat index: fast — range32, on screens of at most 256 x 256 tiles (the only screens that may
+// bin tile-first); wide — the 8-byte range beyond them (sort-first), on every screen the binner takes (binner_run: at most
+// 65535 tiles a side, 2^24 in all).  Screens the binner refuses carry none.
+struct TileBand {
+    uint32_t ntx, nty, row0, row1;
+    uint32_t tiles() const { return ntx * nty; }
+    bool empty() const { return row0 >= row1; }
+    bool strict() const { return row0 > 0 || row1 < nty; }
+    bool fast(uint32_t n) const { return n > 0 && ntx <= 256 && nty <= 256; }
+    bool wide(uint32_t n) const { return n > 0 && !fast(n) && ntx <= 65535 && nty <= 65535 && (uint64_t)ntx * nty <= (1u << 24); }
+};
+static inline TileBand tile_band(uint32_t width, uint32_t height, uint32_t tile, uint32_t cfg_row0, uint32_t cfg_row1) {
+    const uint32_t nty = div_up(height, tile), row1 = cfg_row1 < nty ? cfg_row1 : nty; // GPUTileBinner.ts:198-200
+    return {div_up(width, tile), nty, cfg_row0 < row1 ? cfg_row0 : row1, row1};
+}
+static inline BinParams bin_params(uint32_t width, uint32_t height, uint32_t tile, const TileBand &band, bool skip_outside) {
+    return {width, height, tile, band.ntx, band.nty, band.row0, band.row1, skip_outside ? 1u : 0u};
+}
 
 // Splats per block of the tile-first binner's first pass: 1024, or 256 for small frames — a 10 000-splat frame in
 // 1024-splat blocks is a ten-workgroup kernel expanding 14 pairs per splat in four rounds on an otherwise idle device
@@ -261,6 +291,14 @@ struct TfHistOut {
 __device__ __forceinline__ uint32_t xcd_block_of(uint32_t i, uint32_t xcd_per) {
     return xcd_per ? (i & 7u) * xcd_per + (i >> 3) : i;
 }
+// The launch that goes with it: the grid's size and xcd_per for `blocks` logical blocks (fewer than 64: dealt one to one)
+struct XcdGrid {
+    uint32_t grid, xcd_per;
+};
+static inline XcdGrid xcd_grid(uint32_t blocks) {
+    const uint32_t per = blocks >= 64u ? div_up(blocks, 8u) : 0u;
+    return {per ? 8u * per : blocks, per};
+}
 // tile-id bits and their split over the two sort passes (13 bits -> 6 + 7: longer digit runs than 8 + 5).  The first digit
 // is at most 8 bits wide, the widest radix_sort_pairs takes: ids of 18 to 24 bits (sort-first screens of more than 2^17
 // tiles) get 8 + 8 and then further 8-bit passes.  Up to 17 bits, and so on every tile-first screen, this is bits / 2.
@@ -287,23 +325,65 @@ __device__ __forceinline__ void tile_report(const uint32_t *d_total, uint32_t *r
 
 // bin.hip internals used by frame.hip
 int binner_reserve_range32(splat_binner *b, uint32_t n_splats);
-int binner_run(splat_binner *b, const void *projected, uint32_t n_splats, const void *sorted, uint32_t n_sorted, uint32_t width,
-               uint32_t height, uint32_t tile_row0, uint32_t tile_row1, const uint32_t *range32,
-               const uint32_t *n_sorted_dev = nullptr, const uint32_t *depth_keys = nullptr,
-               const uint2 *range_wide = nullptr); // per splat index, the 8-byte range (screens beyond 256 x 256 tiles, sort-first)
+// binSplats (bin.hip, binner_run).  range32 / range_wide: per splat index, the packed range the caller's projector or band
+// prepare computed for the same band; depth_keys (with range32): per splat index, its depth key — selects the tile-first order
+// of work, `sorted` is then unused
+struct BinRunArgs {
+    const void *projected = nullptr;
+    uint32_t n_splats = 0;
+    const void *sorted = nullptr;
+    uint32_t n_sorted = 0;
+    uint32_t width = 0, height = 0;
+    uint32_t tile_row0 = 0, tile_row1 = UINT32_MAX;
+    const uint32_t *range32 = nullptr;
+    const uint32_t *n_sorted_dev = nullptr; // the number of sorted entries is min(*n_sorted_dev, n_sorted), read on the device
+    const uint32_t *depth_keys = nullptr;
+    const uint2 *range_wide = nullptr; // per splat index, the 8-byte range (screens beyond 256 x 256 tiles, sort-first)
+};
+int binner_run(splat_binner *b, const BinRunArgs &a);
 int binner_reserve(splat_binner *b, uint32_t tiles, uint32_t n_sorted); // per-tile and per-position buffers
 // tile_first.hip (the frame path's bin-then-sort-per-tile kernels) and the wide-payload radix sort
-int tf_scatter_launch(splat_ctx *ctx, const uint32_t *range32, const uint32_t *depth_keys, uint32_t n, uint32_t ntx, uint32_t mask,
-                      const uint32_t *hist, uint32_t *d_total, uint32_t pair_limit, uint32_t *overflow, uint8_t *out_hi,
-                      uint2 *out_val, uint32_t block_splats, uint32_t lo_bits, bool second_pass, const TfRuns *runs,
-                      uint32_t *offsets_if_final, uint32_t tiles, uint32_t *report, uint32_t seq, const uint32_t *cidx = nullptr,
-                      const uint32_t *kept = nullptr); // cidx / kept: a band's kept splats compacted per group of 4096 records (frame.hip)
-int tf_second_pass_launch(splat_ctx *ctx, const uint8_t *hi, const uint2 *val_in, uint2 *val_out, const TfRuns *runs, uint32_t pairs_bound,
-                          uint32_t tiles, uint32_t lo_bits, uint32_t hi_bits, uint32_t *hist, uint32_t *offsets, const uint32_t *d_total);
+struct TfScatterArgs {
+    const uint32_t *range32 = nullptr, *depth_keys = nullptr; // per splat index
+    uint32_t n = 0, ntx = 0, mask = 0;                        // mask: of the low tile-id digit
+    const uint32_t *hist = nullptr;                           // the first pass's histogram, rows scanned
+    uint32_t *d_total = nullptr;
+    uint32_t pair_limit = 0;
+    uint32_t *overflow = nullptr;
+    uint8_t *out_hi = nullptr;
+    uint2 *out_val = nullptr;
+    uint32_t block_splats = TF_BLOCK_LARGE, lo_bits = 0;
+    bool second_pass = false; // a second pass follows: runs are aligned for it; else this pass writes offsets_if_final
+    const TfRuns *runs = nullptr;
+    uint32_t *offsets_if_final = nullptr;
+    uint32_t tiles = 0;
+    uint32_t *report = nullptr;
+    uint32_t seq = 0;
+    const uint32_t *cidx = nullptr, *kept = nullptr; // a band's kept splats compacted per group of 4096 records (frame.hip)
+};
+int tf_scatter_launch(splat_ctx *ctx, const TfScatterArgs &a);
+struct TfSecondPassArgs {
+    const uint8_t *hi = nullptr;
+    const uint2 *val_in = nullptr;
+    uint2 *val_out = nullptr;
+    const TfRuns *runs = nullptr;
+    uint32_t pairs_bound = 0, tiles = 0, lo_bits = 0, hi_bits = 0;
+    uint32_t *hist = nullptr, *offsets = nullptr;
+    const uint32_t *d_total = nullptr;
+};
+int tf_second_pass_launch(splat_ctx *ctx, const TfSecondPassArgs &a);
 int radix_rowscan_launch(splat_ctx *ctx, uint32_t *hist, uint32_t parts, uint32_t rows); // rows -> exclusive prefixes, totals at hist + 256*parts
-int tile_sort_launch(splat_ctx *ctx, const uint32_t *offsets, uint32_t tiles, uint2 *vals, uint2 *scratch, uint32_t *out_idx,
-                     uint32_t *counts, uint32_t *frame_flags, uint32_t mean_list, uint32_t band_tiles = 0,
-                     uint32_t long_tiles_hint = 0xffffffffu, uint32_t *short_class_io = nullptr); // frame_flags: FRAME_FLAG_ORDER is raised if a list fails the order check
+struct TileSortArgs {
+    const uint32_t *offsets = nullptr;
+    uint32_t tiles = 0;
+    uint2 *vals = nullptr, *scratch = nullptr;
+    uint32_t *out_idx = nullptr, *counts = nullptr;
+    uint32_t *frame_flags = nullptr; // FRAME_FLAG_ORDER is raised if a list fails the order check
+    uint32_t mean_list = 0, band_tiles = 0;
+    uint32_t long_tiles_hint = 0xffffffffu;
+    uint32_t *short_class_io = nullptr;
+};
+int tile_sort_launch(splat_ctx *ctx, const TileSortArgs &a);
 int binner_settle(splat_binner *b); // resolves a pending report; SPLAT_ERR_CAPACITY if that frame overflowed, SPLAT_ERR_RETRY if its lists failed the order check
 // composite.hip: what a composite reads and writes — splat_composite_aov's arguments, and for a frame its report and the AOV
 // depth's source
@@ -324,19 +404,54 @@ struct CompositeArgs {
     uint32_t ext_zstride = 0;
 };
 int composite_launch(splat_ctx *ctx, const splat_composite_cfg *cfg, const CompositeArgs &a);
+// A tile-first frame's report is sent by its last kernel, the composite: the frame function takes the binner's promise and
+// clears it (composite_launch sends a promised report whatever happens to its launch)
+static inline void binner_take_report(splat_binner *b, CompositeArgs &a) {
+    a.frame_total = b->d_total, a.report = b->report_for_composite, a.report_seq = b->report_seq;
+    b->report_for_composite = nullptr;
+}
+// "composite this binner's lists", report included (fields, not the public getters: those wait for a sync-free frame's pair
+// total to come back)
+static inline void composite_binner_lists(splat_binner *b, CompositeArgs &a) {
+    a.tile_indices = b->pairs.result_in_primary ? b->pairs.payload : b->pairs.payload_b;
+    a.tile_counts = b->counts, a.tile_offsets = b->offsets;
+    binner_take_report(b, a);
+}
 // The checks of a splat_aov request (aov == NULL: none) a frame makes before its first launch and the composite again:
 // a non-NULL buffer, 16-byte alignment, nearest on top, and for depth, records that carry it (has_depth).
 int aov_check(splat_ctx *ctx, const splat_composite_cfg *cfg, const splat_aov *aov, bool has_depth);
 // project.hip internal: the projector with the optional per-index tile range output
-int project_launch(splat_ctx *ctx, const float *uniforms, const void *pos_radius, uint32_t pr_stride_vec4, uint32_t n,
-                   uint32_t index_base, void *projected, void *keys, void *payload, uint32_t n_padded, uint32_t *range32,
-                   const BinParams *bp, const TfHistOut *hist_out = nullptr, const void *normals = nullptr,
-                   uint32_t normal_stride_vec4 = 1, void *discs = nullptr, // discs != NULL: the oriented-disc footprint (disc.h)
-                   const struct LitIO *lit = nullptr,                      // lit->records != NULL: also write lit composite records (shade.h)
-                   uint2 *range_wide = nullptr, // instead of range32 (screens beyond 256 x 256 tiles): the 8-byte range, sort-first
-                   const struct EllIO *ell = nullptr); // with discs: the anisotropic Gaussian (ellipsoid.h) instead of the disc
+struct ProjectArgs {
+    const float *uniforms = nullptr;
+    const void *pos_radius = nullptr;
+    uint32_t pr_stride_vec4 = 1, n = 0, index_base = 0;
+    void *projected = nullptr, *keys = nullptr, *payload = nullptr;
+    uint32_t n_padded = 0;
+    uint32_t *range32 = nullptr;
+    const BinParams *bp = nullptr;
+    const TfHistOut *hist_out = nullptr;
+    const void *normals = nullptr;
+    uint32_t normal_stride_vec4 = 1;
+    void *discs = nullptr;                  // discs != NULL: the oriented-disc footprint (disc.h)
+    const struct LitIO *lit = nullptr;      // lit->records != NULL: also write lit composite records (shade.h)
+    uint2 *range_wide = nullptr;            // instead of range32 (screens beyond 256 x 256 tiles): the 8-byte range, sort-first
+    const struct EllIO *ell = nullptr;      // with discs: the anisotropic Gaussian (ellipsoid.h) instead of the disc
+};
+int project_launch(splat_ctx *ctx, const ProjectArgs &a);
 // project.hip internal: the antialiased ellipsoid projector (every output optional; rho_out n floats, color_opacity_out n x float4)
-int project_ellipsoid_aa_launch(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4, const struct EllIO &ell,
-                                uint32_t n, void *projected, void *records, void *keys, void *payload, uint32_t n_padded, float *rho_out,
-                                const void *color_opacity, uint32_t color_stride_vec4, void *color_opacity_out, bool timed);
+struct ProjectAaArgs {
+    const float *uniforms = nullptr;
+    const void *positions = nullptr;
+    uint32_t pos_stride_vec4 = 1;
+    const struct EllIO *ell = nullptr;
+    uint32_t n = 0;
+    void *projected = nullptr, *records = nullptr, *keys = nullptr, *payload = nullptr;
+    uint32_t n_padded = 0;
+    float *rho_out = nullptr;
+    const void *color_opacity = nullptr;
+    uint32_t color_stride_vec4 = 1;
+    void *color_opacity_out = nullptr;
+    bool timed = false; // the launch is a SPLAT_STAGE_PROJECT interval of its own
+};
+int project_ellipsoid_aa_launch(splat_ctx *ctx, const ProjectAaArgs &a);
 int binner_reserve_range_wide(splat_binner *b, uint32_t n_splats); // the range32 buffer, grown to 8 bytes per splat; its uint2s

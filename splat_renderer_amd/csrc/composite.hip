@@ -1129,19 +1129,15 @@ static int px_order_prepare(splat_ctx *ctx, uint32_t band_tiles, uint64_t key, C
     }
     h->last_use = ++ctx->px_clock;
     if (band_tiles > h->cap) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // (a launch in flight may still write the old arrays)
-        if (h->mem) (void)hipFree(h->mem);
-        h->mem = nullptr;
-        h->cap = 0;
-        h->streak = 0;
         // (each array padded so that px_make_order's 128 threads read whole 64-byte groups of costs past the last tile)
         const uint32_t cap = (band_tiles + 128u * 16u + 1023u) & ~1023u;
-        if (hipMalloc((void **)&h->mem, (size_t)cap * 16) != hipSuccess) {
-            h->key = 0;
-            return ctx_fail(ctx, SPLAT_ERR_OOM, "composite tile order hipMalloc");
+        const int rc = device_reserve(ctx, &h->mem, &h->cap, cap, (size_t)cap * 16, "composite tile order hipMalloc");
+        if (rc != SPLAT_OK) {
+            if (!h->mem) h->key = 0, h->streak = 0; // (the old arrays are gone: the slot is free)
+            return rc;
         }
+        h->streak = 0;
         (void)hipMemsetAsync(h->mem, 0, (size_t)cap * 16, ctx->stream);
-        h->cap = cap;
     }
     uint32_t *cost[2] = {h->mem, h->mem + h->cap}, *order[2] = {h->mem + 2 * (size_t)h->cap, h->mem + 3 * (size_t)h->cap};
     const uint32_t q = h->parity & 1u;
@@ -1215,14 +1211,11 @@ static bool lit_disc_records(const splat_composite_cfg *cfg) {
            cfg->record_format == SPLAT_RECORDS_LIT32;
 }
 
-extern "C" int splat_composite_aov(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity,
-                                   uint32_t color_stride_vec4, const void *normals, uint32_t normal_stride_vec4,
-                                   const void *projected, const void *tile_indices, const void *tile_counts,
-                                   const void *tile_offsets, uint32_t width, uint32_t height, void *out_rgba8, void *out_rgba32f,
-                                   void *consumed_dptr, const splat_aov *aov) {
-    if (ctx && lit_disc_records(cfg))
-        return ctx_fail(ctx, SPLAT_ERR_INVALID, "splat_composite: the oriented-disc footprint composites from SPLAT_RECORDS_PROJECTED (32-byte disc "
-                                                "records) or SPLAT_RECORDS_DISC48; lit disc records are internal to splat_render_frame");
+// the fields the public composite entry points share, under the names of include/splat.h's arguments
+static CompositeArgs composite_public_args(const void *color_opacity, uint32_t color_stride_vec4, const void *normals, uint32_t normal_stride_vec4,
+                                           const void *projected, const void *tile_indices, const void *tile_counts, const void *tile_offsets,
+                                           uint32_t width, uint32_t height, void *out_rgba8, void *out_rgba32f, void *consumed_dptr,
+                                           const splat_aov *aov) {
     CompositeArgs a;
     a.color_opacity = color_opacity, a.color_stride_vec4 = color_stride_vec4;
     a.normals = normals, a.normal_stride_vec4 = normal_stride_vec4;
@@ -1232,7 +1225,19 @@ extern "C" int splat_composite_aov(splat_ctx *ctx, const splat_composite_cfg *cf
     a.out_rgba8 = out_rgba8, a.out_rgba32f = out_rgba32f;
     a.consumed = consumed_dptr;
     a.aov = aov;
-    return composite_launch(ctx, cfg, a);
+    return a;
+}
+
+extern "C" int splat_composite_aov(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity,
+                                   uint32_t color_stride_vec4, const void *normals, uint32_t normal_stride_vec4,
+                                   const void *projected, const void *tile_indices, const void *tile_counts,
+                                   const void *tile_offsets, uint32_t width, uint32_t height, void *out_rgba8, void *out_rgba32f,
+                                   void *consumed_dptr, const splat_aov *aov) {
+    if (ctx && lit_disc_records(cfg))
+        return ctx_fail(ctx, SPLAT_ERR_INVALID, "splat_composite: the oriented-disc footprint composites from SPLAT_RECORDS_PROJECTED (32-byte disc "
+                                                "records) or SPLAT_RECORDS_DISC48; lit disc records are internal to splat_render_frame");
+    return composite_launch(ctx, cfg, composite_public_args(color_opacity, color_stride_vec4, normals, normal_stride_vec4, projected, tile_indices,
+                                                            tile_counts, tile_offsets, width, height, out_rgba8, out_rgba32f, consumed_dptr, aov));
 }
 
 // splat_composite_aov with the AOV depth of splat i read from depth_f32[i * depth_stride_floats], for every footprint and record
@@ -1247,15 +1252,8 @@ extern "C" int splat_composite_aov_depth(splat_ctx *ctx, const splat_composite_c
     if (lit_disc_records(cfg))
         return ctx_fail(ctx, SPLAT_ERR_INVALID, "splat_composite_aov_depth: the oriented-disc footprint composites from SPLAT_RECORDS_PROJECTED "
                                                 "(32-byte disc records) or SPLAT_RECORDS_DISC48; lit disc records are internal to splat_render_frame");
-    CompositeArgs a;
-    a.color_opacity = color_opacity, a.color_stride_vec4 = color_stride_vec4;
-    a.normals = normals, a.normal_stride_vec4 = normal_stride_vec4;
-    a.projected = projected;
-    a.tile_indices = tile_indices, a.tile_counts = tile_counts, a.tile_offsets = tile_offsets;
-    a.width = width, a.height = height;
-    a.out_rgba8 = out_rgba8, a.out_rgba32f = out_rgba32f;
-    a.consumed = consumed_dptr;
-    a.aov = aov;
+    CompositeArgs a = composite_public_args(color_opacity, color_stride_vec4, normals, normal_stride_vec4, projected, tile_indices, tile_counts,
+                                            tile_offsets, width, height, out_rgba8, out_rgba32f, consumed_dptr, aov);
     a.ext_z = (const float *)depth_f32, a.ext_zstride = depth_stride_floats;
     return composite_launch(ctx, cfg, a);
 }
@@ -1323,9 +1321,9 @@ int composite_launch(splat_ctx *ctx, const splat_composite_cfg *cfg, const Compo
         const int arc = aov_check(ctx, cfg, aov, zsrc != nullptr);
         if (arc != SPLAT_OK) return arc;
     }
-    const uint32_t ntx = div_up(width, T), nty = div_up(height, T);
-    uint32_t r0 = cfg->tile_row0, r1 = cfg->tile_row1 > nty ? nty : cfg->tile_row1;
-    if (r0 >= r1) return SPLAT_OK;
+    const TileBand band = tile_band(width, height, T, cfg->tile_row0, cfg->tile_row1);
+    if (band.empty()) return SPLAT_OK;
+    const uint32_t ntx = band.ntx, nty = band.nty, r0 = band.row0, r1 = band.row1;
     CompositeParams p;
     p.color = (const float4 *)a.color_opacity;
     p.color_stride = a.color_stride_vec4;

@@ -327,17 +327,9 @@ int composite_tile_launch(splat_ctx *ctx, const splat_composite_cfg *cfg, const 
     uint2 *win_counts = nullptr;
     if (p.consumed && wpt > 1) { // (every window of the launch writes its pair: nothing to clear)
         const uint32_t windows = grid.x * grid.y;
-        if (windows > ctx->window_counts_cap) {
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // (a launch in flight may still use the old array)
-            if (ctx->d_window_counts) (void)hipFree(ctx->d_window_counts);
-            ctx->d_window_counts = nullptr;
-            ctx->window_counts_cap = 0;
-            if (hipMalloc((void **)&ctx->d_window_counts, (size_t)windows * sizeof(uint2)) != hipSuccess) {
-                ctx->d_window_counts = nullptr;
-                return ctx_fail(ctx, SPLAT_ERR_OOM, "composite window counters hipMalloc");
-            }
-            ctx->window_counts_cap = windows;
-        }
+        const int rc = device_reserve(ctx, &ctx->d_window_counts, &ctx->window_counts_cap, windows, (size_t)windows * sizeof(uint2),
+                                      "composite window counters hipMalloc");
+        if (rc != SPLAT_OK) return rc;
         win_counts = ctx->d_window_counts;
     }
     // (the auxiliary outputs are nearest-on-top only: composite.hip's aov_check refused them for the reference-literal blend)

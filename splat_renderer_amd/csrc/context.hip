@@ -18,33 +18,27 @@ int ctx_fail(splat_ctx *ctx, int code, const char *what, hipError_t e) {
     return code;
 }
 
+int device_reserve_bytes(splat_ctx *ctx, void **ptr, size_t bytes, const char *what, bool host) {
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (*ptr) (void)(host ? hipHostFree(*ptr) : hipFree(*ptr));
+    *ptr = nullptr;
+    if ((host ? hipHostMalloc(ptr, bytes, hipHostMallocDefault) : hipMalloc(ptr, bytes)) != hipSuccess) {
+        *ptr = nullptr;
+        return ctx_fail(ctx, SPLAT_ERR_OOM, what);
+    }
+    return SPLAT_OK;
+}
+
 int ctx_ensure_scan_ws(splat_ctx *ctx, size_t bytes) {
     if (ctx->scan_ws_bytes >= bytes) return SPLAT_OK;
-    if (ctx->scan_ws) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        HIP_TRY(ctx, hipFree(ctx->scan_ws));
-        ctx->scan_ws = nullptr;
-        ctx->scan_ws_bytes = 0;
-    }
-    size_t want = bytes < (1u << 20) ? (1u << 20) : bytes;
-    if (hipMalloc(&ctx->scan_ws, want) != hipSuccess) return ctx_fail(ctx, SPLAT_ERR_OOM, "scan workspace hipMalloc");
-    ctx->scan_ws_bytes = want;
-    return SPLAT_OK;
+    const size_t want = bytes < (1u << 20) ? (1u << 20) : bytes;
+    return device_reserve(ctx, &ctx->scan_ws, &ctx->scan_ws_bytes, want, want, "scan workspace hipMalloc");
 }
 
 int ctx_ensure_pinned(splat_ctx *ctx, size_t bytes) {
     if (ctx->pinned_bytes >= bytes) return SPLAT_OK;
-    if (ctx->pinned) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        HIP_TRY(ctx, hipHostFree(ctx->pinned));
-        ctx->pinned = nullptr;
-        ctx->pinned_bytes = 0;
-    }
-    size_t want = bytes < (1u << 16) ? (1u << 16) : bytes;
-    if (hipHostMalloc(&ctx->pinned, want, hipHostMallocDefault) != hipSuccess)
-        return ctx_fail(ctx, SPLAT_ERR_OOM, "pinned staging hipHostMalloc");
-    ctx->pinned_bytes = want;
-    return SPLAT_OK;
+    const size_t want = bytes < (1u << 16) ? (1u << 16) : bytes;
+    return device_reserve(ctx, &ctx->pinned, &ctx->pinned_bytes, want, want, "pinned staging hipHostMalloc", true);
 }
 
 void stage_begin(splat_ctx *ctx, int stage) {

@@ -10,6 +10,7 @@
 #include "disc.h"
 #include "ellipsoid.h"
 #include "shade.h"
+#include "variant.h"
 
 #include <cstdlib>
 
@@ -386,15 +387,13 @@ static int band_settle_count(splat_ctx *ctx, splat_sorter *sorter) {
 static int band_keys_device(splat_ctx *ctx, splat_sorter *sorter, const void *projected, uint32_t n, uint32_t width,
                             uint32_t height, uint32_t tile_size, uint32_t tile_row0, uint32_t tile_row1) {
     if (n > sorter->capacity) return ctx_fail(ctx, SPLAT_ERR_CAPACITY, "splat_band_keys: n exceeds the sorter's capacity");
-    const uint32_t ntx = div_up(width, tile_size), nty = div_up(height, tile_size);
-    if (tile_row1 > nty) tile_row1 = nty;
-    if (tile_row0 > tile_row1) tile_row0 = tile_row1;
+    const TileBand band = tile_band(width, height, tile_size, tile_row0, tile_row1);
     // flags live in the sorter's alternate key buffer, the kept count in its device counter
     uint32_t *flags = sorter->keys_b;
     uint32_t *d_total = sorter->d_count;
     stage_begin(ctx, SPLAT_STAGE_PROJECT);
     hipLaunchKernelGGL(k_band_flag, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, (const float4 *)projected, n, width,
-                       height, tile_size, ntx, nty, tile_row0, tile_row1, flags);
+                       height, tile_size, band.ntx, band.nty, band.row0, band.row1, flags);
     LAUNCH_CHECK(ctx, "k_band_flag");
     int rc = scan_exclusive_u32(ctx, flags, flags, n, d_total);
     if (rc != SPLAT_OK) return rc;
@@ -404,12 +403,6 @@ static int band_keys_device(splat_ctx *ctx, splat_sorter *sorter, const void *pr
     stage_end(ctx, SPLAT_STAGE_PROJECT);
     return SPLAT_OK;
 }
-
-// Which packed tile range a frame carries per splat index.  A frame "has a packed range" on every screen the binner takes
-// (binner_run: at most 65535 tiles a side, 2^24 in all): range32 on screens of at most 256 x 256 tiles (the only screens that
-// may bin tile-first), the 8-byte wide range beyond them (sort-first).  Screens the binner refuses carry none.
-static bool range_fits_8_bits(uint32_t ntx, uint32_t nty) { return ntx <= 256 && nty <= 256; }
-static bool bin_accepts(uint32_t ntx, uint32_t nty) { return ntx <= 65535 && nty <= 65535 && (uint64_t)ntx * nty <= (1u << 24); }
 
 // which order of work splat_render_frame uses for this binner (see splat_bin_set_frame_order)
 static int g_frame_order = -2;
@@ -427,26 +420,48 @@ static int frame_order(const splat_binner *b) {
 // scatter runs over the kept splats only.  Measured with virtual ranks at C2: a gain up to a third of the rows and still at 23 of
 // 68 (the tallest of four pair-balanced bands: 0.200 -> 0.185 ms without an exchange, 0.184 -> 0.178 with), a loss at half of
 // them (two ranks: +3..8 us).  The rule: bands of at most two fifths of the rows.  (SPLAT_BAND_COMPACT=0 | 1 forces one of them.)
-static bool band_compacting(uint32_t row0, uint32_t row1, uint32_t nty) {
+static bool band_compacting(const TileBand &band) {
     static int s_compact = -2;
     if (s_compact == -2) {
         const char *e = getenv("SPLAT_BAND_COMPACT");
         s_compact = !e ? -1 : (e[0] == '0' ? 0 : 1);
     }
-    return s_compact == 1 || (s_compact == -1 && 5u * (row1 - row0) <= 2u * nty);
+    return s_compact == 1 || (s_compact == -1 && 5u * (band.row1 - band.row0) <= 2u * band.nty);
 }
 
 // (the compacted splats' indices: one slot per record, rounded up to whole groups)
 static int binner_reserve_band_idx(splat_ctx *ctx, splat_binner *binner, uint32_t n_records) {
-    if (n_records <= binner->band_idx_cap) return SPLAT_OK;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (binner->band_idx) (void)hipFree(binner->band_idx);
-    binner->band_idx = nullptr;
-    binner->band_idx_cap = 0;
     const size_t slots = (size_t)div_up(n_records, BTC_GROUP) * BTC_GROUP;
-    if (hipMalloc((void **)&binner->band_idx, slots * 4 + 256) != hipSuccess) return ctx_fail(ctx, SPLAT_ERR_OOM, "band index hipMalloc");
-    binner->band_idx_cap = n_records;
-    return SPLAT_OK;
+    return device_reserve(ctx, &binner->band_idx, &binner->band_idx_cap, n_records, slots * 4 + 256, "band index hipMalloc");
+}
+
+// The tail the tile-first branches of both frame functions share, up to the composite: what the caller's projector / prepare pass
+// left for THIS run (the first pass's histogram; compacted: a band's kept splats, their indices in band_idx and their numbers
+// per group in the sorter's hist) is handed to the binner, which bins in index order and depth-sorts per tile — no global sort,
+// no gather (tile_first.hip); the sorter holds the frame's unsorted depth keys
+static int bin_tile_first(splat_sorter *sorter, splat_binner *binner, const void *records, uint32_t n, uint32_t width, uint32_t height,
+                          const TileBand &band, bool compacted) {
+    binner->tf_hist_ready = true;
+    binner->tf_cidx = compacted ? binner->band_idx : nullptr;
+    binner->tf_kept = compacted ? sorter->hist : nullptr;
+    sorter->ran = false;
+    BinRunArgs run;
+    run.projected = records, run.n_splats = n, run.n_sorted = n, run.width = width, run.height = height;
+    run.tile_row0 = band.row0, run.tile_row1 = band.row1, run.range32 = binner->range32, run.depth_keys = sorter->keys;
+    return binner_run(binner, run);
+}
+
+// a band frame's composite: the gathered records, the band's rows clamped to the screen
+static CompositeArgs band_composite_args(const void *color, uint32_t color_stride, const void *normals, const void *records, uint32_t width,
+                                         uint32_t height, void *out_rgba8, void *out_rgba32f, void *consumed_dptr) {
+    CompositeArgs a;
+    a.color_opacity = color, a.color_stride_vec4 = color_stride;
+    a.normals = normals;
+    a.projected = records;
+    a.width = width, a.height = height;
+    a.out_rgba8 = out_rgba8, a.out_rgba32f = out_rgba32f;
+    a.consumed = consumed_dptr;
+    return a;
 }
 
 extern "C" {
@@ -481,13 +496,10 @@ int splat_band_frame(splat_ctx *ctx, splat_sorter *sorter, splat_binner *binner,
     // colours: the second vec4 of the reference's interleaved records, or (cfg->prelit) `props` IS the plane of lit colours
     const void *band_color = cfg->prelit ? props : (const void *)((const char *)props + 16);
     const uint32_t band_color_stride = cfg->prelit ? 1u : 2u;
-    const uint32_t tile = cfg->tile_size, nty = div_up(height, tile);
-    uint32_t row0 = cfg->tile_row0, row1 = cfg->tile_row1 > nty ? nty : cfg->tile_row1;
-    if (row0 > row1) row0 = row1;
-    const uint32_t ntx = div_up(width, tile);
+    const uint32_t tile = cfg->tile_size;
+    const TileBand band = tile_band(width, height, tile, cfg->tile_row0, cfg->tile_row1);
     // fast: range32, and the tile-first order may run; wide: beyond 256 x 256 tiles, the 8-byte range (sort-first)
-    const bool fast = range_fits_8_bits(ntx, nty) && n_records > 0;
-    const bool wide = !fast && n_records > 0 && bin_accepts(ntx, nty);
+    const bool fast = band.fast(n_records), wide = band.wide(n_records);
     const bool compact = cfg->record_format == SPLAT_RECORDS_COMPACT;
     const bool disc = cfg->record_format == SPLAT_RECORDS_DISC48;
     // oriented-disc records bin tile-first wherever that order exists (at most 256 x 256 tiles), sort-first from the wide range
@@ -499,82 +511,61 @@ int splat_band_frame(splat_ctx *ctx, splat_sorter *sorter, splat_binner *binner,
     ARG_CHECK(ctx, ((uintptr_t)records & 15) == 0);
     if (compact && n_records > 0 && !(fast && frame_order(binner) == SPLAT_FRAME_TILE_FIRST)) {
         // the other orders of work read ProjectedSplat records: rebuild them once (bit-exact) and go on
-        if (n_records > binner->expanded_cap) {
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (binner->expanded) (void)hipFree(binner->expanded);
-            binner->expanded = nullptr;
-            binner->expanded_cap = 0;
-            if (hipMalloc(&binner->expanded, (size_t)n_records * 32 + 256) != hipSuccess) return ctx_fail(ctx, SPLAT_ERR_OOM, "band frame hipMalloc");
-            binner->expanded_cap = n_records;
-        }
-        int rc = splat_expand_compact(ctx, records, n_records, 0, binner->expanded);
+        int rc = device_reserve(ctx, &binner->expanded, &binner->expanded_cap, n_records, (size_t)n_records * 32 + 256, "band frame hipMalloc");
+        if (rc != SPLAT_OK) return rc;
+        rc = splat_expand_compact(ctx, records, n_records, 0, binner->expanded);
         if (rc != SPLAT_OK) return rc;
         splat_composite_cfg c2 = *cfg;
         c2.record_format = SPLAT_RECORDS_PROJECTED;
         return splat_band_frame(ctx, sorter, binner, &c2, props, normals, binner->expanded, n_records, width, height, out_rgba8,
                                 out_rgba32f, consumed_dptr);
     }
+    const BinParams bp = bin_params(width, height, tile, band, false);
+    const float4 *recs = (const float4 *)records;
+    splat_composite_cfg c2 = *cfg;
+    c2.tile_row0 = band.row0;
+    c2.tile_row1 = band.row1;
     if (fast && frame_order(binner) == SPLAT_FRAME_TILE_FIRST) {
         // tile-first: one pass over the records (keys, band-clamped ranges, pair counts), then the
         // binner in index order — a splat outside the band has an empty range and costs nothing more
         if (n_records > sorter->capacity) return ctx_fail(ctx, SPLAT_ERR_CAPACITY, "splat_band_frame: n_records exceeds the sorter's capacity");
         int rc = binner_reserve_range32(binner, n_records);
         if (rc != SPLAT_OK) return rc;
-        rc = binner_reserve(binner, ntx * nty, n_records);
+        rc = binner_reserve(binner, band.tiles(), n_records);
         if (rc != SPLAT_OK) return rc;
-        const BinParams bp = {width, height, tile, ntx, nty, row0, row1};
-        const bool compacting = band_compacting(row0, row1, nty);
+        const bool compacting = band_compacting(band);
         const uint32_t blocks = div_up(n_records, compacting ? BTC_GROUP : BTF_BLOCK);
         if (compacting) {
             rc = binner_reserve_band_idx(ctx, binner, n_records);
             if (rc != SPLAT_OK) return rc;
         }
-        TfHistOut ho = {binner->tf_hist, binner->blocksums, binner->d_total + 1, (1u << tile_id_low_bits(ntx * nty)) - 1u, blocks};
+        const XcdGrid xg = xcd_grid(blocks); // (a compacting pass's groups dealt as k_tf_scatter<COMPACTED> deals them)
+        TfHistOut ho = {};
+        ho.hist = binner->tf_hist, ho.blocksums = binner->blocksums, ho.overflow_flag = binner->d_total + 1;
+        ho.mask = (1u << tile_id_low_bits(band.tiles())) - 1u, ho.num_parts = blocks;
+        ho.xcd_per = compacting ? xg.xcd_per : 0u;
         stage_begin(ctx, SPLAT_STAGE_PROJECT);
-        if (compacting) {
-            ho.xcd_per = blocks >= 64u ? div_up(blocks, 8u) : 0u; // (the groups dealt as k_tf_scatter<COMPACTED> deals them)
-            const uint32_t grid_blocks = ho.xcd_per ? 8u * ho.xcd_per : blocks;
-#define SPLAT_BAND_PREPARE_C(FORMAT)                                                                                                  \
-    hipLaunchKernelGGL(k_band_prepare_tfc<FORMAT>, dim3(grid_blocks), dim3(BTC_THREADS), 0, ctx->stream, (const float4 *)records, n_records, bp, \
-                       sorter->keys, binner->range32, binner->band_idx, sorter->hist, ho)
-            if (disc) SPLAT_BAND_PREPARE_C(SPLAT_RECORDS_DISC48);
-            else if (compact) SPLAT_BAND_PREPARE_C(SPLAT_RECORDS_COMPACT);
-            else SPLAT_BAND_PREPARE_C(SPLAT_RECORDS_PROJECTED);
-#undef SPLAT_BAND_PREPARE_C
-        } else if (disc)
-            hipLaunchKernelGGL(k_band_prepare_tf<SPLAT_RECORDS_DISC48>, dim3(blocks), dim3(BAND_THREADS), 0, ctx->stream,
-                               (const float4 *)records, n_records, bp, sorter->keys, binner->range32, sorter->hist, ho);
-        else if (compact)
-            hipLaunchKernelGGL(k_band_prepare_tf<SPLAT_RECORDS_COMPACT>, dim3(blocks), dim3(BAND_THREADS), 0, ctx->stream,
-                               (const float4 *)records, n_records, bp, sorter->keys, binner->range32, sorter->hist, ho);
-        else
-            hipLaunchKernelGGL(k_band_prepare_tf<SPLAT_RECORDS_PROJECTED>, dim3(blocks), dim3(BAND_THREADS), 0, ctx->stream,
-                               (const float4 *)records, n_records, bp, sorter->keys, binner->range32, sorter->hist, ho);
+        const bool ok = variant_dispatch(
+            [&](auto format) {
+                if (compacting)
+                    launch_kernel(ctx, NO_STAGE, k_band_prepare_tfc<format.value>, dim3(xg.grid), dim3(BTC_THREADS), recs, n_records, bp,
+                                  sorter->keys, binner->range32, binner->band_idx, sorter->hist, ho);
+                else
+                    launch_kernel(ctx, NO_STAGE, k_band_prepare_tf<format.value>, dim3(blocks), dim3(BAND_THREADS), recs, n_records, bp,
+                                  sorter->keys, binner->range32, sorter->hist, ho);
+                return true;
+            },
+            OneOf<SPLAT_RECORDS_PROJECTED, SPLAT_RECORDS_COMPACT, SPLAT_RECORDS_DISC48>{(int)cfg->record_format});
+        if (!ok) return ctx_fail(ctx, SPLAT_ERR_INVALID, "k_band_prepare_tf: no kernel for this record format");
         LAUNCH_CHECK(ctx, "k_band_prepare_tf");
         stage_end(ctx, SPLAT_STAGE_PROJECT);
-        binner->tf_hist_ready = true;
         binner->tf_block = compacting ? BTC_GROUP : BTF_BLOCK;
-        binner->tf_cidx = compacting ? binner->band_idx : nullptr;
-        binner->tf_kept = compacting ? sorter->hist : nullptr;
-        sorter->ran = false;
         sorter->count_pending = false;
         sorter->kept_blocks = blocks; // the kept count is summed on demand (splat_band_kept / splat_band_settle)
-        rc = binner_run(binner, records, n_records, nullptr, n_records, width, height, row0, row1, binner->range32, nullptr, sorter->keys);
+        rc = bin_tile_first(sorter, binner, records, n_records, width, height, band, compacting);
         if (rc != SPLAT_OK) return rc;
-        splat_composite_cfg c2 = *cfg;
-        c2.tile_row0 = row0;
-        c2.tile_row1 = row1;
-        uint32_t *report = binner->report_for_composite; // (the frame's last kernel reports it: common.h)
-        binner->report_for_composite = nullptr;
-        CompositeArgs a;
-        a.color_opacity = band_color, a.color_stride_vec4 = band_color_stride;
-        a.normals = normals;
-        a.projected = records;
-        a.tile_indices = binner->pairs.payload, a.tile_counts = binner->counts, a.tile_offsets = binner->offsets;
-        a.width = width, a.height = height;
-        a.out_rgba8 = out_rgba8, a.out_rgba32f = out_rgba32f;
-        a.consumed = consumed_dptr;
-        a.frame_total = binner->d_total, a.report = report, a.report_seq = binner->report_seq;
+        CompositeArgs a = band_composite_args(band_color, band_color_stride, normals, records, width, height, out_rgba8, out_rgba32f, consumed_dptr);
+        composite_binner_lists(binner, a); // (with the report: the frame's last kernel sends it, common.h)
         return composite_launch(ctx, &c2, a);
     }
     sorter->kept_blocks = 0;
@@ -595,16 +586,15 @@ int splat_band_frame(splat_ctx *ctx, splat_sorter *sorter, splat_binner *binner,
     }
     if (n_records > 0) {
         if (n_records > sorter->capacity) return ctx_fail(ctx, SPLAT_ERR_CAPACITY, "splat_band_frame: n_records exceeds the sorter's capacity");
+        const uint32_t blocks = div_up(n_records, BAND_BLOCK);
+        uint32_t *keys_by_idx = sorter->keys_b, *blocksums = sorter->hist; // both free until the sort starts
         if (fast) {
             rc = binner_reserve_range32(binner, n_records);
             if (rc != SPLAT_OK) return rc;
             range32 = binner->range32;
-            const BinParams bp = {width, height, tile, ntx, nty, row0, row1};
-            const uint32_t blocks = div_up(n_records, BAND_BLOCK);
-            uint32_t *keys_by_idx = sorter->keys_b, *blocksums = sorter->hist; // both free until the sort starts
             stage_begin(ctx, SPLAT_STAGE_PROJECT);
-            hipLaunchKernelGGL(k_band_prepare, dim3(blocks), dim3(BAND_THREADS), 0, ctx->stream, (const float4 *)records, n_records,
-                               bp, keys_by_idx, range32, blocksums);
+            hipLaunchKernelGGL(k_band_prepare, dim3(blocks), dim3(BAND_THREADS), 0, ctx->stream, recs, n_records, bp, keys_by_idx, range32,
+                               blocksums);
             LAUNCH_CHECK(ctx, "k_band_prepare");
             rc = scan_exclusive_u32(ctx, blocksums, blocksums, blocks, sorter->d_count);
             if (rc != SPLAT_OK) return rc;
@@ -617,16 +607,15 @@ int splat_band_frame(splat_ctx *ctx, splat_sorter *sorter, splat_binner *binner,
             rc = binner_reserve_range_wide(binner, n_records);
             if (rc != SPLAT_OK) return rc;
             range_wide = reinterpret_cast<uint2 *>(binner->range32);
-            const BinParams bp = {width, height, tile, ntx, nty, row0, row1};
-            const uint32_t blocks = div_up(n_records, BAND_BLOCK);
-            uint32_t *keys_by_idx = sorter->keys_b, *blocksums = sorter->hist; // both free until the sort starts
             stage_begin(ctx, SPLAT_STAGE_PROJECT);
-            if (disc)
-                hipLaunchKernelGGL(k_band_prepare_wide<SPLAT_RECORDS_DISC48>, dim3(blocks), dim3(BAND_THREADS), 0, ctx->stream,
-                                   (const float4 *)records, n_records, bp, keys_by_idx, range_wide, blocksums);
-            else
-                hipLaunchKernelGGL(k_band_prepare_wide<SPLAT_RECORDS_PROJECTED>, dim3(blocks), dim3(BAND_THREADS), 0, ctx->stream,
-                                   (const float4 *)records, n_records, bp, keys_by_idx, range_wide, blocksums);
+            const bool ok = variant_dispatch(
+                [&](auto format) {
+                    launch_kernel(ctx, NO_STAGE, k_band_prepare_wide<format.value>, dim3(blocks), dim3(BAND_THREADS), recs, n_records, bp,
+                                  keys_by_idx, range_wide, blocksums);
+                    return true;
+                },
+                OneOf<SPLAT_RECORDS_PROJECTED, SPLAT_RECORDS_DISC48>{(int)cfg->record_format});
+            if (!ok) return ctx_fail(ctx, SPLAT_ERR_INVALID, "k_band_prepare_wide: no kernel for this record format");
             LAUNCH_CHECK(ctx, "k_band_prepare_wide");
             rc = scan_exclusive_u32(ctx, blocksums, blocksums, blocks, sorter->d_count);
             if (rc != SPLAT_OK) return rc;
@@ -635,7 +624,7 @@ int splat_band_frame(splat_ctx *ctx, splat_sorter *sorter, splat_binner *binner,
             LAUNCH_CHECK(ctx, "k_band_compact_wide");
             stage_end(ctx, SPLAT_STAGE_PROJECT);
         } else {
-            rc = band_keys_device(ctx, sorter, records, n_records, width, height, tile, row0, row1);
+            rc = band_keys_device(ctx, sorter, records, n_records, width, height, tile, band.row0, band.row1);
             if (rc != SPLAT_OK) return rc;
         }
         // kept count -> host, without stalling the stream
@@ -655,13 +644,13 @@ int splat_band_frame(splat_ctx *ctx, splat_sorter *sorter, splat_binner *binner,
         if (rc != SPLAT_OK) return rc;
         sorter->ran = true;
     }
-    rc = binner_run(binner, records, n_records, splat_sort_sorted_payload(sorter), bound, width, height, row0, row1, range32,
-                    n_records ? sorter->d_count : nullptr, nullptr, range_wide);
+    BinRunArgs run;
+    run.projected = records, run.n_splats = n_records, run.sorted = splat_sort_sorted_payload(sorter), run.n_sorted = bound;
+    run.width = width, run.height = height, run.tile_row0 = band.row0, run.tile_row1 = band.row1;
+    run.range32 = range32, run.n_sorted_dev = n_records ? sorter->d_count : nullptr, run.range_wide = range_wide;
+    rc = binner_run(binner, run);
     if (rc != SPLAT_OK) return rc;
     void *indices = binner->pairs.result_in_primary ? binner->pairs.payload : binner->pairs.payload_b;
-    splat_composite_cfg c2 = *cfg;
-    c2.tile_row0 = row0;
-    c2.tile_row1 = row1;
     return splat_composite(ctx, &c2, band_color, band_color_stride, normals, 1, records, indices, binner->counts, binner->offsets, width,
                            height, out_rgba8, out_rgba32f, consumed_dptr);
 }
@@ -741,13 +730,10 @@ static int render_frame_impl(splat_ctx *ctx, splat_sorter *sorter, splat_binner 
     // The projector also emits each splat's clamped tile range, which turns the binner's 16-byte bounds gather (in sorted
     // order) into a 4-byte one (tile coordinates of 8 bits) or an 8-byte one (16 bits).
     const uint32_t tile = splat_bin_tile_size(binner);
-    const uint32_t ntx = div_up(width, tile), nty = div_up(height, tile);
-    uint32_t row0 = cfg->tile_row0, row1 = cfg->tile_row1 > nty ? nty : cfg->tile_row1;
-    if (row0 > row1) row0 = row1;
+    const TileBand band = tile_band(width, height, tile, cfg->tile_row0, cfg->tile_row1);
     // fast: range32, and the tile-first order may run; wide: beyond 256 x 256 tiles, the 8-byte range (sort-first).  Either way
     // the binner never reads the records, so lit records and a disc frame without ProjectedSplat records work on every screen.
-    const bool fast = range_fits_8_bits(ntx, nty) && n > 0;
-    const bool wide = !fast && n > 0 && bin_accepts(ntx, nty);
+    const bool fast = band.fast(n), wide = band.wide(n);
     if ((!projected || lit || disc_lit) && n > 0 && !fast && !wide)
         return ctx_fail(ctx, SPLAT_ERR_INVALID, "splat_render_frame: the screen has more tiles than the binner takes (65535 a side, 2^24 "
                                                 "in all)");
@@ -755,7 +741,7 @@ static int render_frame_impl(splat_ctx *ctx, splat_sorter *sorter, splat_binner 
     uint32_t *range32 = nullptr;
     uint2 *range_wide = nullptr;
     // (a strict band: the projector skips what provably cannot reach it; those splats' records are then not written)
-    const BinParams bp = {width, height, tile, ntx, nty, row0, row1, (row0 > 0 || row1 < nty) ? 1u : 0u};
+    const BinParams bp = bin_params(width, height, tile, band, band.strict());
     if (ell && bp.skip_outside)
         return ctx_fail(ctx, SPLAT_ERR_INVALID, "splat_render_frame_ellipsoids: the ellipsoid footprint has no band frame (render every tile row)");
     if (fast) {
@@ -772,13 +758,14 @@ static int render_frame_impl(splat_ctx *ctx, splat_sorter *sorter, splat_binner 
     TfHistOut ho = {};
     // a strict band of a fraction of the screen (the exchange-free multi-GPU cut): the projector leaves the splats that can reach
     // it compacted per group of 4096 (project.hip: k_project_hist_bandc) and the scatter runs over those only
-    const bool band_compact = tile_first && bp.skip_outside && band_compacting(row0, row1, nty);
+    const bool band_compact = tile_first && bp.skip_outside && band_compacting(band);
     if (tile_first) { // the projector also counts each 1024-splat block's pairs per low tile-id digit
-        rc = binner_reserve(binner, ntx * nty, n);
+        rc = binner_reserve(binner, band.tiles(), n);
         if (rc != SPLAT_OK) return rc;
         // small frames: 256-splat blocks, so that the first pass is more than a handful of workgroups
         const uint32_t block = band_compact ? BTC_GROUP : (n <= TF_SMALL_FRAME_SPLATS && !bp.skip_outside) ? TF_BLOCK_SMALL : TF_BLOCK_LARGE;
-        ho = {binner->tf_hist, binner->blocksums, binner->d_total + 1, (1u << tile_id_low_bits(ntx * nty)) - 1u, div_up(n, block), block};
+        ho.hist = binner->tf_hist, ho.blocksums = binner->blocksums, ho.overflow_flag = binner->d_total + 1;
+        ho.mask = (1u << tile_id_low_bits(band.tiles())) - 1u, ho.num_parts = div_up(n, block), ho.block = block;
         binner->tf_block = block;
         if (band_compact) {
             rc = binner_reserve_band_idx(ctx, binner, n);
@@ -787,33 +774,28 @@ static int render_frame_impl(splat_ctx *ctx, splat_sorter *sorter, splat_binner 
             ho.kept_groups = sorter->hist; // (free in the tile-first order: the sorter's own passes do not run)
         }
     }
-    if (disc && n > binner->discs_cap) { // (48 bytes per splat: room for the lit records)
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (binner->discs) (void)hipFree(binner->discs);
-        binner->discs = nullptr;
-        binner->discs_cap = 0;
-        if (hipMalloc(&binner->discs, (size_t)n * 48 + 256) != hipSuccess) return ctx_fail(ctx, SPLAT_ERR_OOM, "disc records hipMalloc");
-        binner->discs_cap = n;
+    if (disc) { // (48 bytes per splat: room for the lit records)
+        rc = device_reserve(ctx, &binner->discs, &binner->discs_cap, n, (size_t)n * 48 + 256, "disc records hipMalloc");
+        if (rc != SPLAT_OK) return rc;
     }
     if (ctx->timing) { // (before binner_run promises a report: nothing that can fail may stand between that promise and the composite_launch that keeps it)
-        rc = ctx_ensure_consumed(ctx, ntx * nty);
+        rc = ctx_ensure_consumed(ctx, band.tiles());
         if (rc != SPLAT_OK) return rc;
     }
     // (the payload array is not written: payload = splat index)
     const LitIO lio = {(const float4 *)color, (const float4 *)normals, color_stride, 1u, cfg->prelit,
                        lit ? (float4 *)projected : disc_lit ? (float4 *)binner->discs : nullptr};
-    rc = project_launch(ctx, uniforms, props, pos_stride, n, 0, lit ? nullptr : projected, splat_sort_keys(sorter), nullptr, n, range32, &bp,
-                        tile_first ? &ho : nullptr, normals, 1, disc ? binner->discs : nullptr, &lio, range_wide, ell);
+    ProjectArgs pa;
+    pa.uniforms = uniforms, pa.pos_radius = props, pa.pr_stride_vec4 = pos_stride, pa.n = n;
+    pa.projected = lit ? nullptr : projected, pa.keys = splat_sort_keys(sorter), pa.n_padded = n;
+    pa.range32 = range32, pa.range_wide = range_wide, pa.bp = &bp, pa.hist_out = tile_first ? &ho : nullptr;
+    pa.normals = normals, pa.discs = disc ? binner->discs : nullptr, pa.lit = &lio, pa.ell = ell;
+    rc = project_launch(ctx, pa);
     if (rc != SPLAT_OK) return rc;
-    binner->tf_hist_ready = tile_first;
-    binner->tf_cidx = band_compact ? binner->band_idx : nullptr;
-    binner->tf_kept = band_compact ? sorter->hist : nullptr;
     // (with per-index tile ranges the binner never reads the records; it only wants a non-null pointer)
     const void *bin_records = projected ? projected : (const void *)binner->discs;
     if (tile_first) {
-        // bin in index order, depth-sort per tile: no global sort, no gather (tile_first.hip)
-        sorter->ran = false; // the sorter holds this frame's unsorted depth keys
-        rc = binner_run(binner, bin_records, n, nullptr, n, width, height, row0, row1, range32, nullptr, sorter->keys);
+        rc = bin_tile_first(sorter, binner, bin_records, n, width, height, band, band_compact);
         if (rc != SPLAT_OK) return rc;
     } else {
         stage_begin(ctx, SPLAT_STAGE_SORT);
@@ -822,26 +804,22 @@ static int render_frame_impl(splat_ctx *ctx, splat_sorter *sorter, splat_binner 
         stage_end(ctx, SPLAT_STAGE_SORT);
         if (rc != SPLAT_OK) return rc;
         sorter->ran = true;
-        rc = binner_run(binner, bin_records, n, splat_sort_sorted_payload(sorter), n, width, height, row0, row1, range32, nullptr, nullptr,
-                        range_wide);
+        BinRunArgs run;
+        run.projected = bin_records, run.n_splats = n, run.sorted = splat_sort_sorted_payload(sorter), run.n_sorted = n;
+        run.width = width, run.height = height, run.tile_row0 = band.row0, run.tile_row1 = band.row1;
+        run.range32 = range32, run.range_wide = range_wide;
+        rc = binner_run(binner, run);
         if (rc != SPLAT_OK) return rc;
     }
-    // (fields, not the public getters: those wait for a sync-free frame's pair total to come back)
-    void *counts = binner->counts, *offsets = binner->offsets;
-    void *indices = binner->pairs.result_in_primary ? binner->pairs.payload : binner->pairs.payload_b;
-    // (n == 0: every list is empty and no record is read; the composite only wants a non-null pointer)
-    const void *records = disc ? (n ? (const void *)binner->discs : (projected ? projected : (const void *)counts)) : projected;
-    uint32_t *report = binner->report_for_composite; // (tile-first frames: the frame's last kernel reports it: common.h)
-    binner->report_for_composite = nullptr;
     CompositeArgs a;
     a.color_opacity = color, a.color_stride_vec4 = color_stride;
     a.normals = normals;
-    a.projected = records;
-    a.tile_indices = indices, a.tile_counts = counts, a.tile_offsets = offsets;
+    // (n == 0: every list is empty and no record is read; the composite only wants a non-null pointer)
+    a.projected = disc ? (n ? (const void *)binner->discs : (projected ? projected : (const void *)binner->counts)) : projected;
+    composite_binner_lists(binner, a); // (tile-first frames: with the report, which the frame's last kernel sends: common.h)
     a.width = width, a.height = height;
     a.out_rgba8 = out_rgba8, a.out_rgba32f = out_rgba32f;
     a.consumed = (ctx->timing && (ctx->timing_mask & SPLAT_TIMING_COUNT_ENTRIES)) ? (void *)ctx->d_consumed : nullptr;
-    a.frame_total = binner->d_total, a.report = report, a.report_seq = binner->report_seq;
     a.aov = aov;
     // (32-byte disc records carry no depth: the ProjectedSplat records' depth words, when the frame writes them)
     a.ext_z = (disc && !disc_lit && projected) ? (const float *)projected + 4 : nullptr, a.ext_zstride = 8u;
@@ -908,17 +886,13 @@ int splat_render_frame_ellipsoids_aa(splat_ctx *ctx, splat_sorter *sorter, splat
     ARG_CHECK(ctx, cfg && cfg->footprint == SPLAT_FOOTPRINT_ELLIPSOID);
     ARG_CHECK(ctx, uniforms && positions && color_opacity && scales && rotations);
     ARG_CHECK(ctx, (((uintptr_t)positions | (uintptr_t)scales | (uintptr_t)rotations | (uintptr_t)color_opacity) & 15) == 0);
-    if (n > ctx->aa_color_cap) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->aa_color) (void)hipFree(ctx->aa_color);
-        ctx->aa_color = nullptr;
-        ctx->aa_color_cap = 0;
-        if (hipMalloc(&ctx->aa_color, (size_t)n * 16) != hipSuccess) return ctx_fail(ctx, SPLAT_ERR_OOM, "antialiased colour plane hipMalloc");
-        ctx->aa_color_cap = n;
-    }
+    int rc = device_reserve(ctx, &ctx->aa_color, &ctx->aa_color_cap, n, (size_t)n * 16, "antialiased colour plane hipMalloc");
+    if (rc != SPLAT_OK) return rc;
     const EllIO ell = {(const float4 *)scales, 1u, (const float4 *)rotations, 1u};
-    const int rc = project_ellipsoid_aa_launch(ctx, uniforms, positions, 1, ell, n, nullptr, nullptr, nullptr, nullptr, 0, nullptr, color_opacity,
-                                               1, ctx->aa_color, false); // (untimed: the frame's projector is the PROJECT stage's one interval)
+    ProjectAaArgs aa; // (untimed: the frame's projector is the PROJECT stage's one interval)
+    aa.uniforms = uniforms, aa.positions = positions, aa.ell = &ell, aa.n = n;
+    aa.color_opacity = color_opacity, aa.color_opacity_out = ctx->aa_color;
+    rc = project_ellipsoid_aa_launch(ctx, aa);
     if (rc != SPLAT_OK) return rc;
     return splat_render_frame_ellipsoids(ctx, sorter, binner, cfg, uniforms, positions, scales, rotations, ctx->aa_color, n, width, height,
                                          projected, out_rgba8, out_rgba32f, aov);

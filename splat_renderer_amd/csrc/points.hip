@@ -256,17 +256,10 @@ extern "C" int splat_point_frame(splat_ctx *ctx, splat_binner *binner, const flo
     const uint32_t ntx = div_up(width, PT_TILE), nty = div_up(height, PT_TILE);
     ARG_CHECK(ctx, ntx <= 65535 && nty <= 65535 && (uint64_t)ntx * nty <= (1u << 24)); // (the binner's limits)
     splat_binner *b = binner;
-    if (n > b->points_cap) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // (the old buffer may still be read by a frame in flight)
-        if (b->points) (void)hipFree(b->points);
-        b->points = nullptr;
-        b->points_cap = 0;
-        const uint32_t cap = n + n / 4;
-        if (hipMalloc(&b->points, (size_t)(cap > n ? cap : n) * kPointBytes) != hipSuccess) {
-            b->points = nullptr;
-            return ctx_fail(ctx, SPLAT_ERR_OOM, "point frame hipMalloc");
-        }
-        b->points_cap = cap > n ? cap : n;
+    if (n > b->points_cap) { // (with a quarter's headroom, unless that overflows)
+        const uint32_t grown = n + n / 4 > n ? n + n / 4 : n;
+        const int rc = device_reserve(ctx, &b->points, &b->points_cap, grown, (size_t)grown * kPointBytes, "point frame hipMalloc");
+        if (rc != SPLAT_OK) return rc;
     }
     const size_t cap = b->points_cap;
     float4 *projected = (float4 *)b->points;
@@ -285,7 +278,9 @@ extern "C" int splat_point_frame(splat_ctx *ctx, splat_binner *binner, const flo
     // lists are complete when the resolve runs and there is never a frame to render again
     const bool allow_async = b->allow_async;
     b->allow_async = false;
-    int rc = binner_run(b, projected, n, sorted, n, width, height, 0, UINT32_MAX, nullptr);
+    BinRunArgs run;
+    run.projected = projected, run.n_splats = n, run.sorted = sorted, run.n_sorted = n, run.width = width, run.height = height;
+    int rc = binner_run(b, run);
     b->allow_async = allow_async;
     if (rc != SPLAT_OK) return rc;
     const uint32_t *indices = b->pairs.result_in_primary ? b->pairs.payload : b->pairs.payload_b;

@@ -607,16 +607,22 @@ static void load_uniforms(FrameUniforms &u, const float *uniforms) {
     u.time = uniforms[19]; u.w = uniforms[20]; u.h = uniforms[21];
 }
 
-int project_launch(splat_ctx *ctx, const float *uniforms, const void *pos_radius, uint32_t pr_stride_vec4, uint32_t n,
-                   uint32_t index_base, void *projected, void *keys, void *payload, uint32_t n_padded, uint32_t *range32,
-                   const BinParams *bp, const TfHistOut *hist_out, const void *normals, uint32_t normal_stride_vec4, void *discs,
-                   const LitIO *lit, uint2 *range_wide, const EllIO *ell) {
+int project_launch(splat_ctx *ctx, const ProjectArgs &a) {
+    const uint32_t pr_stride_vec4 = a.pr_stride_vec4, n = a.n, index_base = a.index_base, n_padded = a.n_padded;
+    const uint32_t normal_stride_vec4 = a.normal_stride_vec4;
+    void *const projected = a.projected, *const keys = a.keys, *const payload = a.payload, *const discs = a.discs;
+    uint32_t *const range32 = a.range32;
+    uint2 *const range_wide = a.range_wide;
+    const BinParams *const bp = a.bp;
+    const TfHistOut *const hist_out = a.hist_out;
+    const LitIO *const lit = a.lit;
+    const EllIO *const ell = a.ell;
     FrameUniforms u;
-    load_uniforms(u, uniforms);
+    load_uniforms(u, a.uniforms);
     const uint32_t work = keys ? n_padded : n;
     if (work == 0) return SPLAT_OK;
     BinParams none = {0, 0, 1, 0, 0, 0, 0};
-    const float4 *src = (const float4 *)pos_radius + (size_t)index_base * pr_stride_vec4;
+    const float4 *src = (const float4 *)a.pos_radius + (size_t)index_base * pr_stride_vec4;
     const bool disc = discs != nullptr; // the oriented-disc footprint (disc.h): normals in, disc records out
     // ... or the anisotropic Gaussian's (ellipsoid.h): scales and rotations in, disc records out (not on the band paths)
     const bool el = disc && ell != nullptr;
@@ -627,7 +633,7 @@ int project_launch(splat_ctx *ctx, const float *uniforms, const void *pos_radius
     const bool with_lit = lit && lit->records && !disc, disc_lit = lit && lit->records && disc;
     if ((with_lit || disc_lit) && !(keys && (range32 || range_wide) && !payload && index_base == 0))
         return ctx_fail(ctx, SPLAT_ERR_INVALID, "project_launch: lit records are written by the frame's projector only");
-    DiscIO dio = {(disc && !el) ? (const float4 *)normals + (size_t)index_base * normal_stride_vec4 : nullptr, normal_stride_vec4,
+    DiscIO dio = {(disc && !el) ? (const float4 *)a.normals + (size_t)index_base * normal_stride_vec4 : nullptr, normal_stride_vec4,
                   (float4 *)discs, disc_lit ? 3u : 2u, EllIO{}};
     if (el) {
         dio.ell = *ell;
@@ -646,8 +652,9 @@ int project_launch(splat_ctx *ctx, const float *uniforms, const void *pos_radius
         // a strict band (no ellipsoid: refused above), in 1024-splat blocks only: the caller keeps hist_out->block at TF_BLOCK_LARGE for it
         TfHistOut ho = *hist_out;
         if (hist_out->cidx) { // ... of a fraction of the screen: groups of 4096 splats, the survivors left compacted (num_parts = groups)
-            ho.xcd_per = ho.num_parts >= 64u ? div_up(ho.num_parts, 8u) : 0u;
-            const dim3 grid(ho.xcd_per ? 8u * ho.xcd_per : ho.num_parts);
+            const XcdGrid xg = xcd_grid(ho.num_parts);
+            ho.xcd_per = xg.xcd_per;
+            const dim3 grid(xg.grid);
             ok = variant_dispatch(
                 [&](auto d, auto l) {
                     launch_kernel(ctx, NO_STAGE, k_project_hist_bandc<d.value, l.value>, grid, dim3(PBC_THREADS), u, src, pr_stride_vec4, n,
@@ -668,8 +675,9 @@ int project_launch(splat_ctx *ctx, const float *uniforms, const void *pos_radius
         TfHistOut ho = *hist_out;
         const bool small = hist_out->block == TF_BLOCK_SMALL;
         const uint32_t blocks = div_up(work, small ? 256u : 1024u);
-        ho.xcd_per = blocks >= 64u ? div_up(blocks, 8u) : 0u; // the blocks dealt as k_tf_scatter's are (common.h: xcd_block_of)
-        const dim3 grid(ho.xcd_per ? 8u * ho.xcd_per : blocks);
+        const XcdGrid xg = xcd_grid(blocks); // the blocks dealt as k_tf_scatter's are (common.h: xcd_block_of)
+        ho.xcd_per = xg.xcd_per;
+        const dim3 grid(xg.grid);
         ok = variant_dispatch(
             [&](auto d, auto l, auto per, auto e) {
                 if constexpr (d.value || !e.value) {
@@ -713,19 +721,17 @@ int project_launch(splat_ctx *ctx, const float *uniforms, const void *pos_radius
 // for the compensated colour plane only.  timed: the launch is a SPLAT_STAGE_PROJECT interval of its own (the staged entry point);
 // the frame passes false, so that a timed antialiased frame still records one PROJECT interval, its projector's: the
 // compensation pass runs before it and outside every stage.
-int project_ellipsoid_aa_launch(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4, const EllIO &ell,
-                                uint32_t n, void *projected, void *records, void *keys, void *payload, uint32_t n_padded, float *rho_out,
-                                const void *color_opacity, uint32_t color_stride_vec4, void *color_opacity_out, bool timed) {
-    const uint32_t work = keys ? n_padded : n;
+int project_ellipsoid_aa_launch(splat_ctx *ctx, const ProjectAaArgs &a) {
+    const uint32_t work = a.keys ? a.n_padded : a.n;
     if (work == 0) return SPLAT_OK;
     FrameUniforms u;
-    load_uniforms(u, uniforms);
-    const AaIO aa = {rho_out, (const float4 *)color_opacity, color_stride_vec4, (float4 *)color_opacity_out};
-    if (timed) stage_begin(ctx, SPLAT_STAGE_PROJECT);
-    hipLaunchKernelGGL(k_project_ellipsoid_aa, dim3(div_up(work, 256)), dim3(256), 0, ctx->stream, u, (const float4 *)positions, pos_stride_vec4, n,
-                       keys ? n_padded : n, (float4 *)projected, (float4 *)records, (uint32_t *)keys, (uint32_t *)payload, ell, aa);
+    load_uniforms(u, a.uniforms);
+    const AaIO aa = {a.rho_out, (const float4 *)a.color_opacity, a.color_stride_vec4, (float4 *)a.color_opacity_out};
+    if (a.timed) stage_begin(ctx, SPLAT_STAGE_PROJECT);
+    hipLaunchKernelGGL(k_project_ellipsoid_aa, dim3(div_up(work, 256)), dim3(256), 0, ctx->stream, u, (const float4 *)a.positions, a.pos_stride_vec4,
+                       a.n, work, (float4 *)a.projected, (float4 *)a.records, (uint32_t *)a.keys, (uint32_t *)a.payload, *a.ell, aa);
     LAUNCH_CHECK(ctx, "k_project_ellipsoid_aa");
-    if (timed) stage_end(ctx, SPLAT_STAGE_PROJECT);
+    if (a.timed) stage_end(ctx, SPLAT_STAGE_PROJECT);
     return SPLAT_OK;
 }
 
@@ -739,7 +745,10 @@ int splat_project(splat_ctx *ctx, const float *uniforms, const void *pos_radius,
     ARG_CHECK(ctx, (keys == nullptr) == (payload == nullptr));
     ARG_CHECK(ctx, keys == nullptr || n_padded >= n);
     ARG_CHECK(ctx, (((uintptr_t)pos_radius | (uintptr_t)projected) & 15) == 0);
-    return project_launch(ctx, uniforms, pos_radius, pr_stride_vec4, n, 0, projected, keys, payload, n_padded, nullptr, nullptr, nullptr);
+    ProjectArgs a;
+    a.uniforms = uniforms, a.pos_radius = pos_radius, a.pr_stride_vec4 = pr_stride_vec4, a.n = n;
+    a.projected = projected, a.keys = keys, a.payload = payload, a.n_padded = n_padded;
+    return project_launch(ctx, a);
 }
 
 int splat_project_disc(splat_ctx *ctx, const float *uniforms, const void *pos_radius, uint32_t pr_stride_vec4, const void *normals,
@@ -752,8 +761,11 @@ int splat_project_disc(splat_ctx *ctx, const float *uniforms, const void *pos_ra
     ARG_CHECK(ctx, keys == nullptr || n_padded >= n);
     ARG_CHECK(ctx, (((uintptr_t)pos_radius | (uintptr_t)normals | (uintptr_t)projected | (uintptr_t)discs) & 15) == 0);
     // (n == 0 with keys only pads them, which either footprint's kernel does)
-    return project_launch(ctx, uniforms, pos_radius, pr_stride_vec4, n, 0, projected, keys, payload, n_padded, nullptr, nullptr, nullptr,
-                          normals, normal_stride_vec4, n ? discs : nullptr);
+    ProjectArgs a;
+    a.uniforms = uniforms, a.pos_radius = pos_radius, a.pr_stride_vec4 = pr_stride_vec4, a.n = n;
+    a.projected = projected, a.keys = keys, a.payload = payload, a.n_padded = n_padded;
+    a.normals = normals, a.normal_stride_vec4 = normal_stride_vec4, a.discs = n ? discs : nullptr;
+    return project_launch(ctx, a);
 }
 
 int splat_project_ellipsoid(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4, const void *scales,
@@ -766,8 +778,11 @@ int splat_project_ellipsoid(splat_ctx *ctx, const float *uniforms, const void *p
     ARG_CHECK(ctx, keys == nullptr || n_padded >= n);
     ARG_CHECK(ctx, (((uintptr_t)positions | (uintptr_t)scales | (uintptr_t)rotations | (uintptr_t)projected | (uintptr_t)records) & 15) == 0);
     const EllIO ell = {(const float4 *)scales, scale_stride_vec4, (const float4 *)rotations, rot_stride_vec4};
-    return project_launch(ctx, uniforms, positions, pos_stride_vec4, n, 0, projected, keys, payload, n_padded, nullptr, nullptr, nullptr,
-                          nullptr, 1, n ? records : nullptr, nullptr, nullptr, &ell);
+    ProjectArgs a;
+    a.uniforms = uniforms, a.pos_radius = positions, a.pr_stride_vec4 = pos_stride_vec4, a.n = n;
+    a.projected = projected, a.keys = keys, a.payload = payload, a.n_padded = n_padded;
+    a.discs = n ? records : nullptr, a.ell = &ell;
+    return project_launch(ctx, a);
 }
 
 int splat_project_ellipsoid_aa(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4, const void *scales,
@@ -783,8 +798,12 @@ int splat_project_ellipsoid_aa(splat_ctx *ctx, const float *uniforms, const void
     ARG_CHECK(ctx, (((uintptr_t)positions | (uintptr_t)scales | (uintptr_t)rotations | (uintptr_t)projected | (uintptr_t)records |
                      (uintptr_t)color_opacity | (uintptr_t)color_opacity_out) & 15) == 0 && ((uintptr_t)rho_out & 3) == 0);
     const EllIO ell = {(const float4 *)scales, scale_stride_vec4, (const float4 *)rotations, rot_stride_vec4};
-    return project_ellipsoid_aa_launch(ctx, uniforms, positions, pos_stride_vec4, ell, n, projected, records, keys, payload, n_padded,
-                                       (float *)rho_out, color_opacity, color_stride_vec4, color_opacity_out, true);
+    ProjectAaArgs a;
+    a.uniforms = uniforms, a.positions = positions, a.pos_stride_vec4 = pos_stride_vec4, a.ell = &ell, a.n = n;
+    a.projected = projected, a.records = records, a.keys = keys, a.payload = payload, a.n_padded = n_padded;
+    a.rho_out = (float *)rho_out, a.color_opacity = color_opacity, a.color_stride_vec4 = color_stride_vec4;
+    a.color_opacity_out = color_opacity_out, a.timed = true;
+    return project_ellipsoid_aa_launch(ctx, a);
 }
 
 int splat_sampling_rate_max(splat_ctx *ctx, const float *uniforms, float focal_px, float near, float margin, const void *positions,
@@ -806,8 +825,10 @@ int splat_project_slice(splat_ctx *ctx, const float *uniforms, const void *pos_r
     if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
     ARG_CHECK(ctx, uniforms && (count == 0 || (pos_radius && projected_slice)) && pr_stride_vec4 >= 1);
     ARG_CHECK(ctx, (((uintptr_t)pos_radius | (uintptr_t)projected_slice) & 15) == 0);
-    return project_launch(ctx, uniforms, pos_radius, pr_stride_vec4, count, first, projected_slice, nullptr, nullptr, 0, nullptr,
-                          nullptr, nullptr);
+    ProjectArgs a;
+    a.uniforms = uniforms, a.pos_radius = pos_radius, a.pr_stride_vec4 = pr_stride_vec4, a.n = count, a.index_base = first;
+    a.projected = projected_slice;
+    return project_launch(ctx, a);
 }
 
 

@@ -399,8 +399,7 @@ static int radix_sort_rowscan(splat_ctx *ctx, uint32_t *k0, uint32_t *p0, uint32
     uint32_t npasses = 0;
     for (uint32_t sh = bit_begin, w = first_bits; sh < bit_end; sh += w, w = 8) ++npasses;
     uint32_t shift = bit_begin;
-    const uint32_t xcd_per = parts >= 64u ? div_up(parts, 8u) : 0u;
-    const uint32_t grid_parts = xcd_per ? 8u * xcd_per : parts;
+    const uint32_t xcd_per = xcd_grid(parts).xcd_per, grid_parts = xcd_grid(parts).grid;
     for (uint32_t pass = 0; pass < npasses; ++pass) {
         const uint32_t want = pass == 0 ? first_bits : 8u;
         const uint32_t bits = bit_end - shift < want ? bit_end - shift : want;

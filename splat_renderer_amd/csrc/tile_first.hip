@@ -643,9 +643,8 @@ __global__ __launch_bounds__(TS_THREADS, TS_MAX_ITEMS <= 8 ? 6 : TS_MAX_ITEMS <=
 }
 
 // mean_list: the frame's pairs per tile of its band, as far as the host knows them (the previous frame's in a sync-free frame).
-int tile_sort_launch(splat_ctx *ctx, const uint32_t *offsets, uint32_t tiles, uint2 *vals, uint2 *scratch, uint32_t *out_idx,
-                     uint32_t *counts, uint32_t *frame_flags, uint32_t mean_list, uint32_t band_tiles, uint32_t long_tiles_hint,
-                     uint32_t *short_class_io) {
+int tile_sort_launch(splat_ctx *ctx, const TileSortArgs &a) {
+    uint32_t *const counts = a.counts, *const short_class_io = a.short_class_io;
     {
         int prc = ctx_resolve_rank_mode(ctx); // (probe of the LDS atomics' lane order, once per context)
         if (prc != SPLAT_OK) return prc;
@@ -662,7 +661,7 @@ int tile_sort_launch(splat_ctx *ctx, const uint32_t *offsets, uint32_t tiles, ui
     // one_class.txt): bands of 840 tiles (C2, eight ranks) 32 -> 22 us, of 2040 (four ranks) 35 -> 29, of ~3000 (C3, eight ranks)
     // 48 -> 44; a whole C2 screen (8160 tiles, 4969 of them non-empty) is slower with one launch (77 -> 83 us,
     // profiles/r03_j_tile_sort_one_launch_C2.txt).
-    const bool one_class = (band_tiles ? band_tiles : tiles) <= 4200u;
+    const bool one_class = (a.band_tiles ? a.band_tiles : a.tiles) <= 4200u;
     // The short class's size, by the frame's mean list length (measured, `bin_tile_sort` with 8 | 12 | 16 elements per thread:
     // C1, mean 570: 45.6 | 41.4 | 45.9 us; C3, mean 910: 193 | 180 | 188; C2, mean 1380: 77.0 | 76.6 | 72.9 — and a third
     // class in between loses its launch: profiles/r04_u_tile_sort_classes.txt).  SPLAT_TILE_SORT_SHORT=8 | 12 | 16 forces one.
@@ -671,13 +670,13 @@ int tile_sort_launch(splat_ctx *ctx, const uint32_t *offsets, uint32_t tiles, ui
         const int v = e ? atoi(e) : 0;
         return (v == 8 || v == 12 || v == 16) ? (uint32_t)v : 0u;
     }();
-    const uint32_t short_items = force_short ? force_short : mean_list < 320u ? 8u : mean_list < 1152u ? 12u : 16u;
+    const uint32_t short_items = force_short ? force_short : a.mean_list < 320u ? 8u : a.mean_list < 1152u ? 12u : 16u;
     const uint32_t short_cap = short_items * TS_THREADS;
     // (two passes of up to 12 bits instead of three of 8 — SPLAT_TILE_SORT_DIGITS=12 in rounds 3 and 4 — measured slower, 76 + 33
     // against 56 + 23 us at C2: profiles/r03_f_tile_sort_wide_digits_C2.txt; removed in round 5)
 #define SPLAT_TILE_SORT_(RA, ITEMS, LAST, ABOVE, COUNTS)                                                                       \
-    hipLaunchKernelGGL((k_tile_sort<RA, ITEMS, LAST>), dim3(tiles), dim3(TS_THREADS), 0, ctx->stream, offsets, tiles, ABOVE, vals, \
-                       scratch, out_idx, COUNTS, frame_flags TS_HOOK_ARGS)
+    hipLaunchKernelGGL((k_tile_sort<RA, ITEMS, LAST>), dim3(a.tiles), dim3(TS_THREADS), 0, ctx->stream, a.offsets, a.tiles, ABOVE, a.vals, \
+                       a.scratch, a.out_idx, COUNTS, a.frame_flags TS_HOOK_ARGS)
 #define SPLAT_TILE_SORT(ITEMS, LAST, ABOVE, COUNTS)                  \
     do {                                                             \
         if (ra) SPLAT_TILE_SORT_(true, ITEMS, LAST, ABOVE, COUNTS);  \
@@ -692,7 +691,7 @@ int tile_sort_launch(splat_ctx *ctx, const uint32_t *offsets, uint32_t tiles, ui
         // class: a tile that has outgrown it since goes through its global-memory passes — slow, correct, and counted, so
         // that the next frame launches both classes again.
         // (the count is of the tiles beyond THAT frame's short class: it says nothing when the class has changed since)
-        no_long = long_tiles_hint == 0u && short_class_io && *short_class_io == short_items;
+        no_long = a.long_tiles_hint == 0u && short_class_io && *short_class_io == short_items;
         if (short_class_io) *short_class_io = short_items;
         if (short_items == 8u) { if (no_long) SPLAT_TILE_SORT(8, true, 0u, counts); else SPLAT_TILE_SORT(8, false, 0u, counts); }
         else if (short_items == 12u) { if (no_long) SPLAT_TILE_SORT(12, true, 0u, counts); else SPLAT_TILE_SORT(12, false, 0u, counts); }
@@ -932,33 +931,31 @@ __global__ __launch_bounds__(NW * 64, 4) void k_tf_downsweep2(const uint8_t *__r
 
 // The second pass and the tile offsets.  hist: 256 * num_parts + 256 words, num_parts = tf2_parts_bound(pairs bound,
 // low digits).  hi_bits == 0: only the offsets (the first pass's output is final).
-int tf_second_pass_launch(splat_ctx *ctx, const uint8_t *hi, const uint2 *val_in, uint2 *val_out, const TfRuns *runs, uint32_t pairs_bound,
-                          uint32_t tiles, uint32_t lo_bits, uint32_t hi_bits, uint32_t *hist, uint32_t *offsets, const uint32_t *d_total) {
-    const uint32_t num_parts = tf2_parts_bound(pairs_bound, lo_bits);
-    uint32_t *totals = hist + (size_t)256 * num_parts;
-    if (hi_bits > 0) {
-        const uint32_t hmask = (1u << hi_bits) - 1u;
+int tf_second_pass_launch(splat_ctx *ctx, const TfSecondPassArgs &a) {
+    const uint32_t num_parts = tf2_parts_bound(a.pairs_bound, a.lo_bits);
+    uint32_t *totals = a.hist + (size_t)256 * num_parts;
+    if (a.hi_bits > 0) {
+        const uint32_t hmask = (1u << a.hi_bits) - 1u;
         // each XCD takes a contiguous eighth of the partitions (common.h: xcd_block_of)
-        const uint32_t xcd_per = num_parts >= 64u ? div_up(num_parts, 8u) : 0u;
-        const uint32_t part_blocks = xcd_per ? 8u * xcd_per : num_parts;
-        hipLaunchKernelGGL(k_tf_upsweep2, dim3(part_blocks), dim3(TF_THREADS), 0, ctx->stream, hi, *runs, hmask, num_parts, hist, xcd_per);
+        const uint32_t xcd_per = xcd_grid(num_parts).xcd_per, part_blocks = xcd_grid(num_parts).grid;
+        hipLaunchKernelGGL(k_tf_upsweep2, dim3(part_blocks), dim3(TF_THREADS), 0, ctx->stream, a.hi, *a.runs, hmask, num_parts, a.hist, xcd_per);
         LAUNCH_CHECK(ctx, "k_tf_upsweep2");
-        int rc = radix_rowscan_launch(ctx, hist, num_parts, hmask + 1u);
+        int rc = radix_rowscan_launch(ctx, a.hist, num_parts, hmask + 1u);
         if (rc != SPLAT_OK) return rc;
-        const TfOffsetsArgs off = {tiles, lo_bits, offsets, d_total};
-        const dim3 grid(part_blocks + div_up(tiles + 1, 256)); // the partitions, then the blocks of tile offsets
+        const TfOffsetsArgs off = {a.tiles, a.lo_bits, a.offsets, a.d_total};
+        const dim3 grid(part_blocks + div_up(a.tiles + 1, 256)); // the partitions, then the blocks of tile offsets
         const bool ra = rank_atomic_ok(ctx, true); // (checked: k_tile_sort verifies every list this pass contributes to)
         // (512 threads per partition, eight pairs per thread: measured level with this, profiles/r05_b_second_pass_xcd_C3_C2.txt)
         // Workgroups per CU: four fit (37.9 KB each) and are what a pass of 7-bit digits likes (C1 22.4 -> 21.0 us, C2 level);
         // with 8-bit digits (screens beyond 2^14 tiles: C3, where a partition leaves 128-byte fragments) a fourth resident
         // workgroup LOSES — 135 -> 143 us, and two are worse still (154) —, so there 4 KB of dynamic LDS that nobody uses
         // keep it at three (profiles/r05_x_downsweep2_workgroups_per_cu.txt).
-        const uint32_t pad = hi_bits >= 8u ? 4096u : 0u;
+        const uint32_t pad = a.hi_bits >= 8u ? 4096u : 0u;
         if (ra)
-            hipLaunchKernelGGL((k_tf_downsweep2<true, 4>), grid, dim3(TF_THREADS), pad, ctx->stream, hi, val_in, val_out, *runs, hmask, num_parts, hist,
+            hipLaunchKernelGGL((k_tf_downsweep2<true, 4>), grid, dim3(TF_THREADS), pad, ctx->stream, a.hi, a.val_in, a.val_out, *a.runs, hmask, num_parts, a.hist,
                                totals, off, part_blocks, xcd_per);
         else
-            hipLaunchKernelGGL((k_tf_downsweep2<false, 4>), grid, dim3(TF_THREADS), pad, ctx->stream, hi, val_in, val_out, *runs, hmask, num_parts, hist,
+            hipLaunchKernelGGL((k_tf_downsweep2<false, 4>), grid, dim3(TF_THREADS), pad, ctx->stream, a.hi, a.val_in, a.val_out, *a.runs, hmask, num_parts, a.hist,
                                totals, off, part_blocks, xcd_per);
         LAUNCH_CHECK(ctx, "k_tf_downsweep2");
     }
@@ -967,32 +964,28 @@ int tf_second_pass_launch(splat_ctx *ctx, const uint8_t *hi, const uint2 *val_in
 
 // hist: the digit histogram the projector (k_project_hist) or the band prepare kernel counted, after
 // radix_rowscan_launch (rows scanned in place, digit totals behind them)
-int tf_scatter_launch(splat_ctx *ctx, const uint32_t *range32, const uint32_t *depth_keys, uint32_t n, uint32_t ntx, uint32_t mask,
-                      const uint32_t *hist, uint32_t *d_total, uint32_t pair_limit, uint32_t *overflow, uint8_t *out_hi,
-                      uint2 *out_val, uint32_t block_splats, uint32_t lo_bits, bool second_pass, const TfRuns *runs,
-                      uint32_t *offsets_if_final, uint32_t tiles, uint32_t *report, uint32_t seq, const uint32_t *cidx,
-                      const uint32_t *kept) {
-    const uint32_t parts = div_up(n, block_splats);
+int tf_scatter_launch(splat_ctx *ctx, const TfScatterArgs &a) {
+    const uint32_t parts = div_up(a.n, a.block_splats);
     // each XCD takes a contiguous eighth of the blocks (common.h: xcd_block_of; C3: this kernel 112 -> 97 us and the second
     // pass's downsweep 145 -> 135, C2 48.5 -> 47.0 / 44.1 -> 42.6: profiles/r05_c_first_pass_projector_xcd_C3_C2.txt)
-    const uint32_t xcd_per = parts >= 64u ? div_up(parts, 8u) : 0u;
-    const uint32_t grid_blocks = xcd_per ? 8u * xcd_per : parts;
-    if (cidx && block_splats != TF_GROUP) return ctx_fail(ctx, SPLAT_ERR_INVALID, "tf_scatter_launch: compacted input comes in groups of 4096 records");
-    const uint32_t *totals = hist + (size_t)256 * parts;
+    const XcdGrid xg = xcd_grid(parts);
+    if (a.cidx && a.block_splats != TF_GROUP) return ctx_fail(ctx, SPLAT_ERR_INVALID, "tf_scatter_launch: compacted input comes in groups of 4096 records");
+    const uint32_t *totals = a.hist + (size_t)256 * parts;
     {
         int prc = ctx_resolve_rank_mode(ctx); // (probe of the LDS atomics' lane order, once per context)
         if (prc != SPLAT_OK) return prc;
     }
     const bool ra = rank_atomic_ok(ctx, true); // (checked: k_tile_sort verifies every list this pass contributes to)
 #define SPLAT_TF_SCATTER_(RA, PER, COMPACTED)                                                                                     \
-    hipLaunchKernelGGL((k_tf_scatter<RA, PER, COMPACTED>), dim3(grid_blocks), dim3(TF_THREADS), 0, ctx->stream, range32, depth_keys, n, ntx, mask, parts, \
-                       hist, totals, d_total, pair_limit, overflow, out_hi, out_val, lo_bits, second_pass ? TF_RUN_ALIGN - 1u : 0u, *runs,         \
-                       second_pass ? nullptr : offsets_if_final, tiles, report, seq, cidx, kept, xcd_per)
+    hipLaunchKernelGGL((k_tf_scatter<RA, PER, COMPACTED>), dim3(xg.grid), dim3(TF_THREADS), 0, ctx->stream, a.range32, a.depth_keys, a.n, a.ntx, a.mask, \
+                       parts, a.hist, totals, a.d_total, a.pair_limit, a.overflow, a.out_hi, a.out_val, a.lo_bits,                \
+                       a.second_pass ? TF_RUN_ALIGN - 1u : 0u, *a.runs, a.second_pass ? nullptr : a.offsets_if_final, a.tiles, a.report, a.seq, \
+                       a.cidx, a.kept, xg.xcd_per)
 #define SPLAT_TF_SCATTER(RA, PER) SPLAT_TF_SCATTER_(RA, PER, false)
-    if (cidx) { // a multi-GPU band's kept splats, compacted per group of TF_GROUP records
+    if (a.cidx) { // a multi-GPU band's kept splats, compacted per group of TF_GROUP records
         if (ra) SPLAT_TF_SCATTER_(true, 4, true);
         else SPLAT_TF_SCATTER_(false, 4, true);
-    } else if (block_splats == TF_BLOCK_SMALL) {
+    } else if (a.block_splats == TF_BLOCK_SMALL) {
         if (ra) SPLAT_TF_SCATTER(true, 1);
         else SPLAT_TF_SCATTER(false, 1);
     } else {
