@@ -556,7 +556,7 @@ def sh_colors(eye, means, sh, degree, opacities):
     if not 0 <= int(degree) <= 3:
         raise SplatError(-1, "degree must be 0-3")
     _cuda_f32(sh, "sh")
-    sh2 = _cuda_f32(sh.reshape(n, -1), "sh")
+    sh2 = _cuda_f32(sh.reshape(n, -1) if n else sh.reshape(0, int(np.prod(sh.shape[1:]))), "sh")  # (no -1 for an empty tensor)
     if sh2.shape[1] < 3 * (int(degree) + 1) ** 2:
         raise SplatError(-1, f"sh holds {sh2.shape[1]} floats per splat; degree {degree} needs {3 * (int(degree) + 1) ** 2}")
     op = _cuda_f32(opacities.reshape(-1), "opacities")

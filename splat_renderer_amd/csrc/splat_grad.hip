@@ -16,7 +16,8 @@
 //                                     <RHO>), whose term joins dL/d(A, B, C) before gT is formed;
 //                                     zero where the forward's binary32 rho is 0
 // k_sh_colors_backward<DEG, CAM>
-//   sh.hip's basis and constants of degree DEG, dir = normalize(p - eye), zero where the forward's max(., 0) clamped.
+//   sh.hip's basis and constants of degree DEG, dir = normalize(p - eye), zero where the forward's max(., 0) clamped
+//   (sh_forward_sums: the forward's sums with the forward's roundings, so that the decision is the forward's).
 //   <CAM> (_camera): also dL/deye = -sum_i gpos[i], each splat's binary32 gpos summed in float64 (ShOpacityCam).
 // k_camera_sum_slices<NV>, k_camera_sum<MODE>
 //   The camera's gradient, dL/d(VP, eye), summed over all splats in a fixed order: the lanes of a wave by DPP
@@ -309,6 +310,51 @@ constexpr float GSH_C2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.315391
 constexpr float GSH_C3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f, 0.3731763325901154f,
                              -0.4570457994644658f, 1.445305721320277f, -0.5900435899266435f};
 
+// k_sh_colors' sums 0.5 + sum_k Y_k sh_k, bit for bit: sh.hip's operations with one rounding each, as sh.hip is built
+// (-ffp-contract=off).  The backward's clamp must be the forward's decision, and this file is built with contraction on: its own
+// sum, contracted to FMAs, lands on the other side of 0 for a channel within a few roundings of the edge.
+template <int DEG>
+__device__ __forceinline__ void sh_forward_sums(float vx, float vy, float vz, const float *__restrict__ row, float &r, float &g, float &b) {
+#pragma clang fp contract(off)
+    const float len = sqrtf((vx * vx + vy * vy) + vz * vz);
+    const bool has_dir = len > 0.0f && len < INFINITY;
+    const float il = has_dir ? 1.0f / len : 0.0f;
+    const float x = has_dir ? vx * il : 0.0f, y = has_dir ? vy * il : 0.0f, z = has_dir ? vz * il : 0.0f;
+    constexpr int NB = (DEG + 1) * (DEG + 1);
+    float Y[NB];
+    Y[0] = GSH_C0;
+    if (DEG > 0) {
+        Y[1] = -GSH_C1 * y;
+        Y[2] = GSH_C1 * z;
+        Y[3] = -GSH_C1 * x;
+    }
+    if (DEG > 1) {
+        const float xx = x * x, yy = y * y, zz = z * z;
+        Y[4] = GSH_C2[0] * (x * y);
+        Y[5] = GSH_C2[1] * (y * z);
+        Y[6] = GSH_C2[2] * ((2.0f * zz - xx) - yy);
+        Y[7] = GSH_C2[3] * (x * z);
+        Y[8] = GSH_C2[4] * (xx - yy);
+        if (DEG > 2) {
+            Y[9] = GSH_C3[0] * (y * (3.0f * xx - yy));
+            Y[10] = GSH_C3[1] * ((x * y) * z);
+            Y[11] = GSH_C3[2] * (y * ((4.0f * zz - xx) - yy));
+            Y[12] = GSH_C3[3] * (z * ((2.0f * zz - 3.0f * xx) - 3.0f * yy));
+            Y[13] = GSH_C3[4] * (x * ((4.0f * zz - xx) - yy));
+            Y[14] = GSH_C3[5] * (z * (xx - yy));
+            Y[15] = GSH_C3[6] * (x * (xx - 3.0f * yy));
+        }
+    }
+    r = 0.0f, g = 0.0f, b = 0.0f;
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {
+        r += Y[k] * row[3 * k];
+        g += Y[k] * row[3 * k + 1];
+        b += Y[k] * row[3 * k + 2];
+    }
+    r += 0.5f, g += 0.5f, b += 0.5f;
+}
+
 // the camera variant's last argument: grad_opacity, and per wave CAM_SLOTS doubles
 struct ShOpacityCam {
     float *gop;
@@ -334,6 +380,11 @@ __global__ __launch_bounds__(256) void k_sh_colors_backward(float ex, float ey, 
         const float4 p = pos[(size_t)i * pos_stride];
         const float4 gc = gcol[i];
         float vx = p.x - ex, vy = p.y - ey, vz = p.z - ez;
+        // the clamp: no gradient where the forward's max(., 0) took the 0 (decided on the forward's own bits, not on this
+        // kernel's contracted Y: everything below keeps the bits it had)
+        float r, g, b;
+        sh_forward_sums<DEG>(vx, vy, vz, row, r, g, b);
+        const float gr = (r > 0.0f) ? gc.x : 0.0f, gg = (g > 0.0f) ? gc.y : 0.0f, gb = (b > 0.0f) ? gc.z : 0.0f;
         const float len = sqrtf((vx * vx + vy * vy) + vz * vz);
         // the forward's rule: no direction where |p - eye| is not a positive finite number (a splat at the eye).  Then Y_0 alone
         // is non-zero, and il = 0 makes grad_positions and the term of dL/deye zeros
@@ -371,15 +422,6 @@ __global__ __launch_bounds__(256) void k_sh_colors_backward(float ex, float ey, 
                 Yx[15] = GSH_C3[6] * 3.0f * (xx - yy); Yy[15] = -6.0f * GSH_C3[6] * x * y; Yz[15] = 0.0f;
             }
         }
-        float r = 0.0f, g = 0.0f, b = 0.0f;
-#pragma unroll
-        for (int k = 0; k < NB; ++k) {
-            r += Y[k] * row[3 * k];
-            g += Y[k] * row[3 * k + 1];
-            b += Y[k] * row[3 * k + 2];
-        }
-        // the clamp: no gradient where the forward's max(., 0) took the 0
-        const float gr = (r + 0.5f > 0.0f) ? gc.x : 0.0f, gg = (g + 0.5f > 0.0f) ? gc.y : 0.0f, gb = (b + 0.5f > 0.0f) ? gc.z : 0.0f;
         float *orow = gsh + (size_t)i * sh_stride;
         float gx = 0.0f, gy = 0.0f, gz = 0.0f;
 #pragma unroll
