@@ -123,6 +123,9 @@ SIGNATURES = {
                                               _u32, _vp, _vp, _vp, _u32, _vp, _vp, _vp, C.c_uint64, _vp]),
     "splat_composite_contribution": (_i, [_vp, C.POINTER(CompositeCfg), _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, C.c_float, _u32,
                                           _vp, _vp, _vp]),
+    "splat_composite_features": (_i, [_vp, C.POINTER(CompositeCfg), _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _u32, _u32, _vp]),
+    "splat_composite_features_backward": (_i, [_vp, C.POINTER(CompositeCfg), _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _u32, _vp,
+                                               _u32, _vp, _vp, _vp, _u32]),
     "splat_project_ellipsoid_backward_depth": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp,
                                                     _vp]),
     "splat_project_ellipsoid_backward_camera": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp,

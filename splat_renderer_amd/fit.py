@@ -103,6 +103,35 @@ original: moments are copied, not zeroed), then resets the statistics, the impor
 frame.  It waits on the host once, for the count.  The planes are integer sums and a maximum: the same views give the same
 scores, and so the same pruned cloud, bit for bit, on every run.  densify_and_prune(), relocate() and add_new() clear the planes
 too: the rows they were accumulated for are gone.
+
+Geometry and feature terms beside the image (include/splat.h, "Feature channels of a frame"; autograd.composite_features):
+
+    rgb, alpha, feat = fit.render(cam, width, height, features=f)       # feat (H, W, K) = sum w_i f[i, k]; after depth if asked
+
+f is the caller's (n, K) CUDA float32 tensor, K <= 32, one row per splat of the fit as it is now: the fit neither owns nor
+optimises it (a learned embedding has its own optimiser, and its rows follow densify_and_prune() only if the caller moves
+them).  It is blended with the frame's own weights from the lists render() binned (no second sort), is not compensated by rho,
+and its gradients reach means, log_scales, rotations and opacity_logits through the same records and opacities as the image's.
+A deterministic fit refuses it (SplatError): the feature gradients are float atomic sums and no fixed-order variant exists.
+absgrad's statistic keeps counting the image's terms only.  The two usual regularisers, in torch ops on the fit's parameters:
+
+    # normal consistency: the shortest axis of every splat, flipped towards the eye, blended into a normal map
+    scales, _ = fit._activated()
+    q = fit.rotations / fit.rotations.norm(dim=1, keepdim=True)
+    r, x, y, z = q.unbind(1)
+    R = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y),
+                     2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x),
+                     2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)], dim=1).reshape(-1, 3, 3)
+    axis = R.gather(2, scales.argmin(dim=1).reshape(-1, 1, 1).expand(-1, 3, 1)).squeeze(2)
+    axis = torch.where(((fit.means - eye) * axis).sum(dim=1, keepdim=True) > 0, -axis, axis)
+    rgb, alpha, normal_map = fit.render(cam, width, height, features=axis)
+
+    # depth distortion: features (1, z, z^2) give W, M, Q per pixel; sum_{j<i} w_i w_j (z_i - z_j)^2 = W Q - M^2
+    z = ((fit.means - eye).norm(dim=1) - near) / (far - near)          # normalised to the scene's depth range: see below
+    rgb, alpha, wmq = fit.render(cam, width, height, features=torch.stack([torch.ones_like(z), z, z * z], dim=1))
+    distortion = (wmq[..., 0] * wmq[..., 2] - wmq[..., 1] ** 2).mean()
+
+Normalise z before squaring it: W Q - M^2 cancels in binary32 where the depth spread inside a pixel is small against the depth.
 """
 import ctypes as C
 import math
@@ -232,11 +261,14 @@ class GaussianFit:
     def parameters(self):
         return [getattr(self, k) for k in PLANES]
 
-    def render(self, camera_or_uniforms, width, height, return_depth=False):
+    def render(self, camera_or_uniforms, width, height, return_depth=False, features=None):
         """(rgb (H, W, 3), alpha (H, W)), or with return_depth (rgb, alpha, depth): autograd.render_gaussians of the activated
         parameters (with the 3D filter fused into scales and opacity when one is set, and the opacity times rho when the fit is
-        antialiased).  The frame's records are kept for the next step()."""
+        antialiased).  The frame's records are kept for the next step().  features ((n, K) or (n,), the caller's tensor: the fit
+        neither owns nor optimises it): autograd.rasterize's features, the map (H, W, K) appended to the tuple; not in a
+        deterministic fit (SplatError)."""
         torch = AG._t()
+        AG._refuse_deterministic_features(self.deterministic, features, "GaussianFit(deterministic=True).render")
         u = AG._uniforms(camera_or_uniforms, width, height)
         scales, opacity = self._activated()
         rho = None
@@ -258,8 +290,8 @@ class GaussianFit:
         self._frame = (rec, int(width), int(height))
         if self.absgrad:
             self._aux = aux
-            return AG.rasterize(rec, col, aux, width, height, depths=depths, deterministic=self.deterministic, absgrad=True)
-        return AG.rasterize(rec, col, aux, width, height, depths=depths, deterministic=self.deterministic)
+            return AG.rasterize(rec, col, aux, width, height, depths=depths, deterministic=self.deterministic, absgrad=True, features=features)
+        return AG.rasterize(rec, col, aux, width, height, depths=depths, deterministic=self.deterministic, features=features)
 
     def _activated(self):
         """(scales (n, 3), opacity (n,)) as render() draws them: exp and sigmoid (in float64, rounded once, with

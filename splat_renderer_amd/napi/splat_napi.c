@@ -454,6 +454,26 @@ FN(composite_contribution) { /* (ctx, cfg[8], colorOpacity, cStride, records, in
     void *hits = arg_dptr(&c, 13), *wmax = arg_dptr(&c, 14), *wsum = arg_dptr(&c, 15); BAIL;
     return check(env, x, splat_composite_contribution(x, &cfg, col, cs, rec, idx, cnt, off, w, h, pw, mw, n, hits, wmax, wsum), mk_undefined(env));
 }
+FN(composite_features) { /* (ctx, cfg[8], colorOpacity, cStride, records, indices, counts, offsets, W, H, features, featureStrideFloats, channels, n, out) */
+    ARGS(15); splat_ctx *x = arg_external(&c, 0); splat_composite_cfg cfg; fill_cfg(&c, 1, &cfg);
+    void *col = arg_dptr(&c, 2); uint32_t cs = (uint32_t)arg_number(&c, 3); void *rec = arg_dptr(&c, 4);
+    void *idx = arg_dptr(&c, 5), *cnt = arg_dptr(&c, 6), *off = arg_dptr(&c, 7);
+    uint32_t w = (uint32_t)arg_number(&c, 8), h = (uint32_t)arg_number(&c, 9); void *f = arg_dptr(&c, 10);
+    uint32_t fs = (uint32_t)arg_number(&c, 11), k = (uint32_t)arg_number(&c, 12), n = (uint32_t)arg_number(&c, 13);
+    void *out = arg_dptr(&c, 14); BAIL;
+    return check(env, x, splat_composite_features(x, &cfg, col, cs, rec, idx, cnt, off, w, h, f, fs, k, n, out), mk_undefined(env));
+}
+FN(composite_features_backward) { /* composite_features' arguments up to channels, then gradOut, n, gradRecords, gradColorOpacity, gradFeatures, gradFeatureStrideFloats */
+    ARGS(19); splat_ctx *x = arg_external(&c, 0); splat_composite_cfg cfg; fill_cfg(&c, 1, &cfg);
+    void *col = arg_dptr(&c, 2); uint32_t cs = (uint32_t)arg_number(&c, 3); void *rec = arg_dptr(&c, 4);
+    void *idx = arg_dptr(&c, 5), *cnt = arg_dptr(&c, 6), *off = arg_dptr(&c, 7);
+    uint32_t w = (uint32_t)arg_number(&c, 8), h = (uint32_t)arg_number(&c, 9); void *f = arg_dptr(&c, 10);
+    uint32_t fs = (uint32_t)arg_number(&c, 11), k = (uint32_t)arg_number(&c, 12); void *gout = arg_dptr(&c, 13);
+    uint32_t n = (uint32_t)arg_number(&c, 14); void *grec = arg_dptr(&c, 15), *gcol = arg_dptr(&c, 16), *gf = arg_dptr(&c, 17);
+    uint32_t gfs = (uint32_t)arg_number(&c, 18); BAIL;
+    return check(env, x, splat_composite_features_backward(x, &cfg, col, cs, rec, idx, cnt, off, w, h, f, fs, k, gout, n, grec, gcol, gf, gfs),
+                 mk_undefined(env));
+}
 FN(project_ellipsoid_backward) { /* (ctx, Float32Array(22), positions, posStride, scales, scaleStride, rotations, rotStride, n, gradRecords, gradPositions, gradScales, gradRotations) */
     ARGS(13); splat_ctx *x = arg_external(&c, 0); size_t ub = 0; float *u = arg_hostbuf(&c, 1, &ub);
     void *pos = arg_dptr(&c, 2); uint32_t ps = (uint32_t)arg_number(&c, 3); void *scl = arg_dptr(&c, 4); uint32_t ss = (uint32_t)arg_number(&c, 5);
@@ -924,6 +944,7 @@ static napi_value init(napi_env env, napi_value exports) {
         EXPORT(project_ellipsoid_aa), EXPORT(render_frame_ellipsoids_aa), EXPORT(project_ellipsoid_backward_aa), EXPORT(sampling_rate_max),
         EXPORT(composite_backward_abs), EXPORT(composite_backward_det_abs_workspace_bytes), EXPORT(composite_backward_det_abs),
         EXPORT(density_accumulate_abs),
+        EXPORT(composite_features), EXPORT(composite_features_backward),
     };
     napi_define_properties(env, exports, sizeof d / sizeof d[0], d);
     return exports;

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Gradients of ellipsoid frames (GPU box only): python tools/grad_bench.py [--depth] [--deterministic] [--antialiased] [--importance] [--absgrad] [--camera | --loss | --optimizer] [C1,C2] [K] [R]
+"""Gradients of ellipsoid frames (GPU box only): python tools/grad_bench.py [--depth] [--deterministic] [--antialiased] [--importance] [--absgrad] [--features K[,K]] [--camera | --loss | --optimizer] [C1,C2] [K] [R]
 
 tools/ellipsoid_bench.py's scenes and method (the scene's positions, sigma = radius / 2 per axis times a random factor in
 [e^-0.3, e^0.3], random rotations, SH of degree 3 with the scene's opacity; R rounds of K calls per kind, kinds alternating
@@ -39,6 +39,13 @@ into the n x 2 plane), with --depth also its depth variant (composite_backward_a
 splat_composite_backward_det_abs over its own, larger workspace (composite_backward_det_abs, and _depth with both), and the
 whole frame's backward with rasterize(..., absgrad=True) (backward_abs; with --deterministic backward_det_abs); each one's
 ratio to the entry point without the absolute sums, timed in the same rounds; the det workspaces' bytes.
+
+--features K[,K...] (3,8 is what profiles/features_bench.txt holds) adds the feature channels beside the kernels they are walks
+of, alternating in the same rounds, per K: splat_composite_features alone on K random floats per splat
+(composite_features_K) beside its one-walk peer splat_composite_contribution with all three outputs
+(composite_contribution), and splat_composite_features_backward alone with a random upstream map
+(composite_features_backward_K: two walks, 6 + K float sums per entry, float atomics) beside its two-walk peer
+splat_composite_backward (composite_backward: 9 sums); their ratios.
 
 --camera adds the camera gradients: splat_project_ellipsoid_backward_camera without and with grad_depth (all of its launches:
 the per-splat kernel with the per-wave sums, then k_camera_sum_slices above 1024 partials, then k_camera_sum) beside
@@ -130,6 +137,11 @@ def torch_camera_terms(U, pos, scl, rot, g, W, H):
     return torch.stack(terms, dim=1).sum(dim=0)
 
 
+feature_ks = []
+if "--features" in sys.argv[1:]:
+    at = sys.argv.index("--features")
+    feature_ks = [int(v) for v in sys.argv[at + 1].split(",")]
+    del sys.argv[at:at + 2]
 argv = [a for a in sys.argv[1:] if a not in ("--depth", "--camera", "--loss", "--optimizer", "--deterministic", "--antialiased", "--importance", "--absgrad")]
 abs_too = "--absgrad" in sys.argv[1:]
 aa_too = "--antialiased" in sys.argv[1:]
@@ -596,6 +608,23 @@ for name in names:
                                                                             h, ones4.data_ptr(), n, grec.data_ptr(), gcol.data_ptr()),
         })
 
+    if feature_ks:
+        hits_f, wmax_f = torch.zeros(n, dtype=torch.int32, device="cuda"), torch.zeros(n, device="cuda")
+        wsum_f = torch.zeros(n, dtype=torch.int64, device="cuda")
+        work["composite_contribution"] = lambda: lib.splat_composite_contribution(cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr(), idx, cnt,
+                                                                                  off, w, h, None, 0.0, n, hits_f.data_ptr(), wmax_f.data_ptr(),
+                                                                                  wsum_f.data_ptr())
+        feature_bufs = {}
+        for fk in feature_ks:
+            fb = dict(f=torch.rand((n, fk), device="cuda") * 4 - 2, out=torch.empty((h, w, fk), device="cuda"),
+                      g=torch.rand((h, w, fk), device="cuda") * 2 - 1, gf=torch.zeros((n, fk), device="cuda"))
+            feature_bufs[fk] = fb
+            work[f"composite_features_{fk}"] = lambda fb=fb, fk=fk: lib.splat_composite_features(
+                cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr(), idx, cnt, off, w, h, fb["f"].data_ptr(), fk, fk, n, fb["out"].data_ptr())
+            work[f"composite_features_backward_{fk}"] = lambda fb=fb, fk=fk: lib.splat_composite_features_backward(
+                cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr(), idx, cnt, off, w, h, fb["f"].data_ptr(), fk, fk, fb["g"].data_ptr(), n,
+                grec.data_ptr(), gcol.data_ptr(), fb["gf"].data_ptr(), fk)
+
     if camera_too:
         ut = torch.tensor(u, device="cuda", requires_grad=True)
         gu, ge = torch.empty(24, device="cuda"), torch.empty(4, device="cuda")
@@ -726,6 +755,11 @@ for name in names:
     if importance_too:
         _lib.check(work["composite_contribution"](), cx.ctx)
         extra.update({"composite_contribution_over_backward_ones": round(med["composite_contribution"] / med["composite_backward_ones"], 3)})
+    for fk in feature_ks:
+        for kind in (f"composite_features_{fk}", f"composite_features_backward_{fk}"):
+            _lib.check(work[kind](), cx.ctx)  # (the timed calls' return codes were not looked at)
+        extra[f"composite_features_{fk}_over_contribution"] = round(med[f"composite_features_{fk}"] / med["composite_contribution"], 3)
+        extra[f"composite_features_backward_{fk}_over_composite_backward"] = round(med[f"composite_features_backward_{fk}"] / med["composite_backward"], 3)
     if aa_too:
         extra.update({f"{a}_over_{b}": round(med[a] / med[b], 3) for a, b in (
             ("forward_aa", "forward"), ("backward_aa", "backward"), ("project_backward_aa", "project_backward"))})
