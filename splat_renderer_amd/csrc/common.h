@@ -17,7 +17,7 @@ struct StageTimer {
     size_t used = 0;
     uint32_t tick = 0; // launches of this stage seen while timing is on (splat_set_timing_sampling: every n-th carries a pair)
 };
-// k_composite_px's history for ONE band of one binner's lists (composite.hip, px_order_prepare): two arrays of per-tile costs
+// k_composite_px's history for ONE band of one binner's lists (composite_px.hip, px_order_prepare): two arrays of per-tile costs
 // and two of tile orders (cap entries each), alternating between launches.  A context keeps a few (two frames in flight on
 // one context, virtual ranks, a band next to the whole frame: each has its own), the least recently used one gives way.
 struct PxHistory {
@@ -77,7 +77,7 @@ struct splat_ctx {
 
 int ctx_fail(splat_ctx *ctx, int code, const char *what, hipError_t e = hipSuccess);
 // Whether a nearest-on-top composite of a whole screen of ntx x nty 16-pixel tiles runs k_composite_px (else k_composite):
-// splat_composite_options' choice for the context, else SPLAT_COMPOSITE's, else ntx * nty >= 2048 (composite.hip).  The
+// splat_composite_options' choice for the context, else SPLAT_COMPOSITE's, else ntx * nty >= 2048 (composite_px.hip).  The
 // composite backward asks the same rule, to replay the transmittance updates of the kernel that drew the frame.
 bool composite_uses_px(const splat_ctx *ctx, uint32_t ntx, uint32_t nty);
 

@@ -1,6 +1,8 @@
-// composite.h — what the two composite translation units share: the launch parameters, the per-entry fetch, the exact
-// coverage masks and the stop rule.  composite.hip holds the 16x16-tile kernels (k_composite, k_composite_px) and the
-// dispatch; composite_tile.hip holds k_composite_tile, the composite for every other tile size.
+// composite.h — what the composite translation units share: the launch parameters, the per-entry fetch, the exact
+// coverage masks and the stop rule.  composite.hip holds the entry points, the argument checks and the choice of kernel,
+// with k_composite (16x16 tiles, a wave per 8x8 quadrant); composite_px.hip holds k_composite_px (16x16 tiles, a lane per
+// 2x2 pixels) and its per-band history; composite_tile.hip holds k_composite_tile, the composite for every other tile size.
+// k_composite and k_composite_tile are one body: composite_quadrant.h.
 #pragma once
 #include "common.h"
 #include "disc.h"
@@ -178,7 +180,15 @@ constexpr bool composite_variant_exists(int mode, bool disc, bool lit32, bool ao
     return (mode == SPLAT_COMPOSITE_FRONT_TO_BACK || !(aov || disc)) && !(disc && lit32) && (disc || !ell);
 }
 
-// composite_tile.hip: the composite for tile sizes other than CT (p is filled in by composite_launch; rows [r0, r1) of the
-// ntx x nty tiles of cfg->tile_size pixels).  *launched: whether the launch that carries the frame's report went out.
-int composite_tile_launch(splat_ctx *ctx, const splat_composite_cfg *cfg, const CompositeParams &p, uint32_t nty, uint32_t r0,
-                          uint32_t r1, bool *launched);
+// Which instantiations of k_composite_px <EARLY_OUT, LIT32, COUNT, AH, DISC, AOV, ELL> exist (EARLY_OUT, COUNT, AH, AOV: all):
+// nearest on top is its only blend; a disc record's lit colour is found at run time (p.disc_lit), not by LIT32; the
+// ellipsoid's records are disc records.
+constexpr bool composite_px_variant_exists(bool disc, bool lit32, bool ell) { return !(disc && lit32) && (disc || !ell); }
+
+// The two launchers composite_launch chooses between before k_composite: p is filled in by composite_launch, `band` is the
+// screen's tiles of cfg->tile_size pixels and the rows of them to render.  *launched: whether the launch that carries the
+// frame's report went out.
+// composite_tile.hip: tile sizes other than CT.
+int composite_tile_launch(splat_ctx *ctx, const splat_composite_cfg *cfg, const CompositeParams &p, const TileBand &band, bool *launched);
+// composite_px.hip: 16x16 tiles, nearest on top, where composite_uses_px says so (the launcher sets p's hints from the band's history).
+int composite_px_launch(splat_ctx *ctx, const splat_composite_cfg *cfg, CompositeParams &p, const TileBand &band, bool *launched);

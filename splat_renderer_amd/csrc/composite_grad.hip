@@ -1,8 +1,9 @@
 // composite_grad.hip — the per-tile kernels behind the gradients of a frame of anisotropic 3D Gaussians
 // (SPLAT_FOOTPRINT_ELLIPSOID; an extension, no reference counterpart): the composite's backward and the contribution scores.
 // Both recompute each pixel's forward in binary32 in the operation order of the kernel that drew the frame
-// (composite_uses_px; this file is compiled with contraction on, as composite.hip is).  The per-splat kernels that take the
-// record and colour gradients on to the parameters are splat_grad.hip.
+// (composite_uses_px: k_composite's, composite_quadrant.h, or k_composite_px's, composite_px.hip; this file is compiled with
+// contraction on, as they are).  The per-splat kernels that take the record and colour gradients on to the parameters are
+// splat_grad.hip.
 //
 // Shared by the two tile kernels, and with composite_features.hip's (composite_walk.h): the pixel mapping
 // (TILE_PIXEL_PROLOGUE), the staged list (stage_chunk), an entry's alpha at a pixel (entry_alpha), the transmittance update

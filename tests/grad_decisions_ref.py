@@ -3,8 +3,8 @@ last entry leaves T within a few ulps of T_STOP (include/splat.h: a pixel stops 
 T <= T_STOP).
 
 For an entry with footprint value g (the hardware exp2's binary32 result) and opacity o the two kernels compute
-  k_composite     a = rn(g o);  w = rn(T a);  T' = rn(T - w)          (csrc/composite.hip: g *= opacity; T -= T * g)
-  k_composite_px  w = rn(T g);  T' = rn(T - o w)  (one fused rounding) (T = fma(-opacity, T * g, T))
+  k_composite     a = rn(g o);  w = rn(T a);  T' = rn(T - w)          (csrc/composite_quadrant.h: g *= opacity; T -= T * g)
+  k_composite_px  w = rn(T g);  T' = rn(T - o w)  (one fused rounding) (csrc/composite_px.hip: T = fma(-opacity, T * g, T))
 where rn is binary32 round-to-nearest-even.  Both are restated here in exact rational arithmetic (fractions), so a stack found
 by search() is known to straddle T_STOP under one order and not the other without trusting any floating-point library.
 

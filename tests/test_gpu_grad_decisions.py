@@ -25,7 +25,7 @@ from tests import test_gpu_ellipsoid_grad as TG
 
 pytestmark = pytest.mark.gpu
 
-PX_MIN_TILES = 2048  # csrc/composite.hip: the default forward is k_composite_px on screens of at least this many tiles
+PX_MIN_TILES = 2048  # csrc/composite_px.hip: the default forward is k_composite_px on screens of at least this many tiles
 # routes: (name, kernel for splat_composite_options, screen); the last two are the default selection on both sides of 2048 tiles
 ROUTES = [("quadrant", 0, (640, 360)), ("px", 1, (640, 360)), ("default-small", -1, (640, 360)), ("default-large", -1, (1024, 768))]
 GEOMS = DR.GEOMS
@@ -34,7 +34,7 @@ UP = np.array([1.0, -1.0, 0.5, 0.25], np.float32)  # the upstream at a target (r
 
 
 def route_order(kernel, w, h):
-    """Which update order draws the frame: the forward's rule (composite.hip's composite_uses_px): the context's choice, else
+    """Which update order draws the frame: the forward's rule (composite_px.hip's composite_uses_px): the context's choice, else
     the SPLAT_COMPOSITE switch (pixel | quadrant), else the screen size."""
     if kernel == -1:
         forced = os.environ.get("SPLAT_COMPOSITE", "")[:1].lower()

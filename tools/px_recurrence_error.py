@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Accuracy of k_composite_px's table recurrence (composite.hip, builder wave) in binary32, on the CPU: along one axis the
+"""Accuracy of k_composite_px's table recurrence (composite_px.hip, builder wave) in binary32, on the CPU: along one axis the
 Gaussian at pixel pairs p0, p0 + 1, ... is G(u + 2k) = G(u) R(u), R(u + 2k) = R(u) D, seeded at the first covered pair with five
 exponentials.  Compared with float64 over random entries (radius 0.5 .. 40 px, centre anywhere a box can reach the tile from),
 next to the direct form it replaced (exp2(-(x k - c k)^2) per pixel).  numpy's exp2 stands in for v_exp_f32 (both ~1 ulp).

@@ -3,7 +3,8 @@
 
 One JSON line per tile size: device ms per frame (K frames, no events), the per-stage times of 10 frames with every stage's
 event pair on (setTiming), the pair total, and the composite's staged / consumed list entries per frame.  Tile size 16 runs
-k_composite_px (or k_composite on small screens); every other size runs k_composite_tile (composite_tile.hip)."""
+k_composite_px (composite_px.hip; or k_composite, composite.hip, on small screens); every other size runs k_composite_tile
+(composite_tile.hip)."""
 import ctypes as C
 import json
 import os
