@@ -18,6 +18,7 @@
 #include "common.h"
 #include <cstring>
 #include "tile_range.h"
+#include "block_scan.h"
 
 #include <chrono>
 #include <cstdio>
@@ -28,19 +29,6 @@ constexpr uint32_t BIN_THREADS = 256;
 constexpr uint32_t BIN_PER_THREAD = 4;
 constexpr uint32_t BIN_BLOCK = BIN_THREADS * BIN_PER_THREAD; // sorted positions per workgroup
 constexpr uint32_t BIN_STAGE_PAIRS = 4096;                   // pairs staged in LDS for coalesced stores (32 KB)
-
-__device__ __forceinline__ uint32_t range_hits(uint2 r) {
-    const uint32_t tx0 = r.x & 0xffffu, tx1 = r.x >> 16, ty0 = r.y & 0xffffu, ty1 = r.y >> 16;
-    return (tx0 > tx1 || ty0 > ty1) ? 0u : (tx1 - tx0 + 1) * (ty1 - ty0 + 1);
-}
-
-__device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t *wsum) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
 
 // count: every sorted position gets its clamped tile range (gathered per splat: 16 B of bounds, or
 // the 4 B range32 the projector wrote on the frame path) and every 1024-position block its pair count.
@@ -67,8 +55,8 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin_count(const float4 *__restr
             uint32_t tx0 = 1, tx1 = 0, ty0 = 1, ty1 = 0;
             if (s < n_splats) { // 0xFFFFFFFF padding bins nowhere
                 if (FROM_RANGE32) {
-                    const uint32_t r = range32[s];
-                    tx0 = r & 0xffu; tx1 = (r >> 8) & 0xffu; ty0 = (r >> 16) & 0xffu; ty1 = r >> 24;
+                    const TileRect t = unpack_range32(range32[s]);
+                    tx0 = t.tx0; tx1 = t.tx1; ty0 = t.ty0; ty1 = t.ty1;
                 } else {
                     const float4 b = projected[(size_t)s * 2];
                     if (!tile_range(b, bp.width, bp.height, bp.tile, bp.ntx, bp.nty, bp.row0, bp.row1, tx0, tx1, ty0, ty1)) {
@@ -124,7 +112,7 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin_expand(const uint32_t *__re
                                                             uint32_t *__restrict__ pair_tile, uint32_t *__restrict__ pair_splat) {
     __shared__ uint32_t wsum[4];
     __shared__ uint2 stage[BIN_STAGE_PAIRS];
-    const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const uint32_t tid = threadIdx.x;
     uint2 r[BIN_PER_THREAD];
     uint32_t s[BIN_PER_THREAD], h[BIN_PER_THREAD];
 #pragma unroll
@@ -143,18 +131,9 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin_expand(const uint32_t *__re
     uint32_t carry = 0;
 #pragma unroll
     for (uint32_t k = 0; k < BIN_PER_THREAD; ++k) {
-        uint32_t incl = h[k];
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t t = __shfl_up(incl, d);
-            if ((int)lane >= d) incl += t;
-        }
-        if (lane == 63) wsum[w] = incl;
-        __syncthreads();
-        const uint32_t s0 = wsum[0], s1 = wsum[1], s2 = wsum[2], s3 = wsum[3];
-        __syncthreads();
-        off[k] = carry + (w > 0 ? s0 : 0u) + (w > 1 ? s1 : 0u) + (w > 2 ? s2 : 0u) + incl - h[k];
-        carry += s0 + s1 + s2 + s3;
+        uint32_t row;
+        off[k] = carry + block_exclusive_scan<true>(h[k], wsum, &row); // (second barrier: the next k rewrites wsum)
+        carry += row;
     }
     const uint32_t total = carry, base = block_base[blockIdx.x];
     if (total == 0) return;

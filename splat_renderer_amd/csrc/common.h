@@ -373,6 +373,7 @@ struct TfSecondPassArgs {
 };
 int tf_second_pass_launch(splat_ctx *ctx, const TfSecondPassArgs &a);
 int radix_rowscan_launch(splat_ctx *ctx, uint32_t *hist, uint32_t parts, uint32_t rows); // rows -> exclusive prefixes, totals at hist + 256*parts
+// tile_sort.hip (the per-tile depth sort that ends the tile-first order)
 struct TileSortArgs {
     const uint32_t *offsets = nullptr;
     uint32_t tiles = 0;

@@ -247,3 +247,22 @@ int composite_launch(splat_ctx *ctx, const splat_composite_cfg *cfg, const Compo
     LAUNCH_CHECK(ctx, "k_composite");
     return SPLAT_OK;
 }
+
+extern "C" int splat_composite_forget_history(splat_ctx *ctx) {
+    if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
+    for (auto &h : ctx->px_hist) { // (the arrays stay: a slot's next launch starts a new streak in them)
+        h.key = 0;
+        h.streak = 0;
+        h.last_use = 0;
+    }
+    return SPLAT_OK;
+}
+
+extern "C" int splat_composite_options(splat_ctx *ctx, int kernel, int ahead, int predict) {
+    if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
+    ARG_CHECK(ctx, kernel >= -1 && kernel <= 1 && ahead >= 0 && ahead <= 2 && predict >= -1 && predict <= 1);
+    ctx->opt_composite_kernel = kernel;
+    ctx->opt_px_ahead = ahead;
+    ctx->opt_px_predict = predict;
+    return splat_composite_forget_history(ctx); // (another schedule: its costs mean something else)
+}

@@ -916,3 +916,11 @@ int composite_px_launch(splat_ctx *ctx, const splat_composite_cfg *cfg, Composit
     LAUNCH_CHECK(ctx, "k_composite_px");
     return SPLAT_OK;
 }
+
+#ifdef SPLAT_TEST_HOOKS // (the test build only: include/splat.h)
+extern "C" int splat_debug_set_tile_order(splat_ctx *ctx, const void *order_dptr) {
+    if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
+    ctx->debug_tile_order = (const uint32_t *)order_dptr;
+    return SPLAT_OK;
+}
+#endif

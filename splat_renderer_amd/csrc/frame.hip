@@ -7,6 +7,7 @@
 // compaction so that ties in depth still resolve by ascending global index.
 #include "common.h"
 #include "tile_range.h"
+#include "block_scan.h"
 #include "disc.h"
 #include "ellipsoid.h"
 #include "shade.h"
@@ -64,11 +65,8 @@ __global__ __launch_bounds__(BAND_THREADS) void k_band_prepare(const float4 *__r
             kept += ok ? 1u : 0u;
         }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) kept += __shfl_xor(kept, d);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = kept;
-    __syncthreads();
-    if (threadIdx.x == 0) blocksums[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    const uint32_t total = block_sum(kept, wsum);
+    if (threadIdx.x == 0) blocksums[blockIdx.x] = total;
 }
 
 // The same pass on a screen beyond 256 x 256 tiles (sort-first, the only order there): the 8-byte wide range per record.
@@ -101,11 +99,8 @@ __global__ __launch_bounds__(BAND_THREADS) void k_band_prepare_wide(const float4
             kept += ok ? 1u : 0u;
         }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) kept += __shfl_xor(kept, d);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = kept;
-    __syncthreads();
-    if (threadIdx.x == 0) blocksums[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    const uint32_t total = block_sum(kept, wsum);
+    if (threadIdx.x == 0) blocksums[blockIdx.x] = total;
 }
 
 // Tile-first band frame: the same pass, 1024 records per block (the binner's block), which also counts
@@ -154,21 +149,18 @@ __global__ __launch_bounds__(BAND_THREADS) void k_band_prepare_tf(const float4 *
             keys_by_idx[i] = depth_key_of(depth);
             if (ok) {
                 kept += 1u;
-                pairs += hist_add_rect(lh[w], tx0, tx1, ty0, ty1, bp.ntx, ho.mask);
+                pairs += hist_add_rect(lh[w], {tx0, tx1, ty0, ty1}, bp.ntx, ho.mask);
             }
         }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        kept += __shfl_xor(kept, d);
-        pairs += __shfl_xor(pairs, d);
-    }
+    kept = wave_sum(kept);
+    pairs = wave_sum(pairs);
     if ((tid & 63) == 0) {
         wsum[0][w] = kept;
         wsum[1][w] = pairs;
     }
     __syncthreads();
-    if (tid <= ho.mask) ho.hist[(size_t)tid * ho.num_parts + blockIdx.x] = lh[0][tid] + lh[1][tid] + lh[2][tid] + lh[3][tid];
+    hist_flush<4>(lh, ho.hist, ho.num_parts, blockIdx.x, ho.mask);
     if (tid == 0) {
         kept_blocks[blockIdx.x] = wsum[0][0] + wsum[0][1] + wsum[0][2] + wsum[0][3];
         ho.blocksums[blockIdx.x] = wsum[1][0] + wsum[1][1] + wsum[1][2] + wsum[1][3];
@@ -257,13 +249,7 @@ __global__ __launch_bounds__(BTC_THREADS) __attribute__((amdgpu_waves_per_eu(FOR
     __syncthreads();
     // where each (row, wave) cell's kept splats go: an exclusive scan of the 64 counts in (row, wave) order = ascending index
     if (w == 0) {
-        const uint32_t mine = rowcnt[lane];
-        uint32_t incl = mine;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t x = __shfl_up(incl, d);
-            if ((int)lane >= d) incl += x;
-        }
+        const uint32_t mine = rowcnt[lane], incl = wave_inclusive_scan(mine);
         rowcnt[lane] = incl - mine;
         if (lane == 63) {
             kept_groups[blk] = incl;
@@ -288,20 +274,11 @@ __global__ __launch_bounds__(BTC_THREADS) __attribute__((amdgpu_waves_per_eu(FOR
     // where they stood, every wave ran the rectangle loops eight times over for its few kept lanes)
     const uint32_t kept = s_kept;
     uint32_t pairs = 0;
-    for (uint32_t j = tid; j < kept; j += BTC_THREADS) {
-        const uint32_t r = s_rng[j];
-        pairs += hist_add_rect(lh[w], r & 0xffu, (r >> 8) & 0xffu, (r >> 16) & 0xffu, r >> 24, bp.ntx, ho.mask);
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) pairs += __shfl_xor(pairs, d);
+    for (uint32_t j = tid; j < kept; j += BTC_THREADS) pairs += hist_add_rect(lh[w], unpack_range32(s_rng[j]), bp.ntx, ho.mask);
+    pairs = wave_sum(pairs);
     if (lane == 0) wsum[w] = pairs;
     __syncthreads();
-    if (tid <= ho.mask) {
-        uint32_t hs = 0;
-#pragma unroll
-        for (uint32_t v = 0; v < BTC_WAVES; ++v) hs += lh[v][tid];
-        ho.hist[(size_t)tid * ho.num_parts + blk] = hs;
-    }
+    hist_flush<BTC_WAVES>(lh, ho.hist, ho.num_parts, blk, ho.mask);
     if (tid == 0) {
         uint32_t ps = 0;
 #pragma unroll

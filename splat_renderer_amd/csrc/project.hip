@@ -12,6 +12,7 @@
 #include "common.h"
 #include "variant.h"
 #include "tile_range.h"
+#include "block_scan.h"
 #include "disc.h"
 #include "ellipsoid.h"
 #include "shade.h"
@@ -309,16 +310,15 @@ __global__ __launch_bounds__(256) void k_project_hist(FrameUniforms u, const flo
             continue;
         }
         const uint32_t r = project_one<true, true, DISC, LIT, false, ELL>(u, in[k], i, 0, projected, keys, nullptr, range32, bp, dio, lio);
-        const uint32_t tx0 = r & 0xffu, tx1 = (r >> 8) & 0xffu, ty0 = (r >> 16) & 0xffu, ty1 = r >> 24;
-        if (tx0 > tx1 || ty0 > ty1) continue;
-        local += hist_add_rect(lh[w], tx0, tx1, ty0, ty1, bp.ntx, ho.mask);
+        const TileRect t = unpack_range32(r);
+        if (t.empty()) continue;
+        local += hist_add_rect(lh[w], t, bp.ntx, ho.mask);
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) local += __shfl_xor(local, d);
+    local = wave_sum(local);
     if ((tid & 63) == 0) wsum[w] = local;
     __syncthreads();
     if (blk < ho.num_parts) { // (blocks that only pad keys past n have no histogram column)
-        if (tid <= ho.mask) ho.hist[(size_t)tid * ho.num_parts + blk] = lh[0][tid] + lh[1][tid] + lh[2][tid] + lh[3][tid];
+        hist_flush<4>(lh, ho.hist, ho.num_parts, blk, ho.mask);
         if (tid == 0) ho.blocksums[blk] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
     }
 }
@@ -374,16 +374,15 @@ __global__ __launch_bounds__(256) void k_project_hist_band(FrameUniforms u, cons
         const uint32_t i = s_list[j];
         const SplatIn in = load_splat<DISC, LIT>(pos_radius, stride_vec4, i, dio, lio);
         const uint32_t r = project_one<true, true, DISC, LIT>(u, in, i, 0, projected, keys, nullptr, range32, bp, dio, lio);
-        const uint32_t tx0 = r & 0xffu, tx1 = (r >> 8) & 0xffu, ty0 = (r >> 16) & 0xffu, ty1 = r >> 24;
-        if (tx0 > tx1 || ty0 > ty1) continue;
-        local += hist_add_rect(lh[w], tx0, tx1, ty0, ty1, bp.ntx, ho.mask);
+        const TileRect t = unpack_range32(r);
+        if (t.empty()) continue;
+        local += hist_add_rect(lh[w], t, bp.ntx, ho.mask);
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) local += __shfl_xor(local, d);
+    local = wave_sum(local);
     if (lane == 0) wsum[w] = local;
     __syncthreads();
     if (blockIdx.x < ho.num_parts) {
-        if (tid <= ho.mask) ho.hist[(size_t)tid * ho.num_parts + blockIdx.x] = lh[0][tid] + lh[1][tid] + lh[2][tid] + lh[3][tid];
+        hist_flush<4>(lh, ho.hist, ho.num_parts, blockIdx.x, ho.mask);
         if (tid == 0) ho.blocksums[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
     }
 }
@@ -444,13 +443,7 @@ __global__ __launch_bounds__(PBC_THREADS) void k_project_hist_bandc(FrameUniform
     }
     __syncthreads();
     if (w == 0) { // the cells in (row, wave) order = ascending splat index
-        const uint32_t mine = rowcnt[lane];
-        uint32_t incl = mine;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t x = __shfl_up(incl, d);
-            if ((int)lane >= d) incl += x;
-        }
+        const uint32_t mine = rowcnt[lane], incl = wave_inclusive_scan(mine);
         rowcnt[lane] = incl - mine;
         if (lane == 63) {
             ho.kept_groups[blk] = incl;
@@ -473,20 +466,14 @@ __global__ __launch_bounds__(PBC_THREADS) void k_project_hist_bandc(FrameUniform
         // (the record goes to the splat's own index — the composite gathers it by that —, key and range to the compacted slot)
         const uint32_t r = project_one<true, true, DISC, LIT>(u, in, i, 0, projected, keys_c, nullptr, range_c, bp, dio, lio, g0 + j);
         ho.cidx[g0 + j] = i;
-        const uint32_t tx0 = r & 0xffu, tx1 = (r >> 8) & 0xffu, ty0 = (r >> 16) & 0xffu, ty1 = r >> 24;
-        if (tx0 > tx1 || ty0 > ty1) continue; // (passed the conservative test, reaches no tile of the band: an empty range in the list)
-        local += hist_add_rect(lh[w], tx0, tx1, ty0, ty1, bp.ntx, ho.mask);
+        const TileRect t = unpack_range32(r);
+        if (t.empty()) continue; // (passed the conservative test, reaches no tile of the band: an empty range in the list)
+        local += hist_add_rect(lh[w], t, bp.ntx, ho.mask);
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) local += __shfl_xor(local, d);
+    local = wave_sum(local);
     if (lane == 0) wsum[w] = local;
     __syncthreads();
-    if (tid <= ho.mask) {
-        uint32_t hs = 0;
-#pragma unroll
-        for (uint32_t v = 0; v < PBC_WAVES; ++v) hs += lh[v][tid];
-        ho.hist[(size_t)tid * ho.num_parts + blk] = hs;
-    }
+    hist_flush<PBC_WAVES>(lh, ho.hist, ho.num_parts, blk, ho.mask);
     if (tid == 0) {
         uint32_t ps = 0;
 #pragma unroll

@@ -24,6 +24,8 @@
 // Roofline: HBM.  Algorithmic bytes per key per pass: 4 (upsweep read) + 8 (read key+payload)
 // + 8 (write) = 20; 80 B/key for the 4-pass depth sort.
 #include "common.h"
+#include "block_scan.h"
+#include "variant.h"
 
 #include <cstdlib>
 
@@ -115,8 +117,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_radix_upsweep(const uint32_t *__
             atomicAdd(&lh[w][(keys[IN_PAIRS ? (size_t)i * 2 : (size_t)i] >> shift) & mask], 1u);
     }
     __syncthreads();
-    // (rows above the mask are never read: a 4-byte store per row is a 64-byte line at the memory side)
-    if (tid <= mask) hist[(size_t)tid * num_parts + part] = lh[0][tid] + lh[1][tid] + lh[2][tid] + lh[3][tid];
+    hist_flush<RS_WAVES>(lh, hist, num_parts, part, mask);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -126,12 +127,7 @@ constexpr uint32_t ROWSCAN_THREADS = 1024;
 // (rows: digits that can occur this pass, mask + 1; the rows above hold zeros already and only need a zero total)
 // one round of the row scan: ROWSCAN_THREADS values (one per thread) -> their exclusive prefixes (+ carry), and the carry
 __device__ __forceinline__ uint32_t rowscan_round(uint32_t v, uint32_t *wsum, unsigned long long &carry, uint32_t lane, uint32_t w) {
-    uint32_t incl = v;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        uint32_t t = __shfl_up(incl, s);
-        if ((int)lane >= s) incl += t;
-    }
+    const uint32_t incl = wave_inclusive_scan(v);
     if (lane == 63) wsum[w] = incl;
     __syncthreads();
     // every wave scans the 16 wave totals itself (lanes 0..15)
@@ -184,11 +180,6 @@ __global__ __launch_bounds__(ROWSCAN_THREADS) void k_radix_rowscan(uint32_t *__r
 // ---------------------------------------------------------------------------------------------
 // downsweep
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t lanemask_lt() {
-    const uint32_t lane = threadIdx.x & 63;
-    return (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-}
-
 struct DownsweepShared {
     uint32_t wave_hist[RS_WAVES][256]; // running per-wave digit counters -> wave offsets
     uint32_t global_base[256];         // (global start of this partition's run of each digit) - (its partition-local start)
@@ -250,7 +241,7 @@ __device__ __forceinline__ void downsweep_body(DownsweepShared &sh, uint2 *__res
     bool use_atomic = RANK_ATOMIC;
     if (RANK_ATOMIC) {
         const uint32_t next = tid > mask ? 0u : (part + 1 < num_parts) ? scanned_hist[(size_t)tid * num_parts + part + 1] : digit_total;
-        use_atomic = !__syncthreads_or((next - row_prefix) > PART_KEYS / 4); // some digit holds > 25 % of the partition
+        use_atomic = ranks_with_atomics(next, row_prefix, PART_KEYS);
     } else {
         __syncthreads(); // wave_hist zeroed
     }
@@ -271,19 +262,11 @@ __device__ __forceinline__ void downsweep_body(DownsweepShared &sh, uint2 *__res
         for (uint32_t i = 0; i < ITEMS; ++i) {
             uint32_t d = (key[i] >> shift) & mask;
             if (!FULL) d = (wbase + i * 64 < valid) ? d : 255u;
-            uint32_t plo = ~0u, phi = ~0u;
-#pragma unroll
-            for (uint32_t b = 0; b < 8; ++b) {
-                const uint32_t m = (uint32_t)(((int32_t)(d << (31 - b))) >> 31); // all ones if bit b of d is set
-                const uint64_t bal = __ballot(m != 0);
-                plo = __builtin_amdgcn_bitop3_b32(plo, (uint32_t)bal, m, 0x90);        // plo & ~(bal ^ m)
-                phi = __builtin_amdgcn_bitop3_b32(phi, (uint32_t)(bal >> 32), m, 0x90);
-            }
-            const uint32_t below = __builtin_amdgcn_mbcnt_hi(phi, __builtin_amdgcn_mbcnt_lo(plo, 0)); // same-digit lanes below me
-            const uint32_t leader = plo ? (uint32_t)__builtin_ctz(plo) : 32u + (uint32_t)__builtin_ctz(phi);
-            rank[i] = below | (leader << 8);
+            const LanePeers p = match_same_digit(d);
+            const uint32_t below = p.below();
+            rank[i] = below | (p.leader() << 8);
             prev[i] = 0;
-            if (below == 0) prev[i] = atomicAdd(&sh.wave_hist[w][d], (uint32_t)(__popc(plo) + __popc(phi)));
+            if (below == 0) prev[i] = atomicAdd(&sh.wave_hist[w][d], p.count());
         }
         // ---- phase B: every lane fetches its leader's result ---------------------------------------
 #pragma unroll
@@ -291,35 +274,24 @@ __device__ __forceinline__ void downsweep_body(DownsweepShared &sh, uint2 *__res
     }
     __syncthreads();
 
-    // thread d: exclusive prefix over waves for digit d, and the partition's count of d
-    uint32_t c0 = sh.wave_hist[0][tid], c1 = sh.wave_hist[1][tid], c2 = sh.wave_hist[2][tid], c3 = sh.wave_hist[3][tid];
-    uint32_t dcount = c0 + c1 + c2 + c3;
-    // exclusive scan of dcount over the 256 digits and, in the same shuffles, of the global digit
-    // totals (start of digit d in the output)
-    uint32_t incl = dcount, gincl = digit_total;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        uint32_t t = __shfl_up(incl, s), g = __shfl_up(gincl, s);
-        if ((int)lane >= s) {
-            incl += t;
-            gincl += g;
-        }
-    }
+    // thread d: the partition's count of digit d per wave; the exclusive scan of the counts over the 256 digits (local starts)
+    // and, in the same shuffles, of the global digit totals (start of digit d in the output)
+    const uint32_t c0 = sh.wave_hist[0][tid], c1 = sh.wave_hist[1][tid], c2 = sh.wave_hist[2][tid], c3 = sh.wave_hist[3][tid];
+    const uint32_t dcount = c0 + c1 + c2 + c3;
+    const auto [incl, gincl] = wave_inclusive_scan(dcount, digit_total);
     if (lane == 63) {
         sh.wave_sums[w] = incl;
         sh.wave_gsums[w] = gincl;
     }
     __syncthreads();
-    uint32_t wprefix = (w > 0 ? sh.wave_sums[0] : 0u) + (w > 1 ? sh.wave_sums[1] : 0u) + (w > 2 ? sh.wave_sums[2] : 0u);
-    uint32_t gprefix = (w > 0 ? sh.wave_gsums[0] : 0u) + (w > 1 ? sh.wave_gsums[1] : 0u) + (w > 2 ? sh.wave_gsums[2] : 0u);
     // one table lookup per element in each of the two loops below instead of two: the wave prefixes
     // absorb the digit's local start, and global_base holds (global start - local start)
-    const uint32_t local_start = wprefix + incl - dcount;
+    const uint32_t local_start = waves_before(sh.wave_sums, w) + incl - dcount;
     sh.wave_hist[0][tid] = local_start;
     sh.wave_hist[1][tid] = local_start + c0;
     sh.wave_hist[2][tid] = local_start + c0 + c1;
     sh.wave_hist[3][tid] = local_start + c0 + c1 + c2;
-    sh.global_base[tid] = gprefix + gincl - digit_total + row_prefix - local_start;
+    sh.global_base[tid] = waves_before(sh.wave_gsums, w) + gincl - digit_total + row_prefix - local_start;
     __syncthreads();
 
     // reorder inside the partition: same-digit keys become contiguous, stable
@@ -405,12 +377,10 @@ static int radix_sort_rowscan(splat_ctx *ctx, uint32_t *k0, uint32_t *p0, uint32
         const uint32_t bits = bit_end - shift < want ? bit_end - shift : want;
         const uint32_t mask = (1u << bits) - 1u;
         const bool in_pairs = can_pair && pass > 0, out_pairs = can_pair && pass + 1 < npasses;
-        if (in_pairs)
-            hipLaunchKernelGGL(k_radix_upsweep<true>, dim3(grid_parts), dim3(RS_THREADS), 0, ctx->stream, ki, n, n_dev, shift, mask, parts,
-                               RS_PART_KEYS, hist, xcd_per);
-        else
-            hipLaunchKernelGGL(k_radix_upsweep<false>, dim3(grid_parts), dim3(RS_THREADS), 0, ctx->stream, ki, n, n_dev, shift, mask, parts,
-                               RS_PART_KEYS, hist, xcd_per);
+        variant_dispatch([&](auto ip) {
+            launch_kernel(ctx, NO_STAGE, k_radix_upsweep<ip.value>, dim3(grid_parts), dim3(RS_THREADS), ki, n, n_dev, shift, mask, parts, RS_PART_KEYS,
+                          hist, xcd_per);
+        }, in_pairs);
         LAUNCH_CHECK(ctx, "k_radix_upsweep");
         uint32_t *totals = hist + (size_t)256 * parts;
         hipLaunchKernelGGL(k_radix_rowscan, dim3(256), dim3(ROWSCAN_THREADS), 0, ctx->stream, hist, parts, totals, mask + 1);
@@ -418,21 +388,10 @@ static int radix_sort_rowscan(splat_ctx *ctx, uint32_t *k0, uint32_t *p0, uint32
         // iota_payload: the input payload is 0,1,2,... (fresh from the projector): the first pass
         // synthesises it instead of reading 4 B per key that the projector would have had to write
         const uint32_t *pin = (iota_payload && pass == 0) ? nullptr : pi;
-#define SPLAT_DS(RA, IP, OP)                                                                                                   \
-    hipLaunchKernelGGL((k_radix_downsweep<RS_ITEMS, RA, IP, OP>), dim3(grid_parts), dim3(RS_THREADS), 0, ctx->stream, ki, pin, ko, po, n, \
-                       n_dev, shift, mask, parts, hist, totals, xcd_per)
-        if (rank_atomic) {
-            if (in_pairs && out_pairs) SPLAT_DS(true, true, true);
-            else if (in_pairs) SPLAT_DS(true, true, false);
-            else if (out_pairs) SPLAT_DS(true, false, true);
-            else SPLAT_DS(true, false, false);
-        } else {
-            if (in_pairs && out_pairs) SPLAT_DS(false, true, true);
-            else if (in_pairs) SPLAT_DS(false, true, false);
-            else if (out_pairs) SPLAT_DS(false, false, true);
-            else SPLAT_DS(false, false, false);
-        }
-#undef SPLAT_DS
+        variant_dispatch([&](auto ra, auto ip, auto op) {
+            launch_kernel(ctx, NO_STAGE, k_radix_downsweep<RS_ITEMS, ra.value, ip.value, op.value>, dim3(grid_parts), dim3(RS_THREADS), ki, pin, ko,
+                          po, n, n_dev, shift, mask, parts, hist, totals, xcd_per);
+        }, rank_atomic, in_pairs, out_pairs);
         LAUNCH_CHECK(ctx, "k_radix_downsweep");
         uint32_t *t = ki; ki = ko; ko = t;
         t = pi; pi = po; po = t;
@@ -475,26 +434,16 @@ __global__ __launch_bounds__(256) void k_probe_lds_atomic_order(uint32_t rounds,
             if (((r >> 3) & 3) == 2) d = (lane * 7u) % k;                          // strided
             d = (d * 37u) & 255u;                                                  // spread over banks
             // reference: the set of lanes with the same address, by ballots
-            uint32_t plo = ~0u, phi = ~0u;
-#pragma unroll
-            for (uint32_t b = 0; b < 8; ++b) {
-                const uint32_t m = (uint32_t)(((int32_t)(d << (31 - b))) >> 31);
-                const uint64_t bal = __ballot(m != 0);
-                plo = __builtin_amdgcn_bitop3_b32(plo, (uint32_t)bal, m, 0x90);
-                phi = __builtin_amdgcn_bitop3_b32(phi, (uint32_t)(bal >> 32), m, 0x90);
-            }
-            const uint32_t below = __builtin_amdgcn_mbcnt_hi(phi, __builtin_amdgcn_mbcnt_lo(plo, 0));
+            const LanePeers p = match_same_digit(d);
             const uint32_t got = atomicAdd(&cnt[w][d], 1u);
             // in lane order every lane of a same-address group reads (count before the instruction)
             // + (same-address lanes below it): got - below must equal the group leader's value
-            const uint32_t base_cnt = got - below;
-            const uint32_t leader = plo ? (uint32_t)__builtin_ctz(plo) : 32u + (uint32_t)__builtin_ctz(phi);
-            if (base_cnt != (uint32_t)__shfl((int)base_cnt, (int)leader)) ++bad;
+            const uint32_t base_cnt = got - p.below();
+            if (base_cnt != (uint32_t)__shfl((int)base_cnt, (int)p.leader())) ++bad;
         }
         __builtin_amdgcn_wave_barrier();
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) bad += __shfl_xor(bad, d);
+    bad = wave_sum(bad);
     if (lane == 0 && bad) atomicAdd(mismatches, bad);
 }
 
@@ -536,9 +485,11 @@ int radix_probe_lds_rate(splat_ctx *ctx, int kind, uint32_t wgs_per_cu, uint32_t
     const dim3 grid(256u * wgs_per_cu);
     for (int rep = 0; rep < 2; ++rep) { // (the second launch is the timed one)
         HIP_TRY(ctx, hipEventRecord(a, ctx->stream));
-        if (kind == 0) hipLaunchKernelGGL(k_probe_lds_rate<0>, grid, dim3(256), 0, ctx->stream, iters, 777u, (uint32_t *)ctx->scan_ws);
-        else if (kind == 1) hipLaunchKernelGGL(k_probe_lds_rate<1>, grid, dim3(256), 0, ctx->stream, iters, 777u, (uint32_t *)ctx->scan_ws);
-        else hipLaunchKernelGGL(k_probe_lds_rate<2>, grid, dim3(256), 0, ctx->stream, iters, 777u, (uint32_t *)ctx->scan_ws);
+        const bool ok = variant_dispatch([&](auto k) {
+            launch_kernel(ctx, NO_STAGE, k_probe_lds_rate<k.value>, grid, dim3(256), iters, 777u, (uint32_t *)ctx->scan_ws);
+            return true;
+        }, OneOf<0, 1, 2>{kind});
+        if (!ok) return ctx_fail(ctx, SPLAT_ERR_INVALID, "radix_probe_lds_rate: kind must be 0, 1 or 2");
         HIP_TRY(ctx, hipEventRecord(b, ctx->stream));
     }
     HIP_TRY(ctx, hipEventSynchronize(b));
@@ -713,57 +664,11 @@ int splat_rank_status(splat_ctx *ctx, int *policy, int *atomics_ordered, uint32_
     return SPLAT_OK;
 }
 
-int splat_composite_options(splat_ctx *ctx, int kernel, int ahead, int predict) {
-    if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
-    ARG_CHECK(ctx, kernel >= -1 && kernel <= 1 && ahead >= 0 && ahead <= 2 && predict >= -1 && predict <= 1);
-    ctx->opt_composite_kernel = kernel;
-    ctx->opt_px_ahead = ahead;
-    ctx->opt_px_predict = predict;
-    return splat_composite_forget_history(ctx); // (another schedule: its costs mean something else)
-}
-
-int splat_composite_forget_history(splat_ctx *ctx) {
-    if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
-    for (auto &h : ctx->px_hist) { // (the arrays stay: a slot's next launch starts a new streak in them)
-        h.key = 0;
-        h.streak = 0;
-        h.last_use = 0;
-    }
-    return SPLAT_OK;
-}
-
 #ifdef SPLAT_TEST_HOOKS // (the test build only: include/splat.h)
-int splat_debug_set_tile_sort_order(splat_ctx *ctx, const void *order_dptr) {
-    if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
-    ctx->debug_sort_order = (const uint32_t *)order_dptr;
-    return SPLAT_OK;
-}
-
-int splat_debug_set_tile_order(splat_ctx *ctx, const void *order_dptr) {
-    if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
-    ctx->debug_tile_order = (const uint32_t *)order_dptr;
-    return SPLAT_OK;
-}
-
 int splat_debug_lds_rate(splat_ctx *ctx, int kind, uint32_t workgroups_per_cu, uint32_t iters, float *ms) {
     if (!ctx || !ms) return ctx_fail(ctx, SPLAT_ERR_INVALID, "ctx/ms is NULL");
     ARG_CHECK(ctx, kind >= 0 && kind <= 2 && workgroups_per_cu >= 1 && workgroups_per_cu <= 8 && iters >= 1 && iters <= (1u << 20));
     return radix_probe_lds_rate(ctx, kind, workgroups_per_cu, iters, ms);
-}
-
-int splat_debug_tile_sort_launches(splat_ctx *ctx, uint32_t *launches) {
-    if (!ctx || !launches) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx/launches is NULL");
-    *launches = ctx->tile_sort_launches;
-    return SPLAT_OK;
-}
-
-int splat_debug_inject_order_fault(splat_ctx *ctx, uint32_t tile, uint32_t position) {
-    if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
-    ARG_CHECK(ctx, tile != 0xffffffffu);
-    ARG_CHECK(ctx, position < 0x3fffffffu); // (the kernel forms position + 2: no wrap, whatever a test passes)
-    ctx->inject_order_fault = tile + 1u;
-    ctx->inject_order_position = position;
-    return SPLAT_OK;
 }
 #endif
 

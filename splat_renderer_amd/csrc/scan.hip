@@ -7,36 +7,13 @@
 //
 // Roofline: HBM, 12 B per element in the 3-phase form (read, read, write), 8 B single-block.
 #include "common.h"
+#include "block_scan.h"
 
 constexpr uint32_t SCAN_THREADS = 256;
 constexpr uint32_t SCAN_UNIT = SCAN_THREADS * 4;  // one uint4 per thread
 constexpr uint32_t SCAN_UNITS_PER_TILE = 8;
 constexpr uint32_t SCAN_TILE = SCAN_UNIT * SCAN_UNITS_PER_TILE; // 8192 elements per workgroup
 constexpr uint32_t SCAN_SINGLE_MAX = 16384;
-
-__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        uint32_t t = __shfl_up(v, d);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-
-// exclusive scan of one value per thread over the 256-thread workgroup; returns this thread's
-// exclusive prefix and the workgroup total. wave_sums is 4 u32 of LDS.
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t *wave_sums, uint32_t &total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t incl = wave_inclusive_scan(v);
-    if (lane == 63) wave_sums[w] = incl;
-    __syncthreads();
-    uint32_t s0 = wave_sums[0], s1 = wave_sums[1], s2 = wave_sums[2], s3 = wave_sums[3];
-    __syncthreads(); // wave_sums may be rewritten by the next unit
-    uint32_t prefix = (w > 0 ? s0 : 0u) + (w > 1 ? s1 : 0u) + (w > 2 ? s2 : 0u);
-    total = s0 + s1 + s2 + s3;
-    return prefix + incl - v;
-}
 
 __device__ __forceinline__ uint4 load_unit(const uint32_t *in, uint32_t base, uint32_t n) {
     uint32_t i = base + threadIdx.x * 4;
@@ -65,7 +42,7 @@ __device__ __forceinline__ uint32_t scan_units(const uint32_t *in, uint32_t *out
     for (uint32_t base = elem0; base < elem1; base += SCAN_UNIT) {
         uint4 v = load_unit(in, base, n);
         uint32_t local = v.x + v.y + v.z + v.w, total;
-        uint32_t ex = block_exclusive_scan(local, wave_sums, total) + carry;
+        uint32_t ex = block_exclusive_scan<true>(local, wave_sums, &total) + carry; // (second barrier: wave_sums is rewritten by the next unit)
         uint4 o;
         o.x = ex;
         o.y = ex + v.x;
@@ -97,11 +74,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_reduce(const uint32_t *__
             acc += v.x + v.y + v.z + v.w;
         }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
-    if ((threadIdx.x & 63) == 0) wave_sums[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) sums[blockIdx.x] = wave_sums[0] + wave_sums[1] + wave_sums[2] + wave_sums[3];
+    const uint32_t total = block_sum(acc, wave_sums);
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(SCAN_THREADS) void k_scan_apply(const uint32_t *in, uint32_t *out, uint32_t n,

@@ -42,6 +42,11 @@ __device__ __forceinline__ bool tile_range(float4 bounds, uint32_t width, uint32
 __device__ __forceinline__ uint32_t pack_range32(bool ok, uint32_t tx0, uint32_t tx1, uint32_t ty0, uint32_t ty1) {
     return ok ? (tx0 | (tx1 << 8) | (ty0 << 16) | (ty1 << 24)) : 1u;
 }
+struct TileRect {
+    uint32_t tx0, tx1, ty0, ty1;
+    __device__ __forceinline__ bool empty() const { return tx0 > tx1 || ty0 > ty1; }
+};
+__device__ __forceinline__ TileRect unpack_range32(uint32_t r) { return {r & 0xffu, (r >> 8) & 0xffu, (r >> 16) & 0xffu, r >> 24}; }
 
 // 16-bit packed tile range (frame path, a side beyond 256 tiles; the binner takes at most 65535 a side):
 // {tx0 | tx1<<16, ty0 | ty1<<16}, the layout of the binner's own per-position ranges (bin.hip: k_bin_count).
@@ -50,11 +55,21 @@ __device__ __forceinline__ uint2 pack_range_wide(bool ok, uint32_t tx0, uint32_t
     return ok ? make_uint2(tx0 | (tx1 << 16), ty0 | (ty1 << 16)) : make_uint2(1u, 1u);
 }
 
+// Number of tiles a packed range covers, one function per format: the 8-bit range of the frame path (tile_first.hip) and the
+// 16-bit one of the binner's per-position ranges (bin.hip).
+__device__ __forceinline__ uint32_t range32_hits(uint32_t r) {
+    const TileRect t = unpack_range32(r);
+    return t.empty() ? 0u : (t.tx1 - t.tx0 + 1) * (t.ty1 - t.ty0 + 1);
+}
+__device__ __forceinline__ uint32_t range_hits(uint2 r) {
+    const uint32_t tx0 = r.x & 0xffffu, tx1 = r.x >> 16, ty0 = r.y & 0xffffu, ty1 = r.y >> 16;
+    return (tx0 > tx1 || ty0 > ty1) ? 0u : (tx1 - tx0 + 1) * (ty1 - ty0 + 1);
+}
+
 // First sort pass's histogram (tile_first.hip): one count per tile of the rectangle, keyed by the low
 // tile-id digit, into a wave-private 256-counter LDS histogram.  Returns the number of tiles.
-__device__ __forceinline__ uint32_t hist_add_rect(uint32_t *wave_hist, uint32_t tx0, uint32_t tx1, uint32_t ty0, uint32_t ty1,
-                                                  uint32_t ntx, uint32_t mask) {
-    for (uint32_t ty = ty0; ty <= ty1; ++ty)
-        for (uint32_t tx = tx0; tx <= tx1; ++tx) atomicAdd(&wave_hist[(ty * ntx + tx) & mask], 1u);
-    return (tx1 - tx0 + 1) * (ty1 - ty0 + 1);
+__device__ __forceinline__ uint32_t hist_add_rect(uint32_t *wave_hist, TileRect t, uint32_t ntx, uint32_t mask) {
+    for (uint32_t ty = t.ty0; ty <= t.ty1; ++ty)
+        for (uint32_t tx = t.tx0; tx <= t.tx1; ++tx) atomicAdd(&wave_hist[(ty * ntx + tx) & mask], 1u);
+    return (t.tx1 - t.tx0 + 1) * (t.ty1 - t.ty0 + 1);
 }

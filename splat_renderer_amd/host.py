@@ -674,7 +674,7 @@ class PerTileSorter:
     the reference's argument list and, with validate=True, runs the order CHECK on the device and
     returns the number of out-of-order neighbours (0).  The real per-tile depth sort (any list length,
     stable) lives inside the whole-frame call: Renderer.render bins in index order and sorts every
-    tile's list in LDS (csrc/tile_first.hip, k_tile_sort)."""
+    tile's list in LDS (csrc/tile_sort.hip, k_tile_sort)."""
 
     def __init__(self, device, validate=False):
         self.device, self.validate = device, validate

@@ -9,35 +9,28 @@ held to the bits of the same library's whole frame, which the other tests hold t
 """
 import ctypes as C
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
 
 import splat_renderer_amd as sr
 from splat_renderer_amd import _lib
+from tests.band_dispatch_child import BANDS, H, N, SEED, TILE, W, compacted_scatter_digests, strict_bands, whole_frame
 from tests.helpers import assert_same, make_case
 from tests.test_gpu_wide_screens import run_band_frame
 
 pytestmark = [pytest.mark.gpu,
               pytest.mark.skipif("SPLAT_BAND_COMPACT" in os.environ, reason="SPLAT_BAND_COMPACT forces one prepare pass for every band")]
 
-TILE, W, H, N, SEED = 16, 80, 80, 5000, 41
-BANDS = [(0, 2), (2, 5)]
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def case():
     assert -(-H // TILE) == 5 and 5 * (BANDS[0][1] - BANDS[0][0]) <= 2 * 5 < 5 * (BANDS[1][1] - BANDS[1][0])
     return make_case(N, W, H, SEED)
-
-
-def whole_frame(device, pbuf, nbuf, u, disc):
-    """The whole frame (records="projected"): its renderer, rgba8 and rgba32f bits."""
-    full = sr.Renderer(device, None, "rgba8unorm", N, TILE, footprint="disc" if disc else "isotropic", records="projected")
-    full.render(u, pbuf, nbuf, None, W, H, wantFloat=True)
-    want32, want8 = full.readPixelsFloat().view(np.uint32).copy(), full.readPixels().copy()
-    assert full.finish() > 0 and len(np.unique(want8.reshape(-1, 4), axis=0)) > 1  # (splats in the picture)
-    return full, want8, want32
 
 
 @pytest.mark.parametrize("order", ["tileFirst", "sortFirst"])
@@ -89,17 +82,16 @@ def test_band_frames_stitch_to_the_whole_frame(device, case, fmt, order):
 def test_strict_bands_stitch_to_the_whole_frame(device, case, records, footprint, order):
     """splat_render_frame's own strict bands (Renderer.render(tileRows=...)): the first band's projector leaves its splats
     compacted per group of 4096 in the tile-first order, the second's does not; both bands' rows are the whole frame's bits."""
-    props, normals, u = case
-    pbuf, nbuf = device.createBufferFrom(props), device.createBufferFrom(normals)
-    full, want8, want32 = whole_frame(device, pbuf, nbuf, u, footprint == "disc")
-    r = sr.Renderer(device, None, "rgba8unorm", N, TILE, frameOrder=order, footprint=footprint, records=records)
-    got8, got32 = np.zeros_like(want8), np.zeros_like(want32)
-    for r0, r1 in BANDS:
-        r.render(u, pbuf, nbuf, None, W, H, tileRows=(r0, r1), wantFloat=True)
-        p0, p1 = r0 * TILE, min(r1 * TILE, H)
-        got32[p0:p1] = r.readPixelsFloat().view(np.uint32)[p0:p1]
-        got8[p0:p1] = r.readPixels()[p0:p1]
-    assert_same(got8, want8, ("strict bands", records, footprint, order, "rgba8"))
-    assert_same(got32, want32, ("strict bands", records, footprint, order, "rgba32f"))
-    for o in (r, full, pbuf, nbuf):
-        o.destroy()
+    strict_bands(device, case, records, footprint, order)
+
+
+
+
+def test_compacted_scatter_with_ballot_ranking(device, case):
+    """SPLAT_RANK=ballot (a child process, tests/band_dispatch_child.py: the policy is read once per context) gives the bits this
+    process's policy gives: the compacted scatter's ballot-ranking kernel, which no other test launches."""
+    env = dict(os.environ, SPLAT_RANK="ballot")
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "band_dispatch_child.py")], cwd=ROOT, env=env, stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, text=True, timeout=300)
+    line = "band_dispatch_child ok: rank=ballot " + " ".join(compacted_scatter_digests(device, case))
+    assert p.returncode == 0 and line in p.stdout.splitlines(), p.stdout[-2000:] + p.stderr[-3000:]

@@ -126,7 +126,23 @@ def test_radix_sort_stable(device, n, kind, mode):
 
 @pytest.mark.parametrize("bits_range", [(0, 8), (0, 13), (8, 16), (0, 15), (5, 6)])
 def test_radix_sort_bit_ranges(device, bits_range):
-    b0, b1 = bits_range
+    sort_bit_range(device, *bits_range)
+
+
+def test_radix_sort_single_pass_with_atomic_ranking(monkeypatch):
+    """One 8-bit pass under SPLAT_RANK=atomic: k_radix_downsweep<16, true, false, false> (atomic ranking, separate arrays in and
+    out), which the two- and four-pass sorts of test_ranking_policies do not launch."""
+    monkeypatch.setenv("SPLAT_RANK", "atomic")
+    dev = sr.Device(0)  # (the ranking is resolved once per context)
+    try:
+        st = dev.rankStatus()
+        assert st["policy"] == "atomic" and st["atomicsOrdered"], st
+        sort_bit_range(dev, 0, 8)
+    finally:
+        dev.destroy()
+
+
+def sort_bit_range(device, b0, b1):
     n = 50000
     rng = np.random.default_rng(b0 * 100 + b1)
     keys = rng.integers(0, 2**32, size=n, dtype=np.uint64).astype(np.uint32)
@@ -1098,6 +1114,21 @@ def test_each_short_class_sorts_an_outgrown_tile_as_the_last_class(short):
         pytest.skip("SPLAT_BIN_SYNC=1: no frame is sync-free")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, SPLAT_LIB_PATH=_lib.HOOKS_LIB_PATH, SPLAT_TILE_SORT_SHORT=str(short))
+    p = subprocess.run([sys.executable, os.path.join(root, "tests", "hooks_child.py"), "long_class_skip"], cwd=root, env=env,
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert p.returncode == 0 and f"long_class_skip ok: 6 frames, short class {short} (forced)" in p.stdout, p.stdout[-2000:] + p.stderr[-3000:]
+
+
+@pytest.mark.parametrize("short", [8, 12, 16])
+def test_each_short_class_as_the_last_class_with_ballot_ranking(short):
+    """The same child under SPLAT_RANK=ballot: k_tile_sort<false, 8 | 12 | 16, true>, which nothing else launches (the other
+    ballot tests' frames have tiles beyond the short class, or one class for every tile)."""
+    import subprocess
+    import sys
+    if os.environ.get("SPLAT_BIN_SYNC") == "1":
+        pytest.skip("SPLAT_BIN_SYNC=1: no frame is sync-free")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, SPLAT_LIB_PATH=_lib.HOOKS_LIB_PATH, SPLAT_TILE_SORT_SHORT=str(short), SPLAT_RANK="ballot")
     p = subprocess.run([sys.executable, os.path.join(root, "tests", "hooks_child.py"), "long_class_skip"], cwd=root, env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert p.returncode == 0 and f"long_class_skip ok: 6 frames, short class {short} (forced)" in p.stdout, p.stdout[-2000:] + p.stderr[-3000:]
