@@ -805,6 +805,68 @@ int splat_image_loss_backward(splat_ctx *ctx, const void *image, uint32_t image_
                               uint32_t width, uint32_t height, float lambda, const void *workspace, uint64_t workspace_bytes,
                               const void *upstream, void *grad_image, uint32_t grad_stride);
 
+/* ---- Normals of a depth map: the surface a depth map describes, and 2DGS's normal-consistency loss (an extension) -------------
+ * Rays.  VP is the uniform block's matrix (VP[r][c] = uniforms[4 c + r], as pinhole_uniforms and Camera store it); M is the 3 x 3
+ * of its rows 0, 1, 3 acting on xyz and m their fourth column.  A pinhole camera has M eye + m = 0, and the point seen at pixel
+ * centre (x + 1/2, y + 1/2) with clip w = s is eye + s d(x, y),
+ *   d(x, y) = M^-1 (2 (x + 1/2) / W - 1, 1 - 2 (y + 1/2) / H, 1)^T = D0 + x Dx + y Dy,
+ * affine in the pixel index.  The host computes D0, Dx, Dy in float64 and the handedness sign
+ *   sigma = -sign((Dy x Dx) . d_c),  d_c = M^-1 (0, 0, 1) the ray of the screen's centre,
+ * with which every normal below faces the eye (N . d < 0) whether or not the camera mirrors an axis.  A camera whose M is
+ * singular (|det M| <= 1e-14 |row 0| |row 1| |row 3|: an orthographic VP is one) or whose sigma is 0 is refused with
+ * SPLAT_ERR_INVALID, and splat_last_error says which.  uniforms[16..21] are not read by the device entry points (the eye cancels:
+ * a normal is a difference of points; the screen is the width and height arguments).
+ *
+ * Ray parameter.  depth_kind says what the depth map holds: SPLAT_DEPTH_DISTANCE, |P - eye| (what splat_project_ellipsoid's depth
+ * and so the AOV depth of a Gaussian frame are): s = depth / |d|;  SPLAT_DEPTH_Z, clip w (planar depth): s = depth.
+ *
+ * Normal at pixel p = (x, y), from the ray parameters s_l, s_r, s_u, s_d of (x-1, y), (x+1, y), (x, y-1), (x, y+1):
+ *   a_x = (s_r - s_l) d(p) + (s_r + s_l) Dx,   a_y = (s_d - s_u) d(p) + (s_d + s_u) Dy,   n = sigma (a_y x a_x),   N = n / |n|:
+ * the central difference P(x+1) - P(x-1) of 2DGS's depth_to_normal, written with d affine so that only the depth difference
+ * cancels, not two world points.  The kernels evaluate the same n with the cross product expanded,
+ *   n = sigma [(s_d - s_u)(s_r + s_l) d x Dx + (s_d + s_u)(s_r - s_l) Dy x d + (s_d + s_u)(s_r + s_l) Dy x Dx]
+ * (the d x d term is zero and is not formed), in binary32 from ray parameters rounded once; 1 / |d| and the three cross products
+ * are made in float64.
+ * Validity.  N = (0, 0, 0), and the pixel passes no gradient, unless 1 <= x <= W - 2 and 1 <= y <= H - 2, all four neighbour
+ * depths are finite and > 0 (an empty pixel of the AOV depth is +inf), and |n|^2 is finite and > 0.  The pixel's own depth is not
+ * read.  Screens with W < 3 or H < 3 are legal and give all zeros.
+ *
+ * splat_depth_normals WRITES the first three floats of every pixel of (normals, normal_stride) (an image as the image loss
+ * defines one: pixel stride in floats >= 3, other words not touched).
+ * splat_depth_normals_backward OVERWRITES grad_depth (W H floats) with dL/ddepth given dL/dN (grad_normals, grad_stride).  A
+ * depth pixel q enters the normals of q + (1, 0), q - (1, 0), q + (0, 1), q - (0, 1) (as their left, right, upper, lower
+ * neighbour); the up to four contributions are gathered and added in that order, then multiplied by ds/ddepth: no atomics, the
+ * same bits on every run.  A pixel whose depth is not finite gets exactly 0.  The upstream of an invalid pixel is not read (it
+ * is selected away, not multiplied by zero): NaN or inf there reaches nothing.  The camera gets no gradient.
+ *
+ * The loss, 2DGS's normal_error.mean():  L = (1 / (W H)) sum_p (1 - w_p F_p . N_p),  F the blended normal map (normal_map,
+ * map_stride: an (H, W, K) feature map whose first three channels are the normal is read in place), w an optional W H weight
+ * (2DGS: the detached alpha; NULL: 1).  An invalid pixel contributes the constant 1, and its F and w are not read.
+ * splat_normal_consistency writes out4 (DEVICE, 4 floats) = {L, fraction of valid pixels, 0, 0}; the sum is made of float64
+ * per-workgroup partials in a scratch buffer of the ctx, added in index order by one small kernel and rounded once.
+ * splat_normal_consistency_backward, one launch, with g = upstream[0] (DEVICE, one float, read on the device):
+ *   dL/dF_p = -(g / (W H)) w_p N_p   OVERWRITES the first three floats of every pixel of (grad_map, grad_map_stride) (0 at an
+ *                                    invalid pixel; other words not touched),
+ *   dL/ddepth                        OVERWRITES grad_depth, splat_depth_normals_backward's gather with dL/dN_p = -(g / (W H)) w_p F_p.
+ * w gets no gradient.
+ *
+ * splat_camera_rays: host only, no ctx, no device: out10 = {D0, Dx, Dy, sigma} in float64 for the screen uniforms[20], [21].
+ * All device work goes to the ctx's stream; nothing waits on the host; no caller workspace.  SPLAT_ERR_INVALID, nothing
+ * launched: a NULL pointer (weight may be NULL), width or height 0 or above 65535, a stride below 3, an unknown depth_kind, a
+ * pointer that is not 4-byte aligned, a refused camera. */
+#define SPLAT_DEPTH_DISTANCE 0u
+#define SPLAT_DEPTH_Z 1u
+int splat_camera_rays(const float *uniforms, double *out10);
+int splat_depth_normals(splat_ctx *ctx, const float *uniforms, uint32_t depth_kind, const void *depth, uint32_t width, uint32_t height,
+                        void *normals, uint32_t normal_stride);
+int splat_depth_normals_backward(splat_ctx *ctx, const float *uniforms, uint32_t depth_kind, const void *depth, uint32_t width,
+                                 uint32_t height, const void *grad_normals, uint32_t grad_stride, void *grad_depth);
+int splat_normal_consistency(splat_ctx *ctx, const float *uniforms, uint32_t depth_kind, const void *depth, const void *normal_map,
+                             uint32_t map_stride, const void *weight, uint32_t width, uint32_t height, void *out4);
+int splat_normal_consistency_backward(splat_ctx *ctx, const float *uniforms, uint32_t depth_kind, const void *depth,
+                                      const void *normal_map, uint32_t map_stride, const void *weight, uint32_t width, uint32_t height,
+                                      const void *upstream, void *grad_map, uint32_t grad_map_stride, void *grad_depth);
+
 /* ---- Density control and optimiser: what fitting a cloud of 3D Gaussians needs beside the frame (an extension) --------------
  * The parameters are 3DGS's raw ones, contiguous float32 DEVICE planes: means (n, 3), log_scales (n, 3), rotations (n, 4) as
  * (w, x, y, z), unnormalised, opacity_logits (n), sh (n, 3 K) basis-major as splat_sh_colors takes it.  The activations

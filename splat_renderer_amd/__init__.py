@@ -15,6 +15,7 @@ from .frameloop import FrameLoop, MouseEvent, OrbitCameraController, SdfSplatSou
 from . import sdf  # noqa: F401
 from .ply import load_gaussian_ply, load_point_ply, save_gaussian_ply  # noqa: F401
 from .fit import GaussianFit  # noqa: F401
+from .autograd import depth_normals, normal_consistency_loss, splat_normals  # noqa: F401  (torch is imported when one is first called)
 
 
 def knn_mean_sq_distance(points, return_evaluations=False):

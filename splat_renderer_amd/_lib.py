@@ -23,6 +23,7 @@ MODE_FRONT_TO_BACK, MODE_REFERENCE_LITERAL = 0, 1
 RECORDS_PROJECTED, RECORDS_COMPACT, RECORDS_DISC48, RECORDS_LIT32 = 0, 1, 2, 3
 FOOTPRINT_ISOTROPIC, FOOTPRINT_DISC, FOOTPRINT_ELLIPSOID = 0, 1, 2
 U32_MAX = 0xFFFFFFFF
+DEPTH_DISTANCE, DEPTH_Z = 0, 1  # include/splat.h, SPLAT_DEPTH_*: what a depth map holds (|P - eye|, or clip w)
 
 
 class SplatError(RuntimeError):
@@ -134,6 +135,11 @@ SIGNATURES = {
     "splat_image_loss_workspace_bytes": (C.c_uint64, [_u32, _u32]),
     "splat_image_loss": (_i, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, C.c_float, _vp, C.c_uint64, _vp]),
     "splat_image_loss_backward": (_i, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, C.c_float, _vp, C.c_uint64, _vp, _vp, _u32]),
+    "splat_camera_rays": (_i, [C.POINTER(C.c_float), C.POINTER(C.c_double)]),
+    "splat_depth_normals": (_i, [_vp, C.POINTER(C.c_float), _u32, _vp, _u32, _u32, _vp, _u32]),
+    "splat_depth_normals_backward": (_i, [_vp, C.POINTER(C.c_float), _u32, _vp, _u32, _u32, _vp, _u32, _vp]),
+    "splat_normal_consistency": (_i, [_vp, C.POINTER(C.c_float), _u32, _vp, _vp, _u32, _vp, _u32, _u32, _vp]),
+    "splat_normal_consistency_backward": (_i, [_vp, C.POINTER(C.c_float), _u32, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _u32, _vp]),
     "splat_adam_step": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _f64, _f64, _f64, _f64, _f64, _f64, _vp]),
     "splat_density_accumulate": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
     "splat_density_accumulate_abs": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),

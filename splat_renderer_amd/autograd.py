@@ -98,6 +98,28 @@ float64 in a fixed order and the backward is a gather: both are bit-reproducible
 so backward() does not synchronise.  lambda_dssim = 0 is a plain L1: the SSIM part is not launched (unless return_terms asks
 for its value).  No masks: multiply both images by one in torch.
 
+The geometry term (include/splat.h, "Normals of a depth map"):
+
+    normals      = depth_normals(depth, camera_or_uniforms, depth_kind="distance")                       # (H, W, 3), differentiable in depth
+    loss         = normal_consistency_loss(normal_map, depth, camera_or_uniforms, weight=None)            # 0-d, differentiable in both
+    loss, valid  = normal_consistency_loss(..., return_terms=True)                                        # valid: fraction of pixels with a normal
+    n            = splat_normals(means, scales, rotations, eye)                                           # (n, 3), torch ops
+
+depth_normals is the unit normal of the surface a depth map describes: the cross product of the central differences of the
+points the four neighbours of a pixel see along the camera's rays, facing the eye whether or not the camera mirrors an axis.  It
+is 0, and passes no gradient, on the border, next to an empty (+inf), non-positive or NaN depth, and on screens below 3 x 3.
+depth_kind says what the map holds: "distance", |P - eye|, which is what rasterize(depths=) gives from project_ellipsoids'
+depths, or "z", clip w.  normal_consistency_loss is 2DGS's normal_error.mean(), mean(1 - weight * normal_map . normals), with
+an invalid pixel contributing the constant 1: one fused kernel and a small sum forward (splat_normal_consistency), one kernel
+backward for both gradients (splat_normal_consistency_backward), instead of some two dozen element-wise ops over (H, W, 3)
+temporaries and their transposes.  normal_map is (H, W, 3) or an (H, W, K >= 3) feature map whose first three channels are the
+normal, read in place by its pixel stride (its other channels get zero gradient from this term); weight (2DGS: alpha.detach())
+is detached.  Every sum is made in a fixed order without atomics and the backward recomputes instead of storing: no workspace,
+the same bits on every run, and the upstream is read on the device, so backward() does not synchronise.  The camera gets no
+gradient from this term: a uniforms tensor that requires grad is refused with SplatError (pass uniforms.detach()) rather than
+its gradient dropped silently.  Only perspective cameras: an orthographic VP is refused.  splat_normals is the per-splat normal
+2DGS blends: the axis of the smallest scale, flipped towards the eye.
+
 `rec` is a real intermediate: rec.retain_grad() gives the screen-space gradient rec.grad[:, :2] that 3DGS densification reads.
 
 The background is the composite's fixed bg = (0.05, 0.05, 0.1).  A caller that wants background b uses
@@ -144,16 +166,11 @@ than mixing a reproducible and a non-reproducible sum.  absgrad keeps counting t
 features= every function runs the calls it always ran.  Measured on one MI355X at 5 M splats, 1920 x 1080:
 the map 0.35 ms at K = 3 and 0.37 at K = 8; its backward 1.13 and 1.35 ms beside the image's 1.10.  Two recipes:
 
-    # Normals, for a normal-consistency term: each splat's shortest axis (a column of R(q)), flipped towards the eye
-    q = rotations / rotations.norm(dim=1, keepdim=True)
-    r, x, y, z = q.unbind(1)
-    R = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y),
-                     2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x),
-                     2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)], dim=1).reshape(-1, 3, 3)
-    axis = R.gather(2, scales.argmin(dim=1).reshape(-1, 1, 1).expand(-1, 3, 1)).squeeze(2)        # (n, 3): column argmin of R
-    axis = torch.where(((means - eye) * axis).sum(dim=1, keepdim=True) > 0, -axis, axis)
-    rgb, alpha, normal_map = render_gaussians(cam, means, scales, rotations, opacities, sh=sh, width=W, height=H, features=axis)
-    # (normal_map is sum w n: divide by alpha.clamp_min(eps)[..., None], or normalise it, as the term at hand wants)
+    # Normal consistency (2DGS): each splat's shortest axis, flipped towards the eye, blended beside the image and held to the
+    # normal of the depth map (below, "The geometry term")
+    rgb, alpha, depth, nmap = render_gaussians(cam, means, scales, rotations, opacities, sh=sh, width=W, height=H, return_depth=True,
+                                               features=splat_normals(means, scales, rotations, eye))
+    loss = photometric_loss(rgb, target) + lam * normal_consistency_loss(nmap, depth, cam, weight=alpha.detach())
 
     # Depth distortion (Mip-NeRF 360, 2DGS): sum over pairs j < i of w_i w_j (z_i - z_j)^2 = W Q - M^2 from one walk
     rec, depths, aux = project_ellipsoids(cam_uniforms, means, scales, rotations, return_depth=True)
@@ -611,8 +628,64 @@ def _functions():
                                                    ws.data_ptr() if nbytes and lam > 0.0 else None, nbytes, up.data_ptr(), g.data_ptr(), 3), cx.ctx)
             return g, None, None, None, None, None
 
+    class DepthNormals(torch.autograd.Function):
+        @staticmethod
+        def forward(fctx, depth, u, kind):
+            cx = _context(depth)
+            h, w = depth.shape
+            out = torch.empty((h, w, 3), device=depth.device, dtype=torch.float32)
+            check(cx.lib.splat_depth_normals(cx.ctx, _fptr(u), kind, depth.data_ptr(), w, h, out.data_ptr(), 3), cx.ctx)
+            fctx.save_for_backward(depth)
+            fctx.args = (u, kind)
+            return out
+
+        @staticmethod
+        def backward(fctx, grad_normals):
+            depth, = fctx.saved_tensors
+            u, kind = fctx.args
+            cx = _context(depth)
+            h, w = depth.shape
+            g, gs = _image(grad_normals, "the gradient of the normals", (3,))
+            gz = torch.empty((h, w), device=depth.device, dtype=torch.float32)
+            check(cx.lib.splat_depth_normals_backward(cx.ctx, _fptr(u), kind, depth.data_ptr(), w, h, g.data_ptr(), gs, gz.data_ptr()), cx.ctx)
+            return gz, None, None
+
+    class NormalConsistency(torch.autograd.Function):
+        @staticmethod
+        def forward(fctx, nmap, ms, depth, weight, u, kind):
+            # (nmap: a tensor whose data_ptr() is an image of pixel stride ms floats, (H, W, K >= 3), perhaps a view)
+            cx = _context(depth)
+            h, w = depth.shape
+            out = torch.empty(4, device=depth.device, dtype=torch.float32)
+            check(cx.lib.splat_normal_consistency(cx.ctx, _fptr(u), kind, depth.data_ptr(), nmap.data_ptr(), ms,
+                                                  weight.data_ptr() if weight is not None else None, w, h, out.data_ptr()), cx.ctx)
+            fctx.save_for_backward(nmap, depth, weight)
+            fctx.args = (ms, u, kind)
+            fctx.set_materialize_grads(False)
+            loss, valid = out[0], out[1]
+            fctx.mark_non_differentiable(valid)
+            return loss, valid
+
+        @staticmethod
+        def backward(fctx, grad_loss, *_):
+            if grad_loss is None:
+                return (None,) * 6
+            nmap, depth, weight = fctx.saved_tensors
+            ms, u, kind = fctx.args
+            cx = _context(depth)
+            h, w = depth.shape
+            up = grad_loss.to(torch.float32).reshape(1).contiguous()
+            k = nmap.shape[2]
+            gmap = torch.empty((h, w, 3), device=depth.device, dtype=torch.float32) if k == 3 else \
+                torch.zeros((h, w, k), device=depth.device, dtype=torch.float32)  # (channels past the normal: no gradient from this term)
+            gz = torch.empty((h, w), device=depth.device, dtype=torch.float32)
+            check(cx.lib.splat_normal_consistency_backward(cx.ctx, _fptr(u), kind, depth.data_ptr(), nmap.data_ptr(), ms,
+                                                           weight.data_ptr() if weight is not None else None, w, h, up.data_ptr(),
+                                                           gmap.data_ptr(), k, gz.data_ptr()), cx.ctx)
+            return gmap, None, gz, None, None, None
+
     fns = globals()["_fns"] = types.SimpleNamespace(Project=Project, ShColors=ShColors, Rasterize=Rasterize, CompositeFeatures=CompositeFeatures,
-                                                  PhotometricLoss=PhotometricLoss)
+                                                  PhotometricLoss=PhotometricLoss, DepthNormals=DepthNormals, NormalConsistency=NormalConsistency)
     return fns
 
 
@@ -837,6 +910,92 @@ def photometric_loss(rgb, target, lambda_dssim=0.2, return_terms=False):
     lam = float(lambda_dssim)
     loss, l1, ssim = _functions().PhotometricLoss.apply(x, xs, y.detach(), ys, lam, bool(return_terms))
     return (loss, l1, ssim) if return_terms else loss
+
+
+def _ray_uniforms(camera_or_uniforms, width, height, who):
+    """The host block of a camera whose rays a depth map's normals are taken along.  No camera gradient exists for them: a
+    uniforms tensor that requires grad is refused rather than its gradient dropped silently."""
+    if getattr(camera_or_uniforms, "requires_grad", False):
+        raise SplatError(-1, f"{who}: the uniforms tensor requires grad, and the normals of a depth map offer no camera gradient; pass "
+                             "uniforms.detach() to hold the camera fixed in this term")
+    return _uniforms(camera_or_uniforms, width, height)
+
+
+def _depth_kind(depth_kind, who):
+    kinds = {"distance": _lib.DEPTH_DISTANCE, "z": _lib.DEPTH_Z}
+    if depth_kind not in kinds:
+        raise SplatError(-1, f"{who}: depth_kind must be 'distance' or 'z', not {depth_kind!r}")
+    return kinds[depth_kind]
+
+
+def _depth_map(depth, width, height, who):
+    _cuda_f32(depth, "depth")
+    if depth.dim() != 2 or depth.shape[0] < 1 or depth.shape[1] < 1:
+        raise SplatError(-1, f"{who}: depth must have shape (H, W), not {tuple(depth.shape)}")
+    h, w = depth.shape
+    if (width is not None and int(width) != w) or (height is not None and int(height) != h):
+        raise SplatError(-1, f"{who}: depth is {w} x {h} pixels, not width x height = {width} x {height}")
+    return depth.contiguous(), w, h
+
+
+def depth_normals(depth, camera_or_uniforms, width=None, height=None, depth_kind="distance"):
+    """(H, W, 3): the unit normal of the surface the depth map (H, W) describes, facing the eye; 0 at the border, next to an empty
+    (+inf) or non-positive depth (include/splat.h, "Normals of a depth map"; the module's docstring).  Differentiable in depth.
+    depth_kind: "distance" (|P - eye|: what rasterize(depths=) and render_gaussians(return_depth=True) give) or "z" (clip w)."""
+    d, w, h = _depth_map(depth, width, height, "depth_normals")
+    u = _ray_uniforms(camera_or_uniforms, w, h, "depth_normals")
+    return _functions().DepthNormals.apply(d, u, _depth_kind(depth_kind, "depth_normals"))
+
+
+def normal_consistency_loss(normal_map, depth, camera_or_uniforms, weight=None, depth_kind="distance", width=None, height=None,
+                            return_terms=False):
+    """2DGS's normal consistency mean(1 - weight * normal_map . depth_normals(depth)): a 0-d tensor, differentiable in normal_map
+    and depth, from one fused kernel forward and one backward.  normal_map (H, W, K >= 3): its first three channels are read
+    where they lie, by the pixel stride, when the tensor (or view) is a packed image of K floats per pixel; weight (H, W) or
+    None is detached.  return_terms=True: (loss, fraction of valid pixels), the second detached.  The module's docstring has
+    the rest."""
+    torch = _t()
+    who = "normal_consistency_loss"
+    d, w, h = _depth_map(depth, width, height, who)
+    u = _ray_uniforms(camera_or_uniforms, w, h, who)
+    f = normal_map
+    if isinstance(f, torch.Tensor) and f.dim() == 3 and f.shape[2] > 4:
+        # (_image's rule for K floats per pixel: read in place when the pixels are packed K apart)
+        if not f.is_cuda:
+            raise SplatError(-1, f"normal_map is on {f.device}: splat_renderer_amd has no CPU path")
+        if f.dtype != torch.float32:
+            raise SplatError(-1, f"normal_map must be float32, not {f.dtype}")
+        k = f.shape[2]
+        packed = f.stride(2) == 1 and (f.shape[1] == 1 or f.stride(1) == k) and (f.shape[0] == 1 or f.stride(0) == f.shape[1] * k)
+        f, fs = (f, k) if packed else (f.contiguous(), k)
+    else:
+        f, fs = _image(f, "normal_map", (3, 4))
+    if tuple(f.shape[:2]) != (h, w):
+        raise SplatError(-1, f"normal_map is {tuple(f.shape[:2])} pixels and depth {(h, w)}")
+    wt = None
+    if weight is not None:
+        wt = _cuda_f32(weight.detach(), "weight")
+        if tuple(wt.shape) != (h, w):
+            raise SplatError(-1, f"weight must have shape ({h}, {w}), not {tuple(wt.shape)}")
+    if f.device != d.device or (wt is not None and wt.device != d.device):
+        raise SplatError(-1, "normal_map, depth and weight must be on one device")
+    loss, valid = _functions().NormalConsistency.apply(f, fs, d, wt, u, _depth_kind(depth_kind, who))
+    return (loss, valid) if return_terms else loss
+
+
+def splat_normals(means, scales, rotations, eye):
+    """(n, 3): each splat's normal for a normal-consistency term, in torch ops (any device): the axis of its shortest scale, a
+    column of R(q) of the normalised quaternion (w, x, y, z), flipped so that it faces the eye.  Differentiable in rotations
+    (the choice of the axis and of the sign are held fixed); pass the result as render_gaussians' features."""
+    torch = _t()
+    q = rotations / rotations.norm(dim=1, keepdim=True)
+    r, x, y, z = q.unbind(1)
+    R = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y),
+                     2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x),
+                     2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)], dim=1).reshape(-1, 3, 3)
+    axis = R.gather(2, scales[:, :3].argmin(dim=1).reshape(-1, 1, 1).expand(-1, 3, 1)).squeeze(2)  # (n, 3): column argmin of R
+    eye = torch.as_tensor(eye, dtype=means.dtype, device=means.device).reshape(3)
+    return torch.where(((means[:, :3] - eye) * axis).sum(dim=1, keepdim=True) > 0, -axis, axis)
 
 
 def pinhole_uniforms(R, t, fx, fy, cx, cy, width, height, near=0.01, far=1000.0):

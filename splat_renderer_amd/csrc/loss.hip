@@ -23,6 +23,7 @@
 // Roofline: both kernels are bound by their LDS passes, not by HBM ("Loss", has the measured times beside
 // the traffic floors).
 #include "common.h"
+#include "image.h"
 
 namespace {
 
@@ -39,30 +40,6 @@ struct LossImages {
     const float *x, *y;
     uint32_t xs, ys, w, h;
 };
-struct Px3 {
-    float c[3];
-};
-
-// pixel i of an image; vec4: stride 4 on a 16-byte aligned base (workgroup-uniform)
-__device__ __forceinline__ Px3 load_px(const float *__restrict__ p, uint32_t stride, bool vec4, size_t i) {
-    Px3 r;
-    if (vec4) {
-        const float4 v = reinterpret_cast<const float4 *>(p)[i];
-        r.c[0] = v.x; r.c[1] = v.y; r.c[2] = v.z;
-    } else {
-        const float *q = p + i * stride;
-        r.c[0] = q[0]; r.c[1] = q[1]; r.c[2] = q[2];
-    }
-    return r;
-}
-__device__ __forceinline__ bool is_vec4(const float *p, uint32_t stride) { return stride == 4u && ((uintptr_t)p & 15u) == 0; }
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 template <bool SSIM>
 __global__ __launch_bounds__(256) void k_image_loss(LossImages im, LossWindow win, float *__restrict__ ws, double *__restrict__ part) {
     __shared__ float s_x[SSIM ? 3 : 1][SSIM ? LSH : 1][SSIM ? LSW : 1], s_y[SSIM ? 3 : 1][SSIM ? LSH : 1][SSIM ? LSW : 1];

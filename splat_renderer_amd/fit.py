@@ -115,16 +115,11 @@ and its gradients reach means, log_scales, rotations and opacity_logits through 
 A deterministic fit refuses it (SplatError): the feature gradients are float atomic sums and no fixed-order variant exists.
 absgrad's statistic keeps counting the image's terms only.  The two usual regularisers, in torch ops on the fit's parameters:
 
-    # normal consistency: the shortest axis of every splat, flipped towards the eye, blended into a normal map
+    # normal consistency (2DGS): the shortest axis of every splat, flipped towards the eye, blended into a normal map and held to
+    # the normal of the frame's own depth map by one fused kernel pair (autograd.normal_consistency_loss)
     scales, _ = fit._activated()
-    q = fit.rotations / fit.rotations.norm(dim=1, keepdim=True)
-    r, x, y, z = q.unbind(1)
-    R = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y),
-                     2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x),
-                     2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)], dim=1).reshape(-1, 3, 3)
-    axis = R.gather(2, scales.argmin(dim=1).reshape(-1, 1, 1).expand(-1, 3, 1)).squeeze(2)
-    axis = torch.where(((fit.means - eye) * axis).sum(dim=1, keepdim=True) > 0, -axis, axis)
-    rgb, alpha, normal_map = fit.render(cam, width, height, features=axis)
+    rgb, alpha, depth, nmap = fit.render(cam, width, height, return_depth=True, features=AG.splat_normals(fit.means, scales, fit.rotations, eye))
+    loss = AG.photometric_loss(rgb, target) + lam * AG.normal_consistency_loss(nmap, depth, cam, weight=alpha.detach())
 
     # depth distortion: features (1, z, z^2) give W, M, Q per pixel; sum_{j<i} w_i w_j (z_i - z_j)^2 = W Q - M^2
     z = ((fit.means - eye).norm(dim=1) - near) / (far - near)          # normalised to the scene's depth range: see below

@@ -542,6 +542,46 @@ FN(image_loss_backward) { /* image_loss's arguments up to workspaceBytes, then u
     void *up = arg_dptr(&c, 10), *g = arg_dptr(&c, 11); uint32_t gs = (uint32_t)arg_number(&c, 12); BAIL;
     return check(env, x, splat_image_loss_backward(x, img, is, tgt, ts, w, h, lambda, ws, wb, up, g, gs), mk_undefined(env));
 }
+FN(camera_rays) { /* (Float32Array(22)) -> [D0 (3), Dx (3), Dy (3), sigma]: host only, no ctx */
+    ARGS(1); size_t ub = 0; float *u = arg_hostbuf(&c, 0, &ub); BAIL;
+    if (ub < 22 * sizeof(float)) { napi_throw_range_error(env, NULL, "uniform block needs 22 floats"); return NULL; }
+    double out[10];
+    int rc = splat_camera_rays(u, out);
+    if (rc != SPLAT_OK) return check(env, NULL, rc, NULL);
+    napi_value arr;
+    if (napi_create_array_with_length(env, 10, &arr) != napi_ok) return NULL;
+    for (uint32_t i = 0; i < 10; ++i) napi_set_element(env, arr, i, mk_number(env, out[i]));
+    return arr;
+}
+FN(depth_normals) { /* (ctx, Float32Array(22), depthKind (0 distance | 1 z), depth, W, H, normals, normalStride) */
+    ARGS(8); splat_ctx *x = arg_external(&c, 0); size_t ub = 0; float *u = arg_hostbuf(&c, 1, &ub); uint32_t kind = (uint32_t)arg_number(&c, 2);
+    void *z = arg_dptr(&c, 3); uint32_t w = (uint32_t)arg_number(&c, 4), h = (uint32_t)arg_number(&c, 5);
+    void *nm = arg_dptr(&c, 6); uint32_t ns = (uint32_t)arg_number(&c, 7); BAIL;
+    if (ub < 22 * sizeof(float)) { napi_throw_range_error(env, NULL, "uniform block needs 22 floats"); return NULL; }
+    return check(env, x, splat_depth_normals(x, u, kind, z, w, h, nm, ns), mk_undefined(env));
+}
+FN(depth_normals_backward) { /* (ctx, Float32Array(22), depthKind, depth, W, H, gradNormals, gradStride, gradDepth) */
+    ARGS(9); splat_ctx *x = arg_external(&c, 0); size_t ub = 0; float *u = arg_hostbuf(&c, 1, &ub); uint32_t kind = (uint32_t)arg_number(&c, 2);
+    void *z = arg_dptr(&c, 3); uint32_t w = (uint32_t)arg_number(&c, 4), h = (uint32_t)arg_number(&c, 5);
+    void *gn = arg_dptr(&c, 6); uint32_t gs = (uint32_t)arg_number(&c, 7); void *gz = arg_dptr(&c, 8); BAIL;
+    if (ub < 22 * sizeof(float)) { napi_throw_range_error(env, NULL, "uniform block needs 22 floats"); return NULL; }
+    return check(env, x, splat_depth_normals_backward(x, u, kind, z, w, h, gn, gs, gz), mk_undefined(env));
+}
+FN(normal_consistency) { /* (ctx, Float32Array(22), depthKind, depth, normalMap, mapStride, weight|null, W, H, out4 (device: loss, valid fraction, 0, 0)) */
+    ARGS(10); splat_ctx *x = arg_external(&c, 0); size_t ub = 0; float *u = arg_hostbuf(&c, 1, &ub); uint32_t kind = (uint32_t)arg_number(&c, 2);
+    void *z = arg_dptr(&c, 3), *nm = arg_dptr(&c, 4); uint32_t ms = (uint32_t)arg_number(&c, 5); void *wt = arg_dptr(&c, 6);
+    uint32_t w = (uint32_t)arg_number(&c, 7), h = (uint32_t)arg_number(&c, 8); void *out = arg_dptr(&c, 9); BAIL;
+    if (ub < 22 * sizeof(float)) { napi_throw_range_error(env, NULL, "uniform block needs 22 floats"); return NULL; }
+    return check(env, x, splat_normal_consistency(x, u, kind, z, nm, ms, wt, w, h, out), mk_undefined(env));
+}
+FN(normal_consistency_backward) { /* normal_consistency's arguments up to H, then upstream (device, 1 float), gradMap, gradMapStride, gradDepth */
+    ARGS(13); splat_ctx *x = arg_external(&c, 0); size_t ub = 0; float *u = arg_hostbuf(&c, 1, &ub); uint32_t kind = (uint32_t)arg_number(&c, 2);
+    void *z = arg_dptr(&c, 3), *nm = arg_dptr(&c, 4); uint32_t ms = (uint32_t)arg_number(&c, 5); void *wt = arg_dptr(&c, 6);
+    uint32_t w = (uint32_t)arg_number(&c, 7), h = (uint32_t)arg_number(&c, 8); void *up = arg_dptr(&c, 9), *gm = arg_dptr(&c, 10);
+    uint32_t gms = (uint32_t)arg_number(&c, 11); void *gz = arg_dptr(&c, 12); BAIL;
+    if (ub < 22 * sizeof(float)) { napi_throw_range_error(env, NULL, "uniform block needs 22 floats"); return NULL; }
+    return check(env, x, splat_normal_consistency_backward(x, u, kind, z, nm, ms, wt, w, h, up, gm, gms, gz), mk_undefined(env));
+}
 /* splat_densify_cfg from [gradThreshold, scaleThreshold, minOpacity, maxScreenRadius, maxWorldScale, maxSplats, seed (integer < 2^53)] */
 static void fill_densify_cfg(call_t *c, size_t i, splat_densify_cfg *cfg) {
     memset(cfg, 0, sizeof *cfg);
@@ -937,6 +977,8 @@ static napi_value init(napi_env env, napi_value exports) {
         EXPORT(composite_backward_det_workspace_bytes), EXPORT(composite_backward_det), EXPORT(composite_contribution),
         EXPORT(project_ellipsoid_backward_camera), EXPORT(sh_colors_backward_camera),
         EXPORT(image_loss_workspace_bytes), EXPORT(image_loss), EXPORT(image_loss_backward),
+        EXPORT(camera_rays), EXPORT(depth_normals), EXPORT(depth_normals_backward), EXPORT(normal_consistency),
+        EXPORT(normal_consistency_backward),
         EXPORT(adam_step), EXPORT(density_accumulate), EXPORT(densify_plan_workspace_bytes), EXPORT(densify_plan),
         EXPORT(densify_geometry), EXPORT(densify_rows),
         EXPORT(mcmc_sample_workspace_bytes), EXPORT(mcmc_sample), EXPORT(mcmc_apply), EXPORT(mcmc_noise),

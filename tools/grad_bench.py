@@ -78,7 +78,16 @@ apply pass (splat_densify_geometry, three COPY and ten ZERO_NEW splat_densify_ro
 MCMC kernels on the same cloud: splat_mcmc_noise (the per-step one: 56 B per splat, its GB/s beside a device-to-device copy of the
 same planes timed in the same rounds, the line's measured copy ceiling), splat_mcmc_sample in relocate mode (host clock: it
 synchronises) and splat_mcmc_apply of that sample, on logits drawn N(-1, 2.5), 4 % of them below min_opacity = 0.005 (the bench
-scene itself is opaque)."""
+scene itself is opaque).
+
+--normal-loss measures the normal-consistency term instead (one JSON line per config, nothing of the above), on the frame's own
+depth map, blended normal map (render_gaussians(return_depth=True, features=splat_normals(...)): a packed (H, W, 3) image) and
+alpha as the weight: splat_normal_consistency (both launches) and splat_normal_consistency_backward alone (fused_normal_forward,
+fused_normal_backward); the same term written in float32 torch ops on the same tensors, below (torch_normal_loss: 2DGS's
+depth_to_normal with the ray directions and 1 / |d| precomputed outside the timed region; forward, and its torch.autograd
+backward), alternating in the same rounds; and the bytes each fused kernel must move (forward: 4 B of depth, 12 B of map and 4 B
+of weight read per pixel; backward: the same reads, 12 B of map gradient and 4 B of depth gradient written) with the time they
+take at 5.1 TB/s and the rate each achieves."""
 import ctypes as C
 import json
 import os
@@ -142,7 +151,7 @@ if "--features" in sys.argv[1:]:
     at = sys.argv.index("--features")
     feature_ks = [int(v) for v in sys.argv[at + 1].split(",")]
     del sys.argv[at:at + 2]
-argv = [a for a in sys.argv[1:] if a not in ("--depth", "--camera", "--loss", "--optimizer", "--deterministic", "--antialiased", "--importance", "--absgrad")]
+argv = [a for a in sys.argv[1:] if a not in ("--depth", "--camera", "--loss", "--normal-loss", "--optimizer", "--deterministic", "--antialiased", "--importance", "--absgrad")]
 abs_too = "--absgrad" in sys.argv[1:]
 aa_too = "--antialiased" in sys.argv[1:]
 importance_too = "--importance" in sys.argv[1:]
@@ -151,6 +160,7 @@ optimizer_only = "--optimizer" in sys.argv[1:]
 depth_too = "--depth" in sys.argv[1:]
 camera_too = "--camera" in sys.argv[1:]
 loss_only = "--loss" in sys.argv[1:]
+normal_loss_only = "--normal-loss" in sys.argv[1:]
 COPY_RATE = 5.1e12  # bytes / s, read + write: the box's device-to-device copy rate
 
 
@@ -256,6 +266,113 @@ def loss_bench(name, k, rounds, stream):
                       "fused_forward_over_floor": round(med["fused_loss_forward"] / (fwd_bytes / COPY_RATE * 1e3), 2),
                       "fused_backward_bytes": bwd_bytes, "fused_backward_floor_ms": round(bwd_bytes / COPY_RATE * 1e3, 4),
                       "fused_backward_over_floor": round(med["fused_loss_backward"] / (bwd_bytes / COPY_RATE * 1e3), 2)}), flush=True)
+
+
+def torch_normal_loss(nmap, depth, weight, d, inv_len, sigma):
+    """mean(1 - w F . N(depth)) in float32 torch ops: 2DGS's depth_to_normal (points along the rays, central differences, cross
+    product, normalise) and its normal_error.mean(), with the validity rule of include/splat.h.  d (H, W, 3) and inv_len (H, W)
+    are the camera's rays and 1 / |d|."""
+    import torch.nn.functional as F
+    ok = torch.isfinite(depth) & (depth > 0)
+    pts = (torch.where(ok, depth, torch.ones_like(depth)) * inv_len)[..., None] * d
+    ax = pts[1:-1, 2:] - pts[1:-1, :-2]
+    ay = pts[2:, 1:-1] - pts[:-2, 1:-1]
+    valid = ok[1:-1, 2:] & ok[1:-1, :-2] & ok[2:, 1:-1] & ok[:-2, 1:-1]
+    n = sigma * torch.linalg.cross(ay, ax)
+    nn = (n * n).sum(dim=2)
+    valid = valid & torch.isfinite(nn) & (nn > 0)
+    N = torch.where(valid[..., None], n / torch.sqrt(torch.where(valid, nn, torch.ones_like(nn)))[..., None], torch.zeros_like(n))
+    N = F.pad(N.permute(2, 0, 1), (1, 1, 1, 1)).permute(1, 2, 0)
+    return (1.0 - weight * (nmap * N).sum(dim=2)).mean()
+
+
+def normal_loss_bench(name, k, rounds, stream):
+    n, w, h = sr.scene.CONFIGS[name]
+    props, _ = sr.scene.make_scene(n)
+    rng = np.random.default_rng(0)
+    scl = (props[:, 3:4] * 0.5 * np.exp(rng.uniform(-0.3, 0.3, (n, 3)))).astype(np.float32)
+    rot = rng.normal(size=(n, 4)).astype(np.float32)
+    cam = sr.Camera()
+    cam.setAspect(w / h)
+    u = cam.uniforms(w, h)
+    t = lambda a: torch.tensor(np.ascontiguousarray(a, np.float32), device="cuda")  # noqa: E731
+    means, scales, rots, ops, cols = t(props[:, :3]), t(scl), t(rot), t(props[:, 7]), t(props[:, 4:7])
+    with torch.no_grad():
+        _, alpha, depth, nmap = AG.render_gaussians(u, means, scales, rots, ops, colors=cols, width=w, height=h, return_depth=True,
+                                                    features=AG.splat_normals(means, scales, rots, u[16:19]))
+    depth, nmap, alpha = depth.contiguous(), nmap.contiguous(), alpha.contiguous()
+    rays = (C.c_double * 10)()
+    _lib.check(_lib.load().splat_camera_rays(AG._fptr(u), rays))
+    r = np.array(rays[:])
+    ys, xs = np.mgrid[0:h, 0:w].astype(np.float64)
+    d64 = r[0:3] + xs[..., None] * r[3:6] + ys[..., None] * r[6:9]
+    d, inv_len, sigma = t(d64), t(1.0 / np.linalg.norm(d64, axis=2)), float(r[9])
+    cx = AG._context(depth)
+    lib = cx.lib
+    out4, up = torch.empty(4, device="cuda"), torch.ones(1, device="cuda")
+    gmap, gz = torch.empty((h, w, 3), device="cuda"), torch.empty((h, w), device="cuda")
+    zt, ft = depth.clone().requires_grad_(), nmap.clone().requires_grad_()
+    state = {}
+    head = (cx.ctx, AG._fptr(u), _lib.DEPTH_DISTANCE, depth.data_ptr(), nmap.data_ptr(), 3, alpha.data_ptr(), w, h)
+
+    def torch_forward():
+        state["loss"] = torch_normal_loss(ft, zt, alpha, d, inv_len, sigma)
+
+    work = {
+        "fused_normal_forward": lambda: lib.splat_normal_consistency(*head, out4.data_ptr()),
+        "fused_normal_backward": lambda: lib.splat_normal_consistency_backward(*head, up.data_ptr(), gmap.data_ptr(), 3, gz.data_ptr()),
+        "torch_normal_forward": torch_forward,
+        "torch_normal_backward": None,  # (a forward, then its backward alone)
+    }
+
+    def run(kind, calls):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        if kind == "torch_normal_backward":
+            tot = 0.0
+            for _ in range(calls):
+                torch_forward()
+                zt.grad = ft.grad = None
+                e0.record(stream)
+                state["loss"].backward()
+                e1.record(stream)
+                e1.synchronize()
+                tot += e0.elapsed_time(e1)
+            return tot / calls
+        e0.record(stream)
+        for _ in range(calls):
+            work[kind]()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / calls
+
+    for kind in list(work) * 2:
+        run(kind, 3)
+    # the two routes compute the same term: the fused loss beside the torch one, and the largest gradient difference
+    work["fused_normal_forward"]()
+    work["fused_normal_backward"]()
+    torch_forward()
+    zt.grad = ft.grad = None
+    state["loss"].backward()
+    agree = {"fused_loss": float(out4[0]), "torch_loss": float(state["loss"].detach()), "valid_fraction": float(out4[1]),
+             "max_abs_dmap_difference": float((gmap - ft.grad).abs().max()), "max_abs_dmap": float(gmap.abs().max()),
+             "max_abs_ddepth_difference": float((gz - zt.grad).abs().max()), "max_abs_ddepth": float(gz.abs().max())}
+    ts = {kind: [] for kind in work}
+    for _ in range(rounds):
+        for kind in work:
+            ts[kind].append(run(kind, k))
+    med = {kind: sorted(v)[len(v) // 2] for kind, v in ts.items()}
+    fwd_bytes, bwd_bytes = (4 + 12 + 4) * w * h, (4 + 12 + 4 + 12 + 4) * w * h
+    fused, torch_ms = med["fused_normal_forward"] + med["fused_normal_backward"], med["torch_normal_forward"] + med["torch_normal_backward"]
+    print(json.dumps({"config": name, "n": n, "width": w, "height": h, "calls_per_round": k, "rounds": rounds,
+                      **{f"{kind}_ms": round(v, 4) for kind, v in med.items()},
+                      **{f"{kind}_ms_min_max": [round(min(v), 4), round(max(v), 4)] for kind, v in ts.items()},
+                      "fused_normal_ms": round(fused, 4), "torch_normal_ms": round(torch_ms, 4), "torch_over_fused": round(torch_ms / fused, 2),
+                      "fused_forward_bytes": fwd_bytes, "fused_forward_floor_ms": round(fwd_bytes / COPY_RATE * 1e3, 4),
+                      "fused_forward_GBps": round(fwd_bytes / med["fused_normal_forward"] * 1e-6, 1),
+                      "fused_forward_over_floor": round(med["fused_normal_forward"] / (fwd_bytes / COPY_RATE * 1e3), 2),
+                      "fused_backward_bytes": bwd_bytes, "fused_backward_floor_ms": round(bwd_bytes / COPY_RATE * 1e3, 4),
+                      "fused_backward_GBps": round(bwd_bytes / med["fused_normal_backward"] * 1e-6, 1),
+                      "fused_backward_over_floor": round(med["fused_normal_backward"] / (bwd_bytes / COPY_RATE * 1e3), 2), **agree}), flush=True)
 
 
 def optimizer_bench(name, k, rounds, stream):
@@ -452,6 +569,10 @@ stream = torch.cuda.current_stream()
 if loss_only:
     for name in names:
         loss_bench(name, k, rounds, stream)
+    names = []
+if normal_loss_only:
+    for name in names:
+        normal_loss_bench(name, k, rounds, stream)
     names = []
 if optimizer_only:
     for name in names:
