@@ -867,6 +867,91 @@ int splat_normal_consistency_backward(splat_ctx *ctx, const float *uniforms, uin
                                       const void *normal_map, uint32_t map_stride, const void *weight, uint32_t width, uint32_t height,
                                       const void *upstream, void *grad_map, uint32_t grad_map_stride, void *grad_depth);
 
+/* ---- TSDF fusion and mesh extraction: from depth maps to a surface (an extension) ---------------------------------------------
+ * What 2DGS, GOF, RaDe-GS and PGSR do with a finished fit: render its depth from the training cameras, fuse the maps into a
+ * truncated signed distance volume, pull a triangle mesh out of it.  No kernel here uses atomics and every sum has a fixed
+ * order: the same inputs give the same bytes on every run.
+ *
+ * The volume is a grid of nx x ny x nz NODES, dims = {nx, ny, nz}; node (i, j, k) sits at origin + voxel (i, j, k) and has the
+ * linear index i + nx (j + ny k).  LIMITS: 1 <= nx, ny, nz <= 2048 and nx ny nz <= 2^30; anything beyond is refused.  It lives in
+ * caller-owned DEVICE planes: tsdf, one float per node, the signed distance over trunc, in [-1, 1]; weight, one float per node,
+ * 0 = never observed; color, optional, 3 floats per node (node-major).  A fresh volume is weight = 0 everywhere: the tsdf and
+ * colour of a node of weight 0 are never read, so nothing else needs clearing.
+ *
+ * splat_tsdf_integrate fuses one view: uniforms (the block splat_depth_normals reads: VP[r][c] = uniforms[4 c + r], the eye in
+ * [16..18]; [19..21] are not read), depth_kind (SPLAT_DEPTH_DISTANCE, |X - eye|, what the AOV depth of a Gaussian frame is, or
+ * SPLAT_DEPTH_Z, clip w), a width x height depth map, an optional width x height observation weight (obs_weight; NULL: 1), an
+ * optional image (pixel stride image_stride >= 3 floats, the first three read) and max_weight.  Per node X, in binary32, every
+ * quantity formed from (i, j, k) alone (X_c = fma(voxel, i_c, origin_c)), so that the result does not depend on how the grid is
+ * walked:
+ *   1. clip = VP (X, 1), each row fma(VP[r][0], x, fma(VP[r][1], y, fma(VP[r][2], z, VP[r][3])));  skip unless clip.w > 0.
+ *   2. u = (clip.x / clip.w * 0.5 + 0.5) W,  v = (0.5 - 0.5 clip.y / clip.w) H: continuous pixel coordinates, pixel (x, y)'s
+ *      centre at (x + 1/2, y + 1/2), the convention of the rays in "Normals of a depth map".
+ *   3. ix = floor(u), iy = floor(v);  skip unless 0 <= u < W and 0 <= v < H.
+ *   4. D = depth[iy W + ix];  skip unless D is finite and > 0 (an empty pixel of the AOV depth is +inf).
+ *   5. a = obs_weight[iy W + ix], skip unless a > 0;  without a map a = 1.  (a must be finite.)
+ *   6. r = |X - eye| (DISTANCE) or clip.w (Z): the node's own depth in the map's unit.
+ *   7. s = D - r;  skip if s < -trunc (the node is hidden behind the surface by more than the band).
+ *   8. f = min(1, s / trunc),  w' = w + a.
+ *   9. tsdf = (tsdf w + f a) / w';  with both color and image given, color_c = (color_c w + image_c a) / w' likewise.  (w = 0: the
+ *      old value is taken as 0 without reading it.)
+ *  10. weight = max_weight > 0 ? min(w', max_weight) : w'.
+ * A node that is skipped is not written.  The kernel works in bricks of 32 x 4 x 4 nodes and leaves a brick without a load when
+ * its eight corner nodes are all behind the eye, or all safely in front of it and beyond the same side of the screen by more
+ * than a pixel; the margins exceed the binary32 error of steps 1-3, so the cull never changes a byte.
+ *
+ * The mesh is marching tetrahedra on the Kuhn split: the cube with lower corner (i, j, k), i < nx - 1, j < ny - 1, k < nz - 1, is
+ * cut into six tetrahedra, one per permutation pi of the axes, numbered by the lexicographic order of pi: v0 = (0,0,0),
+ * v1 = v0 + e_pi1, v2 = v1 + e_pi2, v3 = (1,1,1).  All six share the body diagonal and every cube face is cut by the diagonal
+ * from its lowest to its highest corner, so neighbouring cubes agree and the surface has no cracks.
+ *   Nodes.     VALID: weight > min_weight (a NaN weight is invalid).  INSIDE: tsdf < 0 (exactly 0, -0 and NaN are outside).
+ *   Cubes.     MESHED only when all eight corners are valid.
+ *   Edges.     Every tetrahedron edge is owned by its lower node and has one of 7 directions, numbered 0-6:
+ *              (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1).
+ *   Vertices.  One on an edge exactly when its endpoints differ in the inside test and at least one of the cubes the edge lies
+ *              in (four for an axis edge, two for a face diagonal, one for the body diagonal) is meshed: no vertex is left
+ *              unreferenced.  Position p0 + t (p1 - p0), t = f0 / (f0 - f1) from the lower endpoint, as fma(t, p1 - p0, p0) per
+ *              component with p = fma(voxel, index, origin); the colour likewise from the endpoints' colours.  A shared vertex is
+ *              one value, not one per triangle.  Ordered by (owning node's linear index, edge number).
+ *   Triangles. Ordered by (cube's lower-corner linear index, tetrahedron number, triangle number).  A tetrahedron with one or
+ *              three inside vertices gives one triangle; with two, a quad: its four vertices are taken in the cyclic order that
+ *              runs counter-clockwise seen from outside, starting at the smallest vertex id q0, and split along the diagonal
+ *              from it: (q0, q1, q2) then (q0, q2, q3).  Every triangle starts at its smallest vertex id and is wound
+ *              counter-clockwise seen from outside: (b - a) x (c - a) points from the tetrahedron's inside vertices towards its
+ *              outside ones.
+ *   Degenerate triangles (two corners at one position) are legal output where a tsdf is exactly 0 beside a negative one (t = 0 or
+ *   t = 1).  The tsdf of a valid node should be finite: a NaN counts as outside and gives NaN positions on its edges.  The mesh is
+ *   a function of the volume's bytes alone.  Vertex ids are 32-bit: a volume whose mesh has 2^32 or more vertices or triangles
+ *   (some 6 10^8 active edges) is beyond this section and is not detected.
+ *
+ * splat_tsdf_mesh_workspace_bytes(nx, ny, nz): the size of the DEVICE workspace count and emit share (10 bytes per node and
+ * some alignment; 0 for dimensions beyond the limits).  splat_tsdf_mesh_count classifies every node and cube into it (per node
+ * a 7-bit mask of active edges and its cube's inside pattern; two splat_scan_u32 scans give the vertex and triangle bases) and
+ * writes the two counts to HOST pointers: it waits for the stream, the one host synchronisation of this section.
+ * splat_tsdf_mesh_emit writes the mesh from the same volume and the workspace count left, repeating none of the classification:
+ * vertices (3 floats each), vertex_colors (3 floats each; optional, needs color), triangles (3 uint32 each); exactly the counted
+ * numbers, nothing beyond them.  The tsdf plane is read again only at the endpoints of active edges.
+ *
+ * All work goes to the ctx's stream.  SPLAT_ERR_INVALID, nothing launched and nothing written: a NULL grid, ctx or required
+ * pointer (color, obs_weight, image and vertex_colors may be NULL; vertex_colors without color is refused); a plane or buffer that
+ * is not 4-byte aligned, a workspace that is not 16-byte aligned or smaller than splat_tsdf_mesh_workspace_bytes; dimensions
+ * beyond the limits; voxel or trunc not finite and > 0; a non-finite origin; an unknown depth_kind; an image with a stride below
+ * 3; width or height 0 or above 65535; max_weight or min_weight negative or not finite. */
+typedef struct splat_tsdf_grid {
+    float origin[3]; /* position of node (0, 0, 0) */
+    float voxel;     /* node spacing */
+    uint32_t dims[3]; /* nx, ny, nz */
+    float trunc;     /* truncation distance, in world units */
+} splat_tsdf_grid;
+int splat_tsdf_integrate(splat_ctx *ctx, const splat_tsdf_grid *grid, void *tsdf, void *weight, void *color, const float *uniforms,
+                         uint32_t depth_kind, const void *depth, const void *obs_weight, const void *image, uint32_t image_stride,
+                         uint32_t width, uint32_t height, float max_weight);
+uint64_t splat_tsdf_mesh_workspace_bytes(uint32_t nx, uint32_t ny, uint32_t nz);
+int splat_tsdf_mesh_count(splat_ctx *ctx, const splat_tsdf_grid *grid, const void *tsdf, const void *weight, float min_weight,
+                          void *workspace, uint64_t workspace_bytes, uint32_t *n_vertices_host, uint32_t *n_triangles_host);
+int splat_tsdf_mesh_emit(splat_ctx *ctx, const splat_tsdf_grid *grid, const void *tsdf, const void *color, const void *workspace,
+                         uint64_t workspace_bytes, void *vertices, void *vertex_colors, void *triangles);
+
 /* ---- Density control and optimiser: what fitting a cloud of 3D Gaussians needs beside the frame (an extension) --------------
  * The parameters are 3DGS's raw ones, contiguous float32 DEVICE planes: means (n, 3), log_scales (n, 3), rotations (n, 4) as
  * (w, x, y, z), unnormalised, opacity_logits (n), sh (n, 3 K) basis-major as splat_sh_colors takes it.  The activations

@@ -68,6 +68,14 @@ class McmcPlanes(C.Structure):
 
 MCMC_RELOCATE, MCMC_ADD = 1, 2
 
+
+class TsdfGrid(C.Structure):
+    """splat_tsdf_grid: a volume of dims = (nx, ny, nz) nodes, node (i, j, k) at origin + voxel (i, j, k), truncated at trunc."""
+    _fields_ = [("origin", C.c_float * 3), ("voxel", C.c_float), ("dims", C.c_uint32 * 3), ("trunc", C.c_float)]
+
+
+TSDF_MAX_DIM, TSDF_MAX_NODES = 2048, 1 << 30  # include/splat.h, "TSDF fusion and mesh extraction": LIMITS
+
 # name -> (restype, argtypes); the single source of truth checked against include/splat.h by
 # tests/test_abi_cpu.py
 _vp, _u32, _sz, _i, _f64 = C.c_void_p, C.c_uint32, C.c_size_t, C.c_int, C.c_double
@@ -140,6 +148,10 @@ SIGNATURES = {
     "splat_depth_normals_backward": (_i, [_vp, C.POINTER(C.c_float), _u32, _vp, _u32, _u32, _vp, _u32, _vp]),
     "splat_normal_consistency": (_i, [_vp, C.POINTER(C.c_float), _u32, _vp, _vp, _u32, _vp, _u32, _u32, _vp]),
     "splat_normal_consistency_backward": (_i, [_vp, C.POINTER(C.c_float), _u32, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _u32, _vp]),
+    "splat_tsdf_integrate": (_i, [_vp, C.POINTER(TsdfGrid), _vp, _vp, _vp, C.POINTER(C.c_float), _u32, _vp, _vp, _vp, _u32, _u32, _u32, C.c_float]),
+    "splat_tsdf_mesh_workspace_bytes": (C.c_uint64, [_u32, _u32, _u32]),
+    "splat_tsdf_mesh_count": (_i, [_vp, C.POINTER(TsdfGrid), _vp, _vp, C.c_float, _vp, C.c_uint64, C.POINTER(_u32), C.POINTER(_u32)]),
+    "splat_tsdf_mesh_emit": (_i, [_vp, C.POINTER(TsdfGrid), _vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp]),
     "splat_adam_step": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _f64, _f64, _f64, _f64, _f64, _f64, _vp]),
     "splat_density_accumulate": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
     "splat_density_accumulate_abs": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),

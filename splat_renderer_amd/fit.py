@@ -127,6 +127,18 @@ absgrad's statistic keeps counting the image's terms only.  The two usual regula
     distortion = (wmq[..., 0] * wmq[..., 2] - wmq[..., 1] ** 2).mean()
 
 Normalise z before squaring it: W Q - M^2 cancels in binary32 where the depth spread inside a pixel is small against the depth.
+
+The surface of a finished fit (include/splat.h, "TSDF fusion and mesh extraction"; tsdf.TsdfVolume), 2DGS's recipe:
+
+    vertices, triangles, colors = fit.extract_mesh(train_cameras, width, height, voxel=0.01)   # device tensors
+    save_mesh_ply(path, vertices.cpu(), triangles.cpu(), colors.cpu())
+
+Under no_grad every camera is rendered with depth, the depth maps are fused into a truncated signed distance volume over the box
+of the means (padded by trunc = 4 voxel; bounds= names another box) with the frame's alpha as the weight of the observation
+where alpha >= alpha_min, and marching tetrahedra pull the zero surface out: indexed, consistently wound, the same bytes on
+every run.  The depth is the blended distance to the splats' centres, so the surface sits where the fit's mass does: a fit
+trained with normal_consistency_loss and the distortion term has flat, thin splats and gives the cleaner surface.  One launch
+per view on top of the render, one host wait for the mesh's size.
 """
 import ctypes as C
 import math
@@ -618,6 +630,37 @@ class GaussianFit:
         plain torch.  They reach splats the frame did not see, so a fit that uses them wants sparse=False."""
         torch = AG._t()
         return opacity_reg * torch.sigmoid(self.opacity_logits).mean() + scale_reg * torch.exp(self.log_scales).mean()
+
+    def extract_mesh(self, cameras, width, height, voxel, trunc=None, bounds=None, alpha_min=0.5, color=True, return_volume=False):
+        """The surface of the fit as a triangle mesh, the way 2DGS gets one (the module's docstring): every camera (Cameras or
+        uniform blocks) is rendered with depth under no_grad, the depth maps are fused into a TsdfVolume of spacing `voxel` with
+        the frame's alpha as the observation weight where alpha >= alpha_min (and nothing elsewhere), and the mesh is extracted.
+        trunc=None: 4 voxel.  bounds=None: the box of the means padded by trunc; else ((x0, y0, z0), (x1, y1, z1)).  Returns
+        (vertices (V, 3) float32, triangles (T, 3) int32[, colors (V, 3)]) on the device (tsdf.TsdfVolume.extract_mesh);
+        return_volume=True appends the volume.  The pending frame of render() / step() is not touched."""
+        torch = AG._t()
+        from .tsdf import TsdfVolume
+        voxel = float(voxel)
+        trunc = 4.0 * voxel if trunc is None else float(trunc)
+        if not (voxel > 0 and trunc > 0):
+            raise SplatError(-1, "extract_mesh: voxel and trunc must be > 0")
+        frame, aux = self._frame, self._aux
+        with torch.no_grad():
+            if bounds is None:
+                if self.n == 0:
+                    raise SplatError(-1, "extract_mesh: the fit has no splats to take bounds from")
+                lo, hi = (self.means.min(dim=0).values - trunc).tolist(), (self.means.max(dim=0).values + trunc).tolist()
+            else:
+                lo, hi = [float(x) for x in bounds[0]], [float(x) for x in bounds[1]]
+            dims = [int(math.ceil((b - a) / voxel)) + 1 for a, b in zip(lo, hi)]
+            vol = TsdfVolume(lo, voxel, dims, trunc, color=color, device=self.means.device)
+            for cam in cameras:
+                rgb, alpha, depth = self.render(cam, width, height, return_depth=True)[:3]
+                weight = torch.where(alpha >= alpha_min, alpha, torch.zeros_like(alpha))
+                vol.integrate(depth, cam, image=rgb if color else None, weight=weight)
+            mesh = vol.extract_mesh()
+        self._frame, self._aux = frame, aux
+        return (*mesh, vol) if return_volume else mesh
 
     def save_ply(self, path):
         """The cloud as a 3D Gaussian splatting PLY file (ply.save_gaussian_ply): the raw parameters, bit for bit; with a 3D

@@ -582,6 +582,50 @@ FN(normal_consistency_backward) { /* normal_consistency's arguments up to H, the
     if (ub < 22 * sizeof(float)) { napi_throw_range_error(env, NULL, "uniform block needs 22 floats"); return NULL; }
     return check(env, x, splat_normal_consistency_backward(x, u, kind, z, nm, ms, wt, w, h, up, gm, gms, gz), mk_undefined(env));
 }
+static void fill_tsdf_grid(call_t *c, size_t i, splat_tsdf_grid *g) { /* [originX, originY, originZ, voxel, nx, ny, nz, trunc] */
+    memset(g, 0, sizeof *g);
+    double v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    bool is = false;
+    napi_is_array(c->env, c->argv[i], &is);
+    if (!is) { c->failed = 1; napi_throw_type_error(c->env, NULL, "expected the TSDF grid as an array of 8 numbers"); return; }
+    for (uint32_t k = 0; k < 8; ++k) {
+        napi_value e;
+        double d;
+        if (napi_get_element(c->env, c->argv[i], k, &e) == napi_ok && napi_get_value_double(c->env, e, &d) == napi_ok) v[k] = d;
+    }
+    g->origin[0] = (float)v[0]; g->origin[1] = (float)v[1]; g->origin[2] = (float)v[2]; g->voxel = (float)v[3];
+    g->dims[0] = (uint32_t)v[4]; g->dims[1] = (uint32_t)v[5]; g->dims[2] = (uint32_t)v[6]; g->trunc = (float)v[7];
+}
+FN(tsdf_integrate) { /* (ctx, grid[8], tsdf, weight, color|null, Float32Array(22), depthKind, depth, obsWeight|null, image|null, imageStride, W, H, maxWeight) */
+    ARGS(14); splat_ctx *x = arg_external(&c, 0); splat_tsdf_grid g; fill_tsdf_grid(&c, 1, &g);
+    void *td = arg_dptr(&c, 2), *wt = arg_dptr(&c, 3), *col = arg_dptr(&c, 4); size_t ub = 0; float *u = arg_hostbuf(&c, 5, &ub);
+    uint32_t kind = (uint32_t)arg_number(&c, 6); void *z = arg_dptr(&c, 7), *ow = arg_dptr(&c, 8), *img = arg_dptr(&c, 9);
+    uint32_t is = (uint32_t)arg_number(&c, 10), w = (uint32_t)arg_number(&c, 11), h = (uint32_t)arg_number(&c, 12); float mw = (float)arg_number(&c, 13); BAIL;
+    if (ub < 22 * sizeof(float)) { napi_throw_range_error(env, NULL, "uniform block needs 22 floats"); return NULL; }
+    return check(env, x, splat_tsdf_integrate(x, &g, td, wt, col, u, kind, z, ow, img, is, w, h, mw), mk_undefined(env));
+}
+FN(tsdf_mesh_workspace_bytes) { /* (nx, ny, nz) -> bytes */
+    ARGS(3); uint32_t nx = (uint32_t)arg_number(&c, 0), ny = (uint32_t)arg_number(&c, 1), nz = (uint32_t)arg_number(&c, 2); BAIL;
+    return mk_number(env, (double)splat_tsdf_mesh_workspace_bytes(nx, ny, nz));
+}
+FN(tsdf_mesh_count) { /* (ctx, grid[8], tsdf, weight, minWeight, workspace, workspaceBytes) -> [vertices, triangles] (waits) */
+    ARGS(7); splat_ctx *x = arg_external(&c, 0); splat_tsdf_grid g; fill_tsdf_grid(&c, 1, &g);
+    void *td = arg_dptr(&c, 2), *wt = arg_dptr(&c, 3); float mw = (float)arg_number(&c, 4); void *ws = arg_dptr(&c, 5);
+    uint64_t wb = (uint64_t)arg_number(&c, 6); BAIL;
+    uint32_t counts[2] = {0, 0};
+    int rc = splat_tsdf_mesh_count(x, &g, td, wt, mw, ws, wb, &counts[0], &counts[1]);
+    if (rc != SPLAT_OK) return check(env, x, rc, NULL);
+    napi_value arr;
+    if (napi_create_array_with_length(env, 2, &arr) != napi_ok) return NULL;
+    for (uint32_t k = 0; k < 2; ++k) napi_set_element(env, arr, k, mk_number(env, (double)counts[k]));
+    return arr;
+}
+FN(tsdf_mesh_emit) { /* (ctx, grid[8], tsdf, color|null, workspace, workspaceBytes, vertices, vertexColors|null, triangles) */
+    ARGS(9); splat_ctx *x = arg_external(&c, 0); splat_tsdf_grid g; fill_tsdf_grid(&c, 1, &g);
+    void *td = arg_dptr(&c, 2), *col = arg_dptr(&c, 3), *ws = arg_dptr(&c, 4); uint64_t wb = (uint64_t)arg_number(&c, 5);
+    void *vx = arg_dptr(&c, 6), *vc = arg_dptr(&c, 7), *tr = arg_dptr(&c, 8); BAIL;
+    return check(env, x, splat_tsdf_mesh_emit(x, &g, td, col, ws, wb, vx, vc, tr), mk_undefined(env));
+}
 /* splat_densify_cfg from [gradThreshold, scaleThreshold, minOpacity, maxScreenRadius, maxWorldScale, maxSplats, seed (integer < 2^53)] */
 static void fill_densify_cfg(call_t *c, size_t i, splat_densify_cfg *cfg) {
     memset(cfg, 0, sizeof *cfg);
@@ -979,6 +1023,7 @@ static napi_value init(napi_env env, napi_value exports) {
         EXPORT(image_loss_workspace_bytes), EXPORT(image_loss), EXPORT(image_loss_backward),
         EXPORT(camera_rays), EXPORT(depth_normals), EXPORT(depth_normals_backward), EXPORT(normal_consistency),
         EXPORT(normal_consistency_backward),
+        EXPORT(tsdf_integrate), EXPORT(tsdf_mesh_workspace_bytes), EXPORT(tsdf_mesh_count), EXPORT(tsdf_mesh_emit),
         EXPORT(adam_step), EXPORT(density_accumulate), EXPORT(densify_plan_workspace_bytes), EXPORT(densify_plan),
         EXPORT(densify_geometry), EXPORT(densify_rows),
         EXPORT(mcmc_sample_workspace_bytes), EXPORT(mcmc_sample), EXPORT(mcmc_apply), EXPORT(mcmc_noise),

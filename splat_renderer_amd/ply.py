@@ -11,6 +11,8 @@ load_point_ply reads what a fit starts from instead: a coloured point cloud, x y
 
 save_gaussian_ply is its exact inverse: the same file 3D Gaussian splatting writes (x y z, zero nx ny nz, f_dc, channel-major
 f_rest, opacity as a logit, log scales, rot), from the arrays load_gaussian_ply returns.
+
+save_mesh_ply writes a triangle mesh (TsdfVolume.extract_mesh's, GaussianFit.extract_mesh's): vertex and face elements, uchar colours.
 """
 import numpy as np
 
@@ -141,6 +143,41 @@ def load_gaussian_ply(path):
         "sh": sh,
         "degree": degree,
     }
+
+
+def save_mesh_ply(path, vertices, triangles, colors=None):
+    """A triangle mesh as a binary_little_endian PLY any mesh viewer reads: element vertex with float x y z (and, with colors,
+    uchar red green blue: round(255 c) clamped to [0, 255]), element face with `property list uchar int vertex_indices`.
+    vertices (V, 3) float32, triangles (T, 3) integers in [0, V), colors (V, 3) in [0, 1] or None: NumPy arrays or anything
+    np.asarray takes (device tensors are downloaded by the caller: TsdfVolume.extract_mesh's results want .cpu() first).
+    Positions and indices are stored bit for bit."""
+    v = np.asarray(vertices, np.float32)
+    t = np.asarray(triangles)
+    if v.ndim != 2 or v.shape[1] != 3 or t.ndim != 2 or t.shape[1] != 3 or t.dtype.kind not in "iu":
+        raise SplatError(-1, "save_mesh_ply: vertices (V, 3) floats and triangles (T, 3) integers are expected")
+    if t.size and (int(t.min()) < 0 or int(t.max()) >= v.shape[0]):
+        raise SplatError(-1, f"save_mesh_ply: a triangle names a vertex outside [0, {v.shape[0]})")
+    fields = [("xyz", "<f4", 3)]
+    header = "ply\nformat binary_little_endian 1.0\n" + f"element vertex {v.shape[0]}\n" + "property float x\nproperty float y\nproperty float z\n"
+    if colors is not None:
+        c = np.asarray(colors, np.float32)
+        if c.shape != v.shape:
+            raise SplatError(-1, f"save_mesh_ply: colors must have shape {v.shape}, not {c.shape}")
+        fields.append(("rgb", "u1", 3))
+        header += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+    header += f"element face {t.shape[0]}\nproperty list uchar int vertex_indices\nend_header\n"
+    vt = np.zeros(v.shape[0], np.dtype(fields))
+    vt["xyz"] = v
+    if colors is not None:
+        with np.errstate(invalid="ignore"):
+            vt["rgb"] = np.clip(np.rint(np.nan_to_num(c.astype(np.float64)) * 255.0), 0, 255).astype(np.uint8)
+    ft = np.zeros(t.shape[0], np.dtype([("n", "u1"), ("idx", "<i4", 3)]))
+    ft["n"] = 3
+    ft["idx"] = t
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(vt.tobytes())
+        f.write(ft.tobytes())
 
 
 def save_gaussian_ply(path, positions, scales, rotations, opacity, sh, log_scales=None, opacity_logits=None):
