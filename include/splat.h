@@ -298,6 +298,8 @@ int splat_validate_tile_order(splat_ctx *ctx, const void *projected, const void 
 #define SPLAT_FOOTPRINT_ISOTROPIC 0
 #define SPLAT_FOOTPRINT_DISC 1
 #define SPLAT_FOOTPRINT_ELLIPSOID 2 /* an anisotropic 3D Gaussian (extension, no reference counterpart): splat_project_ellipsoid */
+#define SPLAT_FOOTPRINT_SURFEL 3    /* a 2D Gaussian surfel (extension; "2D Gaussian surfels" below): splat_project_surfel; the
+                                     * staged composites, the composite backward, the feature channels and splat_composite_surfel_depth take it */
 typedef struct splat_composite_cfg {
     uint32_t mode;       /* SPLAT_COMPOSITE_* */
     uint32_t early_out;  /* 1 = stop a pixel at alpha >= 0.99 (reference :187-190) */
@@ -683,6 +685,62 @@ int splat_project_ellipsoid_backward_aa(splat_ctx *ctx, const float *uniforms, c
 int splat_sh_colors_backward_camera(splat_ctx *ctx, const float *eye3, const void *positions, uint32_t pos_stride_vec4, const void *sh,
                                     uint32_t sh_stride_floats, uint32_t degree, const void *opacity_f32, const void *grad_color_opacity,
                                     uint32_t n, void *grad_sh, void *grad_positions, void *grad_opacity, void *grad_eye);
+
+/* ---- 2D Gaussian surfels (SPLAT_FOOTPRINT_SURFEL; an extension, no reference counterpart; 2DGS, Huang et al. 2024) ---------
+ * A surfel is the ellipsoid's four planes read differently: position xyz, scales (x and y used: standard deviations along the
+ * tangent axes; z and w ignored), rotation quaternion (w, x, y, z) of any non-zero length, colour and opacity.  Its tangent axes
+ * are columns 0 and 1 of R(q), its normal column 2, its half-axes e0 = 3 s.x R[:,0], e1 = 3 s.y R[:,1]: a planar quad, whose
+ * 8-float record {c.x, c.y, B00, B01, B10, B11, q0, q1} is the oriented disc's (splat_project_disc) from the half-axes on.  Per
+ * pixel, (u, v) = B d / (1 - q.d), d = pixel centre - c, is the exact ray-surfel intersection in the surfel's coordinates (no
+ * affine approximation), the record's unit circle is the 3-sigma cut, and alpha = opacity exp(-4.5 (u^2 + v^2)): the
+ * ellipsoid's exponent.  The record is all zeros (culled) when a corner of the 3-sigma quad has clip w <= 0, when det == 0 (an
+ * edge-on surfel, a zero scale), when the quaternion is zero and when anything is not finite.  Binary32, one IEEE operation per
+ * operator in the order stated in csrc/surfel.h.
+ *
+ * splat_project_surfel: splat_project_ellipsoid's arguments and checks.  Writes `records` (n x 8 floats), `projected` (bounds:
+ * the record's exact screen extent; depth |p - eye|, as splat_project: surfels sort by the distance to their centre;
+ * screenRadius half the larger extent), keys and payload exactly as splat_project_ellipsoid, and, when clip_w_out is not NULL
+ * (n floats, 4-byte aligned), the centre's clip w (0 for a culled surfel).
+ *
+ * Forward images need no kernel of their own: a surfel frame is sort -> bin -> splat_composite / splat_composite_aov with
+ * cfg->footprint = SPLAT_FOOTPRINT_SURFEL over these records, which runs the ellipsoid's kernels (they evaluate B10 and q of
+ * every record): the same bits as cfg->footprint = SPLAT_FOOTPRINT_ELLIPSOID over the same records.  splat_composite_aov's depth
+ * stays the blend of one number per splat, as for every footprint.
+ *
+ * The intersection depth.  With c = VP [P; 1] for the plane point P = p + u e0 + v e1 a pixel sees, c.w = cw / (1 - q.d), cw the
+ * centre's clip w: a pixel's depth on surfel i is z_i rd_i, rd = 1 / (1 - q.d), the reciprocal the footprint already forms.
+ * splat_composite_surfel_depth: one walk of the frame's lists writes D = sum w_i z_i rd_i / sum w_i over the entries the pixel
+ * consumed (w_i = T_i alpha_i, the image's own weights and stop), +inf where nothing contributed, to out_depth_f32 (W x H
+ * floats), and 1 - T to out_alpha_f32 when that is not NULL.  z_i = depth_f32[i * depth_stride_floats]: the caller's float, by
+ * default clip_w_out, which makes D the clip w of the blended intersections (SPLAT_DEPTH_Z for splat_depth_normals).  cfg:
+ * footprint SURFEL, FRONT_TO_BACK, early_out = 1, tile_size = 16, PROJECTED records, the whole screen.
+ *
+ * Gradients.  splat_composite_backward and splat_composite_backward_depth take cfg->footprint = SPLAT_FOOTPRINT_SURFEL: the
+ * contract above (the cut and the stop held fixed, float atomic sums ADDED into the outputs, the drawing kernel's operation
+ * order by splat_composite_options), with gradients to all eight record columns.  _depth differentiates the intersection depth
+ * map D above (not the centre blend): grad_depth receives dL/dz_i, and the q and c columns the terms through rd.  Every other
+ * splat_composite_features and splat_composite_features_backward take it too ("Feature channels of a frame", below): the same
+ * contract with the surfel's alpha, the map blended with the surfel image's own weights, the record gradient in all eight
+ * columns.  Every other entry point that takes a cfg and replays a frame refuses SPLAT_FOOTPRINT_SURFEL with SPLAT_ERR_INVALID
+ * and a message naming it (the _det, _abs and _det_abs backwards, splat_composite_contribution): their kernels take B10 = 0
+ * and q = 0, and none runs with q ignored.  The ellipsoid's projector entry points (the _aa projector, the
+ * _camera backwards) take no cfg: a surfel's planes given to them are projected as an ellipsoid's.
+ *
+ * splat_project_surfel_backward: per splat, in float64, the chain of csrc/surfel.h reversed.  grad_records (n x 8 floats) and
+ * grad_clip_w (n floats, or NULL: zeros) in; grad_positions, grad_scales (x and y; z and w exactly 0) and grad_rotations
+ * (through the quaternion's normalisation) OVERWRITTEN, n x 4 floats each.  The cull is the projector's own: a culled surfel
+ * gets exact zeros. */
+int splat_project_surfel(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4, const void *scales,
+                         uint32_t scale_stride_vec4, const void *rotations, uint32_t rot_stride_vec4, uint32_t n, void *projected,
+                         void *records, void *keys, void *payload, uint32_t n_padded, void *clip_w_out);
+int splat_composite_surfel_depth(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4,
+                                 const void *records, const void *tile_indices, const void *tile_counts, const void *tile_offsets,
+                                 uint32_t width, uint32_t height, const void *depth_f32, uint32_t depth_stride_floats, uint32_t n,
+                                 void *out_depth_f32, void *out_alpha_f32);
+int splat_project_surfel_backward(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4,
+                                  const void *scales, uint32_t scale_stride_vec4, const void *rotations, uint32_t rot_stride_vec4,
+                                  uint32_t n, const void *grad_records, const void *grad_clip_w, void *grad_positions, void *grad_scales,
+                                  void *grad_rotations);
 
 /* ---- Contribution of every splat to a frame: hit count, largest and summed blend weight (an extension) --------------------
  * Which splats does a view actually see, and how much?  RadSplat prunes a fit on the largest blend weight a splat reaches in any

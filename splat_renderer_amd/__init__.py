@@ -17,6 +17,7 @@ from .ply import load_gaussian_ply, load_point_ply, save_gaussian_ply, save_mesh
 from .fit import GaussianFit  # noqa: F401
 from .tsdf import TsdfVolume  # noqa: F401  (torch is imported when a volume is first made)
 from .autograd import depth_normals, normal_consistency_loss, splat_normals  # noqa: F401  (torch is imported when one is first called)
+from .autograd import project_surfels, render_surfels, surfel_normals  # noqa: F401  (2D Gaussian surfels: autograd's docstring)
 
 
 def knn_mean_sq_distance(points, return_evaluations=False):

@@ -21,7 +21,7 @@ STAGE_NAMES = ("project", "sort", "bin", "composite", "exchange", "bin_scatter",
 TIMING_COUNT_ENTRIES = 0x80000000  # splat_set_timing_stages: also count the entries a timed frame's composite staged / consumed
 MODE_FRONT_TO_BACK, MODE_REFERENCE_LITERAL = 0, 1
 RECORDS_PROJECTED, RECORDS_COMPACT, RECORDS_DISC48, RECORDS_LIT32 = 0, 1, 2, 3
-FOOTPRINT_ISOTROPIC, FOOTPRINT_DISC, FOOTPRINT_ELLIPSOID = 0, 1, 2
+FOOTPRINT_ISOTROPIC, FOOTPRINT_DISC, FOOTPRINT_ELLIPSOID, FOOTPRINT_SURFEL = 0, 1, 2, 3
 U32_MAX = 0xFFFFFFFF
 DEPTH_DISTANCE, DEPTH_Z = 0, 1  # include/splat.h, SPLAT_DEPTH_*: what a depth map holds (|P - eye|, or clip w)
 
@@ -140,6 +140,9 @@ SIGNATURES = {
     "splat_project_ellipsoid_backward_camera": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp,
                                                      _vp, _vp]),
     "splat_sh_colors_backward_camera": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _vp, _u32, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "splat_project_surfel": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _vp]),
+    "splat_composite_surfel_depth": (_i, [_vp, C.POINTER(CompositeCfg), _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _u32, _vp, _vp]),
+    "splat_project_surfel_backward": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     "splat_image_loss_workspace_bytes": (C.c_uint64, [_u32, _u32]),
     "splat_image_loss": (_i, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, C.c_float, _vp, C.c_uint64, _vp]),
     "splat_image_loss_backward": (_i, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, C.c_float, _vp, C.c_uint64, _vp, _vp, _u32]),

@@ -181,6 +181,32 @@ the map 0.35 ms at K = 3 and 0.37 at K = 8; its backward 1.13 and 1.35 ms beside
 W Q - M^2 is a difference of products of sums: in binary32 it cancels where the spread of depth within a pixel is small against
 the depth itself (z = 100 +- 0.01 leaves no digits), so subtract the near plane and divide by the range before squaring.
 
+2D Gaussian surfels (include/splat.h, "2D Gaussian surfels"; 2DGS): the same planes read as a planar Gaussian, scales x and y along
+columns 0 and 1 of R(rotations), normal column 2.
+
+    rec, aux           = project_surfels(uniforms, means, scales, rotations)                       # rec (n, 8): all eight columns
+    rec, clip_w, aux   = project_surfels(uniforms, means, scales, rotations, return_depth=True)    # clip_w (n,): the centres' clip w
+    rgb, alpha, depth  = rasterize(rec, col, aux, width, height, depths=clip_w)                    # aux says the footprint
+    rgb, alpha, depth  = render_surfels(camera_or_uniforms, means, scales, rotations, opacities, colors=..., width=W, height=H,
+                                        return_depth=True)
+
+The footprint is the exact ray-surfel intersection, (u, v) = B d / (1 - q.d), not the ellipsoid's affine approximation (q = 0), and
+the image is drawn by the ellipsoid's composites over these records.  depth is the intersection depth map sum w z rd / sum w with
+rd = 1 / (1 - q.d) (splat_composite_surfel_depth): with z = clip_w it is the clip w of the points the pixel's ray meets the surfels
+at, so a large flat surfel reports the plane it lies in, not a constant; +inf where nothing contributed.  It is a depth_kind="z"
+map.  Every result is differentiable in means, scales (x, y; a third column gets zeros), rotations, opacities and colours
+(splat_composite_backward / _depth with the surfel footprint, splat_project_surfel_backward).  features= and composite_features
+blend with the surfel image's own weights (the same entry points under the surfel footprint: their kernels evaluate the whole
+record), differentiable in all eight record columns.  project_surfels returns (rec, clip_w, aux), aux last as project_ellipsoids
+does.  Not built for surfels, and refused with SplatError rather than run with q ignored: deterministic=True, absgrad=True,
+contribution(), and a uniforms tensor that requires grad (no camera gradient yet).  The recipe of 2DGS, image + depth + normal map
++ normal consistency:
+
+    eye = uniforms[16:19]
+    rgb, alpha, depth, nmap = render_surfels(cam, means, scales, rotations, opacities, sh=sh, width=W, height=H, return_depth=True,
+                                             features=surfel_normals(rotations, means, eye))
+    loss = photometric_loss(rgb, target) + lam * normal_consistency_loss(nmap, depth, cam, weight=alpha.detach(), depth_kind="z")
+
 torch is imported when a function here is first called, so `import splat_renderer_amd` does not need it.
 """
 import collections
@@ -365,17 +391,23 @@ class ProjectedSplats:
     absgrad: None, or after the backward of a rasterize(absgrad=True) over this projection the (n, 2) sums of |term c.x|,
     |term c.y| (the module's docstring)."""
 
-    def __init__(self, ctx, u, n, projected, keys, payload):
+    def __init__(self, ctx, u, n, projected, keys, payload, footprint=_lib.FOOTPRINT_ELLIPSOID):
         self.ctx, self.u, self.n = ctx, u, n
+        self.footprint = footprint  # (FOOTPRINT_SURFEL: project_surfels' records; rasterize reads it)
         self.absgrad = None
         self.binned = None  # (generation, width, height) of the context's binning of this projection, once there is one
         self.projected, self.keys, self.payload = projected, keys, payload
         self.width, self.height = int(u[20]), int(u[21])
 
 
-def _ellipsoid_cfg():
-    """The one composite configuration the ellipsoid footprint's backward and contribution kernels accept."""
-    return CompositeCfg(_lib.MODE_FRONT_TO_BACK, 1, TILE, 0, _lib.U32_MAX, _lib.RECORDS_PROJECTED, 1, _lib.FOOTPRINT_ELLIPSOID)
+def _ellipsoid_cfg(footprint=_lib.FOOTPRINT_ELLIPSOID):
+    """The one composite configuration the ellipsoid footprint's backward and contribution kernels accept (footprint: the
+    projection's, ProjectedSplats.footprint; the surfel's kernels take the same configuration under their own footprint)."""
+    return CompositeCfg(_lib.MODE_FRONT_TO_BACK, 1, TILE, 0, _lib.U32_MAX, _lib.RECORDS_PROJECTED, 1, footprint)
+
+
+def _is_surfel(aux):
+    return aux.footprint == _lib.FOOTPRINT_SURFEL
 
 
 # Rasterize.backward's entry point: (deterministic, absgrad, a depth gradient arrived) -> its name.  The _det and _abs entry
@@ -456,6 +488,46 @@ def _functions():
                 check(cx.lib.splat_project_ellipsoid_backward_depth(*args, gz_ptr), cx.ctx)
             return None, gp, gs, gr, None, (_like(gu, fctx.u_t) if cam else None), None
 
+    class ProjectSurfel(torch.autograd.Function):
+        """splat_project_surfel and splat_project_surfel_backward.  Returns (rec, [clip_w,] aux)."""
+
+        @staticmethod
+        def forward(fctx, u, means4, scales4, rots, with_depth):
+            cx = _context(means4)
+            n = means4.shape[0]
+            dev = means4.device
+            padded = cx.ensure_sorter(n)
+            rec = torch.empty((n, 8), device=dev, dtype=torch.float32)
+            proj = torch.empty((n, 8), device=dev, dtype=torch.float32)
+            cw = torch.empty(n, device=dev, dtype=torch.float32) if with_depth else None
+            keys = torch.empty(padded, device=dev, dtype=torch.int32)
+            pay = torch.empty(padded, device=dev, dtype=torch.int32)
+            if n:
+                check(cx.lib.splat_project_surfel(cx.ctx, _fptr(u), means4.data_ptr(), 1, scales4.data_ptr(), 1, rots.data_ptr(), 1, n,
+                                                  proj.data_ptr(), rec.data_ptr(), keys.data_ptr(), pay.data_ptr(), padded,
+                                                  cw.data_ptr() if with_depth else None), cx.ctx)
+            fctx.save_for_backward(means4, scales4, rots)
+            fctx.u, fctx.with_depth = u, with_depth
+            fctx.set_materialize_grads(False)
+            aux = ProjectedSplats(cx, u, n, proj, keys, pay, _lib.FOOTPRINT_SURFEL)
+            return (rec, cw, aux) if with_depth else (rec, aux)
+
+        @staticmethod
+        def backward(fctx, grad_rec, *grads):
+            grad_cw = grads[0] if fctx.with_depth else None
+            means4, scales4, rots = fctx.saved_tensors
+            n = means4.shape[0]
+            cx = _context(means4)
+            dev = means4.device
+            g = _cuda_f32(grad_rec, "grad_records", 8) if grad_rec is not None else torch.zeros((n, 8), device=dev, dtype=torch.float32)
+            gw = _cuda_f32(grad_cw.reshape(-1), "grad_clip_w") if grad_cw is not None else None
+            gp, gs, gr = (torch.empty((n, 4), device=dev, dtype=torch.float32) for _ in range(3))
+            if n:
+                check(cx.lib.splat_project_surfel_backward(cx.ctx, _fptr(fctx.u), means4.data_ptr(), 1, scales4.data_ptr(), 1, rots.data_ptr(), 1,
+                                                           n, g.data_ptr(), gw.data_ptr() if gw is not None else None, gp.data_ptr(),
+                                                           gs.data_ptr(), gr.data_ptr()), cx.ctx)
+            return None, gp, gs, gr, None
+
     class ShColors(torch.autograd.Function):
         @staticmethod
         def forward(fctx, eye, means4, sh, degree, opacities, eye_t):
@@ -497,15 +569,19 @@ def _functions():
             alpha = torch.empty((height, width), device=rec.device, dtype=torch.float32)
             gen = cx.bin(aux, width, height)
             idx, cnt, off = cx.lists()
-            cfg = _ellipsoid_cfg()
+            cfg = _ellipsoid_cfg(aux.footprint)
+            surfel = _is_surfel(aux)
             depth = torch.empty((height, width), device=rec.device, dtype=torch.float32) if depths is not None else None
-            aov = _lib.Aov(depth.data_ptr() if depth is not None else None, alpha.data_ptr(), None)
+            aov = _lib.Aov(depth.data_ptr() if depth is not None and not surfel else None, alpha.data_ptr(), None)
             args = (cx.ctx, C.byref(cfg), col.data_ptr(), 1, None, 1, rec.data_ptr(), idx, cnt, off, width, height, None, out.data_ptr(), None,
                     C.byref(aov))
-            if depths is None:
+            if depths is None or surfel:
                 check(cx.lib.splat_composite_aov(*args), cx.ctx)
             else:
                 check(cx.lib.splat_composite_aov_depth(*args, depths.data_ptr(), 1), cx.ctx)
+            if depths is not None and surfel:  # the intersection depth sum w z rd / sum w: a walk of its own over the same lists
+                check(cx.lib.splat_composite_surfel_depth(cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr(), idx, cnt, off, width, height,
+                                                          depths.data_ptr(), 1, aux.n, depth.data_ptr(), None), cx.ctx)
             fctx.save_for_backward(rec, col, depths)
             fctx.set_materialize_grads(False)  # (an unused depth map: None, and the colour-only kernel)
             fctx.aux, fctx.gen, fctx.wh = aux, gen, (width, height)
@@ -539,7 +615,7 @@ def _functions():
             gabs = torch.zeros((n, 2), device=dev, dtype=torch.float32) if absgrad else None
             if n:
                 name = _COMPOSITE_BACKWARD[det, absgrad, with_depth]
-                cfg = _ellipsoid_cfg()
+                cfg = _ellipsoid_cfg(aux.footprint)
                 head, lists = [cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr()], [idx, cnt, off]
                 frame = [width, height, g.data_ptr(), n, grec.data_ptr(), gcol.data_ptr()]
                 if with_depth:
@@ -570,7 +646,7 @@ def _functions():
             n, k = aux.n, feats.shape[1]
             out = torch.empty((height, width, k), device=rec.device, dtype=torch.float32)
             idx, cnt, off = cx.lists_for(aux, width, height)
-            cfg = _ellipsoid_cfg()
+            cfg = _ellipsoid_cfg(aux.footprint)
             check(cx.lib.splat_composite_features(cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr(), idx, cnt, off, width, height,
                                                   feats.data_ptr() if n else None, max(int(feats.stride(0)), k), k, n, out.data_ptr()), cx.ctx)
             fctx.save_for_backward(rec, col, feats)
@@ -590,7 +666,7 @@ def _functions():
             gcol = torch.zeros((n, 4), device=rec.device, dtype=torch.float32)
             gfeat = torch.zeros((n, k), device=rec.device, dtype=torch.float32)
             if n:
-                cfg = _ellipsoid_cfg()
+                cfg = _ellipsoid_cfg(aux.footprint)
                 check(cx.lib.splat_composite_features_backward(cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr(), idx, cnt, off, width,
                                                                height, feats.data_ptr(), max(int(feats.stride(0)), k), k, g.data_ptr(), n,
                                                                grec.data_ptr(), gcol.data_ptr(), gfeat.data_ptr(), k), cx.ctx)
@@ -684,7 +760,7 @@ def _functions():
                                                            gmap.data_ptr(), k, gz.data_ptr()), cx.ctx)
             return gmap, None, gz, None, None, None
 
-    fns = globals()["_fns"] = types.SimpleNamespace(Project=Project, ShColors=ShColors, Rasterize=Rasterize, CompositeFeatures=CompositeFeatures,
+    fns = globals()["_fns"] = types.SimpleNamespace(Project=Project, ProjectSurfel=ProjectSurfel, ShColors=ShColors, Rasterize=Rasterize, CompositeFeatures=CompositeFeatures,
                                                   PhotometricLoss=PhotometricLoss, DepthNormals=DepthNormals, NormalConsistency=NormalConsistency)
     return fns
 
@@ -704,6 +780,76 @@ def project_ellipsoids(uniforms, means, scales, rotations, width=None, height=No
     if not (means4.shape[0] == scales4.shape[0] == rots.shape[0]):
         raise SplatError(-1, "means, scales and rotations must hold the same number of splats")
     return _functions().Project.apply(u, means4, scales4, rots, bool(return_depth), u_t, bool(antialiased))
+
+
+def _refuse_surfel_camera_grad(uniforms, who):
+    """No camera gradient exists for surfels yet: a uniforms tensor that requires grad is refused rather than its gradient dropped
+    silently (as _ray_uniforms does for the normals of a depth map)."""
+    if getattr(uniforms, "requires_grad", False):
+        raise SplatError(-1, f"{who}: the uniforms tensor requires grad, and surfels offer no camera gradient yet; pass uniforms.detach()")
+
+
+def project_surfels(uniforms, means, scales, rotations, width=None, height=None, return_depth=False):
+    """(rec (n, 8) differentiable surfel records {c.x, c.y, B00, B01, B10, B11, q0, q1}, aux: ProjectedSplats of
+    footprint SURFEL).  A surfel is the ellipsoid's planes read as a 2D Gaussian (the module's docstring): scales x and y along
+    columns 0 and 1 of R(rotations), normal column 2; a third scale column is ignored and gets a zero gradient.
+    return_depth=True: (rec, clip_w, aux), aux last as in project_ellipsoids' (rec, depths, aux); clip_w (n,) the differentiable
+    clip w of each centre (0 for a culled surfel): the z_i of rasterize's intersection depth map.  uniforms: a Camera (then width and height are required) or the 22-float block; one
+    that requires grad is refused (SplatError)."""
+    _refuse_surfel_camera_grad(uniforms, "project_surfels")
+    u = _uniforms(uniforms, width, height)
+    means4 = _cuda_f32(_vec4(means, "means", 1.0), "means", 4)
+    if isinstance(scales, _t().Tensor) and scales.dim() == 2 and scales.shape[1] == 2:
+        scales = _t().cat([scales, scales.new_zeros((scales.shape[0], 2))], dim=1)
+    scales4 = _cuda_f32(_vec4(scales, "scales"), "scales", 4)
+    rots = _cuda_f32(rotations, "rotations", 4)
+    if not (means4.shape[0] == scales4.shape[0] == rots.shape[0]):
+        raise SplatError(-1, "means, scales and rotations must hold the same number of splats")
+    return _functions().ProjectSurfel.apply(u, means4, scales4, rots, bool(return_depth))
+
+
+def surfel_normals(rotations, means, eye):
+    """(n, 3): each surfel's normal, column 2 of R(q) of the normalised quaternion (w, x, y, z), flipped so that it faces the eye;
+    torch ops, any device, differentiable in rotations (the sign held fixed).  Pass it as render_surfels' features for 2DGS's
+    normal map."""
+    torch = _t()
+    q = rotations / rotations.norm(dim=1, keepdim=True)
+    r, x, y, z = q.unbind(1)
+    axis = torch.stack([2 * (x * z + r * y), 2 * (y * z - r * x), 1 - 2 * (x * x + y * y)], dim=1)
+    eye = torch.as_tensor(eye, dtype=means.dtype, device=means.device).reshape(3)
+    return torch.where(((means[:, :3] - eye) * axis).sum(dim=1, keepdim=True) > 0, -axis, axis)
+
+
+def render_surfels(camera_or_uniforms, means, scales, rotations, opacities, colors=None, sh=None, width=None, height=None, degree=None,
+                   return_depth=False, features=None, return_aux=False):
+    """render_gaussians' surfel twin: project_surfels, the colour (sh_colors when `sh` is given, else cat(colors, opacities)),
+    rasterize.  Returns (rgb (H, W, 3), alpha (H, W)); return_depth=True: (rgb, alpha, depth (H, W)), the ray-surfel
+    intersection depth map sum w z rd / sum w in clip w (depth_kind="z" for depth_normals and normal_consistency_loss), +inf where
+    nothing contributed; features ((n, K) or (n,)): rasterize's, blended with the surfel image's own weights, the map after depth:
+    (rgb, alpha[, depth], feat[, aux]); return_aux=True appends the frame's ProjectedSplats."""
+    if width is None or height is None:
+        raise SplatError(-1, "render_surfels needs width and height")
+    _refuse_surfel_camera_grad(camera_or_uniforms, "render_surfels")
+    for name, t in (("means", means), ("scales", scales), ("rotations", rotations), ("opacities", opacities)):
+        _cuda_f32(t, name)
+    u = _uniforms(camera_or_uniforms, width, height)
+    out = project_surfels(u, means, scales, rotations, return_depth=return_depth)  # (rec, [clip_w,] aux)
+    rec, aux = out[0], out[-1]
+    depths = out[1] if return_depth else None
+    n = aux.n
+    if sh is not None:
+        k = sh.reshape(n, -1).shape[1] // 3
+        deg = {1: 0, 4: 1, 9: 2, 16: 3}.get(k) if degree is None else degree
+        if deg is None:
+            raise SplatError(-1, f"sh must hold 3 (degree + 1)^2 floats per splat, not {3 * k}")
+        col = sh_colors(u[16:19], means, sh, deg, opacities)
+    elif colors is not None:
+        _cuda_f32(colors, "colors", 3)
+        col = _t().cat([colors, opacities.reshape(-1, 1)], dim=1)
+    else:
+        raise SplatError(-1, "render_surfels needs colors or sh")
+    out = rasterize(rec, col, aux, width, height, depths=depths, features=features)
+    return (*out, aux) if return_aux else out
 
 
 def sh_colors(eye, means, sh, degree, opacities):
@@ -736,6 +882,9 @@ def rasterize(rec, col, aux, width=None, height=None, depths=None, deterministic
     width = aux.width if width is None else int(width)
     height = aux.height if height is None else int(height)
     _refuse_deterministic_features(deterministic, features, "rasterize")
+    if _is_surfel(aux) and (deterministic or absgrad):
+        raise SplatError(-1, "rasterize: deterministic=True and absgrad=True are not built for surfels (their fixed-order and absolute "
+                             "sums take q = 0 of every record)")
     rec_c = _cuda_f32(rec, "rec", 8)
     col_c = _cuda_f32(col, "col", 4)
     if rec_c.shape[0] != aux.n or col_c.shape[0] != aux.n:
@@ -872,7 +1021,7 @@ def contribution(rec, col, aux, width=None, height=None, pixel_weight=None, min_
         cx = aux.ctx
         cx.bin(aux, width, height)
         idx, cnt, off = cx.lists()
-        cfg = _ellipsoid_cfg()
+        cfg = _ellipsoid_cfg(aux.footprint)
         check(cx.lib.splat_composite_contribution(cx.ctx, C.byref(cfg), col_c.data_ptr(), 1, rec_c.data_ptr(), idx, cnt, off, width, height,
                                                   pw.data_ptr() if pw is not None else None, float(min_weight), n, out.hits.data_ptr(),
                                                   out.weight_max.data_ptr(), out.weight_sum.data_ptr()), cx.ctx)

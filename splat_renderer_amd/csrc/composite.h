@@ -140,6 +140,9 @@ constexpr float DISC_EXP2_SCALE = -4.508422002777011f;
 constexpr float ELLIPSOID_EXP2_SCALE = -6.492127684000335f;
 // The exponent scale is a property of the footprint; the disc-record kernels take it at compile time (ELL: the ellipsoid's)
 template <bool ELL> struct FootprintExp2 { static constexpr float scale = ELL ? ELLIPSOID_EXP2_SCALE : DISC_EXP2_SCALE; };
+// The footprints whose records the ELL instantiations draw: the ellipsoid's (q = 0) and the surfel's (surfel.h: full disc
+// records with the ellipsoid's exponent scale and alpha = opacity g; the forward kernels evaluate B10 and q of every record)
+inline bool footprint_is_ell(uint32_t footprint) { return footprint == SPLAT_FOOTPRINT_ELLIPSOID || footprint == SPLAT_FOOTPRINT_SURFEL; }
 
 // DISC: the footprint is SequentialRenderer's oriented disc (disc.h) — per entry the 32-byte disc record and
 // the lit colour are staged, a pixel is inside when u^2 + v^2 <= 1 with (u,v) = B*d / (1 - q.d); the

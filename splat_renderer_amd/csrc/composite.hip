@@ -67,7 +67,7 @@ extern "C" int splat_composite(splat_ctx *ctx, const splat_composite_cfg *cfg, c
 // disc records are the projector's 32-byte ones (splat_project_disc) or 48-byte exchange records (taken at its
 // word this pair would read idx * 48 out of an n * 32 allocation)
 static bool lit_disc_records(const splat_composite_cfg *cfg) {
-    return cfg && (cfg->footprint == SPLAT_FOOTPRINT_DISC || cfg->footprint == SPLAT_FOOTPRINT_ELLIPSOID) &&
+    return cfg && (cfg->footprint == SPLAT_FOOTPRINT_DISC || footprint_is_ell(cfg->footprint)) &&
            cfg->record_format == SPLAT_RECORDS_LIT32;
 }
 
@@ -149,7 +149,7 @@ int composite_launch(splat_ctx *ctx, const splat_composite_cfg *cfg, const Compo
     ARG_CHECK(ctx, a.color_stride_vec4 >= 1 && a.normal_stride_vec4 >= 1);
     ARG_CHECK(ctx, a.out_rgba8 || a.out_rgba32f);
     ARG_CHECK(ctx, (((uintptr_t)a.color_opacity | (uintptr_t)a.normals | (uintptr_t)a.projected | (uintptr_t)a.out_rgba32f) & 15) == 0);
-    ARG_CHECK(ctx, cfg->prelit <= 1 && cfg->footprint <= SPLAT_FOOTPRINT_ELLIPSOID);
+    ARG_CHECK(ctx, cfg->prelit <= 1 && cfg->footprint <= SPLAT_FOOTPRINT_SURFEL);
     // the oriented disc is SequentialRenderer's footprint: nearest-on-top "over" is its only blend, and its
     // records are the projector's 32-byte disc records.  The ellipsoid's records are disc records (ellipsoid.h) under the
     // same rules, and have no 48-byte exchange form: no band frame exists for them
@@ -241,7 +241,7 @@ int composite_launch(splat_ctx *ctx, const splat_composite_cfg *cfg, const Compo
             } else return false;
         },
         OneOf<SPLAT_COMPOSITE_FRONT_TO_BACK, SPLAT_COMPOSITE_REFERENCE_LITERAL>{(int)cfg->mode}, cfg->early_out != 0, p.disc != 0, lit32 && !p.disc,
-        aov != nullptr, cfg->footprint == SPLAT_FOOTPRINT_ELLIPSOID);
+        aov != nullptr, footprint_is_ell(cfg->footprint));
     if (!ok) return ctx_fail(ctx, SPLAT_ERR_INVALID, "k_composite: no kernel for this footprint, record format, blend and outputs");
     report.launched = hipPeekAtLastError() == hipSuccess;
     LAUNCH_CHECK(ctx, "k_composite");

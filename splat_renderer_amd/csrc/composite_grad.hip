@@ -620,6 +620,11 @@ extern "C" int splat_composite_backward(splat_ctx *ctx, const splat_composite_cf
                                         const void *records, const void *tile_indices, const void *tile_counts, const void *tile_offsets,
                                         uint32_t width, uint32_t height, const void *grad_rgba32f, uint32_t n, void *grad_records,
                                         void *grad_color_opacity) {
+    if (ctx && cfg && cfg->footprint == SPLAT_FOOTPRINT_SURFEL) { // (surfel.hip: the whole record's alpha and gradient)
+        SurfelBackwardCall a{};
+        BACKWARD_ARGS(a);
+        return surfel_composite_backward(ctx, a);
+    }
     BackwardArgs a{};
     BACKWARD_ARGS(a);
     return a.launch(ctx);
@@ -630,6 +635,12 @@ extern "C" int splat_composite_backward_depth(splat_ctx *ctx, const splat_compos
                                               const void *tile_offsets, uint32_t width, uint32_t height, const void *grad_rgba32f, uint32_t n,
                                               void *grad_records, void *grad_color_opacity, const void *depth_f32, uint32_t depth_stride_floats,
                                               const void *grad_depth_f32, void *grad_depth) {
+    if (ctx && cfg && cfg->footprint == SPLAT_FOOTPRINT_SURFEL) {
+        SurfelBackwardCall a{};
+        BACKWARD_ARGS(a), DEPTH_ARGS(a);
+        a.depth = true;
+        return surfel_composite_backward(ctx, a);
+    }
     BackwardArgs a{};
     BACKWARD_ARGS(a), DEPTH_ARGS(a);
     a.depth = true;

@@ -910,7 +910,7 @@ int composite_px_launch(splat_ctx *ctx, const splat_composite_cfg *cfg, Composit
             } else return false;
         },
         eo, p.lit32 && !p.disc, p.consumed != nullptr, OneOf<1, 2>{ahead == 2 ? 2 : 1}, p.disc != 0, want_aov,
-        cfg->footprint == SPLAT_FOOTPRINT_ELLIPSOID);
+        footprint_is_ell(cfg->footprint));
     if (!ok) return ctx_fail(ctx, SPLAT_ERR_INVALID, "k_composite_px: no kernel for this footprint and record format");
     *launched = hipPeekAtLastError() == hipSuccess; // (only a launch that went out carries the frame's report)
     LAUNCH_CHECK(ctx, "k_composite_px");

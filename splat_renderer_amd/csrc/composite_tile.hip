@@ -58,7 +58,7 @@ int composite_tile_launch(splat_ctx *ctx, const splat_composite_cfg *cfg, const 
             } else return false;
         },
         OneOf<SPLAT_COMPOSITE_FRONT_TO_BACK, SPLAT_COMPOSITE_REFERENCE_LITERAL>{(int)cfg->mode}, cfg->early_out != 0, p.disc != 0,
-        p.lit32 && !p.disc, want_aov, cfg->footprint == SPLAT_FOOTPRINT_ELLIPSOID);
+        p.lit32 && !p.disc, want_aov, footprint_is_ell(cfg->footprint));
     if (!ok) return ctx_fail(ctx, SPLAT_ERR_INVALID, "k_composite_tile: no kernel for this footprint, record format, blend and outputs");
     *launched = hipPeekAtLastError() == hipSuccess;
     LAUNCH_CHECK(ctx, "k_composite_tile");

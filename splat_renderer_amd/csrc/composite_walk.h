@@ -119,13 +119,20 @@ struct FrameArgs {
 
     // The cfg restrictions (who: the family's name in their error), the screen limits, the whole screen's tile rows and the
     // colour stride; then the frame's part of p (its gradient pointers are the backward's to set) and the screen's tile rows.
-    int setup(splat_ctx *ctx, const char *who, BackParams &p, uint32_t &nty) const {
+    // surfel: the caller's kernels evaluate the whole record (surfel.hip) and take SPLAT_FOOTPRINT_SURFEL, and only it; every
+    // other family refuses that footprint by name (its kernels take B10 = 0, q = 0: entry_alpha).
+    int setup(splat_ctx *ctx, const char *who, BackParams &p, uint32_t &nty, bool surfel = false) const {
         if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
         ARG_CHECK(ctx, cfg != nullptr);
-        if (cfg->footprint != SPLAT_FOOTPRINT_ELLIPSOID || cfg->mode != SPLAT_COMPOSITE_FRONT_TO_BACK || cfg->early_out != 1 ||
+        if (cfg->footprint == SPLAT_FOOTPRINT_SURFEL && !surfel)
+            return ctx_fail(ctx, SPLAT_ERR_INVALID,
+                            (std::string(who) + ": not built for SPLAT_FOOTPRINT_SURFEL (this entry point's kernels take B10 = 0 and q = 0 "
+                                                "of every record; a surfel's are not)").c_str());
+        if (cfg->footprint != (surfel ? SPLAT_FOOTPRINT_SURFEL : SPLAT_FOOTPRINT_ELLIPSOID) || cfg->mode != SPLAT_COMPOSITE_FRONT_TO_BACK || cfg->early_out != 1 ||
             cfg->tile_size != GT || cfg->record_format != SPLAT_RECORDS_PROJECTED)
             return ctx_fail(ctx, SPLAT_ERR_INVALID,
-                            (std::string(who) + ": footprint ELLIPSOID, FRONT_TO_BACK, early_out = 1, tile_size = 16 and PROJECTED records only").c_str());
+                            (std::string(who) + (surfel ? ": footprint SURFEL" : ": footprint ELLIPSOID") +
+                             ", FRONT_TO_BACK, early_out = 1, tile_size = 16 and PROJECTED records only").c_str());
         ARG_CHECK(ctx, width >= 1 && height >= 1 && width <= 65535u * GT && height <= 65535u * GT);
         nty = div_up(height, GT);
         ARG_CHECK(ctx, cfg->tile_row0 == 0 && cfg->tile_row1 >= nty); // the whole screen: no strict band
@@ -144,6 +151,20 @@ struct FrameArgs {
 };
 
 } // namespace
+
+// surfel.hip: splat_composite_backward / _depth with cfg->footprint = SPLAT_FOOTPRINT_SURFEL (composite_grad.hip's two entry
+// points hand their arguments over under include/splat.h's names; depth: the _depth entry point, with its four arguments)
+struct SurfelBackwardCall {
+    const splat_composite_cfg *cfg;
+    const void *color_opacity, *records, *tile_indices, *tile_counts, *tile_offsets, *grad_rgba32f;
+    uint32_t color_stride_vec4, width, height, n;
+    void *grad_records, *grad_color_opacity;
+    const void *depth_f32, *grad_depth_f32;
+    uint32_t depth_stride_floats;
+    void *grad_depth;
+    bool depth;
+};
+int surfel_composite_backward(splat_ctx *ctx, const SurfelBackwardCall &c);
 
 // The frame's arguments of every entry point, by name (their parameter names are FrameArgs' field names)
 #define FRAME_ARGS(a)                                                                                                          \

@@ -51,22 +51,13 @@ __device__ __forceinline__ bool disc_bounds(const DiscRecord &r, float4 &bounds)
     return ok;
 }
 
-// The record of one splat.  m = view-projection (column-major), w/h = screen size, pr = (pos, radius),
-// n = normal.  Same operation order as oracle.c's disc_record.
-__device__ __forceinline__ DiscRecord disc_record(const float *m, float w, float h, float4 pr, float4 n) {
+// The record of a planar quad with centre pr.xyz and world-space half-axes e0, e1: what the oriented disc (disc_record) and
+// the 2D Gaussian surfel (surfel.h) share.  cw (optional): the centre's clip w, written when the record is not culled.
+__device__ __forceinline__ DiscRecord disc_record_axes(const float *m, float w, float h, float4 pr, float e0x, float e0y, float e0z, float e1x,
+                                                       float e1y, float e1z, float *cw = nullptr) {
 #pragma clang fp contract(off)
     DiscRecord zero = {make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0)};
-    // computeTangent :68-71, bitangent :96
-    const bool steep = fabsf(n.y) > 0.9f;
-    const float ux = steep ? 1.0f : 0.0f, uy = steep ? 0.0f : 1.0f, uz = 0.0f;
-    float tx = uy * n.z - uz * n.y, ty = uz * n.x - ux * n.z, tz = ux * n.y - uy * n.x; // cross(up, n)
-    const float tl = sqrtf((tx * tx + ty * ty) + tz * tz);
-    const float itl = 1.0f / tl; // normalize(): one reciprocal, three products
-    tx *= itl; ty *= itl; tz *= itl;
-    const float bx = n.y * tz - n.z * ty, by = n.z * tx - n.x * tz, bz = n.x * ty - n.y * tx; // cross(n, t)
-    // half-axes of the quad in world space (:107-109) and their clip-space images (x, y, w rows)
-    const float r = pr.w;
-    const float e0x = tx * r, e0y = ty * r, e0z = tz * r, e1x = bx * r, e1y = by * r, e1z = bz * r;
+    // the half-axes' clip-space images (x, y, w rows)
     const float ctx = (m[0] * e0x + m[4] * e0y) + m[8] * e0z;
     const float cty = (m[1] * e0x + m[5] * e0y) + m[9] * e0z;
     const float ctw = (m[3] * e0x + m[7] * e0y) + m[11] * e0z;
@@ -92,5 +83,23 @@ __device__ __forceinline__ DiscRecord disc_record(const float *m, float w, float
     o.a = make_float4(scx, scy, a11 * k, (-a01) * k);
     o.b = make_float4((-a10) * k, a00 * k, (a11 * ctw - a10 * cbw) * idet, (a00 * cbw - a01 * ctw) * idet);
     if (!disc_finite4(o.a.z, o.a.w, o.b.x, o.b.y) || !disc_finite4(o.a.x, o.a.y, o.b.z, o.b.w)) return zero;
+    if (cw) *cw = cpw;
     return o;
+}
+
+// The record of one splat.  m = view-projection (column-major), w/h = screen size, pr = (pos, radius),
+// n = normal.  Same operation order as oracle.c's disc_record.
+__device__ __forceinline__ DiscRecord disc_record(const float *m, float w, float h, float4 pr, float4 n) {
+#pragma clang fp contract(off)
+    // computeTangent :68-71, bitangent :96
+    const bool steep = fabsf(n.y) > 0.9f;
+    const float ux = steep ? 1.0f : 0.0f, uy = steep ? 0.0f : 1.0f, uz = 0.0f;
+    float tx = uy * n.z - uz * n.y, ty = uz * n.x - ux * n.z, tz = ux * n.y - uy * n.x; // cross(up, n)
+    const float tl = sqrtf((tx * tx + ty * ty) + tz * tz);
+    const float itl = 1.0f / tl; // normalize(): one reciprocal, three products
+    tx *= itl; ty *= itl; tz *= itl;
+    const float bx = n.y * tz - n.z * ty, by = n.z * tx - n.x * tz, bz = n.x * ty - n.y * tx; // cross(n, t)
+    // half-axes of the quad in world space (:107-109)
+    const float r = pr.w;
+    return disc_record_axes(m, w, h, pr, tx * r, ty * r, tz * r, bx * r, by * r, bz * r);
 }

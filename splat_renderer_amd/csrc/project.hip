@@ -15,6 +15,7 @@
 #include "block_scan.h"
 #include "disc.h"
 #include "ellipsoid.h"
+#include "surfel.h"
 #include "shade.h"
 
 struct FrameUniforms {
@@ -531,6 +532,40 @@ __global__ __launch_bounds__(256) void k_project_ellipsoid_aa(FrameUniforms u, c
     if (aa.color_out) aa.color_out[i] = make_float4(col.x, col.y, col.z, col.w * rho);
 }
 
+// The surfel projector (splat_project_surfel; surfel.h): project_one's DISC branch over surfel_record — the record, the
+// ProjectedSplat (disc_bounds, depth |p - eye|, half the larger extent), key and payload — and beside them the centre's clip w
+// (the z_i of the intersection-depth map; 0 for a culled surfel).  One thread per splat.
+__global__ __launch_bounds__(256) void k_project_surfel(FrameUniforms u, const float4 *__restrict__ pos, uint32_t stride_vec4, uint32_t n,
+                                                        uint32_t n_padded, float4 *__restrict__ projected, float4 *__restrict__ records,
+                                                        uint32_t *__restrict__ keys, uint32_t *__restrict__ payload, EllIO ell,
+                                                        float *__restrict__ clip_w) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) {
+        if (keys && i < n_padded) { // extract-depth-keys.wgsl:46-50
+            keys[i] = 0xffffffffu;
+            payload[i] = 0xffffffffu;
+        }
+        return;
+    }
+    const float4 pr = pos[(size_t)i * stride_vec4];
+    const float4 scl = ell.scales[(size_t)i * ell.scale_stride], rot = ell.rotations[(size_t)i * ell.rot_stride];
+    float cw;
+    const DiscRecord d = surfel_record(u.m, u.w, u.h, pr, scl, rot, &cw);
+    records[(size_t)i * 2] = d.a;
+    records[(size_t)i * 2 + 1] = d.b;
+    const float dx = pr.x - u.eye[0], dy = pr.y - u.eye[1], dz = pr.z - u.eye[2];
+    const float depth = sqrtf((dx * dx + dy * dy) + dz * dz); // SplatProjector.ts:77: surfels sort by centre distance, as 2DGS does
+    float4 a;
+    disc_bounds(d, a);
+    projected[(size_t)i * 2] = a;
+    projected[(size_t)i * 2 + 1] = make_float4(depth, 0.5f * fmaxf(a.z - a.x, a.w - a.y), __uint_as_float(i), 0.0f);
+    if (keys) {
+        keys[i] = depth_key(depth);
+        payload[i] = i;
+    }
+    if (clip_w) clip_w[i] = cw;
+}
+
 // splat_sampling_rate_max: one thread per splat, no atomics.  c = VP [p; 1] and the screen centre exactly as to_screen();
 // a splat in front of `near` and inside the screen widened by `margin` of its size on every side raises its rate to
 // focal_px / c.w (Mip-Splatting's compute_3D_filter, one camera per call).  A NaN anywhere fails a comparison: unchanged.
@@ -791,6 +826,29 @@ int splat_project_ellipsoid_aa(splat_ctx *ctx, const float *uniforms, const void
     a.rho_out = (float *)rho_out, a.color_opacity = color_opacity, a.color_stride_vec4 = color_stride_vec4;
     a.color_opacity_out = color_opacity_out, a.timed = true;
     return project_ellipsoid_aa_launch(ctx, a);
+}
+
+int splat_project_surfel(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4, const void *scales,
+                         uint32_t scale_stride_vec4, const void *rotations, uint32_t rot_stride_vec4, uint32_t n, void *projected, void *records,
+                         void *keys, void *payload, uint32_t n_padded, void *clip_w_out) {
+    if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
+    ARG_CHECK(ctx, uniforms && (n == 0 || (positions && scales && rotations && projected && records)));
+    ARG_CHECK(ctx, pos_stride_vec4 >= 1 && scale_stride_vec4 >= 1 && rot_stride_vec4 >= 1);
+    ARG_CHECK(ctx, (keys == nullptr) == (payload == nullptr));
+    ARG_CHECK(ctx, keys == nullptr || n_padded >= n);
+    ARG_CHECK(ctx, (((uintptr_t)positions | (uintptr_t)scales | (uintptr_t)rotations | (uintptr_t)projected | (uintptr_t)records) & 15) == 0 &&
+                       ((uintptr_t)clip_w_out & 3) == 0);
+    const uint32_t work = keys ? n_padded : n; // (n == 0 with keys only pads them)
+    if (work == 0) return SPLAT_OK;
+    FrameUniforms u;
+    load_uniforms(u, uniforms);
+    const EllIO ell = {(const float4 *)scales, scale_stride_vec4, (const float4 *)rotations, rot_stride_vec4};
+    stage_begin(ctx, SPLAT_STAGE_PROJECT);
+    hipLaunchKernelGGL(k_project_surfel, dim3(div_up(work, 256)), dim3(256), 0, ctx->stream, u, (const float4 *)positions, pos_stride_vec4, n, work,
+                       (float4 *)projected, (float4 *)records, (uint32_t *)keys, (uint32_t *)payload, ell, (float *)clip_w_out);
+    LAUNCH_CHECK(ctx, "k_project_surfel");
+    stage_end(ctx, SPLAT_STAGE_PROJECT);
+    return SPLAT_OK;
 }
 
 int splat_sampling_rate_max(splat_ctx *ctx, const float *uniforms, float focal_px, float near, float margin, const void *positions,

@@ -369,6 +369,31 @@ FN(project_ellipsoid_aa) { /* project_ellipsoid's arguments, then rho|null, colo
     if (ub < 22 * sizeof(float)) { napi_throw_range_error(env, NULL, "uniform block needs 22 floats"); return NULL; }
     return check(env, x, splat_project_ellipsoid_aa(x, u, pos, ps, scl, ss, rot, rs, n, proj, rec, keys, pay, np, rho, co, cs, coo), mk_undefined(env));
 }
+FN(project_surfel) { /* project_ellipsoid's arguments, then clipW|null */
+    ARGS(15); splat_ctx *x = arg_external(&c, 0); size_t ub = 0; float *u = arg_hostbuf(&c, 1, &ub);
+    void *pos = arg_dptr(&c, 2); uint32_t ps = (uint32_t)arg_number(&c, 3); void *scl = arg_dptr(&c, 4); uint32_t ss = (uint32_t)arg_number(&c, 5);
+    void *rot = arg_dptr(&c, 6); uint32_t rs = (uint32_t)arg_number(&c, 7), n = (uint32_t)arg_number(&c, 8);
+    void *proj = arg_dptr(&c, 9), *rec = arg_dptr(&c, 10), *keys = arg_dptr(&c, 11), *pay = arg_dptr(&c, 12); uint32_t np = (uint32_t)arg_number(&c, 13);
+    void *cw = arg_dptr(&c, 14); BAIL;
+    if (ub < 22 * sizeof(float)) { napi_throw_range_error(env, NULL, "uniform block needs 22 floats"); return NULL; }
+    return check(env, x, splat_project_surfel(x, u, pos, ps, scl, ss, rot, rs, n, proj, rec, keys, pay, np, cw), mk_undefined(env));
+}
+FN(composite_surfel_depth) { /* (ctx, cfg[8], colorOpacity, cStride, records, indices, counts, offsets, W, H, depth, depthStrideFloats, n, outDepth, outAlpha|null) */
+    ARGS(15); splat_ctx *x = arg_external(&c, 0); splat_composite_cfg cfg; fill_cfg(&c, 1, &cfg);
+    void *col = arg_dptr(&c, 2); uint32_t cs = (uint32_t)arg_number(&c, 3); void *rec = arg_dptr(&c, 4);
+    void *idx = arg_dptr(&c, 5), *cnt = arg_dptr(&c, 6), *off = arg_dptr(&c, 7);
+    uint32_t w = (uint32_t)arg_number(&c, 8), h = (uint32_t)arg_number(&c, 9); void *z = arg_dptr(&c, 10);
+    uint32_t zs = (uint32_t)arg_number(&c, 11), n = (uint32_t)arg_number(&c, 12); void *od = arg_dptr(&c, 13), *oa = arg_dptr(&c, 14); BAIL;
+    return check(env, x, splat_composite_surfel_depth(x, &cfg, col, cs, rec, idx, cnt, off, w, h, z, zs, n, od, oa), mk_undefined(env));
+}
+FN(project_surfel_backward) { /* (ctx, Float32Array(22), positions, posStride, scales, scaleStride, rotations, rotStride, n, gradRecords, gradClipW|null, gradPositions, gradScales, gradRotations) */
+    ARGS(14); splat_ctx *x = arg_external(&c, 0); size_t ub = 0; float *u = arg_hostbuf(&c, 1, &ub);
+    void *pos = arg_dptr(&c, 2); uint32_t ps = (uint32_t)arg_number(&c, 3); void *scl = arg_dptr(&c, 4); uint32_t ss = (uint32_t)arg_number(&c, 5);
+    void *rot = arg_dptr(&c, 6); uint32_t rs = (uint32_t)arg_number(&c, 7), n = (uint32_t)arg_number(&c, 8);
+    void *grec = arg_dptr(&c, 9), *gcw = arg_dptr(&c, 10), *gp = arg_dptr(&c, 11), *gs = arg_dptr(&c, 12), *gr = arg_dptr(&c, 13); BAIL;
+    if (ub < 22 * sizeof(float)) { napi_throw_range_error(env, NULL, "uniform block needs 22 floats"); return NULL; }
+    return check(env, x, splat_project_surfel_backward(x, u, pos, ps, scl, ss, rot, rs, n, grec, gcw, gp, gs, gr), mk_undefined(env));
+}
 FN(sampling_rate_max) { /* (ctx, Float32Array(22), focalPx, near, margin, positions, posStride, n, rateInOut) */
     ARGS(9); splat_ctx *x = arg_external(&c, 0); size_t ub = 0; float *u = arg_hostbuf(&c, 1, &ub);
     float focal = (float)arg_number(&c, 2), near_ = (float)arg_number(&c, 3), margin = (float)arg_number(&c, 4);
@@ -1032,6 +1057,7 @@ static napi_value init(napi_env env, napi_value exports) {
         EXPORT(composite_backward_abs), EXPORT(composite_backward_det_abs_workspace_bytes), EXPORT(composite_backward_det_abs),
         EXPORT(density_accumulate_abs),
         EXPORT(composite_features), EXPORT(composite_features_backward),
+        EXPORT(project_surfel), EXPORT(composite_surfel_depth), EXPORT(project_surfel_backward),
     };
     napi_define_properties(env, exports, sizeof d / sizeof d[0], d);
     return exports;

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Gradients of ellipsoid frames (GPU box only): python tools/grad_bench.py [--depth] [--deterministic] [--antialiased] [--importance] [--absgrad] [--features K[,K]] [--camera | --loss | --optimizer] [C1,C2] [K] [R]
+"""Gradients of ellipsoid frames (GPU box only): python tools/grad_bench.py [--depth] [--deterministic] [--antialiased] [--importance] [--absgrad] [--features K[,K]] [--surfel] [--camera | --loss | --optimizer] [C1,C2] [K] [R]
 
 tools/ellipsoid_bench.py's scenes and method (the scene's positions, sigma = radius / 2 per axis times a random factor in
 [e^-0.3, e^0.3], random rotations, SH of degree 3 with the scene's opacity; R rounds of K calls per kind, kinds alternating
@@ -46,6 +46,14 @@ of, alternating in the same rounds, per K: splat_composite_features alone on K r
 (composite_contribution), and splat_composite_features_backward alone with a random upstream map
 (composite_features_backward_K: two walks, 6 + K float sums per entry, float atomics) beside its two-walk peer
 splat_composite_backward (composite_backward: 9 sums); their ratios.
+
+--surfel adds 2D Gaussian surfels beside the ellipsoid, alternating in the same rounds, on the same planes read as surfels (scales
+x and y, the same quaternions): the staged forward with render_surfels' calls (forward_surfel: project_surfels, SH colour, sort,
+bin, composite) and its backward (backward_surfel); with --depth the forward with the intersection depth map
+(forward_surfel_depth: one more walk, splat_composite_surfel_depth) and its backward; splat_composite_backward(_depth) alone with
+cfg.footprint = SURFEL over the surfel frame's own lists (composite_backward_surfel(_depth): 12 or 13 wave sums per entry against
+9 or 10, and one rcp per pair), splat_composite_surfel_depth alone (surfel_depth_forward) and splat_project_surfel_backward alone
+with a random grad_clip_w (project_backward_surfel); each one's ratio to its ellipsoid peer, and the surfel frame's own pairs.
 
 --camera adds the camera gradients: splat_project_ellipsoid_backward_camera without and with grad_depth (all of its launches:
 the per-splat kernel with the per-wave sums, then k_camera_sum_slices above 1024 partials, then k_camera_sum) beside
@@ -151,7 +159,8 @@ if "--features" in sys.argv[1:]:
     at = sys.argv.index("--features")
     feature_ks = [int(v) for v in sys.argv[at + 1].split(",")]
     del sys.argv[at:at + 2]
-argv = [a for a in sys.argv[1:] if a not in ("--depth", "--camera", "--loss", "--normal-loss", "--optimizer", "--deterministic", "--antialiased", "--importance", "--absgrad")]
+argv = [a for a in sys.argv[1:] if a not in ("--depth", "--camera", "--loss", "--normal-loss", "--optimizer", "--deterministic", "--antialiased", "--importance", "--absgrad", "--surfel")]
+surfel_too = "--surfel" in sys.argv[1:]
 abs_too = "--absgrad" in sys.argv[1:]
 aa_too = "--antialiased" in sys.argv[1:]
 importance_too = "--importance" in sys.argv[1:]
@@ -789,6 +798,59 @@ for name in names:
             "project_backward_plus_torch_terms": plus_torch_terms,
         })
     forwards = {"backward": forward, "backward_depth": forward_depth}
+    if surfel_too:
+        def forward_surfel():
+            rec, aux = AG.project_surfels(u, means, scales, rots)
+            col = AG.sh_colors(u[16:19], means, shs, 3, ops)
+            rgb, _ = AG.rasterize(rec, col, aux, w, h)
+            state.update(srec=rec, scol=col, saux=aux, loss=(rgb * gimg).sum())
+
+        def forward_surfel_depth():
+            rec, cw, aux = AG.project_surfels(u, means, scales, rots, return_depth=True)
+            col = AG.sh_colors(u[16:19], means, shs, 3, ops)
+            rgb, _, depth = AG.rasterize(rec, col, aux, w, h, depths=cw)
+            dz = torch.where(torch.isfinite(depth), depth, torch.zeros_like(depth))
+            state.update(srec=rec, scol=col, saux=aux, scw=cw, loss=(rgb * gimg).sum() + (dz * gdimg).sum())
+
+        # the surfel frame's own lists, copied out of the binner (the ellipsoid kinds re-bin it between the surfel kinds' calls)
+        forward_surfel_depth()
+        srec, scw = state["srec"].detach().contiguous(), state["scw"].detach().contiguous()
+        saux = state["saux"]
+        cx.bin(saux, w, h)
+        sidx_p, scnt_p, soff_p = cx.lists()
+        _lib.check(lib.splat_bin_total(cx.binner, C.byref(tot)), cx.ctx)
+        surfel_pairs = int(tot.value)
+        sidx = torch.empty(max(surfel_pairs, 1), dtype=torch.int32, device="cuda")
+        scnt, soff = torch.empty(tiles, dtype=torch.int32, device="cuda"), torch.empty(tiles, dtype=torch.int32, device="cuda")
+        for dst, src, nb in ((sidx, sidx_p, surfel_pairs * 4), (scnt, scnt_p, tiles * 4), (soff, soff_p, tiles * 4)):
+            if nb:
+                _lib.check(lib.splat_buf_copy(cx.ctx, dst.data_ptr(), src, nb), cx.ctx)
+        torch.cuda.synchronize()
+        scfg = _lib.CompositeCfg(_lib.MODE_FRONT_TO_BACK, 1, 16, 0, _lib.U32_MAX, _lib.RECORDS_PROJECTED, 1, _lib.FOOTPRINT_SURFEL)
+        sdepth = torch.empty((h, w), device="cuda")
+        slists = (sidx.data_ptr(), scnt.data_ptr(), soff.data_ptr())
+        work.update({
+            "forward_surfel": forward_surfel,
+            "backward_surfel": None,
+            "composite_backward_surfel": lambda: lib.splat_composite_backward(cx.ctx, C.byref(scfg), col.data_ptr(), 1, srec.data_ptr(), *slists, w, h,
+                                                                              g4.data_ptr(), n, grec.data_ptr(), gcol.data_ptr()),
+            "surfel_depth_forward": lambda: lib.splat_composite_surfel_depth(cx.ctx, C.byref(scfg), col.data_ptr(), 1, srec.data_ptr(), *slists, w, h,
+                                                                             scw.data_ptr(), 1, n, sdepth.data_ptr(), None),
+            "project_backward_surfel": lambda: lib.splat_project_surfel_backward(cx.ctx, uf, m4.data_ptr(), 1, s4.data_ptr(), 1, rots.data_ptr(), 1, n,
+                                                                                 grec.data_ptr(), gzp.data_ptr(), gp.data_ptr(), gs.data_ptr(),
+                                                                                 gq.data_ptr()),
+        })
+        forwards["backward_surfel"] = forward_surfel
+        if depth_too:
+            work.update({
+                "forward_surfel_depth": forward_surfel_depth,
+                "backward_surfel_depth": None,
+                "composite_backward_surfel_depth": lambda: lib.splat_composite_backward_depth(cx.ctx, C.byref(scfg), col.data_ptr(), 1, srec.data_ptr(),
+                                                                                              *slists, w, h, g4.data_ptr(), n, grec.data_ptr(),
+                                                                                              gcol.data_ptr(), scw.data_ptr(), 1, gdimg.data_ptr(),
+                                                                                              gz.data_ptr()),
+            })
+            forwards["backward_surfel_depth"] = forward_surfel_depth
     if aa_too:
         grho = torch.rand(n, device="cuda") * 2 - 1
 
@@ -881,6 +943,16 @@ for name in names:
             _lib.check(work[kind](), cx.ctx)  # (the timed calls' return codes were not looked at)
         extra[f"composite_features_{fk}_over_contribution"] = round(med[f"composite_features_{fk}"] / med["composite_contribution"], 3)
         extra[f"composite_features_backward_{fk}_over_composite_backward"] = round(med[f"composite_features_backward_{fk}"] / med["composite_backward"], 3)
+    if surfel_too:
+        peers = [("forward_surfel", "forward"), ("backward_surfel", "backward"), ("composite_backward_surfel", "composite_backward"),
+                 ("project_backward_surfel", "project_backward")]
+        if depth_too:
+            peers += [("forward_surfel_depth", "forward_depth"), ("backward_surfel_depth", "backward_depth"),
+                      ("composite_backward_surfel_depth", "composite_backward_depth")]
+        for a in ("composite_backward_surfel", "surfel_depth_forward", "project_backward_surfel"):
+            _lib.check(work[a](), cx.ctx)  # (the timed calls' return codes were not looked at)
+        extra.update({f"{a}_over_{b}": round(med[a] / med[b], 3) for a, b in peers})
+        extra["surfel_pairs"] = surfel_pairs
     if aa_too:
         extra.update({f"{a}_over_{b}": round(med[a] / med[b], 3) for a, b in (
             ("forward_aa", "forward"), ("backward_aa", "backward"), ("project_backward_aa", "project_backward"))})
