@@ -299,7 +299,8 @@ int splat_validate_tile_order(splat_ctx *ctx, const void *projected, const void 
 #define SPLAT_FOOTPRINT_DISC 1
 #define SPLAT_FOOTPRINT_ELLIPSOID 2 /* an anisotropic 3D Gaussian (extension, no reference counterpart): splat_project_ellipsoid */
 #define SPLAT_FOOTPRINT_SURFEL 3    /* a 2D Gaussian surfel (extension; "2D Gaussian surfels" below): splat_project_surfel; the
-                                     * staged composites, the composite backward, the feature channels and splat_composite_surfel_depth take it */
+                                     * staged composites, the composite backward, the feature channels, splat_composite_surfel_depth,
+                                     * splat_composite_surfel_distortion and splat_composite_backward_distortion take it */
 typedef struct splat_composite_cfg {
     uint32_t mode;       /* SPLAT_COMPOSITE_* */
     uint32_t early_out;  /* 1 = stop a pixel at alpha >= 0.99 (reference :187-190) */
@@ -726,6 +727,28 @@ int splat_sh_colors_backward_camera(splat_ctx *ctx, const float *eye3, const voi
  * and q = 0, and none runs with q ignored.  The ellipsoid's projector entry points (the _aa projector, the
  * _camera backwards) take no cfg: a surfel's planes given to them are projected as an ellipsoid's.
  *
+ * Depth distortion (2DGS's and Mip-NeRF 360's regulariser, over the intersection depth).  With 0 < near < far (far = +inf
+ * allowed; anything else is SPLAT_ERR_INVALID) and t_i = z_i rd_i the depth above, m_i = far (t_i - near) / ((far - near) t_i)
+ * maps depth to [0, 1) (far = +inf: m_i = 1 - near / t_i), and per pixel
+ *     Dist = sum_{i > j} w_i w_j (m_i - m_j)^2
+ * over the entries the pixel consumed that are inside the cut and whose t_i is finite and > 0; an entry inside the cut whose
+ * t_i is not draws the image as before, takes no part in Dist and receives nothing from it.  0 where nothing took part.  It is
+ * formed front to back, Dist += w_i (m'_i^2 A + Q - 2 m'_i M), then A += w_i, M += w_i m'_i, Q += w_i m'_i^2, over
+ * m'_i = m_i - m_first, m_first the m of the pixel's first participating entry: the term depends on differences only, and the
+ * sums of unshifted m's (or W Q - M^2) cancel four digits away in binary32.  m'_i is formed as c (1 / t_first - 1 / t_i),
+ * c = near far / (far - near) (near when far = +inf): the same difference without its common constant.  One binary32
+ * rounding per operator in the order stated in csrc/surfel.h.
+ * splat_composite_surfel_distortion: splat_composite_surfel_depth's arguments and cfg, then near, far and out_distortion_f32
+ * (W x H floats, 4-byte aligned).  One walk, one launch; out_depth_f32 and out_alpha_f32 are each optional here, and what they
+ * receive is bit for bit what splat_composite_surfel_depth writes.
+ * splat_composite_backward_distortion: splat_composite_backward_depth's arguments, contract and cfg (footprint SURFEL only),
+ * then near, far and grad_distortion_f32 (W x H floats: dL/dDist; not read where nothing took part).  One launch adds the
+ * image's, the depth map's and the distortion's gradients: through the weights Dist is one more colour channel with the
+ * per-entry colour e_i = sum_j w_j (m_i - m_j)^2 and background 0, and through m_i, with dm/dt = c / t^2, dL/dt_i = dL/dDist
+ * 2 w_i (m'_i W - M) c / t_i^2 joins the depth map's term: grad_depth receives dL/dz_i, and all eight record columns their
+ * share.  grad_depth_f32 may be NULL here (no depth-map term).  With grad_distortion_f32 all zeros the outputs are
+ * splat_composite_backward_depth's, to the order of the atomic sums.  Both refuse every other footprint with a message.
+ *
  * splat_project_surfel_backward: per splat, in float64, the chain of csrc/surfel.h reversed.  grad_records (n x 8 floats) and
  * grad_clip_w (n floats, or NULL: zeros) in; grad_positions, grad_scales (x and y; z and w exactly 0) and grad_rotations
  * (through the quaternion's normalisation) OVERWRITTEN, n x 4 floats each.  The cull is the projector's own: a culled surfel
@@ -737,6 +760,16 @@ int splat_composite_surfel_depth(splat_ctx *ctx, const splat_composite_cfg *cfg,
                                  const void *records, const void *tile_indices, const void *tile_counts, const void *tile_offsets,
                                  uint32_t width, uint32_t height, const void *depth_f32, uint32_t depth_stride_floats, uint32_t n,
                                  void *out_depth_f32, void *out_alpha_f32);
+int splat_composite_surfel_distortion(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4,
+                                      const void *records, const void *tile_indices, const void *tile_counts, const void *tile_offsets,
+                                      uint32_t width, uint32_t height, const void *depth_f32, uint32_t depth_stride_floats, uint32_t n,
+                                      void *out_depth_f32, void *out_alpha_f32, float near, float far, void *out_distortion_f32);
+int splat_composite_backward_distortion(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4,
+                                        const void *records, const void *tile_indices, const void *tile_counts, const void *tile_offsets,
+                                        uint32_t width, uint32_t height, const void *grad_rgba32f, uint32_t n, void *grad_records,
+                                        void *grad_color_opacity, const void *depth_f32, uint32_t depth_stride_floats,
+                                        const void *grad_depth_f32, void *grad_depth, float near, float far,
+                                        const void *grad_distortion_f32);
 int splat_project_surfel_backward(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4,
                                   const void *scales, uint32_t scale_stride_vec4, const void *rotations, uint32_t rot_stride_vec4,
                                   uint32_t n, const void *grad_records, const void *grad_clip_w, void *grad_positions, void *grad_scales,

@@ -142,6 +142,10 @@ SIGNATURES = {
     "splat_sh_colors_backward_camera": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _vp, _u32, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "splat_project_surfel": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _vp]),
     "splat_composite_surfel_depth": (_i, [_vp, C.POINTER(CompositeCfg), _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _u32, _vp, _vp]),
+    "splat_composite_surfel_distortion": (_i, [_vp, C.POINTER(CompositeCfg), _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _u32, _vp, _vp,
+                                               C.c_float, C.c_float, _vp]),
+    "splat_composite_backward_distortion": (_i, [_vp, C.POINTER(CompositeCfg), _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _vp, _vp,
+                                                 _vp, _u32, _vp, _vp, C.c_float, C.c_float, _vp]),
     "splat_project_surfel_backward": (_i, [_vp, C.POINTER(C.c_float), _vp, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     "splat_image_loss_workspace_bytes": (C.c_uint64, [_u32, _u32]),
     "splat_image_loss": (_i, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, C.c_float, _vp, C.c_uint64, _vp]),

@@ -207,6 +207,22 @@ contribution(), and a uniforms tensor that requires grad (no camera gradient yet
                                              features=surfel_normals(rotations, means, eye))
     loss = photometric_loss(rgb, target) + lam * normal_consistency_loss(nmap, depth, cam, weight=alpha.detach(), depth_kind="z")
 
+Depth distortion for surfels (2DGS's fourth term).  The (1, z, z^2) recipe above blends one constant per splat, so for a surfel it
+sees the centre's depth only; 2DGS's term is over the per-pixel intersection depth t_i = z_i rd_i, whose spread across one surfel is
+what flattens surfels onto the surface.  distortion=(near, far), 0 < near < far (far = inf allowed), adds the map
+dist = sum_{i > j} w_i w_j (m_i - m_j)^2, m = far (t - near) / ((far - near) t) in [0, 1), 0 where nothing contributed, after depth:
+
+    rgb, alpha, depth, dist, nmap = render_surfels(cam, means, scales, rotations, opacities, sh=sh, width=W, height=H,
+                                                   distortion=(near, far), features=surfel_normals(rotations, means, eye))
+    loss = photometric_loss(rgb, target) + lam_d * dist.mean() \
+        + lam_n * normal_consistency_loss(nmap, depth, cam, weight=alpha.detach(), depth_kind="z")
+
+The map comes from the depth map's own walk (splat_composite_surfel_distortion in place of splat_composite_surfel_depth: depth
+keeps its bits), summed front to back over m_i - m_first so that nothing cancels in binary32 (relative L2 of 3e-7 of float64
+where W Q - M^2 and the unshifted prefix sums sit at 1e-4), and its gradient joins the image's and the depth map's in one launch
+(splat_composite_backward_distortion), to all eight record columns, the opacity and z.  Surfel projections only, and with
+depths= (render_surfels: implied): anything else raises SplatError.
+
 torch is imported when a function here is first called, so `import splat_renderer_amd` does not need it.
 """
 import collections
@@ -563,7 +579,7 @@ def _functions():
 
     class Rasterize(torch.autograd.Function):
         @staticmethod
-        def forward(fctx, rec, col, aux, width, height, depths, deterministic, absgrad):
+        def forward(fctx, rec, col, aux, width, height, depths, deterministic, absgrad, distortion=None):
             cx = aux.ctx
             out = torch.empty((height, width, 4), device=rec.device, dtype=torch.float32)
             alpha = torch.empty((height, width), device=rec.device, dtype=torch.float32)
@@ -579,18 +595,27 @@ def _functions():
                 check(cx.lib.splat_composite_aov(*args), cx.ctx)
             else:
                 check(cx.lib.splat_composite_aov_depth(*args, depths.data_ptr(), 1), cx.ctx)
-            if depths is not None and surfel:  # the intersection depth sum w z rd / sum w: a walk of its own over the same lists
+            dist = None
+            if depths is not None and surfel and distortion is not None:  # the same walk writes the distortion map beside it
+                dist = torch.empty((height, width), device=rec.device, dtype=torch.float32)
+                check(cx.lib.splat_composite_surfel_distortion(cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr(), idx, cnt, off, width,
+                                                               height, depths.data_ptr(), 1, aux.n, depth.data_ptr(), None, distortion[0],
+                                                               distortion[1], dist.data_ptr()), cx.ctx)
+            elif depths is not None and surfel:  # the intersection depth sum w z rd / sum w: a walk of its own over the same lists
                 check(cx.lib.splat_composite_surfel_depth(cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr(), idx, cnt, off, width, height,
                                                           depths.data_ptr(), 1, aux.n, depth.data_ptr(), None), cx.ctx)
+            fctx.distortion = distortion
             fctx.save_for_backward(rec, col, depths)
             fctx.set_materialize_grads(False)  # (an unused depth map: None, and the colour-only kernel)
             fctx.aux, fctx.gen, fctx.wh = aux, gen, (width, height)
             fctx.deterministic, fctx.absgrad = deterministic, absgrad
             rgb = out[..., :3]
+            if dist is not None:
+                return rgb, alpha, depth, dist
             return (rgb, alpha) if depths is None else (rgb, alpha, depth)
 
         @staticmethod
-        def backward(fctx, grad_rgb, grad_alpha, grad_depth_map=None):
+        def backward(fctx, grad_rgb, grad_alpha, grad_depth_map=None, grad_dist_map=None):
             rec, col, depths = fctx.saved_tensors
             aux = fctx.aux
             cx = aux.ctx
@@ -608,12 +633,19 @@ def _functions():
             grec = torch.zeros((n, 8), device=dev, dtype=torch.float32)
             gcol = torch.zeros((n, 4), device=dev, dtype=torch.float32)
             det, absgrad = fctx.deterministic, fctx.absgrad
+            with_dist = fctx.distortion is not None and grad_dist_map is not None
             with_depth = depths is not None and grad_depth_map is not None
             gd = _cuda_f32(grad_depth_map, "grad_depth") if with_depth else None
-            gz = torch.zeros(n, device=dev, dtype=torch.float32) if with_depth else None
+            gz = torch.zeros(n, device=dev, dtype=torch.float32) if with_depth or with_dist else None
             # absgrad: beside the signed sums, sum |term c.x| and sum |term c.y|, left on the projection
             gabs = torch.zeros((n, 2), device=dev, dtype=torch.float32) if absgrad else None
-            if n:
+            if n and with_dist:  # one launch: the image's, the depth map's (when it has an upstream) and the distortion's gradients
+                gdist = _cuda_f32(grad_dist_map, "grad_distortion")
+                check(cx.lib.splat_composite_backward_distortion(cx.ctx, C.byref(_ellipsoid_cfg(aux.footprint)), col.data_ptr(), 1, rec.data_ptr(),
+                                                                 idx, cnt, off, width, height, g.data_ptr(), n, grec.data_ptr(), gcol.data_ptr(),
+                                                                 depths.data_ptr(), 1, gd.data_ptr() if with_depth else None, gz.data_ptr(),
+                                                                 fctx.distortion[0], fctx.distortion[1], gdist.data_ptr()), cx.ctx)
+            elif n:
                 name = _COMPOSITE_BACKWARD[det, absgrad, with_depth]
                 cfg = _ellipsoid_cfg(aux.footprint)
                 head, lists = [cx.ctx, C.byref(cfg), col.data_ptr(), 1, rec.data_ptr()], [idx, cnt, off]
@@ -634,7 +666,7 @@ def _functions():
                 check(getattr(cx.lib, name)(*args), cx.ctx)
             if absgrad:
                 aux.absgrad = gabs
-            return grec, gcol, None, None, None, gz, None, None
+            return grec, gcol, None, None, None, gz, None, None, None
 
     class CompositeFeatures(torch.autograd.Function):
         """splat_composite_features and splat_composite_features_backward over the projection's lists.  feats: (n, K), its rows
@@ -821,14 +853,18 @@ def surfel_normals(rotations, means, eye):
 
 
 def render_surfels(camera_or_uniforms, means, scales, rotations, opacities, colors=None, sh=None, width=None, height=None, degree=None,
-                   return_depth=False, features=None, return_aux=False):
+                   return_depth=False, features=None, return_aux=False, distortion=None):
     """render_gaussians' surfel twin: project_surfels, the colour (sh_colors when `sh` is given, else cat(colors, opacities)),
     rasterize.  Returns (rgb (H, W, 3), alpha (H, W)); return_depth=True: (rgb, alpha, depth (H, W)), the ray-surfel
     intersection depth map sum w z rd / sum w in clip w (depth_kind="z" for depth_normals and normal_consistency_loss), +inf where
     nothing contributed; features ((n, K) or (n,)): rasterize's, blended with the surfel image's own weights, the map after depth:
-    (rgb, alpha[, depth], feat[, aux]); return_aux=True appends the frame's ProjectedSplats."""
+    (rgb, alpha[, depth], feat[, aux]); return_aux=True appends the frame's ProjectedSplats.  distortion=(near, far) implies
+    return_depth=True and adds rasterize's depth-distortion map after depth: (rgb, alpha, depth, dist[, feat][, aux])."""
     if width is None or height is None:
         raise SplatError(-1, "render_surfels needs width and height")
+    if distortion is not None:
+        distortion = _distortion_range(distortion, "render_surfels")
+        return_depth = True
     _refuse_surfel_camera_grad(camera_or_uniforms, "render_surfels")
     for name, t in (("means", means), ("scales", scales), ("rotations", rotations), ("opacities", opacities)):
         _cuda_f32(t, name)
@@ -848,7 +884,7 @@ def render_surfels(camera_or_uniforms, means, scales, rotations, opacities, colo
         col = _t().cat([colors, opacities.reshape(-1, 1)], dim=1)
     else:
         raise SplatError(-1, "render_surfels needs colors or sh")
-    out = rasterize(rec, col, aux, width, height, depths=depths, features=features)
+    out = rasterize(rec, col, aux, width, height, depths=depths, features=features, distortion=distortion)
     return (*out, aux) if return_aux else out
 
 
@@ -871,14 +907,29 @@ def sh_colors(eye, means, sh, degree, opacities):
     return _functions().ShColors.apply(e, means4, sh2, int(degree), op, e_t)
 
 
-def rasterize(rec, col, aux, width=None, height=None, depths=None, deterministic=False, absgrad=False, features=None):
+def _distortion_range(distortion, who):
+    """(near, far) as floats, 0 < near < far (far = inf allowed), or SplatError."""
+    try:
+        near, far = (float(x) for x in distortion)
+    except (TypeError, ValueError):
+        raise SplatError(-1, f"{who}: distortion must be (near, far)") from None
+    near, far = float(np.float32(near)), float(np.float32(far))
+    if not (0.0 < near < far and near < float("inf")):
+        raise SplatError(-1, f"{who}: distortion=(near, far) needs 0 < near < far, not ({near}, {far})")
+    return near, far
+
+
+def rasterize(rec, col, aux, width=None, height=None, depths=None, deterministic=False, absgrad=False, features=None, distortion=None):
     """(rgb (H, W, 3), alpha (H, W)) of the records and colours over the projection's lists; both differentiable.  With
     depths ((n,) per-splat z, differentiable): (rgb, alpha, depth), depth (H, W) = sum w z / sum w per pixel, +inf where
     nothing contributed.  deterministic=True: the backward sums in a fixed order (the module's docstring).  absgrad=True: the
     backward also leaves the (n, 2) absolute sums of the centre's terms in aux.absgrad (the module's docstring): the colour,
     alpha and depth terms only, never a feature map's.  features ((n, K) or (n,), 1 <= K <= 32): composite_features' map
     (H, W, K) is appended to the tuple, (rgb, alpha[, depth], feat), from the lists this call binned; not with deterministic=True
-    (SplatError: no fixed-order feature backward exists)."""
+    (SplatError: no fixed-order feature backward exists).  distortion=(near, far), on a surfel projection with depths= only
+    (SplatError otherwise, and unless 0 < near < far): (rgb, alpha, depth, dist[, feat]), dist (H, W) 2DGS's depth-distortion
+    map of the intersection depths (the module's docstring), written by the depth map's own walk and differentiated by the one
+    fused backward launch."""
     width = aux.width if width is None else int(width)
     height = aux.height if height is None else int(height)
     _refuse_deterministic_features(deterministic, features, "rasterize")
@@ -894,7 +945,14 @@ def rasterize(rec, col, aux, width=None, height=None, depths=None, deterministic
         z = _cuda_f32(depths, "depths")
         if z.dim() != 1 or z.shape[0] != aux.n:
             raise SplatError(-1, f"depths must have shape ({aux.n},), not {tuple(z.shape)}")
-    out = _functions().Rasterize.apply(rec_c, col_c, aux, width, height, z, bool(deterministic), bool(absgrad))
+    if distortion is not None:
+        if not _is_surfel(aux):
+            raise SplatError(-1, "rasterize: distortion= is built for surfel projections only (project_surfels); an ellipsoid has one "
+                                 "depth per splat: the (1, z, z^2) feature recipe of the module's docstring")
+        if z is None:
+            raise SplatError(-1, "rasterize: distortion= needs depths= (project_surfels(..., return_depth=True)'s clip_w)")
+        distortion = _distortion_range(distortion, "rasterize")
+    out = _functions().Rasterize.apply(rec_c, col_c, aux, width, height, z, bool(deterministic), bool(absgrad), distortion)
     if features is None:
         return out
     return (*out, composite_features(rec_c, col_c, aux, features, width, height))

@@ -163,6 +163,10 @@ struct SurfelBackwardCall {
     uint32_t depth_stride_floats;
     void *grad_depth;
     bool depth;
+    // splat_composite_backward_distortion (surfel.hip's own entry point; dist implies depth, and grad_depth_f32 may be NULL)
+    float near, far;
+    const void *grad_distortion_f32;
+    bool dist;
 };
 int surfel_composite_backward(splat_ctx *ctx, const SurfelBackwardCall &c);
 

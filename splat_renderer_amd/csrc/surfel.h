@@ -18,8 +18,49 @@
 //   record       disc_record_axes(m, w, h, p, e0, e1): culled (all zeros) when a corner of the quad has w <= 0, when det == 0
 //                (edge-on, a zero scale) and when anything is not finite (a zero quaternion: k = inf, 0 inf = NaN)
 // cw (optional): the centre's clip w where the record is kept, 0 where it is culled.
+//
+// Depth distortion (surfel.hip: k_surfel_depth<PX, DIST>, k_surfel_backward<DEPTH, PX, DIST>; 2DGS's term): per pixel
+// Dist = sum_{i > j} w_i w_j (m_i - m_j)^2 over the consumed entries inside the cut whose t = z rd is finite and > 0 (the
+// others draw the image and take no part), m = far (t - near) / ((far - near) t) = ka - c / t, ka = far / (far - near),
+// c = near ka.  The term depends on differences of m only, and a sum of m's near 1 cancels in binary32 (W Q - M^2 and the
+// unshifted prefix sums lose four digits), so every m is taken relative to the pixel's first participating entry, and ka is
+// dropped before anything is rounded: m'_i = m_i - m_first = c (1 / t_first - 1 / t_i).
+// Operation order (tests/surfel_distortion_ref.py restates it; one binary32 rounding per operator, no contraction; rcp is the
+// hardware's reciprocal, a division in the restatement):
+//   host         c = near when far = +inf, else the binary32 nearest to near far / (far - near) formed in binary64
+//   per entry    t = z rd,  rt = rcp(t),  rt0 = rt of the first participating entry,  m' = c (rt0 - rt),  mm = m' m'
+//                d = (mm A + Q) - (2 m') M,  Dist = Dist + w d,  A = A + w,  M = M + w m',  Q = Q + w mm
+// with A = M = Q = Dist = 0 before the first entry and w the image's own weight (surfel_walk.h).
 #pragma once
 #include "disc.h"
+
+// The distortion sums one pixel carries front to back (the order above), and one participating entry's step.
+struct SurfDist {
+    float dist = 0.0f, A = 0.0f, M = 0.0f, Q = 0.0f;
+    float rt0 = -1.0f; // (negative: no entry has participated yet; a participating rt is >= 0)
+};
+
+__device__ __forceinline__ bool surf_dist_participates(float t) { return t > 0.0f && t < __builtin_inff(); }
+
+// m' of an entry at depth t against the pixel's first (rt0 < 0: this is the first, and becomes it)
+__device__ __forceinline__ float surf_dist_m(float c, float t, float &rt0, float &rt) {
+#pragma clang fp contract(off)
+    rt = __builtin_amdgcn_rcpf(t);
+    if (rt0 < 0.0f) rt0 = rt;
+    return c * (rt0 - rt);
+}
+
+__device__ __forceinline__ void surf_dist_step(SurfDist &s, float c, float t, float w) {
+#pragma clang fp contract(off)
+    float rt;
+    const float mp = surf_dist_m(c, t, s.rt0, rt);
+    const float mm = mp * mp;
+    const float d = (mm * s.A + s.Q) - (2.0f * mp) * s.M;
+    s.dist = s.dist + w * d;
+    s.A = s.A + w;
+    s.M = s.M + w * mp;
+    s.Q = s.Q + w * mm;
+}
 
 __device__ __forceinline__ DiscRecord surfel_record(const float *m, float w, float h, float4 p, float4 s, float4 q, float *cw = nullptr) {
 #pragma clang fp contract(off)

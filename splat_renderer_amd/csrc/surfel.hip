@@ -16,7 +16,15 @@
 //     z += w GDn rd     q_k += w GDn z rd^2 d_k     c_k -= w GDn z rd^2 q_k
 //   Twelve numbers per entry (thirteen with DEPTH) go through the wave DPP tree and LDS, then one float atomic add per touched
 //   (entry, number): reproducible to rounding.
-// k_surfel_depth<PX>   walk 1 alone: D (+inf where nothing contributed) and optionally alpha = 1 - T.
+//   DIST (with DEPTH): the depth-distortion map of surfel.h joins the same launch.  Walk 1 carries Dist, A, M, Q and rt0 in
+//   surfel.h's order; with the pixel's totals W = A, Mb = M / W, and upstream G_Dist, an entry that participates has
+//     dm = m' - Mb     e = W dm^2 + Dist / W (= sum_j w_j (m_i - m_j)^2, without the cancelling W m'^2 - 2 M m' + Q)
+//   G_Dist e joins cg as one more colour channel with background 0, and through m_i, dm/dt = c / t^2,
+//     gt = G_Dist 2 w W dm c rt^2
+//   joins w GDn as dL / d(z rd).  m_first is a constant (the term is shift invariant).  grad_depth_img may be NULL: GDn = 0.
+//   No number more than DEPTH's thirteen.
+// k_surfel_depth<PX, DIST>   walk 1 alone: D (+inf where nothing contributed) and optionally alpha = 1 - T; DIST: the
+//   distortion map too (0 where nothing participated), each of D and alpha optional.
 // k_project_surfel_backward   one thread per splat, float64: surfel_record's chain reversed — the record's eight gradients and
 //   the clip w's to position, scales x and y (z, w: exact zeros) and the quaternion through its normalisation.  The cull is
 //   surfel_record's own (binary32): a culled surfel gets exact zeros.
@@ -40,12 +48,17 @@ struct SurfDepthParams : BackParams {
     const float *grad_depth_img;
     float *grad_depth;
     float *out_depth, *out_alpha; // (k_surfel_depth)
+    // DIST: surfel.h's c, the map's upstream (k_surfel_backward) and the map (k_surfel_depth)
+    float dist_c;
+    const float *grad_dist_img;
+    float *out_dist;
 };
 
 } // namespace
 
-template <bool DEPTH, bool PX>
+template <bool DEPTH, bool PX, bool DIST = false>
 __global__ __launch_bounds__(256) void k_surfel_backward(SurfDepthParams p) {
+    static_assert(DEPTH || !DIST, "the distortion's gradient reaches z and rd: DEPTH's numbers");
     constexpr int NV = surf_nv(DEPTH);
     __shared__ SurfEntry s_ent[GCH];
     __shared__ uint32_t s_idx[GCH];
@@ -60,6 +73,7 @@ __global__ __launch_bounds__(256) void k_surfel_backward(SurfDepthParams p) {
     uint32_t L = 0;
     float T = 1.0f, T_last = 1.0f; // T_L, T_{L-1}
     float zw = 0.0f, ws = 0.0f;    // (DEPTH) sum w z rd, sum w over the consumed entries
+    [[maybe_unused]] SurfDist ds;  // (DIST)
     if (tid == 0) s_maxL = 0;
     for (uint32_t c0 = 0; c0 < count; c0 += GCH) {
         const uint32_t m = min((uint32_t)GCH, count - c0);
@@ -76,6 +90,10 @@ __global__ __launch_bounds__(256) void k_surfel_backward(SurfDepthParams p) {
                     if (in) { // (outside the cut wgt is 0, and rd may be inf there: 0 inf)
                         zw += (s_ent[j].d.x * rd) * wgt;
                         ws += wgt;
+                        if constexpr (DIST) {
+                            const float t = s_ent[j].d.x * rd;
+                            if (surf_dist_participates(t)) surf_dist_step(ds, p.dist_c, t, wgt);
+                        }
                     }
                 }
                 if (T <= T_STOP) {
@@ -96,7 +114,18 @@ __global__ __launch_bounds__(256) void k_surfel_backward(SurfDepthParams p) {
     if constexpr (DEPTH) {
         if (pixel_ok && ws > 0.0f) {
             D = zw / ws;
-            GDn = p.grad_depth_img[(size_t)py * p.width + px] / ws;
+            if constexpr (DIST) GDn = p.grad_depth_img ? p.grad_depth_img[(size_t)py * p.width + px] / ws : 0.0f;
+            else GDn = p.grad_depth_img[(size_t)py * p.width + px] / ws;
+        }
+    }
+    // (DIST) G_Dist, W, M / W, Dist / W; G_Dist = 0, and not read, where nothing participated
+    [[maybe_unused]] float GDist = 0.0f, dW = 0.0f, dMb = 0.0f, dDW = 0.0f;
+    if constexpr (DIST) {
+        if (pixel_ok && ds.A > 0.0f) {
+            GDist = p.grad_dist_img[(size_t)py * p.width + px];
+            dW = ds.A;
+            dMb = ds.M / ds.A;
+            dDW = ds.dist / ds.A;
         }
     }
     float Tn = T; // T_{i+1} on the way back
@@ -131,8 +160,18 @@ __global__ __launch_bounds__(256) void k_surfel_backward(SurfDepthParams p) {
                 const float Ti = (i + 1 == L) ? T_last : Tn / (1.0f - alpha);
                 float cg = ((G.x * e.c.x + G.y * e.c.y) + G.z * e.c.z) + G.w; // G . (c, 1)
                 if constexpr (DEPTH) cg += GDn * (e.d.x * rd - D);             // the centred depth channel
-                const float dA = Ti * (cg - S);
                 const float wgt = Ti * alpha;
+                [[maybe_unused]] float gt = 0.0f; // (DIST) dL / d(z rd) through m_i
+                if constexpr (DIST) {
+                    const float t = e.d.x * rd;
+                    if (GDist != 0.0f && surf_dist_participates(t)) {
+                        float rt;
+                        const float dm = surf_dist_m(p.dist_c, t, ds.rt0, rt) - dMb;
+                        cg += GDist * (dW * (dm * dm) + dDW);
+                        gt = ((GDist * 2.0f) * (wgt * dW)) * (dm * ((p.dist_c * rt) * rt));
+                    }
+                }
+                const float dA = Ti * (cg - S);
                 vals[SF_R] = wgt * G.x;
                 vals[SF_R + 1] = wgt * G.y;
                 vals[SF_R + 2] = wgt * G.z;
@@ -144,7 +183,8 @@ __global__ __launch_bounds__(256) void k_surfel_backward(SurfDepthParams p) {
                 float gcx = -(dur * (e.a.z + u * e.b.z) + dvr * (e.b.x + v * e.b.z));
                 float gcy = -(dur * (e.a.w + u * e.b.w) + dvr * (e.b.y + v * e.b.w));
                 if constexpr (DEPTH) {
-                    const float gz = wgt * GDn;    // dL / d(z rd)
+                    float gz = wgt * GDn;          // dL / d(z rd)
+                    if constexpr (DIST) gz += gt;
                     vals[SF_Z] = gz * rd;
                     const float grd = (gz * e.d.x) * (rd * rd); // d / d(q.d) through rd
                     gq += grd;
@@ -187,7 +227,7 @@ __global__ __launch_bounds__(256) void k_surfel_backward(SurfDepthParams p) {
     }
 }
 
-template <bool PX>
+template <bool PX, bool DIST = false>
 __global__ __launch_bounds__(256) void k_surfel_depth(SurfDepthParams p) {
     __shared__ SurfEntry s_ent[GCH];
     __shared__ uint32_t s_idx[GCH];
@@ -197,6 +237,7 @@ __global__ __launch_bounds__(256) void k_surfel_depth(SurfDepthParams p) {
 
     bool live = pixel_ok;
     float T = 1.0f, zw = 0.0f, ws = 0.0f;
+    [[maybe_unused]] SurfDist ds; // (DIST)
     for (uint32_t c0 = 0; c0 < count; c0 += GCH) {
         const uint32_t m = min((uint32_t)GCH, count - c0);
         __syncthreads();
@@ -210,6 +251,10 @@ __global__ __launch_bounds__(256) void k_surfel_depth(SurfDepthParams p) {
                 if (in) {
                     zw += (s_ent[j].d.x * rd) * wgt;
                     ws += wgt;
+                    if constexpr (DIST) {
+                        const float t = s_ent[j].d.x * rd;
+                        if (surf_dist_participates(t)) surf_dist_step(ds, p.dist_c, t, wgt);
+                    }
                 }
                 if (T <= T_STOP) {
                     live = false;
@@ -221,7 +266,12 @@ __global__ __launch_bounds__(256) void k_surfel_depth(SurfDepthParams p) {
     }
     if (pixel_ok) {
         const size_t o = (size_t)py * p.width + px;
-        p.out_depth[o] = ws > 0.0f ? zw / ws : __builtin_inff();
+        if constexpr (DIST) {
+            if (p.out_depth) p.out_depth[o] = ws > 0.0f ? zw / ws : __builtin_inff();
+            p.out_dist[o] = ds.dist;
+        } else {
+            p.out_depth[o] = ws > 0.0f ? zw / ws : __builtin_inff();
+        }
         if (p.out_alpha) p.out_alpha[o] = 1.0f - T;
     }
 }
@@ -332,6 +382,14 @@ int surf_frame_checks(splat_ctx *ctx, const FrameArgs &f) {
     return SPLAT_OK;
 }
 
+// surfel.h's c of a call's (near, far): 0 < near < far, far = +inf allowed
+int surf_dist_constant(splat_ctx *ctx, float near, float far, float &c) {
+    if (!(near > 0.0f && near < far && near < __builtin_inff()))
+        return ctx_fail(ctx, SPLAT_ERR_INVALID, "the depth distortion needs 0 < near < far (far = +inf: m = 1 - near / t)");
+    c = far == __builtin_inff() ? near : (float)((double)near * (double)far / ((double)far - (double)near));
+    return SPLAT_OK;
+}
+
 } // namespace
 
 int surfel_composite_backward(splat_ctx *ctx, const SurfelBackwardCall &c) {
@@ -340,15 +398,22 @@ int surfel_composite_backward(splat_ctx *ctx, const SurfelBackwardCall &c) {
     f.tile_indices = c.tile_indices, f.tile_counts = c.tile_counts, f.tile_offsets = c.tile_offsets, f.width = c.width, f.height = c.height, f.n = c.n;
     SurfDepthParams p{};
     uint32_t nty = 0;
-    const int rc_setup = f.setup(ctx, c.depth ? "splat_composite_backward_depth" : "splat_composite_backward", p, nty, true);
+    const char *who = c.dist ? "splat_composite_backward_distortion" : c.depth ? "splat_composite_backward_depth" : "splat_composite_backward";
+    const int rc_setup = f.setup(ctx, who, p, nty, true);
     if (rc_setup != SPLAT_OK) return rc_setup;
     const int rc_frame = surf_frame_checks(ctx, f);
     if (rc_frame != SPLAT_OK) return rc_frame;
     ARG_CHECK(ctx, c.grad_rgba32f && (c.n == 0 || (c.grad_records && c.grad_color_opacity)));
     ARG_CHECK(ctx, (((uintptr_t)c.grad_rgba32f | (uintptr_t)c.grad_records | (uintptr_t)c.grad_color_opacity) & 15) == 0);
     if (c.depth) {
-        ARG_CHECK(ctx, c.depth_f32 && c.grad_depth_f32 && (c.n == 0 || c.grad_depth) && c.depth_stride_floats >= 1);
+        ARG_CHECK(ctx, c.depth_f32 && (c.grad_depth_f32 || c.dist) && (c.n == 0 || c.grad_depth) && c.depth_stride_floats >= 1);
         ARG_CHECK(ctx, (((uintptr_t)c.depth_f32 | (uintptr_t)c.grad_depth_f32 | (uintptr_t)c.grad_depth) & 3) == 0);
+    }
+    if (c.dist) {
+        ARG_CHECK(ctx, c.depth && c.grad_distortion_f32 && ((uintptr_t)c.grad_distortion_f32 & 3) == 0);
+        const int rc_dist = surf_dist_constant(ctx, c.near, c.far, p.dist_c);
+        if (rc_dist != SPLAT_OK) return rc_dist;
+        p.grad_dist_img = (const float *)c.grad_distortion_f32;
     }
     if (c.n == 0) return SPLAT_OK; // (no splat: every list is empty)
     p.grad_img = (const float4 *)c.grad_rgba32f;
@@ -358,10 +423,57 @@ int surfel_composite_backward(splat_ctx *ctx, const SurfelBackwardCall &c) {
     p.z_stride = c.depth_stride_floats;
     p.grad_depth_img = (const float *)c.grad_depth_f32;
     p.grad_depth = (float *)c.grad_depth;
-    variant_dispatch([&](auto d, auto px) { launch_kernel(ctx, NO_STAGE, k_surfel_backward<d.value, px.value>, dim3(p.ntx, nty), dim3(256), p); },
-                     c.depth, composite_uses_px(ctx, p.ntx, nty));
-    return launch_check(ctx, c.depth ? "launch k_surfel_backward<DEPTH>" : "launch k_surfel_backward");
+    variant_dispatch([&](auto d, auto px, auto dist) {
+        if constexpr (d.value || !dist.value) // (DIST is a flag on DEPTH's kernel)
+            launch_kernel(ctx, NO_STAGE, k_surfel_backward<d.value, px.value, dist.value>, dim3(p.ntx, nty), dim3(256), p);
+    }, c.depth, composite_uses_px(ctx, p.ntx, nty), c.dist);
+    return launch_check(ctx, c.dist ? "launch k_surfel_backward<DEPTH, DIST>" : c.depth ? "launch k_surfel_backward<DEPTH>" : "launch k_surfel_backward");
 }
+
+extern "C" int splat_composite_backward_distortion(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity,
+                                                   uint32_t color_stride_vec4, const void *records, const void *tile_indices,
+                                                   const void *tile_counts, const void *tile_offsets, uint32_t width, uint32_t height,
+                                                   const void *grad_rgba32f, uint32_t n, void *grad_records, void *grad_color_opacity,
+                                                   const void *depth_f32, uint32_t depth_stride_floats, const void *grad_depth_f32,
+                                                   void *grad_depth, float near, float far, const void *grad_distortion_f32) {
+    SurfelBackwardCall a{};
+    FRAME_ARGS(a);
+    a.grad_rgba32f = grad_rgba32f, a.grad_records = grad_records, a.grad_color_opacity = grad_color_opacity;
+    a.depth_f32 = depth_f32, a.depth_stride_floats = depth_stride_floats, a.grad_depth_f32 = grad_depth_f32, a.grad_depth = grad_depth;
+    a.near = near, a.far = far, a.grad_distortion_f32 = grad_distortion_f32;
+    a.depth = a.dist = true;
+    return surfel_composite_backward(ctx, a);
+}
+
+namespace {
+
+// splat_composite_surfel_depth, and (out_distortion_f32 given: dist) splat_composite_surfel_distortion: one walk, one launch
+int surfel_depth_forward(splat_ctx *ctx, const FrameArgs &f, const void *depth_f32, uint32_t depth_stride_floats, void *out_depth_f32,
+                         void *out_alpha_f32, bool dist, float near, float far, void *out_distortion_f32) {
+    SurfDepthParams p{};
+    uint32_t nty = 0;
+    const int rc_setup = f.setup(ctx, dist ? "splat_composite_surfel_distortion" : "splat_composite_surfel_depth", p, nty, true);
+    if (rc_setup != SPLAT_OK) return rc_setup;
+    const int rc_frame = surf_frame_checks(ctx, f);
+    if (rc_frame != SPLAT_OK) return rc_frame;
+    ARG_CHECK(ctx, depth_f32 && depth_stride_floats >= 1 && (out_depth_f32 || dist));
+    ARG_CHECK(ctx, (((uintptr_t)depth_f32 | (uintptr_t)out_depth_f32 | (uintptr_t)out_alpha_f32) & 3) == 0);
+    if (dist) {
+        ARG_CHECK(ctx, out_distortion_f32 && ((uintptr_t)out_distortion_f32 & 3) == 0);
+        const int rc_dist = surf_dist_constant(ctx, near, far, p.dist_c);
+        if (rc_dist != SPLAT_OK) return rc_dist;
+        p.out_dist = (float *)out_distortion_f32;
+    }
+    p.z = (const float *)depth_f32;
+    p.z_stride = depth_stride_floats;
+    p.out_depth = (float *)out_depth_f32;
+    p.out_alpha = (float *)out_alpha_f32;
+    variant_dispatch([&](auto px, auto d) { launch_kernel(ctx, NO_STAGE, k_surfel_depth<px.value, d.value>, dim3(p.ntx, nty), dim3(256), p); },
+                     composite_uses_px(ctx, p.ntx, nty), dist);
+    return launch_check(ctx, dist ? "launch k_surfel_depth<DIST>" : "launch k_surfel_depth");
+}
+
+} // namespace
 
 extern "C" int splat_composite_surfel_depth(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity, uint32_t color_stride_vec4,
                                             const void *records, const void *tile_indices, const void *tile_counts, const void *tile_offsets,
@@ -369,21 +481,17 @@ extern "C" int splat_composite_surfel_depth(splat_ctx *ctx, const splat_composit
                                             void *out_depth_f32, void *out_alpha_f32) {
     FrameArgs f{};
     FRAME_ARGS(f);
-    SurfDepthParams p{};
-    uint32_t nty = 0;
-    const int rc_setup = f.setup(ctx, "splat_composite_surfel_depth", p, nty, true);
-    if (rc_setup != SPLAT_OK) return rc_setup;
-    const int rc_frame = surf_frame_checks(ctx, f);
-    if (rc_frame != SPLAT_OK) return rc_frame;
-    ARG_CHECK(ctx, depth_f32 && depth_stride_floats >= 1 && out_depth_f32);
-    ARG_CHECK(ctx, (((uintptr_t)depth_f32 | (uintptr_t)out_depth_f32 | (uintptr_t)out_alpha_f32) & 3) == 0);
-    p.z = (const float *)depth_f32;
-    p.z_stride = depth_stride_floats;
-    p.out_depth = (float *)out_depth_f32;
-    p.out_alpha = (float *)out_alpha_f32;
-    variant_dispatch([&](auto px) { launch_kernel(ctx, NO_STAGE, k_surfel_depth<px.value>, dim3(p.ntx, nty), dim3(256), p); },
-                     composite_uses_px(ctx, p.ntx, nty));
-    return launch_check(ctx, "launch k_surfel_depth");
+    return surfel_depth_forward(ctx, f, depth_f32, depth_stride_floats, out_depth_f32, out_alpha_f32, false, 0.0f, 0.0f, nullptr);
+}
+
+extern "C" int splat_composite_surfel_distortion(splat_ctx *ctx, const splat_composite_cfg *cfg, const void *color_opacity,
+                                                 uint32_t color_stride_vec4, const void *records, const void *tile_indices,
+                                                 const void *tile_counts, const void *tile_offsets, uint32_t width, uint32_t height,
+                                                 const void *depth_f32, uint32_t depth_stride_floats, uint32_t n, void *out_depth_f32,
+                                                 void *out_alpha_f32, float near, float far, void *out_distortion_f32) {
+    FrameArgs f{};
+    FRAME_ARGS(f);
+    return surfel_depth_forward(ctx, f, depth_f32, depth_stride_floats, out_depth_f32, out_alpha_f32, true, near, far, out_distortion_f32);
 }
 
 extern "C" int splat_project_surfel_backward(splat_ctx *ctx, const float *uniforms, const void *positions, uint32_t pos_stride_vec4,

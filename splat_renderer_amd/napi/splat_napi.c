@@ -386,6 +386,27 @@ FN(composite_surfel_depth) { /* (ctx, cfg[8], colorOpacity, cStride, records, in
     uint32_t zs = (uint32_t)arg_number(&c, 11), n = (uint32_t)arg_number(&c, 12); void *od = arg_dptr(&c, 13), *oa = arg_dptr(&c, 14); BAIL;
     return check(env, x, splat_composite_surfel_depth(x, &cfg, col, cs, rec, idx, cnt, off, w, h, z, zs, n, od, oa), mk_undefined(env));
 }
+FN(composite_surfel_distortion) { /* composite_surfel_depth's arguments (outDepth|null, outAlpha|null), then near, far, outDistortion */
+    ARGS(18); splat_ctx *x = arg_external(&c, 0); splat_composite_cfg cfg; fill_cfg(&c, 1, &cfg);
+    void *col = arg_dptr(&c, 2); uint32_t cs = (uint32_t)arg_number(&c, 3); void *rec = arg_dptr(&c, 4);
+    void *idx = arg_dptr(&c, 5), *cnt = arg_dptr(&c, 6), *off = arg_dptr(&c, 7);
+    uint32_t w = (uint32_t)arg_number(&c, 8), h = (uint32_t)arg_number(&c, 9); void *z = arg_dptr(&c, 10);
+    uint32_t zs = (uint32_t)arg_number(&c, 11), n = (uint32_t)arg_number(&c, 12); void *od = arg_dptr(&c, 13), *oa = arg_dptr(&c, 14);
+    float near_ = (float)arg_number(&c, 15), far_ = (float)arg_number(&c, 16); void *odist = arg_dptr(&c, 17); BAIL;
+    return check(env, x, splat_composite_surfel_distortion(x, &cfg, col, cs, rec, idx, cnt, off, w, h, z, zs, n, od, oa, near_, far_, odist),
+                 mk_undefined(env));
+}
+FN(composite_backward_distortion) { /* composite_backward_depth's arguments (gradDepthImage|null), then near, far, gradDistortionImage */
+    ARGS(21); splat_ctx *x = arg_external(&c, 0); splat_composite_cfg cfg; fill_cfg(&c, 1, &cfg);
+    void *col = arg_dptr(&c, 2); uint32_t cs = (uint32_t)arg_number(&c, 3); void *rec = arg_dptr(&c, 4);
+    void *idx = arg_dptr(&c, 5), *cnt = arg_dptr(&c, 6), *off = arg_dptr(&c, 7);
+    uint32_t w = (uint32_t)arg_number(&c, 8), h = (uint32_t)arg_number(&c, 9); void *gimg = arg_dptr(&c, 10);
+    uint32_t n = (uint32_t)arg_number(&c, 11); void *grec = arg_dptr(&c, 12), *gcol = arg_dptr(&c, 13);
+    void *z = arg_dptr(&c, 14); uint32_t zs = (uint32_t)arg_number(&c, 15); void *gdimg = arg_dptr(&c, 16), *gz = arg_dptr(&c, 17);
+    float near_ = (float)arg_number(&c, 18), far_ = (float)arg_number(&c, 19); void *gdist = arg_dptr(&c, 20); BAIL;
+    return check(env, x, splat_composite_backward_distortion(x, &cfg, col, cs, rec, idx, cnt, off, w, h, gimg, n, grec, gcol, z, zs, gdimg, gz,
+                                                             near_, far_, gdist), mk_undefined(env));
+}
 FN(project_surfel_backward) { /* (ctx, Float32Array(22), positions, posStride, scales, scaleStride, rotations, rotStride, n, gradRecords, gradClipW|null, gradPositions, gradScales, gradRotations) */
     ARGS(14); splat_ctx *x = arg_external(&c, 0); size_t ub = 0; float *u = arg_hostbuf(&c, 1, &ub);
     void *pos = arg_dptr(&c, 2); uint32_t ps = (uint32_t)arg_number(&c, 3); void *scl = arg_dptr(&c, 4); uint32_t ss = (uint32_t)arg_number(&c, 5);
@@ -1057,7 +1078,8 @@ static napi_value init(napi_env env, napi_value exports) {
         EXPORT(composite_backward_abs), EXPORT(composite_backward_det_abs_workspace_bytes), EXPORT(composite_backward_det_abs),
         EXPORT(density_accumulate_abs),
         EXPORT(composite_features), EXPORT(composite_features_backward),
-        EXPORT(project_surfel), EXPORT(composite_surfel_depth), EXPORT(project_surfel_backward),
+        EXPORT(project_surfel), EXPORT(composite_surfel_depth), EXPORT(composite_surfel_distortion), EXPORT(composite_backward_distortion),
+        EXPORT(project_surfel_backward),
     };
     napi_define_properties(env, exports, sizeof d / sizeof d[0], d);
     return exports;

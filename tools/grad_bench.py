@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Gradients of ellipsoid frames (GPU box only): python tools/grad_bench.py [--depth] [--deterministic] [--antialiased] [--importance] [--absgrad] [--features K[,K]] [--surfel] [--camera | --loss | --optimizer] [C1,C2] [K] [R]
+"""Gradients of ellipsoid frames (GPU box only): python tools/grad_bench.py [--depth] [--deterministic] [--antialiased] [--importance] [--absgrad] [--features K[,K]] [--surfel [--distortion]] [--camera | --loss | --optimizer] [C1,C2] [K] [R]
 
 tools/ellipsoid_bench.py's scenes and method (the scene's positions, sigma = radius / 2 per axis times a random factor in
 [e^-0.3, e^0.3], random rotations, SH of degree 3 with the scene's opacity; R rounds of K calls per kind, kinds alternating
@@ -54,6 +54,14 @@ bin, composite) and its backward (backward_surfel); with --depth the forward wit
 cfg.footprint = SURFEL over the surfel frame's own lists (composite_backward_surfel(_depth): 12 or 13 wave sums per entry against
 9 or 10, and one rcp per pair), splat_composite_surfel_depth alone (surfel_depth_forward) and splat_project_surfel_backward alone
 with a random grad_clip_w (project_backward_surfel); each one's ratio to its ellipsoid peer, and the surfel frame's own pairs.
+--surfel --distortion (implies --depth) adds the depth-distortion map in the same rounds: the staged forward with the map
+(forward_surfel_distortion: splat_composite_surfel_distortion in place of splat_composite_surfel_depth) beside
+forward_surfel_depth and its backward (backward_surfel_distortion); the two entry points alone (surfel_distortion_forward beside
+surfel_depth_forward; composite_backward_surfel_distortion, the one fused launch with all three upstreams, beside
+composite_backward_surfel_depth); and, for context, what the centre-depth recipe costs on the same lists: splat_composite_features
+and its backward with K = 3 under the surfel footprint (surfel_features_3, surfel_features_backward_3), whose sum with
+composite_backward_surfel_depth is centre_recipe_backward_ms.  fused_backward_over_depth_ms is what the map adds to the depth
+backward; a second replay of the lists would add surfel_features_backward_3_ms.
 
 --camera adds the camera gradients: splat_project_ellipsoid_backward_camera without and with grad_depth (all of its launches:
 the per-splat kernel with the per-wave sums, then k_camera_sum_slices above 1024 partials, then k_camera_sum) beside
@@ -159,14 +167,16 @@ if "--features" in sys.argv[1:]:
     at = sys.argv.index("--features")
     feature_ks = [int(v) for v in sys.argv[at + 1].split(",")]
     del sys.argv[at:at + 2]
-argv = [a for a in sys.argv[1:] if a not in ("--depth", "--camera", "--loss", "--normal-loss", "--optimizer", "--deterministic", "--antialiased", "--importance", "--absgrad", "--surfel")]
+argv = [a for a in sys.argv[1:] if a not in ("--depth", "--camera", "--loss", "--normal-loss", "--optimizer", "--deterministic", "--antialiased", "--importance", "--absgrad", "--surfel", "--distortion")]
 surfel_too = "--surfel" in sys.argv[1:]
 abs_too = "--absgrad" in sys.argv[1:]
 aa_too = "--antialiased" in sys.argv[1:]
 importance_too = "--importance" in sys.argv[1:]
 det_too = "--deterministic" in sys.argv[1:]
 optimizer_only = "--optimizer" in sys.argv[1:]
-depth_too = "--depth" in sys.argv[1:]
+dist_too = "--distortion" in sys.argv[1:] and surfel_too
+depth_too = "--depth" in sys.argv[1:] or dist_too
+DIST_RANGE = (0.2, 100.0)  # near, far of the distortion map's depth mapping
 camera_too = "--camera" in sys.argv[1:]
 loss_only = "--loss" in sys.argv[1:]
 normal_loss_only = "--normal-loss" in sys.argv[1:]
@@ -851,6 +861,34 @@ for name in names:
                                                                                               gz.data_ptr()),
             })
             forwards["backward_surfel_depth"] = forward_surfel_depth
+        if dist_too:
+            gdist = (torch.rand((h, w), device="cuda") * 2 - 1) * 100.0
+            sdist = torch.empty((h, w), device="cuda")
+            sfeat = dict(f=torch.rand((n, 3), device="cuda"), out=torch.empty((h, w, 3), device="cuda"),
+                         g=torch.rand((h, w, 3), device="cuda") * 2 - 1, gf=torch.zeros((n, 3), device="cuda"))
+
+            def forward_surfel_distortion():
+                rec, cw, aux = AG.project_surfels(u, means, scales, rots, return_depth=True)
+                col = AG.sh_colors(u[16:19], means, shs, 3, ops)
+                rgb, _, depth, dist = AG.rasterize(rec, col, aux, w, h, depths=cw, distortion=DIST_RANGE)
+                dz = torch.where(torch.isfinite(depth), depth, torch.zeros_like(depth))
+                state.update(srec=rec, scol=col, saux=aux, scw=cw, loss=(rgb * gimg).sum() + (dz * gdimg).sum() + (dist * gdist).sum())
+            work.update({
+                "forward_surfel_distortion": forward_surfel_distortion,
+                "backward_surfel_distortion": None,
+                "surfel_distortion_forward": lambda: lib.splat_composite_surfel_distortion(
+                    cx.ctx, C.byref(scfg), col.data_ptr(), 1, srec.data_ptr(), *slists, w, h, scw.data_ptr(), 1, n, sdepth.data_ptr(), None,
+                    DIST_RANGE[0], DIST_RANGE[1], sdist.data_ptr()),
+                "composite_backward_surfel_distortion": lambda: lib.splat_composite_backward_distortion(
+                    cx.ctx, C.byref(scfg), col.data_ptr(), 1, srec.data_ptr(), *slists, w, h, g4.data_ptr(), n, grec.data_ptr(), gcol.data_ptr(),
+                    scw.data_ptr(), 1, gdimg.data_ptr(), gz.data_ptr(), DIST_RANGE[0], DIST_RANGE[1], gdist.data_ptr()),
+                "surfel_features_3": lambda: lib.splat_composite_features(
+                    cx.ctx, C.byref(scfg), col.data_ptr(), 1, srec.data_ptr(), *slists, w, h, sfeat["f"].data_ptr(), 3, 3, n, sfeat["out"].data_ptr()),
+                "surfel_features_backward_3": lambda: lib.splat_composite_features_backward(
+                    cx.ctx, C.byref(scfg), col.data_ptr(), 1, srec.data_ptr(), *slists, w, h, sfeat["f"].data_ptr(), 3, 3, sfeat["g"].data_ptr(), n,
+                    grec.data_ptr(), gcol.data_ptr(), sfeat["gf"].data_ptr(), 3),
+            })
+            forwards["backward_surfel_distortion"] = forward_surfel_distortion
     if aa_too:
         grho = torch.rand(n, device="cuda") * 2 - 1
 
@@ -953,6 +991,16 @@ for name in names:
             _lib.check(work[a](), cx.ctx)  # (the timed calls' return codes were not looked at)
         extra.update({f"{a}_over_{b}": round(med[a] / med[b], 3) for a, b in peers})
         extra["surfel_pairs"] = surfel_pairs
+        if dist_too:
+            for a in ("surfel_distortion_forward", "composite_backward_surfel_distortion", "surfel_features_3", "surfel_features_backward_3"):
+                _lib.check(work[a](), cx.ctx)  # (the timed calls' return codes were not looked at)
+            extra.update({f"{a}_over_{b}": round(med[a] / med[b], 3) for a, b in (
+                ("forward_surfel_distortion", "forward_surfel_depth"), ("backward_surfel_distortion", "backward_surfel_depth"),
+                ("surfel_distortion_forward", "surfel_depth_forward"),
+                ("composite_backward_surfel_distortion", "composite_backward_surfel_depth"))})
+            extra["fused_backward_over_depth_ms"] = round(med["composite_backward_surfel_distortion"] - med["composite_backward_surfel_depth"], 4)
+            extra["centre_recipe_forward_ms"] = round(med["surfel_depth_forward"] + med["surfel_features_3"], 4)
+            extra["centre_recipe_backward_ms"] = round(med["composite_backward_surfel_depth"] + med["surfel_features_backward_3"], 4)
     if aa_too:
         extra.update({f"{a}_over_{b}": round(med[a] / med[b], 3) for a, b in (
             ("forward_aa", "forward"), ("backward_aa", "backward"), ("project_backward_aa", "project_backward"))})
