@@ -1125,6 +1125,29 @@ int splat_densify_geometry(splat_ctx *ctx, const void *rows, uint32_t n_out, con
                            const void *rotations, const splat_densify_cfg *cfg, void *means_out, void *log_scales_out);
 int splat_densify_rows(splat_ctx *ctx, const void *rows, uint32_t n_out, const void *in, void *out, uint32_t floats_per_row,
                        uint32_t mode);
+/* Density control for 2D Gaussian surfels ("2D Gaussian surfels", above): the three entry points above that read what an
+ * ellipsoid and a surfel do not share.  A surfel's log_scales plane is n x 2 floats (sx, sy), 4-byte aligned; everything not
+ * said here - the other arguments, the checks, the stream, no atomics, n = 0 - is the peer's, and splat_adam_step and
+ * splat_densify_rows move a surfel's planes as they are (floats_per_row = 2 for the log-scales and their moments).
+ * splat_density_accumulate_surfel: splat_density_accumulate over splat_project_surfel's records, whose B10 and q are not zero.
+ * With (x0, y0, x1, y1) the record's exact screen extent (csrc/disc.h, disc_bounds(): binary32, one rounding per operator; the
+ * box splat_project_surfel wrote to `projected`), surfel i is VISIBLE when the extent exists (a culled all-zero record has none,
+ * nor has one whose disc reaches the eye's plane) and x1 > 0, x0 < W, y1 > 0, y0 < H.  Its radius is
+ * 0.5 max(x1 - x0, y1 - y0): the bits of projected[i].screenRadius.  grad_accum, denom, max_radius and visible_u8 as above.
+ * SPLAT_ERR_INVALID also for n >= 2^30.
+ * splat_densify_plan_surfel: splat_densify_plan with s = exp(max(l0, l1)) (NaN if either is) of the n x 2 plane: the same
+ * workspace function, rows, cap rule and single host synchronisation.
+ * splat_densify_geometry_surfel: log_scales and log_scales_out are n x 2 and n_out x 2.  Kinds 0 and 1 copy; child k of a split
+ * gets log sigma - log 1.6 on both scales (rounded once) and mu + R[:,0] sx xi_x + R[:,1] sy xi_y, R as csrc/surfel.h forms it,
+ * (xi_x, xi_y) the first two normals of splat_densify_geometry's Philox draw for (parent, k); the third is not used.  This is
+ * 2DGS's split, stds = (sx, sy, 0): the children stay in the parent's plane. */
+int splat_density_accumulate_surfel(splat_ctx *ctx, const void *records, const void *grad_records, uint32_t n, uint32_t width,
+                                    uint32_t height, void *grad_accum, void *denom, void *max_radius, void *visible_u8);
+int splat_densify_plan_surfel(splat_ctx *ctx, const void *log_scales, const void *opacity_logits, const void *grad_accum,
+                              const void *denom, const void *max_radius, uint32_t n, const splat_densify_cfg *cfg, void *workspace,
+                              uint64_t workspace_bytes, void *rows, uint32_t *n_out_host, uint32_t *counts4_host);
+int splat_densify_geometry_surfel(splat_ctx *ctx, const void *rows, uint32_t n_out, const void *means, const void *log_scales,
+                                  const void *rotations, const splat_densify_cfg *cfg, void *means_out, void *log_scales_out);
 
 /* ---- MCMC relocation: 3DGS-MCMC's way of deciding where the splats live (Kheradmand et al., "3D Gaussian Splatting as Markov
  * Chain Monte Carlo", 2024; an extension) -----------------------------------------------------------------------------------------

@@ -13,8 +13,8 @@ from .host import (Buffer, CommandEncoder, ComputeShaderRenderer, DepthKeyExtrac
                    SplatProjector, SplatPropertyManager, TileRenderer)
 from .frameloop import FrameLoop, MouseEvent, OrbitCameraController, SdfSplatSource, read_png, write_png  # noqa: F401
 from . import sdf  # noqa: F401
-from .ply import load_gaussian_ply, load_point_ply, save_gaussian_ply, save_mesh_ply  # noqa: F401
-from .fit import GaussianFit  # noqa: F401
+from .ply import load_gaussian_ply, load_point_ply, load_surfel_ply, save_gaussian_ply, save_mesh_ply, save_surfel_ply  # noqa: F401
+from .fit import GaussianFit, SurfelFit  # noqa: F401
 from .tsdf import TsdfVolume  # noqa: F401  (torch is imported when a volume is first made)
 from .autograd import depth_normals, normal_consistency_loss, splat_normals  # noqa: F401  (torch is imported when one is first called)
 from .autograd import project_surfels, render_surfels, surfel_normals  # noqa: F401  (2D Gaussian surfels: autograd's docstring)

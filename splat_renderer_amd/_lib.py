@@ -167,6 +167,10 @@ SIGNATURES = {
                                 C.POINTER(_u32)]),
     "splat_densify_geometry": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, C.POINTER(DensifyCfg), _vp, _vp]),
     "splat_densify_rows": (_i, [_vp, _vp, _u32, _vp, _vp, _u32, _u32]),
+    "splat_density_accumulate_surfel": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "splat_densify_plan_surfel": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, C.POINTER(DensifyCfg), _vp, C.c_uint64, _vp, C.POINTER(_u32),
+                                       C.POINTER(_u32)]),
+    "splat_densify_geometry_surfel": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, C.POINTER(DensifyCfg), _vp, _vp]),
     "splat_mcmc_sample_workspace_bytes": (C.c_uint64, [_u32]),
     "splat_mcmc_sample": (_i, [_vp, _vp, _u32, _u32, _u32, _f64, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, C.POINTER(_u32)]),
     "splat_mcmc_apply": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _f64, C.POINTER(McmcPlanes)]),

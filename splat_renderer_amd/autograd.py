@@ -853,13 +853,15 @@ def surfel_normals(rotations, means, eye):
 
 
 def render_surfels(camera_or_uniforms, means, scales, rotations, opacities, colors=None, sh=None, width=None, height=None, degree=None,
-                   return_depth=False, features=None, return_aux=False, distortion=None):
+                   return_depth=False, features=None, return_aux=False, distortion=None, return_records=False):
     """render_gaussians' surfel twin: project_surfels, the colour (sh_colors when `sh` is given, else cat(colors, opacities)),
     rasterize.  Returns (rgb (H, W, 3), alpha (H, W)); return_depth=True: (rgb, alpha, depth (H, W)), the ray-surfel
     intersection depth map sum w z rd / sum w in clip w (depth_kind="z" for depth_normals and normal_consistency_loss), +inf where
     nothing contributed; features ((n, K) or (n,)): rasterize's, blended with the surfel image's own weights, the map after depth:
     (rgb, alpha[, depth], feat[, aux]); return_aux=True appends the frame's ProjectedSplats.  distortion=(near, far) implies
-    return_depth=True and adds rasterize's depth-distortion map after depth: (rgb, alpha, depth, dist[, feat][, aux])."""
+    return_depth=True and adds rasterize's depth-distortion map after depth: (rgb, alpha, depth, dist[, feat][, aux]).
+    return_records=True appends, last of all, the frame's differentiable records (n, 8): what SurfelFit keeps for its density
+    statistics."""
     if width is None or height is None:
         raise SplatError(-1, "render_surfels needs width and height")
     if distortion is not None:
@@ -885,7 +887,8 @@ def render_surfels(camera_or_uniforms, means, scales, rotations, opacities, colo
     else:
         raise SplatError(-1, "render_surfels needs colors or sh")
     out = rasterize(rec, col, aux, width, height, depths=depths, features=features, distortion=distortion)
-    return (*out, aux) if return_aux else out
+    out = (*out, aux) if return_aux else out
+    return (*out, rec) if return_records else out
 
 
 def sh_colors(eye, means, sh, degree, opacities):

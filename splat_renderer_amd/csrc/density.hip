@@ -12,10 +12,13 @@
 //                         element the same bits.
 // k_density_accumulate    one thread per splat: visibility of the record's 3-sigma box, the three running statistics, the mask.
 //                         <PLANE2>: the gradient read from an n x 2 plane (splat_density_accumulate_abs) instead of columns 0, 1
-//                         of the n x 8 plane; everything else the same code.
+//                         of the n x 8 plane; everything else the same code.  <SURFEL>: the visibility and the radius from
+//                         disc_bounds() of the record itself (splat_density_accumulate_surfel: a surfel's B10 and q are not 0).
 // k_densify_classify ..   splat_densify_plan: classify -> scan(alive), scan(wants) -> grant under the cap -> scan(rows per
 // k_densify_fill          splat), scan(granted clones) -> one thread per splat writes its rows.  The scans are scan.hip's.
 // k_densify_geometry      one thread per OUTPUT row: means and log-scales, the split children drawn with Philox4x32-10 (philox.h).
+// k_densify_classify and k_densify_geometry are templates on NS, the log-scales per row: 3 for an ellipsoid, 2 for a 2D Gaussian
+// surfel (the _surfel entry points), whose split children stay in its plane: 2DGS's stds = (sx, sy, 0).
 // k_densify_rows<VEC>     one thread per float (float4) of the OUTPUT plane: a gather, contiguous writes.
 // No atomics anywhere: the same inputs give the same bits.
 //
@@ -23,6 +26,7 @@
 // with SH of degree 3, 1.6 ms at the 5.1 TB/s copy rate ("Density control and optimiser";
 // tools/grad_bench.py --optimizer measures the step against that floor).
 #include "common.h"
+#include "disc.h"
 #include "philox.h"
 
 namespace {
@@ -122,7 +126,18 @@ __device__ __forceinline__ bool density_visible(float4 ra, float4 rb, float w, f
     return !culled && ra.x + hx > 0.0f && ra.x - hx < w && ra.y + hy > 0.0f && ra.y - hy < h; // (false for a NaN)
 }
 
-template <bool PLANE2>
+// A surfel record's own rule: disc_bounds() (disc.h; binary32, bit for bit the box splat_project_surfel wrote to `projected`),
+// visible when the box overlaps the screen, radius half its larger side: projected[i].screenRadius.
+__device__ __forceinline__ bool density_visible_surfel(float4 ra, float4 rb, float w, float h, float &radius) {
+#pragma clang fp contract(off)
+    const DiscRecord rec = {ra, rb};
+    float4 b;
+    const bool ok = disc_bounds(rec, b);
+    radius = 0.5f * fmaxf(b.z - b.x, b.w - b.y);
+    return ok && b.z > 0.0f && b.x < w && b.w > 0.0f && b.y < h;
+}
+
+template <bool PLANE2, bool SURFEL>
 __global__ __launch_bounds__(DT) void k_density_accumulate(const float4 *__restrict__ rec, const void *__restrict__ grad, uint32_t n, float w,
                                                            float h, float *__restrict__ grad_accum, float *__restrict__ denom,
                                                            float *__restrict__ max_radius, uint8_t *__restrict__ vis) {
@@ -130,7 +145,9 @@ __global__ __launch_bounds__(DT) void k_density_accumulate(const float4 *__restr
     if (i >= n) return;
     const float4 ra = rec[2 * (size_t)i], rb = rec[2 * (size_t)i + 1];
     float radius;
-    const bool on = density_visible(ra, rb, w, h, radius);
+    bool on;
+    if constexpr (SURFEL) on = density_visible_surfel(ra, rb, w, h, radius);
+    else on = density_visible(ra, rb, w, h, radius);
     vis[i] = on ? 1 : 0;
     if (!on) return;
     float gx, gy;
@@ -151,15 +168,22 @@ __global__ __launch_bounds__(DT) void k_density_accumulate(const float4 *__restr
 enum : uint32_t { CLS_DEAD = 0, CLS_KEPT = 1, CLS_CLONE = 2, CLS_SPLIT = 3 };
 constexpr uint32_t ROW_PARENT_MASK = 0x3fffffffu;
 
+template <int NS>
 __global__ __launch_bounds__(DT) void k_densify_classify(const float *__restrict__ log_scales, const float *__restrict__ logits,
                                                          const float *__restrict__ grad_accum, const float *__restrict__ denom,
                                                          const float *__restrict__ max_radius, uint32_t n, splat_densify_cfg cfg,
                                                          uint32_t *__restrict__ cls, uint32_t *__restrict__ alive, uint32_t *__restrict__ wants) {
     const uint32_t i = blockIdx.x * DT + threadIdx.x;
     if (i >= n) return;
-    const float l0 = log_scales[3 * (size_t)i], l1 = log_scales[3 * (size_t)i + 1], l2 = log_scales[3 * (size_t)i + 2];
-    float lmax = fmaxf(fmaxf(l0, l1), l2);
-    if (l0 != l0 || l1 != l1 || l2 != l2) lmax = __builtin_nanf(""); // (fmaxf drops a NaN; the rule's max keeps it)
+    const float l0 = log_scales[NS * (size_t)i], l1 = log_scales[NS * (size_t)i + 1];
+    float lmax = fmaxf(l0, l1);
+    bool nan = l0 != l0 || l1 != l1;
+    if constexpr (NS == 3) {
+        const float l2 = log_scales[NS * (size_t)i + 2];
+        lmax = fmaxf(lmax, l2);
+        nan = nan || l2 != l2;
+    }
+    if (nan) lmax = __builtin_nanf(""); // (fmaxf drops a NaN; the rule's max keeps it)
     const float s = expf(lmax), o = 1.0f / (1.0f + expf(-logits[i])), r = max_radius[i];
     const float d = denom[i], g = d > 0.0f ? grad_accum[i] / d : 0.0f;
     const bool dead = !(o >= cfg.min_opacity) || (cfg.max_screen_radius > 0.0f && r > cfg.max_screen_radius) ||
@@ -200,34 +224,43 @@ __global__ __launch_bounds__(DT) void k_densify_fill(const uint32_t *__restrict_
 
 constexpr double LOG_SPLIT_SHRINK = 0.47000362924573555; // log 1.6
 
+template <int NS>
 __global__ __launch_bounds__(DT) void k_densify_geometry(const uint32_t *__restrict__ rows, uint32_t n_out, const float *__restrict__ means,
                                                          const float *__restrict__ log_scales, const float4 *__restrict__ rotations, uint2 key,
                                                          float *__restrict__ means_out, float *__restrict__ log_scales_out) {
     const uint32_t r = blockIdx.x * DT + threadIdx.x;
     if (r >= n_out) return;
     const uint32_t code = rows[r], parent = code & ROW_PARENT_MASK, kind = code >> 30;
-    const size_t src = 3 * (size_t)parent, dst = 3 * (size_t)r;
+    const size_t src = 3 * (size_t)parent, dst = 3 * (size_t)r, lsrc = NS * (size_t)parent, ldst = NS * (size_t)r;
     float px = means[src], py = means[src + 1], pz = means[src + 2];
-    float lx = log_scales[src], ly = log_scales[src + 1], lz = log_scales[src + 2];
+    float lx = log_scales[lsrc], ly = log_scales[lsrc + 1], lz = 0.0f;
+    if constexpr (NS == 3) lz = log_scales[lsrc + 2];
     if (kind >= 2u) {
         const uint4 x = philox4x32_10(make_uint4(parent, kind - 2u, 0u, 0u), key);
         const float3 xi = philox_normals3(x);
-        const float ex = expf(lx) * xi.x, ey = expf(ly) * xi.y, ez = expf(lz) * xi.z;
+        const float ex = expf(lx) * xi.x, ey = expf(ly) * xi.y, ez = NS == 3 ? expf(lz) * xi.z : 0.0f;
         const float4 q = rotations[parent]; // (w, x, y, z), normalised as ellipsoid_record() does
         const float k = 1.0f / sqrtf(((q.x * q.x + q.y * q.y) + q.z * q.z) + q.w * q.w);
         const float qr = q.x * k, qx = q.y * k, qy = q.z * k, qz = q.w * k;
         const float r00 = 1.0f - 2.0f * (qy * qy + qz * qz), r01 = 2.0f * (qx * qy - qr * qz), r02 = 2.0f * (qx * qz + qr * qy);
         const float r10 = 2.0f * (qx * qy + qr * qz), r11 = 1.0f - 2.0f * (qx * qx + qz * qz), r12 = 2.0f * (qy * qz - qr * qx);
         const float r20 = 2.0f * (qx * qz - qr * qy), r21 = 2.0f * (qy * qz + qr * qx), r22 = 1.0f - 2.0f * (qx * qx + qy * qy);
-        px += (r00 * ex + r01 * ey) + r02 * ez;
-        py += (r10 * ex + r11 * ey) + r12 * ez;
-        pz += (r20 * ex + r21 * ey) + r22 * ez;
+        if constexpr (NS == 3) {
+            px += (r00 * ex + r01 * ey) + r02 * ez;
+            py += (r10 * ex + r11 * ey) + r12 * ez;
+            pz += (r20 * ex + r21 * ey) + r22 * ez;
+        } else { // a surfel: the tangent axes only (csrc/surfel.h's R[:,0], R[:,1]); the third normal is not used
+            px += r00 * ex + r01 * ey;
+            py += r10 * ex + r11 * ey;
+            pz += r20 * ex + r21 * ey;
+        }
         lx = (float)((double)lx - LOG_SPLIT_SHRINK); // (in float64: rounded once, also where log sigma is near log 1.6)
         ly = (float)((double)ly - LOG_SPLIT_SHRINK);
         lz = (float)((double)lz - LOG_SPLIT_SHRINK);
     }
     means_out[dst] = px; means_out[dst + 1] = py; means_out[dst + 2] = pz;
-    log_scales_out[dst] = lx; log_scales_out[dst + 1] = ly; log_scales_out[dst + 2] = lz;
+    log_scales_out[ldst] = lx; log_scales_out[ldst + 1] = ly;
+    if constexpr (NS == 3) log_scales_out[ldst + 2] = lz;
 }
 
 // `per` = floats (VEC: float4s) per row
@@ -281,18 +314,21 @@ extern "C" int splat_adam_step(splat_ctx *ctx, void *param, const void *grad, vo
 
 // splat_density_accumulate (grad: the n x 8 plane, 16-byte aligned) and splat_density_accumulate_abs (plane2: the n x 2 plane,
 // 8-byte aligned): one kernel, the gradient's layout its template argument
-static int density_accumulate(splat_ctx *ctx, const void *records, const void *grad, bool plane2, uint32_t n, uint32_t width, uint32_t height,
+static int density_accumulate(splat_ctx *ctx, const void *records, const void *grad, bool plane2, bool surfel, uint32_t n, uint32_t width, uint32_t height,
                               void *grad_accum, void *denom, void *max_radius, void *visible_u8) {
     if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
     if (n == 0) return SPLAT_OK;
     ARG_CHECK(ctx, records && grad && grad_accum && denom && max_radius && visible_u8 && width >= 1 && height >= 1);
     ARG_CHECK(ctx, ((uintptr_t)records & 15) == 0 && ((uintptr_t)grad & (plane2 ? 7 : 15)) == 0);
     ARG_CHECK(ctx, (((uintptr_t)grad_accum | (uintptr_t)denom | (uintptr_t)max_radius) & 3) == 0);
-    if (plane2)
-        hipLaunchKernelGGL(k_density_accumulate<true>, dim3(div_up(n, DT)), dim3(DT), 0, ctx->stream, (const float4 *)records, grad, n, (float)width,
+    if (surfel)
+        hipLaunchKernelGGL((k_density_accumulate<false, true>), dim3(div_up(n, DT)), dim3(DT), 0, ctx->stream, (const float4 *)records, grad, n,
+                           (float)width, (float)height, (float *)grad_accum, (float *)denom, (float *)max_radius, (uint8_t *)visible_u8);
+    else if (plane2)
+        hipLaunchKernelGGL((k_density_accumulate<true, false>), dim3(div_up(n, DT)), dim3(DT), 0, ctx->stream, (const float4 *)records, grad, n, (float)width,
                            (float)height, (float *)grad_accum, (float *)denom, (float *)max_radius, (uint8_t *)visible_u8);
     else
-        hipLaunchKernelGGL(k_density_accumulate<false>, dim3(div_up(n, DT)), dim3(DT), 0, ctx->stream, (const float4 *)records, grad, n, (float)width,
+        hipLaunchKernelGGL((k_density_accumulate<false, false>), dim3(div_up(n, DT)), dim3(DT), 0, ctx->stream, (const float4 *)records, grad, n, (float)width,
                            (float)height, (float *)grad_accum, (float *)denom, (float *)max_radius, (uint8_t *)visible_u8);
     LAUNCH_CHECK(ctx, "k_density_accumulate");
     return SPLAT_OK;
@@ -300,19 +336,27 @@ static int density_accumulate(splat_ctx *ctx, const void *records, const void *g
 
 extern "C" int splat_density_accumulate(splat_ctx *ctx, const void *records, const void *grad_records, uint32_t n, uint32_t width,
                                         uint32_t height, void *grad_accum, void *denom, void *max_radius, void *visible_u8) {
-    return density_accumulate(ctx, records, grad_records, false, n, width, height, grad_accum, denom, max_radius, visible_u8);
+    return density_accumulate(ctx, records, grad_records, false, false, n, width, height, grad_accum, denom, max_radius, visible_u8);
 }
 
 extern "C" int splat_density_accumulate_abs(splat_ctx *ctx, const void *records, const void *grad_center_abs, uint32_t n, uint32_t width,
                                             uint32_t height, void *grad_accum, void *denom, void *max_radius, void *visible_u8) {
-    return density_accumulate(ctx, records, grad_center_abs, true, n, width, height, grad_accum, denom, max_radius, visible_u8);
+    return density_accumulate(ctx, records, grad_center_abs, true, false, n, width, height, grad_accum, denom, max_radius, visible_u8);
+}
+
+extern "C" int splat_density_accumulate_surfel(splat_ctx *ctx, const void *records, const void *grad_records, uint32_t n, uint32_t width,
+                                               uint32_t height, void *grad_accum, void *denom, void *max_radius, void *visible_u8) {
+    if (n >= DENSIFY_MAX_SPLATS) return ctx_fail(ctx, SPLAT_ERR_INVALID, "splat_density_accumulate_surfel: n must be below 2^30");
+    return density_accumulate(ctx, records, grad_records, false, true, n, width, height, grad_accum, denom, max_radius, visible_u8);
 }
 
 extern "C" uint64_t splat_densify_plan_workspace_bytes(uint32_t n) { return 4 * (uint64_t)plan_plane_bytes(n) + 256; }
 
-extern "C" int splat_densify_plan(splat_ctx *ctx, const void *log_scales, const void *opacity_logits, const void *grad_accum, const void *denom,
-                                  const void *max_radius, uint32_t n, const splat_densify_cfg *cfg, void *workspace, uint64_t workspace_bytes,
-                                  void *rows, uint32_t *n_out_host, uint32_t *counts4_host) {
+// splat_densify_plan (ns = 3) and splat_densify_plan_surfel (ns = 2): one plan, the log-scales per row the classify kernel's
+// template argument
+static int densify_plan(splat_ctx *ctx, int ns, const void *log_scales, const void *opacity_logits, const void *grad_accum, const void *denom,
+                        const void *max_radius, uint32_t n, const splat_densify_cfg *cfg, void *workspace, uint64_t workspace_bytes, void *rows,
+                        uint32_t *n_out_host, uint32_t *counts4_host) {
     if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
     ARG_CHECK(ctx, cfg && n_out_host && counts4_host);
     if (n >= DENSIFY_MAX_SPLATS) return ctx_fail(ctx, SPLAT_ERR_INVALID, "splat_densify_plan: n must be below 2^30 (a row keeps its parent in 30 bits)");
@@ -331,8 +375,12 @@ extern "C" int splat_densify_plan(splat_ctx *ctx, const void *log_scales, const 
     int rc = ctx_ensure_pinned(ctx, 4 * sizeof(uint32_t));
     if (rc != SPLAT_OK) return rc;
     const dim3 grid(div_up(n, DT)), block(DT);
-    hipLaunchKernelGGL(k_densify_classify, grid, block, 0, ctx->stream, (const float *)log_scales, (const float *)opacity_logits,
-                       (const float *)grad_accum, (const float *)denom, (const float *)max_radius, n, *cfg, cls, a, c);
+    if (ns == 2)
+        hipLaunchKernelGGL(k_densify_classify<2>, grid, block, 0, ctx->stream, (const float *)log_scales, (const float *)opacity_logits,
+                           (const float *)grad_accum, (const float *)denom, (const float *)max_radius, n, *cfg, cls, a, c);
+    else
+        hipLaunchKernelGGL(k_densify_classify<3>, grid, block, 0, ctx->stream, (const float *)log_scales, (const float *)opacity_logits,
+                           (const float *)grad_accum, (const float *)denom, (const float *)max_radius, n, *cfg, cls, a, c);
     LAUNCH_CHECK(ctx, "k_densify_classify");
     if ((rc = scan_exclusive_u32(ctx, a, a, n, tot + 0)) != SPLAT_OK) return rc;
     if ((rc = scan_exclusive_u32(ctx, c, b, n, tot + 1)) != SPLAT_OK) return rc;
@@ -354,8 +402,22 @@ extern "C" int splat_densify_plan(splat_ctx *ctx, const void *log_scales, const 
     return SPLAT_OK;
 }
 
-extern "C" int splat_densify_geometry(splat_ctx *ctx, const void *rows, uint32_t n_out, const void *means, const void *log_scales,
-                                      const void *rotations, const splat_densify_cfg *cfg, void *means_out, void *log_scales_out) {
+extern "C" int splat_densify_plan(splat_ctx *ctx, const void *log_scales, const void *opacity_logits, const void *grad_accum, const void *denom,
+                                  const void *max_radius, uint32_t n, const splat_densify_cfg *cfg, void *workspace, uint64_t workspace_bytes,
+                                  void *rows, uint32_t *n_out_host, uint32_t *counts4_host) {
+    return densify_plan(ctx, 3, log_scales, opacity_logits, grad_accum, denom, max_radius, n, cfg, workspace, workspace_bytes, rows, n_out_host,
+                        counts4_host);
+}
+
+extern "C" int splat_densify_plan_surfel(splat_ctx *ctx, const void *log_scales, const void *opacity_logits, const void *grad_accum,
+                                         const void *denom, const void *max_radius, uint32_t n, const splat_densify_cfg *cfg, void *workspace,
+                                         uint64_t workspace_bytes, void *rows, uint32_t *n_out_host, uint32_t *counts4_host) {
+    return densify_plan(ctx, 2, log_scales, opacity_logits, grad_accum, denom, max_radius, n, cfg, workspace, workspace_bytes, rows, n_out_host,
+                        counts4_host);
+}
+
+static int densify_geometry(splat_ctx *ctx, int ns, const void *rows, uint32_t n_out, const void *means, const void *log_scales,
+                            const void *rotations, const splat_densify_cfg *cfg, void *means_out, void *log_scales_out) {
     if (!ctx) return ctx_fail(nullptr, SPLAT_ERR_INVALID, "ctx is NULL");
     ARG_CHECK(ctx, cfg);
     if (n_out == 0) return SPLAT_OK;
@@ -363,11 +425,27 @@ extern "C" int splat_densify_geometry(splat_ctx *ctx, const void *rows, uint32_t
     ARG_CHECK(ctx, (((uintptr_t)rows | (uintptr_t)means | (uintptr_t)log_scales | (uintptr_t)means_out | (uintptr_t)log_scales_out) & 3) == 0 &&
                        ((uintptr_t)rotations & 15) == 0);
     ARG_CHECK(ctx, means_out != means && log_scales_out != log_scales);
-    hipLaunchKernelGGL(k_densify_geometry, dim3(div_up(n_out, DT)), dim3(DT), 0, ctx->stream, (const uint32_t *)rows, n_out, (const float *)means,
-                       (const float *)log_scales, (const float4 *)rotations, make_uint2((uint32_t)cfg->seed, (uint32_t)(cfg->seed >> 32)),
-                       (float *)means_out, (float *)log_scales_out);
+    const uint2 key = make_uint2((uint32_t)cfg->seed, (uint32_t)(cfg->seed >> 32));
+    if (ns == 2)
+        hipLaunchKernelGGL(k_densify_geometry<2>, dim3(div_up(n_out, DT)), dim3(DT), 0, ctx->stream, (const uint32_t *)rows, n_out,
+                           (const float *)means, (const float *)log_scales, (const float4 *)rotations, key, (float *)means_out,
+                           (float *)log_scales_out);
+    else
+        hipLaunchKernelGGL(k_densify_geometry<3>, dim3(div_up(n_out, DT)), dim3(DT), 0, ctx->stream, (const uint32_t *)rows, n_out,
+                           (const float *)means, (const float *)log_scales, (const float4 *)rotations, key, (float *)means_out,
+                           (float *)log_scales_out);
     LAUNCH_CHECK(ctx, "k_densify_geometry");
     return SPLAT_OK;
+}
+
+extern "C" int splat_densify_geometry(splat_ctx *ctx, const void *rows, uint32_t n_out, const void *means, const void *log_scales,
+                                      const void *rotations, const splat_densify_cfg *cfg, void *means_out, void *log_scales_out) {
+    return densify_geometry(ctx, 3, rows, n_out, means, log_scales, rotations, cfg, means_out, log_scales_out);
+}
+
+extern "C" int splat_densify_geometry_surfel(splat_ctx *ctx, const void *rows, uint32_t n_out, const void *means, const void *log_scales,
+                                             const void *rotations, const splat_densify_cfg *cfg, void *means_out, void *log_scales_out) {
+    return densify_geometry(ctx, 2, rows, n_out, means, log_scales, rotations, cfg, means_out, log_scales_out);
 }
 
 extern "C" int splat_densify_rows(splat_ctx *ctx, const void *rows, uint32_t n_out, const void *in, void *out, uint32_t floats_per_row,

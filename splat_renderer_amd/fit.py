@@ -139,6 +139,32 @@ where alpha >= alpha_min, and marching tetrahedra pull the zero surface out: ind
 every run.  The depth is the blended distance to the splats' centres, so the surface sits where the fit's mass does: a fit
 trained with normal_consistency_loss and the distortion term has flat, thin splats and gives the cleaner surface.  One launch
 per view on top of the render, one host wait for the mesh's size.
+
+Fitting 2D Gaussian surfels (include/splat.h, "2D Gaussian surfels"; 2DGS, Huang et al. 2024): SurfelFit is GaussianFit with
+2DGS's parameters, log_scales (n, 2) along the two tangent axes, and the whole 2DGS objective:
+
+    fit = SurfelFit.from_points(xyz, rgb)                               # or SurfelFit(means, scales (n, 2), rotations, opacity, sh)
+    for step in range(steps):
+        rgb, alpha, depth, dist, nmap = fit.render(cam, width, height, return_depth=True, normals=True, distortion=(near, far))
+        loss = AG.photometric_loss(rgb, target)                         # L1 + D-SSIM
+        loss = loss + lam_n * AG.normal_consistency_loss(nmap, depth, cam, weight=alpha.detach(), depth_kind="z")
+        loss = loss + lam_d * dist.mean()
+        loss.backward()
+        fit.step()
+        if step % 100 == 99:
+            fit.densify_and_prune(max_splats=...)
+    fit.save_ply(path)                                                  # 2DGS's file: ply.load_surfel_ply reads it
+    mesh = fit.extract_mesh(train_cameras, width, height, voxel=0.01)
+
+render() is autograd.render_surfels: depth is the ray-surfel intersection depth in clip w, dist 2DGS's depth-distortion map, nmap
+the blended surfel normals.  step() takes the frame's statistics with splat_density_accumulate_surfel, whose visibility and screen
+radius come from the surfel record's own extent (a surfel's record has B10 and q terms the ellipsoid's rule takes for zero), then
+runs the same five Adam launches.  densify_and_prune() plans on the larger of the two scales and splits inside the surfel's
+plane (splat_densify_plan_surfel, splat_densify_geometry_surfel), min_opacity 2DGS's 0.05.  extract_mesh() fuses the intersection
+depth (depth_kind "z"), the reason to fit surfels: a flat surfel's depth is its plane, not the distance to its centre.
+from_points() starts from 2DGS's rand((n, 4)) rotations, drawn on the host from rotation_seed.  Not built for surfels (each
+raises SplatError): deterministic, antialiased and absgrad fits, update_filter_3d, relocate, add_new, inject_noise and the
+importance scores.
 """
 import ctypes as C
 import math
@@ -180,6 +206,12 @@ def select_by_importance(score, threshold=None, keep=None):
 
 
 class GaussianFit:
+    # what a fit of another footprint (SurfelFit) replaces: the scales per splat, the three entry points that read them or the
+    # record, and the kind of depth its render() returns
+    SCALES = 3
+    _ACCUMULATE, _PLAN, _GEOMETRY = "splat_density_accumulate", "splat_densify_plan", "splat_densify_geometry"
+    _DEPTH_KIND = "distance"
+
     def __init__(self, means, scales, rotations, opacity, sh, degree=None, lr=None, betas=(0.9, 0.999), eps=1e-15, sparse=True,
                  device="cuda", exact_activations=False, deterministic=False, antialiased=False, absgrad=False):
         """means (n, 3), scales (n, 3) > 0, rotations (n, 4), opacity (n,) in (0, 1), sh (n, K, 3) or (n, 3 K), K = (degree +
@@ -199,8 +231,8 @@ class GaussianFit:
         self.degree = {1: 0, 4: 1, 9: 2, 16: 3}.get(k) if degree is None else int(degree)
         if self.degree is None or sh.shape[1] != 3 * (self.degree + 1) ** 2:
             raise SplatError(-1, f"sh must hold 3 (degree + 1)^2 floats per splat, degree 0-3, not {sh.shape[1]}")
-        if means.shape != (n, 3) or scales.shape != (n, 3) or rotations.shape != (n, 4) or opacity.shape != (n,):
-            raise SplatError(-1, "means (n, 3), scales (n, 3), rotations (n, 4) and opacity (n,) are expected")
+        if means.shape != (n, 3) or scales.shape != (n, self.SCALES) or rotations.shape != (n, 4) or opacity.shape != (n,):
+            raise SplatError(-1, f"means (n, 3), scales (n, {self.SCALES}), rotations (n, 4) and opacity (n,) are expected")
         self.lr = dict(DEFAULT_LR, **(lr or {}))
         self.betas, self.eps, self.sparse = (float(betas[0]), float(betas[1])), float(eps), bool(sparse)
         self.exact_activations = bool(exact_activations)
@@ -229,6 +261,18 @@ class GaussianFit:
         distance to the three nearest neighbours (autograd.knn_mean_sq_distance); rotations (1, 0, 0, 0); the given opacity;
         sh[:, 0] = (rgb - 0.5) / 0.28209479177387814 and the higher coefficients zero.  **kw goes to GaussianFit.  SplatError
         when a row of mean_sq is not finite: fewer than four usable points, or a point with a NaN or infinite coordinate."""
+        return cls._from_points(points, colors, degree, opacity, min_sq_distance, cls._identity_rotations, kw)
+
+    @staticmethod
+    def _identity_rotations(n, device):
+        torch = AG._t()
+        rotations = torch.zeros((n, 4), device=device, dtype=torch.float32)
+        rotations[:, 0] = 1.0
+        return rotations
+
+    @classmethod
+    def _from_points(cls, points, colors, degree, opacity, min_sq_distance, make_rotations, kw):
+        """from_points for a fit of cls.SCALES scales per splat; make_rotations(n, device) gives the (n, 4) start."""
         torch = AG._t()
         device = kw.get("device", "cuda")
         t = lambda a: torch.as_tensor(a, dtype=torch.float32).to(device).detach()  # noqa: E731
@@ -243,9 +287,8 @@ class GaussianFit:
         if bad or n == 0:
             raise SplatError(-1, f"from_points: {bad} of {n} points have no three usable neighbours (fewer than four points, or "
                                  "NaN or infinite coordinates): no scale can be given to them")
-        scales = torch.sqrt(torch.clamp(mean_sq, min=float(min_sq_distance)))[:, None].repeat(1, 3)
-        rotations = torch.zeros((n, 4), device=points.device, dtype=torch.float32)
-        rotations[:, 0] = 1.0
+        scales = torch.sqrt(torch.clamp(mean_sq, min=float(min_sq_distance)))[:, None].repeat(1, cls.SCALES)
+        rotations = make_rotations(n, points.device)
         sh = torch.zeros((n, (int(degree) + 1) ** 2, 3), device=points.device, dtype=torch.float32)
         sh[:, 0] = ((colors.double() - 0.5) / 0.28209479177387814).float()  # (in float64, rounded once)
         return cls(points, scales, rotations, torch.full((n,), float(opacity), device=points.device, dtype=torch.float32), sh,
@@ -347,7 +390,7 @@ class GaussianFit:
         """One optimiser step after backward(): this frame's density statistics and visibility mask, five Adam launches, the
         gradients zeroed.  lr: a dict that overrides per-plane rates for this step (e.g. {"means": scheduled_rate})."""
         if self._frame is None or self._frame[0].grad is None:
-            raise SplatError(-5, "GaussianFit.step: call render() and backward() first")
+            raise SplatError(-5, f"{type(self).__name__}.step: call render() and backward() first")
         rec, width, height = self._frame
         n = self.n
         cx = AG._context(self.means)
@@ -361,8 +404,8 @@ class GaussianFit:
             self._aux = None
         else:
             grec = AG._cuda_f32(rec.grad, "grad_records", 8)
-            check(lib.splat_density_accumulate(cx.ctx, rec.data_ptr(), grec.data_ptr(), n, width, height, self.grad_accum.data_ptr(),
-                                               self.denom.data_ptr(), self.max_radius.data_ptr(), self.visible.data_ptr()), cx.ctx)
+            check(getattr(lib, self._ACCUMULATE)(cx.ctx, rec.data_ptr(), grec.data_ptr(), n, width, height, self.grad_accum.data_ptr(),
+                                                 self.denom.data_ptr(), self.max_radius.data_ptr(), self.visible.data_ptr()), cx.ctx)
         self.steps += 1
         rates = dict(self.lr, **(lr or {}))
         b1, b2 = self.betas
@@ -402,14 +445,14 @@ class GaussianFit:
         rows = torch.empty(max(2 * n, 1), device=dev, dtype=torch.int32)
         n_out, counts = C.c_uint32(), (C.c_uint32 * 4)()
         with torch.no_grad():
-            check(lib.splat_densify_plan(cx.ctx, self.log_scales.data_ptr(), self.opacity_logits.data_ptr(), self.grad_accum.data_ptr(),
-                                         self.denom.data_ptr(), self.max_radius.data_ptr(), n, C.byref(cfg), ws.data_ptr(), nbytes,
-                                         rows.data_ptr(), C.byref(n_out), counts), cx.ctx)
+            check(getattr(lib, self._PLAN)(cx.ctx, self.log_scales.data_ptr(), self.opacity_logits.data_ptr(), self.grad_accum.data_ptr(),
+                                           self.denom.data_ptr(), self.max_radius.data_ptr(), n, C.byref(cfg), ws.data_ptr(), nbytes,
+                                           rows.data_ptr(), C.byref(n_out), counts), cx.ctx)
             k = int(n_out.value)
             new = {name: torch.empty((k,) + tuple(getattr(self, name).shape[1:]), device=dev, dtype=torch.float32) for name in PLANES}
-            check(lib.splat_densify_geometry(cx.ctx, rows.data_ptr(), k, self.means.data_ptr(), self.log_scales.data_ptr(),
-                                             self.rotations.data_ptr(), C.byref(cfg), new["means"].data_ptr(), new["log_scales"].data_ptr()),
-                  cx.ctx)
+            check(getattr(lib, self._GEOMETRY)(cx.ctx, rows.data_ptr(), k, self.means.data_ptr(), self.log_scales.data_ptr(),
+                                               self.rotations.data_ptr(), C.byref(cfg), new["means"].data_ptr(),
+                                               new["log_scales"].data_ptr()), cx.ctx)
 
             def move(src, mode):
                 out = torch.empty((k,) + tuple(src.shape[1:]), device=dev, dtype=torch.float32)
@@ -657,7 +700,7 @@ class GaussianFit:
             for cam in cameras:
                 rgb, alpha, depth = self.render(cam, width, height, return_depth=True)[:3]
                 weight = torch.where(alpha >= alpha_min, alpha, torch.zeros_like(alpha))
-                vol.integrate(depth, cam, image=rgb if color else None, weight=weight)
+                vol.integrate(depth, cam, image=rgb if color else None, weight=weight, depth_kind=self._DEPTH_KIND)
             mesh = vol.extract_mesh()
         self._frame, self._aux = frame, aux
         return (*mesh, vol) if return_volume else mesh
@@ -680,3 +723,87 @@ class GaussianFit:
             return
         save_gaussian_ply(path, c(self.means), None, c(self.rotations), None, c(self.sh).reshape(self.n, -1, 3), log_scales=c(self.log_scales),
                           opacity_logits=c(self.opacity_logits))
+
+
+class SurfelFit(GaussianFit):
+    """GaussianFit for 2D Gaussian surfels (the module's docstring, "Fitting 2D Gaussian surfels"): log_scales is (n, 2), render()
+    is autograd.render_surfels, the density statistics, the plan and the split are the surfel entry points, the mesh is fused
+    from the intersection depth.  step(), the row moves, the moments and the opacity reset are GaussianFit's own code."""
+    SCALES = 2
+    _ACCUMULATE, _PLAN, _GEOMETRY = "splat_density_accumulate_surfel", "splat_densify_plan_surfel", "splat_densify_geometry_surfel"
+    _DEPTH_KIND = "z"
+
+    def __init__(self, means, scales, rotations, opacity, sh, degree=None, lr=None, betas=(0.9, 0.999), eps=1e-15, sparse=True,
+                 device="cuda", exact_activations=False, deterministic=False, antialiased=False, absgrad=False):
+        """GaussianFit's arguments with scales (n, 2) > 0, the standard deviations along the two tangent axes (columns 0 and 1 of
+        R(rotations); the normal is column 2).  deterministic, antialiased and absgrad are refused when true (SplatError)."""
+        for name, flag in (("deterministic", deterministic), ("antialiased", antialiased), ("absgrad", absgrad)):
+            if flag:
+                raise _not_built_for_surfels(f"SurfelFit({name}=True)")
+        super().__init__(means, scales, rotations, opacity, sh, degree=degree, lr=lr, betas=betas, eps=eps, sparse=sparse, device=device,
+                         exact_activations=exact_activations)
+
+    @classmethod
+    def from_points(cls, points, colors, degree=3, opacity=0.1, min_sq_distance=1e-7, rotation_seed=0, **kw):
+        """2DGS's initialisation: GaussianFit.from_points with the k-NN scale on both tangent axes, and the rotations 2DGS starts
+        from, rand((n, 4)): uniform in [0, 1), drawn on the host from a torch.Generator seeded with rotation_seed and uploaded,
+        so that a seed gives the same start on every machine."""
+        def random_rotations(n, device):
+            torch = AG._t()
+            gen = torch.Generator(device="cpu")
+            gen.manual_seed(int(rotation_seed))
+            return torch.rand((n, 4), generator=gen, dtype=torch.float32).to(device)
+        return cls._from_points(points, colors, degree, opacity, min_sq_distance, random_rotations, kw)
+
+    def render(self, camera_or_uniforms, width, height, return_depth=False, normals=False, distortion=None, features=None):
+        """autograd.render_surfels of the activated parameters (exp and sigmoid; in float64 rounded once with exact_activations;
+        no 3D filter): (rgb (H, W, 3), alpha (H, W)[, depth][, dist][, feat]).  return_depth: the ray-surfel intersection depth
+        map in clip w (depth_kind="z").  distortion=(near, far): 2DGS's depth-distortion map, after the depth it implies.
+        normals=True: the blended normal map (H, W, 3) last, features=autograd.surfel_normals(rotations, means, eye) with the eye
+        of the uniforms; a caller's own features are then refused (SplatError).  The frame's records are kept for step()."""
+        if normals and features is not None:
+            raise SplatError(-1, "SurfelFit.render: normals=True blends the surfels' normals as the frame's features; give features= "
+                                 "or normals=True, not both")
+        scales, opacity = self._activated()
+        if normals:
+            features = AG.surfel_normals(self.rotations, self.means, AG._uniforms(camera_or_uniforms, width, height)[16:19])
+        *out, rec = AG.render_surfels(camera_or_uniforms, self.means, scales, self.rotations, opacity, sh=self.sh, width=width, height=height,
+                                      degree=self.degree, return_depth=return_depth, features=features, distortion=distortion,
+                                      return_records=True)
+        if rec.requires_grad:
+            rec.retain_grad()
+        self._frame = (rec, int(width), int(height))
+        return tuple(out)
+
+    def densify_and_prune(self, grad_threshold=None, scale_threshold=None, min_opacity=0.05, max_screen_radius=0.0, max_world_scale=0.0,
+                          max_splats=0, seed=None):
+        """GaussianFit.densify_and_prune with the surfel plan and split (include/splat.h, splat_densify_plan_surfel,
+        splat_densify_geometry_surfel: the larger of two scales decides, and a split's children stay in the parent's plane);
+        min_opacity defaults to 2DGS's 0.05."""
+        return super().densify_and_prune(grad_threshold=grad_threshold, scale_threshold=scale_threshold, min_opacity=min_opacity,
+                                         max_screen_radius=max_screen_radius, max_world_scale=max_world_scale, max_splats=max_splats,
+                                         seed=seed)
+
+    def save_ply(self, path):
+        """The cloud as a 2D Gaussian splatting PLY file (ply.save_surfel_ply): the raw parameters, bit for bit."""
+        from .ply import save_surfel_ply
+        c = lambda t: t.detach().cpu().numpy()  # noqa: E731
+        save_surfel_ply(path, c(self.means), None, c(self.rotations), None, c(self.sh).reshape(self.n, -1, 3), log_scales=c(self.log_scales),
+                        opacity_logits=c(self.opacity_logits))
+
+
+def _not_built_for_surfels(who):
+    return SplatError(-1, f"{who}: not built for surfels")
+
+
+def _refusal(name):
+    def method(self, *args, **kw):
+        raise _not_built_for_surfels(f"SurfelFit.{name}")
+    method.__name__ = name
+    method.__doc__ = f"Not built for surfels: SplatError.  (GaussianFit.{name} projects its planes as ellipsoids.)"
+    return method
+
+
+for _name in ("update_filter_3d", "relocate", "add_new", "inject_noise", "accumulate_importance", "importance", "prune_by_importance"):
+    setattr(SurfelFit, _name, _refusal(_name))
+del _name

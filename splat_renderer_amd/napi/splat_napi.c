@@ -694,28 +694,29 @@ FN(adam_step) { /* (ctx, param, grad, m, v, rows, floatsPerRow, headFloats, step
     double eps = arg_number(&c, 13); void *vis = arg_dptr(&c, 14); BAIL;
     return check(env, x, splat_adam_step(x, p, g, m, v, rows, fpr, head, sh, st, b1, b2, bc, eps, vis), mk_undefined(env));
 }
-FN(density_accumulate) { /* (ctx, records, gradRecords, n, W, H, gradAccum, denom, maxRadius, visible) */
+typedef int (*density_accumulate_fn)(splat_ctx *, const void *, const void *, uint32_t, uint32_t, uint32_t, void *, void *, void *, void *);
+static napi_value density_accumulate_call(napi_env env, napi_callback_info info, density_accumulate_fn accumulate) {
     ARGS(10); splat_ctx *x = arg_external(&c, 0); void *rec = arg_dptr(&c, 1), *gr = arg_dptr(&c, 2);
     uint32_t n = (uint32_t)arg_number(&c, 3), w = (uint32_t)arg_number(&c, 4), h = (uint32_t)arg_number(&c, 5);
     void *ga = arg_dptr(&c, 6), *dn = arg_dptr(&c, 7), *mr = arg_dptr(&c, 8), *vis = arg_dptr(&c, 9); BAIL;
-    return check(env, x, splat_density_accumulate(x, rec, gr, n, w, h, ga, dn, mr, vis), mk_undefined(env));
+    return check(env, x, accumulate(x, rec, gr, n, w, h, ga, dn, mr, vis), mk_undefined(env));
 }
-FN(density_accumulate_abs) { /* (ctx, records, gradCenterAbs, n, W, H, gradAccum, denom, maxRadius, visible) */
-    ARGS(10); splat_ctx *x = arg_external(&c, 0); void *rec = arg_dptr(&c, 1), *gr = arg_dptr(&c, 2);
-    uint32_t n = (uint32_t)arg_number(&c, 3), w = (uint32_t)arg_number(&c, 4), h = (uint32_t)arg_number(&c, 5);
-    void *ga = arg_dptr(&c, 6), *dn = arg_dptr(&c, 7), *mr = arg_dptr(&c, 8), *vis = arg_dptr(&c, 9); BAIL;
-    return check(env, x, splat_density_accumulate_abs(x, rec, gr, n, w, h, ga, dn, mr, vis), mk_undefined(env));
-}
+/* (ctx, records, gradRecords, n, W, H, gradAccum, denom, maxRadius, visible); _abs: gradCenterAbs (n x 2) for gradRecords; _surfel: surfel records */
+FN(density_accumulate) { return density_accumulate_call(env, info, splat_density_accumulate); }
+FN(density_accumulate_abs) { return density_accumulate_call(env, info, splat_density_accumulate_abs); }
+FN(density_accumulate_surfel) { return density_accumulate_call(env, info, splat_density_accumulate_surfel); }
 FN(densify_plan_workspace_bytes) { /* (n) -> bytes */
     ARGS(1); uint32_t n = (uint32_t)arg_number(&c, 0); BAIL;
     return mk_number(env, (double)splat_densify_plan_workspace_bytes(n));
 }
-FN(densify_plan) { /* (ctx, logScales, opacityLogits, gradAccum, denom, maxRadius, n, cfg[7], workspace, workspaceBytes, rows) -> [nOut, pruned, kept, cloned, split] (waits) */
+typedef int (*densify_plan_fn)(splat_ctx *, const void *, const void *, const void *, const void *, const void *, uint32_t,
+                               const splat_densify_cfg *, void *, uint64_t, void *, uint32_t *, uint32_t *);
+static napi_value densify_plan_call(napi_env env, napi_callback_info info, densify_plan_fn plan) {
     ARGS(11); splat_ctx *x = arg_external(&c, 0); void *ls = arg_dptr(&c, 1), *ol = arg_dptr(&c, 2), *ga = arg_dptr(&c, 3), *dn = arg_dptr(&c, 4);
     void *mr = arg_dptr(&c, 5); uint32_t n = (uint32_t)arg_number(&c, 6); splat_densify_cfg cfg; fill_densify_cfg(&c, 7, &cfg);
     void *ws = arg_dptr(&c, 8); uint64_t wb = (uint64_t)arg_number(&c, 9); void *rows = arg_dptr(&c, 10); BAIL;
     uint32_t n_out = 0, counts[4] = {0, 0, 0, 0};
-    int rc = splat_densify_plan(x, ls, ol, ga, dn, mr, n, &cfg, ws, wb, rows, &n_out, counts);
+    int rc = plan(x, ls, ol, ga, dn, mr, n, &cfg, ws, wb, rows, &n_out, counts);
     if (rc != SPLAT_OK) return check(env, x, rc, NULL);
     napi_value arr;
     if (napi_create_array_with_length(env, 5, &arr) != napi_ok) return NULL;
@@ -723,12 +724,20 @@ FN(densify_plan) { /* (ctx, logScales, opacityLogits, gradAccum, denom, maxRadiu
     for (uint32_t k = 0; k < 4; ++k) napi_set_element(env, arr, k + 1, mk_number(env, counts[k]));
     return arr;
 }
-FN(densify_geometry) { /* (ctx, rows, nOut, means, logScales, rotations, cfg[7], meansOut, logScalesOut) */
+/* (ctx, logScales, opacityLogits, gradAccum, denom, maxRadius, n, cfg[7], workspace, workspaceBytes, rows) -> [nOut, pruned, kept, cloned, split] (waits) */
+FN(densify_plan) { return densify_plan_call(env, info, splat_densify_plan); }
+FN(densify_plan_surfel) { return densify_plan_call(env, info, splat_densify_plan_surfel); } /* logScales: n x 2 */
+typedef int (*densify_geometry_fn)(splat_ctx *, const void *, uint32_t, const void *, const void *, const void *, const splat_densify_cfg *,
+                                   void *, void *);
+static napi_value densify_geometry_call(napi_env env, napi_callback_info info, densify_geometry_fn geometry) {
     ARGS(9); splat_ctx *x = arg_external(&c, 0); void *rows = arg_dptr(&c, 1); uint32_t n = (uint32_t)arg_number(&c, 2);
     void *mu = arg_dptr(&c, 3), *ls = arg_dptr(&c, 4), *rot = arg_dptr(&c, 5); splat_densify_cfg cfg; fill_densify_cfg(&c, 6, &cfg);
     void *mo = arg_dptr(&c, 7), *lo = arg_dptr(&c, 8); BAIL;
-    return check(env, x, splat_densify_geometry(x, rows, n, mu, ls, rot, &cfg, mo, lo), mk_undefined(env));
+    return check(env, x, geometry(x, rows, n, mu, ls, rot, &cfg, mo, lo), mk_undefined(env));
 }
+/* (ctx, rows, nOut, means, logScales, rotations, cfg[7], meansOut, logScalesOut); _surfel: logScales n x 2, logScalesOut nOut x 2 */
+FN(densify_geometry) { return densify_geometry_call(env, info, splat_densify_geometry); }
+FN(densify_geometry_surfel) { return densify_geometry_call(env, info, splat_densify_geometry_surfel); }
 FN(densify_rows) { /* (ctx, rows, nOut, in, out, floatsPerRow, mode: 0 copy, 1 zero the new rows) */
     ARGS(7); splat_ctx *x = arg_external(&c, 0); void *rows = arg_dptr(&c, 1); uint32_t n = (uint32_t)arg_number(&c, 2);
     void *in = arg_dptr(&c, 3), *out = arg_dptr(&c, 4); uint32_t fpr = (uint32_t)arg_number(&c, 5), mode = (uint32_t)arg_number(&c, 6); BAIL;
@@ -1076,7 +1085,7 @@ static napi_value init(napi_env env, napi_value exports) {
         EXPORT(knn_workspace_bytes), EXPORT(knn_mean_sq),
         EXPORT(project_ellipsoid_aa), EXPORT(render_frame_ellipsoids_aa), EXPORT(project_ellipsoid_backward_aa), EXPORT(sampling_rate_max),
         EXPORT(composite_backward_abs), EXPORT(composite_backward_det_abs_workspace_bytes), EXPORT(composite_backward_det_abs),
-        EXPORT(density_accumulate_abs),
+        EXPORT(density_accumulate_abs), EXPORT(density_accumulate_surfel), EXPORT(densify_plan_surfel), EXPORT(densify_geometry_surfel),
         EXPORT(composite_features), EXPORT(composite_features_backward),
         EXPORT(project_surfel), EXPORT(composite_surfel_depth), EXPORT(composite_surfel_distortion), EXPORT(composite_backward_distortion),
         EXPORT(project_surfel_backward),

@@ -12,6 +12,9 @@ load_point_ply reads what a fit starts from instead: a coloured point cloud, x y
 save_gaussian_ply is its exact inverse: the same file 3D Gaussian splatting writes (x y z, zero nx ny nz, f_dc, channel-major
 f_rest, opacity as a logit, log scales, rot), from the arrays load_gaussian_ply returns.
 
+load_surfel_ply and save_surfel_ply are the same pair for 2D Gaussian surfels (2DGS's files; SurfelFit.save_ply): the same
+properties in the same order with scale_0 and scale_1 only.  Each loader refuses the other's file.
+
 save_mesh_ply writes a triangle mesh (TsdfVolume.extract_mesh's, GaussianFit.extract_mesh's): vertex and face elements, uchar colours.
 """
 import numpy as np
@@ -107,22 +110,39 @@ def load_point_ply(path):
     return xyz, rgb
 
 
+def _bad_surfels(path, why):
+    return SplatError(-1, f"{path}: not a 2D Gaussian splatting PLY file: {why}")
+
+
 def load_gaussian_ply(path):
     """Returns a dict of float32 arrays: positions (n, 3), scales (n, 3), rotations (n, 4) as (w, x, y, z), opacity (n,),
     sh (n, (degree + 1)^2, 3), and the int degree.  Pass them to GaussianCloud.fromArrays(device, positions, scales,
     rotations, opacity=opacity, sh=sh)."""
+    return _load_splat_ply(path, 3, _bad)
+
+
+def load_surfel_ply(path):
+    """A 2D Gaussian splatting file (2DGS's layout: 3DGS's with scale_0 and scale_1 only): load_gaussian_ply's dict with scales
+    (n, 2), the standard deviations along the surfel's two tangent axes, as autograd.render_surfels and SurfelFit take them.  A
+    file with a scale_2 property is a 3D Gaussian splatting file and is refused: load_gaussian_ply reads it."""
+    return _load_splat_ply(path, 2, _bad_surfels)
+
+
+def _load_splat_ply(path, n_scales, bad):
+    scale_keys = [f"scale_{j}" for j in range(n_scales)]
     with open(path, "rb") as f:
-        n, props = _read_vertex_header(f, path, _bad)
+        n, props = _read_vertex_header(f, path, bad)
         names = [p[0] for p in props]
-        need = ["x", "y", "z", "f_dc_0", "f_dc_1", "f_dc_2", "opacity", "scale_0", "scale_1", "scale_2",
-                "rot_0", "rot_1", "rot_2", "rot_3"]
+        need = ["x", "y", "z", "f_dc_0", "f_dc_1", "f_dc_2", "opacity"] + scale_keys + ["rot_0", "rot_1", "rot_2", "rot_3"]
         missing = [k for k in need if k not in names]
         if missing:
-            raise _bad(path, f"missing properties {missing}")
+            raise bad(path, f"missing properties {missing}")
+        if n_scales == 2 and "scale_2" in names:
+            raise bad(path, "it has a scale_2 property: a 3D Gaussian splatting file, which load_gaussian_ply reads")
         rest = sorted((k for k in names if k.startswith("f_rest_")), key=lambda k: int(k[len("f_rest_"):]))
         if len(rest) not in _REST_TO_DEGREE or rest != [f"f_rest_{j}" for j in range(len(rest))]:
-            raise _bad(path, f"{len(rest)} f_rest properties; 0, 9, 24 or 45 (f_rest_0 ... in order) are expected")
-        v = _read_vertices(f, path, _bad, n, props)
+            raise bad(path, f"{len(rest)} f_rest properties; 0, 9, 24 or 45 (f_rest_0 ... in order) are expected")
+        v = _read_vertices(f, path, bad, n, props)
 
     def cols(keys):
         return np.stack([v[k].astype(np.float32) for k in keys], axis=1) if keys else np.zeros((n, 0), np.float32)
@@ -137,7 +157,7 @@ def load_gaussian_ply(path):
     return {
         "positions": cols(["x", "y", "z"]),
         # (both activations in float64, rounded once: the same arrays on every host, whatever its NumPy's float32 exp)
-        "scales": np.exp(cols(["scale_0", "scale_1", "scale_2"]).astype(np.float64)).astype(np.float32),
+        "scales": np.exp(cols(scale_keys).astype(np.float64)).astype(np.float32),
         "rotations": cols(["rot_0", "rot_1", "rot_2", "rot_3"]),
         "opacity": (1.0 / (1.0 + np.exp(-op.astype(np.float64)))).astype(np.float32),
         "sh": sh,
@@ -187,6 +207,17 @@ def save_gaussian_ply(path, positions, scales, rotations, opacity, sh, log_scale
     basis-major.  The file stores log(scales) and logit(opacity), formed in float64 and rounded once.  A caller that holds the
     raw parameters passes them as log_scales / opacity_logits (scales / opacity may then be None): they are stored as they are,
     bit for bit.  Positions, rotations and SH are stored bit for bit."""
+    _save_splat_ply("save_gaussian_ply", 3, path, positions, scales, rotations, opacity, sh, log_scales, opacity_logits)
+
+
+def save_surfel_ply(path, positions, scales, rotations, opacity, sh, log_scales=None, opacity_logits=None):
+    """Writes 2D Gaussian surfels as 2DGS does: save_gaussian_ply's properties in its order with scale_0 and scale_1 only;
+    load_surfel_ply's inverse.  scales (n, 2) > 0; everything else, the raw planes (log_scales (n, 2)) included, as
+    save_gaussian_ply takes it."""
+    _save_splat_ply("save_surfel_ply", 2, path, positions, scales, rotations, opacity, sh, log_scales, opacity_logits)
+
+
+def _save_splat_ply(who, n_scales, path, positions, scales, rotations, opacity, sh, log_scales, opacity_logits):
     pos = np.asarray(positions, np.float32)
     n = pos.shape[0]
     rot = np.asarray(rotations, np.float32)
@@ -194,7 +225,7 @@ def save_gaussian_ply(path, positions, scales, rotations, opacity, sh, log_scale
     nb = coef.shape[1]
     degree = {1: 0, 4: 1, 9: 2, 16: 3}.get(nb)
     if degree is None:
-        raise SplatError(-1, f"save_gaussian_ply: sh must hold 3 (degree + 1)^2 floats per splat, degree 0-3, not {3 * nb}")
+        raise SplatError(-1, f"{who}: sh must hold 3 (degree + 1)^2 floats per splat, degree 0-3, not {3 * nb}")
     with np.errstate(all="ignore"):
         ls = (np.asarray(log_scales, np.float32) if log_scales is not None
               else np.log(np.asarray(scales, np.float32).astype(np.float64)).astype(np.float32))
@@ -203,11 +234,11 @@ def save_gaussian_ply(path, positions, scales, rotations, opacity, sh, log_scale
         else:
             o = np.asarray(opacity, np.float32).reshape(-1).astype(np.float64)
             ol = (np.log(o) - np.log1p(-o)).astype(np.float32)
-    if pos.shape != (n, 3) or ls.shape != (n, 3) or rot.shape != (n, 4) or ol.shape != (n,):
-        raise SplatError(-1, "save_gaussian_ply: positions (n, 3), scales (n, 3), rotations (n, 4) and opacity (n,) are expected")
+    if pos.shape != (n, 3) or ls.shape != (n, n_scales) or rot.shape != (n, 4) or ol.shape != (n,):
+        raise SplatError(-1, f"{who}: positions (n, 3), scales (n, {n_scales}), rotations (n, 4) and opacity (n,) are expected")
     rest = coef[:, 1:, :].transpose(0, 2, 1).reshape(n, 3 * (nb - 1))  # channel-major: f_rest_{c (nb - 1) + (k - 1)}
     names = (["x", "y", "z", "nx", "ny", "nz", "f_dc_0", "f_dc_1", "f_dc_2"] + [f"f_rest_{j}" for j in range(rest.shape[1])]
-             + ["opacity", "scale_0", "scale_1", "scale_2", "rot_0", "rot_1", "rot_2", "rot_3"])
+             + ["opacity"] + [f"scale_{j}" for j in range(n_scales)] + ["rot_0", "rot_1", "rot_2", "rot_3"])
     table = np.concatenate([pos, np.zeros((n, 3), np.float32), coef[:, 0, :], rest, ol[:, None], ls, rot], axis=1).astype("<f4")
     header = "ply\nformat binary_little_endian 1.0\n" + f"element vertex {n}\n" + "".join(f"property float {k}\n" for k in names) + "end_header\n"
     with open(path, "wb") as f:

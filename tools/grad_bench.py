@@ -96,6 +96,13 @@ same planes timed in the same rounds, the line's measured copy ceiling), splat_m
 synchronises) and splat_mcmc_apply of that sample, on logits drawn N(-1, 2.5), 4 % of them below min_opacity = 0.005 (the bench
 scene itself is opaque).
 
+--surfel --optimizer measures the three surfel entry points of density control instead (one JSON line per config, nothing of the
+above): a GaussianFit and a SurfelFit of the same cloud (the surfel takes the first two scales) each render one frame and take its
+backward, and then splat_density_accumulate_surfel, splat_densify_plan_surfel (host clock: it synchronises) and
+splat_densify_geometry_surfel run beside their ellipsoid peers on the same n, alternating in the same rounds, as do the two
+fits' whole step() (the statistics and the five Adam launches on the frame's gradients, restored before every call) and each of
+its five masked splat_adam_step launches alone (adam_<plane>_<kind>: which plane a difference between the two steps comes from).
+
 --normal-loss measures the normal-consistency term instead (one JSON line per config, nothing of the above), on the frame's own
 depth map, blended normal map (render_gaussians(return_depth=True, features=splat_normals(...)): a packed (H, W, 3) image) and
 alpha as the weight: splat_normal_consistency (both launches) and splat_normal_consistency_backward alone (fused_normal_forward,
@@ -559,6 +566,111 @@ def optimizer_bench(name, k, rounds, stream):
                       "plan_counts": {"pruned": counts[0], "kept": counts[1], "cloned": counts[2], "split": counts[3], "rows": kout}}), flush=True)
 
 
+def surfel_optimizer_bench(name, k, rounds, stream):
+    import time
+    from splat_renderer_amd.fit import PLANES, GaussianFit, SurfelFit
+    n, w, h = sr.scene.CONFIGS[name]
+    props, _ = sr.scene.make_scene(n)
+    rng = np.random.default_rng(0)
+    scl = (props[:, 3:4] * 0.5 * np.exp(rng.uniform(-0.3, 0.3, (n, 3)))).astype(np.float32)
+    rot = rng.normal(size=(n, 4)).astype(np.float32)
+    sh = rng.normal(0, 0.3, (n, 16, 3)).astype(np.float32)
+    cam = sr.Camera()
+    cam.setAspect(w / h)
+    u = cam.uniforms(w, h)
+    opacity = np.clip(props[:, 7], 1e-4, 1 - 1e-4)
+    target = torch.rand((h, w, 3), device="cuda")
+    fits = {"ellipsoid": GaussianFit(props[:, :3], scl, rot, opacity, sh), "surfel": SurfelFit(props[:, :3], scl[:, :2], rot, opacity, sh)}
+    entry = {"ellipsoid": ("splat_density_accumulate", "splat_densify_plan", "splat_densify_geometry"),
+             "surfel": ("splat_density_accumulate_surfel", "splat_densify_plan_surfel", "splat_densify_geometry_surfel")}
+    cx = AG._context(fits["ellipsoid"].means)
+    lib = cx.lib
+    work, host, info = {}, {}, {}
+    for kind, fit in fits.items():
+        rgb, _ = fit.render(u, w, h)
+        AG.photometric_loss(rgb, target).backward()
+        frame = fit._frame
+        rec = frame[0]
+        grec = rec.grad.contiguous()
+        grads = {p: getattr(fit, p).grad.contiguous() for p in PLANES}
+        ga, dn, mr = (torch.zeros(n, device="cuda") for _ in range(3))
+        vis = torch.zeros(n, device="cuda", dtype=torch.uint8)
+        acc_fn, plan_fn, geo_fn = (getattr(lib, e) for e in entry[kind])
+
+        def accumulate(acc_fn=acc_fn, rec=rec, grec=grec, ga=ga, dn=dn, mr=mr, vis=vis):
+            _lib.check(acc_fn(cx.ctx, rec.data_ptr(), grec.data_ptr(), n, w, h, ga.data_ptr(), dn.data_ptr(), mr.data_ptr(), vis.data_ptr()), cx.ctx)
+        accumulate()
+        cfg = _lib.DensifyCfg(2e-4, 0.01 * fit.extent, 0.005, 0.0, 0.0, 0, 1)
+        nbytes = int(lib.splat_densify_plan_workspace_bytes(n))
+        ws = torch.empty(nbytes // 4, device="cuda", dtype=torch.int32)
+        rows = torch.empty(2 * n, device="cuda", dtype=torch.int32)
+        n_out, counts = C.c_uint32(), (C.c_uint32 * 4)()
+
+        def plan(plan_fn=plan_fn, fit=fit, ga=ga, dn=dn, mr=mr, cfg=cfg, ws=ws, nbytes=nbytes, rows=rows, n_out=n_out, counts=counts):
+            _lib.check(plan_fn(cx.ctx, fit.log_scales.data_ptr(), fit.opacity_logits.data_ptr(), ga.data_ptr(), dn.data_ptr(), mr.data_ptr(), n,
+                               C.byref(cfg), ws.data_ptr(), nbytes, rows.data_ptr(), C.byref(n_out), counts), cx.ctx)
+        plan()
+        kout = int(n_out.value)
+        mu_out = torch.empty((kout, 3), device="cuda")
+        ls_out = torch.empty((kout, fit.SCALES), device="cuda")
+
+        def geometry(geo_fn=geo_fn, fit=fit, rows=rows, kout=kout, cfg=cfg, mu_out=mu_out, ls_out=ls_out):
+            _lib.check(geo_fn(cx.ctx, rows.data_ptr(), kout, fit.means.data_ptr(), fit.log_scales.data_ptr(), fit.rotations.data_ptr(),
+                              C.byref(cfg), mu_out.data_ptr(), ls_out.data_ptr()), cx.ctx)
+
+        def step(fit=fit, frame=frame, grads=grads):  # (the frame and its gradients put back: step() consumes them)
+            fit._frame = frame
+            for p in PLANES:
+                getattr(fit, p).grad = grads[p]
+            fit.step()
+        work.update({f"accumulate_{kind}": accumulate, f"geometry_{kind}": geometry, f"step_{kind}": step})
+
+        def adam(p, fit=fit, grads=grads, vis=vis):  # (one plane of the step, masked by the frame's visibility, at a fixed step count)
+            x = getattr(fit, p)
+            fpr = x.shape[1] if x.dim() == 2 else 1
+            _lib.check(lib.splat_adam_step(cx.ctx, x.data_ptr(), grads[p].data_ptr(), fit.m[p].data_ptr(), fit.v[p].data_ptr(), n, fpr,
+                                           3 if p == "sh" else fpr, fit.lr[p] / 0.1, fit.lr["sh_rest" if p == "sh" else p] / 0.1, 0.9, 0.999,
+                                           1.0 / 0.001 ** 0.5, 1e-15, vis.data_ptr()), cx.ctx)
+        for p in PLANES:
+            work[f"adam_{p}_{kind}"] = lambda p=p, adam=adam: adam(p)
+        host[f"plan_{kind}"] = plan
+        info[kind] = {"visible_fraction": round(float(vis.float().mean()), 4), "rows": kout,
+                      "plan_counts": {"pruned": counts[0], "kept": counts[1], "cloned": counts[2], "split": counts[3]}}
+
+    def run(fn, calls):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(calls):
+            fn()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / calls
+
+    def run_host(fn, calls):  # (it synchronises: a host clock, the stream idle before and after)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(calls):
+            fn()
+        return (time.perf_counter() - t0) * 1e3 / calls
+
+    for fn in list(work.values()) * 2:
+        run(fn, 3)
+    for fn in host.values():
+        run_host(fn, 3)
+    ts = {kind: [] for kind in list(work) + list(host)}
+    for _ in range(rounds):
+        for kind, fn in work.items():
+            ts[kind].append(run(fn, k))
+        for kind, fn in host.items():
+            ts[kind].append(run_host(fn, max(k // 4, 1)))
+    med = {kind: sorted(x)[len(x) // 2] for kind, x in ts.items()}
+    print(json.dumps({"config": name, "n": n, "width": w, "height": h, "calls_per_round": k, "rounds": rounds, **info,
+                      **{f"{kind}_us": round(x * 1e3, 2) for kind, x in med.items()},
+                      **{f"{kind}_us_min_max": [round(min(x) * 1e3, 2), round(max(x) * 1e3, 2)] for kind, x in ts.items()},
+                      **{f"{what}_surfel_over_ellipsoid": round(med[f"{what}_surfel"] / med[f"{what}_ellipsoid"], 3)
+                         for what in ("accumulate", "plan", "geometry", "step")}}), flush=True)
+
+
 def torch_records(U, pos, scl, rot, W, H):
     """The records {c.x, c.y, B00, B01, B11} (n, 5) as plain float32 torch ops of the uniform block U (include/splat.h; no cull)."""
     q = rot / torch.sqrt((rot * rot).sum(dim=1, keepdim=True))
@@ -595,7 +707,7 @@ if normal_loss_only:
     names = []
 if optimizer_only:
     for name in names:
-        optimizer_bench(name, k, rounds, stream)
+        (surfel_optimizer_bench if surfel_too else optimizer_bench)(name, k, rounds, stream)
     names = []
 for name in names:
     n, w, h = sr.scene.CONFIGS[name]
